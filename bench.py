@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the landmark hot path on MI355X.
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W [--config 4]
 
@@ -10,9 +10,9 @@ One step = one pass of the hot path over one batch of synthetic 256x256 uint8 BG
     decode) -> similarity fit + alignment warp to 256x256 -> (N > 1) RCCL all-gather of the landmark tensors.
 
 --config 2 (default)  BASELINE.json configs[1]: 64 faces per GPU, fp32 -- the headline (`value`, dtype "f32").
-                      At N = 1 the line also carries: cpu_baseline, parity, the bf16 configs[2] run with its own roofline
-                      block, and HBM-bound kernel entries.  At N > 1 it also carries `config4` (below) as a side object,
-                      so one driver run per N measures both.
+                      With --full, at N = 1 the line also carries: cpu_baseline, parity, the bf16 configs[2] run with its
+                      own roofline block, the fp32 batch-512 run and HBM-bound kernel entries.  At N > 1 it also carries
+                      `config4` (below) as a side object, so one driver run per N measures both.
 --config 3            BASELINE.json configs[2]: 512 faces, bf16 operands / fp32 accumulate, one GPU, as the headline.
 --config 4            BASELINE.json configs[3]: 512 bf16 faces per GPU (4096 at 8) + all-gather, as the headline.
 --config 5            BASELINE.json configs[4]: 1080p multi-face stream -- per GPU 64 synthetic 1920x1080 frames with 1..16
@@ -20,6 +20,16 @@ One step = one pass of the hot path over one batch of synthetic 256x256 uint8 BG
                       16 frames per launch sequence; one step = one pass over a rank's frames; frames are independent, no
                       collective.  `value` is faces/s, `frames_per_s` rides along.
 Ranks are weak-scaled: every rank runs its own batch; the only collective is the landmark gather.  ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line: `value` (faces/s), `ms_per_step` and what describes
+the run.  --full adds everything else it measures or checks, each outside the headline's timed region: the headline's
+roofline block (HIP events around the roofline kernel inside the timed region) and per-layer pass, the all-gather timed
+alone, and with --config 2 the side objects above.
+--dump-outputs DIR    after the timed steps, rank 0 writes what the last timed step returned as DIR/<name>.npy (float64 /
+                      float32): `landmarks` [B, 68, 2] (all ranks' at N > 1), `aligned` [B, 256, 256, 3] and `align_m`
+                      [B, 2, 3] (--config 5: the last launch sequence's `landmarks`).  At most 64 MB in all: an array that
+                      does not fit keeps a fixed seeded sample of its faces, listed in `<name>_sample_index.npy`.  Inputs
+                      and weights are seeded: the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -295,7 +305,7 @@ class Workload:
             lm = self.model.forward_device(self.crops, "landmarks", n_points=self.n_points, thresh=0.0)
             aligned = None
             if self.align:
-                aligned, _m = alignment.align_device(self.crops, lm, self.tmpl, self.H, self.W, self.scale)
+                aligned = alignment.align_device(self.crops, lm, self.tmpl, self.H, self.W, self.scale)   # (crops, M)
             return lm, aligned
         return pipeline_gather(produce, world, total)
 
@@ -345,16 +355,20 @@ class StreamWorkload:
         return step
 
 
-def measure(lib, wl, steps, warmup, world, roof_layer, settle_s):
+def measure(lib, wl, steps, warmup, world, roof_layer, settle_s, profile=True):
     """Timed region of one workload with the roofline kernel's launches bracketed by HIP events on the launch stream,
-    then the per-layer pass.  Returns (seconds, roofline-layer ms, {layer: ms})."""
+    then the per-layer pass.  Returns (seconds, roofline-layer ms, {layer: ms}, per-rank ms, the last timed step's
+    result).  profile=False (a plain run): the timed region alone, no events and no per-layer pass (None, None)."""
     import torch
     from flm_amd import _lib
     step = wl.make_step(world, wl.batch * world)
+    if not profile:
+        dt, out, per_rank = timed_region(step, steps, warmup, world, wl.dev, settle_s)
+        return dt, None, None, per_rank, out
     _lib.check(lib.flm_profile_enable(max(steps, LAYER_PASS_STEPS) * RECORDS_PER_STEP + 64), "flm_profile_enable")
     _lib.check(lib.flm_profile_filter(roof_layer.encode()), "flm_profile_filter")
 
-    dt, _, per_rank = timed_region(step, steps, warmup, world, wl.dev, settle_s, before_timed=lib.flm_profile_reset)
+    dt, out, per_rank = timed_region(step, steps, warmup, world, wl.dev, settle_s, before_timed=lib.flm_profile_reset)
     roof_ms = read_profile(lib).get(roof_layer, float("nan"))
     _lib.check(lib.flm_profile_filter(None), "flm_profile_filter")
     lib.flm_profile_reset()
@@ -365,7 +379,7 @@ def measure(lib, wl, steps, warmup, world, roof_layer, settle_s):
     torch.cuda.synchronize()
     layers = read_profile(lib)
     lib.flm_profile_disable()
-    return dt, roof_ms, layers, per_rank
+    return dt, roof_ms, layers, per_rank, out
 
 
 def forward_summary(layers, batch, peak):
@@ -448,6 +462,43 @@ def hbm_kernels(lib, dev, only=None):
     return out
 
 
+# ---- --dump-outputs ------------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 64 * 10 ** 6   # every file written, .npy headers included
+NPY_HEADER_BYTES = 128
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """{name: array} -> out_dir/<name>.npy: float64 stays float64, every other dtype becomes float32.  Smallest arrays
+    first, each whole while it fits; one that does not keeps a sorted sample of rows of its leading axis (the faces) drawn
+    with a fixed seed -- the same rows in every run -- and lists them in <name>_sample_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    left = budget
+    for name in sorted(arrays, key=lambda k: (arrays[k].nbytes, k)):
+        a = arrays[name]
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes + NPY_HEADER_BYTES > left:
+            row = a.nbytes // max(1, a.shape[0])
+            keep = max(0, (left - 2 * NPY_HEADER_BYTES) // (row + 8))
+            idx = np.sort(np.random.default_rng(seed).choice(a.shape[0], min(keep, a.shape[0]), replace=False))
+            np.save(os.path.join(out_dir, name + "_sample_index.npy"), idx.astype(np.float64))
+            left -= 8 * len(idx) + NPY_HEADER_BYTES
+            a = a[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes + NPY_HEADER_BYTES
+
+
+def step_arrays(out):
+    """What the last timed step returned, as host arrays: (landmarks, (aligned, M) or None) of Workload, (landmarks,
+    None) of StreamWorkload."""
+    lm, aux = out
+    arrays = {"landmarks": lm.cpu().numpy()}
+    if aux is not None:
+        arrays["aligned"] = aux[0].cpu().numpy()
+        arrays["align_m"] = aux[1].cpu().numpy()
+    return arrays
+
+
 # ---- CPU baseline --------------------------------------------------------------------------------------------------
 def usable_cores():
     """CPUs this process may really use: the affinity mask, cut by a cgroup CPU quota if one is set (the GPU box hands a
@@ -524,7 +575,7 @@ def bf16_side_object(lib, args, world, rank, tag):
     """BASELINE configs[2] (N = 1) / configs[3] (N > 1): 512 bf16 faces per rank, same step, own timed region."""
     wl = Workload("bf16", args.bf16_batch, rank, args.n_points, not args.no_align, seed=3)
     steps = max(5, args.steps)
-    dt, up3_ms, layers, per_rank = measure(lib, wl, steps, max(2, args.warmup), world, "up3", args.settle_ms / 1e3)
+    dt, up3_ms, layers, per_rank, _ = measure(lib, wl, steps, max(2, args.warmup), world, "up3", args.settle_ms / 1e3)
     total = wl.batch * world
     fwd = forward_summary(layers, wl.batch, PEAK_BF16_TFLOPS)
     obj = {"workload": "%s: %d faces per GPU x %d GPU(s), 256x256 crops, bf16 operands / fp32 accumulate, same step as "
@@ -543,7 +594,9 @@ def stream_config(lib, args, rank, world, dev):
     sequence; the kernels are the ones the other configurations price)."""
     wl = StreamWorkload(args.stream_dtype, rank, args.n_points, group=args.stream_group)
     step = wl.make_step(world, 0)
-    dt, _, per_rank = timed_region(step, args.steps, args.warmup, world, dev, args.settle_ms / 1e3)
+    dt, out, per_rank = timed_region(step, args.steps, args.warmup, world, dev, args.settle_ms / 1e3)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_arrays(out))
     import torch
     import torch.distributed as dist
     faces = torch.tensor([wl.batch], dtype=torch.int64, device=dev)
@@ -557,7 +610,7 @@ def stream_config(lib, args, rank, world, dev):
                       "(top-%d) + similarity/alignment warp" % args.n_points,
             "value": total * args.steps / dt, "unit": "faces/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": args.stream_dtype, "data": "synthetic", "per_rank_ms_per_step": per_rank,
+            "dtype": args.stream_dtype, "data": "synthetic", "full": args.full, "per_rank_ms_per_step": per_rank,
             "frames_per_s": wl.n_frames * world * args.steps / dt,
             "config": {"workload": "BASELINE configs[4]: per GPU %d synthetic 1920x1080x3 uint8 frames resident in HBM, 1..16 "
                                    "boxes each (sides 96..400 px, %d faces on rank 0), %d frames per launch sequence, "
@@ -572,25 +625,30 @@ def stream_config(lib, args, rank, world, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline and per-layer blocks, the "
+                         "CPU baseline and parity, the other precision and batch, the HBM-bound kernels, the gather alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (64 MB at most)")
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4, 5),
                     help="BASELINE.json configs[config-1] as the headline: 2 = 64 fp32 faces per GPU (default), 3 = 512 "
                          "bf16 faces on one GPU, 4 = 512 bf16 faces per GPU + all-gather, 5 = the 1080p multi-face stream")
     ap.add_argument("--stream-dtype", default="f32", choices=("f32", "bf16"), help="arithmetic of --config 5")
     ap.add_argument("--batch", type=int, default=0, help="faces per GPU per step (0 = the configuration's: 64 or 512)")
     ap.add_argument("--n-points", type=int, default=4)
-    ap.add_argument("--cpu-faces", type=int, default=16, help="faces per repetition of the CPU baseline leg (0 = skip)")
+    ap.add_argument("--cpu-faces", type=int, default=16, help="--full: faces per repetition of the CPU baseline leg (0 = skip)")
     ap.add_argument("--no-align", action="store_true")
     ap.add_argument("--bf16-batch", type=int, default=512,
-                    help="with --config 2: also time the bf16 configuration (this many faces per GPU per step) and report "
+                    help="with --full and --config 2: also time the bf16 configuration (this many faces per GPU per step) and report "
                          "it as a side object (`bf16_config3` at N = 1, `config4` at N > 1); 0 = skip")
     ap.add_argument("--f32-big-batch", type=int, default=512,
-                    help="with --config 2 at N = 1: also time this many fp32 faces in one batch (side object "
+                    help="with --full and --config 2 at N = 1: also time this many fp32 faces in one batch (side object "
                          "`f32_batch512`); 0 = skip")
     ap.add_argument("--settle-ms", type=float, default=300.0,
                     help="extra untimed warm-up before the timed region so a short region starts at settled clocks")
-    ap.add_argument("--no-hbm-kernels", action="store_true")
+    ap.add_argument("--no-hbm-kernels", action="store_true", help="--full: skip the HBM-bound kernel entries")
     ap.add_argument("--stream-group", type=int, default=64,
                     help="--config 5: frames whose faces share one launch sequence (crop / resize, landmarks, alignment); "
                          "64 = the whole step (about 500 faces per sequence), 16 = a shorter pipeline (about 130)")
@@ -599,6 +657,8 @@ def main():
                          "run of the multi-rank flow on a box with fewer GPUs than ranks: ranks share devices, the "
                          "gather goes through the host; its numbers mean nothing)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -638,14 +698,18 @@ def main():
     wl = Workload(dtype, B, rank, args.n_points, not args.no_align, seed=3 if bf16_head else 1)
     roof_layer = "up3" if bf16_head else "fc6"
     peak = PEAK_BF16_TFLOPS if bf16_head else PEAK_F32_TFLOPS
-    dt, roof_ms, layer_avg, per_rank = measure(lib, wl, args.steps, args.warmup, world, roof_layer, args.settle_ms / 1e3)
+    dt, roof_ms, layer_avg, per_rank, out = measure(lib, wl, args.steps, args.warmup, world, roof_layer,
+                                                    args.settle_ms / 1e3, profile=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_arrays(out))
+    del out
     total = B * world
     coll = describe_collective(world, dev, B, CLS)
-    gather_ms = time_gather(world, dev, B, CLS)
+    gather_ms = time_gather(world, dev, B, CLS) if args.full else None
 
     side = None
-    side_coll = describe_collective(world, dev, args.bf16_batch, CLS) if world > 1 else None
-    if args.config == 2 and args.bf16_batch > 0:
+    side_coll = describe_collective(world, dev, args.bf16_batch, CLS) if world > 1 and args.full else None
+    if args.full and args.config == 2 and args.bf16_batch > 0:
         side, wl16 = bf16_side_object(lib, args, world, rank,
                                       "BASELINE configs[2]" if world == 1 else "BASELINE configs[3]")
         if world == 1 and rank == 0:   # bf16 landmarks of the whole 512 batch against the fp32 HIP path, same crops
@@ -659,14 +723,14 @@ def main():
         del wl16
 
     f32_big = None
-    if args.config == 2 and world == 1 and args.f32_big_batch > 0:
+    if args.full and args.config == 2 and world == 1 and args.f32_big_batch > 0:
         # the largest single-GPU configuration at the reference's own precision: does the 64-face roofline fraction hold
         # when fc6 runs eight generations of workgroups instead of two?  (enc2's 2 GiB input runs as two face slices)
         del wl
         torch.cuda.empty_cache()
         wlb = Workload("f32", args.f32_big_batch, rank, args.n_points, not args.no_align, seed=1)
         steps_b = max(3, args.steps // 4)
-        dtb, fc6_b, layers_b, _ = measure(lib, wlb, steps_b, 2, 1, "fc6", args.settle_ms / 1e3)
+        dtb, fc6_b, layers_b, _, _ = measure(lib, wlb, steps_b, 2, 1, "fc6", args.settle_ms / 1e3)
         issued = fc6_issued_gflop(wlb.batch)
         f32_big = {"workload": "%d faces fp32 on one GPU, same step as the headline" % wlb.batch, "dtype": "f32",
                    "faces_per_s": wlb.batch * steps_b / dtb, "ms_per_step": 1e3 * dtb / steps_b, "steps": steps_b,
@@ -682,7 +746,9 @@ def main():
     if rank == 0:
         value = total * args.steps / dt
         names = {2: "BASELINE configs[1]", 3: "BASELINE configs[2]", 4: "BASELINE configs[3]"}
-        if bf16_head:
+        if not args.full:
+            roof = None
+        elif bf16_head:
             roof = mfma_roofline("up3", "up3_cand8_kernel<bf16, 8 waves> (up3 + softmax + candidate keys)", roof_ms, B, peak,
                                  "traffic_bf16_latest.json")
         else:
@@ -696,7 +762,7 @@ def main():
                       "softmax + top-%d landmark decode + similarity/alignment warp" % args.n_points,
             "value": value, "unit": "faces/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": dtype, "data": "synthetic",
+            "vs_baseline": None, "dtype": dtype, "data": "synthetic", "full": args.full,
             "per_rank_ms_per_step": per_rank, "gather_ms": gather_ms,
             "config": {"workload": "%s: batch=%d/GPU 256x256x3 uint8 crops, fcn_8(68) vanilla encoder %s, random-init "
                                    "weights (seed 2), decode top-%d thresh 0, align to 256x256%s"
@@ -705,9 +771,9 @@ def main():
                        "faces_per_gpu_per_step": B, "global_batch": total, "parallelism": "dp%d" % world,
                        "collective": coll, "settle_ms_before_timed_region": args.settle_ms},
             "roofline": roof,
-            "forward": forward_summary(layer_avg, B, peak),
+            "forward": forward_summary(layer_avg, B, peak) if args.full else None,
         }
-        if args.cpu_faces > 0 and world == 1 and not bf16_head:   # CPU leg: rank 0 at N=1 only
+        if args.full and args.cpu_faces > 0 and world == 1 and not bf16_head:   # CPU leg: rank 0 at N=1 only
             base, lm_cpu, crops_cpu = cpu_baseline(args.cpu_faces, args.n_points, seed=1)
             rec["cpu_baseline"] = base
             # the same crops on the GPU: landmark NME vs the oracle (NME := mean ||p - p_ref|| / 256)
@@ -732,7 +798,7 @@ def main():
                                      "float32 evaluation may select another pixel there).  The float32 CPU oracle's own "
                                      "error on the same pairs rides along; the gate on all 64 faces of configs[1] is "
                                      "tests/test_gpu_baseline_configs.py" % args.n_points}
-        if not args.no_hbm_kernels and world == 1:
+        if args.full and not args.no_hbm_kernels and world == 1:
             rec["hbm_kernels"] = hbm_kernels(lib, dev)
         if f32_big is not None:
             rec["f32_batch512"] = f32_big

@@ -3,8 +3,8 @@
 PINNED: `tests/golden/make_decode_golden.py` imports the reference's
 `keypoints_detector/utils/metrics.py` in the build container, runs it on seeded
 heatmaps and freezes inputs + outputs in `tests/golden/decode_golden.npz`;
-`tests/test_oracle_decode.py` checks this file against that fixture (and, when
-`/root/reference` is present, against the live import).
+`tests/test_oracle_decode.py` checks this file against that fixture and against
+a seeded sweep recorded the same way (`tests/golden/decode_sweep_golden.npz`).
 
 Follows utils/metrics.py:46-109.  numpy dtype behaviour that the restatement
 keeps (NumPy >= 2 promotion rules, the version installed here):

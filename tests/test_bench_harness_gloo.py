@@ -116,3 +116,27 @@ def test_work_accounting_is_physical():
         assert useful * b - 1e-6 <= bench.fc6_issued_gflop(b) <= dense * max(b, 2) + 1e-6
     r = bench.mfma_roofline("fc6", "k", 2.2026, 64, bench.PEAK_F32_TFLOPS, "traffic_latest.json")
     assert 0.74 < r["frac"] < 0.76 and r["frac_dense"] > 1.2               # round 1's launch: 0.75 useful, 1.21 dense
+
+
+def test_dump_outputs_budget_and_seeded_sample(tmp_path):
+    """bench.py --dump-outputs: float64 stays float64, the rest becomes float32; what fits is written whole; an array
+    beyond the budget keeps a sorted seeded sample of its faces (the same in every run) and lists it."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"landmarks": rng.random((40, 68, 2)), "aligned": rng.random((40, 16, 16, 3)).astype(np.float32),
+              "align_m": rng.random((40, 2, 3)).astype(np.float32), "flags": np.arange(40, dtype=np.int32)}
+    budget = 100_000                                   # everything but `aligned` (40 x 3,072 B) fits whole
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget=budget)
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert sorted(got) == ["align_m", "aligned", "aligned_sample_index", "flags", "landmarks"]
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))) <= budget
+    assert got["landmarks"].dtype == np.float64 and np.array_equal(got["landmarks"], arrays["landmarks"])
+    assert got["flags"].dtype == np.float32 and np.array_equal(got["flags"], np.arange(40))
+    assert np.array_equal(got["align_m"], arrays["align_m"])
+    idx = got["aligned_sample_index"]
+    assert idx.dtype == np.float64 and 0 < len(idx) < 40 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got["aligned"], arrays["aligned"][idx.astype(int)])
+    for f in os.listdir(str(tmp_path / "a")):           # the same arguments write the same files
+        assert np.array_equal(np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f)))

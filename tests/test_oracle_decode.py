@@ -1,18 +1,17 @@
 """Pin oracle/decode_ref.py against the reference's own utils/metrics.py.
 
-Golden fixture: tests/golden/decode_golden.npz, produced by
+Golden fixtures: tests/golden/decode_golden.npz, produced by
 tests/golden/make_decode_golden.py which RUNS the reference implementation
-(utils/metrics.py:46-109) in the build container.
+(utils/metrics.py:46-109) in the build container, and
+tests/golden/decode_sweep_golden.npz, produced the same way by
+tests/golden/make_decode_sweep_golden.py.
 """
-import importlib.util
 import os
 
 import numpy as np
 import pytest
 
 from oracle import decode_ref
-
-REF_METRICS = "/root/reference/keypoints_detector/utils/metrics.py"
 
 
 @pytest.fixture(scope="module")
@@ -52,26 +51,19 @@ def test_transfer_target_as_shipped(gold):
     assert np.array_equal(a, c)
 
 
-@pytest.mark.skipif(not os.path.isfile(REF_METRICS), reason="reference not present (GPU box)")
-def test_live_reference_property():
-    """Seeded sweep against the live import of the reference (container only)."""
-    os.environ.setdefault("MPLBACKEND", "Agg")
-    spec = importlib.util.spec_from_file_location("ref_metrics_live", REF_METRICS)
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    rng = np.random.default_rng(7)
-    for k in range(40):
-        h, w = int(rng.integers(4, 70)), int(rng.integers(4, 70))
-        hm = rng.random((h, w), dtype=np.float32)
-        if k % 5 == 0:
-            hm = hm.astype(np.float64)
-        n = int(rng.choice([0, 1, 2, 4, 7, 16]))
-        n = min(n, h * w)
-        t = float(rng.choice([0.0, 0.3, 0.6]))
+def test_live_reference_property(golden_dir):
+    """Seeded sweep against what the reference's own get_average_xy returned for it (recorded in
+    decode_sweep_golden.npz): 40 random heatmaps, float32 and float64, top-n 0..16, thresholds 0 / 0.3 / 0.6."""
+    gold = np.load(os.path.join(golden_dir, "decode_sweep_golden.npz"))
+    params, expected = gold["params"], gold["expected"]
+    assert len(params) == len(expected) == 40
+    for k in range(len(params)):
+        hm = gold["hm_%02d" % k]
+        h, w = hm.shape
+        n, t = int(params[k, 0]), float(params[k, 1])
         with np.errstate(all="ignore"):
-            exp = ref.get_average_xy(hm, h, w, n, t)
             got = decode_ref.get_average_xy_ref(hm, n, t)
-        assert float(exp[0]) == float(got[0]) and float(exp[1]) == float(got[1]), (k, h, w, n, t)
+        assert float(expected[k, 0]) == float(got[0]) and float(expected[k, 1]) == float(got[1]), (k, h, w, n, t)
 
 
 def test_topn_gap_rel_is_the_relative_gap_at_the_nth_place():
