@@ -17,6 +17,7 @@ OUT_PROBS, OUT_CLASSMAP, OUT_LANDMARKS, OUT_LOGITS = 0, 1, 2, 3
 DECODE_ALL, DECODE_TOPN = 0, 1
 NORM_SUB_MEAN, NORM_SUB_AND_DIVIDE, NORM_DIVIDE = 0, 1, 2
 ABI_VERSION = 2
+SWEEP_MAX_MODES = 16  # FLM_SWEEP_MAX_MODES
 
 EXPORTS = [
     "flm_abi_version", "flm_last_error",
@@ -27,7 +28,8 @@ EXPORTS = [
     "flm_fcn8_workspace_bytes", "flm_fcn8_forward", "flm_fcn8_workspace_offset", "flm_fcn8_run_layer",
     "flm_set_tuning", "flm_debug_query", "flm_profile_enable", "flm_profile_filter", "flm_profile_reset", "flm_profile_read", "flm_profile_disable",
     "flm_preprocess",
-    "flm_decode_workspace_bytes", "flm_decode",
+    "flm_decode_workspace_bytes", "flm_decode", "flm_decode_sweep_workspace_bytes", "flm_decode_sweep",
+    "flm_gaussian_heatmaps",
     "flm_similarity_from_landmarks", "flm_similarity_from_landmarks_scaled", "flm_warp_affine", "flm_crop_resize", "flm_crop_resize_frames",
 ]
 
@@ -138,6 +140,13 @@ def _declare(lib):
     lib.flm_decode_workspace_bytes.argtypes = [i] * 6
     lib.flm_decode.restype = i
     lib.flm_decode.argtypes = [vp, vp, i, i, i, i, i, i, f, vp, vp, sz]
+    ip = C.POINTER(C.c_int)
+    lib.flm_decode_sweep_workspace_bytes.restype = sz
+    lib.flm_decode_sweep_workspace_bytes.argtypes = [i, i, i, i, ip, i]
+    lib.flm_decode_sweep.restype = i
+    lib.flm_decode_sweep.argtypes = [vp, vp, i, i, i, i, ip, i, f, vp, vp, sz]
+    lib.flm_gaussian_heatmaps.restype = i
+    lib.flm_gaussian_heatmaps.argtypes = [vp, vp, i, i, i, i, C.c_double, vp]
     lib.flm_similarity_from_landmarks.restype = i
     lib.flm_similarity_from_landmarks.argtypes = [vp, vp, vp, i, i, vp]
     lib.flm_similarity_from_landmarks_scaled.restype = i
@@ -193,6 +202,12 @@ def require_gpu():
 def stream_ptr():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def int_array(values):
+    """A host int32 array for the `const int*` arguments (flm_decode_sweep's mode list)."""
+    values = [int(v) for v in values]
+    return (C.c_int * max(1, len(values)))(*values)
 
 
 def ptr(t):

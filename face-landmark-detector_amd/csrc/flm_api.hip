@@ -796,6 +796,29 @@ int flm_decode(flm_stream_t stream, const float* hm, int n, int h, int w, int l,
                        ws_bytes);
 }
 
+size_t flm_decode_sweep_workspace_bytes(int n, int h, int w, int l, const int* modes, int n_modes) {
+  return decode_sweep_ws_bytes(n, h, w, l, modes, n_modes);
+}
+
+int flm_decode_sweep(flm_stream_t stream, const float* hm, int n, int h, int w, int l, const int* modes, int n_modes,
+                     float thresh, double* out, void* ws, size_t ws_bytes) {
+  if (!hm || !out || !ws) {
+    set_error("flm_decode_sweep: null argument");
+    return FLM_ERR_ARG;
+  }
+  return launch_decode_sweep(static_cast<hipStream_t>(stream), hm, n, h, w, l, modes, n_modes, thresh, out, ws,
+                             ws_bytes);
+}
+
+int flm_gaussian_heatmaps(flm_stream_t stream, const double* kp, int n, int l, int h, int w, double two_sigma_sq,
+                          float* out) {
+  if (!kp || !out) {
+    set_error("flm_gaussian_heatmaps: null argument");
+    return FLM_ERR_ARG;
+  }
+  return launch_gaussian_heatmaps(static_cast<hipStream_t>(stream), kp, n, l, h, w, two_sigma_sq, out);
+}
+
 int flm_similarity_from_landmarks(flm_stream_t stream, const double* lm, const double* tmpl, int n, int k,
                                   float* m) {
   if (!lm || !tmpl || !m) {

@@ -236,6 +236,11 @@ size_t decode_ws_bytes(int n, int h, int w, int l, int mode, int n_points);
 int launch_decode(hipStream_t s, const float* hm, int n, int h, int w, int l, int ld, int mode, int n_points,
                   float thresh, double* out, void* ws, size_t ws_bytes, float* tau_out = nullptr,
                   const unsigned* gate = nullptr);
+size_t decode_sweep_ws_bytes(int n, int h, int w, int l, const int* modes, int n_modes);
+int launch_decode_sweep(hipStream_t s, const float* hm, int n, int h, int w, int l, const int* modes, int n_modes,
+                        float thresh, double* out, void* ws, size_t ws_bytes);
+int launch_gaussian_heatmaps(hipStream_t s, const double* kp, int n, int l, int h, int w, double two_sigma_sq,
+                             float* out);
 int launch_cand_merge(hipStream_t s, const unsigned long long* cand, unsigned* cand_cnt, int n, int w, int l,
                       int n_points, float thresh, int cap, double* out);
 

@@ -19,6 +19,8 @@
 // arithmetic in the reference's order.
 #include "flm_common.h"
 
+#include <algorithm>
+
 namespace flm {
 
 constexpr int PT = 64;  // pixels per tile
@@ -808,6 +810,506 @@ int launch_decode(hipStream_t s, const float* hm, int n, int h, int w, int l, in
     decode_merge_kernel<FLM_DECODE_TOPN><<<dim3(l, n), 64, 0, s>>>(a);
   }
   FLM_LAUNCH_CHECK("decode_merge_kernel");
+  return FLM_OK;
+}
+
+
+// ---- one-pass multi-n decode (flm_decode_sweep) ------------------------------------------------------------------------
+// The reference's n_points experiment (utils/metrics.py:118-154) decodes the same maps at n = k*k, k = 1..9, and at the
+// all-pixel centroid.  Here one read of the maps serves every mode: the partial pass keeps, per chunk, the descending
+// (value, index) list of n_max = max(top-n modes) keys and, when some mode is 0, the float64 all-pixel sums; the merge
+// builds the face's top n_max list once and finishes every mode from it.  Under the total (value, index) order the top n
+// set is the first n keys of the top n_max list, so a top-n slice selects exactly what flm_decode(n) selects, ties
+// included; each n then redoes its own float32 hsum chain in the reference's order (rank n-1 down to rank 0: a prefix sum
+// of the n_max chain rounds differently), its own float64 index sums and its own reject test -- finish_topn.
+//
+// All-pixel sums in the sweep: thread t of a workgroup owns channel t % L and every G-th pixel of a tile (G = 256 / L
+// groups), three float64 accumulators per thread instead of three per channel and lane, so that the sums fit beside the
+// key lists without spilling.  The groups are reduced through LDS in a fixed order at the end of the chunk; the order
+// of the float64 additions differs from flm_decode(0)'s, hence agreement within 1e-9 px rather than bit for bit.
+struct SweepArgs {
+  const float* hm;
+  int n, h, w, l;
+  int chunks, chunk_px;  // decode_plan's
+  int vec;               // face stride is a multiple of 16 bytes
+  int n_max;             // largest top-n mode (0: all-pixel modes only)
+  int has_all;           // some mode is 0
+  float thresh;
+  unsigned long long* keys;  // [n][chunks][l][n_max]
+  double* sums;              // [n][chunks][l][3] (has_all)
+  double* out;               // [n_modes][n][l][2]
+  int n_modes;
+  int modes[FLM_SWEEP_MAX_MODES];
+};
+
+// this thread's share of a tile's all-pixel sums: pixels g, g + G, ... of the tile (row stride `rs` floats), channel c
+__device__ __forceinline__ void sweep_all_tile(const float* tile, int rs, int c, int g, int G, int p0, int npx, int w,
+                                               double& s0, double& sx, double& sy) {
+  if (g >= G) return;
+  int pix = p0 + g;
+  int y = pix / w, x = pix - y * w;
+  for (int p = g; p < npx; p += G) {
+    const double hv = (double)tile[p * rs + c];
+    s0 += hv;
+    sx = fma(hv, (double)x, sx);
+    sy = fma(hv, (double)y, sy);
+    x += G;
+    while (x >= w) { x -= w; ++y; }
+  }
+}
+
+// end of chunk: the G groups' sums of every channel, added in group order, to sums[face][chunk][c][0..2].
+// `red` is LDS of at least 256 x 3 doubles that no wave reads any more.
+__device__ __forceinline__ void sweep_all_flush(const SweepArgs& a, double* red, int tid, int c, int g, int G,
+                                                double s0, double sx, double sy) {
+  __syncthreads();
+  if (g < G) {
+    red[tid * 3 + 0] = s0;
+    red[tid * 3 + 1] = sx;
+    red[tid * 3 + 2] = sy;
+  }
+  __syncthreads();
+  if (tid < a.l) {
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0;
+    for (int k = 0; k < G; ++k) {
+      const int t = k * a.l + tid;
+      v0 += red[t * 3 + 0];
+      v1 += red[t * 3 + 1];
+      v2 += red[t * 3 + 2];
+    }
+    double* dst = a.sums + (((size_t)blockIdx.y * a.chunks + blockIdx.x) * a.l + tid) * 3;
+    dst[0] = v0;
+    dst[1] = v1;
+    dst[2] = v2;
+  }
+}
+
+// register-prefetch form: decode_partial_kernel<FLM_DECODE_TOPN, CPW, WIDE> with n_points = n_max, plus the all-pixel
+// sums when ALL.  Dynamic LDS: max(tile, 256 x 3 doubles).
+template <int CPW, bool WIDE, bool ALL>
+__global__ __launch_bounds__(256) void decode_sweep_partial_kernel(SweepArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float tile[];  // [PT][LS]
+  const int L = a.l, LS = L | 1;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int face = blockIdx.y, chunk = blockIdx.x;
+  const int HW = a.h * a.w;
+  const int p_begin = chunk * a.chunk_px;
+  const int p_end = min(p_begin + a.chunk_px, HW);
+  const float* src = a.hm + (size_t)face * HW * L;
+  const int c_first = wave * CPW;
+  const int n_max = a.n_max;
+  const int G = 256 / L, ag = tid / L, ac = tid - ag * L;  // all-pixel sums: group, channel
+
+  double s0 = 0.0, sx = 0.0, sy = 0.0;
+  unsigned long long list[CPW], tau[CPW];
+  unsigned long long list_hi[WIDE ? CPW : 1];
+#pragma unroll
+  for (int i = 0; i < CPW; ++i) {
+    list[i] = 0ull; tau[i] = 0ull;
+    if (WIDE) list_hi[i] = 0ull;
+  }
+
+  const int tile_f = PT * L;
+  float4 pf0, pf1, pf2, pf3, pf4, pf5;
+  pf0 = pf1 = pf2 = pf3 = pf4 = pf5 = make_float4(0.f, 0.f, 0.f, 0.f);
+#define FLM_PF_LOAD(I, R)                                                         \
+  {                                                                               \
+    const int e4 = tid * 4 + 1024 * I;                                            \
+    if (e4 < tile_f) R = load_stream16(nsrc + e4);                                \
+  }
+#define FLM_PF_STORE(I, R)                                                        \
+  {                                                                               \
+    const int e4 = tid * 4 + 1024 * I;                                            \
+    if (e4 < tile_f) {                                                            \
+      int p = e4 / L, c = e4 - p * L;                                             \
+      tile[p * LS + c] = R.x; if (++c == L) { c = 0; ++p; }                       \
+      tile[p * LS + c] = R.y; if (++c == L) { c = 0; ++p; }                       \
+      tile[p * LS + c] = R.z; if (++c == L) { c = 0; ++p; }                       \
+      tile[p * LS + c] = R.w;                                                     \
+    }                                                                             \
+  }
+  bool pf_valid = false;
+  if (a.vec && p_begin + PT <= p_end) {
+    const float* nsrc = src + (size_t)p_begin * L;
+    FLM_PF_LOAD(0, pf0) FLM_PF_LOAD(1, pf1) FLM_PF_LOAD(2, pf2) FLM_PF_LOAD(3, pf3) FLM_PF_LOAD(4, pf4)
+    FLM_PF_LOAD(5, pf5)
+    pf_valid = true;
+  }
+  for (int p0 = p_begin; p0 < p_end; p0 += PT) {
+    const int npx = min(PT, p_end - p0);
+    const int nf = npx * L;
+    __syncthreads();
+    if (pf_valid) {
+      FLM_PF_STORE(0, pf0) FLM_PF_STORE(1, pf1) FLM_PF_STORE(2, pf2) FLM_PF_STORE(3, pf3) FLM_PF_STORE(4, pf4)
+      FLM_PF_STORE(5, pf5)
+    } else {
+      const float* tsrc = src + (size_t)p0 * L;
+      for (int e = tid; e < tile_f; e += 256) {
+        const int p = e / L, c = e - p * L;
+        tile[p * LS + c] = (e < nf) ? tsrc[e] : 0.f;
+      }
+    }
+    pf_valid = a.vec && p0 + 2 * PT <= p_end;
+    if (pf_valid) {
+      const float* nsrc = src + (size_t)(p0 + PT) * L;
+      FLM_PF_LOAD(0, pf0) FLM_PF_LOAD(1, pf1) FLM_PF_LOAD(2, pf2) FLM_PF_LOAD(3, pf3) FLM_PF_LOAD(4, pf4)
+      FLM_PF_LOAD(5, pf5)
+    }
+    __syncthreads();
+
+    if (ALL) sweep_all_tile(tile, LS, ac, ag, G, p0, npx, a.w, s0, sx, sy);
+    if (n_max > 0) {  // (uniform)
+      const int pix = p0 + lane;
+      const bool pvalid = lane < npx;
+#pragma unroll
+      for (int i = 0; i < CPW; ++i) {
+        const int c = c_first + i;
+        if (c < L) {  // wave-uniform
+          const float hv = tile[lane * LS + c];
+          const unsigned long long key =
+              pvalid ? (((unsigned long long)order_bits(hv) << 32) | (unsigned)pix) : 0ull;
+          if (__any(key > tau[i])) {
+            if constexpr (WIDE) insert_candidates_wide(list[i], list_hi[i], tau[i], key, n_max, lane);
+            else insert_candidates(list[i], tau[i], key, n_max, lane);
+          }
+        }
+      }
+    }
+  }
+#undef FLM_PF_LOAD
+#undef FLM_PF_STORE
+
+  if (n_max > 0) {
+    unsigned long long* part = a.keys + ((size_t)face * a.chunks + chunk) * L * n_max;
+#pragma unroll
+    for (int i = 0; i < CPW; ++i) {
+      const int c = c_first + i;
+      if (c < L && lane < n_max) part[(size_t)c * n_max + lane] = list[i];
+      if (WIDE && c < L && lane + 64 < n_max) part[(size_t)c * n_max + 64 + lane] = list_hi[i];
+    }
+  }
+  if (ALL) sweep_all_flush(a, reinterpret_cast<double*>(tile), tid, ac, ag, G, s0, sx, sy);
+}
+
+// LDS-DMA form (68 landmarks, 16-byte-aligned faces, n_max <= 64): decode_partial_dma_kernel<FLM_DECODE_TOPN> with
+// n_points = n_max, plus the all-pixel sums when ALL (read from the same ring slot, row stride 68).
+template <bool ALL>
+__global__ __launch_bounds__(256) void decode_sweep_partial_dma_kernel(SweepArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char ring[];  // [D_RING][PT][DL] floats
+  constexpr int CPW = 17;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int face = blockIdx.y, chunk = blockIdx.x;
+  const int HW = a.h * a.w;
+  const int p_begin = chunk * a.chunk_px;
+  const int p_end = min(p_begin + a.chunk_px, HW);
+  const int ntiles = (p_end - p_begin + PT - 1) / PT;
+  if (ntiles <= 0) return;  // (uniform)
+  const int n_max = a.n_max;
+  constexpr int G = 256 / DL;
+  const int ag = tid / DL, ac = tid - ag * DL;
+
+  double s0 = 0.0, sx = 0.0, sy = 0.0;
+  unsigned long long list[CPW], tau[CPW];
+  float tauf[CPW];
+#pragma unroll
+  for (int i = 0; i < CPW; ++i) {
+    list[i] = 0ull; tau[i] = 0ull;
+    tauf[i] = from_order_bits(0u);
+  }
+
+  typedef int dsrd_t __attribute__((ext_vector_type(4)));
+  typedef __attribute__((address_space(3))) char lds_char;
+  const unsigned ring_lds = (unsigned)(size_t)((lds_char*)ring);
+  const unsigned long long cb = reinterpret_cast<unsigned long long>(a.hm + ((size_t)face * HW + p_begin) * DL);
+  const dsrd_t srd = (dsrd_t){(int)(unsigned)cb, (int)(unsigned)((cb >> 32) & 0xffffu), (p_end - p_begin) * DL * 4, 0x00020000};
+  auto issue = [&](int t) __attribute__((always_inline)) {
+    const unsigned slot = ring_lds + (unsigned)(t % D_RING) * D_TILE_B;
+#pragma unroll
+    for (int j = 0; j < D_PPW; ++j) {
+      const int k = wave + 4 * j < D_PIECES ? wave + 4 * j : wave;
+      asm volatile("s_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen nt lds"
+                   :
+                   : "v"((unsigned)t * D_TILE_B + (unsigned)k * 1024u + (unsigned)lane * 16u), "s"(srd), "{m0}"(slot + k * 1024)
+                   : "memory");
+    }
+  };
+  issue(0);
+  if (ntiles > 1) issue(1);
+  const int c16 = 16 * wave;
+  for (int t = 0; t < ntiles; ++t) {
+    if (t + 1 < ntiles) __builtin_amdgcn_s_waitcnt(0x0f75);  // vmcnt(5)
+    else __builtin_amdgcn_s_waitcnt(0x0f70);
+    __syncthreads();
+    if (t + 2 < ntiles) issue(t + 2);
+    const char* slot = ring + (size_t)(t % D_RING) * D_TILE_B;
+    const int p0 = p_begin + t * PT;
+    if (ALL) sweep_all_tile(reinterpret_cast<const float*>(slot), DL, ac, ag, G, p0, min(PT, p_end - p0), a.w, s0, sx, sy);
+    if (n_max > 0) {  // (uniform)
+      const char* tile = slot + lane * (DL * 4);
+      float v[CPW];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float4 q = *reinterpret_cast<const float4*>(tile + (c16 + 4 * j) * 4);
+        v[4 * j] = q.x; v[4 * j + 1] = q.y; v[4 * j + 2] = q.z; v[4 * j + 3] = q.w;
+      }
+      v[16] = *reinterpret_cast<const float*>(tile + (64 + wave) * 4);
+      const int pix = p0 + lane;
+      const bool pvalid = pix < p_end;
+#pragma unroll
+      for (int i = 0; i < CPW; ++i) {
+        if (__any(!(v[i] < tauf[i]))) {
+          const unsigned long long key = pvalid ? (((unsigned long long)order_bits(v[i]) << 32) | (unsigned)pix) : 0ull;
+          if (__any(key > tau[i])) {
+            insert_candidates(list[i], tau[i], key, n_max, lane);
+            tauf[i] = from_order_bits((unsigned)(tau[i] >> 32));
+          }
+        }
+      }
+    }
+  }
+
+  if (n_max > 0) {
+    unsigned long long* part = a.keys + ((size_t)face * a.chunks + chunk) * DL * n_max;
+#pragma unroll
+    for (int i = 0; i < CPW; ++i) {
+      const int c = i < 16 ? c16 + i : 64 + wave;
+      if (lane < n_max) part[(size_t)c * n_max + lane] = list[i];
+    }
+  }
+  if (ALL) sweep_all_flush(a, reinterpret_cast<double*>(ring), tid, ac, ag, G, s0, sx, sy);
+}
+
+// one wave per (face, landmark): merge the chunk lists to the face's top n_max once, then finish every mode
+template <bool WIDE>
+__global__ __launch_bounds__(64) void decode_sweep_merge_kernel(SweepArgs a) {
+  const int lane = threadIdx.x;
+  const int c = blockIdx.x, face = blockIdx.y;
+  const int L = a.l, n_max = a.n_max;
+  unsigned long long list = 0ull, list_hi = 0ull, tau = 0ull;
+  if (n_max > 0) {
+    const unsigned long long* part = a.keys + (size_t)face * a.chunks * L * n_max;
+    if constexpr (WIDE) {
+      for (int s = 0; s < a.chunks; ++s)
+        for (int r0 = 0; r0 < n_max; r0 += 64) {
+          const unsigned long long cand = r0 + lane < n_max ? part[((size_t)s * L + c) * n_max + r0 + lane] : 0ull;
+          if (__any(cand > tau)) insert_candidates_wide(list, list_hi, tau, cand, n_max, lane);
+        }
+    } else {
+      const int per = 64 / n_max;
+      for (int s0 = 0; s0 < a.chunks; s0 += per) {
+        const int s = s0 + lane / n_max, rk = lane % n_max;
+        const unsigned long long cand =
+            (lane < per * n_max && s < a.chunks) ? part[((size_t)s * L + c) * n_max + rk] : 0ull;
+        if (__any(cand > tau)) insert_candidates(list, tau, cand, n_max, lane);
+      }
+    }
+  }
+  double ax = 0.0, ay = 0.0;  // the all-pixel centroid (decode_merge_kernel<FLM_DECODE_ALL>'s arithmetic)
+  if (a.has_all) {
+    const double* part = a.sums + (size_t)face * a.chunks * L * 3;
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0;
+    for (int s = 0; s < a.chunks; ++s) {
+      v0 += part[((size_t)s * L + c) * 3 + 0];
+      v1 += part[((size_t)s * L + c) * 3 + 1];
+      v2 += part[((size_t)s * L + c) * 3 + 2];
+    }
+    const float hsum = (float)v0;
+    ax = v1 / (double)hsum;
+    ay = v2 / (double)hsum;
+    if (hsum / (float)(a.h * a.w) <= a.thresh) { ax = -1.0; ay = -1.0; }
+  }
+  for (int m = 0; m < a.n_modes; ++m) {
+    const int np = a.modes[m];
+    double* out = a.out + (((size_t)m * a.n + face) * L + c) * 2;
+    if (np == 0) {
+      if (lane == 0) {
+        out[0] = ax;
+        out[1] = ay;
+      }
+    } else {
+      finish_topn(list, np, a.w, a.thresh, lane, out, list_hi);
+    }
+  }
+}
+
+// workspace of a validated mode list: the key lists, then the all-pixel sums
+static void sweep_layout(int n, int h, int w, int l, int n_max, int has_all, size_t* keys_bytes, size_t* sums_bytes) {
+  int chunks, chunk_px;
+  decode_plan(n, h, w, &chunks, &chunk_px);
+  *keys_bytes = align_up((size_t)n * chunks * l * n_max * sizeof(unsigned long long), 256);
+  *sums_bytes = has_all ? align_up((size_t)n * chunks * l * 3 * sizeof(double), 256) : 0;
+}
+
+static int sweep_check_modes(const int* modes, int n_modes, int* n_max, int* has_all) {
+  if (!modes || n_modes < 1 || n_modes > FLM_SWEEP_MAX_MODES) {
+    set_error("decode_sweep: 1 <= n_modes <= %d mode entries required (got %d%s)", FLM_SWEEP_MAX_MODES, n_modes,
+              modes ? "" : ", null list");
+    return FLM_ERR_ARG;
+  }
+  *n_max = 0;
+  *has_all = 0;
+  for (int i = 0; i < n_modes; ++i) {
+    if (modes[i] < 0 || modes[i] > 128) {
+      set_error("decode_sweep: mode %d is %d; each mode is 0 (all pixels) or 1 <= n_points <= 128", i, modes[i]);
+      return FLM_ERR_UNSUPPORTED;
+    }
+    if (modes[i] == 0) *has_all = 1;
+    *n_max = std::max(*n_max, modes[i]);
+  }
+  return FLM_OK;
+}
+
+static int sweep_check_shape(int n, int h, int w, int l) {
+  if (n <= 0 || h <= 0 || w <= 0 || l <= 0 || l > kMaxClasses) {
+    set_error("decode_sweep: unsupported shape n=%d h=%d w=%d l=%d (max %d landmarks)", n, h, w, l, kMaxClasses);
+    return FLM_ERR_SHAPE;
+  }
+  if ((long long)h * w >= (1ll << 31)) {
+    set_error("decode_sweep: map too large");
+    return FLM_ERR_SHAPE;
+  }
+  return FLM_OK;
+}
+
+size_t decode_sweep_ws_bytes(int n, int h, int w, int l, const int* modes, int n_modes) {
+  int n_max, has_all;
+  if (sweep_check_shape(n, h, w, l) != FLM_OK || sweep_check_modes(modes, n_modes, &n_max, &has_all) != FLM_OK) return 0;
+  size_t kb, sb;
+  sweep_layout(n, h, w, l, n_max, has_all, &kb, &sb);
+  return kb + sb;
+}
+
+int launch_decode_sweep(hipStream_t s, const float* hm, int n, int h, int w, int l, const int* modes, int n_modes,
+                        float thresh, double* out, void* ws, size_t ws_bytes) {
+  int rc = sweep_check_shape(n, h, w, l);
+  if (rc != FLM_OK) return rc;
+  SweepArgs a;
+  rc = sweep_check_modes(modes, n_modes, &a.n_max, &a.has_all);
+  if (rc != FLM_OK) return rc;
+  if (reinterpret_cast<uintptr_t>(hm) & 15) {
+    set_error("decode_sweep: heatmap pointer must be 16-byte aligned");
+    return FLM_ERR_ARG;
+  }
+  size_t kb, sb;
+  sweep_layout(n, h, w, l, a.n_max, a.has_all, &kb, &sb);
+  if (ws_bytes < kb + sb) {
+    set_error("decode_sweep: workspace too small");
+    return FLM_ERR_WORKSPACE;
+  }
+  a.hm = hm; a.n = n; a.h = h; a.w = w; a.l = l;
+  decode_plan(n, h, w, &a.chunks, &a.chunk_px);
+  a.vec = (((long long)h * w * l) & 3) == 0;
+  a.thresh = thresh;
+  a.keys = static_cast<unsigned long long*>(ws);
+  a.sums = reinterpret_cast<double*>(static_cast<char*>(ws) + kb);
+  a.out = out;
+  a.n_modes = n_modes;
+  for (int i = 0; i < FLM_SWEEP_MAX_MODES; ++i) a.modes[i] = i < n_modes ? modes[i] : 0;
+
+  const dim3 grid(a.chunks, n);
+  const bool wide = a.n_max > 64;
+  const bool dma = g_decode_dma.load(std::memory_order_relaxed) && l == DL && a.vec && !wide &&
+                   (long long)a.chunk_px * DL * 4 < (1ll << 31);
+  if (dma) {
+    constexpr size_t dlds = (size_t)D_RING * D_TILE_B;
+    static_assert(dlds >= 256 * 3 * sizeof(double), "the ring holds the all-pixel reduction");
+    if (a.has_all) {
+      static FuncAttrOnce attr;
+      FLM_FUNC_ATTR_ONCE(attr, (&decode_sweep_partial_dma_kernel<true>), dlds);
+      decode_sweep_partial_dma_kernel<true><<<grid, 256, dlds, s>>>(a);
+    } else {
+      static FuncAttrOnce attr;
+      FLM_FUNC_ATTR_ONCE(attr, (&decode_sweep_partial_dma_kernel<false>), dlds);
+      decode_sweep_partial_dma_kernel<false><<<grid, 256, dlds, s>>>(a);
+    }
+    FLM_LAUNCH_CHECK("decode_sweep_partial_dma_kernel");
+  } else {
+    const size_t lds = std::max(sizeof(float) * PT * (l | 1), 256 * 3 * sizeof(double));
+    const bool small = l <= 68;
+#define FLM_SWEEP_PARTIAL(CPW, WIDE, ALL) decode_sweep_partial_kernel<CPW, WIDE, ALL><<<grid, 256, lds, s>>>(a)
+    if (small) {
+      if (wide) { if (a.has_all) FLM_SWEEP_PARTIAL(17, true, true); else FLM_SWEEP_PARTIAL(17, true, false); }
+      else      { if (a.has_all) FLM_SWEEP_PARTIAL(17, false, true); else FLM_SWEEP_PARTIAL(17, false, false); }
+    } else {
+      if (wide) { if (a.has_all) FLM_SWEEP_PARTIAL(24, true, true); else FLM_SWEEP_PARTIAL(24, true, false); }
+      else      { if (a.has_all) FLM_SWEEP_PARTIAL(24, false, true); else FLM_SWEEP_PARTIAL(24, false, false); }
+    }
+#undef FLM_SWEEP_PARTIAL
+    FLM_LAUNCH_CHECK("decode_sweep_partial_kernel");
+  }
+  if (wide) decode_sweep_merge_kernel<true><<<dim3(l, n), 64, 0, s>>>(a);
+  else decode_sweep_merge_kernel<false><<<dim3(l, n), 64, 0, s>>>(a);
+  FLM_LAUNCH_CHECK("decode_sweep_merge_kernel");
+  return FLM_OK;
+}
+
+// ---- Gaussian target maps (flm_gaussian_heatmaps) ----------------------------------------------------------------------
+// generate_hm / gaussian_k (data/generator.py:274-296) on the device: float64 keypoints [N,L,2] (x,y) in grid pixels ->
+// float32 [N,H,W,L], hm[r,c,i] = float32(exp(-((c - x0)**2 + (r - y0)**2) / (2 * sigma**2))) in float64, in that
+// operation order (-ffp-contract=off: nothing fuses); a keypoint equal to (-1,-1) gives an all-zero map (:292).
+// `two_sigma_sq` is the host's `2 * sigma**2`.  Far from the centre the value rounds to +0.0f: where
+// d2 > 106 * two_sigma_sq the exponent -d2 / two_sigma_sq is below -105 even after the rounding of that product, so
+// exp() < 2.6e-46 < 2^-150 (half the smallest float32 subnormal) and the float32 value is +0.0f -- the skipped exp()
+// cannot change a bit.  NaN / infinite inputs fail the test and take the formula.  The kernel is bound by its writes:
+// four consecutive floats of the channel-last output per thread, one 16-byte store.
+__global__ __launch_bounds__(256) void gaussian_hm_kernel(const double* __restrict__ kp, int n, int l, int h, int w,
+                                                          double two_sigma_sq, float* __restrict__ out, long long total) {
+  const long long e0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (e0 >= total) return;
+  const double cut = 106.0 * two_sigma_sq;
+  const long long hw = (long long)h * w;
+  const long long q = e0 / l;  // (face, pixel) of the first element; the next three follow by increments
+  int c = (int)(e0 - q * l);
+  long long face = q / hw;
+  const int pix = (int)(q - face * hw);
+  int row = pix / w, col = pix - row * w;
+  float v[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float r = 0.f;
+    if (e0 + j < total) {
+      const double x0 = kp[(face * l + c) * 2 + 0], y0 = kp[(face * l + c) * 2 + 1];
+      if (!(x0 == -1.0 && y0 == -1.0)) {
+        const double dx = (double)col - x0, dy = (double)row - y0;
+        const double d2 = dx * dx + dy * dy;
+        if (!(d2 > cut)) r = (float)exp(-d2 / two_sigma_sq);
+      }
+    }
+    v[j] = r;
+    if (++c == l) {
+      c = 0;
+      if (++col == w) {
+        col = 0;
+        if (++row == h) { row = 0; ++face; }
+      }
+    }
+  }
+  if (e0 + 3 < total) {
+    *reinterpret_cast<float4*>(out + e0) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    for (int j = 0; j < 4 && e0 + j < total; ++j) out[e0 + j] = v[j];
+  }
+}
+
+int launch_gaussian_heatmaps(hipStream_t s, const double* kp, int n, int l, int h, int w, double two_sigma_sq,
+                             float* out) {
+  if (n <= 0 || l <= 0 || h <= 0 || w <= 0 || (long long)h * w >= (1ll << 31)) {
+    set_error("gaussian_heatmaps: unsupported shape n=%d l=%d h=%d w=%d", n, l, h, w);
+    return FLM_ERR_SHAPE;
+  }
+  if (reinterpret_cast<uintptr_t>(out) & 15) {
+    set_error("gaussian_heatmaps: output pointer must be 16-byte aligned");
+    return FLM_ERR_ARG;
+  }
+  const long long total = (long long)n * h * w * l;
+  const long long blocks = (total + 1023) / 1024;
+  if (blocks >= (1ll << 31)) {
+    set_error("gaussian_heatmaps: output too large");
+    return FLM_ERR_SHAPE;
+  }
+  gaussian_hm_kernel<<<dim3((unsigned)blocks), 256, 0, s>>>(kp, n, l, h, w, two_sigma_sq, out, total);
+  FLM_LAUNCH_CHECK("gaussian_hm_kernel");
   return FLM_OK;
 }
 

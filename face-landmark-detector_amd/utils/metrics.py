@@ -100,3 +100,118 @@ def get_RMSE(y_pred_xy, y_train_xy, pick_not_NA):
     """utils/metrics.py:112-115 (host numpy, unchanged semantics)."""
     res = y_pred_xy[pick_not_NA] - y_train_xy[pick_not_NA]
     return np.sqrt(np.mean(res ** 2))
+
+
+# ---- the n_points experiment (utils/metrics.py:1-37, :118-154) -------------------------------------------------------
+SWEEP_N_POINTS = tuple(k * k for k in range(1, 10)) + (0,)   # `[nw * nw for nw in range(1, 10) + [0]]`, :129-131
+RMSE_LABELS = ("(x,y) from est heatmap  VS (x,y) from true heatmap",
+               "(x,y) from est heatmap  VS true (x,y)",
+               "(x,y) from true heatmap VS true (x,y)")
+
+
+def decode_sweep_device(hm, n_points_list, thresh=0.0):
+    """hm: CUDA float32 [N,H,W,L] contiguous -> CUDA float64 [S,N,L,2]: slice s is decode_device(hm, n_points_list[s],
+    thresh) (top-n bit for bit, all-pixel within 1e-9 px), every 16 modes from one read of the maps (flm_decode_sweep)."""
+    import torch
+    lib = _lib.load()
+    if hm.dim() != 4 or hm.dtype != torch.float32 or not hm.is_cuda or not hm.is_contiguous():
+        raise ValueError("decode_sweep_device needs a contiguous CUDA float32 [N,H,W,L] tensor")
+    modes = [max(int(n), 0) for n in n_points_list]   # n_points < 1: all pixels, as decode_device
+    if not modes:
+        raise ValueError("n_points_list is empty")
+    n, h, w, l = [int(v) for v in hm.shape]
+    out = torch.empty((len(modes), n, l, 2), dtype=torch.float64, device=hm.device)
+    if n == 0:
+        return out
+    for lo in range(0, len(modes), _lib.SWEEP_MAX_MODES):
+        part = modes[lo:lo + _lib.SWEEP_MAX_MODES]
+        arr = _lib.int_array(part)
+        nbytes = lib.flm_decode_sweep_workspace_bytes(n, h, w, l, arr, len(part))
+        ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=hm.device)
+        _lib.check(lib.flm_decode_sweep(_lib.stream_ptr(), _lib.ptr(hm), n, h, w, l, arr, len(part), float(thresh),
+                                        _lib.ptr(out[lo:lo + len(part)]), _lib.ptr(ws), ws.numel()), "flm_decode_sweep")
+    return out
+
+
+def _maps_on_device(y):
+    import torch
+    if isinstance(y, torch.Tensor):
+        hm = y if y.is_cuda else y.to(_lib.require_gpu())
+        return hm.contiguous().float()
+    return _to_device(np.asarray(y))
+
+
+def transfer_target_sweep(y_pred, n_points_list, thresh=0):
+    """transfer_target(y_pred, thresh, n) for every n of `n_points_list` in one pass over the maps:
+    [N,H,W,L] -> float64 [S, N, 2L].  numpy in -> numpy out, torch tensor in -> CUDA tensor out."""
+    import torch
+    was_np = not isinstance(y_pred, torch.Tensor)
+    out = decode_sweep_device(_maps_on_device(y_pred), n_points_list, thresh)
+    out = out.reshape(out.shape[0], out.shape[1], 2 * out.shape[2])
+    return out.cpu().numpy() if was_np else out
+
+
+def _masked_sq_sums(pred_xy, true_xy, actual_xy):
+    """Per mode, over the coordinates the true heatmap decoded (`pick_not_NA = (y_train_xy != -1)`, :134): float64
+    sums of the squared residuals of the three RMSEs and the count.  pred_xy / true_xy [S,N,2L], actual_xy [N,2L], all
+    CUDA float64 -> ([S,3], [S]) on the device."""
+    import torch
+    pick = true_xy != -1
+    act = actual_xy.unsqueeze(0)
+    zero = torch.zeros((), dtype=torch.float64, device=pred_xy.device)
+    sums = torch.stack([torch.where(pick, (pred_xy - true_xy) ** 2, zero).sum(dim=(1, 2)),
+                        torch.where(pick, (pred_xy - act) ** 2, zero).sum(dim=(1, 2)),
+                        torch.where(pick, (true_xy - act) ** 2, zero).sum(dim=(1, 2))], dim=1)
+    return sums, pick.sum(dim=(1, 2))
+
+
+def _rmse_table(sums, counts):
+    """[S,3] float64 sums and [S] counts -> the [S,3] RMSE table (numpy; NaN where nothing was counted, as np.mean of
+    an empty selection)."""
+    s = sums.cpu().numpy()
+    c = counts.cpu().numpy().astype(np.float64)[:, None]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.sqrt(s / c)
+
+
+def plot_keypoints_metric(res, n_points_list=SWEEP_N_POINTS, im_dim=(96, 96)):
+    """What get_keypoints_metric draws (:147-153): the three RMSEs against sqrt(n_points), the all-pixel mode at
+    im_dim[0]."""
+    import matplotlib.pyplot as plt
+    xs = [im_dim[0] if int(n) < 1 else float(np.sqrt(int(n))) for n in n_points_list]
+    if list(n_points_list) == list(SWEEP_N_POINTS):
+        xs = list(range(1, 10)) + [im_dim[0]]
+    for i, lab in enumerate(RMSE_LABELS):
+        plt.plot(xs, res[:, i], label=lab)
+    plt.legend()
+    plt.ylabel("RMSE")
+    plt.xlabel("n_points")
+    plt.show()
+
+
+def get_keypoints_metric(ytrain_dist, ypred_dist, ytrain_actual, nimage=500, im_dim=(96, 96), plotting=True,
+                         n_points_list=None):
+    """utils/metrics.py:118-154: for n = 1, 4, ..., 81 and then 0 (all pixels) -- or `n_points_list` -- the three RMSEs
+    of the module docstring (:17-20): est. heatmap vs true heatmap, est. heatmap vs true (x,y), true heatmap vs true
+    (x,y), over the coordinates the true heatmap decodes (:134).  Returns the [S, 3] float64 table (the reference
+    returns nothing; as shipped it cannot run on Python 3).  The maps are decoded with thresh 0 and the
+    n asked for (the reference's docstring, not its argument slip at :98); each set of maps is read once
+    (transfer_target_sweep) and the residual sums stay on the device in float64.
+    ytrain_dist / ypred_dist: [N,H,W,L] maps; ytrain_actual: [N, 2L] true (x,y) in grid pixels."""
+    import torch
+    modes = list(SWEEP_N_POINTS if n_points_list is None else n_points_list)
+    y_pred_xy = transfer_target_sweep(_maps_on_device(ypred_dist[:nimage]), modes, 0)
+    y_train_xy = transfer_target_sweep(_maps_on_device(ytrain_dist[:nimage]), modes, 0)
+    act = ytrain_actual[:nimage]
+    act = (act.to(y_pred_xy.device) if isinstance(act, torch.Tensor)
+           else torch.from_numpy(np.ascontiguousarray(act)).to(y_pred_xy.device)).to(torch.float64)
+    if tuple(act.shape) != tuple(y_pred_xy.shape[1:]):
+        raise ValueError("ytrain_actual must be [N, 2L] = %s, got %s" % (tuple(y_pred_xy.shape[1:]), tuple(act.shape)))
+    sums, counts = _masked_sq_sums(y_pred_xy, y_train_xy, act)
+    res = _rmse_table(sums, counts)
+    for n in modes:   # (:143-144)
+        print("n_points to evaluate (x,y) coordinates = {}".format(n))
+        print(" RMSE")
+    if plotting:
+        plot_keypoints_metric(res, modes, im_dim)
+    return res

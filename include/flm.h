@@ -285,6 +285,28 @@ int flm_decode(flm_stream_t stream, const float* hm_dev, int n, int h, int w, in
                int n_points, float thresh, double* out_dev, void* workspace_dev,
                size_t workspace_bytes);
 
+/* One read of the maps, up to FLM_SWEEP_MAX_MODES decodes (the n_points experiment of utils/metrics.py:118-154).
+ * `modes` (host memory, n_modes entries, duplicates and any order allowed): 0 = all-pixel centroid, 1..128 = top-n.
+ * out: float64 [n_modes, N, L, 2], slice m for modes[m].  A top-n slice is byte for byte what flm_decode(TOPN, n)
+ * writes (same selection under the (value, flat index) order, the same float32 hsum chain, float64 index sums and reject
+ * test); an all-pixel slice agrees with flm_decode(ALL) within 1e-9 px (float64 partial sums added in another order).
+ * Errors: FLM_ERR_ARG for a null or empty list, more than FLM_SWEEP_MAX_MODES entries, or a misaligned map;
+ * FLM_ERR_UNSUPPORTED for a mode outside 0..128; FLM_ERR_SHAPE / FLM_ERR_WORKSPACE as flm_decode.  The workspace query
+ * returns 0 for arguments the call rejects. */
+#define FLM_SWEEP_MAX_MODES 16
+size_t flm_decode_sweep_workspace_bytes(int n, int h, int w, int l, const int* modes, int n_modes);
+int flm_decode_sweep(flm_stream_t stream, const float* hm_dev, int n, int h, int w, int l, const int* modes,
+                     int n_modes, float thresh, double* out_dev, void* workspace_dev, size_t workspace_bytes);
+
+/* Gaussian target maps: generate_hm(height, width, keypoints, s) (data/generator.py:274-296) on the device.
+ * kp_dev float64 [N,L,2] (x,y) in grid pixels -> out_dev float32 [N,H,W,L] (channel last, hm[:, :, i]):
+ * out[r,c,i] = float32(exp(-((c - x0)**2 + (r - y0)**2) / two_sigma_sq)), evaluated in float64 in that order;
+ * two_sigma_sq is the caller's `2 * sigma**2`.  A keypoint equal to (-1,-1) gives an all-zero map.  x runs along
+ * the width (the reference passes (height, width) into gaussian_k's (width, height) slots, :293, so it only runs
+ * on square maps, where the two agree).  out_dev must be 16-byte aligned. */
+int flm_gaussian_heatmaps(flm_stream_t stream, const double* kp_dev, int n, int l, int h, int w, double two_sigma_sq,
+                          float* out_dev);
+
 /* ---- alignment (no reference implementation: README.md:1 states the intent only) --
  * Least-squares similarity (Umeyama, 4 dof) mapping each face's K landmarks onto a
  * template, returned as the 2x3 matrix M that maps SOURCE pixel coords to ALIGNED
