@@ -31,6 +31,7 @@ EXPORTS = [
     "flm_decode_workspace_bytes", "flm_decode", "flm_decode_sweep_workspace_bytes", "flm_decode_sweep",
     "flm_gaussian_heatmaps",
     "flm_similarity_from_landmarks", "flm_similarity_from_landmarks_scaled", "flm_warp_affine", "flm_crop_resize", "flm_crop_resize_frames",
+    "flm_landmarks_to_frame", "flm_warp_affine_frames",
 ]
 
 
@@ -157,6 +158,10 @@ def _declare(lib):
     lib.flm_crop_resize.argtypes = [vp, vp, i, i, vp, i, vp, i, i]
     lib.flm_crop_resize_frames.restype = i
     lib.flm_crop_resize_frames.argtypes = [vp, vp, C.c_size_t, i, i, i, vp, vp, i, vp, i, i]
+    lib.flm_landmarks_to_frame.restype = i
+    lib.flm_landmarks_to_frame.argtypes = [vp, vp, vp, i, i, i, i, i, i, vp]
+    lib.flm_warp_affine_frames.restype = i
+    lib.flm_warp_affine_frames.argtypes = [vp, vp, C.c_size_t, i, i, i, vp, vp, vp, i, vp, i, i, i]
 
 
 def load():

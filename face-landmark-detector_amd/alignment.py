@@ -82,3 +82,75 @@ def align_device(crops, landmarks_in, template, out_h, out_w, landmark_scale=(1.
     """crops [N,H,W,3] + landmarks (crop pixel units after `landmark_scale`) -> aligned crops, M."""
     m = similarity_device(landmarks_in, template, landmark_scale)
     return warp_device(crops, m, out_h, out_w), m
+
+
+def _check_boxes(boxes_dev, k):
+    import torch
+    if (not isinstance(boxes_dev, torch.Tensor) or boxes_dev.dtype != torch.int32 or not boxes_dev.is_cuda
+            or not boxes_dev.is_contiguous() or tuple(boxes_dev.shape) != (k, 4)):
+        raise ValueError("boxes_dev must be a contiguous CUDA int32 [%d,4] tensor" % k)
+
+
+def landmarks_to_frame_device(lm, boxes_dev, grid_hw, frame_hw, out=None):
+    """lm: CUDA float64 [K,C,2] in output-grid pixels; boxes_dev: CUDA int32 [K,4] (the squared boxes the crops were
+    cut from) -> CUDA float64 [K,C,2] in frame pixels (flm_landmarks_to_frame: the box clipped to the frame as the crop
+    kernel clips it, then x0 + x * (w / grid_w) in float64; rejected points and faces without pixels stay (-1,-1)).
+    `out` may be `lm` itself."""
+    import torch
+    if not isinstance(lm, torch.Tensor) or lm.dtype != torch.float64 or lm.dim() != 3 or lm.shape[2] != 2 or not lm.is_cuda:
+        raise ValueError("lm must be a CUDA float64 [K,C,2] tensor")
+    k, c = int(lm.shape[0]), int(lm.shape[1])
+    _check_boxes(boxes_dev, k)
+    gh, gw = [int(v) for v in grid_hw]
+    fh, fw = [int(v) for v in frame_hw]
+    if min(gh, gw, fh, fw) < 1:
+        raise ValueError("grid_hw and frame_hw must be positive")
+    if out is None:
+        out = torch.empty_like(lm, memory_format=torch.contiguous_format)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != (k, c, 2)
+          or not out.is_cuda or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous CUDA float64 [%d,%d,2] tensor" % (k, c))
+    if k and c:
+        lib = _lib.load()
+        _lib.check(lib.flm_landmarks_to_frame(_lib.stream_ptr(), _lib.ptr(lm.contiguous()), _lib.ptr(boxes_dev), k, c,
+                                              gh, gw, fh, fw, _lib.ptr(out)), "flm_landmarks_to_frame")
+    return out
+
+
+def warp_frames_device(frames, m, out_h, out_w, frame_index_dev=None, boxes_dev=None, samples=1, out=None):
+    """frames: contiguous CUDA uint8 [F,H,W,3] ring; m: CUDA float32 [K,2,3] (FRAME pixels -> aligned pixels);
+    frame_index_dev: CUDA int32 [K] ring slot of every face (default: slot 0); boxes_dev: CUDA int32 [K,4], faces whose
+    clipped box is empty come back as zeros; samples: 1, 2 or 4 bilinear samples per axis and output pixel
+    -> CUDA float32 [K,out_h,out_w,3] (flm_warp_affine_frames)."""
+    import torch
+    if (not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8
+            or not frames.is_cuda or not frames.is_contiguous()):
+        raise ValueError("frames must be a contiguous CUDA uint8 [F,H,W,3] tensor")
+    if not isinstance(m, torch.Tensor) or m.dtype != torch.float32 or m.dim() != 3 or tuple(m.shape[1:]) != (2, 3) or not m.is_cuda:
+        raise ValueError("m must be a CUDA float32 [K,2,3] tensor")
+    if samples not in (1, 2, 4):
+        raise ValueError("samples must be 1, 2 or 4")
+    out_h, out_w = int(out_h), int(out_w)
+    if out_h < 1 or out_w < 1:
+        raise ValueError("out_h and out_w must be positive")
+    k = int(m.shape[0])
+    nf, fh, fw = [int(v) for v in frames.shape[:3]]
+    if frame_index_dev is not None and (not isinstance(frame_index_dev, torch.Tensor) or frame_index_dev.dtype != torch.int32
+                                        or not frame_index_dev.is_cuda or not frame_index_dev.is_contiguous()
+                                        or tuple(frame_index_dev.shape) != (k,)):
+        raise ValueError("frame_index_dev must be a contiguous CUDA int32 [%d] tensor" % k)
+    if boxes_dev is not None:
+        _check_boxes(boxes_dev, k)
+    if out is None:
+        out = torch.empty((k, out_h, out_w, 3), dtype=torch.float32, device=frames.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (k, out_h, out_w, 3)
+          or not out.is_cuda or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous CUDA float32 [%d,%d,%d,3] tensor" % (k, out_h, out_w))
+    if k:
+        lib = _lib.load()
+        _lib.check(lib.flm_warp_affine_frames(_lib.stream_ptr(), _lib.ptr(frames), fh * fw * 3, nf, fh, fw,
+                                              None if frame_index_dev is None else _lib.ptr(frame_index_dev),
+                                              None if boxes_dev is None else _lib.ptr(boxes_dev),
+                                              _lib.ptr(m.contiguous()), k, _lib.ptr(out), out_h, out_w, int(samples)),
+                   "flm_warp_affine_frames")
+    return out

@@ -31,6 +31,7 @@ SOURCES = [
     "flm_up3_wreg.hip",
     "flm_decode.hip",
     "flm_misc.hip",
+    "flm_frames.hip",
     "flm_mobile.hip",
 ]
 # -ffp-contract=off: only the fma() calls written in the sources fuse, so the arithmetic of the

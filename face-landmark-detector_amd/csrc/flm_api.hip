@@ -865,4 +865,24 @@ int flm_crop_resize_frames(flm_stream_t stream, const uint8_t* frames, size_t fr
                             frame_stride, nframes);
 }
 
+int flm_landmarks_to_frame(flm_stream_t stream, const double* lm, const int32_t* boxes, int k, int c, int grid_h,
+                           int grid_w, int fh, int fw, double* out) {
+  if (!lm || !boxes || !out) {
+    set_error("flm_landmarks_to_frame: null argument");
+    return FLM_ERR_ARG;
+  }
+  return launch_landmarks_to_frame(static_cast<hipStream_t>(stream), lm, boxes, k, c, grid_h, grid_w, fh, fw, out);
+}
+
+int flm_warp_affine_frames(flm_stream_t stream, const uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
+                           const int32_t* frame_idx, const int32_t* boxes, const float* m, int k, float* dst, int hd,
+                           int wd, int samples) {
+  if (!frames || !m || !dst) {  // frame_idx and boxes are optional
+    set_error("flm_warp_affine_frames: null argument");
+    return FLM_ERR_ARG;
+  }
+  return launch_warp_frames(static_cast<hipStream_t>(stream), frames, frame_stride, nframes, fh, fw, frame_idx, boxes, m,
+                            k, dst, hd, wd, samples);
+}
+
 }  // extern "C"

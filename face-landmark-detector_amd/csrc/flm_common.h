@@ -251,6 +251,12 @@ int launch_warp(hipStream_t s, const void* src, int src_is_u8, int n, int hs, in
 int launch_crop_resize(hipStream_t s, const uint8_t* frame, int fh, int fw, const int32_t* boxes, int k,
                        uint8_t* out, int oh, int ow, const int32_t* frame_idx = nullptr, size_t frame_stride = 0,
                        int nframes = 0);
+// frame-space tail (flm_frames.hip)
+int launch_landmarks_to_frame(hipStream_t s, const double* lm, const int32_t* boxes, int k, int c, int grid_h,
+                              int grid_w, int fh, int fw, double* out);
+int launch_warp_frames(hipStream_t s, const uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
+                       const int32_t* frame_idx, const int32_t* boxes, const float* m, int k, float* dst, int hd,
+                       int wd, int samples);
 
 // Bijective XCD-aware remap of a 1-D grid: blocks that the dispatcher deals to the same XCD
 // (b % 8) receive consecutive logical ids, so neighbours in logical order share an L2.

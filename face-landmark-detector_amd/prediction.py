@@ -224,13 +224,16 @@ def crop_faces_device(frame, boxes, out_h, out_w, out=None, boxes_dev=None):
     return out
 
 
-def crop_frames_device(frames, faces_per_frame, out_h, out_w, frame_index=None):
+def crop_frames_device(frames, faces_per_frame, out_h, out_w, frame_index=None, return_device=False):
     """The faces of several frames as ONE batch: faces_per_frame: per frame a list of detector boxes (x0,y0,x1,y1) ->
     (CUDA uint8 [K_total,out_h,out_w,3], squared boxes per frame).  One upload of all boxes; no per-frame allocation,
     no concatenation: the shape a multi-face stream feeds the landmark model with (prediction.py:99-113 loops per face).
     frames: either a list of CUDA uint8 [H,W,3] tensors (one crop / resize launch per frame straight into its slice of
     the batch) or ONE CUDA uint8 [F,H,W,3] tensor -- a ring of stream frames in one allocation -- with `frame_index`
-    naming the ring slot of every entry of faces_per_frame (default 0, 1, ...): then all faces are cut in one launch."""
+    naming the ring slot of every entry of faces_per_frame (default 0, 1, ...): then all faces are cut in one launch.
+    `return_device=True` also returns the CUDA int32 tensors of the squared boxes [K_total,4] and of every face's frame
+    (ring slot, or position in the list) [K_total], views of the one upload: what the frame-space tail
+    (`align_frames`) reads."""
     import torch
     boxes = [face_boxes(f) for f in faces_per_frame]
     total = sum(len(b) for b in boxes)
@@ -241,6 +244,9 @@ def crop_frames_device(frames, faces_per_frame, out_h, out_w, frame_index=None):
     dev = frames.device if ring else (frames[0].device if len(frames) else _lib.require_gpu())
     out = torch.empty((total, out_h, out_w, 3), dtype=torch.uint8, device=dev)
     if total == 0:
+        if return_device:
+            return (out, boxes, torch.empty((0, 4), dtype=torch.int32, device=dev),
+                    torch.empty((0,), dtype=torch.int32, device=dev))
         return out, boxes
     flat = np.concatenate([np.asarray(b, np.int32).reshape(len(b), 4) for b in boxes if len(b)], 0)
     if ring:
@@ -254,14 +260,90 @@ def crop_frames_device(frames, faces_per_frame, out_h, out_w, frame_index=None):
         _lib.check(lib.flm_crop_resize_frames(_lib.stream_ptr(), _lib.ptr(frames), fh * fw * 3, int(frames.shape[0]), fh, fw,
                                               _lib.ptr(both), _lib.ptr(both[4 * total:]), total, _lib.ptr(out), out_h, out_w),
                    "flm_crop_resize_frames")
+        if return_device:
+            return out, boxes, both[:4 * total].view(total, 4), both[4 * total:]
         return out, boxes
-    bdev = torch.from_numpy(flat).to(dev)
+    if return_device:
+        idx = np.concatenate([np.full(len(b), v, np.int32) for v, b in enumerate(boxes) if len(b)])
+        both = torch.from_numpy(np.concatenate([flat.reshape(-1), idx])).to(dev)   # one upload: boxes, then frames
+        bdev = both[:4 * total].view(total, 4)
+    else:
+        bdev = torch.from_numpy(flat).to(dev)
     o = 0
     for frame, b in zip(frames, boxes):
         if len(b):
             crop_faces_device(frame, None, out_h, out_w, out=out[o:o + len(b)], boxes_dev=bdev[o:o + len(b)])
             o += len(b)
+    if return_device:
+        return out, boxes, bdev, both[4 * total:]
     return out, boxes
+
+
+_TEMPLATES = {}   # (landmarks, out_h, out_w, device) -> canonical template on the device, uploaded once
+
+
+def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 112), n_points=4, thresh=0.0,
+                 frame_index=None, samples=1):
+    """The multi-face stream end to end in FRAME coordinates: detector boxes of a group of frames -> aligned faces
+    sampled from the frames themselves.
+
+    frames: the CUDA uint8 [F,H,W,3] ring (or a list of same-size CUDA uint8 [H,W,3] frames, stacked once);
+    faces_per_frame: per entry a list of detector boxes (x0,y0,x1,y1); `frame_index` names the ring slot of every entry
+    (default 0, 1, ...).  Sequence: crop_frames_device -> model.forward_device(crops, "landmarks") ->
+    alignment.landmarks_to_frame_device -> alignment.similarity_device -> alignment.warp_frames_device: one upload (the
+    boxes), no download, no host synchronisation.  `template` float64 [C,2] in aligned pixels (numpy or CUDA; default
+    `alignment.canonical_template`); `samples` 1, 2 or 4 bilinear samples per axis and aligned pixel (for faces much
+    larger than out_size).
+    Returns CUDA tensors (aligned float32 [K,oh,ow,3], M float32 [K,2,3] frame px -> aligned px, landmarks float64
+    [K,C,2] in frame px with (-1,-1) for rejected points, squared boxes int32 [K,4]); K == 0 launches nothing."""
+    import torch
+    if isinstance(frames, (list, tuple)):
+        if not len(frames) or any(not isinstance(f, torch.Tensor) or f.dim() != 3 or f.dtype != torch.uint8
+                                  or tuple(f.shape) != tuple(frames[0].shape) for f in frames):
+            raise ValueError("frames must be a non-empty list of same-size uint8 [H,W,3] tensors")
+        frames = torch.stack(list(frames), 0)
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.dtype != torch.uint8 or frames.shape[3] != 3:
+        raise ValueError("frames must be one uint8 [F,H,W,3] tensor or a list of uint8 [H,W,3] tensors")
+    nf, fh, fw = [int(v) for v in frames.shape[:3]]
+    if fw < 2 or fh < 1 or fh * fw * 3 >= 2 ** 31:
+        raise ValueError("frames of %dx%d are outside the warp's reach (width >= 2, H*W*3 < 2^31)" % (fh, fw))
+    slots = list(range(len(faces_per_frame))) if frame_index is None else [int(v) for v in frame_index]
+    if len(slots) != len(faces_per_frame) or any(not (0 <= v < nf) for v in slots):
+        raise ValueError("frame_index must name a ring slot in [0, %d) for every entry of faces_per_frame" % nf)
+    if samples not in (1, 2, 4):
+        raise ValueError("samples must be 1, 2 or 4")
+    oh, ow = [int(v) for v in out_size]
+    if oh < 1 or ow < 1:
+        raise ValueError("out_size must be positive")
+    if not frames.is_cuda:
+        raise ValueError("frames must live on the GPU")
+    frames = frames.contiguous()
+    dev = frames.device
+    c = int(model.n_classes)
+    crops, _, boxes_dev, idx_dev = crop_frames_device(frames, faces_per_frame, model.input_height, model.input_width,
+                                                      frame_index=slots, return_device=True)
+    k = int(crops.shape[0])
+    if k == 0:
+        return (torch.empty((0, oh, ow, 3), dtype=torch.float32, device=dev),
+                torch.empty((0, 2, 3), dtype=torch.float32, device=dev),
+                torch.empty((0, c, 2), dtype=torch.float64, device=dev), boxes_dev)
+    if template is None:
+        key = (c, oh, ow, str(dev))
+        if key not in _TEMPLATES:
+            _TEMPLATES[key] = torch.from_numpy(alignment.canonical_template(c, oh, ow)).to(dev)
+        tmd = _TEMPLATES[key]
+    elif isinstance(template, torch.Tensor):
+        tmd = template.to(device=dev, dtype=torch.float64)
+    else:
+        tmd = torch.from_numpy(np.ascontiguousarray(np.asarray(template, np.float64))).to(dev)
+    if tuple(tmd.shape) != (c, 2):
+        raise ValueError("template must be [%d,2]" % c)
+    lm = model.forward_device(crops, "landmarks", n_points=n_points, thresh=thresh)
+    lm = alignment.landmarks_to_frame_device(lm, boxes_dev, (model.output_height, model.output_width), (fh, fw))
+    m = alignment.similarity_device(lm, tmd)
+    aligned = alignment.warp_frames_device(frames, m, oh, ow, frame_index_dev=idx_dev, boxes_dev=boxes_dev,
+                                           samples=samples)
+    return aligned, m, lm, boxes_dev
 
 
 def detect_marks_batch(img, model, faces, n_points=4, thresh=0.0):

@@ -341,6 +341,44 @@ int flm_crop_resize_frames(flm_stream_t stream, const uint8_t* frames_dev, size_
                            const int32_t* boxes_dev /*[K,4]*/, const int32_t* frame_idx_dev /*[K]*/, int k,
                            uint8_t* out_dev, int out_h, int out_w);
 
+/* ---- frame-space tail of the multi-face stream ----------------------------------------------------------
+ * The stream pipeline crops faces out of a ring of frames (flm_crop_resize_frames) and decodes landmarks on the
+ * model's output grid.  These two calls finish it in FRAME coordinates: the landmarks of every face in pixels of its
+ * frame, and the aligned face sampled from the frame itself -- one bilinear resampling of the original pixels instead
+ * of the crop's resize followed by a warp, and real frame pixels where the rotated aligned square leaves the box.
+ * flm_similarity_from_landmarks on the frame-space landmarks gives the M (frame px -> aligned px) the warp takes.
+ *
+ * flm_landmarks_to_frame: lm_dev float64 [K,C,2] (x,y) in output-grid pixels -> out_dev float64 [K,C,2] in frame
+ * pixels (out_dev may equal lm_dev).  Per face the box (x0,y0,x1,y1) is clipped to the frame exactly as
+ * flm_crop_resize clips it: cx0 = min(max(x0,0),fw), cx1 = min(max(x1,0),fw), cw = cx1-cx0 (same for y with fh).
+ * Then, in float64 and in this order,
+ *   xf = (double)cx0 + x * ((double)cw / grid_w);   yf = (double)cy0 + y * ((double)ch / grid_h)
+ * -- the pure-scale convention of the reference's back-projection (prediction.py:91-94) before its float32 rounding
+ * and truncation, on the region that was actually cropped.  A point the decode rejected (either coordinate negative)
+ * stays (-1,-1); a face whose clipped box is empty gets (-1,-1) everywhere.
+ * Errors: null pointer -> FLM_ERR_ARG; k, c, grid_h, grid_w, fh or fw below 1 -> FLM_ERR_SHAPE. */
+int flm_landmarks_to_frame(flm_stream_t stream, const double* lm_dev /*[K,C,2] output-grid px*/,
+                           const int32_t* boxes_dev /*[K,4]*/, int k, int c, int grid_h, int grid_w, int fh, int fw,
+                           double* out_dev /*[K,C,2]*/);
+/* flm_warp_affine_frames: the alignment warp with a per-face source frame.  The source of face f is frame
+ * frame_idx_dev[f] of the ring (frames_dev + idx*frame_stride, uint8 BGR fh x fw: the layout flm_crop_resize_frames
+ * reads; frame_idx_dev NULL = frame 0 for every face).  An index outside [0, nframes) gives zeros; with boxes_dev
+ * given, a face whose clipped box is empty gives zeros too (it had no pixels to find landmarks in).
+ *   samples == 1: per output pixel the arithmetic of flm_warp_affine (csrc/flm_misc.hip states it operation by
+ *     operation: det, idet, the inverse, the two fmaf chains, clamp to [0,fw-1] x [0,fh-1], floor, the three fmafs
+ *     of the bilinear blend) with the frame as the source: the same bits as flm_warp_affine on that frame.
+ *   samples == 2 | 4: an s x s grid of such samples per output pixel, for faces that shrink on their way to the
+ *     aligned size.  Sub-sample (i,j), i the row, is taken at destination coordinates xd + (2j+1-s)/(2s),
+ *     yd + (2i+1-s)/(2s) (float32 sums; the offsets are exact), the sample values are added in float32 in row-major
+ *     order starting from the first sample, and the sum is multiplied by 1/(s*s).
+ * Errors: null frames / m / dst, or any other `samples` -> FLM_ERR_ARG; FLM_ERR_SHAPE (the limit is named in
+ * flm_last_error()) unless 1 <= k <= 65535, nframes >= 1, fh >= 1, fw >= 2, fh*fw*3 < 2^31,
+ * frame_stride >= fh*fw*3, hd, wd >= 1 and hd*wd*12 < 2^31. */
+int flm_warp_affine_frames(flm_stream_t stream, const uint8_t* frames_dev, size_t frame_stride, int nframes, int fh,
+                           int fw, const int32_t* frame_idx_dev /*[K] or NULL = frame 0*/,
+                           const int32_t* boxes_dev /*[K,4] or NULL*/, const float* m_dev /*[K,2,3] frame px -> aligned px*/,
+                           int k, float* dst_dev /*[K,hd,wd,3]*/, int hd, int wd, int samples);
+
 #ifdef __cplusplus
 }
 #endif
