@@ -719,9 +719,9 @@ static int forward_impl(flm_stream_t stream, const void* packed_dev, const void*
   rc = launch_convt(s, t); }
   if (rc) return rc;
   ProfScope ps(s, gate ? "decode_fallback" : "decode");
-  return launch_decode(s, probs, n, W.oh, W.ow, C, C, decode_mode, n_points, thresh,
+  return launch_decode(s, probs, n, W.oh, W.ow, C, decode_mode, n_points, thresh,
                        static_cast<double*>(out_dev), ws + W.decode,
-                       decode_ws_bytes(n, W.oh, W.ow, C, decode_mode, n_points), nullptr, gate);
+                       decode_ws_bytes(n, W.oh, W.ow, C, decode_mode, n_points), gate);
 }
 
 int flm_fcn8_run_layer(flm_stream_t stream, const void* packed_dev, const char* layer, const void* x_dev,
@@ -792,8 +792,7 @@ int flm_decode(flm_stream_t stream, const float* hm, int n, int h, int w, int l,
     set_error("flm_decode: null argument");
     return FLM_ERR_ARG;
   }
-  return launch_decode(static_cast<hipStream_t>(stream), hm, n, h, w, l, l, mode, n_points, thresh, out, ws,
-                       ws_bytes);
+  return launch_decode(static_cast<hipStream_t>(stream), hm, n, h, w, l, mode, n_points, thresh, out, ws, ws_bytes);
 }
 
 size_t flm_decode_sweep_workspace_bytes(int n, int h, int w, int l, const int* modes, int n_modes) {

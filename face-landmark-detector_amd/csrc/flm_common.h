@@ -233,9 +233,8 @@ int launch_rn_conv1(hipStream_t s, const void* x, int in_format, int n, int h, i
 int launch_maxpool3(hipStream_t s, const void* x, int n, int h, int w, int c, void* y, int bf16);
 
 size_t decode_ws_bytes(int n, int h, int w, int l, int mode, int n_points);
-int launch_decode(hipStream_t s, const float* hm, int n, int h, int w, int l, int ld, int mode, int n_points,
-                  float thresh, double* out, void* ws, size_t ws_bytes, float* tau_out = nullptr,
-                  const unsigned* gate = nullptr);
+int launch_decode(hipStream_t s, const float* hm, int n, int h, int w, int l, int mode, int n_points, float thresh,
+                  double* out, void* ws, size_t ws_bytes, const unsigned* gate = nullptr);
 size_t decode_sweep_ws_bytes(int n, int h, int w, int l, const int* modes, int n_modes);
 int launch_decode_sweep(hipStream_t s, const float* hm, int n, int h, int w, int l, const int* modes, int n_modes,
                         float thresh, double* out, void* ws, size_t ws_bytes);

@@ -28,13 +28,13 @@
 //      phases is a fixed function of the tile index, spread over all 64: the phases are separate filters, so
 //      a sample from one phase alone is not representative of the map).  It writes no map either: every
 //      wave keeps the per-class maximum of its 16*NT pixels of every sampled phase (epilogue 4), and
-//      cand_tau_kernel (flm_decode.hip) takes tau[face][class] = the n-th largest of the face's 144..288 maxima.  Those
+//      cand_tau_kernel (flm_cand.hip) takes tau[face][class] = the n-th largest of the face's 144..288 maxima.  Those
 //      are values of n distinct pixels of the full map, so at least n pixels are >= tau and every member of
 //      the true top n is;
 //   2. the full launch keeps its probabilities in registers and appends (value, class, pixel) keys of the
 //      pixels with p >= tau (and p > 0: zero weights cannot move a centroid) to an LDS list -- about 64*n of
 //      the 69,696 pixels per class -- which the workgroup flushes to its face's list with one atomic;
-//   3. cand_merge_kernel (flm_decode.hip) selects the exact top n from the list, same keys and tie rule as
+//   3. cand_merge_kernel (flm_cand.hip) selects the exact top n from the list, same keys and tie rule as
 //      the decode of the materialised map.
 // A list that overflows (flat maps: everything ties with tau) raises a flag; the materialising launch and
 // the ordinary decode follow in the stream, gated on that flag, so the result is exact in every case.

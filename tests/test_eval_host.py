@@ -192,9 +192,20 @@ def test_sweep_and_gaussian_kernels_compile_without_scratch(tmp_path):
     text = open(out).read()
     kernels = {m.group(1): int(m.group(2)) for m in re.finditer(
         r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n", text)}
-    new = {k: v for k, v in kernels.items() if "decode_sweep" in k or "gaussian_hm" in k}
-    assert sum("decode_sweep_partial_kernel" in k for k in new) == 8      # CPW 17|24 x one|two list registers x all-pixel
-    assert sum("decode_sweep_partial_dma_kernel" in k for k in new) == 2
-    assert sum("decode_sweep_merge_kernel" in k for k in new) == 2
-    assert sum("gaussian_hm_kernel" in k for k in new) == 1
-    assert all(v == 0 for v in new.values()), new
+    # every instantiation launch_decode and launch_decode_sweep can launch, by its (Itanium-mangled) name
+    def kernel(name, *targs):      # flm::name<targs...>(flm::DecodeArgs); a template's name carries its return type (v)
+        args = "I%sEEv" % "".join("Li%dE" % a if type(a) is int else "Lb%dE" % a for a in targs) if targs else "E"
+        return "_ZN3flm%d%s%sNS_10DecodeArgsE" % (len(name), name, args)
+    tf = (False, True)
+    expected = {kernel("decode_partial_kernel", cpw, wide, sums)               # top-n family, register prefetch:
+                for cpw in (17, 24) for wide in tf for sums in tf}              # CPW x one|two list registers x all-pixel sums
+    expected |= {kernel("decode_partial_dma_kernel", sums) for sums in tf}     # top-n family, LDS-DMA ring
+    expected |= {kernel("decode_merge_kernel", wide) for wide in tf}           # flm_decode top-n: one mode
+    expected |= {kernel("decode_merge_modes_kernel", wide) for wide in tf}     # flm_decode_sweep: the mode loop
+    expected |= {kernel("decode_partial_all_kernel", 17), kernel("decode_partial_all_kernel", 24),   # flm_decode, all pixels
+                 kernel("decode_partial_all_dma_kernel"), kernel("decode_merge_all_kernel")}
+    decode = {k for k in kernels if "decode_" in k}
+    assert decode == expected, (sorted(decode - expected), sorted(expected - decode))
+    assert sum("gaussian_hm_kernel" in k for k in kernels) == 1
+    new = {k: v for k, v in kernels.items() if "decode_" in k or "gaussian_hm" in k}
+    assert len(new) == 19 and all(v == 0 for v in new.values()), new
