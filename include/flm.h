@@ -205,8 +205,16 @@ int64_t flm_fcn8_workspace_offset_opts(const char* name, int n, int h, int w, in
                                        int out_mode, int decode_mode, int n_points, const flm_forward_opts* opts);
 
 /* One named Conv2D layer of the model in isolation ("enc2".."enc5" with BN+ReLU+pool fused,
- * "fc6", "fc7", "score5", "score4", "score3"): x_dev float32 [n,h,w,Cin] -> y_dev.  For tests and
- * developer tools that run or time one layer in isolation. */
+ * "fc6", "fc7", "score5", "score4", "score3"), exactly the launch the forward makes for it except that no
+ * split-K scratch is passed (the layer never splits K here).  For tests and developer tools that run or time one layer.
+ * Types follow the forward's own intermediates -- the call converts nothing:
+ *   FLM_F32:  x_dev float32 [n,h,w,Cin] -> y_dev float32 [n,ho,wo,Cout]
+ *   FLM_BF16: x_dev bfloat16 [n,h,w,Cin] (what the previous layer stored) -> y_dev bfloat16 [n,ho,wo,Cout] for
+ *             "enc2".."enc5", "fc6", "fc7"; float32 for "score5", "score4", "score3"
+ * ho x wo = h x w (h/2 x w/2 for the pooled "enc" layers).  Cout of the score layers is the padded class count of the
+ * configuration (n_classes = 68: 68 in FLM_F32, 72 in FLM_BF16; otherwise 16 * ceil(n_classes / 16)); the columns from
+ * n_classes on are written as exact zeros.  tests/test_gpu_bf16_layers.py holds fc6, fc7 and the score layers to an
+ * integer reference bit for bit in both types. */
 int flm_fcn8_run_layer(flm_stream_t stream, const void* packed_dev, const char* layer, const void* x_dev,
                        void* y_dev, int n, int h, int w, int n_classes, int dtype);
 

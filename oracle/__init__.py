@@ -16,6 +16,11 @@ Parity pin status (details in DESIGN.md):
   tests, fixtures or golden outputs.  The restatement follows the cited source
   lines plus documented Keras layer defaults and is cross-checked against an
   independent naive-loop restatement (``tests/test_oracle_fcn.py``).
+* ``fcn_bf16_ref`` -- the same graphs in float64 with bfloat16 roundings at the points
+  where the bf16 kernels round (each cited from the kernel source): the reference
+  has no bf16 arithmetic, so this pins the BUILD's bf16 configuration, not parity.
+  With rounding off it is ``fcn_ref`` in float64 bit for bit
+  (``tests/test_oracle_fcn_bf16.py``).
 * ``warp_ref``    -- PARITY UNPINNED against the reference (it has no alignment
   code at all); cross-checked against scikit-image 0.18.3, the library the
   reference's only affine warp calls (``data/generator.py:192-200``).

@@ -1,0 +1,68 @@
+"""Teacher-forced layer checks of the bf16 configuration (vanilla fcn_8), shared by the GPU test modules.
+
+Every layer is handed the DEVICE's own input, read back exactly through model.intermediate, and its device output is
+held against the float64 evaluation of that input by oracle/fcn_bf16_ref.py:
+
+  bf16-stored (f1..f5, fc6, fc7):            |got - exact64| <= ulp_bf16(exact64) / 2 + slack * max|exact64|
+  fp32-stored (score5, fuse4, seg_feats,
+               logits):                      |got - exact64| <=                        slack * max|exact64|
+  flips (bf16-stored):  elements with got != round_bf16(exact64)  <=  max(4 x the float32 evaluation's, 8)
+
+slack is measured on the reference side, per layer and input: 4 x the largest error of torch's float32 evaluation of
+the same rounded operands against float64, capped at the fp32 suite's 2e-5 (never below one float32 step, 2^-23).
+"""
+import numpy as np
+import torch
+
+from oracle import fcn_bf16_ref as B
+from oracle import fcn_ref
+
+STORED_BF16 = ("f1", "f2", "f3", "f4", "f5", "fc6", "fc7")
+CHAIN = (("f1", "enc1", ("x",)), ("f2", "enc2", ("f1",)), ("f3", "enc3", ("f2",)), ("f4", "enc4", ("f3",)),
+         ("f5", "enc5", ("f4",)), ("fc6", "fc6", ("f5",)), ("fc7", "fc7", ("fc6",)), ("score5", "score5", ("fc7",)),
+         ("fuse4", "fuse4", ("score5", "f4")), ("seg_feats", "seg_feats", ("fuse4", "f3")))
+
+
+def check_layers(model, params, crops_u8, n, out, faces=None, logits=None, probs=None, label=""):
+    """Gate every layer of the last forward (n faces, output mode `out`) on `faces` (default: all).  `logits` / `probs`:
+    device outputs of forwards of the SAME faces (numpy, [F,H',W',C] / [F,H'*W',C]) whose workspaces hold the seg_feats
+    they were computed from.  Prints one line per layer, then asserts.  Returns {name: report}."""
+    c = model.n_classes
+    faces = list(range(n)) if faces is None else list(faces)
+    dev = {"x": np.stack([fcn_ref.get_image_array_ref(crops_u8[f]) for f in faces])}
+    for name, _, _ in CHAIN:
+        dev[name] = model.intermediate(name, n, out)[faces].cpu().numpy().astype(np.float64)
+    reports, bad = {}, []
+
+    def gate(name, layer, xin, got):
+        exact, _ = B.layer_bf16_ref(layer, xin, params)
+        e32, s32 = B.layer_bf16_ref(layer, xin, params, accum=torch.float32)
+        rep = B.layer_report(got[..., : exact.shape[-1]], exact, e32, s32, name in STORED_BF16)
+        if got.shape[-1] > exact.shape[-1] and np.any(got[..., exact.shape[-1]:] != 0):   # class pad columns 68..71
+            rep["ok"] = False
+            rep["pad"] = float(np.abs(got[..., exact.shape[-1]:]).max())
+        print("%s %s" % (label, B.format_report(name, rep)) + (" pad columns not zero: %g" % rep["pad"] if "pad" in rep else ""))
+        reports[name] = rep
+        if not rep["ok"]:
+            bad.append(name)
+        return exact
+
+    for name, layer, srcs in CHAIN:
+        xin = dev[srcs[0]] if len(srcs) == 1 else tuple(dev[s] for s in srcs)
+        gate(name, layer, xin, dev[name])
+    for what, arr, mode in (("logits", logits, "logits"), ("probs", probs, "probs")):
+        if arr is None:
+            continue
+        seg = model.intermediate("seg_feats", len(faces) if mode != out else n, mode)
+        seg = (seg[faces] if mode == out else seg).cpu().numpy().astype(np.float64)
+        if what == "logits":
+            gate("logits", "logits", seg, np.asarray(arr, np.float64))
+        else:   # the fp32 suite's bar, against the softmax of the oracle's logits FROM THE DEVICE'S seg_feats
+            exp = B.softmax_ref(B.layer_bf16_ref("logits", seg, params)[0])
+            d = float(np.abs(arr - exp).max())
+            print("%s probs     max-abs error %.3g (bar 1e-5), rows sum to 1 within %.3g" % (label, d, np.abs(arr.sum(-1) - 1).max()))
+            reports["probs"] = dict(err=d, ok=d <= 1e-5)
+            if d > 1e-5:
+                bad.append("probs")
+    assert not bad, (label, {k: reports[k] for k in bad})
+    return reports
