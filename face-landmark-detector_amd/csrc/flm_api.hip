@@ -235,6 +235,10 @@ int flm_set_tuning(const char* key, int value) {
     flm::igemm_f32_group(value ? 0 : -1);
     return FLM_OK;
   }
+  if (!strcmp(key, "f32_lean_tile")) {  // fp32 implicit GEMMs (row-major and pooled): lean set-up and write-out (1) or the plain ones (0)
+    flm::igemm_f32_lean_enable(value);
+    return FLM_OK;
+  }
   if (!strcmp(key, "bf16_mfma16")) {  // 256x256 LDS-DMA tiles on v_mfma_f32_16x16x32_bf16 (1) or 32x32x16 (0)
     flm::igemm_bf16_big_m16(value);
     return FLM_OK;

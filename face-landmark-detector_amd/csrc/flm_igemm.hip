@@ -32,6 +32,7 @@
 //      every workgroup ranks the tiles by tap count (a few hundred integer ops); the bf16 / single-chain form runs
 //      the i-th heaviest and the i-th lightest back to back, the fp32 parity form (TWO) one tile per workgroup,
 //      handed out longest-first inside each XCD's share of the grid -- either way the generations end together.
+#include <type_traits>
 #include <vector>
 
 #include "flm_igemm_args.h"
@@ -40,7 +41,9 @@
 // 4 no vmcnt wait before the step's barrier, 8 no LDS-DMA requests in the k-loop, 16 no barrier (4 / 8 / 16: timing
 // ablations, results wrong), 1 no third accumulation level, 2 two fragment address registers + one v_xor per read instead of eight registers
 // (chunk (2t + lh) ^ swx = ((lh ^ swx) ^ 2t): group t's address is group 0's with bits 5-6 flipped; frees six registers,
-// costs 1.5 % of a layer).
+// costs 1.5 % of a layer).  Per-tile cost (timing only, results wrong; profiles/igemm_tile_cost.json): 32 the workgroup returns
+// after the k-loop and its closing sums, no write-out; 64 the LEAN = false set-up takes its rows apart with shifts and
+// assumes every tap in bounds -- no division, no tap-mask loop.
 #ifndef FLM_IGEMM_VAR
 #define FLM_IGEMM_VAR 0
 #endif
@@ -79,9 +82,18 @@ __device__ __forceinline__ void mfma_slot(const float4& a0, const float4& a1, co
   }
 }
 
-template <bool BF, int MMAP, bool RELU, bool TWO = false>
+// LEAN (fp32 TWO form, MMAP 0 / 1; knob "f32_lean_tile"): the same tile with a shorter path into and out of the k-loop.
+//   set-up    rows are taken apart with the launcher's multiply-shift constants (no integer division); the tap mask is
+//             the full set where the launcher has proven that every tile sees every tap (IgemmArgs::all_taps: no ballot
+//             loop, no LDS round trip, no barrier); the operand requests of the first two stages are issued as soon as
+//             their addresses exist, and fragment offsets and the 192 accumulator clears run under their latency;
+//   write-out a full tile of an unsplit launch stores through one scalar base and 32-bit offsets with no per-element
+//             test, the residual variant chosen once; partial tiles and split-K slices take the guarded path below.
+// The k-loop, the summation tree and every arithmetic operation of the write-out are those of LEAN = false: same bits.
+template <bool BF, int MMAP, bool RELU, bool TWO = false, bool LEAN = false>
 __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
   static_assert(!TWO || !BF, "the multi-level accumulation is the fp32 (parity) form");
+  static_assert(!LEAN || (TWO && MMAP != 2), "the lean set-up / write-out is built for the fp32 form, row-major and quad order");
   constexpr int ES = BF ? 2 : 4;    // operand element size
   constexpr int EPC = 16 / ES;      // elements per 16-byte chunk
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -158,7 +170,21 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
     const int m = m0 + r0 + 32 * j;
     pv[j] = m < a.M;
     const int mm = pv[j] ? m : 0;
-    if (MMAP == 0) {  // (py, px) are INPUT coordinates of the filter centre: output pixel * stride
+    if constexpr (LEAN) {  // q / d as one v_mul_hi (igemm_fastdiv): dx, dy = (wo, ho) or the quad grid (w / 2, h / 2)
+      const int q = MMAP == 1 ? mm >> 2 : mm, d = mm & 3;
+      const int q1 = igemm_fastdiv(q, a.dx_magic, a.dx_shift), xq = q - q1 * a.dx;
+      const int q2 = igemm_fastdiv(q1, a.dy_magic, a.dy_shift), yq = q1 - q2 * a.dy;
+      px[j] = MMAP == 1 ? 2 * xq + (d & 1) : xq * a.stride;
+      py[j] = MMAP == 1 ? 2 * yq + (d >> 1) : yq * a.stride;
+      pn[j] = q2;
+    } else if ((FLM_IGEMM_VAR & 64) && MMAP != 2) {  // (timing only: right for power-of-two maps)
+      const int q = MMAP == 1 ? mm >> 2 : mm, d = mm & 3;
+      const int lw = __builtin_ctz(MMAP == 1 ? a.w >> 1 : a.wo), lh2 = __builtin_ctz(MMAP == 1 ? a.h >> 1 : a.ho);
+      const int xq = q & ((1 << lw) - 1), yq = (q >> lw) & ((1 << lh2) - 1);
+      px[j] = MMAP == 1 ? 2 * xq + (d & 1) : xq * a.stride;
+      py[j] = MMAP == 1 ? 2 * yq + (d >> 1) : yq * a.stride;
+      pn[j] = q >> (lw + lh2);
+    } else if (MMAP == 0) {  // (py, px) are INPUT coordinates of the filter centre: output pixel * stride
       px[j] = (mm % a.wo) * a.stride;
       py[j] = ((mm / a.wo) % a.ho) * a.stride;
       pn[j] = mm / (a.wo * a.ho);
@@ -180,6 +206,8 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
   unsigned long long tapmask;
   if (ntaps == 1) {
     tapmask = 1ull;
+  } else if ((LEAN && a.all_taps) || ((FLM_IGEMM_VAR & 64) && !LEAN && MMAP != 2)) {
+    tapmask = ntaps >= 64 ? ~0ull : (1ull << ntaps) - 1ull;
   } else {
     unsigned long long mymask = 0;
     for (int t = 0; t < ntaps; ++t) {
@@ -239,19 +267,24 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
 
   // fragment read offsets (floats): rows 64*wr + 32*i + lr of A, 64*wc + 32*j + lr of B; the XOR term of
   // the swizzle depends on lr only, the chunk is 2*t + lh
+  // (LEAN: behind the first two stages' requests, see FLM_FRAG_OFFSETS below)
   int fa0, fa1, fb0, fb1, fc0, fc1, fc2, fc3;
-  {
-    const int wr = wave >> 1, wc = wave & 1;
-    const int lr = lane & 31, lh = lane >> 5;
-    const int swx = (lr >> 1) & 7;
-    fa0 = (64 * wr + lr) * BK, fa1 = fa0 + 32 * BK;
-    fb0 = (64 * wc + lr) * BK, fb1 = fb0 + 32 * BK;
-    fc0 = ((0 + lh) ^ swx) << 2, fc1 = ((2 + lh) ^ swx) << 2, fc2 = ((4 + lh) ^ swx) << 2, fc3 = ((6 + lh) ^ swx) << 2;
+#define FLM_FRAG_OFFSETS()                                                                                              \
+  {                                                                                                                     \
+    const int wr = wave >> 1, wc = wave & 1;                                                                            \
+    const int lr = lane & 31, lh = lane >> 5;                                                                           \
+    const int swx = (lr >> 1) & 7;                                                                                      \
+    fa0 = (64 * wr + lr) * BK, fa1 = fa0 + 32 * BK;                                                                     \
+    fb0 = (64 * wc + lr) * BK, fb1 = fb0 + 32 * BK;                                                                     \
+    fc0 = ((0 + lh) ^ swx) << 2, fc1 = ((2 + lh) ^ swx) << 2, fc2 = ((4 + lh) ^ swx) << 2, fc3 = ((6 + lh) ^ swx) << 2; \
   }
+  if constexpr (!LEAN) FLM_FRAG_OFFSETS()
 
   f32x16 acc00, acc01, acc10, acc11;
+  if constexpr (!LEAN) {
 #pragma unroll
-  for (int r = 0; r < 16; ++r) acc00[r] = acc01[r] = acc10[r] = acc11[r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc00[r] = acc01[r] = acc10[r] = acc11[r] = 0.f;
+  }
 
   // ---- fp32 parity form: LDS-DMA operand ring + three-level accumulation -------------------------------------------
   // A v_mfma_f32_32x32x2_f32 stream is bit for bit ONE fmaf chain per output: K = 576 .. 12,544 sequential roundings,
@@ -275,11 +308,11 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
   if constexpr (TWO) {
     f32x16 sum00, sum01, sum10, sum11;   // second level: step sums of the current group
     f32x16 top00, top01, top10, top11;   // third level: group sums
-#pragma unroll
-    for (int r = 0; r < 16; ++r) sum00[r] = sum01[r] = sum10[r] = sum11[r] = top00[r] = top01[r] = top10[r] = top11[r] = 0.f;
     f32x16 zero16;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
+#define FLM_CLEAR_SETS()                                                                                                       \
+  _Pragma("unroll") for (int r = 0; r < 16; ++r)                                                                               \
+      sum00[r] = sum01[r] = sum10[r] = sum11[r] = top00[r] = top01[r] = top10[r] = top11[r] = zero16[r] = 0.f;
+    if constexpr (!LEAN) FLM_CLEAR_SETS()
 
     typedef __attribute__((address_space(3))) char lds_char;
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
@@ -294,7 +327,6 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
     int pyx[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) pyx[j] = ((pv[j] ? py[j] : 0x7000) << 16) | px[j];
-    const int off_a = (fa0 + fc0) * 4, off_b = (fb0 + fc0) * 4;  // byte offsets of k-group 0 in an A / B stage
 
     unsigned long long rem = rem0;
     int cur_chunk = chunk0 < a.cpt ? chunk0 : 0;
@@ -412,6 +444,14 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
       FLM_DMA_A(0, 1) FLM_DMA_A(1, 1) FLM_DMA_A(2, 1) FLM_DMA_A(3, 1)
       FLM_DMA_B(0, 1) FLM_DMA_B(1, 1) FLM_DMA_B(2, 1) FLM_DMA_B(3, 1)
     }
+    if constexpr (LEAN) {  // everything the requests did not need, under their latency
+      __builtin_amdgcn_sched_barrier(0);
+      FLM_FRAG_OFFSETS()
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc00[r] = acc01[r] = acc10[r] = acc11[r] = 0.f;
+      FLM_CLEAR_SETS()
+    }
+    const int off_a = (fa0 + fc0) * 4, off_b = (fb0 + fc0) * 4;  // byte offsets of k-group 0 in an A / B stage
     __builtin_amdgcn_s_waitcnt(0x0f70);
     __syncthreads();
     float4 afx0, afx1, bfx0, bfx1, afy0, afy1, bfy0, bfy1;
@@ -438,7 +478,13 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
 #undef FLM_SLOT_z
 #undef FLM_SLOT_w
 #undef FLM_STEP2
+#undef FLM_CLEAR_SETS
+    if (FLM_IGEMM_VAR & 32) {  // (timing only) the sums stay alive, nothing is written
+      asm volatile("" ::"v"(acc00), "v"(acc01), "v"(acc10), "v"(acc11));
+      return;
+    }
   }
+#undef FLM_FRAG_OFFSETS
 
   if constexpr (!TWO) {
   // ---- software pipeline ---------------------------------------------------------------------------
@@ -612,6 +658,62 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
   const int lane_e = TWO ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : lane;
   const int wave_e = TWO ? __builtin_amdgcn_readfirstlane(wave) : wave;
   const int wr = wave_e >> 1, wc = wave_e & 1, lr = lane_e & 31, lh = lane_e >> 5;
+  if constexpr (LEAN) {
+    // A whole tile of an unsplit launch (wave-uniform test): every row and column is stored, so the stores need no test;
+    // they go through one scalar base per tile plus a 32-bit lane offset (at most 128 rows of ldc floats), the row
+    // displacement of each store is a scalar.  Same operations in the same order as the guarded path below.
+    if (a.ksplit <= 1 && m0 + BM <= a.M && n0 + BN <= a.cout) {
+      const unsigned ldc = (unsigned)a.ldc;
+      float sc[2], sh[2];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        sc[j] = a.scale[n0 + 64 * wc + 32 * j + lr];
+        sh[j] = a.shift[n0 + 64 * wc + 32 * j + lr];
+      }
+      if constexpr (MMAP == 1) {
+        float* yt = reinterpret_cast<float*>(a.y) + ((size_t)(m0 >> 2) * ldc + n0);
+        const unsigned lane_off = (unsigned)(16 * wr + lh) * ldc + (unsigned)(64 * wc + lr);  // pooled row 16 wr + 8 i + 2 g + lh
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+              float v = -3.402823466e38f;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                float u = fmaf(acc[i][j][4 * g + e], sc[j], sh[j]);
+                if (RELU) u = fminf(fmaxf(u, 0.f), a.relu_max);
+                v = fmaxf(v, u);
+              }
+              float* yr = yt + ((unsigned)(8 * i + 2 * g) * ldc + 32u * j);
+              yr[lane_off] = v;
+            }
+      } else {
+        const size_t tile_off = (size_t)m0 * ldc + n0;
+        float* yt = reinterpret_cast<float*>(a.y) + tile_off;
+        const unsigned lane_off = (unsigned)(64 * wr + 4 * lh) * ldc + (unsigned)(64 * wc + lr);
+        auto store_tile = [&](auto with_res) {
+          const float* rt = reinterpret_cast<const float*>(a.res) + tile_off;
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) {
+                const unsigned row_off = (unsigned)(32 * i + (r & 3) + 8 * (r >> 2)) * ldc + 32u * j;
+                float u = fmaf(acc[i][j][r], sc[j], sh[j]);
+                if (decltype(with_res)::value) u += (rt + row_off)[lane_off];  // residual add before the activation
+                if (RELU) u = fminf(fmaxf(u, 0.f), a.relu_max);
+                (yt + row_off)[lane_off] = u;
+              }
+        };
+        if (a.res) store_tile(std::true_type());
+        else store_tile(std::false_type());
+      }
+      continue;  // (the one pass of this form)
+    }
+  }
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int col = n0 + 64 * wc + 32 * j + lr;
@@ -697,15 +799,20 @@ void posperm_cache_put(const PospermEntry& e) {
   if (g_posperm_cache.size() < 64) g_posperm_cache.push_back(e);
 }
 
-template <bool BF, int MMAP, bool RELU, bool TWO = false>
+// A/B knob "f32_lean_tile": the fp32 TWO form with the lean set-up and write-out (1, default) or without (0); same bits
+static std::atomic<int> g_f32_lean{1};
+void igemm_f32_lean_enable(int on) { g_f32_lean.store(on, std::memory_order_relaxed); }
+
+template <bool BF, int MMAP, bool RELU, bool TWO = false, bool LEAN = false>
 static int launch_t(hipStream_t s, const IgemmArgs& a_in) {
   IgemmArgs a = a_in;
   if (MMAP == 2) posmajor_fill_perm(a, BM);
+  if (LEAN) igemm_fill_lean(a, MMAP == 1, BM);
   const size_t lds = sizeof(float) * 4 * TILE_F + 64;
   static FuncAttrOnce attr;
-  FLM_FUNC_ATTR_ONCE(attr, (&igemm_kernel<BF, MMAP, RELU, TWO>), lds);
+  FLM_FUNC_ATTR_ONCE(attr, (&igemm_kernel<BF, MMAP, RELU, TWO, LEAN>), lds);
   const int mslots = (MMAP == 2 && !TWO) ? (a.mtiles + 1) / 2 : a.mtiles;
-  igemm_kernel<BF, MMAP, RELU, TWO><<<dim3(mslots * a.ntiles, a.ksplit > 1 ? a.ksplit : 1), 256, lds, s>>>(a);
+  igemm_kernel<BF, MMAP, RELU, TWO, LEAN><<<dim3(mslots * a.ntiles, a.ksplit > 1 ? a.ksplit : 1), 256, lds, s>>>(a);
   FLM_LAUNCH_CHECK("igemm_kernel");
   return FLM_OK;
 }
@@ -760,6 +867,12 @@ int igemm_occupancy(size_t lds_bytes) {
 
 template <bool BF, bool TWO = false>
 static int dispatch(hipStream_t s, const IgemmDesc& d, const IgemmArgs& a) {
+  if constexpr (TWO) {  // (position-major tiles keep their set-up: masks and ranking are what make fc6's tiles unequal)
+    if (!d.posmajor && g_f32_lean.load(std::memory_order_relaxed)) {
+      if (d.pool) return d.relu ? launch_t<BF, 1, true, TWO, true>(s, a) : launch_t<BF, 1, false, TWO, true>(s, a);
+      return d.relu ? launch_t<BF, 0, true, TWO, true>(s, a) : launch_t<BF, 0, false, TWO, true>(s, a);
+    }
+  }
   if (d.pool) return d.relu ? launch_t<BF, 1, true, TWO>(s, a) : launch_t<BF, 1, false, TWO>(s, a);
   if (d.posmajor) return d.relu ? launch_t<BF, 2, true, TWO>(s, a) : launch_t<BF, 2, false, TWO>(s, a);
   return d.relu ? launch_t<BF, 0, true, TWO>(s, a) : launch_t<BF, 0, false, TWO>(s, a);
@@ -822,6 +935,10 @@ int launch_igemm(hipStream_t s, const IgemmDesc& d) {
   a.grp_magic = 0;
   a.posperm_on = 0;
   for (int k = 0; k < 8; ++k) a.posperm[k] = 0ull;
+  a.dx = a.dy = 1;
+  a.dx_magic = a.dy_magic = 1u << 30;
+  a.dx_shift = a.dy_shift = 0;
+  a.all_taps = 0;
   a.part = nullptr;
   const int tiles = cdiv(a.M, BM) * cdiv(d.cout, BN);
   // The slice count is a step function of the tile count, the same for fc6 and fc7 (<= 64 tiles, i.e. up to 4

@@ -33,7 +33,54 @@ struct IgemmArgs {
   // of its positions' taps (posmajor_fill_perm below).  posperm_on == 0: places are positions.
   unsigned long long posperm[8];
   int posperm_on;
+  // Lean set-up of the fp32 kernel (igemm_fill_lean below): GEMM row -> (face, y, x) without integer division.
+  // dx, dy = the grid the rows walk (wo, ho; quad order: w / 2, h / 2), each with its multiply-shift pair for igemm_fastdiv.
+  int dx, dy;
+  unsigned dx_magic, dx_shift, dy_magic, dy_shift;
+  int all_taps;  // the launcher has proven that every tile has, for every filter tap, a pixel that sees it in bounds
 };
+
+// n / d for 0 <= n < 2^30 as one multiply-high: with l = ceil(log2 d) and magic = ceil(2^(30 + l) / d) (< 2^31),
+// floor(n * magic / 2^(30 + l)) == floor(n / d) for every n < 2^30 (Granlund & Montgomery 1994, theorem 4.2 with N = 30);
+// 4 n < 2^32, so the quotient is the high word of (4 n) * magic shifted right by l.  Powers of two get magic = 2^30: a shift.
+inline void igemm_fastdiv_make(int d, unsigned& magic, unsigned& shift) {
+  unsigned l = 0;
+  while ((1ull << l) < (unsigned long long)d) ++l;
+  magic = (unsigned)(((1ull << (30 + l)) + (unsigned long long)d - 1ull) / (unsigned long long)d);
+  shift = l;
+}
+__host__ __device__ __forceinline__ int igemm_fastdiv(int n, unsigned magic, unsigned shift) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (int)(__umulhi((unsigned)n << 2, magic) >> shift);
+#else  // (tests/native/igemm_lean_host.cpp)
+  return (int)((unsigned)(((unsigned long long)((unsigned)n << 2) * magic) >> 32) >> shift);
+#endif
+}
+
+// Host side of the lean set-up for a launch with bm rows per tile (launch_igemm has checked M <= 2^30).
+// all_taps -- every tile sees every tap, so the kernel takes the full mask without looking.  Write dy = ky - pad,
+// dx = kx - pad for a tap's displacement; pixel (y, x) of the output grid sees it when 0 <= y s + dy < h and
+// 0 <= x s + dx < w.  With pad <= s and kh, kw >= 2 pad + 1, a row y fails only as y = 0 for dy < 0 and as y = ho - 1
+// for dy > 0 ((ho - 2) s + kh - 1 - pad <= h - 1 + pad - s), never for dy = 0; columns alike.
+//   quad order (pooled layers, stride 1, h and w even): a tile is made of whole 2 x 2 quads {2a, 2a+1} x {2b, 2b+1} and
+//     holds at least one (M and the tile's first row are multiples of 4).  With pad <= 1 and kh - 1 - pad <= 1 (|dy| <= 1)
+//     row 2a+1 serves dy < 0 and row 2a serves dy > 0 (2a <= h - 2); columns alike, and the quad is their product.
+//   row-major: when every tile is full (M % bm == 0) and bm >= 3 wo - 1, a tile contains two complete consecutive rows
+//     of the (face, y) sequence: (y, y+1), or (ho-1, 0) across two faces.  With ho, wo >= 2 one of the two serves dy < 0
+//     (the one with y >= 1) and one dy > 0 (the one with y <= ho - 2); a complete row has x = 1 for dx < 0 and x = 0 for dx > 0.
+// Anything else (a tile inside the top row of a wide map, a partial last tile) keeps the kernel's ballot loop.
+inline void igemm_fill_lean(IgemmArgs& a, bool quads, int bm) {
+  a.dx = quads ? a.w >> 1 : a.wo;
+  a.dy = quads ? a.h >> 1 : a.ho;
+  igemm_fastdiv_make(a.dx, a.dx_magic, a.dx_shift);
+  igemm_fastdiv_make(a.dy, a.dy_magic, a.dy_shift);
+  const bool edge_only = a.pad <= a.stride && a.kh >= 2 * a.pad + 1 && a.kw >= 2 * a.pad + 1;
+  if (quads)
+    a.all_taps = edge_only && a.stride == 1 && a.pad <= 1 && a.kh - 1 - a.pad <= 1 && a.kw - 1 - a.pad <= 1 &&
+                 a.h >= 2 && a.w >= 2 && !(a.h & 1) && !(a.w & 1);
+  else
+    a.all_taps = edge_only && a.ho >= 2 && a.wo >= 2 && a.M % bm == 0 && bm >= 3 * a.wo - 1;
+}
 
 // place -> map position (see IgemmArgs::posperm).  The table sits in scalar registers: eight selects and a shift.
 __device__ __forceinline__ int posmajor_pos(const IgemmArgs& a, int place) {

@@ -242,6 +242,11 @@ int flm_profile_filter(const char* layer);
  *                           sums into a second accumulator set (chains of 32 + K/32 roundings, operands by LDS-DMA;
  *                           csrc/flm_igemm.hip); 0: one fmaf chain of K per output (round 2's kernel).  Both are valid
  *                           fp32 evaluations of the layer; the bits differ
+ *   "f32_lean_tile"         1 (default): the row-major and pooled layers of that kernel enter and leave the k-loop by a
+ *                           shorter path -- no integer division and, where the launcher proves every tap in bounds for
+ *                           every tile, no tap-mask loop in the set-up; the first operand requests issued before anything
+ *                           they do not need; full tiles stored without per-element tests (csrc/flm_igemm.hip, LEAN);
+ *                           0: the set-up and write-out as they were.  Same bits
  *   "bf16_group_n"          weight panels per tile group of that kernel (0 default, else a power of two <= 32)
  *   "bf16_conv3_halo"       0 off | 1 auto (default) | 2 always: halo-resident 3x3 kernel for 64-channel inputs
  *   "bf16_score1x1"         1 (default): 1x1 classifiers on 256-channel bf16 maps (score4, score3) run the kernel that
