@@ -748,6 +748,27 @@ int flm_fcn8_run_layer(flm_stream_t stream, const void* packed_dev, const char* 
   if (!strcmp(layer, "score5")) return conv_layer(s, blob, L.score5, x_dev, y_dev, n, h, w, 0, 0, 0, dtype, 1);
   if (!strcmp(layer, "score4")) return conv_layer(s, blob, L.score4, x_dev, y_dev, n, h, w, 0, 0, 0, dtype, 1);
   if (!strcmp(layer, "score3")) return conv_layer(s, blob, L.score3, x_dev, y_dev, n, h, w, 0, 0, 0, dtype, 1);
+  if (!strcmp(layer, "up5") || !strcmp(layer, "up4") || !strcmp(layer, "up3")) {
+    // the decoder's transposed convs, as forward_impl launches them (always launch_convt, never the fused up4 + score3)
+    ConvTDesc t;
+    t.g = L.g;
+    t.n = n;
+    t.x = static_cast<const float*>(x_dev);
+    t.hi = h; t.wi = w; t.epilogue = 0;
+    if (layer[2] == '3') {  // raw logits [n,8h+8,8w+8,C]
+      if (C & 3) {
+        set_error("flm_fcn8_run_layer: \"up3\" writes raw logits, which needs n_classes %% 4 == 0");
+        return FLM_ERR_UNSUPPORTED;
+      }
+      t.wf = blob + L.up3; t.skip = nullptr; t.y = y_dev;
+      t.ho = 8 * h + 8; t.wo = 8 * w + 8; t.s = 8; t.ldy = C;
+    } else {  // crop + Add in place on the skip map y_dev holds
+      t.wf = blob + (layer[2] == '5' ? L.up5 : L.up4);
+      t.skip = static_cast<const float*>(y_dev); t.y = y_dev;
+      t.ho = 2 * h; t.wo = 2 * w; t.s = 2; t.ldy = L.g.Cp;
+    }
+    return launch_convt(s, t);
+  }
   set_error("flm_fcn8_run_layer: unknown layer '%s'", layer);
   return FLM_ERR_ARG;
 }

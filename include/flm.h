@@ -214,7 +214,17 @@ int64_t flm_fcn8_workspace_offset_opts(const char* name, int n, int h, int w, in
  * ho x wo = h x w (h/2 x w/2 for the pooled "enc" layers).  Cout of the score layers is the padded class count of the
  * configuration (n_classes = 68: 68 in FLM_F32, 72 in FLM_BF16; otherwise 16 * ceil(n_classes / 16)); the columns from
  * n_classes on are written as exact zeros.  tests/test_gpu_bf16_layers.py holds fc6, fc7 and the score layers to an
- * integer reference bit for bit in both types. */
+ * integer reference bit for bit in both types.
+ *
+ * The decoder's Conv2DTranspose layers, with the forward's own launch (kernel 2s x 2s, stride s, crop to the top-left
+ * window fused); n, h, w are the INPUT grid.  Both types take and write float32 maps -- FLM_BF16 re-reads x_dev as a
+ * bf16 operand, as the forward does.  Cp is the padded class count above:
+ *   "up5", "up4":  x_dev float32 [n,h,w,Cp]; y_dev float32 [n,2h,2w,Cp] HOLDS THE SKIP MAP ON ENTRY and the call adds
+ *                  crop(convT(x)) onto it in place (s = 2; fuse4 = up5(score5) + score4, seg_feats = up4(fuse4) + score3).
+ *                  Pad columns of x_dev and y_dev must be zeros and stay exact zeros.  ("up4" is always the stand-alone
+ *                  launch; the 68-class bf16 forward may fuse it with score3 -- same bits.)
+ *   "up3":         x_dev float32 [n,h,w,Cp] -> y_dev float32 [n,8h+8,8w+8,n_classes] raw logits (s = 8);
+ *                  FLM_ERR_UNSUPPORTED unless n_classes % 4 == 0, as FLM_OUT_LOGITS. */
 int flm_fcn8_run_layer(flm_stream_t stream, const void* packed_dev, const char* layer, const void* x_dev,
                        void* y_dev, int n, int h, int w, int n_classes, int dtype);
 

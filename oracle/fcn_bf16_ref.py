@@ -37,6 +37,13 @@ epilogue: a legitimate implementation in another summation order.  Its distance 
 the yardstick for what float32 accumulation can move (tests/test_oracle_fcn_bf16.py, tests/test_gpu_bf16_layers.py).
 
 With rounding=False every function performs fcn_ref's float64 operations in fcn_ref's order: bit-identical.
+
+A third arithmetic, the exact-fp32 configuration's (FLM_F32; layer_f32_ref, or fp32=True): the same packed form of every
+conv -- raw float32 kernel (pack_conv_kernel<float> / pack_convt_kernel<float>), BatchNorm and bias as the float32-stored
+scale / shift of pack_affine_kernel applied to the accumulator (flm_igemm.hip igemm_kernel, flm_enc1.hip) -- with no
+bf16 rounding of weights, inputs or outputs, and transposed convs on the unrounded float32 maps.  accum=float64 is the
+exact value of that arithmetic, accum=float32 the yardstick of the fp32 gate (tests/test_oracle_fcn_f32.py,
+tests/test_gpu_fp32_layers.py).  It differs from fcn_ref's float64 only by the float32 storage of scale and shift.
 """
 from __future__ import annotations
 
@@ -148,6 +155,28 @@ def layer_report(got, exact64, ref32_exact, ref32_stored, stored_bf16) -> dict:
     return rep
 
 
+def gate_layer(got, exact64, ref32_exact, ref32_stored, stored_bf16) -> dict:
+    """layer_report of the first exact64.shape[-1] columns of `got`; the columns beyond them -- the class padding of
+    score5 / fuse4 / seg_feats -- must be exact zeros (else ok = False and `pad` = their largest magnitude)."""
+    got = np.asarray(got)
+    c = np.shape(exact64)[-1]
+    rep = layer_report(got[..., :c], exact64, ref32_exact, ref32_stored, stored_bf16)
+    if got.shape[-1] > c and np.any(got[..., c:] != 0):
+        rep["ok"] = False
+        rep["pad"] = float(np.abs(got[..., c:]).max())
+    return rep
+
+
+PROBS_BAR = 1e-5       # the suite's bar on probabilities (tests/test_gpu_forward.py)
+
+
+def probs_report(got, logits64) -> dict:
+    """The probabilities `got` [N,H'*W',C] against the float64 softmax of `logits64` [N,H',W',C]: largest absolute
+    error `err`, ok = err <= PROBS_BAR."""
+    d = float(np.abs(np.asarray(got, np.float64) - softmax_ref(logits64)).max())
+    return dict(err=d, ok=d <= PROBS_BAR)
+
+
 def format_report(name, rep) -> str:
     s = "%-9s over-half-step %.3g (slack %.3g = min(2e-5, 4 x e32 %.3g))" % (name, rep["over"], rep["slack"], rep["e32"])
     if "flips" in rep:
@@ -161,12 +190,17 @@ def format_report(name, rep) -> str:
 
 class Arith:
     """rounding: restate the bf16 rounding points (False: fcn_ref's float64 arithmetic, bit for bit).
-    accum: torch.float64, or torch.float32 = the same rounded operands summed by torch's float32 CPU kernels."""
+    accum: torch.float64, or torch.float32 = the same rounded operands summed by torch's float32 CPU kernels.
+    fp32: the exact-fp32 configuration (FLM_F32) -- the packed form of every conv (raw float32 kernel, BatchNorm and
+    bias as _fold's float32-stored scale / shift applied to the accumulator) with NO bf16 rounding of weights, inputs
+    or outputs; `accum` is honoured (float64: the exact value of that arithmetic; float32: the yardstick)."""
 
-    def __init__(self, rounding=True, accum=F64):
+    def __init__(self, rounding=True, accum=F64, fp32=False):
         assert accum in (torch.float64, torch.float32)
-        self.rounding = bool(rounding)
-        self.accum = accum if rounding else F64
+        self.fp32 = bool(fp32)
+        self.rounding = bool(rounding) and not self.fp32
+        self.folded = self.rounding or self.fp32     # the packer's scale / shift form instead of fcn_ref's BatchNorm
+        self.accum = accum if self.folded else F64
 
     def q(self, t: torch.Tensor) -> torch.Tensor:
         """One bf16 rounding of a float64 tensor (identity with rounding off)."""
@@ -221,7 +255,7 @@ def _conv_block(A: Arith, x, p, conv, bn=None, pad=0, stride=1, relu=0, pool=0, 
     exact: float64 (accum=float32: the float32 result), before the rounding of the stored value."""
     dw = conv + "/depthwise_kernel" in p
     kern = p[conv + ("/depthwise_kernel" if dw else "/kernel")]
-    if not A.rounding:   # fcn_ref's operations, in its order
+    if not A.folded:   # fcn_ref's operations, in its order
         if dw:
             w = fcn_ref._t(kern, F64).permute(2, 3, 0, 1).contiguous()
         else:
@@ -236,7 +270,7 @@ def _conv_block(A: Arith, x, p, conv, bn=None, pad=0, stride=1, relu=0, pool=0, 
         if pool:
             y = F.max_pool2d(y, 2, 2)
         return y, y
-    w = _weight(kern, (2, 3, 0, 1) if dw else (3, 2, 0, 1), round_w)
+    w = _weight(kern, (2, 3, 0, 1) if dw else (3, 2, 0, 1), round_w and A.rounding)
     xo = A.q(x) if round_x else x
     scale, shift = _fold(p, conv, bn)
     dt = A.accum
@@ -254,9 +288,9 @@ def _conv_block(A: Arith, x, p, conv, bn=None, pad=0, stride=1, relu=0, pool=0, 
 def _convt_block(A: Arith, x, p, name, stride):
     """Transposed conv of the decoder: the float32 map x is re-read as a bf16 operand, the kernel is rounded raw
     (flm_convt.hip / flm_tail_bf16.hip / flm_up3_wreg.hip; flm_pack.hip pack_convt_kernel<unsigned short>)."""
-    if not A.rounding:
+    if not A.folded:
         return fcn_ref._convT(x, p[name + "/kernel"], stride, F64)
-    w = _weight(p[name + "/kernel"], (3, 2, 0, 1), True)
+    w = _weight(p[name + "/kernel"], (3, 2, 0, 1), A.rounding)   # (fp32 configuration: unrounded operands)
     return F.conv_transpose2d(A.q(x).to(A.accum), w.to(A.accum), None, stride=stride).to(F64)
 
 
@@ -350,15 +384,16 @@ def _seg(A, fuse4, f3, p):
     return o2 + o                                        # fcn.py:119
 
 
-def layer_bf16_ref(layer: str, inputs, p: dict, rounding=True, accum=F64):
+def layer_bf16_ref(layer: str, inputs, p: dict, rounding=True, accum=F64, fp32=False):
     """One layer of the vanilla fcn_8 in the bf16 configuration, given its INPUT (NHWC arrays; a tuple for the
     two-input layers).  Returns (exact, stored), NHWC float64: the unrounded output and the value the layer
     stores (rounded to bf16 for f1..f5 / fc6 / fc7; the float32-stored layers return exact twice).
 
       enc1: preprocessed float32 RGB input    enc2..enc5: f1..f4    fc6: f5    fc7: fc6    score5: fc7
       score4: f4    score3: f3    fuse4: (score5, f4)    seg_feats: (fuse4, f3)    logits: seg_feats
-    Class columns beyond n_classes of score5 / fuse4 / seg_feats inputs are ignored (they hold zeros)."""
-    A = Arith(rounding, accum)
+    Class columns beyond n_classes of score5 / fuse4 / seg_feats inputs are ignored (they hold zeros).
+    fp32=True: the same layer in the fp32 configuration's arithmetic (Arith); exact and stored are then equal."""
+    A = Arith(rounding, accum, fp32)
     c = p["score5/kernel"].shape[3]
     if layer in ("enc1", "enc2", "enc3", "enc4", "enc5"):
         e, s = _conv_block(A, _nchw(inputs), p, layer, bn=layer, pad=1, relu=1, pool=1, round_x=(layer == "enc1"))
@@ -377,6 +412,12 @@ def layer_bf16_ref(layer: str, inputs, p: dict, rounding=True, accum=F64):
     else:
         raise KeyError(layer)
     return _nhwc(e), _nhwc(s)
+
+
+def layer_f32_ref(layer: str, inputs, p: dict, accum=F64) -> np.ndarray:
+    """One layer of the vanilla fcn_8 as the fp32 configuration (FLM_F32) evaluates it, given its input (the layers and
+    inputs of layer_bf16_ref): folded float32 scale / shift, nothing rounded to bf16, sums in `accum`.  NHWC float64."""
+    return layer_bf16_ref(layer, inputs, p, accum=accum, fp32=True)[0]
 
 
 def fcn8_logits_bf16_ref(x_nhwc, p, return_intermediates=False, encoder="vanilla", rounding=True, accum=F64):

@@ -10,6 +10,11 @@ held against the float64 evaluation of that input by oracle/fcn_bf16_ref.py:
 
 slack is measured on the reference side, per layer and input: 4 x the largest error of torch's float32 evaluation of
 the same rounded operands against float64, capped at the fp32 suite's 2e-5 (never below one float32 step, 2^-23).
+
+dtype="f32" gates the exact-fp32 configuration the same way against the oracle's fp32 arithmetic (layer_f32_ref: the
+packer's folded float32 scale / shift, nothing rounded to bf16): every layer is fp32-stored, so the criterion is
+|got - exact64| <= slack * max|exact64| with e32 from the float32-accumulating evaluation of the same input, and there
+is no flip count.  Class pad columns of score5 / fuse4 / seg_feats must be exact zeros in both configurations.
 """
 import numpy as np
 import torch
@@ -23,25 +28,28 @@ CHAIN = (("f1", "enc1", ("x",)), ("f2", "enc2", ("f1",)), ("f3", "enc3", ("f2",)
          ("fuse4", "fuse4", ("score5", "f4")), ("seg_feats", "seg_feats", ("fuse4", "f3")))
 
 
-def check_layers(model, params, crops_u8, n, out, faces=None, logits=None, probs=None, label=""):
+def check_layers(model, params, crops_u8, n, out, faces=None, logits=None, probs=None, label="", dtype="bf16"):
     """Gate every layer of the last forward (n faces, output mode `out`) on `faces` (default: all).  `logits` / `probs`:
     device outputs of forwards of the SAME faces (numpy, [F,H',W',C] / [F,H'*W',C]) whose workspaces hold the seg_feats
-    they were computed from.  Prints one line per layer, then asserts.  Returns {name: report}."""
-    c = model.n_classes
+    they were computed from.  `crops_u8` may also be the float32 preprocessed input the forward was given.  Prints one
+    line per layer, then asserts.  Returns {name: report}."""
+    assert dtype in ("bf16", "f32") and model.dtype == dtype, (dtype, model.dtype)
+    f32 = dtype == "f32"
+    crops_u8 = np.asarray(crops_u8)
     faces = list(range(n)) if faces is None else list(faces)
-    dev = {"x": np.stack([fcn_ref.get_image_array_ref(crops_u8[f]) for f in faces])}
+    dev = {"x": np.stack([fcn_ref.get_image_array_ref(crops_u8[f]) if crops_u8.dtype == np.uint8 else crops_u8[f] for f in faces])}
     for name, _, _ in CHAIN:
         dev[name] = model.intermediate(name, n, out)[faces].cpu().numpy().astype(np.float64)
     reports, bad = {}, []
 
     def gate(name, layer, xin, got):
-        exact, _ = B.layer_bf16_ref(layer, xin, params)
-        e32, s32 = B.layer_bf16_ref(layer, xin, params, accum=torch.float32)
-        rep = B.layer_report(got[..., : exact.shape[-1]], exact, e32, s32, name in STORED_BF16)
-        if got.shape[-1] > exact.shape[-1] and np.any(got[..., exact.shape[-1]:] != 0):   # class pad columns 68..71
-            rep["ok"] = False
-            rep["pad"] = float(np.abs(got[..., exact.shape[-1]:]).max())
-        print("%s %s" % (label, B.format_report(name, rep)) + (" pad columns not zero: %g" % rep["pad"] if "pad" in rep else ""))
+        exact, _ = B.layer_bf16_ref(layer, xin, params, fp32=f32)
+        e32, s32 = B.layer_bf16_ref(layer, xin, params, accum=torch.float32, fp32=f32)
+        rep = B.gate_layer(got, exact, e32, s32, name in STORED_BF16 and not f32)   # class pad columns: exact zeros
+        line = B.format_report(name, rep)
+        if f32:   # nothing is stored rounded: `over` is the whole error
+            line = line.replace("over-half-step", "error")
+        print("%s %s" % (label, line) + (" pad columns not zero: %g" % rep["pad"] if "pad" in rep else ""))
         reports[name] = rep
         if not rep["ok"]:
             bad.append(name)
@@ -58,8 +66,7 @@ def check_layers(model, params, crops_u8, n, out, faces=None, logits=None, probs
         if what == "logits":
             gate("logits", "logits", seg, np.asarray(arr, np.float64))
         else:   # the fp32 suite's bar, against the softmax of the oracle's logits FROM THE DEVICE'S seg_feats
-            exp = B.softmax_ref(B.layer_bf16_ref("logits", seg, params)[0])
-            d = float(np.abs(arr - exp).max())
+            d = B.probs_report(arr, B.layer_bf16_ref("logits", seg, params, fp32=f32)[0])["err"]
             print("%s probs     max-abs error %.3g (bar 1e-5), rows sum to 1 within %.3g" % (label, d, np.abs(arr.sum(-1) - 1).max()))
             reports["probs"] = dict(err=d, ok=d <= 1e-5)
             if d > 1e-5:

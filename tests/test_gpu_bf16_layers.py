@@ -11,7 +11,11 @@ bfloat16 exactly where the kernels do.
 (2) Exact arithmetic through flm_fcn8_run_layer: small-integer weights, biases and inputs keep every partial sum
     below 2^24, so products and sums are exact in any order and the output must equal the integer reference bit for
     bit (rounded once to bf16 where the layer stores bf16) -- any tap, padding, k-slice or pad-column indexing error
-    shows at zero tolerance.
+    shows at zero tolerance.  fc6, fc7 and the score convs; the encoder branch ("enc2" .. "enc5": BatchNorm that folds
+    exactly, ReLU clamping 70 % of the sums, 2 x 2 max; maps of 2 x 2, 6 x 10 and 8 x 24 at 1, 3 and 17 faces) with enc1
+    through a float32-input forward; and the decoder in isolation ("up5" / "up4" in place on their skip maps, "up3" as raw
+    logits, with the score convs) at the 68-class layouts and at one class count per generic instantiation of
+    launch_convt at its full and its ragged edge: 1, 16, 17, 36, 48, 52, 64, 65, 80, 84, 96 -- pad columns exact zeros.
 
 Reference-side values and what the kernels measured on an MI355X over the four shapes (the 16 faces of the 512-face
 launch of tests/test_gpu_baseline_configs.py beside them).  e32: the float32 CPU evaluation's largest error against
@@ -36,7 +40,7 @@ closest; flips: elements that are not round_bf16(exact64), kernels | float32 ref
 The 2e-5 cap never binds: every slack is 4 x e32.  At 512 faces fc6, fc7 and score5 run without split-K -- one chain of
 K / 16 accumulator updates per output where the small batches add 8 to 32 partial sums -- and come closest to the
 gate: score5 (K = 4096, 256 updates) uses 0.97 of its allowance, fc6's flips half of theirs.  Every integer case of (2)
-matches bit for bit in both configurations.
+matches bit for bit in both configurations (the twelve class counts included: 0 of up to 6,690,816 elements differ).
 
 Fault injection (scratch build, not committed): with pack_conv_kernel<unsigned short> zeroing channels 64..95 of fc6's
 centre tap, fc6 of 2 x 256 x 256 is over the half step by 4.0e-2 of its maximum against a slack of 1.3e-06 and flips
@@ -84,9 +88,14 @@ def test_bf16_layers_teacher_forced(flm, weights68, n, h, w):
 
 # ---- exact arithmetic through flm_fcn8_run_layer ---------------------------------------------------------------
 
+ENC_BIAS = {"enc1": (-40, 10), "enc2": (-200, 50), "enc3": (-300, 75), "enc4": (-300, 75), "enc5": (-300, 75)}
+
+
 def _int_params(seed=11):
-    """fcn_8 tensors of small integers: conv kernels in [-2, 2], biases in [-8, 8]; BatchNorm of the (unused) encoder
-    left at the identity."""
+    """fcn_8 tensors of small integers: conv kernels in [-2, 2], biases in [-8, 8].  The encoder's BatchNorm folds
+    EXACTLY: moving_variance = float32(0.999) (with the float32 epsilon 1e-3 the scale is gamma * (1 - 6.5e-9), which
+    rounds to gamma in float32), gamma in {0.5, 1, 2} per channel, moving_mean = beta = 0, integer biases shifted below
+    zero so that the ReLU clamps a visible share of the outputs -- scale = gamma and shift = gamma * bias in float32."""
     from flm_amd.weights import fcn8_param_shapes
     rng = np.random.default_rng(seed)
     p = {}
@@ -99,6 +108,24 @@ def _int_params(seed=11):
             p[name] = np.ones(shape, np.float32)
         else:
             p[name] = np.zeros(shape, np.float32)
+    rng = np.random.default_rng(seed + 1)     # (a stream of its own: the head's tensors above stay what they were)
+    for layer, (lo, hi) in ENC_BIAS.items():
+        f = p[layer + "/bias"].shape
+        p[layer + "/bias"] = rng.integers(lo, hi + 1, f).astype(np.float32)
+        p[layer + "/gamma"] = rng.choice(np.array([0.5, 1.0, 2.0], np.float32), f)
+        p[layer + "/moving_variance"] = np.full(f, 0.999, np.float32)
+    return p
+
+
+def _with_classes(base, c):
+    """The integer tensors with the class-dependent ones (score convs, transposed convs) redrawn for c classes."""
+    from flm_amd.weights import fcn8_param_shapes
+    rng = np.random.default_rng(1000 + c)
+    p = dict(base)
+    for name, shape in fcn8_param_shapes(c).items():
+        if name.split("/")[0] in ("score5", "score4", "score3", "up5", "up4", "up3"):
+            p[name] = rng.integers(-2, 3, shape).astype(np.float32) if name.endswith("/kernel") else \
+                rng.integers(-8, 9, shape).astype(np.float32)
     return p
 
 
@@ -113,22 +140,27 @@ def int_models(flm):
     return p, models
 
 
-def _run_layer(model, layer, x_nhwc, cout):
-    """flm_fcn8_run_layer on an integer-valued input; the output buffer carries guard rows that must stay untouched."""
+def _run_layer(model, layer, x_nhwc, cout, out_hw=None, skip=None):
+    """flm_fcn8_run_layer on an integer-valued input; the output buffer carries guard rows that must stay untouched.
+    out_hw: output grid when it is not the input's; skip: what the output buffer holds on entry ("up5" / "up4")."""
     from flm_amd import _lib
     lib = _lib.load()
     bf = model.dtype == "bf16"
     n, h, w, _ = x_nhwc.shape
-    xd = torch.from_numpy(x_nhwc).cuda().to(torch.bfloat16 if bf else torch.float32).contiguous()
-    out_bf = bf and layer in ("fc6", "fc7")
-    rows, guard = n * h * w, 64
+    up = layer.startswith("up")   # the decoder reads float32 maps in both configurations
+    xd = torch.from_numpy(x_nhwc).cuda().to(torch.bfloat16 if bf and not up else torch.float32).contiguous()
+    out_bf = bf and (layer in ("fc6", "fc7") or layer.startswith("enc"))
+    ho, wo = out_hw if out_hw else (h, w)
+    rows, guard = n * ho * wo, 64
     y = torch.full((rows + guard, cout), -12345.0, dtype=torch.bfloat16 if out_bf else torch.float32, device="cuda")
+    if skip is not None:
+        y[:rows] = torch.from_numpy(np.ascontiguousarray(skip, np.float32).reshape(rows, cout)).cuda()
     _lib.check(lib.flm_fcn8_run_layer(_lib.stream_ptr(), _lib.ptr(model._packed), layer.encode(), _lib.ptr(xd), _lib.ptr(y),
-                                      n, h, w, 68, model._dt), "flm_fcn8_run_layer")
+                                      n, h, w, model.n_classes, model._dt), "flm_fcn8_run_layer")
     torch.cuda.synchronize()
     y = y.float().cpu().numpy()
     assert (y[rows:] == np.float32(y[rows, 0])).all() and y[rows, 0] != 0, "guard rows written"
-    return y[:rows].reshape(n, h, w, cout).astype(np.float64)
+    return y[:rows].reshape(n, ho, wo, cout).astype(np.float64)
 
 
 _REF = {}   # both configurations run the same integer cases: one float64 reference each
@@ -201,3 +233,154 @@ def test_run_layer_fc7_and_scores_are_exact_on_integers(int_models, dtype):
         bad = got != exp
         print("%s %s %dx%dx%d: %d of %d elements differ" % (layer, dtype, n, h, w, bad.sum(), bad.size))
         assert not bad.any(), (layer, dtype, n, h, w, int(bad.sum()), float(np.abs(got - exp).max()))
+
+
+# ---- the encoder branch of flm_fcn8_run_layer, and enc1 through a float32-input forward ---------------------------
+
+def _enc_reference(p, layer, x_nhwc):
+    """conv + bias, times gamma, ReLU, 2 x 2 max in float64; asserts on the CPU that the packer's fold (_fold restates
+    pack_affine_kernel) is exactly scale = gamma, shift = gamma * bias, and that every partial sum stays below 2^24."""
+    import torch.nn.functional as F
+    from oracle.fcn_bf16_ref import _fold
+    k = p[layer + "/kernel"].astype(np.float64)
+    g, b = p[layer + "/gamma"].astype(np.float64), p[layer + "/bias"].astype(np.float64)
+    scale, shift = _fold(p, layer, layer)
+    assert np.array_equal(scale, g) and np.array_equal(shift, g * b), (layer, "BatchNorm does not fold exactly")
+    xt = torch.from_numpy(x_nhwc.astype(np.float64)).permute(0, 3, 1, 2)
+    kt = torch.from_numpy(k).permute(3, 2, 0, 1)
+    bound = (F.conv2d(xt.abs(), kt.abs(), None, padding=1).max().item() + np.abs(b).max()) * 2
+    assert bound < 2 ** 24
+    pre = F.conv2d(xt, kt, None, padding=1) * torch.from_numpy(g)[None, :, None, None] + torch.from_numpy(g * b)[None, :, None, None]
+    y = F.max_pool2d(torch.relu(pre), 2, 2).permute(0, 2, 3, 1).numpy()
+    return y, float((pre <= 0).float().mean()), float((y == 0).mean())
+
+
+ENC_MAPS = [(n, h, w) for (h, w) in ((2, 2), (6, 10), (8, 24)) for n in (1, 3, 17)]
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_run_layer_encoder_is_exact_on_integers(int_models, dtype):
+    """enc2 .. enc5 (3 x 3, BatchNorm + ReLU + 2 x 2 max fused; K = 576, 1152, 2304, 2304) on maps of 2 x 2 (every tap but
+    the centre quad is padding), 6 x 10 and 8 x 24 at 1, 3 and 17 faces; inputs in [-4, 4].  bf16 stores round_bf16(exact)."""
+    from oracle.fcn_bf16_ref import round_bf16
+    p, models = int_models
+    rng = np.random.default_rng(7)
+    for i, cin in ((2, 64), (3, 128), (4, 256), (5, 256)):
+        layer = "enc%d" % i
+        cout = p[layer + "/bias"].shape[0]
+        for n, h, w in ENC_MAPS:
+            x = rng.integers(-4, 5, (n, h, w, cin)).astype(np.float32)
+            exp, neg, zero = _enc_reference(p, layer, x)
+            if dtype == "bf16":
+                exp = round_bf16(exp)
+            got = _run_layer(models[dtype], layer, x, cout, out_hw=(h // 2, w // 2))
+            bad = got != exp
+            print("%s %s %dx%dx%d: %d of %d elements differ; ReLU clamps %.0f %% before the pool, %.0f %% of the outputs are 0" % (
+                layer, dtype, n, h, w, bad.sum(), bad.size, 100 * neg, 100 * zero))
+            assert not bad.any(), (layer, dtype, n, h, w, int(bad.sum()), float(np.abs(got - exp).max()))
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_enc1_is_exact_on_integers_through_a_float32_forward(int_models, dtype):
+    """enc1 (3 input channels, K = 27; flm_enc1.hip) has no run_layer entry: integer pixels in [-4, 4] go in as the
+    float32 preprocessed input (FLM_IN_F32_RGB) of a whole forward and f1 is read back."""
+    from flm_amd.networks import LANDMARKS_MODELS
+    from oracle.fcn_bf16_ref import round_bf16
+    p, models = int_models
+    rng = np.random.default_rng(8)
+    for n, h, w in ((1, 32, 32), (3, 32, 32), (3, 64, 96)):
+        model = LANDMARKS_MODELS["fcn_8"](68, input_height=h, input_width=w, dtype=dtype)
+        model._packed = models[dtype]._packed          # the same packed integers at another input size
+        x = rng.integers(-4, 5, (n, h, w, 3)).astype(np.float32)
+        exp, neg, zero = _enc_reference(p, "enc1", x)
+        if dtype == "bf16":
+            exp = round_bf16(exp)
+        model.forward_device(torch.from_numpy(x).cuda(), "probs")
+        torch.cuda.synchronize()
+        got = model.intermediate("f1", n, "probs").cpu().numpy().astype(np.float64)
+        bad = got != exp
+        print("enc1 %s %dx%dx%d: %d of %d elements differ; ReLU clamps %.0f %% before the pool, %.0f %% of the outputs are 0" % (
+            dtype, n, h, w, bad.sum(), bad.size, 100 * neg, 100 * zero))
+        assert not bad.any(), (dtype, n, h, w, int(bad.sum()), float(np.abs(got - exp).max()))
+
+
+# ---- the decoder in isolation: up5 / up4 / up3 and the score convs at every class-tile count ----------------------
+
+# 68: the special layouts (fp32 G = 17; bf16 Cp = 72, the fifth class tile shared at stride 8); then one count per generic
+# instantiation of launch_convt (MT = ceil(C / 16) = 1 .. 6) at its full and its ragged edge
+CLASS_COUNTS = [68, 1, 16, 17, 36, 48, 52, 64, 65, 80, 84, 96]
+UP_GRIDS = {"up5": [(1, 1, 1), (3, 2, 3), (3, 3, 5), (17, 2, 2), (2, 8, 8)],
+            "up4": [(1, 2, 2), (3, 4, 6), (3, 6, 10), (2, 16, 16)],
+            "up3": [(1, 4, 4), (3, 8, 12), (2, 12, 20), (1, 32, 32)]}
+
+
+def _cp(c, dtype):
+    return (72 if dtype == "bf16" else 68) if c == 68 else 16 * ((c + 15) // 16)
+
+
+def _convt_reference(p, layer, x_nhwc, skip_nhwc):
+    """F.conv_transpose2d in float64, the top-left crop of fcn_ref.crop_ref and the skip add; every partial sum < 2^24."""
+    import torch.nn.functional as F
+    from oracle import fcn_ref
+    s = 8 if layer == "up3" else 2
+    k = torch.from_numpy(p[layer + "/kernel"].astype(np.float64)).permute(3, 2, 0, 1)   # (kh, kw, out, in) -> (in, out, kh, kw)
+    xt = torch.from_numpy(x_nhwc.astype(np.float64)).permute(0, 3, 1, 2)
+    assert F.conv_transpose2d(xt.abs(), k.abs(), None, stride=s).max().item() + 8 < 2 ** 24
+    o = F.conv_transpose2d(xt, k, None, stride=s)
+    if skip_nhwc is not None:
+        sk = torch.from_numpy(skip_nhwc.astype(np.float64)).permute(0, 3, 1, 2)
+        o, sk = fcn_ref.crop_ref(o, sk)
+        o = o + sk
+    return o.permute(0, 2, 3, 1).numpy()
+
+
+@pytest.mark.parametrize("c", CLASS_COUNTS)
+def test_run_layer_decoder_is_exact_on_integers(flm, int_models, c):
+    """up5 / up4 (4 x 4, stride 2, crop + Add in place on the skip map), up3 (16 x 16, stride 8, raw logits; class counts
+    that are multiples of 4) and score5 / score4 / score3 at one class count, in both types.  Grids: one partial
+    64-position tile, tiles that span faces, and the far row and column of P = n (h + 1)(w + 1).  Integer kernels in
+    [-2, 2], x in [-4, 4], skip maps in [-8, 8], pad columns zero on entry and exact zeros on exit."""
+    from flm_amd.networks import LANDMARKS_MODELS
+    base, models68 = int_models
+    p = base if c == 68 else _with_classes(base, c)
+    rng = np.random.default_rng(2000 + c)
+    cases = []
+    for layer in ("up5", "up4", "up3"):
+        if layer == "up3" and c % 4:
+            continue
+        for n, h, w in UP_GRIDS[layer]:
+            x = rng.integers(-4, 5, (n, h, w, c)).astype(np.float32)
+            skip = None if layer == "up3" else rng.integers(-8, 9, (n, 2 * h, 2 * w, c)).astype(np.float32)
+            cases.append((layer, x, skip, _convt_reference(p, layer, x, skip)))
+    for layer, cin, shapes in (("score5", 4096, ((1, 1, 1), (3, 3, 5), (17, 7, 9))), ("score4", 256, ((3, 6, 10), (17, 7, 9))),
+                               ("score3", 256, ((3, 12, 20), (1, 1, 1)))):
+        for shp in shapes:
+            x = rng.integers(-4, 5, shp + (cin,)).astype(np.float32)
+            cases.append((layer, x, None, _int_reference_eval(p, layer, x, relu=False)))
+    for dtype in ("f32", "bf16"):
+        if c == 68:
+            model = models68[dtype]
+        else:
+            model = LANDMARKS_MODELS["fcn_8"](c, input_height=32, input_width=32, dtype=dtype)
+            model.load_weights(p)
+        cp = _cp(c, dtype)
+        padded = lambda a: np.concatenate([a, np.zeros(a.shape[:3] + (cp - c,), np.float32)], -1)
+        for layer, x, skip, exp in cases:
+            n, h, w, _ = x.shape
+            if layer == "up3":
+                got = _run_layer(model, layer, padded(x), c, out_hw=(8 * h + 8, 8 * w + 8))
+            elif layer.startswith("up"):
+                got = _run_layer(model, layer, padded(x), cp, out_hw=(2 * h, 2 * w), skip=padded(skip))
+            else:
+                got = _run_layer(model, layer, x, cp)
+            assert (got[..., c:] == 0).all(), (layer, dtype, c, "pad columns", float(np.abs(got[..., c:]).max()))
+            bad = got[..., :c] != exp
+            print("%s %s C=%d %dx%dx%d: %d of %d elements differ" % (layer, dtype, c, n, h, w, bad.sum(), bad.size))
+            assert not bad.any(), (layer, dtype, c, n, h, w, int(bad.sum()), float(np.abs(got[..., :c] - exp).max()))
+        if c % 4:   # the raw-logits launch needs float4 rows: refused (FLM_ERR_UNSUPPORTED = -5), not mis-stored
+            from flm_amd import _lib
+            x, y = torch.zeros((1, 4, 4, cp), device="cuda"), torch.zeros((1, 40, 40, c), device="cuda")
+            rc = _lib.load().flm_fcn8_run_layer(_lib.stream_ptr(), _lib.ptr(model._packed), b"up3", _lib.ptr(x), _lib.ptr(y),
+                                                1, 4, 4, c, model._dt)
+            assert rc == -5, rc
+        del model
