@@ -4,6 +4,7 @@ There is no CPU fallback: if the library is missing or a call fails, the op rais
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -26,7 +27,7 @@ EXPORTS = [
     "flm_fcn_packed_bytes", "flm_fcn_pack", "flm_fcn_workspace_bytes", "flm_fcn_forward",
     "flm_forward_opts_init", "flm_fcn_workspace_bytes_opts", "flm_fcn_forward_opts", "flm_fcn8_workspace_offset_opts",
     "flm_fcn8_workspace_bytes", "flm_fcn8_forward", "flm_fcn8_workspace_offset", "flm_fcn8_run_layer",
-    "flm_set_tuning", "flm_debug_query", "flm_profile_enable", "flm_profile_filter", "flm_profile_reset", "flm_profile_read", "flm_profile_disable",
+    "flm_set_tuning", "flm_get_tuning", "flm_debug_query", "flm_profile_enable", "flm_profile_filter", "flm_profile_reset", "flm_profile_read", "flm_profile_disable",
     "flm_preprocess",
     "flm_decode_workspace_bytes", "flm_decode", "flm_decode_sweep_workspace_bytes", "flm_decode_sweep",
     "flm_gaussian_heatmaps",
@@ -125,6 +126,8 @@ def _declare(lib):
     lib.flm_profile_filter.argtypes = [C.c_char_p]
     lib.flm_set_tuning.restype = i
     lib.flm_set_tuning.argtypes = [C.c_char_p, i]
+    lib.flm_get_tuning.restype = i
+    lib.flm_get_tuning.argtypes = [C.c_char_p, C.POINTER(i)]
     lib.flm_debug_query.restype = i
     lib.flm_debug_query.argtypes = [C.c_char_p, i]
     lib.flm_profile_enable.restype = i
@@ -193,6 +196,26 @@ def check(rc: int, what: str = ""):
     if rc != 0:
         msg = load().flm_last_error()
         raise FlmError("%s failed (%d): %s" % (what or "flm call", rc, msg.decode() if msg else "?"))
+
+
+@contextlib.contextmanager
+def tuning(*keys, **knobs):
+    """The A/B knobs of flm_set_tuning for the length of a `with` block: tuning(up3_wreg=1) sets a knob, tuning("warp_rows")
+    only names one the block sets itself.  On exit, also by exception, every named knob returns to the value it had on
+    entry (read with flm_get_tuning); blocks nest."""
+    lib = load()
+    saved = {}
+    try:
+        for key in (*keys, *knobs):
+            old = C.c_int()
+            check(lib.flm_get_tuning(key.encode(), C.byref(old)), "get_tuning")
+            saved[key] = old.value
+            if key in knobs:
+                check(lib.flm_set_tuning(key.encode(), int(knobs[key])), "set_tuning")
+        yield
+    finally:
+        for key, old in saved.items():
+            check(lib.flm_set_tuning(key.encode(), old), "set_tuning")
 
 
 def require_gpu():

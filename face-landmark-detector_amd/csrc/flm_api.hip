@@ -21,6 +21,40 @@ int hip_fail(hipError_t e, const char* what) {
   return FLM_ERR_HIP;
 }
 
+// ---- A/B knobs: one row per KnobId, in the enum's order (include/flm.h documents the keys and values) ------------
+struct Knob {
+  const char* key;
+  std::atomic<int> value;  // initialised with the default
+  bool (*valid)(int);      // null: every value is accepted
+  const char* domain;      // what a rejected value is told ("<key> must be <domain>")
+};
+static Knob g_knobs[] = {
+    {"bf16_big_tiles", {1}, nullptr, nullptr},
+    {"bf16_lds_dma", {1}, nullptr, nullptr},
+    {"bf16_mfma16", {1}, nullptr, nullptr},
+    {"bf16_halo_mfma16", {1}, nullptr, nullptr},
+    {"f32_two_level", {1}, nullptr, nullptr},
+    {"f32_lean_tile", {1}, nullptr, nullptr},
+    {"bf16_group_n", {0}, [](int v) { return v >= 0 && v <= 32 && !(v & (v - 1)); }, "0 or a power of two <= 32"},
+    {"bf16_conv3_halo", {1}, nullptr, nullptr},
+    {"bf16_score1x1", {1}, nullptr, nullptr},
+    {"bf16_fused_tail", {1}, nullptr, nullptr},
+    {"decode_lds_dma", {1}, nullptr, nullptr},
+    {"posmajor_order", {1}, nullptr, nullptr},
+    {"warp_rows", {1}, [](int v) { return v == 0 || v == 1 || v == 4; }, "0, 1 or 4"},
+    {"up3_cand8", {1}, [](int v) { return v >= 0 && v <= 7; }, "in [0,7]"},
+    {"up3_cand8_rows", {0}, [](int v) { return v >= 0 && v <= 8 && !(v & (v - 1)); }, "0, 1, 2, 4 or 8"},
+    {"up3_wreg", {0}, [](int v) { return v == 0 || v == 1; }, "0 or 1"},
+};
+static_assert(sizeof(g_knobs) / sizeof(g_knobs[0]) == KNOB_COUNT, "one row per KnobId");
+int tuning(KnobId id) { return g_knobs[id].value.load(std::memory_order_relaxed); }
+static Knob* find_knob(const char* who, const char* key) {
+  for (Knob& k : g_knobs)
+    if (!strcmp(k.key, key)) return &k;
+  set_error("%s: unknown key '%s'", who, key);
+  return nullptr;
+}
+
 // ---- optional per-launch timing (bench.py): hipEvent pairs around every launch of the forward --------
 // Off by default; when enabled the forward records two events per layer on the caller's stream and
 // never synchronises -- flm_profile_read() does, after the caller's own timed region has ended.
@@ -35,8 +69,8 @@ static char g_prof_filter[32] = "";  // non-empty: only launches of this layer a
 struct ProfScope {
   hipStream_t s;
   ProfRec* r;
-  ProfScope(hipStream_t st, const char* name) : s(st), r(nullptr) {
-    if (g_prof && g_prof_n < g_prof_cap && (!g_prof_filter[0] || !strcmp(g_prof_filter, name))) {
+  ProfScope(hipStream_t st, const char* name) : s(st), r(nullptr) {  // (null name: no record)
+    if (name && g_prof && g_prof_n < g_prof_cap && (!g_prof_filter[0] || !strcmp(g_prof_filter, name))) {
       r = &g_prof[g_prof_n++];
       r->name = name;
       (void)hipEventRecord(r->a, s);
@@ -146,13 +180,13 @@ Fcn8Ws fcn8_ws_layout(int n, int h, int w, int C, int dtype, int out_mode, int d
   W.probs = SIZE_MAX;
   W.decode = SIZE_MAX;
   W.sub = W.tau = W.cand = W.cand_cnt = SIZE_MAX;
-  W.cand_cap = 0;
+  W.cand_cap = W.cand_sub = 0;
   if (out_mode == FLM_OUT_LANDMARKS) {
     W.probs = take(cur, sizeof(float) * (size_t)n * W.oh * W.ow * C);
     W.decode = take(cur, decode_ws_bytes(n, W.oh, W.ow, C, decode_mode, n_points));
     if (landmark_candidates_enabled(co, g, A.fcn32, decode_mode, n_points, W.oh, W.ow)) {
-      const int h3 = h / 8, w3 = w / 8;
-      W.sub = take(cur, sizeof(unsigned) * (size_t)n * convt_sample_slots(g, h3, w3, cand_sub_for(co, n_points, g.bf16 != 0)) * 16 * g.MT);  // sampled maxima
+      W.cand_sub = cand_sub_for(co, n_points, g.bf16 != 0);
+      W.sub = take(cur, sizeof(unsigned) * (size_t)n * convt_sample_slots(g, h3, w3, W.cand_sub) * 16 * g.MT);  // sampled maxima
       W.tau = take(cur, sizeof(float) * (size_t)n * C);
       // expected keys per class: the n-th of 1/64 of the pixels ranks about 64*n-th overall; x4 head room
       // (never below one 64-key block: a huge cap_div then still takes the documented overflow fallback instead of
@@ -167,17 +201,24 @@ Fcn8Ws fcn8_ws_layout(int n, int h, int w, int C, int dtype, int out_mode, int d
   return W;
 }
 
-static int check_fcn8_shape(int n, int h, int w, int C, int dtype) {
+// The operand type and class count every entry point takes; `what` names the entry point in the message.
+static int check_dtype_classes(const char* what, int dtype, int C) {
   if (dtype != FLM_F32 && dtype != FLM_BF16) {
-    set_error("fcn8: unknown dtype %d (FLM_F32 = 0, FLM_BF16 = 1)", dtype);
+    set_error("%s: unknown dtype %d (FLM_F32 = 0, FLM_BF16 = 1)", what, dtype);
     return FLM_ERR_UNSUPPORTED;
   }
-  if (n <= 0 || h <= 0 || w <= 0 || (h % 32) || (w % 32)) {
-    set_error("fcn8: input must be [N>0, H, W, 3] with H and W multiples of 32 (got n=%d h=%d w=%d)", n, h, w);
+  if (C < 1 || C > kMaxClasses) {
+    set_error("%s: n_classes must be in [1,%d] (got %d)", what, kMaxClasses, C);
     return FLM_ERR_SHAPE;
   }
-  if (C < 1 || C > kMaxClasses) {
-    set_error("fcn8: n_classes must be in [1,%d] (got %d)", kMaxClasses, C);
+  return FLM_OK;
+}
+
+static int check_fcn8_shape(int n, int h, int w, int C, int dtype) {
+  const int rc = check_dtype_classes("fcn8", dtype, C);
+  if (rc) return rc;
+  if (n <= 0 || h <= 0 || w <= 0 || (h % 32) || (w % 32)) {
+    set_error("fcn8: input must be [N>0, H, W, 3] with H and W multiples of 32 (got n=%d h=%d w=%d)", n, h, w);
     return FLM_ERR_SHAPE;
   }
   // (factors bounded first: the product below then fits 64 bits -- found by the UBSan sweep, tests/test_abi_sanitized.py)
@@ -211,6 +252,26 @@ static int conv_layer(hipStream_t s, const char* blob, const ConvPack& c, const 
   return launch_igemm(s, d);
 }
 
+// The decoder's transposed convs on an hi x wi input grid (networks/fcn.py).  up5 / up4 (fcn.py:104-119): stride 2, crop
+// to 2hi x 2wi and Add in place onto the skip map y holds.  up3 (fcn.py:121; fcn_32's 64x64 stride-32 form, fcn.py:143-146):
+// stride s = 8 | 32 to the raw [n, s*hi + s, s*wi + s, C] map; the caller sets another epilogue and its buffers.
+static ConvTDesc up_desc(const Fcn8Pack& L, const char* blob, int layer, int n, int hi, int wi, const float* x, void* y) {
+  ConvTDesc t;
+  t.g = L.g;
+  t.n = n; t.hi = hi; t.wi = wi;
+  t.x = x; t.y = y;
+  t.epilogue = 0;
+  t.s = layer != 3 ? 2 : (L.spec.fcn32 ? 32 : 8);
+  if (layer == 3) {
+    t.wf = blob + L.up3; t.skip = nullptr;
+    t.ho = t.s * hi + t.s; t.wo = t.s * wi + t.s; t.ldy = L.g.C;
+  } else {
+    t.wf = blob + (layer == 5 ? L.up5 : L.up4); t.skip = static_cast<const float*>(y);
+    t.ho = 2 * hi; t.wo = 2 * wi; t.ldy = L.g.Cp;
+  }
+  return t;
+}
+
 }  // namespace flm
 
 using namespace flm;
@@ -227,100 +288,30 @@ int flm_debug_query(const char* key, int arg) {
 int flm_set_tuning(const char* key, int value) {
   if (!key) return FLM_ERR_ARG;
   if (!strcmp(key, "none")) return FLM_OK;
-  if (!strcmp(key, "bf16_big_tiles")) {  // 256-row bf16 implicit-GEMM tiles on/off (A/B runs of tools/tune.py)
-    flm::igemm_bf16_big_enable(value);
-    return FLM_OK;
-  }
-  if (!strcmp(key, "f32_two_level")) {  // fp32 implicit GEMMs: two-level accumulation (1) or one chain per output (0)
-    flm::igemm_f32_group(value ? 0 : -1);
-    return FLM_OK;
-  }
-  if (!strcmp(key, "f32_lean_tile")) {  // fp32 implicit GEMMs (row-major and pooled): lean set-up and write-out (1) or the plain ones (0)
-    flm::igemm_f32_lean_enable(value);
-    return FLM_OK;
-  }
-  if (!strcmp(key, "bf16_mfma16")) {  // 256x256 LDS-DMA tiles on v_mfma_f32_16x16x32_bf16 (1) or 32x32x16 (0)
-    flm::igemm_bf16_big_m16(value);
-    return FLM_OK;
-  }
-  if (!strcmp(key, "bf16_halo_mfma16")) {  // the halo-resident 3x3 kernel on v_mfma_f32_16x16x32_bf16 (1) or 32x32x16 (0)
-    flm::conv3_halo_m16(value);
-    return FLM_OK;
-  }
-  if (!strcmp(key, "bf16_lds_dma")) {  // 256x256 tiles: operands by buffer_load ... lds (1) or through registers (0)
-    flm::igemm_bf16_big_dma(value);
-    return FLM_OK;
-  }
   if (!strcmp(key, "landmark_candidates") || !strcmp(key, "candidate_sub_phases") || !strcmp(key, "candidate_cap_div")) {
     set_error("flm_set_tuning: '%s' changes the workspace layout and is a per-call option now: pass flm_forward_opts to "
               "flm_fcn_workspace_bytes_opts / flm_fcn_forward_opts", key);
     return FLM_ERR_ARG;
   }
-  if (!strcmp(key, "up3_cand8")) {  // candidate launch of up3: bit 0 = bf16 takes the 8-wave kernel (default 1), bit 2 = its
-                                    // 4-wave shape; bit 1 (the fp32 form) is accepted and ignored since round 3
-    if (value < 0 || value > 7) {
-      set_error("flm_set_tuning: up3_cand8 must be in [0,7]");
-      return FLM_ERR_ARG;
-    }
-    flm::convt_cand8_enable(value);
-    return FLM_OK;
+  Knob* k = find_knob("flm_set_tuning", key);
+  if (!k) return FLM_ERR_ARG;
+  if (k->valid && !k->valid(value)) {
+    set_error("flm_set_tuning: %s must be %s", key, k->domain);
+    return FLM_ERR_ARG;
   }
-  if (!strcmp(key, "up3_cand8_rows")) {  // phase rows per workgroup of that kernel: 0 automatic, else 1, 2, 4 or 8
-    if (value < 0 || value > 8 || (value & (value - 1))) {
-      set_error("flm_set_tuning: up3_cand8_rows must be 0, 1, 2, 4 or 8");
-      return FLM_ERR_ARG;
-    }
-    flm::convt_cand8_rows(value);
-    return FLM_OK;
+  k->value.store(value, std::memory_order_relaxed);
+  return FLM_OK;
+}
+
+int flm_get_tuning(const char* key, int* value) {
+  if (!key || !value) {
+    set_error("flm_get_tuning: null argument");
+    return FLM_ERR_ARG;
   }
-  if (!strcmp(key, "up3_wreg")) {  // bf16 candidate launch of up3: 1 the weights-in-registers kernel (flm_up3_wreg.hip)
-                                   // where its conditions hold, 0 (default) always the 8-wave kernel.  Same keys
-    if (value < 0 || value > 1) {
-      set_error("flm_set_tuning: up3_wreg must be 0 or 1");
-      return FLM_ERR_ARG;
-    }
-    flm::convt_wreg_enable(value);
-    return FLM_OK;
-  }
-  if (!strcmp(key, "bf16_score1x1")) {  // register-resident 1x1 classifier kernel for 256-channel inputs: 0 off, 1 on
-    flm::score1x1_enable(value);
-    return FLM_OK;
-  }
-  if (!strcmp(key, "bf16_fused_tail")) {  // score3 + up4 as one launch (flm_tail_bf16.hip): 0 off, 1 on.  Same bits
-    flm::tail_fused_enable(value);
-    return FLM_OK;
-  }
-  if (!strcmp(key, "decode_lds_dma")) {  // standalone decode of 68-landmark maps: tiles by LDS-DMA (1) or register prefetch (0)
-    flm::decode_dma_enable(value);
-    return FLM_OK;
-  }
-  if (!strcmp(key, "posmajor_order")) {  // fc6 at batches below a tile's rows: positions sharing a tile chosen by their taps (1) or in map order (0)
-    flm::igemm_posperm_enable(value);
-    return FLM_OK;
-  }
-  if (!strcmp(key, "warp_rows")) {  // uint8 warp, destination width % 64 == 0: a wave per row segment, 2 rows per wave (1;
-                                    // 4: four rows) or the pixel-list kernel (0)
-    if (value != 0 && value != 1 && value != 4) {
-      set_error("flm_set_tuning: warp_rows must be 0, 1 or 4");
-      return FLM_ERR_ARG;
-    }
-    flm::warp_rows_enable(value);
-    return FLM_OK;
-  }
-  if (!strcmp(key, "bf16_conv3_halo")) {  // halo-resident 3x3 kernel for 64-channel inputs: 0 off, 1 auto, 2 always
-    flm::conv3_halo_enable(value);
-    return FLM_OK;
-  }
-  if (!strcmp(key, "bf16_group_n")) {  // weight panels per tile group of the 256-row kernel (0: default)
-    if (value < 0 || value > 32 || (value & (value - 1))) {
-      set_error("flm_set_tuning: bf16_group_n must be 0 or a power of two <= 32");
-      return FLM_ERR_ARG;
-    }
-    flm::igemm_bf16_group_n(value);
-    return FLM_OK;
-  }
-  set_error("flm_set_tuning: unknown key '%s'", key);
-  return FLM_ERR_ARG;
+  const Knob* k = find_knob("flm_get_tuning", key);
+  if (!k) return FLM_ERR_ARG;
+  *value = k->value.load(std::memory_order_relaxed);
+  return FLM_OK;
 }
 
 int flm_profile_enable(int max_records) {
@@ -378,8 +369,7 @@ int flm_profile_filter(const char* layer) {
 const char* flm_last_error(void) { return g_err; }
 
 static size_t packed_bytes_impl(int n_classes, int dtype, int arch) {
-  if ((dtype != FLM_F32 && dtype != FLM_BF16) || n_classes < 1 || n_classes > kMaxClasses) return 0;
-  if (!arch_spec(arch).valid) return 0;
+  if (check_dtype_classes("flm_fcn_packed_bytes", dtype, n_classes) || !arch_spec(arch).valid) return 0;
   return fcn8_pack_layout(n_classes, dtype, arch).total;
 }
 size_t flm_fcn_packed_bytes(int arch, int n_classes, int dtype) { return packed_bytes_impl(n_classes, dtype, arch); }
@@ -396,14 +386,8 @@ static int pack_impl(flm_stream_t stream, const flm_fcn_params* p, int n_classes
     set_error("flm_fcn8_pack: null argument");
     return FLM_ERR_ARG;
   }
-  if (dtype != FLM_F32 && dtype != FLM_BF16) {
-    set_error("flm_fcn8_pack: unknown dtype %d", dtype);
-    return FLM_ERR_UNSUPPORTED;
-  }
-  if (n_classes < 1 || n_classes > kMaxClasses) {
-    set_error("flm_fcn8_pack: n_classes must be in [1,%d]", kMaxClasses);
-    return FLM_ERR_SHAPE;
-  }
+  const int rc = check_dtype_classes("flm_fcn8_pack", dtype, n_classes);
+  if (rc) return rc;
   const Fcn8Pack L = fcn8_pack_layout(n_classes, dtype, arch);
   if (packed_bytes < L.total) {
     set_error("flm_fcn8_pack: packed buffer too small (%zu < %zu)", packed_bytes, L.total);
@@ -533,6 +517,15 @@ static int forward_impl(flm_stream_t stream, const void* packed_dev, const void*
   float* fuse4 = reinterpret_cast<float*>(ws + W.fuse4);
   float* seg = reinterpret_cast<float*>(ws + W.seg);
 
+  const int h5 = h / 32, w5 = w / 32, h4 = h / 16, w4 = w / 16, h3 = h / 8, w3 = w / 8;
+  // one implicit-GEMM layer of this call under the profile record `name` (null: the caller holds one), with the split-K
+  // scratch where `splitk`
+  const auto conv = [&](const char* name, const ConvPack& c, const void* x, void* y, int hh, int ww, int relu, int pool,
+                        int posmajor, int out_f32, bool splitk) {
+    ProfScope ps(s, name);
+    return conv_layer(s, blob, c, x, y, n, hh, ww, relu, pool, posmajor, dtype, out_f32,
+                      splitk ? reinterpret_cast<float*>(ws + W.splitk) : nullptr, splitk ? W.splitk_bytes : 0);
+  };
   // encoder: vanilla (networks/fcn.py:10-51) or VGG16 (networks/vgg16.py:27-72)
   static const EncNames enc_name_table;  // "enc1".."enc64" (profile record labels); built once, thread-safe (C++11 statics)
   const char (*enc_names)[8] = enc_name_table.s;
@@ -572,8 +565,7 @@ static int forward_impl(flm_stream_t stream, const void* packed_dev, const void*
         rc = launch_mb_depthwise(s, xin, n, hi, wi, e.cin, e.stride, w0, sc0, sh0, yout, bf);
         break;
       case ENC_CONV3:
-        rc = conv_layer(s, blob, L.enc[i], xin, yout, n, hi, wi, /*relu*/ 1, e.pool, 0, dtype, 0,
-                        reinterpret_cast<float*>(ws + W.splitk), W.splitk_bytes);
+        rc = conv(nullptr, L.enc[i], xin, yout, hi, wi, /*relu*/ 1, e.pool, 0, 0, true);
         break;
       case ENC_MB_PW:
         if (L.enc[i].cin != e.cin) {
@@ -603,71 +595,43 @@ static int forward_impl(flm_stream_t stream, const void* packed_dev, const void*
     }
     if (rc) return rc;
   }
-  const int h5 = h / 32, w5 = w / 32, h4 = h / 16, w4 = w / 16, h3 = h / 8, w3 = w / 8;
   // head (fcn.py:98-103); Dropout is the identity at inference
-  { ProfScope ps(s, "fc6");
-  rc = conv_layer(s, blob, L.fc6, f[4], fc6, n, h5, w5, 1, 0, /*posmajor*/ 1, dtype, 0,
-                  reinterpret_cast<float*>(ws + W.splitk), W.splitk_bytes); }
-  if (rc) return rc;
-  { ProfScope ps(s, "fc7");
-  rc = conv_layer(s, blob, L.fc7, fc6, fc7, n, h5, w5, 1, 0, 0, dtype, 0,
-                  reinterpret_cast<float*>(ws + W.splitk), W.splitk_bytes); }
-  if (rc) return rc;
-  { ProfScope ps(s, "score5");
-  rc = conv_layer(s, blob, L.score5, fc7, score5, n, h5, w5, 0, 0, 0, dtype, /*out_f32*/ 1,
-                  reinterpret_cast<float*>(ws + W.splitk), W.splitk_bytes); }
-  if (rc) return rc;
-  ConvTDesc t;
-  t.g = L.g;
-  t.n = n;
+  if ((rc = conv("fc6", L.fc6, f[4], fc6, h5, w5, 1, 0, /*posmajor*/ 1, 0, true))) return rc;
+  if ((rc = conv("fc7", L.fc7, fc6, fc7, h5, w5, 1, 0, 0, 0, true))) return rc;
+  if ((rc = conv("score5", L.score5, fc7, score5, h5, w5, 0, 0, 0, /*out_f32*/ 1, true))) return rc;
   if (!fcn32) {
-  // skip branches: score4 on f4 -> fuse4 buffer, score3 on f3 -> seg buffer, then the transposed
-  // convs add themselves onto those (crop keeps the top-left window, fcn.py:76-84)
-  { ProfScope ps(s, "score4");
-  rc = conv_layer(s, blob, L.score4, f[3], fuse4, n, h4, w4, 0, 0, 0, dtype, 1); }
-  if (rc) return rc;
-  // (bf16, 68 classes: score3 and up4 run as ONE launch after up5, flm_tail_bf16.hip -- same bits)
-  const bool fuse_seg = bf && L.g.C == 68 && L.score3.cin == 256 && L.score3.kh == 1;
-  int fused_seg = 0;
-  if (!fuse_seg) {
-  { ProfScope ps(s, "score3");
-  rc = conv_layer(s, blob, L.score3, f[2], seg, n, h3, w3, 0, 0, 0, dtype, 1); }
-  if (rc) return rc;
-  }
-  // up5 (fcn.py:104) + crop + Add (fcn.py:110-112), in place on fuse4
-  t.x = score5; t.wf = blob + L.up5; t.skip = fuse4; t.y = fuse4;
-  t.hi = h5; t.wi = w5; t.ho = h4; t.wo = w4; t.s = 2; t.ldy = L.g.Cp; t.epilogue = 0;
-  { ProfScope ps(s, "up5");
-  rc = launch_convt(s, t); }
-  if (rc) return rc;
-  // up4 (fcn.py:114) + crop + Add (fcn.py:118-119), in place on seg ("seg_feats")
-  if (fuse_seg) {
-    ProfScope ps(s, "seg_fused");
-    fused_seg = launch_seg_fused_bf16(s, fuse4, blob + L.up4, f[2], blob + L.score3.w,
+    // skip branches: score4 on f4 -> fuse4 buffer, score3 on f3 -> seg buffer, then the transposed
+    // convs add themselves onto those (crop keeps the top-left window, fcn.py:76-84)
+    if ((rc = conv("score4", L.score4, f[3], fuse4, h4, w4, 0, 0, 0, 1, false))) return rc;
+    const auto score3 = [&] { return conv("score3", L.score3, f[2], seg, h3, w3, 0, 0, 0, 1, false); };
+    const auto up5 = [&] {  // up5 (fcn.py:104) + crop + Add (fcn.py:110-112), in place on fuse4
+      ProfScope ps(s, "up5");
+      return launch_convt(s, up_desc(L, blob, 5, n, h5, w5, score5, fuse4));
+    };
+    const auto up4 = [&] {  // up4 (fcn.py:114) + crop + Add (fcn.py:118-119), in place on seg ("seg_feats")
+      ProfScope ps(s, "up4");
+      return launch_convt(s, up_desc(L, blob, 4, n, h4, w4, fuse4, seg));
+    };
+    // (bf16, 68 classes: score3 and up4 run as ONE launch after up5, flm_tail_bf16.hip -- same bits)
+    if (!(bf && L.g.C == 68 && L.score3.cin == 256 && L.score3.kh == 1)) {
+      if ((rc = score3()) || (rc = up5()) || (rc = up4())) return rc;
+    } else {
+      if ((rc = up5())) return rc;
+      int fused;
+      { ProfScope ps(s, "seg_fused");
+        fused = launch_seg_fused_bf16(s, fuse4, blob + L.up4, f[2], blob + L.score3.w,
                                       reinterpret_cast<const float*>(blob + L.score3.scale),
                                       reinterpret_cast<const float*>(blob + L.score3.shift), seg, n, h4, w4, L.g.C, L.g.Cp,
-                                      L.g.G, L.score3.cin, L.score3.coutpad);
-    if (fused_seg < 0) return fused_seg;
+                                      L.g.G, L.score3.cin, L.score3.coutpad); }
+      if (fused < 0) return fused;
+      // (knob off, or a shape the fused kernel leaves alone: the two-launch form)
+      if (!fused && ((rc = score3()) || (rc = up4()))) return rc;
+    }
   }
-  if (fuse_seg && !fused_seg) {  // (knob off, or a shape the fused kernel leaves alone: the two-launch form)
-    ProfScope ps(s, "score3");
-    rc = conv_layer(s, blob, L.score3, f[2], seg, n, h3, w3, 0, 0, 0, dtype, 1);
-    if (rc) return rc;
-  }
-  t.x = fuse4; t.wf = blob + L.up4; t.skip = seg; t.y = seg;
-  t.hi = h4; t.wi = w4; t.ho = h3; t.wo = w3;
-  if (!fused_seg) {
-  { ProfScope ps(s, "up4");
-  rc = launch_convt(s, t); }
-  if (rc) return rc;
-  }
-  }  // !fcn32
   // last upsampling + softmax (networks/utils.py:30) / argmax (prediction.py:209):
   //   fcn_8 : Conv2DTranspose(16x16, s8) on seg_feats  (fcn.py:121)
   //   fcn_32: Conv2DTranspose(64x64, s32) on the 1x1 classifier output  (fcn.py:143-146)
-  t.wf = blob + L.up3; t.skip = nullptr; t.ho = W.oh; t.wo = W.ow; t.ldy = C;
-  if (fcn32) { t.x = score5; t.hi = h5; t.wi = w5; t.s = 32; }
-  else { t.x = seg; t.hi = h3; t.wi = w3; t.s = 8; }
+  ConvTDesc t = fcn32 ? up_desc(L, blob, 3, n, h5, w5, score5, nullptr) : up_desc(L, blob, 3, n, h3, w3, seg, nullptr);
   if (out_mode == FLM_OUT_LOGITS || out_mode == FLM_OUT_PROBS) {
     t.y = out_dev;
     t.epilogue = (out_mode == FLM_OUT_PROBS) ? 1 : 0;
@@ -696,13 +660,12 @@ static int forward_impl(flm_stream_t stream, const void* packed_dev, const void*
     unsigned long long* cand = reinterpret_cast<unsigned long long*>(ws + W.cand);
     FLM_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned) * ((size_t)n + 1), s));
     ConvTDesc ts = t;
-    ts.y = sub; ts.epilogue = 4; ts.sub = cand_sub_for(co, n_points, L.g.bf16 != 0);
+    ts.y = sub; ts.epilogue = 4; ts.sub = W.cand_sub;
     { ProfScope ps(s, "up3_sub");
     rc = launch_convt(s, ts); }
     if (rc) return rc;
     { ProfScope ps(s, "tau");
-    rc = launch_cand_tau(s, reinterpret_cast<const unsigned*>(sub), n, convt_sample_slots(L.g, t.hi, t.wi, cand_sub_for(co, n_points, L.g.bf16 != 0)), 16 * L.g.MT, C,
-                         n_points, tau); }
+    rc = launch_cand_tau(s, reinterpret_cast<const unsigned*>(sub), n, convt_sample_slots(L.g, t.hi, t.wi, W.cand_sub), 16 * L.g.MT, C, n_points, tau); }
     if (rc) return rc;
     ConvTDesc tc = t;
     tc.y = nullptr; tc.epilogue = 3; tc.tau = tau; tc.cand = cand; tc.cand_cnt = cnt; tc.cand_cap = W.cand_cap;
@@ -734,10 +697,7 @@ int flm_fcn8_run_layer(flm_stream_t stream, const void* packed_dev, const char* 
     set_error("flm_fcn8_run_layer: bad argument");
     return FLM_ERR_ARG;
   }
-  if ((dtype != FLM_F32 && dtype != FLM_BF16) || C < 1 || C > kMaxClasses) {
-    set_error("flm_fcn8_run_layer: unsupported dtype/n_classes");
-    return FLM_ERR_UNSUPPORTED;
-  }
+  if (check_dtype_classes("flm_fcn8_run_layer", dtype, C)) return FLM_ERR_UNSUPPORTED;
   const Fcn8Pack L = fcn8_pack_layout(C, dtype);
   const char* blob = static_cast<const char*>(packed_dev);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -749,25 +709,13 @@ int flm_fcn8_run_layer(flm_stream_t stream, const void* packed_dev, const char* 
   if (!strcmp(layer, "score4")) return conv_layer(s, blob, L.score4, x_dev, y_dev, n, h, w, 0, 0, 0, dtype, 1);
   if (!strcmp(layer, "score3")) return conv_layer(s, blob, L.score3, x_dev, y_dev, n, h, w, 0, 0, 0, dtype, 1);
   if (!strcmp(layer, "up5") || !strcmp(layer, "up4") || !strcmp(layer, "up3")) {
-    // the decoder's transposed convs, as forward_impl launches them (always launch_convt, never the fused up4 + score3)
-    ConvTDesc t;
-    t.g = L.g;
-    t.n = n;
-    t.x = static_cast<const float*>(x_dev);
-    t.hi = h; t.wi = w; t.epilogue = 0;
-    if (layer[2] == '3') {  // raw logits [n,8h+8,8w+8,C]
-      if (C & 3) {
-        set_error("flm_fcn8_run_layer: \"up3\" writes raw logits, which needs n_classes %% 4 == 0");
-        return FLM_ERR_UNSUPPORTED;
-      }
-      t.wf = blob + L.up3; t.skip = nullptr; t.y = y_dev;
-      t.ho = 8 * h + 8; t.wo = 8 * w + 8; t.s = 8; t.ldy = C;
-    } else {  // crop + Add in place on the skip map y_dev holds
-      t.wf = blob + (layer[2] == '5' ? L.up5 : L.up4);
-      t.skip = static_cast<const float*>(y_dev); t.y = y_dev;
-      t.ho = 2 * h; t.wo = 2 * w; t.s = 2; t.ldy = L.g.Cp;
+    // the decoder's transposed convs, as forward_impl launches them (always launch_convt, never the fused up4 + score3):
+    // up5 / up4 crop + Add in place on the skip map y_dev holds, up3 writes raw logits [n,8h+8,8w+8,C]
+    if (layer[2] == '3' && (C & 3)) {
+      set_error("flm_fcn8_run_layer: \"up3\" writes raw logits, which needs n_classes %% 4 == 0");
+      return FLM_ERR_UNSUPPORTED;
     }
-    return launch_convt(s, t);
+    return launch_convt(s, up_desc(L, blob, layer[2] - '0', n, h, w, static_cast<const float*>(x_dev), y_dev));
   }
   set_error("flm_fcn8_run_layer: unknown layer '%s'", layer);
   return FLM_ERR_ARG;

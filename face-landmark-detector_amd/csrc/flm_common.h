@@ -136,12 +136,24 @@ struct Fcn8Ws {
   // landmark mode without the probability tensor (flm_convt.hip); cand == SIZE_MAX when not used
   size_t sub, tau, cand, cand_cnt;
   int cand_cap;
+  int cand_sub;  // phases the sampling launch takes per tile
   size_t total;
   int oh, ow;
 };
 // `opts` (NULL = defaults) carries the per-call options that change the layout (include/flm.h: flm_forward_opts).
 Fcn8Ws fcn8_ws_layout(int n, int h, int w, int C, int dtype, int out_mode, int decode_mode, int n_points,
                       int arch = 0, const flm_forward_opts* opts = nullptr);
+
+// ---- A/B knobs (flm_set_tuning / flm_get_tuning; include/flm.h documents every key) ----------
+// One row per knob in the table of flm_api.hip, in this order.  A launcher reads each knob it uses exactly ONCE per
+// launch, into a local const int, and decides from that: calls may run concurrently with a setter, and a launch must not
+// mix two configurations.
+enum KnobId {
+  KNOB_BF16_BIG_TILES, KNOB_BF16_LDS_DMA, KNOB_BF16_MFMA16, KNOB_BF16_HALO_MFMA16, KNOB_F32_TWO_LEVEL, KNOB_F32_LEAN_TILE,
+  KNOB_BF16_GROUP_N, KNOB_BF16_CONV3_HALO, KNOB_BF16_SCORE1X1, KNOB_BF16_FUSED_TAIL, KNOB_DECODE_LDS_DMA,
+  KNOB_POSMAJOR_ORDER, KNOB_WARP_ROWS, KNOB_UP3_CAND8, KNOB_UP3_CAND8_ROWS, KNOB_UP3_WREG, KNOB_COUNT
+};
+int tuning(KnobId id);  // the knob's current value (relaxed load)
 
 // ---- kernel launchers (each returns FLM_OK or an error) --------------------------------------
 int launch_pack_fcn(hipStream_t s, const flm_fcn_params& p, int C, const Fcn8Pack& L, char* blob);
@@ -170,19 +182,6 @@ struct IgemmDesc {
 };
 int launch_igemm(hipStream_t s, const IgemmDesc& d);
 int igemm_occupancy(size_t lds_bytes);
-void igemm_f32_group(int steps);
-void igemm_f32_lean_enable(int on);
-void igemm_bf16_big_enable(int on);
-void igemm_bf16_group_n(int gn);
-void igemm_bf16_big_dma(int on);
-void igemm_bf16_big_m16(int on);
-void conv3_halo_enable(int on);
-void conv3_halo_m16(int on);
-void score1x1_enable(int on);
-void tail_fused_enable(int on);
-void decode_dma_enable(int on);
-void warp_rows_enable(int on);
-void igemm_posperm_enable(int on);
 // seg_feats = crop(up4(fuse4)) + score3(f3) in one launch (flm_tail_bf16.hip; bf16, 68 classes, 256-channel f3):
 // 1 launched, 0 shape left to the two-launch form, < 0 error
 int launch_seg_fused_bf16(hipStream_t s, const float* fuse4, const void* w4_packed, const void* f3, const void* w3,
@@ -219,9 +218,6 @@ __host__ __device__ inline int convt_share_layout(const ConvTGeom& g, int s) {
   return g.C == 68 && (g.bf16 ? g.G == 9 : g.G == 17) && (s % 4) == 0;
 }
 int convt_sample_slots(const ConvTGeom& g, int hi, int wi, int sub);
-void convt_cand8_enable(int mask);  // A/B knob "up3_cand8"
-void convt_cand8_rows(int rpw);     // A/B knob "up3_cand8_rows"
-void convt_wreg_enable(int on);     // A/B knob "up3_wreg"
 int launch_cand_tau(hipStream_t s, const unsigned* wave_max, int n, int slots, int ld, int l, int n_points, float* tau);
 
 // (activations fp32, or bf16 when `bf16`)

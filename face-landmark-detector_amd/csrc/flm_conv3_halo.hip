@@ -248,11 +248,6 @@ __global__ __launch_bounds__(256, 1) void conv3_halo_bf16_kernel(IgemmArgs a, in
 #undef FLM_FINAL_EPI
 }
 
-static std::atomic<int> g_halo_enable{1};  // A/B knob: never changes results or layouts
-void conv3_halo_enable(int on) { g_halo_enable.store(on, std::memory_order_relaxed); }
-static std::atomic<int> g_halo_m16{1};     // 16x16x32 MFMAs (1) or 32x32x16 (0); same bits
-void conv3_halo_m16(int on) { g_halo_m16.store(on, std::memory_order_relaxed); }
-
 template <bool POOL, bool RELU, bool M16>
 static int launch_halo_t(hipStream_t s, const IgemmArgs& a, int slices) {
   constexpr size_t lds = WSLICE_BYTES + 2 * HALO_BYTES;
@@ -269,15 +264,16 @@ static int launch_halo_t(hipStream_t s, const IgemmArgs& a, int slices) {
 
 // 1: launched; 0: shape left to the implicit-GEMM kernels
 int launch_conv3_halo_bf16(hipStream_t s, const IgemmArgs& a, int relu, int pool, int posmajor) {
-  if (!g_halo_enable || a.kh != 3 || a.kw != 3 || a.pad != 1 || a.stride != 1 || a.cin != 64 || a.res || posmajor ||
+  const int enable = tuning(KNOB_BF16_CONV3_HALO);
+  if (!enable || a.kh != 3 || a.kw != 3 || a.pad != 1 || a.stride != 1 || a.cin != 64 || a.res || posmajor ||
       a.ksplit > 1 || a.out_f32 || (a.cout % 64) || (a.h % HT) || (a.w % HT) || (a.ldc & 1) ||
       (long long)a.n * a.h * a.w * 128 >= (1ll << 31))
     return 0;
   const int slices = a.cout / 64;
   if (slices > 256) return 0;
-  // few tiles: the implicit GEMM fills the chip better (g_halo_enable == 2 forces this kernel: tests)
-  if (g_halo_enable != 2 && (long long)a.n * (a.h / HT) * (a.w / HT) * slices < 1024) return 0;
-  if (g_halo_m16.load(std::memory_order_relaxed)) {
+  // few tiles: the implicit GEMM fills the chip better (knob value 2 forces this kernel: tests)
+  if (enable != 2 && (long long)a.n * (a.h / HT) * (a.w / HT) * slices < 1024) return 0;
+  if (tuning(KNOB_BF16_HALO_MFMA16)) {  // 16x16x32 MFMAs (1) or 32x32x16 (0); same bits
     if (pool) return relu ? launch_halo_t<true, true, true>(s, a, slices) : launch_halo_t<true, false, true>(s, a, slices);
     return relu ? launch_halo_t<false, true, true>(s, a, slices) : launch_halo_t<false, false, true>(s, a, slices);
   }

@@ -1088,9 +1088,6 @@ __global__ __launch_bounds__(WAVES * 64, 2) void up3_cand8_kernel(ConvTArgs a) {
 }
 #undef FLM_PIN
 
-static std::atomic<int> g_cand8_rpw{0};  // A/B knob "up3_cand8_rows": 0 = automatic, else phase rows per workgroup (1, 2, 4, 8)
-void convt_cand8_rows(int rpw) { g_cand8_rpw.store(rpw, std::memory_order_relaxed); }
-
 template <bool BF, int WAVES, int STEP_G>
 static int launch_cand8(hipStream_t st, ConvTArgs a) {
   using namespace cand8;
@@ -1102,7 +1099,7 @@ static int launch_cand8(hipStream_t st, ConvTArgs a) {
   a.ppf = cdiv((a.hi + 1) * (a.wi + 1), 16 * NT) * 16 * NT;  // per-face padding at wave granularity
   const long long pos = (long long)a.n * a.ppf;
   const int xblocks = (int)((pos + WAVES * 16 * NT - 1) / (WAVES * 16 * NT));
-  a.rpw = convt_rows_per_wg(xblocks, a.s, 256 * (8 / WAVES), g_cand8_rpw.load(std::memory_order_relaxed));
+  a.rpw = convt_rows_per_wg(xblocks, a.s, 256 * (8 / WAVES), tuning(KNOB_UP3_CAND8_ROWS));  // (knob: 0 = automatic, else phase rows per workgroup)
   up3_cand8_kernel<BF, WAVES, STEP_G><<<dim3(xblocks, a.s / a.rpw), WAVES * 64, lds, st>>>(a);
   FLM_LAUNCH_CHECK("up3_cand8_kernel");
   return FLM_OK;
@@ -1146,12 +1143,6 @@ int convt_sample_slots(const ConvTGeom& g, int hi, int wi, int sub) {
   return 4 * cdiv((hi + 1) * (wi + 1), 64 * nt) * sub;
 }
 
-// A/B knob (flm_set_tuning "up3_cand8"): bit 0 the 8-wave kernel above for the bf16 candidate launch (default 1), bit 2
-// its 4-wave shape, 0 the generic kernel; same keys either way, so it never changes results or layouts.  Bit 1 asked for
-// an fp32 form (a tie at best); retired when the generic kernel's fp32 sum became two-level
-static std::atomic<int> g_cand8{1};
-void convt_cand8_enable(int on) { g_cand8.store(on, std::memory_order_relaxed); }
-
 int convt_candidates_supported(const ConvTGeom& g) {
   return g.C == 68 && ((g.bf16 && g.G == 9) || (!g.bf16 && g.G == 17));
 }
@@ -1190,7 +1181,9 @@ int launch_convt(hipStream_t st, const ConvTDesc& d) {
       set_error("convt: the candidate epilogue is built for strides that are multiples of 4");
       return FLM_ERR_UNSUPPORTED;
     }
-    const int c8 = g_cand8.load(std::memory_order_relaxed);  // bit 0: bf16, bit 1: fp32, bit 2: the 4-wave shape
+    // knob "up3_cand8": bit 0 the 8-wave kernel above for the bf16 candidate launch (default 1), bit 2 its 4-wave shape,
+    // 0 the generic kernel; same keys either way.  Bit 1 asked for an fp32 form (a tie at best; retired, see below)
+    const int c8 = tuning(KNOB_UP3_CAND8);
     // (the 8-wave kernel decodes a phase as (b >> log2 s, b & (s - 1)): s a power of two, checked above)
     if ((d.s & 3) == 0 && d.s >= 4 && (d.s & (d.s - 1)) == 0 && (long long)d.s * d.s * cand8::Cfg<false>::PHASE_BYTES < 0x7fffffffll) {
       if (d.g.bf16 && (c8 & 1)) {

@@ -552,8 +552,6 @@ __global__ __launch_bounds__(64) void decode_merge_all_kernel(DecodeArgs a) {
   out[1] = y;
 }
 
-static std::atomic<int> g_decode_dma{1};  // A/B knob "decode_lds_dma": same results either way
-void decode_dma_enable(int on) { g_decode_dma.store(on, std::memory_order_relaxed); }
 
 // Chunks per face.  The kernel holds 155 registers: three workgroups per CU, 768 on the chip at a time.  What counts is
 // that the launch is whole rounds of those 768 -- 1024 or 1152 workgroups run a second, mostly empty round (batch 512:
@@ -629,8 +627,9 @@ static int sweep_check_modes(const int* modes, int n_modes, int* n_max, int* has
 }
 
 // 68-landmark maps, 16-byte-aligned faces, one list register: the LDS-DMA form (a chunk stays below the 2 GiB buffer range)
+// (knob "decode_lds_dma": same results either way)
 static bool use_dma(int l, int vec, bool wide, int chunk_px) {
-  return g_decode_dma.load(std::memory_order_relaxed) && l == DL && vec && !wide && (long long)chunk_px * DL * 4 < (1ll << 31);
+  return tuning(KNOB_DECODE_LDS_DMA) && l == DL && vec && !wide && (long long)chunk_px * DL * 4 < (1ll << 31);
 }
 
 constexpr size_t kRingLds = (size_t)D_RING * D_TILE_B;
@@ -683,8 +682,9 @@ static int decode_run(const char* who, hipStream_t s, const float* hm, int n, in
   const bool wide = n_max > 64;  // two list registers per lane (the reference's sweep reaches n = 81)
   const bool big = l > 68;       // 24 channels per wave instead of 17
   const size_t tile_lds = sizeof(float) * PT * (l | 1);
+  const bool dma = use_dma(l, a.vec, wide, a.chunk_px);
   if (kind == kDecodeAll) {
-    if (use_dma(l, a.vec, wide, a.chunk_px)) {
+    if (dma) {
       static FuncAttrOnce attr;
       FLM_FUNC_ATTR_ONCE(attr, (&decode_partial_all_dma_kernel), kRingLds);
       decode_partial_all_dma_kernel<<<grid, 256, kRingLds, s>>>(a);
@@ -698,7 +698,7 @@ static int decode_run(const char* who, hipStream_t s, const float* hm, int n, in
     FLM_LAUNCH_CHECK("decode_merge_all_kernel");
     return FLM_OK;
   }
-  if (use_dma(l, a.vec, wide, a.chunk_px)) {
+  if (dma) {
     const int rc = has_all ? launch_partial_dma<true>(s, grid, a) : launch_partial_dma<false>(s, grid, a);
     if (rc != FLM_OK) return rc;
     FLM_LAUNCH_CHECK("decode_partial_dma_kernel");

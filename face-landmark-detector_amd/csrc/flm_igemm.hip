@@ -778,9 +778,6 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
   }  // pass
 }
 
-static std::atomic<int> g_posperm{1};  // A/B knob "posmajor_order": same results either way
-void igemm_posperm_enable(int on) { g_posperm.store(on, std::memory_order_relaxed); }
-int igemm_posperm_enabled() { return g_posperm.load(std::memory_order_relaxed); }
 static std::mutex g_posperm_mu;
 static std::vector<PospermEntry> g_posperm_cache;
 static bool posperm_same(const PospermEntry& x, const PospermEntry& y) {
@@ -799,9 +796,6 @@ void posperm_cache_put(const PospermEntry& e) {
   if (g_posperm_cache.size() < 64) g_posperm_cache.push_back(e);
 }
 
-// A/B knob "f32_lean_tile": the fp32 TWO form with the lean set-up and write-out (1, default) or without (0); same bits
-static std::atomic<int> g_f32_lean{1};
-void igemm_f32_lean_enable(int on) { g_f32_lean.store(on, std::memory_order_relaxed); }
 
 template <bool BF, int MMAP, bool RELU, bool TWO = false, bool LEAN = false>
 static int launch_t(hipStream_t s, const IgemmArgs& a_in) {
@@ -867,8 +861,9 @@ int igemm_occupancy(size_t lds_bytes) {
 
 template <bool BF, bool TWO = false>
 static int dispatch(hipStream_t s, const IgemmDesc& d, const IgemmArgs& a) {
+  // knob "f32_lean_tile": the fp32 TWO form with the lean set-up and write-out (1, default) or without (0); same bits
   if constexpr (TWO) {  // (position-major tiles keep their set-up: masks and ranking are what make fc6's tiles unequal)
-    if (!d.posmajor && g_f32_lean.load(std::memory_order_relaxed)) {
+    if (!d.posmajor && tuning(KNOB_F32_LEAN_TILE)) {
       if (d.pool) return d.relu ? launch_t<BF, 1, true, TWO, true>(s, a) : launch_t<BF, 1, false, TWO, true>(s, a);
       return d.relu ? launch_t<BF, 0, true, TWO, true>(s, a) : launch_t<BF, 0, false, TWO, true>(s, a);
     }
@@ -878,11 +873,9 @@ static int dispatch(hipStream_t s, const IgemmDesc& d, const IgemmArgs& a) {
   return d.relu ? launch_t<BF, 0, true, TWO>(s, a) : launch_t<BF, 0, false, TWO>(s, a);
 }
 
-// fp32 summation: 0 = multi-level (igemm_kernel<.., TWO>, the default), -1 = the single-chain kernel with register
-// staging (A/B of accuracy and speed, tools/).  Unlike the other knobs this one changes the fp32 summation order, i.e.
-// result bits (never their validity).
-static std::atomic<int> g_f32_group{0};
-void igemm_f32_group(int steps) { g_f32_group = steps; }
+// Knob "f32_two_level", the fp32 summation: non-zero = multi-level (igemm_kernel<.., TWO>, the default), 0 = the
+// single-chain kernel with register staging (A/B of accuracy and speed, tools/).  Unlike the other knobs this one changes
+// the fp32 summation order, i.e. result bits (never their validity).
 
 int launch_igemm(hipStream_t s, const IgemmDesc& d) {
   const int es = d.bf16 ? 2 : 4;
@@ -995,10 +988,10 @@ int launch_igemm(hipStream_t s, const IgemmDesc& d) {
     if (big == 1) return FLM_OK;
   }
   int rc;
-  const int f32_knob = g_f32_group.load(std::memory_order_relaxed);
+  const int two_level = tuning(KNOB_F32_TWO_LEVEL);
   if (d.bf16) {
     rc = dispatch<true>(s, d, a);
-  } else if (f32_knob < 0) {
+  } else if (!two_level) {
     rc = dispatch<false>(s, d, a);
   } else {
     // groups of the third accumulation level: floor(sqrt(k-steps per output)) steps, at least 2

@@ -159,8 +159,6 @@ __device__ __forceinline__ size_t posmajor_orow(int m, int m_first, int nn0, int
 // headline batch, 512 faces, has one position per tile anyway.)  Only the ORDER in which tiles take positions changes: every output is the same sum in the
 // same order (the skipped and the not-skipped taps of a row outside its own set are zero products either way), the same
 // bits (tests/test_gpu_forward.py).  Maps of more than 64 positions, n >= bm, n < 32 (split-K territory) or n not dividing bm: left alone.
-void igemm_posperm_enable(int on);
-int igemm_posperm_enabled();
 struct PospermEntry {
   int h, w, kh, kw, pad, g, on;
   unsigned long long table[8];
@@ -173,7 +171,7 @@ inline void posmajor_fill_perm(IgemmArgs& a, int bm) {
   a.posperm_on = 0;
   for (int k = 0; k < 8; ++k) a.posperm[k] = 0ull;
   const int P = a.h * a.w;
-  if (!igemm_posperm_enabled() || P > 64 || P < 2 || a.n < 32 || a.n >= bm || bm % a.n != 0 || a.kh * a.kw > 64) return;
+  if (!tuning(KNOB_POSMAJOR_ORDER) || P > 64 || P < 2 || a.n < 32 || a.n >= bm || bm % a.n != 0 || a.kh * a.kw > 64) return;
   const int g = bm / a.n;
   PospermEntry ent = {a.h, a.w, a.kh, a.kw, a.pad, g, 0, {0, 0, 0, 0, 0, 0, 0, 0}};
   if (!posperm_cache_get(ent)) {

@@ -611,19 +611,6 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void igemm_bf16_big_kernel(IgemmAr
   }
 }
 
-// A/B knobs (flm_set_tuning): atomics read at launch time; they never change results or memory layouts
-static std::atomic<int> g_big_enable{1};  // 0 never, 1 when the tile grid fills the chip, 2 whenever the shape allows (tests),
-                              // 3 like 1 plus the 256x128 shape for 128-channel layers
-static std::atomic<int> g_group_n{0};     // weight panels per tile group (0: default)
-void igemm_bf16_big_enable(int on) { g_big_enable = on; }
-void igemm_bf16_group_n(int gn) { g_group_n = gn; }
-
-static std::atomic<int> g_big_dma{1};  // operands reach LDS by buffer_load ... lds (256x256 tiles); 0: through staging registers
-void igemm_bf16_big_dma(int on) { g_big_dma = on; }
-
-static std::atomic<int> g_big_m16{1};  // the 256x256 LDS-DMA kernel computes with v_mfma_f32_16x16x32_bf16 (1) or 32x32x16 (0); same bits
-void igemm_bf16_big_m16(int on) { g_big_m16 = on; }
-
 template <int MMAP, bool RELU, int WM, int WN, int TM, int TN, bool DMA, bool M16 = false>
 static int launch_big_t(hipStream_t s, IgemmArgs a) {
   constexpr int BMt = WM * TM * 32, BNt = WN * TN * 32;
@@ -633,7 +620,7 @@ static int launch_big_t(hipStream_t s, IgemmArgs a) {
   a.mtiles = cdiv(a.M, BMt);
   a.ntiles = cdiv(a.cout, BNt);
   // fc6 (position-major): its 100 MB of weights are the big operand, one weight panel per group keeps it in L2
-  const int group_n = g_group_n.load(std::memory_order_relaxed);
+  const int group_n = tuning(KNOB_BF16_GROUP_N);  // weight panels per tile group (0: default)
   a.gn = group_n > 0 ? group_n : (MMAP == 2 ? 1 : 4);
   if (a.gn > a.ntiles) a.gn = a.ntiles;
   a.gm = 32 / a.gn > 0 ? 32 / a.gn : 1;
@@ -645,9 +632,11 @@ static int launch_big_t(hipStream_t s, IgemmArgs a) {
 
 template <int MMAP, bool RELU, int WM, int WN, int TM, int TN>
 static int launch_big(hipStream_t s, const IgemmArgs& a) {
-  if (WM == 2 && g_big_dma && g_big_m16)
-    return launch_big_t<MMAP, RELU, WM, WN, TM, TN, (WM == 2), (WM == 2)>(s, a);
-  if (WM == 2 && g_big_dma) return launch_big_t<MMAP, RELU, WM, WN, TM, TN, (WM == 2)>(s, a);
+  // 256x256 tiles: operands reach LDS by buffer_load ... lds (0: through staging registers), and that form computes with
+  // v_mfma_f32_16x16x32_bf16 (0: 32x32x16; same bits)
+  const int dma = tuning(KNOB_BF16_LDS_DMA), m16 = tuning(KNOB_BF16_MFMA16);
+  if (WM == 2 && dma && m16) return launch_big_t<MMAP, RELU, WM, WN, TM, TN, (WM == 2), (WM == 2)>(s, a);
+  if (WM == 2 && dma) return launch_big_t<MMAP, RELU, WM, WN, TM, TN, (WM == 2)>(s, a);
   return launch_big_t<MMAP, RELU, WM, WN, TM, TN, false>(s, a);
 }
 
@@ -659,7 +648,10 @@ static int dispatch_big(hipStream_t s, const IgemmArgs& a, int relu, int pool, i
 }
 
 int launch_igemm_bf16_big(hipStream_t s, const IgemmArgs& a, int relu, int pool, int posmajor, int coutpad) {
-  if (!g_big_enable || a.ksplit > 1 || a.stride != 1 || a.res) return 0;
+  // 0 never, 1 when the tile grid fills the chip, 2 whenever the shape allows (tests), 3 like 1 plus the 256x128 shape
+  // for 128-channel layers
+  const int enable = tuning(KNOB_BF16_BIG_TILES);
+  if (!enable || a.ksplit > 1 || a.stride != 1 || a.res) return 0;
   // buffer offsets at or above 0x80000000 mean "zero padding" here: operands must stay below 2 GiB
   if ((long long)a.n * a.h * a.w * a.cin * 2 + (1 << 20) >= (1ll << 31) || (long long)coutpad * a.K * 2 >= (1ll << 31)) return 0;
   // 256-wide N tiles need whole 256-row weight panels; 128-channel layers take the 256x128 shape
@@ -667,11 +659,11 @@ int launch_igemm_bf16_big(hipStream_t s, const IgemmArgs& a, int relu, int pool,
   const int bn = wide ? 256 : 128;
   if (!wide && a.cout > 128) return 0;
   const long long tiles = (long long)cdiv(a.M, 256) * cdiv(a.cout, bn);
-  if (g_big_enable != 2) {
+  if (enable != 2) {
     if (tiles < 192) return 0;  // too few workgroups for 256 CUs: 128x128 tiles fill the chip better
     // 128-channel layers (enc2: 9 k-steps per tile) gain nothing from one 256x128 workgroup per CU over two
     // co-resident 128x128 ones, which overlap each other's prologue and epilogue
-    if (!wide && g_big_enable != 3) return 0;
+    if (!wide && enable != 3) return 0;
   }
   return wide ? dispatch_big<2, 4, 4, 2>(s, a, relu, pool, posmajor) : dispatch_big<4, 2, 2, 2>(s, a, relu, pool, posmajor);
 }

@@ -2,7 +2,6 @@
 // alignment warp, crop front-end.
 #include "flm_common.h"
 
-#include <atomic>
 
 namespace flm {
 
@@ -320,9 +319,6 @@ __global__ __launch_bounds__(256) void warp_u8_kernel(const uint8_t* __restrict_
   }
 }
 
-static std::atomic<int> g_warp_rows{1};  // A/B knob "warp_rows": same results either way
-void warp_rows_enable(int on) { g_warp_rows.store(on, std::memory_order_relaxed); }
-
 // uint8 sources, destination width a multiple of 64: one wave = 64 consecutive pixels of ROWS consecutive output rows, a
 // workgroup = a strip of 256 columns x ROWS rows (grid: strips across, row groups, faces).  What the FLM_WARP_VAR
 // ablations of warp_u8_kernel showed at batch 512 (0.163 ms as shipped): 0.092 ms without the stores, 0.090 ms without
@@ -419,10 +415,10 @@ int launch_warp(hipStream_t s, const void* src, int src_is_u8, int n, int hs, in
     set_error("warp: bad sizes (a face must stay below 2^31 bytes on either side)");
     return FLM_ERR_SHAPE;
   }
-  if (src_is_u8 && ws >= 2 && (wd & 63) == 0 && hs < (1 << 24) && ws < (1 << 24) &&
-      g_warp_rows.load(std::memory_order_relaxed)) {
+  const int warp_rows = tuning(KNOB_WARP_ROWS);
+  if (src_is_u8 && ws >= 2 && (wd & 63) == 0 && hs < (1 << 24) && ws < (1 << 24) && warp_rows) {
     // rows per wave: 2 by default (knob value 4: four)
-    const int rows = g_warp_rows.load(std::memory_order_relaxed) == 4 ? 4 : 2;
+    const int rows = warp_rows == 4 ? 4 : 2;
     const int gy = cdiv(hd, rows);
     if (gy <= 65535) {
       const dim3 grid(cdiv(wd / 64, 4), gy, n);

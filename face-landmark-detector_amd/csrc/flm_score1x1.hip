@@ -78,12 +78,10 @@ __global__ __launch_bounds__(256, 2) void score1x1_bf16_kernel(const unsigned sh
   }
 }
 
-static std::atomic<int> g_score1x1{1};  // A/B knob: never changes results or layouts
-void score1x1_enable(int on) { g_score1x1.store(on, std::memory_order_relaxed); }
 
 // 1: launched; 0: shape left to the implicit-GEMM kernels
 int launch_score1x1_bf16(hipStream_t s, const IgemmArgs& a, int relu, int pool, int posmajor, int coutpad) {
-  if (!g_score1x1.load(std::memory_order_relaxed) || a.kh != 1 || a.kw != 1 || a.pad != 0 || a.stride != 1 || a.res ||
+  if (!tuning(KNOB_BF16_SCORE1X1) || a.kh != 1 || a.kw != 1 || a.pad != 0 || a.stride != 1 || a.res ||
       relu || pool || posmajor || a.ksplit > 1 || !a.out_f32 || a.cin != S1_K || a.cout > S1_MAXLD || a.ldc > S1_MAXLD ||
       (a.ldc & 3) || a.cout > a.ldc || coutpad < S1_MAXLD || a.M < 1)
     return 0;

@@ -167,14 +167,12 @@ __global__ __launch_bounds__(64 * T2_WAVES, 1) void seg_fused_bf16_kernel(const 
   }
 }
 
-static std::atomic<int> g_fused_tail{1};  // A/B knob "bf16_fused_tail": same bits either way
-void tail_fused_enable(int on) { g_fused_tail.store(on, std::memory_order_relaxed); }
 
 // 1: launched (seg_feats written); 0: shape left to the two-launch form; < 0: error
 int launch_seg_fused_bf16(hipStream_t s, const float* fuse4, const void* w4_packed, const void* f3, const void* w3,
                           const float* scale3, const float* shift3, float* seg, int n, int h4, int w4d, int C, int Cp,
                           int G, int cin3, int coutpad3) {
-  if (!g_fused_tail.load(std::memory_order_relaxed) || C != T2_C || Cp != T2_CP || G != T2_G || cin3 != T2_K3 ||
+  if (!tuning(KNOB_BF16_FUSED_TAIL) || C != T2_C || Cp != T2_CP || G != T2_G || cin3 != T2_K3 ||
       coutpad3 < 16 * T2_TILES || n < 1 || h4 < 1 || w4d < 1)
     return 0;
   // 32-bit slice arithmetic; the buffers themselves are indexed with size_t

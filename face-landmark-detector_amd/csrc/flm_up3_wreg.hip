@@ -423,14 +423,12 @@ __global__ __launch_bounds__(wreg::WAVES * 64, 2) void up3_wreg_kernel(wreg::Arg
   }
 }
 
-static std::atomic<int> g_wreg{0};  // A/B knob "up3_wreg": 1 = the bf16 candidate launch of up3 runs this kernel (default 0: it ties with
-                                    // up3_cand8_kernel, 1.94 against 1.94-1.97 ms per 512 faces, and that one takes every shape)
-void convt_wreg_enable(int on) { g_wreg.store(on, std::memory_order_relaxed); }
-
+// A/B knob "up3_wreg": 1 = the bf16 candidate launch of up3 runs this kernel (default 0: it ties with
+// up3_cand8_kernel, 1.94 against 1.94-1.97 ms per 512 faces, and that one takes every shape)
 // 1: launched; 0: not this kernel's case (the caller takes up3_cand8_kernel); < 0: error
 int launch_up3_wreg(hipStream_t st, const ConvTArgs& c, void* scratch, size_t scratch_bytes) {
   using namespace wreg;
-  if (!g_wreg.load(std::memory_order_relaxed)) return 0;
+  if (!tuning(KNOB_UP3_WREG)) return 0;
   if (c.s != 8 || c.C != 68 || c.Cp != CP || !scratch || c.hi < 2 || c.wi < 2) return 0;
   Args a;
   a.wf = c.wf; a.tau = c.tau; a.cand = c.cand; a.cand_cnt = c.cand_cnt; a.gate = c.gate; a.cand_cap = c.cand_cap;

@@ -19,8 +19,8 @@
  *    thread-local message for the last failing call on this thread.
  *  - reentrancy: calls on different streams may run concurrently from different threads.
  *    Process state is limited to (1) the thread-local error string, (2) the A/B
- *    performance knobs of flm_set_tuning -- atomic integers read at launch time that
- *    never change results or memory layouts, (3) the measurement hook flm_profile_*
+ *    performance knobs of flm_set_tuning -- integers that every launch reads once, at
+ *    launch time, and that never change results or memory layouts, (3) the measurement hook flm_profile_*
  *    (off by default; a measurement aid, NOT thread-safe).  Everything that changes
  *    results' provenance or the workspace layout is an argument (flm_forward_opts).
  *  - layouts are NHWC ("channels_last", networks/config.py:5) throughout.
@@ -239,7 +239,9 @@ int flm_profile_enable(int max_records);
 int flm_profile_filter(const char* layer);
 /* A/B performance knobs: they never change memory layouts, and -- with the one exception of "f32_two_level", which
  * selects between two fp32 summation orders -- never results; key "none" is always accepted, unknown keys
- * fail.  Atomic integers read at launch time; meant for A/B runs (tools/tune.py) and for tests that force a code path:
+ * fail.  A launch reads each knob it depends on exactly once, when it is issued: a setter running concurrently with
+ * launches on other threads takes effect between launches, never inside one.  A rejected value leaves the knob as it
+ * was.  Meant for A/B runs (tools/tune.py) and for tests that force a code path:
  *   "bf16_big_tiles"        0 off | 1 auto (default) | 2 whenever the shape allows | 3 auto + 256x128 tiles
  *                           256-row bf16 implicit-GEMM tiles (csrc/flm_igemm_bf16.hip)
  *   "bf16_lds_dma"          1 (default): the 256x256 tiles fetch their operands with buffer_load ... lds (no staging
@@ -286,6 +288,8 @@ int flm_profile_filter(const char* layer);
  * The options that change the workspace layout ("landmark_candidates", "candidate_*") are per-call arguments:
  * flm_forward_opts above. */
 int flm_set_tuning(const char* key, int value);
+/* The current value of a knob listed above: FLM_OK, or FLM_ERR_ARG (null pointer, unknown key) with a message. */
+int flm_get_tuning(const char* key, int* value);
 /* Diagnostics for developers ("igemm_occupancy", arg = dynamic LDS bytes -> workgroups per CU). */
 int flm_debug_query(const char* key, int arg);
 int flm_profile_reset(void);

@@ -4,6 +4,8 @@ import ctypes
 import json
 import os
 import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -49,8 +51,23 @@ def test_size_queries_answer_without_a_gpu():
     assert lib.flm_decode_workspace_bytes(2, 264, 264, 68, _lib.DECODE_TOPN, 4) > 0
 
 
+def documented_knobs():
+    """{key: default} of the knob comment above flm_set_tuning in include/flm.h: one entry per line that opens with a quoted
+    key; the default is the value the entry marks ("1 (default)", "1 auto (default)", "0 default", "default 1")."""
+    src = open(os.path.join(ROOT, "include", "flm.h")).read()
+    text = src[src.index("/* A/B performance knobs"):src.index("int flm_set_tuning")]
+    entries = re.split(r'\n \*   "([a-z0-9_]+)" ', text)[1:]
+    knobs = {}
+    for key, body in zip(entries[0::2], entries[1::2]):
+        m = re.search(r"(\d+)(?: [a-z]+)? \(?default\b|\bdefault (\d+)", body)
+        assert m, "no default documented for %s" % key
+        knobs[key] = int(m.group(1) or m.group(2))
+    return knobs
+
+
 def test_tuning_knobs_and_workspace_layout():
-    """flm_set_tuning: documented A/B keys are accepted, unknown keys and bad values fail with a message.  What changes the
+    """flm_set_tuning / flm_get_tuning: every documented A/B key starts at its documented default, round-trips, and keeps
+    its value when a set is rejected; unknown keys and bad values fail with a message; _lib.tuning restores what it found.  What changes the
     workspace layout is NOT process state: the candidate landmark path is chosen per call by flm_forward_opts, and adds its
     lists to the workspace only where it applies (top-n <= 32, 68 classes, fcn_8)."""
     import ctypes as C
@@ -62,6 +79,50 @@ def test_tuning_knobs_and_workspace_layout():
     assert lib.flm_set_tuning(b"bf16_group_n", 3) != 0
     for key in (b"landmark_candidates", b"candidate_sub_phases", b"candidate_cap_div"):   # moved into the call
         assert lib.flm_set_tuning(key, 1) != 0 and b"flm_forward_opts" in lib.flm_last_error()
+
+    def get(key):
+        v = C.c_int(-12345)
+        assert lib.flm_get_tuning(key.encode(), C.byref(v)) == 0, key
+        return v.value
+    knobs = documented_knobs()
+    assert len(knobs) == 16 and knobs["up3_wreg"] == 0 and knobs["bf16_group_n"] == 0 and knobs["up3_cand8"] == 1
+    # a fresh process: what the library starts with, whatever earlier tests of this one have set
+    child = ("import json, sys, ctypes as C; sys.path.insert(0, %r); import flm_amd; from flm_amd import _lib; lib = _lib.load(); "
+             "v = C.c_int(); print(json.dumps({k: (lib.flm_get_tuning(k.encode(), C.byref(v)), v.value) for k in %r}))"
+             % (ROOT, sorted(knobs)))
+    r = subprocess.run([sys.executable, "-c", child], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1]) == {k: [0, d] for k, d in knobs.items()}
+    rejected = {"bf16_group_n": 3, "warp_rows": 3, "up3_cand8": 8, "up3_cand8_rows": 3, "up3_wreg": 2}
+    other = {"bf16_group_n": 8, "warp_rows": 4, "up3_cand8": 5, "up3_cand8_rows": 2}      # accepted, not the default
+    before = {k: get(k) for k in knobs}
+    with _lib.tuning(*knobs):                                # (leaves every knob as this test found it)
+        for key, dflt in knobs.items():
+            val = other.get(key, 1 - dflt)
+            assert lib.flm_set_tuning(key.encode(), val) == 0 and get(key) == val != dflt, key
+            if key in rejected:
+                assert lib.flm_set_tuning(key.encode(), rejected[key]) != 0 and key.encode() in lib.flm_last_error()
+                assert get(key) == val, key
+            # _lib.tuning puts the (non-default) value back after a normal exit and after an exception, and nests
+            with _lib.tuning(**{key: dflt}):
+                assert get(key) == dflt
+                with _lib.tuning(key):
+                    assert lib.flm_set_tuning(key.encode(), val) == 0 and get(key) == val
+                assert get(key) == dflt
+            assert get(key) == val
+            with pytest.raises(ZeroDivisionError):
+                with _lib.tuning(**{key: dflt}):
+                    assert get(key) == dflt
+                    1 / 0
+            assert get(key) == val
+    assert {k: get(k) for k in knobs} == before
+    v = C.c_int(7)
+    for fn in (lambda k: lib.flm_set_tuning(k, 1), lambda k: lib.flm_get_tuning(k, C.byref(v))):
+        assert fn(b"no_such_knob") != 0 and b"no_such_knob" in lib.flm_last_error()
+    assert v.value == 7 and lib.flm_get_tuning(b"up3_wreg", None) != 0 and b"null" in lib.flm_last_error()
+    with pytest.raises(_lib.FlmError):
+        with _lib.tuning(no_such_knob=1):
+            pass
     dflt = _lib.ForwardOpts.make()
     assert dflt.struct_size == C.sizeof(_lib.ForwardOpts) == 16 and dflt.key() == (1, 0, 1)
     off_o = _lib.ForwardOpts.make(landmark_candidates=0)

@@ -70,12 +70,10 @@ def test_warp_row_segment_kernel(A, shape):
     m[0] = [[1, 0, 0], [0, 1, 0]]            # identity: the last column is xs = ws - 1 exactly when wd >= ws
     exp = warp_ref.warp_affine_ref(src, m, hd, wd)
     got = {}
-    try:
+    with _lib.tuning("warp_rows"):
         for knob in (0, 1, 4):
             _lib.check(lib.flm_set_tuning(b"warp_rows", knob), "set_tuning")
             got[knob] = A.warp_device(torch.from_numpy(src).cuda(), torch.from_numpy(m).cuda(), hd, wd).cpu().numpy()
-    finally:
-        _lib.check(lib.flm_set_tuning(b"warp_rows", 1), "set_tuning")
     assert ulp_diff(got[1], exp).max() <= 1
     for knob in (1, 4):
         assert np.array_equal(got[0], got[knob]), knob

@@ -59,7 +59,7 @@ def test_eight_wave_kernel_equals_generic_kernel(flm, weights68, dtype):
     model = LANDMARKS_MODELS["fcn_8"](68, input_height=256, input_width=256, dtype=dtype)
     model.load_weights(weights68)
     xd = torch.from_numpy(rng.integers(0, 256, (9, 256, 256, 3), dtype=np.uint8)).cuda()
-    try:
+    with _lib.tuning("up3_cand8", "up3_cand8_rows"):
         for n_points in (4, 25):
             ref = _landmarks(model, xd, n_points, 0.0, candidates=False)
             for knob, rows in ((0, 0), (3, 0), (3, 1), (3, 8)):
@@ -70,9 +70,6 @@ def test_eight_wave_kernel_equals_generic_kernel(flm, weights68, dtype):
         _lib.check(lib.flm_set_tuning(b"up3_cand8", 3), "set_tuning")
         got = _landmarks(model, xd, 4, 0.0, candidates=True, cap_div=4096)
         assert np.array_equal(got, _landmarks(model, xd, 4, 0.0, candidates=False))
-    finally:
-        _lib.check(lib.flm_set_tuning(b"up3_cand8", 1), "set_tuning")
-        _lib.check(lib.flm_set_tuning(b"up3_cand8_rows", 0), "set_tuning")
 
 
 def test_weights_in_registers_kernel_equals_materialised_decode(flm, weights68):
@@ -84,8 +81,7 @@ def test_weights_in_registers_kernel_equals_materialised_decode(flm, weights68):
     from flm_amd.networks import LANDMARKS_MODELS
     lib = _lib.load()
     rng = np.random.default_rng(48)
-    try:
-        _lib.check(lib.flm_set_tuning(b"up3_wreg", 1), "set_tuning")
+    with _lib.tuning(up3_wreg=1):
         model = LANDMARKS_MODELS["fcn_8"](68, input_height=256, input_width=256, dtype="bf16")
         model.load_weights(weights68)
         for n in (1, 9, 40):
@@ -117,8 +113,6 @@ def test_weights_in_registers_kernel_equals_materialised_decode(flm, weights68):
             ref = _landmarks(model, xd, n_points, 0.0, candidates=False)
             got = _landmarks(model, xd, n_points, 0.0, candidates=True)
             assert np.array_equal(got, ref), ("96x160", n_points)
-    finally:
-        _lib.check(lib.flm_set_tuning(b"up3_wreg", 0), "set_tuning")
 
 
 def test_candidate_overflow_falls_back(flm, weights68):

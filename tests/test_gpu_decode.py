@@ -121,12 +121,10 @@ def test_lds_dma_form_equals_register_prefetch_form(M):
         hm = torch.rand(shape, device="cuda", generator=g)
         hm[0, :2, :7, 3] = 0.875      # ties
         out = {}
-        try:
+        with _lib.tuning("decode_lds_dma"):
             for knob in (0, 1):
                 _lib.check(lib.flm_set_tuning(b"decode_lds_dma", knob), "set_tuning")
                 out[knob] = [M.decode_device(hm, n, 0.1).cpu().numpy() for n in (0, 1, 4, 25, 64)]
-        finally:
-            _lib.check(lib.flm_set_tuning(b"decode_lds_dma", 1), "set_tuning")
         for a, b, n in zip(out[0], out[1], (0, 1, 4, 25, 64)):
             assert np.array_equal(a, b, equal_nan=True), (shape, n)
         del hm

@@ -138,14 +138,12 @@ def test_fp32_two_level_accumulation_beats_the_single_chain(flm, weights68):
     xd = torch.from_numpy(crops).cuda()
     names = ("f2", "f3", "f4", "f5", "fc6", "fc7")
     err = {}
-    try:
+    with _lib.tuning("f32_two_level"):
         for two in (0, 1):
             _lib.check(lib.flm_set_tuning(b"f32_two_level", two), "set_tuning")
             model.forward_device(xd, "probs")
             torch.cuda.synchronize()
             err[two] = {k: rms(model.intermediate(k, n, "probs").cpu().numpy()[..., : i64[k].shape[-1]], i64[k]) for k in names}
-    finally:
-        _lib.check(lib.flm_set_tuning(b"f32_two_level", 1), "set_tuning")
     e32 = {k: rms(i32[k], i64[k]) for k in names}
     print("relative RMS error vs the float64 oracle:", {k: "%.2g / %.2g / %.2g" % (err[0][k], err[1][k], e32[k]) for k in names},
           "(single chain / two-level / float32 CPU oracle)")
@@ -167,15 +165,13 @@ def test_fc6_position_order_keeps_the_bits(flm, weights68, dtype, n):
     model.load_weights(weights68)
     xd = torch.from_numpy(np.random.default_rng(21).integers(0, 256, (n, 256, 256, 3), dtype=np.uint8)).cuda()
     got = {}
-    try:
+    with _lib.tuning("posmajor_order"):
         for knob in (0, 1):
             _lib.check(lib.flm_set_tuning(b"posmajor_order", knob), "set_tuning")
             lm = model.forward_device(xd, "landmarks", n_points=4).clone()
             model.forward_device(xd, "probs")
             torch.cuda.synchronize()
             got[knob] = (model.intermediate("fc6", n, "probs").clone(), lm)
-    finally:
-        _lib.check(lib.flm_set_tuning(b"posmajor_order", 1), "set_tuning")
     assert torch.equal(got[0][0], got[1][0]), "fc6"
     assert torch.equal(got[0][1], got[1][1]), "landmarks"
 
@@ -273,7 +269,7 @@ def test_bf16_256_row_tiles_equal_128_row_tiles(flm, weights68):
         model.load_weights(weights68)
         xd = torch.from_numpy(rng.integers(0, 256, (n, h, w, 3), dtype=np.uint8)).cuda()
         outs = {}
-        try:
+        with _lib.tuning("bf16_big_tiles", "bf16_lds_dma", "bf16_mfma16"):
             # 0: 128x128 tiles; (2, 0): 256-row tiles staged through registers; (2, 1): filled by LDS-DMA, 32x32x16 MFMAs;
             # (2, 2): LDS-DMA with 16x16x32 MFMAs (the default; the shape sums a k-run of 32 in one instruction)
             for mode, dma in ((0, 0), (2, 0), (2, 1), (2, 2)):
@@ -283,10 +279,6 @@ def test_bf16_256_row_tiles_equal_128_row_tiles(flm, weights68):
                 probs = model.forward_device(xd, "probs").cpu().numpy()
                 inter = {k: model.intermediate(k, n, "probs").cpu().numpy() for k in ("f2", "f3", "f4", "f5", "fc6", "fc7")}
                 outs[(mode, dma)] = (probs, inter)
-        finally:
-            _lib.check(lib.flm_set_tuning(b"bf16_big_tiles", 1), "set_tuning")
-            _lib.check(lib.flm_set_tuning(b"bf16_lds_dma", 1), "set_tuning")
-            _lib.check(lib.flm_set_tuning(b"bf16_mfma16", 1), "set_tuning")
         for key in ((2, 0), (2, 1), (2, 2)):
             for k in outs[(0, 0)][1]:
                 assert np.array_equal(outs[(0, 0)][1][k], outs[key][1][k]), (k, key, n, h, w)
@@ -306,16 +298,12 @@ def test_bf16_score_kernel_equals_implicit_gemm(flm, weights68):
         model.load_weights(weights68)
         xd = torch.from_numpy(rng.integers(0, 256, (n, h, w, 3), dtype=np.uint8)).cuda()
         outs = {}
-        try:
-            _lib.check(lib.flm_set_tuning(b"bf16_fused_tail", 0), "set_tuning")   # (score3 as a launch of its own)
+        with _lib.tuning("bf16_score1x1", bf16_fused_tail=0):   # (score3 as a launch of its own)
             for knob in (0, 1):
                 _lib.check(lib.flm_set_tuning(b"bf16_score1x1", knob), "set_tuning")
                 probs = model.forward_device(xd, "probs").cpu().numpy()
                 inter = {k: model.intermediate(k, n, "probs").cpu().numpy() for k in ("fuse4", "seg_feats")}
                 outs[knob] = (probs, inter)
-        finally:
-            _lib.check(lib.flm_set_tuning(b"bf16_score1x1", 1), "set_tuning")
-            _lib.check(lib.flm_set_tuning(b"bf16_fused_tail", 1), "set_tuning")
         for k in outs[0][1]:
             assert np.array_equal(outs[0][1][k], outs[1][1][k]), (k, n, h, w)
         assert np.array_equal(outs[0][0], outs[1][0]), (n, h, w)
@@ -334,15 +322,13 @@ def test_bf16_fused_skip_stage_equals_the_two_launches(flm, weights68):
         model.load_weights(weights68)
         xd = torch.from_numpy(rng.integers(0, 256, (n, h, w, 3), dtype=np.uint8)).cuda()
         outs = {}
-        try:
+        with _lib.tuning("bf16_fused_tail"):
             for knob in (0, 1):
                 _lib.check(lib.flm_set_tuning(b"bf16_fused_tail", knob), "set_tuning")
                 probs = model.forward_device(xd, "probs").cpu().numpy()
                 seg = model.intermediate("seg_feats", n, "probs").cpu().numpy()
                 lm = model.forward_device(xd, "landmarks", n_points=4).cpu().numpy()
                 outs[knob] = (probs, seg, lm)
-        finally:
-            _lib.check(lib.flm_set_tuning(b"bf16_fused_tail", 1), "set_tuning")
         for a, b, what in zip(outs[0], outs[1], ("probs", "seg_feats", "landmarks")):
             assert np.array_equal(a, b), (what, n, h, w)
 
@@ -363,7 +349,7 @@ def test_bf16_halo_conv_equals_implicit_gemm(flm, weights68):
         model.load_weights(wts)
         xd = torch.from_numpy(rng.integers(0, 256, (n, h, w, 3), dtype=np.uint8)).cuda()
         outs = {}
-        try:
+        with _lib.tuning("bf16_conv3_halo", "bf16_halo_mfma16"):
             # (0, .): implicit GEMM; (2, 0): halo kernel on 32x32x16 MFMAs; (2, 1): on 16x16x32 (the default shape)
             for mode, m16 in ((0, 0), (2, 0), (2, 1)):
                 _lib.check(lib.flm_set_tuning(b"bf16_conv3_halo", mode), "set_tuning")
@@ -372,9 +358,6 @@ def test_bf16_halo_conv_equals_implicit_gemm(flm, weights68):
                 outs[key] = model.forward_device(xd, "probs").cpu().numpy()
                 if name == "fcn_8":
                     outs[key] = (outs[key], model.intermediate("f2", n, "probs").cpu().numpy())
-        finally:
-            _lib.check(lib.flm_set_tuning(b"bf16_conv3_halo", 1), "set_tuning")
-            _lib.check(lib.flm_set_tuning(b"bf16_halo_mfma16", 1), "set_tuning")
         for key in ((2, 0), (2, 1)):
             if name == "fcn_8":
                 assert np.array_equal(outs[(0, 0)][1], outs[key][1]), (name, n, h, w, "f2", key)

@@ -113,18 +113,12 @@ FP32_CASES = [(1, 32, 32, None), (3, 96, 160, None), (2, 64, 512, None), (20, 64
 def test_fp32_layers_teacher_forced(flm, n, h, w, knob_off):
     from flm_amd import _lib
     from flm_amd.networks import LANDMARKS_MODELS
-    lib = _lib.load()
     params = _weights(68)
     model = LANDMARKS_MODELS["fcn_8"](68, input_height=h, input_width=w)
     model.load_weights(params)
     crops = np.random.default_rng(100 + h + w).integers(0, 256, (n, h, w, 3), dtype=np.uint8)
-    try:
-        if knob_off:
-            _lib.check(lib.flm_set_tuning(knob_off.encode(), 0), "set_tuning")
+    with _lib.tuning(**({knob_off: 0} if knob_off else {})):
         _forward_and_gate(model, params, crops, "f32", "fp32 %dx%dx%d%s" % (n, h, w, " %s=0" % knob_off if knob_off else ""))
-    finally:
-        if knob_off:
-            _lib.check(lib.flm_set_tuning(knob_off.encode(), 1), "set_tuning")
 
 
 # ---- every class-tile count through a whole forward --------------------------------------------------------------

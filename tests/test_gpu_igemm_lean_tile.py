@@ -20,15 +20,13 @@ def lib():
 
 
 def _both_knobs(lib, run):
-    """run() under f32_lean_tile = 0 and = 1; the default is restored whatever happens."""
+    """run() under f32_lean_tile = 0 and = 1; the value on entry is restored whatever happens."""
     from flm_amd import _lib
     got = {}
-    try:
+    with _lib.tuning("f32_lean_tile"):
         for knob in (0, 1):
             _lib.check(lib.flm_set_tuning(b"f32_lean_tile", knob), "set_tuning")
             got[knob] = run()
-    finally:
-        _lib.check(lib.flm_set_tuning(b"f32_lean_tile", 1), "set_tuning")
     return got
 
 
