@@ -14,7 +14,8 @@ LIB_PATH = os.path.join(HERE, "libflm_hip.so")
 # enums of include/flm.h
 FLM_F32, FLM_BF16 = 0, 1
 IN_U8_BGR, IN_F32_RGB = 0, 1
-OUT_PROBS, OUT_CLASSMAP, OUT_LANDMARKS, OUT_LOGITS = 0, 1, 2, 3
+OUT_PROBS, OUT_CLASSMAP, OUT_LANDMARKS, OUT_LOGITS, OUT_LANDMARKS_STATS = 0, 1, 2, 3, 4
+LANDMARK_REC = 6  # FLM_LANDMARK_REC: x, y, score, var_x, var_y, cov_xy
 DECODE_ALL, DECODE_TOPN = 0, 1
 NORM_SUB_MEAN, NORM_SUB_AND_DIVIDE, NORM_DIVIDE = 0, 1, 2
 ABI_VERSION = 2
@@ -30,6 +31,7 @@ EXPORTS = [
     "flm_set_tuning", "flm_get_tuning", "flm_debug_query", "flm_profile_enable", "flm_profile_filter", "flm_profile_reset", "flm_profile_read", "flm_profile_disable",
     "flm_preprocess",
     "flm_decode_workspace_bytes", "flm_decode", "flm_decode_sweep_workspace_bytes", "flm_decode_sweep",
+    "flm_decode_stats_workspace_bytes", "flm_decode_stats", "flm_similarity_from_landmarks_weighted",
     "flm_gaussian_heatmaps",
     "flm_similarity_from_landmarks", "flm_similarity_from_landmarks_scaled", "flm_warp_affine", "flm_crop_resize", "flm_crop_resize_frames",
     "flm_landmarks_to_frame", "flm_warp_affine_frames",
@@ -144,6 +146,12 @@ def _declare(lib):
     lib.flm_decode_workspace_bytes.argtypes = [i] * 6
     lib.flm_decode.restype = i
     lib.flm_decode.argtypes = [vp, vp, i, i, i, i, i, i, f, vp, vp, sz]
+    lib.flm_decode_stats_workspace_bytes.restype = sz
+    lib.flm_decode_stats_workspace_bytes.argtypes = [i] * 6
+    lib.flm_decode_stats.restype = i
+    lib.flm_decode_stats.argtypes = [vp, vp, i, i, i, i, i, i, f, vp, vp, sz]
+    lib.flm_similarity_from_landmarks_weighted.restype = i
+    lib.flm_similarity_from_landmarks_weighted.argtypes = [vp, vp, sz, vp, sz, vp, i, i, C.c_double, C.c_double, vp]
     ip = C.POINTER(C.c_int)
     lib.flm_decode_sweep_workspace_bytes.restype = sz
     lib.flm_decode_sweep_workspace_bytes.argtypes = [i, i, i, i, ip, i]

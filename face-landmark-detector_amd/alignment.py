@@ -43,10 +43,28 @@ def canonical_template(n_landmarks: int, out_h: int, out_w: int) -> np.ndarray:
     return pts * np.array([out_w - 1, out_h - 1], np.float64)
 
 
-def similarity_device(landmarks, template, landmark_scale=(1.0, 1.0)):
+def _uniform_stride(t, inner):
+    """Element stride between consecutive points of a [N,K(,inner)] view whose points lie `stride` elements apart, the
+    `inner` elements of a point adjacent (rec[..., :2], rec[..., 2] of a landmark record tensor); None when the view has
+    no such stride."""
+    n, k = int(t.shape[0]), int(t.shape[1])
+    st = t.stride()
+    if inner > 1 and st[2] != 1:
+        return None
+    step = st[1] if k > 1 else (st[0] if n > 1 else inner)
+    if step < inner or (n > 1 and st[0] != k * step):
+        return None
+    return int(step)
+
+
+def similarity_device(landmarks, template, landmark_scale=(1.0, 1.0), weights=None):
     """landmarks: CUDA float64 [N,K,2]; template: CUDA float64 [K,2] -> CUDA float32 [N,2,3].
     `landmark_scale` (sx, sy) takes the landmarks to the template's pixel units inside the kernel (float64
-    products; the decode's reject marker (-1,-1) stays negative, so the fit skips those points)."""
+    products; the decode's reject marker (-1,-1) stays negative, so the fit skips those points).
+    `weights`: CUDA float64 [N,K], one weight per landmark (flm_similarity_from_landmarks_weighted: a point takes part
+    when its weight is > 0; None = the unweighted fit, unchanged).  Then `landmarks` and `weights` may be views with a
+    uniform element stride -- rec[..., :2] and rec[..., 2] of a landmark record tensor -- and are read in place; any
+    other layout is copied first."""
     import torch
     lib = _lib.load()
     n, k, _ = landmarks.shape
@@ -55,6 +73,25 @@ def similarity_device(landmarks, template, landmark_scale=(1.0, 1.0)):
     if tuple(template.shape) != (k, 2):
         raise ValueError("template must be [K,2]")
     m = torch.empty((n, 2, 3), dtype=torch.float32, device=landmarks.device)
+    if weights is not None:
+        if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64 or tuple(weights.shape) != (n, k)
+                or weights.device != landmarks.device):
+            raise ValueError("weights must be a float64 [%d,%d] tensor on the landmarks' device" % (n, k))
+        if landmarks.shape[2] != 2:
+            raise ValueError("landmarks must be [N,K,2]")
+        ls = _uniform_stride(landmarks, 2)
+        if ls is None:
+            landmarks, ls = landmarks.contiguous(), 2
+        wst = _uniform_stride(weights, 1)
+        if wst is None:
+            weights, wst = weights.contiguous(), 1
+        if n and k:
+            _lib.check(lib.flm_similarity_from_landmarks_weighted(_lib.stream_ptr(), _lib.ptr(landmarks), ls,
+                                                                  _lib.ptr(weights), wst, _lib.ptr(template.contiguous()),
+                                                                  n, k, float(landmark_scale[0]), float(landmark_scale[1]),
+                                                                  _lib.ptr(m)),
+                       "flm_similarity_from_landmarks_weighted")
+        return m
     _lib.check(lib.flm_similarity_from_landmarks_scaled(_lib.stream_ptr(), _lib.ptr(landmarks.contiguous()),
                                                         _lib.ptr(template.contiguous()), n, k,
                                                         float(landmark_scale[0]), float(landmark_scale[1]),
@@ -78,9 +115,10 @@ def warp_device(src, m, out_h, out_w, out=None):
     return out
 
 
-def align_device(crops, landmarks_in, template, out_h, out_w, landmark_scale=(1.0, 1.0)):
-    """crops [N,H,W,3] + landmarks (crop pixel units after `landmark_scale`) -> aligned crops, M."""
-    m = similarity_device(landmarks_in, template, landmark_scale)
+def align_device(crops, landmarks_in, template, out_h, out_w, landmark_scale=(1.0, 1.0), weights=None):
+    """crops [N,H,W,3] + landmarks (crop pixel units after `landmark_scale`) -> aligned crops, M.
+    `weights`: per-landmark weights of the fit, as similarity_device takes them."""
+    m = similarity_device(landmarks_in, template, landmark_scale, weights)
     return warp_device(crops, m, out_h, out_w), m
 
 

@@ -30,6 +30,7 @@ SOURCES = [
     "flm_convt.hip",
     "flm_up3_wreg.hip",
     "flm_decode.hip",
+    "flm_decode_stats.hip",
     "flm_cand.hip",
     "flm_misc.hip",
     "flm_frames.hip",

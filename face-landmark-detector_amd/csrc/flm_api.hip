@@ -181,9 +181,10 @@ Fcn8Ws fcn8_ws_layout(int n, int h, int w, int C, int dtype, int out_mode, int d
   W.decode = SIZE_MAX;
   W.sub = W.tau = W.cand = W.cand_cnt = SIZE_MAX;
   W.cand_cap = W.cand_sub = 0;
-  if (out_mode == FLM_OUT_LANDMARKS) {
+  const int stats = out_mode == FLM_OUT_LANDMARKS_STATS;  // (adds only the all-pixel mode's three further partial sums)
+  if (out_mode == FLM_OUT_LANDMARKS || stats) {
     W.probs = take(cur, sizeof(float) * (size_t)n * W.oh * W.ow * C);
-    W.decode = take(cur, decode_ws_bytes(n, W.oh, W.ow, C, decode_mode, n_points));
+    W.decode = take(cur, decode_ws_bytes(n, W.oh, W.ow, C, decode_mode, n_points, stats));
     if (landmark_candidates_enabled(co, g, A.fcn32, decode_mode, n_points, W.oh, W.ow)) {
       W.cand_sub = cand_sub_for(co, n_points, g.bf16 != 0);
       W.sub = take(cur, sizeof(unsigned) * (size_t)n * convt_sample_slots(g, h3, w3, W.cand_sub) * 16 * g.MT);  // sampled maxima
@@ -495,7 +496,7 @@ static int forward_impl(flm_stream_t stream, const void* packed_dev, const void*
   }
   int rc = check_fcn8_shape(n, h, w, C, dtype);
   if (rc) return rc;
-  if (out_mode < FLM_OUT_PROBS || out_mode > FLM_OUT_LOGITS) {
+  if (out_mode < FLM_OUT_PROBS || out_mode > FLM_OUT_LANDMARKS_STATS) {
     set_error("flm_fcn8_forward: unknown output mode %d", out_mode);
     return FLM_ERR_ARG;
   }
@@ -648,7 +649,8 @@ static int forward_impl(flm_stream_t stream, const void* packed_dev, const void*
     ProfScope ps(s, "up3");
     return launch_convt(s, t);
   }
-  // landmarks (utils/metrics.py:102-109)
+  // landmarks (utils/metrics.py:102-109), as [n][C][2] or as landmark records
+  const int stats = out_mode == FLM_OUT_LANDMARKS_STATS;
   float* probs = reinterpret_cast<float*>(ws + W.probs);
   const unsigned* gate = nullptr;
   if (W.cand != SIZE_MAX) {
@@ -675,7 +677,7 @@ static int forward_impl(flm_stream_t stream, const void* packed_dev, const void*
     rc = launch_convt(s, tc); }
     if (rc) return rc;
     { ProfScope ps(s, "decode");
-    rc = launch_cand_merge(s, cand, cnt, n, W.ow, C, n_points, thresh, W.cand_cap, static_cast<double*>(out_dev)); }
+    rc = launch_cand_merge(s, cand, cnt, n, W.ow, C, n_points, thresh, W.cand_cap, static_cast<double*>(out_dev), stats); }
     if (rc) return rc;
     gate = cnt + n;  // overflow flag: non-zero -> redo this batch through the probability tensor
     t.gate = gate;
@@ -688,7 +690,7 @@ static int forward_impl(flm_stream_t stream, const void* packed_dev, const void*
   ProfScope ps(s, gate ? "decode_fallback" : "decode");
   return launch_decode(s, probs, n, W.oh, W.ow, C, decode_mode, n_points, thresh,
                        static_cast<double*>(out_dev), ws + W.decode,
-                       decode_ws_bytes(n, W.oh, W.ow, C, decode_mode, n_points), gate);
+                       decode_ws_bytes(n, W.oh, W.ow, C, decode_mode, n_points, stats), gate, stats);
 }
 
 int flm_fcn8_run_layer(flm_stream_t stream, const void* packed_dev, const char* layer, const void* x_dev,
@@ -768,6 +770,23 @@ int flm_decode(flm_stream_t stream, const float* hm, int n, int h, int w, int l,
   return launch_decode(static_cast<hipStream_t>(stream), hm, n, h, w, l, mode, n_points, thresh, out, ws, ws_bytes);
 }
 
+// (0 for what flm_decode_stats rejects: a shape outside the kernels' reach, an unknown mode, n_points outside [1,128])
+size_t flm_decode_stats_workspace_bytes(int n, int h, int w, int l, int mode, int n_points) {
+  if (n <= 0 || h <= 0 || w <= 0 || l <= 0 || l > kMaxClasses || (long long)h * w >= (1ll << 31)) return 0;
+  if (mode != FLM_DECODE_ALL && (mode != FLM_DECODE_TOPN || n_points < 1 || n_points > 128)) return 0;
+  return decode_ws_bytes(n, h, w, l, mode, n_points, 1);
+}
+
+int flm_decode_stats(flm_stream_t stream, const float* hm, int n, int h, int w, int l, int mode, int n_points,
+                     float thresh, double* rec, void* ws, size_t ws_bytes) {
+  if (!hm || !rec || !ws) {
+    set_error("flm_decode_stats: null argument");
+    return FLM_ERR_ARG;
+  }
+  return launch_decode(static_cast<hipStream_t>(stream), hm, n, h, w, l, mode, n_points, thresh, rec, ws, ws_bytes,
+                       nullptr, 1);
+}
+
 size_t flm_decode_sweep_workspace_bytes(int n, int h, int w, int l, const int* modes, int n_modes) {
   return decode_sweep_ws_bytes(n, h, w, l, modes, n_modes);
 }
@@ -807,6 +826,16 @@ int flm_similarity_from_landmarks_scaled(flm_stream_t stream, const double* lm, 
     return FLM_ERR_ARG;
   }
   return launch_similarity(static_cast<hipStream_t>(stream), lm, tmpl, n, k, sx, sy, m);
+}
+
+int flm_similarity_from_landmarks_weighted(flm_stream_t stream, const double* lm, size_t lm_stride, const double* wt,
+                                           size_t w_stride, const double* tmpl, int n, int k, double sx, double sy,
+                                           float* m) {
+  if (!lm || !tmpl || !m) {  // (wt is optional)
+    set_error("flm_similarity_from_landmarks_weighted: null argument");
+    return FLM_ERR_ARG;
+  }
+  return launch_similarity_weighted(static_cast<hipStream_t>(stream), lm, lm_stride, wt, w_stride, tmpl, n, k, sx, sy, m);
 }
 
 int flm_warp_affine(flm_stream_t stream, const void* src, int src_is_u8, int n, int hs, int ws, const float* m,

@@ -19,14 +19,16 @@ struct CandMergeArgs {
   unsigned* cand_cnt;  // [n] fill counts, [n] = fallback flag
   int n, w, l, n_points, cap;
   float thresh;
-  double* out;
+  double* out;  // [n][l][2], or landmark records [n][l][FLM_LANDMARK_REC] for the stats kernel
   int cpg;  // classes per workgroup
 };
 
 constexpr int kMergeKeys = 6144;     // 48 KiB of keys per pass: three workgroups per CU
 constexpr int kCandFineBatch = 128;  // below: four workgroups per face (the chip would sit empty with one)
 
-template <int CPW, int NW>  // NW waves, CPW = ceil(cpg / NW) classes per wave
+// STATS: the lists are finished as landmark records (finish_topn_stats); the selection is the same code, and the
+// STATS = false instantiations are the kernels FLM_OUT_LANDMARKS ran before the flag.
+template <int CPW, int NW, bool STATS>  // NW waves, CPW = ceil(cpg / NW) classes per wave
 __global__ __launch_bounds__(NW * 64) void cand_merge_kernel(CandMergeArgs a) {
   __shared__ unsigned long long keys[kMergeKeys];
   __shared__ int hist[NW * CPW + 1], off[NW * CPW + 1];
@@ -109,7 +111,8 @@ __global__ __launch_bounds__(NW * 64) void cand_merge_kernel(CandMergeArgs a) {
       // fewer than n keys: the threshold did not have n pixels above it (or the class has fewer than n non-zero
       // pixels), so the list may not hold the whole top n -> let the materialising path redo the batch
       if (readlane64(list[k], a.n_points - 1) == 0ull && lane == 0) atomicOr(&a.cand_cnt[a.n], 1u);
-      finish_topn(list[k], a.n_points, a.w, a.thresh, lane, a.out + ((size_t)face * a.l + c) * 2);
+      if constexpr (STATS) finish_topn_stats(list[k], a.n_points, a.w, a.thresh, lane, a.out + ((size_t)face * a.l + c) * FLM_LANDMARK_REC);
+      else finish_topn(list[k], a.n_points, a.w, a.thresh, lane, a.out + ((size_t)face * a.l + c) * 2);
     }
   }
 }
@@ -209,7 +212,7 @@ int launch_cand_tau(hipStream_t s, const unsigned* wave_max, int n, int slots, i
 }
 
 int launch_cand_merge(hipStream_t s, const unsigned long long* cand, unsigned* cand_cnt, int n, int w, int l,
-                      int n_points, float thresh, int cap, double* out) {
+                      int n_points, float thresh, int cap, double* out, int stats) {
   if (l > 68 || n_points < 1 || n_points > 64) {
     set_error("cand_merge: unsupported l=%d n_points=%d", l, n_points);
     return FLM_ERR_UNSUPPORTED;
@@ -219,10 +222,12 @@ int launch_cand_merge(hipStream_t s, const unsigned long long* cand, unsigned* c
   a.thresh = thresh; a.out = out;
   if (n < kCandFineBatch) {
     a.cpg = 17;
-    cand_merge_kernel<5, 4><<<dim3(cdiv(l, 17), n), 256, 0, s>>>(a);
+    if (stats) cand_merge_kernel<5, 4, true><<<dim3(cdiv(l, 17), n), 256, 0, s>>>(a);
+    else cand_merge_kernel<5, 4, false><<<dim3(cdiv(l, 17), n), 256, 0, s>>>(a);
   } else {
     a.cpg = 68;
-    cand_merge_kernel<9, 8><<<dim3(1, n), 512, 0, s>>>(a);
+    if (stats) cand_merge_kernel<9, 8, true><<<dim3(1, n), 512, 0, s>>>(a);
+    else cand_merge_kernel<9, 8, false><<<dim3(1, n), 512, 0, s>>>(a);
   }
   FLM_LAUNCH_CHECK("cand_merge_kernel");
   return FLM_OK;

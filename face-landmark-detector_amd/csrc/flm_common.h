@@ -229,19 +229,22 @@ int launch_rn_conv1(hipStream_t s, const void* x, int in_format, int n, int h, i
                     const float* scale, const float* shift, void* y, int bf16);
 int launch_maxpool3(hipStream_t s, const void* x, int n, int h, int w, int c, void* y, int bf16);
 
-size_t decode_ws_bytes(int n, int h, int w, int l, int mode, int n_points);
+// `stats`: `out` takes landmark records [n][l][FLM_LANDMARK_REC] instead of [n][l][2] (flm_decode_stats; include/flm.h)
+size_t decode_ws_bytes(int n, int h, int w, int l, int mode, int n_points, int stats = 0);
 int launch_decode(hipStream_t s, const float* hm, int n, int h, int w, int l, int mode, int n_points, float thresh,
-                  double* out, void* ws, size_t ws_bytes, const unsigned* gate = nullptr);
+                  double* out, void* ws, size_t ws_bytes, const unsigned* gate = nullptr, int stats = 0);
 size_t decode_sweep_ws_bytes(int n, int h, int w, int l, const int* modes, int n_modes);
 int launch_decode_sweep(hipStream_t s, const float* hm, int n, int h, int w, int l, const int* modes, int n_modes,
                         float thresh, double* out, void* ws, size_t ws_bytes);
 int launch_gaussian_heatmaps(hipStream_t s, const double* kp, int n, int l, int h, int w, double two_sigma_sq,
                              float* out);
 int launch_cand_merge(hipStream_t s, const unsigned long long* cand, unsigned* cand_cnt, int n, int w, int l,
-                      int n_points, float thresh, int cap, double* out);
+                      int n_points, float thresh, int cap, double* out, int stats = 0);
 
 int launch_preprocess(hipStream_t s, const uint8_t* img, int n, int h, int w, int norm, float* out);
 int launch_similarity(hipStream_t s, const double* lm, const double* tmpl, int n, int k, double sx, double sy, float* m);
+int launch_similarity_weighted(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
+                               const double* tmpl, int n, int k, double sx, double sy, float* m);
 int launch_warp(hipStream_t s, const void* src, int src_is_u8, int n, int hs, int ws, const float* m, float* dst,
                 int hd, int wd);
 int launch_crop_resize(hipStream_t s, const uint8_t* frame, int fh, int fw, const int32_t* boxes, int k,

@@ -106,6 +106,77 @@ int launch_similarity(hipStream_t s, const double* lm, const double* tmpl, int n
   return FLM_OK;
 }
 
+// The weighted fit (flm_similarity_from_landmarks_weighted; include/flm.h states it): the same kernel shape and the same
+// sums with a weight on every term -- W = sum w; means sum(w*p)/W; sa, sb, var with w on each summand.  Points and
+// weights are read at element strides, so the fit takes the forward's landmark records in place (stride 6, weights =
+// the score column).  A point takes part when both coordinates are >= 0 and its weight is > 0 (a NaN weight fails that
+// test); `wt` null: every weight is 1, and then every product by w is exact and W equals the count -- the bits of
+// similarity_kernel.
+__global__ __launch_bounds__(64) void similarity_weighted_kernel(const double* __restrict__ lm, size_t lm_stride,
+                                                                 const double* __restrict__ wt, size_t w_stride,
+                                                                 const double* __restrict__ tmpl, int n, int k, double sx,
+                                                                 double sy, float* __restrict__ m) {
+  extern __shared__ double sim_s[];  // [k][2] landmarks, [k][2] template, [k] weights
+  const int f = blockIdx.x;
+  double* p = sim_s;
+  double* t = sim_s + 2 * k;
+  double* w = sim_s + 4 * k;
+  for (int i = threadIdx.x; i < 2 * k; i += 64) {
+    const double v = lm[((size_t)f * k + (i >> 1)) * lm_stride + (i & 1)];
+    p[i] = v < 0.0 ? v : v * ((i & 1) ? sy : sx);
+    t[i] = tmpl[i];
+    if (!(i & 1)) w[i >> 1] = wt ? wt[((size_t)f * k + (i >> 1)) * w_stride] : 1.0;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double mpx = 0, mpy = 0, mqx = 0, mqy = 0, wsum = 0;
+  int cnt = 0;
+  for (int i = 0; i < k; ++i) {
+    if (!(p[2 * i] >= 0.0 && p[2 * i + 1] >= 0.0 && w[i] > 0.0)) continue;
+    mpx += w[i] * p[2 * i]; mpy += w[i] * p[2 * i + 1];
+    mqx += w[i] * t[2 * i]; mqy += w[i] * t[2 * i + 1];
+    wsum += w[i];
+    ++cnt;
+  }
+  double a = 1.0, b = 0.0, tx = 0.0, ty = 0.0;
+  if (cnt >= 2) {
+    mpx /= wsum; mpy /= wsum; mqx /= wsum; mqy /= wsum;
+    double sa = 0, sb = 0, var = 0;
+    for (int i = 0; i < k; ++i) {
+      if (!(p[2 * i] >= 0.0 && p[2 * i + 1] >= 0.0 && w[i] > 0.0)) continue;
+      const double px = p[2 * i] - mpx, py = p[2 * i + 1] - mpy;
+      const double qx = t[2 * i] - mqx, qy = t[2 * i + 1] - mqy;
+      sa += w[i] * (px * qx + py * qy);
+      sb += w[i] * (px * qy - py * qx);
+      var += w[i] * (px * px + py * py);
+    }
+    if (var > 0.0) {
+      a = sa / var;
+      b = sb / var;
+      tx = mqx - (a * mpx - b * mpy);
+      ty = mqy - (b * mpx + a * mpy);
+    }
+  }
+  float* o = m + (size_t)f * 6;
+  o[0] = (float)a; o[1] = (float)(-b); o[2] = (float)tx;
+  o[3] = (float)b; o[4] = (float)a;    o[5] = (float)ty;
+}
+
+int launch_similarity_weighted(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
+                               const double* tmpl, int n, int k, double sx, double sy, float* m) {
+  if (n <= 0 || k <= 0 || k > 1024) {
+    set_error("similarity_weighted: bad sizes n=%d k=%d", n, k);
+    return FLM_ERR_SHAPE;
+  }
+  if (lm_stride < 2 || w_stride < 1) {
+    set_error("similarity_weighted: lm_stride must be >= 2 and w_stride >= 1 (got %zu, %zu)", lm_stride, w_stride);
+    return FLM_ERR_SHAPE;
+  }
+  similarity_weighted_kernel<<<n, 64, sizeof(double) * 5 * k, s>>>(lm, lm_stride, wt, w_stride, tmpl, n, k, sx, sy, m);
+  FLM_LAUNCH_CHECK("similarity_weighted_kernel");
+  return FLM_OK;
+}
+
 // ---- alignment warp: inverse-map bilinear, edge clamp, explicit fma order ------------------------------
 // M maps source pixel coords to aligned coords; each output pixel samples the source at M^-1 (xd, yd).
 // The arithmetic below is the specification (oracle/warp_ref.py restates it operation by operation):

@@ -95,4 +95,51 @@ __device__ __forceinline__ void finish_topn(unsigned long long list, int n_point
   }
 }
 
+// The same finish as a landmark record (include/flm.h, FLM_LANDMARK_REC): x, y and the reject test are finish_topn's own
+// chain; score is the float32 quotient that test compares; the moments come from a second walk over the keys in the same
+// order, centred on (x, y), so every term of var_x / var_y is non-negative and nothing cancels.
+__device__ __forceinline__ void finish_topn_stats(unsigned long long list, int n_points, int w, float thresh, int lane,
+                                                  double* rec, unsigned long long list_hi = 0ull) {
+  float hsum = 0.f;
+  double i0 = 0.0, i1 = 0.0;
+  for (int i = n_points - 1; i >= 0; --i) {
+    const unsigned long long k = i >= 64 ? readlane64(list_hi, i - 64) : readlane64(list, i);
+    if (k == 0ull) continue;
+    const float hv = from_order_bits((unsigned)(k >> 32));
+    const unsigned idx = (unsigned)k;
+    hsum += hv;
+    i0 += (double)(idx / (unsigned)w) * (double)hv;
+    i1 += (double)(idx % (unsigned)w) * (double)hv;
+  }
+  double x = i1 / (double)hsum, y = i0 / (double)hsum;
+  const float mean = hsum / (float)n_points;
+  double var_x = -1.0, var_y = -1.0, cov_xy = 0.0;
+  if (mean <= thresh) {
+    x = -1.0; y = -1.0;
+  } else {
+    double vxx = 0.0, vyy = 0.0, vxy = 0.0;
+    for (int i = n_points - 1; i >= 0; --i) {
+      const unsigned long long k = i >= 64 ? readlane64(list_hi, i - 64) : readlane64(list, i);
+      if (k == 0ull) continue;
+      const float hv = from_order_bits((unsigned)(k >> 32));
+      const unsigned idx = (unsigned)k;
+      const double dx = (double)(idx % (unsigned)w) - x, dy = (double)(idx / (unsigned)w) - y;
+      vxx += (double)hv * (dx * dx);
+      vyy += (double)hv * (dy * dy);
+      vxy += (double)hv * (dx * dy);
+    }
+    var_x = vxx / (double)hsum;
+    var_y = vyy / (double)hsum;
+    cov_xy = vxy / (double)hsum;
+  }
+  if (lane == 0) {
+    rec[0] = x;
+    rec[1] = y;
+    rec[2] = (double)mean;
+    rec[3] = var_x;
+    rec[4] = var_y;
+    rec[5] = cov_xy;
+  }
+}
+
 }  // namespace flm

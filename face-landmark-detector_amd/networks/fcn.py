@@ -19,7 +19,8 @@ from .. import _lib
 from .. import weights as W
 
 _OUT = {"probs": _lib.OUT_PROBS, "classmap": _lib.OUT_CLASSMAP, "landmarks": _lib.OUT_LANDMARKS,
-        "logits": _lib.OUT_LOGITS}
+        "logits": _lib.OUT_LOGITS, "landmark_stats": _lib.OUT_LANDMARKS_STATS}
+_DECODING = (_lib.OUT_LANDMARKS, _lib.OUT_LANDMARKS_STATS)   # the output modes that take n_points / thresh
 
 
 def decode_mode_of(n_points: int):
@@ -136,7 +137,7 @@ class Fcn8Model:
 
     def workspace_bytes(self, n, out="probs", n_points=0, opts=None):
         om = _OUT[out]
-        dmode, npts = decode_mode_of(n_points) if om == _lib.OUT_LANDMARKS else (0, 0)
+        dmode, npts = decode_mode_of(n_points) if om in _DECODING else (0, 0)
         fo = self._opts(opts)
         nbytes = _lib.load().flm_fcn_workspace_bytes_opts(self._arch, n, self.input_height, self.input_width,
                                                           self.n_classes, self._dt, om, dmode, npts, C.byref(fo))
@@ -173,7 +174,9 @@ class Fcn8Model:
         x: torch CUDA tensor [N,H,W,3], uint8 (raw BGR crop: preprocess fused) or float32
            (already preprocessed, what model.predict receives).
         out: "probs" float32 [N,H'*W',C] | "classmap" int32 [N,H',W'] |
-             "landmarks" float64 [N,C,2] | "logits" float32 [N,H',W',C].
+             "landmarks" float64 [N,C,2] | "logits" float32 [N,H',W',C] |
+             "landmark_stats" float64 [N,C,6]: per landmark x, y, score, var_x, var_y, cov_xy (include/flm.h, the
+             landmark record; columns 0-1 are "landmarks" bit for bit).
         workspace: a caller-owned workspace from `new_workspace` (same n / out / n_points / opts); default: a cached one.
         opts: dict of flm_forward_opts fields (landmark_candidates, candidate_sub_phases, candidate_cap_div).
         """
@@ -198,15 +201,17 @@ class Fcn8Model:
             shp0, dt0 = {_lib.OUT_PROBS: ((0, oh0 * ow0, c0), torch.float32),
                          _lib.OUT_LOGITS: ((0, oh0, ow0, c0), torch.float32),
                          _lib.OUT_CLASSMAP: ((0, oh0, ow0), torch.int32),
-                         _lib.OUT_LANDMARKS: ((0, c0, 2), torch.float64)}[om]
+                         _lib.OUT_LANDMARKS: ((0, c0, 2), torch.float64),
+                         _lib.OUT_LANDMARKS_STATS: ((0, c0, _lib.LANDMARK_REC), torch.float64)}[om]
             return torch.empty(shp0, dtype=dt0, device=x.device)
-        dmode, npts = decode_mode_of(n_points) if om == _lib.OUT_LANDMARKS else (0, 0)
+        dmode, npts = decode_mode_of(n_points) if om in _DECODING else (0, 0)
         oh, ow, c = self.output_height, self.output_width, self.n_classes
         shape, dt = {
             _lib.OUT_PROBS: ((n, oh * ow, c), torch.float32),
             _lib.OUT_LOGITS: ((n, oh, ow, c), torch.float32),
             _lib.OUT_CLASSMAP: ((n, oh, ow), torch.int32),
             _lib.OUT_LANDMARKS: ((n, c, 2), torch.float64),
+            _lib.OUT_LANDMARKS_STATS: ((n, c, _lib.LANDMARK_REC), torch.float64),
         }[om]
         if out_tensor is None:
             out_tensor = torch.empty(shape, dtype=dt, device=x.device)
@@ -233,7 +238,7 @@ class Fcn8Model:
         import torch
         lib = _lib.load()
         om = _OUT[out]
-        dmode, npts = decode_mode_of(n_points) if om == _lib.OUT_LANDMARKS else (0, 0)
+        dmode, npts = decode_mode_of(n_points) if om in _DECODING else (0, 0)
         fo = self._opts(opts)
         off = lib.flm_fcn8_workspace_offset_opts(name.encode(), n, self.input_height, self.input_width, self.n_classes,
                                                  self._dt, om, dmode, npts, C.byref(fo))

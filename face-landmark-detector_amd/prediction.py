@@ -108,9 +108,38 @@ def keypts_predict(model=None, inp=None, out_fname=None, checkpoints_path=None, 
 
 
 # ---- batch entry points --------------------------------------------------------------------------------
-def predict(crops, model, n_points=4, thresh=0.0, to_input_space=False):
+def _fit_weights(weights, landmarks_given):
+    """The `weights` argument of align / align_frames: None, "score" or an [N,C] array / tensor; anything else is a
+    ValueError raised before any device work."""
+    if weights is None:
+        return
+    if isinstance(weights, str):
+        if weights != "score":
+            raise ValueError("weights must be None, \"score\" or an [N,C] tensor (got %r)" % (weights,))
+        if landmarks_given:
+            raise ValueError("weights=\"score\" needs the model's own forward: pass the weights as a tensor with `landmarks`")
+    elif getattr(weights, "ndim", None) != 2:
+        raise ValueError("weights must be None, \"score\" or an [N,C] tensor")
+
+
+def _weights_on_device(weights, n, c, dev):
+    import torch
+    w = torch.as_tensor(weights).to(device=dev, dtype=torch.float64)
+    if tuple(w.shape) != (n, c):
+        raise ValueError("weights must be [%d,%d], got %s" % (n, c, tuple(w.shape)))
+    return w
+
+
+def predict(crops, model, n_points=4, thresh=0.0, to_input_space=False, return_stats=False):
     """Batched landmarks: crops [N,H,W,3] (numpy or CUDA tensor; uint8 BGR or float32
     preprocessed) -> float64 [N,C,2] (x,y).
+
+    `return_stats=True` returns (landmarks [N,C,2], score [N,C], cov [N,C,3]) instead: three views of ONE landmark
+    record tensor [N,C,6] (forward_device "landmark_stats"; include/flm.h).  score is the mean selected probability the
+    reject test of utils/metrics.py:78-79 compares -- the reference computes it and keeps only the verdict, which with
+    the shipped thresh = 0 never rejects; cov = (var_x, var_y, cov_xy) of the selected pixels about (x, y), in
+    output-grid px^2, (-1, -1, 0) for a rejected landmark.  `to_input_space` scales the COORDINATES only: score has no
+    unit and cov stays in output-grid px^2.
 
     Coordinates are in output-grid pixels (0..W'-1), as the reference's decode leaves them
     (utils/metrics.py:80); `to_input_space=True` rescales to input-crop pixels
@@ -119,34 +148,60 @@ def predict(crops, model, n_points=4, thresh=0.0, to_input_space=False):
     Returns the type it was given (numpy -> numpy, CUDA tensor -> CUDA tensor).
     """
     import torch
+    if return_stats not in (False, True):
+        raise ValueError("return_stats must be a bool")
+    if return_stats and (getattr(crops, "ndim", None) != 4 or crops.shape[3] != 3):
+        raise ValueError("crops must be [N,H,W,3]")
     was_np = not isinstance(crops, torch.Tensor)
     xd = torch.from_numpy(np.ascontiguousarray(crops)).to(_lib.require_gpu()) if was_np else crops
-    lm = model.forward_device(xd, "landmarks", n_points=n_points, thresh=thresh)
+    rec = model.forward_device(xd, "landmark_stats" if return_stats else "landmarks", n_points=n_points, thresh=thresh)
+    if was_np and return_stats:
+        rec = rec.cpu()
+    lm = rec[..., :2] if return_stats else rec
     if to_input_space:
         scale = torch.tensor([model.input_width / model.output_width, model.input_height / model.output_height],
                              dtype=torch.float64, device=lm.device)
-        lm = torch.where(lm < 0, lm, lm * scale)
+        if return_stats:
+            lm.copy_(torch.where(lm < 0, lm, lm * scale))   # in place: the three results stay views of one tensor
+        else:
+            lm = torch.where(lm < 0, lm, lm * scale)
+    if return_stats:
+        out = (lm, rec[..., 2], rec[..., 3:])
+        return tuple(t.numpy() for t in out) if was_np else out
     return lm.cpu().numpy() if was_np else lm
 
 
-def align(crops, model=None, landmarks=None, template=None, out_size=None, n_points=4, thresh=0.0):
+def align(crops, model=None, landmarks=None, template=None, out_size=None, n_points=4, thresh=0.0, weights=None):
     """Align face crops by the similarity transform that maps their landmarks onto a template.
 
     crops [N,H,W,3] uint8/float32; `landmarks` float64 [N,C,2] in output-grid pixels (predicted
     with `model` when omitted); `template` float64 [C,2] in aligned-image pixels (default
     `alignment.canonical_template`); out_size (h, w) defaults to the crop size.
     Returns (aligned float32 [N,h,w,3], M float32 [N,2,3], landmarks).
+
+    `weights` weighs the landmarks of the fit (flm_similarity_from_landmarks_weighted): None, the unweighted fit on every
+    landmark the decode kept -- with the shipped thresh = 0 that is all of them, occluded ones included; "score", the
+    model's own per-landmark score: the forward runs in its "landmark_stats" mode and the fit reads coordinates and
+    scores from that record tensor in place, no launch in between; or a float64 [N,C] array / tensor (weight <= 0 or
+    NaN: the landmark is left out).  With weights the call returns a fourth value, the [N,C] weights it used.
     """
     import torch
+    _fit_weights(weights, landmarks is not None)
     was_np = not isinstance(crops, torch.Tensor)
     dev = _lib.require_gpu()
     xd = torch.from_numpy(np.ascontiguousarray(crops)).to(dev) if was_np else crops
     if landmarks is None:
         if model is None:
             raise ValueError("align needs either landmarks or a model")
-        lm = model.forward_device(xd, "landmarks", n_points=n_points, thresh=thresh)
+        if isinstance(weights, str):   # "score"
+            rec = model.forward_device(xd, "landmark_stats", n_points=n_points, thresh=thresh)
+            lm, wd = rec[..., :2], rec[..., 2]
+        else:
+            lm = model.forward_device(xd, "landmarks", n_points=n_points, thresh=thresh)
     else:
         lm = torch.as_tensor(landmarks, dtype=torch.float64).to(dev)
+    if weights is not None and not isinstance(weights, str):
+        wd = _weights_on_device(weights, int(lm.shape[0]), int(lm.shape[1]), dev)
     h, w = int(xd.shape[1]), int(xd.shape[2])
     oh, ow = out_size if out_size is not None else (h, w)
     k = int(lm.shape[1])
@@ -156,6 +211,11 @@ def align(crops, model=None, landmarks=None, template=None, out_size=None, n_poi
     sc = (1.0, 1.0)
     if model is not None:
         sc = (model.input_width / model.output_width, model.input_height / model.output_height)
+    if weights is not None:
+        aligned, m = alignment.align_device(xd, lm, tmd, oh, ow, sc, weights=wd)
+        if was_np:
+            return aligned.cpu().numpy(), m.cpu().numpy(), lm.cpu().numpy(), wd.cpu().numpy()
+        return aligned, m, lm, wd
     aligned, m = alignment.align_device(xd, lm, tmd, oh, ow, sc)
     if was_np:
         return aligned.cpu().numpy(), m.cpu().numpy(), lm.cpu().numpy()
@@ -283,7 +343,7 @@ _TEMPLATES = {}   # (landmarks, out_h, out_w, device) -> canonical template on t
 
 
 def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 112), n_points=4, thresh=0.0,
-                 frame_index=None, samples=1):
+                 frame_index=None, samples=1, weights=None):
     """The multi-face stream end to end in FRAME coordinates: detector boxes of a group of frames -> aligned faces
     sampled from the frames themselves.
 
@@ -293,10 +353,14 @@ def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 1
     alignment.landmarks_to_frame_device -> alignment.similarity_device -> alignment.warp_frames_device: one upload (the
     boxes), no download, no host synchronisation.  `template` float64 [C,2] in aligned pixels (numpy or CUDA; default
     `alignment.canonical_template`); `samples` 1, 2 or 4 bilinear samples per axis and aligned pixel (for faces much
-    larger than out_size).
+    larger than out_size).  `weights`: None, "score" or a float64 [K,C] tensor, as `align` takes it -- "score" runs the
+    forward in its "landmark_stats" mode, hands a contiguous copy of the record's xy columns (16 bytes per landmark) to
+    flm_landmarks_to_frame and feeds the score column to the weighted fit in place; the call then returns the [K,C]
+    weights it used as a fifth value.
     Returns CUDA tensors (aligned float32 [K,oh,ow,3], M float32 [K,2,3] frame px -> aligned px, landmarks float64
     [K,C,2] in frame px with (-1,-1) for rejected points, squared boxes int32 [K,4]); K == 0 launches nothing."""
     import torch
+    _fit_weights(weights, False)
     if isinstance(frames, (list, tuple)):
         if not len(frames) or any(not isinstance(f, torch.Tensor) or f.dim() != 3 or f.dtype != torch.uint8
                                   or tuple(f.shape) != tuple(frames[0].shape) for f in frames):
@@ -324,9 +388,10 @@ def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 1
                                                       frame_index=slots, return_device=True)
     k = int(crops.shape[0])
     if k == 0:
-        return (torch.empty((0, oh, ow, 3), dtype=torch.float32, device=dev),
-                torch.empty((0, 2, 3), dtype=torch.float32, device=dev),
-                torch.empty((0, c, 2), dtype=torch.float64, device=dev), boxes_dev)
+        empty = (torch.empty((0, oh, ow, 3), dtype=torch.float32, device=dev),
+                 torch.empty((0, 2, 3), dtype=torch.float32, device=dev),
+                 torch.empty((0, c, 2), dtype=torch.float64, device=dev), boxes_dev)
+        return empty if weights is None else empty + (torch.empty((0, c), dtype=torch.float64, device=dev),)
     if template is None:
         key = (c, oh, ow, str(dev))
         if key not in _TEMPLATES:
@@ -338,11 +403,20 @@ def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 1
         tmd = torch.from_numpy(np.ascontiguousarray(np.asarray(template, np.float64))).to(dev)
     if tuple(tmd.shape) != (c, 2):
         raise ValueError("template must be [%d,2]" % c)
-    lm = model.forward_device(crops, "landmarks", n_points=n_points, thresh=thresh)
+    wd = None
+    if isinstance(weights, str):   # "score"
+        rec = model.forward_device(crops, "landmark_stats", n_points=n_points, thresh=thresh)
+        lm, wd = rec[..., :2].contiguous(), rec[..., 2]
+    else:
+        lm = model.forward_device(crops, "landmarks", n_points=n_points, thresh=thresh)
+        if weights is not None:
+            wd = _weights_on_device(weights, k, c, dev)
     lm = alignment.landmarks_to_frame_device(lm, boxes_dev, (model.output_height, model.output_width), (fh, fw))
-    m = alignment.similarity_device(lm, tmd)
+    m = alignment.similarity_device(lm, tmd, weights=wd)
     aligned = alignment.warp_frames_device(frames, m, oh, ow, frame_index_dev=idx_dev, boxes_dev=boxes_dev,
                                            samples=samples)
+    if weights is not None:
+        return aligned, m, lm, boxes_dev, wd
     return aligned, m, lm, boxes_dev
 
 

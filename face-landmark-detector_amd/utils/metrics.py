@@ -58,6 +58,31 @@ def decode_device(hm, n_points=4, thresh=0.0, out=None):
     return out
 
 
+def decode_stats_device(hm, n_points=4, thresh=0.0, out=None):
+    """hm: CUDA float32 [N,H,W,L] contiguous -> CUDA float64 [N,L,6] landmark records (flm_decode_stats): per landmark
+    x, y, score, var_x, var_y, cov_xy.  x, y are decode_device's bits; score is the mean selected value the reject test of
+    utils/metrics.py:78-79 compares (the reference computes it and keeps only the verdict); the moments are the
+    value-weighted spread of the selected pixels about (x, y) in px^2.  A rejected landmark reads (-1, -1, score, -1, -1, 0)."""
+    import torch
+    lib = _lib.load()
+    if hm.dim() != 4 or hm.dtype != torch.float32 or not hm.is_cuda or not hm.is_contiguous():
+        raise ValueError("decode_stats_device needs a contiguous CUDA float32 [N,H,W,L] tensor")
+    n, h, w, l = [int(v) for v in hm.shape]
+    shape = (n, l, _lib.LANDMARK_REC)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=hm.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError("out must be a contiguous CUDA float64 %s tensor" % (shape,))
+    if n == 0:
+        return out
+    mode, npts = (_lib.DECODE_ALL, 0) if n_points < 1 else (_lib.DECODE_TOPN, int(n_points))
+    nbytes = lib.flm_decode_stats_workspace_bytes(n, h, w, l, mode, npts)
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=hm.device)
+    _lib.check(lib.flm_decode_stats(_lib.stream_ptr(), _lib.ptr(hm), n, h, w, l, mode, npts, float(thresh),
+                                    _lib.ptr(out), _lib.ptr(ws), ws.numel()), "flm_decode_stats")
+    return out
+
+
 def _to_device(a):
     import torch
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(_lib.require_gpu())
@@ -94,6 +119,16 @@ def transfer_target(y_pred, thresh=_UNSET, n_points=_UNSET, as_shipped=None):
         hm = _to_device(np.asarray(y_pred))
     out = decode_device(hm, n_points, thresh)
     return out.reshape(out.shape[0], 2 * out.shape[1]).cpu().numpy()
+
+
+def transfer_target_stats(y_pred, thresh=0, n_points=4):
+    """transfer_target's maps -> the landmark records of decode_stats_device: [N,H,W,L] -> float64 [N,L,6].  numpy in ->
+    numpy out, torch tensor in -> CUDA tensor out.  `thresh` and `n_points` are honoured as given (defaults: the decode
+    the reference runs as shipped, top-4 with thresh 0)."""
+    import torch
+    was_np = not isinstance(y_pred, torch.Tensor)
+    out = decode_stats_device(_maps_on_device(y_pred), n_points, thresh)
+    return out.cpu().numpy() if was_np else out
 
 
 def get_RMSE(y_pred_xy, y_train_xy, pick_not_NA):

@@ -68,7 +68,9 @@ enum flm_output_mode {
   FLM_OUT_PROBS = 0,     /* float32 [N, H'*W', C]: model.predict (networks/utils.py:28-30) */
   FLM_OUT_CLASSMAP = 1,  /* int32 [N, H', W']: pr.argmax(axis=2) (prediction.py:209) */
   FLM_OUT_LANDMARKS = 2, /* float64 [N, C, 2] (x,y): transfer_target (utils/metrics.py:102-109) */
-  FLM_OUT_LOGITS = 3     /* float32 [N, H', W', C] before the softmax (debug / tests) */
+  FLM_OUT_LOGITS = 3,    /* float32 [N, H', W', C] before the softmax (debug / tests) */
+  FLM_OUT_LANDMARKS_STATS = 4 /* float64 [N, C, FLM_LANDMARK_REC] landmark records (below, at flm_decode_stats): the
+                                 landmarks of FLM_OUT_LANDMARKS, bit for bit, with their score and spread */
 };
 
 enum flm_decode_mode {
@@ -312,6 +314,36 @@ int flm_decode(flm_stream_t stream, const float* hm_dev, int n, int h, int w, in
                int n_points, float thresh, double* out_dev, void* workspace_dev,
                size_t workspace_bytes);
 
+/* ---- the landmark record -----------------------------------------------------------
+ * The decode with what it knows about every landmark kept: float64 [N,L,FLM_LANDMARK_REC], one row per landmark,
+ *   x, y, score, var_x, var_y, cov_xy
+ * in heatmap pixel units (px and px^2); score is the mean selected value the reject test of utils/metrics.py:78-79
+ * compares.  Operation by operation (-ffp-contract=off: only the fma named below fuses):
+ *  top-n (n_points >= 1), keys visited rank n-1 down to rank 0, empty slots skipped:
+ *    hsum (float32) += hv;  i0 += (double)row * (double)hv;  i1 += (double)col * (double)hv
+ *    x = i1 / (double)hsum;  y = i0 / (double)hsum                      -- flm_decode's chain and bits
+ *    score = (double)(hsum / (float)n_points)                           -- the float32 quotient, widened
+ *    rejected (hsum / (float)n_points <= thresh):  x = y = -1, var_x = var_y = -1, cov_xy = 0; score is still written
+ *    else a second walk in the same order: dx = (double)col - x, dy = (double)row - y,
+ *      vxx += (double)hv * (dx*dx);  vyy += (double)hv * (dy*dy);  vxy += (double)hv * (dx*dy)
+ *      var_x = vxx / (double)hsum;  var_y = vyy / (double)hsum;  cov_xy = vxy / (double)hsum
+ *    (centred on purpose: every term of vxx and vyy is non-negative, nothing cancels; n_points = 1 gives exact zeros)
+ *  all-pixel (n_points < 1):
+ *    per lane and chunk, in pixel order, float64: S0 += hv, Sx = fma(hv, col, Sx), Sy = fma(hv, row, Sy) as flm_decode,
+ *    and beside them Sxx = fma(hv, col*col, Sxx), Syy = fma(hv, row*row, Syy), Sxy = fma(hv, col*row, Sxy); lanes are
+ *    added by the same fixed-order butterfly, chunks in chunk order
+ *    hsum = (float)S0;  x = Sx / (double)hsum;  y = Sy / (double)hsum   -- flm_decode's bits
+ *    score = (double)(hsum / (float)(H*W));  rejected rows as above
+ *    var_x = max(0, Sxx / (double)hsum - x*x);  var_y = max(0, Syy / (double)hsum - y*y);  cov_xy = Sxy / (double)hsum - x*y
+ * A map on which flm_decode yields NaN (hsum == 0 under a negative thresh) yields NaN moments too.
+ * flm_decode_stats has flm_decode's contracts and error codes (l <= 96, n_points <= 128, 16-byte aligned maps) and
+ * reads the maps once; its workspace differs from flm_decode's only by the all-pixel partial sums (six instead of
+ * three).  The workspace query returns 0 for arguments the call rejects. */
+#define FLM_LANDMARK_REC 6
+size_t flm_decode_stats_workspace_bytes(int n, int h, int w, int l, int mode, int n_points);
+int flm_decode_stats(flm_stream_t stream, const float* hm_dev, int n, int h, int w, int l, int mode, int n_points,
+                     float thresh, double* rec_dev /*[N,L,6]*/, void* workspace_dev, size_t workspace_bytes);
+
 /* One read of the maps, up to FLM_SWEEP_MAX_MODES decodes (the n_points experiment of utils/metrics.py:118-154).
  * `modes` (host memory, n_modes entries, duplicates and any order allowed): 0 = all-pixel centroid, 1..128 = top-n.
  * out: float64 [n_modes, N, L, 2], slice m for modes[m].  A top-n slice is byte for byte what flm_decode(TOPN, n)
@@ -347,6 +379,21 @@ int flm_similarity_from_landmarks(flm_stream_t stream, const double* lm_dev /*[N
 int flm_similarity_from_landmarks_scaled(flm_stream_t stream, const double* lm_dev /*[N,K,2]*/,
                                          const double* tmpl_dev /*[K,2]*/, int n, int k, double sx, double sy,
                                          float* m_dev /*[N,2,3]*/);
+/* The same fit with a weight per point, read at element strides: point i of face f is the two doubles at
+ * lm_dev + (f*k + i)*lm_stride, its weight the double at w_dev + (f*k + i)*w_stride; w_dev == NULL: every weight is 1.
+ * With strides of FLM_LANDMARK_REC and w_dev = rec_dev + 2 the fit reads the forward's landmark records in place,
+ * weighted by their scores.  A point takes part when both coordinates are >= 0 and its weight is > 0 (a NaN weight
+ * fails that test and is left out).  float64, sequential sums in landmark order over the participating points, the
+ * coordinates first multiplied by sx, sy as in the _scaled call:
+ *   W = sum w;  mpx = sum(w*px) / W, likewise mpy, mqx, mqy (q: the template);  p' = p - mp, q' = q - mq
+ *   sa = sum w*(px'*qx' + py'*qy');  sb = sum w*(px'*qy' - py'*qx');  var = sum w*(px'*px' + py'*py')
+ *   a = sa / var, b = sb / var, tx = mqx - (a*mpx - b*mpy), ty = mqy - (b*mpx + a*mpy);  M = [[a,-b,tx],[b,a,ty]]
+ * Fewer than two participating points, or var <= 0, gives the identity.  With unit weights every product by w is exact
+ * and W is the count: the bits of flm_similarity_from_landmarks_scaled.
+ * Errors: null lm, tmpl or m -> FLM_ERR_ARG; lm_stride < 2, w_stride < 1, n < 1 or k outside [1,1024] -> FLM_ERR_SHAPE. */
+int flm_similarity_from_landmarks_weighted(flm_stream_t stream, const double* lm_dev, size_t lm_stride,
+                                           const double* w_dev, size_t w_stride, const double* tmpl_dev /*[K,2]*/,
+                                           int n, int k, double sx, double sy, float* m_dev /*[N,2,3]*/);
 int flm_warp_affine(flm_stream_t stream, const void* src_dev /*[N,Hs,Ws,3]*/, int src_is_u8, int n,
                     int hs, int ws, const float* m_dev /*[N,2,3] src->dst*/,
                     float* dst_dev /*[N,Hd,Wd,3]*/, int hd, int wd);
