@@ -20,6 +20,8 @@ DECODE_ALL, DECODE_TOPN = 0, 1
 NORM_SUB_MEAN, NORM_SUB_AND_DIVIDE, NORM_DIVIDE = 0, 1, 2
 ABI_VERSION = 2
 SWEEP_MAX_MODES = 16  # FLM_SWEEP_MAX_MODES
+LAYOUT_NHWC, LAYOUT_NCHW = 0, 1                      # flm_pixel_layout
+PIX_F32, PIX_F16, PIX_BF16, PIX_U8 = 0, 1, 2, 3      # flm_pixel_type
 
 EXPORTS = [
     "flm_abi_version", "flm_last_error",
@@ -35,6 +37,7 @@ EXPORTS = [
     "flm_gaussian_heatmaps",
     "flm_similarity_from_landmarks", "flm_similarity_from_landmarks_scaled", "flm_warp_affine", "flm_crop_resize", "flm_crop_resize_frames",
     "flm_landmarks_to_frame", "flm_warp_affine_frames",
+    "flm_image_format_init", "flm_image_format_bytes", "flm_warp_affine_fmt", "flm_warp_affine_frames_fmt",
 ]
 
 
@@ -68,6 +71,12 @@ class ForwardOpts(C.Structure):
 
     def key(self):
         return (self.landmark_candidates, self.candidate_sub_phases, self.candidate_cap_div)
+
+
+class ImageFormat(C.Structure):
+    """flm_image_format: layout, type, channel order, scale and bias of the aligned faces (include/flm.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("layout", C.c_int32), ("type", C.c_int32), ("reverse_channels", C.c_int32),
+                ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
 
 
 class FcnParams(C.Structure):
@@ -173,6 +182,15 @@ def _declare(lib):
     lib.flm_landmarks_to_frame.argtypes = [vp, vp, vp, i, i, i, i, i, i, vp]
     lib.flm_warp_affine_frames.restype = i
     lib.flm_warp_affine_frames.argtypes = [vp, vp, C.c_size_t, i, i, i, vp, vp, vp, i, vp, i, i, i]
+    lib.flm_image_format_init.restype = None
+    lib.flm_image_format_init.argtypes = [C.POINTER(ImageFormat)]
+    lib.flm_image_format_bytes.restype = sz
+    lib.flm_image_format_bytes.argtypes = [C.POINTER(ImageFormat), i, i, i]
+    lib.flm_warp_affine_fmt.restype = i
+    lib.flm_warp_affine_fmt.argtypes = [vp, vp, i, i, i, i, vp, vp, i, i, C.POINTER(ImageFormat)]
+    lib.flm_warp_affine_frames_fmt.restype = i
+    lib.flm_warp_affine_frames_fmt.argtypes = [vp, vp, C.c_size_t, i, i, i, vp, vp, vp, i, vp, i, i, i,
+                                               C.POINTER(ImageFormat)]
 
 
 def load():

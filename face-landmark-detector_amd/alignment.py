@@ -43,6 +43,129 @@ def canonical_template(n_landmarks: int, out_h: int, out_w: int) -> np.ndarray:
     return pts * np.array([out_w - 1, out_h - 1], np.float64)
 
 
+class AlignedFormat:
+    """What the aligned faces look like when they leave the warp (flm_image_format, include/flm.h): the conversion runs
+    in the warp's own store, so no float32 [N,h,w,3] copy exists and no launch follows.
+
+    layout   "nhwc" [N,h,w,3] or "nchw" [N,3,h,w], dense
+    dtype    "float32", "float16", "bfloat16" or "uint8" (a torch or numpy dtype of those names does too)
+    channels "bgr": output channel c is source channel c (the sources of this package are BGR throughout);
+             "rgb": output channel c is source channel 2-c
+    scale, bias  three numbers each, by OUTPUT channel (one number: all three): stored = convert(v * scale + bias), a
+             float32 multiply, then a float32 add, then the rounding the header states per type (float16 / bfloat16:
+             nearest even; uint8: rint, clamped to [0,255]).
+
+    The defaults are the format the warps have without one: float32 NHWC BGR, scale 1, bias 0."""
+    _LAYOUTS = {"nhwc": _lib.LAYOUT_NHWC, "nchw": _lib.LAYOUT_NCHW}
+    _DTYPES = {"float32": _lib.PIX_F32, "float16": _lib.PIX_F16, "bfloat16": _lib.PIX_BF16, "uint8": _lib.PIX_U8}
+    _ITEMSIZE = {"float32": 4, "float16": 2, "bfloat16": 2, "uint8": 1}
+
+    def __init__(self, layout="nhwc", dtype="float32", channels="bgr", scale=(1.0, 1.0, 1.0), bias=(0.0, 0.0, 0.0)):
+        if not isinstance(layout, str) or layout.lower() not in self._LAYOUTS:
+            raise ValueError("layout must be \"nhwc\" or \"nchw\" (got %r)" % (layout,))
+        if isinstance(dtype, str):
+            name = dtype
+        else:
+            try:
+                name = np.dtype(dtype).name
+            except TypeError:   # a torch dtype
+                name = str(dtype)
+        name = name.lower().replace("torch.", "")
+        if name not in self._DTYPES:
+            raise ValueError("dtype must be one of %s (got %r)" % (", ".join(sorted(self._DTYPES)), dtype))
+        if not isinstance(channels, str) or channels.lower() not in ("bgr", "rgb"):
+            raise ValueError("channels must be \"bgr\" or \"rgb\" (got %r)" % (channels,))
+        self.layout = layout.lower()
+        self.dtype = name
+        self.channels = channels.lower()
+        self.scale = self._triple("scale", scale)
+        self.bias = self._triple("bias", bias)
+
+    @staticmethod
+    def _triple(what, v):
+        if isinstance(v, (int, float)) and not isinstance(v, bool):
+            v = (v, v, v)
+        try:
+            vals = tuple(float(x) for x in v)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be three numbers (got %r)" % (what, v))
+        if len(vals) != 3:
+            raise ValueError("%s must have one value per channel, three in all (got %d)" % (what, len(vals)))
+        # the C struct holds float32: a value that is finite only in float64 is not a scale the kernel can apply
+        with np.errstate(over="ignore"):
+            if not all(np.isfinite(np.float32(x)) for x in vals):
+                raise ValueError("%s must be finite in float32 (got %r)" % (what, vals))
+        return vals
+
+    @classmethod
+    def matcher(cls, dtype="float16"):
+        """What face-embedding networks take: planar [N,3,h,w], RGB, (x - 127.5) / 127.5 written as x * (1/127.5) - 1."""
+        return cls("nchw", dtype, "rgb", (1.0 / 127.5,) * 3, (-1.0,) * 3)
+
+    @property
+    def torch_dtype(self):
+        import torch
+        return getattr(torch, self.dtype)
+
+    @property
+    def numpy_dtype(self):
+        """The numpy type of the same bits, None for bfloat16 (numpy has none)."""
+        return None if self.dtype == "bfloat16" else np.dtype(self.dtype)
+
+    @property
+    def itemsize(self):
+        return self._ITEMSIZE[self.dtype]
+
+    def shape(self, n, h, w):
+        n, h, w = int(n), int(h), int(w)
+        return (n, h, w, 3) if self.layout == "nhwc" else (n, 3, h, w)
+
+    def nbytes(self, n, h, w):
+        return int(n) * int(h) * int(w) * 3 * self.itemsize
+
+    def struct(self):
+        """The flm_image_format of this format (struct_size set, as flm_image_format_init sets it)."""
+        f = _lib.ImageFormat()
+        f.struct_size = _lib.C.sizeof(_lib.ImageFormat)
+        f.layout = self._LAYOUTS[self.layout]
+        f.type = self._DTYPES[self.dtype]
+        f.reverse_channels = int(self.channels == "rgb")
+        for c in range(3):
+            f.scale[c] = self.scale[c]
+            f.bias[c] = self.bias[c]
+        return f
+
+    def key(self):
+        return (self.layout, self.dtype, self.channels, self.scale, self.bias)
+
+    def __eq__(self, other):
+        return isinstance(other, AlignedFormat) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        return "AlignedFormat(layout=%r, dtype=%r, channels=%r, scale=%r, bias=%r)" % self.key()
+
+
+def _check_format(fmt):
+    if not isinstance(fmt, AlignedFormat):
+        raise ValueError("fmt must be an alignment.AlignedFormat or None (got %r)" % (fmt,))
+
+
+def _format_out(fmt, out, n, h, w, device):
+    """The destination of a formatted warp: a new tensor of the format's dtype and shape, or `out` checked against them."""
+    import torch
+    shape = fmt.shape(n, h, w)
+    if out is None:
+        return torch.empty(shape, dtype=fmt.torch_dtype, device=device)
+    if not isinstance(out, torch.Tensor) or out.dtype != fmt.torch_dtype or tuple(out.shape) != shape:
+        raise ValueError("out must be a %s tensor of shape %s for %r" % (fmt.dtype, list(shape), fmt))
+    if not out.is_cuda or not out.is_contiguous():
+        raise ValueError("out must be a contiguous CUDA tensor")
+    return out
+
+
 def _uniform_stride(t, inner):
     """Element stride between consecutive points of a [N,K(,inner)] view whose points lie `stride` elements apart, the
     `inner` elements of a point adjacent (rec[..., :2], rec[..., 2] of a landmark record tensor); None when the view has
@@ -100,13 +223,28 @@ def similarity_device(landmarks, template, landmark_scale=(1.0, 1.0), weights=No
     return m
 
 
-def warp_device(src, m, out_h, out_w, out=None):
-    """src: CUDA uint8/float32 [N,Hs,Ws,3]; m: CUDA float32 [N,2,3] (source -> aligned)."""
+def warp_device(src, m, out_h, out_w, out=None, fmt=None):
+    """src: CUDA uint8/float32 [N,Hs,Ws,3]; m: CUDA float32 [N,2,3] (source -> aligned).
+    `fmt`: an AlignedFormat -- the faces leave the warp in that layout, type, channel order and normalisation
+    (flm_warp_affine_fmt; `out`, when given, must have the format's dtype and shape); None: float32 [N,h,w,3] from
+    flm_warp_affine, as ever."""
     import torch
-    lib = _lib.load()
+    if fmt is not None:
+        _check_format(fmt)
     if src.dim() != 4 or src.shape[3] != 3 or src.dtype not in (torch.uint8, torch.float32):
         raise ValueError("src must be uint8/float32 [N,H,W,3]")
     n, hs, ws, _ = [int(v) for v in src.shape]
+    if fmt is not None:
+        out_h, out_w = int(out_h), int(out_w)
+        out = _format_out(fmt, out, n, out_h, out_w, src.device)
+        if n:
+            lib = _lib.load()
+            cf = fmt.struct()
+            _lib.check(lib.flm_warp_affine_fmt(_lib.stream_ptr(), _lib.ptr(src.contiguous()), int(src.dtype == torch.uint8),
+                                               n, hs, ws, _lib.ptr(m.contiguous()), _lib.ptr(out), out_h, out_w,
+                                               _lib.C.byref(cf)), "flm_warp_affine_fmt")
+        return out
+    lib = _lib.load()
     if out is None:
         out = torch.empty((n, out_h, out_w, 3), dtype=torch.float32, device=src.device)
     _lib.check(lib.flm_warp_affine(_lib.stream_ptr(), _lib.ptr(src.contiguous()), int(src.dtype == torch.uint8),
@@ -115,11 +253,16 @@ def warp_device(src, m, out_h, out_w, out=None):
     return out
 
 
-def align_device(crops, landmarks_in, template, out_h, out_w, landmark_scale=(1.0, 1.0), weights=None):
+def align_device(crops, landmarks_in, template, out_h, out_w, landmark_scale=(1.0, 1.0), weights=None, fmt=None):
     """crops [N,H,W,3] + landmarks (crop pixel units after `landmark_scale`) -> aligned crops, M.
-    `weights`: per-landmark weights of the fit, as similarity_device takes them."""
+    `weights`: per-landmark weights of the fit, as similarity_device takes them; `fmt`: the AlignedFormat of the aligned
+    crops, as warp_device takes it (M does not depend on it)."""
+    if fmt is not None:
+        _check_format(fmt)
     m = similarity_device(landmarks_in, template, landmark_scale, weights)
-    return warp_device(crops, m, out_h, out_w), m
+    if fmt is None:
+        return warp_device(crops, m, out_h, out_w), m
+    return warp_device(crops, m, out_h, out_w, fmt=fmt), m
 
 
 def _check_boxes(boxes_dev, k):
@@ -155,12 +298,17 @@ def landmarks_to_frame_device(lm, boxes_dev, grid_hw, frame_hw, out=None):
     return out
 
 
-def warp_frames_device(frames, m, out_h, out_w, frame_index_dev=None, boxes_dev=None, samples=1, out=None):
+def warp_frames_device(frames, m, out_h, out_w, frame_index_dev=None, boxes_dev=None, samples=1, out=None, fmt=None):
     """frames: contiguous CUDA uint8 [F,H,W,3] ring; m: CUDA float32 [K,2,3] (FRAME pixels -> aligned pixels);
     frame_index_dev: CUDA int32 [K] ring slot of every face (default: slot 0); boxes_dev: CUDA int32 [K,4], faces whose
     clipped box is empty come back as zeros; samples: 1, 2 or 4 bilinear samples per axis and output pixel
-    -> CUDA float32 [K,out_h,out_w,3] (flm_warp_affine_frames)."""
+    -> CUDA float32 [K,out_h,out_w,3] (flm_warp_affine_frames).
+    `fmt`: an AlignedFormat -- the faces leave the warp in that layout, type, channel order and normalisation
+    (flm_warp_affine_frames_fmt), e.g. AlignedFormat.matcher() -> CUDA float16 [K,3,out_h,out_w], RGB, in [-1,1];
+    `out`, when given, must then have the format's dtype and shape."""
     import torch
+    if fmt is not None:
+        _check_format(fmt)
     if (not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8
             or not frames.is_cuda or not frames.is_contiguous()):
         raise ValueError("frames must be a contiguous CUDA uint8 [F,H,W,3] tensor")
@@ -179,6 +327,18 @@ def warp_frames_device(frames, m, out_h, out_w, frame_index_dev=None, boxes_dev=
         raise ValueError("frame_index_dev must be a contiguous CUDA int32 [%d] tensor" % k)
     if boxes_dev is not None:
         _check_boxes(boxes_dev, k)
+    if fmt is not None:
+        out = _format_out(fmt, out, k, out_h, out_w, frames.device)
+        if k:
+            lib = _lib.load()
+            cf = fmt.struct()
+            _lib.check(lib.flm_warp_affine_frames_fmt(_lib.stream_ptr(), _lib.ptr(frames), fh * fw * 3, nf, fh, fw,
+                                                      None if frame_index_dev is None else _lib.ptr(frame_index_dev),
+                                                      None if boxes_dev is None else _lib.ptr(boxes_dev),
+                                                      _lib.ptr(m.contiguous()), k, _lib.ptr(out), out_h, out_w,
+                                                      int(samples), _lib.C.byref(cf)),
+                       "flm_warp_affine_frames_fmt")
+        return out
     if out is None:
         out = torch.empty((k, out_h, out_w, 3), dtype=torch.float32, device=frames.device)
     elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (k, out_h, out_w, 3)

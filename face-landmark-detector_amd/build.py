@@ -34,6 +34,7 @@ SOURCES = [
     "flm_cand.hip",
     "flm_misc.hip",
     "flm_frames.hip",
+    "flm_warp_fmt.hip",
     "flm_mobile.hip",
 ]
 # -ffp-contract=off: only the fma() calls written in the sources fuse, so the arithmetic of the

@@ -1,4 +1,5 @@
 // extern "C" entry points of libflm_hip.so (see include/flm.h) and the forward's launch sequence.
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -884,6 +885,95 @@ int flm_warp_affine_frames(flm_stream_t stream, const uint8_t* frames, size_t fr
   }
   return launch_warp_frames(static_cast<hipStream_t>(stream), frames, frame_stride, nframes, fh, fw, frame_idx, boxes, m,
                             k, dst, hd, wd, samples);
+}
+
+void flm_image_format_init(flm_image_format* fmt) {
+  if (!fmt) return;
+  fmt->struct_size = (uint32_t)sizeof(flm_image_format);
+  fmt->layout = FLM_LAYOUT_NHWC;
+  fmt->type = FLM_PIX_F32;
+  fmt->reverse_channels = 0;
+  for (int c = 0; c < 3; ++c) {
+    fmt->scale[c] = 1.0f;
+    fmt->bias[c] = 0.0f;
+  }
+}
+
+// FLM_OK, or FLM_ERR_ARG with the reason in the message; `who` names the call.
+static int check_image_format(const char* who, const flm_image_format* fmt) {
+  if (!fmt) {
+    set_error("%s: null format", who);
+    return FLM_ERR_ARG;
+  }
+  if (fmt->struct_size < sizeof(flm_image_format)) {
+    set_error("%s: flm_image_format struct_size %u is smaller than this library's %zu (initialise with "
+              "flm_image_format_init)", who, fmt->struct_size, sizeof(flm_image_format));
+    return FLM_ERR_ARG;
+  }
+  if (fmt->layout != FLM_LAYOUT_NHWC && fmt->layout != FLM_LAYOUT_NCHW) {
+    set_error("%s: unknown layout %d", who, fmt->layout);
+    return FLM_ERR_ARG;
+  }
+  if (fmt->type != FLM_PIX_F32 && fmt->type != FLM_PIX_F16 && fmt->type != FLM_PIX_BF16 && fmt->type != FLM_PIX_U8) {
+    set_error("%s: unknown pixel type %d", who, fmt->type);
+    return FLM_ERR_ARG;
+  }
+  if (fmt->reverse_channels != 0 && fmt->reverse_channels != 1) {
+    set_error("%s: reverse_channels=%d (must be 0 or 1)", who, fmt->reverse_channels);
+    return FLM_ERR_ARG;
+  }
+  for (int c = 0; c < 3; ++c) {
+    if (!std::isfinite(fmt->scale[c]) || !std::isfinite(fmt->bias[c])) {
+      set_error("%s: scale and bias must be finite (channel %d: %g, %g)", who, c, (double)fmt->scale[c],
+                (double)fmt->bias[c]);
+      return FLM_ERR_ARG;
+    }
+  }
+  return FLM_OK;
+}
+
+// the destination needs the alignment of its element type, no more (a slice of a larger buffer is fine)
+static int check_image_dst(const char* who, const void* dst, const flm_image_format* fmt) {
+  const uintptr_t esize = fmt->type == FLM_PIX_F32 ? 4 : fmt->type == FLM_PIX_U8 ? 1 : 2;
+  if (reinterpret_cast<uintptr_t>(dst) % esize) {
+    set_error("%s: dst is not aligned to its %d-byte element", who, (int)esize);
+    return FLM_ERR_ARG;
+  }
+  return FLM_OK;
+}
+
+size_t flm_image_format_bytes(const flm_image_format* fmt, int n, int h, int w) {
+  if (check_image_format("flm_image_format_bytes", fmt) != FLM_OK) return 0;
+  if (n < 1 || h < 1 || w < 1) {
+    set_error("flm_image_format_bytes: n, h, w must be >= 1 (got %d, %d, %d)", n, h, w);
+    return 0;
+  }
+  const size_t esize = fmt->type == FLM_PIX_F32 ? 4 : fmt->type == FLM_PIX_U8 ? 1 : 2;
+  return (size_t)n * (size_t)h * (size_t)w * 3 * esize;
+}
+
+int flm_warp_affine_fmt(flm_stream_t stream, const void* src, int src_is_u8, int n, int hs, int ws, const float* m,
+                        void* dst, int hd, int wd, const flm_image_format* fmt) {
+  if (!src || !m || !dst) {
+    set_error("flm_warp_affine_fmt: null argument");
+    return FLM_ERR_ARG;
+  }
+  if (const int rc = check_image_format("flm_warp_affine_fmt", fmt)) return rc;
+  if (const int rc = check_image_dst("flm_warp_affine_fmt", dst, fmt)) return rc;
+  return launch_warp_fmt(static_cast<hipStream_t>(stream), src, src_is_u8, n, hs, ws, m, dst, hd, wd, fmt);
+}
+
+int flm_warp_affine_frames_fmt(flm_stream_t stream, const uint8_t* frames, size_t frame_stride, int nframes, int fh,
+                               int fw, const int32_t* frame_idx, const int32_t* boxes, const float* m, int k, void* dst,
+                               int hd, int wd, int samples, const flm_image_format* fmt) {
+  if (!frames || !m || !dst) {  // frame_idx and boxes are optional
+    set_error("flm_warp_affine_frames_fmt: null argument");
+    return FLM_ERR_ARG;
+  }
+  if (const int rc = check_image_format("flm_warp_affine_frames_fmt", fmt)) return rc;
+  if (const int rc = check_image_dst("flm_warp_affine_frames_fmt", dst, fmt)) return rc;
+  return launch_warp_frames_fmt(static_cast<hipStream_t>(stream), frames, frame_stride, nframes, fh, fw, frame_idx, boxes,
+                                m, k, dst, hd, wd, samples, fmt);
 }
 
 }  // extern "C"

@@ -256,6 +256,12 @@ int launch_landmarks_to_frame(hipStream_t s, const double* lm, const int32_t* bo
 int launch_warp_frames(hipStream_t s, const uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
                        const int32_t* frame_idx, const int32_t* boxes, const float* m, int k, float* dst, int hd,
                        int wd, int samples);
+// the two warps with the output format in the epilogue (flm_warp_fmt.hip); the format has been checked by the caller
+int launch_warp_fmt(hipStream_t s, const void* src, int src_is_u8, int n, int hs, int ws, const float* m, void* dst, int hd,
+                    int wd, const flm_image_format* fmt);
+int launch_warp_frames_fmt(hipStream_t s, const uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
+                           const int32_t* frame_idx, const int32_t* boxes, const float* m, int k, void* dst, int hd,
+                           int wd, int samples, const flm_image_format* fmt);
 
 // Bijective XCD-aware remap of a 1-D grid: blocks that the dispatcher deals to the same XCD
 // (b % 8) receive consecutive logical ids, so neighbours in logical order share an L2.

@@ -130,6 +130,17 @@ def _weights_on_device(weights, n, c, dev):
     return w
 
 
+def _aligned_format(aligned_format, numpy_io):
+    """The `aligned_format` argument of align / align_frames, checked before any device work."""
+    if aligned_format is None:
+        return
+    if not isinstance(aligned_format, alignment.AlignedFormat):
+        raise ValueError("aligned_format must be an alignment.AlignedFormat or None (got %r)" % (aligned_format,))
+    if numpy_io and aligned_format.numpy_dtype is None:
+        raise ValueError("numpy has no %s: pass the crops as a CUDA tensor to get aligned faces of that type"
+                         % aligned_format.dtype)
+
+
 def predict(crops, model, n_points=4, thresh=0.0, to_input_space=False, return_stats=False):
     """Batched landmarks: crops [N,H,W,3] (numpy or CUDA tensor; uint8 BGR or float32
     preprocessed) -> float64 [N,C,2] (x,y).
@@ -171,7 +182,8 @@ def predict(crops, model, n_points=4, thresh=0.0, to_input_space=False, return_s
     return lm.cpu().numpy() if was_np else lm
 
 
-def align(crops, model=None, landmarks=None, template=None, out_size=None, n_points=4, thresh=0.0, weights=None):
+def align(crops, model=None, landmarks=None, template=None, out_size=None, n_points=4, thresh=0.0, weights=None,
+          aligned_format=None):
     """Align face crops by the similarity transform that maps their landmarks onto a template.
 
     crops [N,H,W,3] uint8/float32; `landmarks` float64 [N,C,2] in output-grid pixels (predicted
@@ -184,10 +196,16 @@ def align(crops, model=None, landmarks=None, template=None, out_size=None, n_poi
     model's own per-landmark score: the forward runs in its "landmark_stats" mode and the fit reads coordinates and
     scores from that record tensor in place, no launch in between; or a float64 [N,C] array / tensor (weight <= 0 or
     NaN: the landmark is left out).  With weights the call returns a fourth value, the [N,C] weights it used.
+
+    `aligned_format`: an `alignment.AlignedFormat` -- the aligned crops leave the warp in that layout, type, channel
+    order and normalisation (`AlignedFormat.matcher()`: float16 [N,3,h,w], RGB, in [-1,1]) instead of float32
+    [N,h,w,3]; every other returned value is what the call returns without it.  numpy callers get numpy arrays
+    (float32, float16, uint8; bfloat16 needs tensors: ValueError).
     """
     import torch
     _fit_weights(weights, landmarks is not None)
     was_np = not isinstance(crops, torch.Tensor)
+    _aligned_format(aligned_format, was_np)
     dev = _lib.require_gpu()
     xd = torch.from_numpy(np.ascontiguousarray(crops)).to(dev) if was_np else crops
     if landmarks is None:
@@ -212,11 +230,11 @@ def align(crops, model=None, landmarks=None, template=None, out_size=None, n_poi
     if model is not None:
         sc = (model.input_width / model.output_width, model.input_height / model.output_height)
     if weights is not None:
-        aligned, m = alignment.align_device(xd, lm, tmd, oh, ow, sc, weights=wd)
+        aligned, m = alignment.align_device(xd, lm, tmd, oh, ow, sc, weights=wd, fmt=aligned_format)
         if was_np:
             return aligned.cpu().numpy(), m.cpu().numpy(), lm.cpu().numpy(), wd.cpu().numpy()
         return aligned, m, lm, wd
-    aligned, m = alignment.align_device(xd, lm, tmd, oh, ow, sc)
+    aligned, m = alignment.align_device(xd, lm, tmd, oh, ow, sc, fmt=aligned_format)
     if was_np:
         return aligned.cpu().numpy(), m.cpu().numpy(), lm.cpu().numpy()
     return aligned, m, lm
@@ -343,7 +361,7 @@ _TEMPLATES = {}   # (landmarks, out_h, out_w, device) -> canonical template on t
 
 
 def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 112), n_points=4, thresh=0.0,
-                 frame_index=None, samples=1, weights=None):
+                 frame_index=None, samples=1, weights=None, aligned_format=None):
     """The multi-face stream end to end in FRAME coordinates: detector boxes of a group of frames -> aligned faces
     sampled from the frames themselves.
 
@@ -356,11 +374,14 @@ def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 1
     larger than out_size).  `weights`: None, "score" or a float64 [K,C] tensor, as `align` takes it -- "score" runs the
     forward in its "landmark_stats" mode, hands a contiguous copy of the record's xy columns (16 bytes per landmark) to
     flm_landmarks_to_frame and feeds the score column to the weighted fit in place; the call then returns the [K,C]
-    weights it used as a fifth value.
+    weights it used as a fifth value.  `aligned_format`: an `alignment.AlignedFormat` for the aligned faces, written by
+    the warp itself -- `AlignedFormat.matcher()` gives float16 [K,3,oh,ow], RGB, in [-1,1], what a face-embedding network
+    reads -- instead of float32 [K,oh,ow,3]; the other returned values do not depend on it.
     Returns CUDA tensors (aligned float32 [K,oh,ow,3], M float32 [K,2,3] frame px -> aligned px, landmarks float64
     [K,C,2] in frame px with (-1,-1) for rejected points, squared boxes int32 [K,4]); K == 0 launches nothing."""
     import torch
     _fit_weights(weights, False)
+    _aligned_format(aligned_format, False)
     if isinstance(frames, (list, tuple)):
         if not len(frames) or any(not isinstance(f, torch.Tensor) or f.dim() != 3 or f.dtype != torch.uint8
                                   or tuple(f.shape) != tuple(frames[0].shape) for f in frames):
@@ -388,7 +409,8 @@ def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 1
                                                       frame_index=slots, return_device=True)
     k = int(crops.shape[0])
     if k == 0:
-        empty = (torch.empty((0, oh, ow, 3), dtype=torch.float32, device=dev),
+        empty = (torch.empty((0, oh, ow, 3), dtype=torch.float32, device=dev) if aligned_format is None else
+                 torch.empty(aligned_format.shape(0, oh, ow), dtype=aligned_format.torch_dtype, device=dev),
                  torch.empty((0, 2, 3), dtype=torch.float32, device=dev),
                  torch.empty((0, c, 2), dtype=torch.float64, device=dev), boxes_dev)
         return empty if weights is None else empty + (torch.empty((0, c), dtype=torch.float64, device=dev),)
@@ -414,7 +436,7 @@ def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 1
     lm = alignment.landmarks_to_frame_device(lm, boxes_dev, (model.output_height, model.output_width), (fh, fw))
     m = alignment.similarity_device(lm, tmd, weights=wd)
     aligned = alignment.warp_frames_device(frames, m, oh, ow, frame_index_dev=idx_dev, boxes_dev=boxes_dev,
-                                           samples=samples)
+                                           samples=samples, fmt=aligned_format)
     if weights is not None:
         return aligned, m, lm, boxes_dev, wd
     return aligned, m, lm, boxes_dev

@@ -453,6 +453,61 @@ int flm_warp_affine_frames(flm_stream_t stream, const uint8_t* frames_dev, size_
                            const int32_t* boxes_dev /*[K,4] or NULL*/, const float* m_dev /*[K,2,3] frame px -> aligned px*/,
                            int k, float* dst_dev /*[K,hd,wd,3]*/, int hd, int wd, int samples);
 
+/* ---- aligned faces in the consumer's format ---------------------------------------------------------------
+ * flm_warp_affine and flm_warp_affine_frames write float32 [n,hd,wd,3], NHWC, in the source's channel order (BGR),
+ * values as sampled (0..255 for uint8 sources).  The two calls below are the same warps with the conversion to what
+ * reads the faces next -- an embedding network's planar, RGB, normalised float16 / bfloat16 input, or uint8 for
+ * storage -- in the store of the warp itself, so that the single resampling of the original pixels is also the single
+ * write of the result.  The format travels with the call: */
+enum flm_pixel_layout { FLM_LAYOUT_NHWC = 0, FLM_LAYOUT_NCHW = 1 };
+enum flm_pixel_type { FLM_PIX_F32 = 0, FLM_PIX_F16 = 1, FLM_PIX_BF16 = 2, FLM_PIX_U8 = 3 };
+typedef struct flm_image_format {
+  uint32_t struct_size;      /* as flm_forward_opts: lets the struct grow */
+  int32_t layout, type;      /* flm_pixel_layout, flm_pixel_type */
+  int32_t reverse_channels;  /* 0: output channel c = source channel c (BGR stays BGR); 1: source channel 2-c (RGB) */
+  float scale[3], bias[3];   /* indexed by OUTPUT channel */
+} flm_image_format;
+/* NHWC, F32, reverse_channels 0, scale 1, bias 0: with these the calls below store the bits of the calls above. */
+void flm_image_format_init(flm_image_format* fmt);
+/* Bytes of n faces of h x w in this format (n*h*w*3 elements of 4, 2, 2 or 1 bytes); 0 for a format the calls below
+ * reject (null, struct_size, unknown layout or type, reverse_channels, non-finite scale or bias) and for n, h or w
+ * below 1. */
+size_t flm_image_format_bytes(const flm_image_format* fmt, int n, int h, int w);
+/* The contract, for output pixel (row, col) of face f, output channel c, source channel s = reverse_channels ? 2-c : c:
+ *   v   the float32 value flm_warp_affine (flm_warp_affine_frames) writes for that pixel and channel s: the same
+ *       operations in the same order, the same bits -- for samples = 2 | 4 including the float32 sum of the samples
+ *       and the multiply by 1/(s*s).  A face those calls fill with zeros (a ring slot outside the ring, an empty
+ *       clipped box) has v = 0, which goes through the next steps like any other value.
+ *   t = v * scale[c]      float32 multiply, rounded
+ *   u = t + bias[c]       float32 add, rounded: two operations, two roundings, never a fused multiply-add
+ *   stored value:
+ *     FLM_PIX_F32   u
+ *     FLM_PIX_F16   u rounded to IEEE binary16, to nearest, ties to even; subnormals are gradual, overflow gives +-inf
+ *     FLM_PIX_BF16  u rounded to bfloat16, to nearest, ties to even (on the float32 bits b:
+ *                   (b + 0x7fff + ((b >> 16) & 1)) >> 16); a NaN stays a NaN
+ *     FLM_PIX_U8    rintf(u) (ties to even) clamped to [0, 255]; a NaN u stores 0
+ *   at element  FLM_LAYOUT_NHWC  ((f*hd + row)*wd + col)*3 + c          dense [n,hd,wd,3]
+ *               FLM_LAYOUT_NCHW  (((f*3 + c)*hd + row)*wd + col         dense [n,3,hd,wd]
+ * dst_dev needs the alignment of its element type and no more: it may be a slice of a larger buffer.  The kernels
+ * choose 16-byte stores from the actual address of every run they write and fall back to element stores elsewhere;
+ * no byte outside the n faces is written.
+ * Errors, all found before anything is launched: a null src / frames / m / dst or fmt, an unknown layout or type, a
+ * reverse_channels outside {0, 1}, a non-finite scale or bias, a dst that is not aligned to its element, or (frames
+ * call) `samples` outside {1, 2, 4} -> FLM_ERR_ARG; a struct_size smaller than this library's -> FLM_ERR_ARG with
+ * "struct_size" in the message.  FLM_ERR_SHAPE, the limit named in flm_last_error(), unless
+ *   flm_warp_affine_fmt         1 <= n <= 65535, hs, ws >= 1, hs*ws*3*4 < 2^31, hd, wd >= 1, hd*wd*3*4 < 2^31
+ *   flm_warp_affine_frames_fmt  1 <= k <= 65535, nframes >= 1, fh >= 1, fw >= 2, fh*fw*3 < 2^31,
+ *                               frame_stride >= fh*fw*3, hd, wd >= 1, hd*wd*3*4 < 2^31
+ * -- the limits of the float32 calls; the aligned-size limit counts float32 bytes whatever the type. */
+int flm_warp_affine_fmt(flm_stream_t stream, const void* src_dev /*[N,Hs,Ws,3]*/, int src_is_u8, int n, int hs, int ws,
+                        const float* m_dev /*[N,2,3] src->dst*/, void* dst_dev, int hd, int wd,
+                        const flm_image_format* fmt);
+int flm_warp_affine_frames_fmt(flm_stream_t stream, const uint8_t* frames_dev, size_t frame_stride, int nframes, int fh,
+                               int fw, const int32_t* frame_idx_dev /*[K] or NULL = frame 0*/,
+                               const int32_t* boxes_dev /*[K,4] or NULL*/,
+                               const float* m_dev /*[K,2,3] frame px -> aligned px*/, int k, void* dst_dev, int hd,
+                               int wd, int samples, const flm_image_format* fmt);
+
 #ifdef __cplusplus
 }
 #endif
