@@ -22,6 +22,8 @@ ABI_VERSION = 2
 SWEEP_MAX_MODES = 16  # FLM_SWEEP_MAX_MODES
 LAYOUT_NHWC, LAYOUT_NCHW = 0, 1                      # flm_pixel_layout
 PIX_F32, PIX_F16, PIX_BF16, PIX_U8 = 0, 1, 2, 3      # flm_pixel_type
+FRAME_BGR24, FRAME_NV12 = 0, 1                       # flm_frame_pixel
+YUV_BT601_LIMITED, YUV_BT709_LIMITED = 0, 1          # flm_yuv_matrix
 
 EXPORTS = [
     "flm_abi_version", "flm_last_error",
@@ -38,6 +40,8 @@ EXPORTS = [
     "flm_similarity_from_landmarks", "flm_similarity_from_landmarks_scaled", "flm_warp_affine", "flm_crop_resize", "flm_crop_resize_frames",
     "flm_landmarks_to_frame", "flm_warp_affine_frames",
     "flm_image_format_init", "flm_image_format_bytes", "flm_warp_affine_fmt", "flm_warp_affine_frames_fmt",
+    "flm_frame_format_init", "flm_frame_format_bytes", "flm_frames_to_bgr", "flm_crop_resize_frames_src",
+    "flm_warp_affine_frames_src",
 ]
 
 
@@ -77,6 +81,12 @@ class ImageFormat(C.Structure):
     """flm_image_format: layout, type, channel order, scale and bias of the aligned faces (include/flm.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("layout", C.c_int32), ("type", C.c_int32), ("reverse_channels", C.c_int32),
                 ("scale", C.c_float * 3), ("bias", C.c_float * 3)]
+
+
+class FrameFormat(C.Structure):
+    """flm_frame_format: how a ring slot holds its pixels -- dense BGR, or the NV12 surface of a decoder (include/flm.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("pixel", C.c_int32), ("matrix", C.c_int32), ("y_pitch", C.c_uint32),
+                ("uv_pitch", C.c_uint32), ("uv_offset", C.c_uint64)]
 
 
 class FcnParams(C.Structure):
@@ -191,6 +201,17 @@ def _declare(lib):
     lib.flm_warp_affine_frames_fmt.restype = i
     lib.flm_warp_affine_frames_fmt.argtypes = [vp, vp, C.c_size_t, i, i, i, vp, vp, vp, i, vp, i, i, i,
                                                C.POINTER(ImageFormat)]
+    lib.flm_frame_format_init.restype = None
+    lib.flm_frame_format_init.argtypes = [C.POINTER(FrameFormat)]
+    lib.flm_frame_format_bytes.restype = sz
+    lib.flm_frame_format_bytes.argtypes = [C.POINTER(FrameFormat), i, i]
+    lib.flm_frames_to_bgr.restype = i
+    lib.flm_frames_to_bgr.argtypes = [vp, vp, C.c_size_t, i, i, i, C.POINTER(FrameFormat), vp]
+    lib.flm_crop_resize_frames_src.restype = i
+    lib.flm_crop_resize_frames_src.argtypes = [vp, vp, C.c_size_t, i, i, i, vp, vp, i, vp, i, i, C.POINTER(FrameFormat)]
+    lib.flm_warp_affine_frames_src.restype = i
+    lib.flm_warp_affine_frames_src.argtypes = [vp, vp, C.c_size_t, i, i, i, vp, vp, vp, i, vp, i, i, i,
+                                               C.POINTER(ImageFormat), C.POINTER(FrameFormat)]
 
 
 def load():

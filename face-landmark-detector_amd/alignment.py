@@ -148,6 +148,105 @@ class AlignedFormat:
         return "AlignedFormat(layout=%r, dtype=%r, channels=%r, scale=%r, bias=%r)" % self.key()
 
 
+class FrameFormat:
+    """How a ring slot holds its pixels (flm_frame_format, include/flm.h): what the frame-reading calls take as
+    `frame_format=` / `src=`.
+
+    FrameFormat.bgr()   the dense ring of today: one contiguous CUDA uint8 [F,H,W,3] tensor.
+    FrameFormat.nv12(height, width, matrix="bt601", uv_row=None)
+                        a decoder's NV12 surfaces: one contiguous CUDA uint8 [F,rows,pitch] tensor.  Luma is rows
+                        0..height-1 of a slot, the interleaved U,V rows start at row `uv_row` (default `height`), both
+                        planes use the tensor's pitch, and a slot is rows*pitch bytes.  `matrix`: "bt601" or "bt709",
+                        limited range (what the decoder tags; 1080p streams are BT.709).
+    The kernels convert a tap with the integer arithmetic the header states and then compute what the BGR calls compute:
+    the results have the bits of those calls on `prediction.frames_to_bgr_device(frames, frame_format)`."""
+    _MATRICES = {"bt601": _lib.YUV_BT601_LIMITED, "bt709": _lib.YUV_BT709_LIMITED}
+
+    def __init__(self, pixel="bgr", height=None, width=None, matrix="bt601", uv_row=None):
+        if pixel not in ("bgr", "nv12"):
+            raise ValueError("pixel must be \"bgr\" or \"nv12\" (got %r)" % (pixel,))
+        if not isinstance(matrix, str) or matrix.lower() not in self._MATRICES:
+            raise ValueError("matrix must be \"bt601\" or \"bt709\" (got %r)" % (matrix,))
+        self.pixel = pixel
+        self.matrix = matrix.lower()
+        self.height = self.width = self.uv_row = None
+        if pixel == "nv12":
+            height, width = int(height), int(width)
+            if height < 2 or width < 2 or height % 2 or width % 2:
+                raise ValueError("NV12 frames have even sizes of 2 or more (got %dx%d)" % (height, width))
+            uv_row = height if uv_row is None else int(uv_row)
+            if uv_row < height:
+                raise ValueError("uv_row=%d lies inside the %d luma rows" % (uv_row, height))
+            self.height, self.width, self.uv_row = height, width, uv_row
+
+    @classmethod
+    def bgr(cls):
+        return cls("bgr")
+
+    @classmethod
+    def nv12(cls, height, width, matrix="bt601", uv_row=None):
+        return cls("nv12", height, width, matrix, uv_row)
+
+    def ring(self, frames):
+        """(slots, frame height, frame width, bytes between slots) of the ring tensor `frames`; ValueError for a tensor
+        that is not a ring of this format (a list of frames, the wrong rank or type, too few rows, too short a pitch)."""
+        import torch
+        if self.pixel == "bgr":
+            if (not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.shape[3] != 3
+                    or frames.dtype != torch.uint8 or not frames.is_cuda or not frames.is_contiguous()):
+                raise ValueError("frames must be a contiguous CUDA uint8 [F,H,W,3] tensor")
+            nf, fh, fw = [int(v) for v in frames.shape[:3]]
+            return nf, fh, fw, fh * fw * 3
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 3 or frames.dtype != torch.uint8:
+            raise ValueError("an NV12 ring is one uint8 [F,rows,pitch] tensor (got %s)" % (
+                "a %s" % type(frames).__name__ if not isinstance(frames, torch.Tensor) else
+                "%s %s" % (frames.dtype, list(frames.shape))))
+        nf, rows, pitch = [int(v) for v in frames.shape]
+        if pitch < self.width:
+            raise ValueError("the ring's pitch of %d bytes is shorter than the frame width %d" % (pitch, self.width))
+        if rows < self.uv_row + self.height // 2:
+            raise ValueError("a slot of %d rows does not hold %d U,V rows from row %d" % (rows, self.height // 2, self.uv_row))
+        if rows * pitch >= 2 ** 31:
+            raise ValueError("a slot of %d bytes is outside the kernels' reach (< 2^31)" % (rows * pitch))
+        if not frames.is_cuda or not frames.is_contiguous():
+            raise ValueError("frames must be a contiguous CUDA tensor")
+        return nf, self.height, self.width, rows * pitch
+
+    def struct(self, frames=None):
+        """The flm_frame_format of this format for the ring tensor `frames` (its pitch)."""
+        f = _lib.FrameFormat()
+        f.struct_size = _lib.C.sizeof(_lib.FrameFormat)
+        f.matrix = self._MATRICES[self.matrix]
+        if self.pixel == "bgr":
+            f.pixel = _lib.FRAME_BGR24
+            return f
+        pitch = int(frames.shape[2])
+        f.pixel = _lib.FRAME_NV12
+        f.y_pitch = pitch
+        f.uv_pitch = pitch
+        f.uv_offset = self.uv_row * pitch
+        return f
+
+    def key(self):
+        return (self.pixel, self.height, self.width, self.matrix, self.uv_row)
+
+    def __eq__(self, other):
+        return isinstance(other, FrameFormat) and self.key() == other.key()
+
+    def __hash__(self):
+        return hash(self.key())
+
+    def __repr__(self):
+        if self.pixel == "bgr":
+            return "FrameFormat.bgr()"
+        return "FrameFormat.nv12(%d, %d, matrix=%r, uv_row=%d)" % (self.height, self.width, self.matrix, self.uv_row)
+
+
+def _check_frame_format(src):
+    if not isinstance(src, FrameFormat):
+        raise ValueError("the frame format must be an alignment.FrameFormat or None (got %r)" % (src,))
+
+
 def _check_format(fmt):
     if not isinstance(fmt, AlignedFormat):
         raise ValueError("fmt must be an alignment.AlignedFormat or None (got %r)" % (fmt,))
@@ -298,18 +397,25 @@ def landmarks_to_frame_device(lm, boxes_dev, grid_hw, frame_hw, out=None):
     return out
 
 
-def warp_frames_device(frames, m, out_h, out_w, frame_index_dev=None, boxes_dev=None, samples=1, out=None, fmt=None):
+def warp_frames_device(frames, m, out_h, out_w, frame_index_dev=None, boxes_dev=None, samples=1, out=None, fmt=None,
+                       src=None):
     """frames: contiguous CUDA uint8 [F,H,W,3] ring; m: CUDA float32 [K,2,3] (FRAME pixels -> aligned pixels);
     frame_index_dev: CUDA int32 [K] ring slot of every face (default: slot 0); boxes_dev: CUDA int32 [K,4], faces whose
     clipped box is empty come back as zeros; samples: 1, 2 or 4 bilinear samples per axis and output pixel
     -> CUDA float32 [K,out_h,out_w,3] (flm_warp_affine_frames).
     `fmt`: an AlignedFormat -- the faces leave the warp in that layout, type, channel order and normalisation
     (flm_warp_affine_frames_fmt), e.g. AlignedFormat.matcher() -> CUDA float16 [K,3,out_h,out_w], RGB, in [-1,1];
-    `out`, when given, must then have the format's dtype and shape."""
+    `out`, when given, must then have the format's dtype and shape.
+    `src`: a FrameFormat -- how the ring holds its pixels (flm_warp_affine_frames_src).  FrameFormat.nv12(H, W, ...):
+    `frames` is the decoder's CUDA uint8 [F,rows,pitch] ring and every tap is converted to BGR on its way in; the result
+    has the bits of this call on the converted ring.  None: the BGR ring through the calls above, as ever."""
     import torch
     if fmt is not None:
         _check_format(fmt)
-    if (not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8
+    if src is not None:
+        _check_frame_format(src)
+        ring = src.ring(frames)
+    elif (not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8
             or not frames.is_cuda or not frames.is_contiguous()):
         raise ValueError("frames must be a contiguous CUDA uint8 [F,H,W,3] tensor")
     if not isinstance(m, torch.Tensor) or m.dtype != torch.float32 or m.dim() != 3 or tuple(m.shape[1:]) != (2, 3) or not m.is_cuda:
@@ -320,7 +426,11 @@ def warp_frames_device(frames, m, out_h, out_w, frame_index_dev=None, boxes_dev=
     if out_h < 1 or out_w < 1:
         raise ValueError("out_h and out_w must be positive")
     k = int(m.shape[0])
-    nf, fh, fw = [int(v) for v in frames.shape[:3]]
+    if src is not None:
+        nf, fh, fw, stride = ring
+    else:
+        nf, fh, fw = [int(v) for v in frames.shape[:3]]
+        stride = fh * fw * 3
     if frame_index_dev is not None and (not isinstance(frame_index_dev, torch.Tensor) or frame_index_dev.dtype != torch.int32
                                         or not frame_index_dev.is_cuda or not frame_index_dev.is_contiguous()
                                         or tuple(frame_index_dev.shape) != (k,)):
@@ -329,26 +439,25 @@ def warp_frames_device(frames, m, out_h, out_w, frame_index_dev=None, boxes_dev=
         _check_boxes(boxes_dev, k)
     if fmt is not None:
         out = _format_out(fmt, out, k, out_h, out_w, frames.device)
-        if k:
-            lib = _lib.load()
-            cf = fmt.struct()
-            _lib.check(lib.flm_warp_affine_frames_fmt(_lib.stream_ptr(), _lib.ptr(frames), fh * fw * 3, nf, fh, fw,
-                                                      None if frame_index_dev is None else _lib.ptr(frame_index_dev),
-                                                      None if boxes_dev is None else _lib.ptr(boxes_dev),
-                                                      _lib.ptr(m.contiguous()), k, _lib.ptr(out), out_h, out_w,
-                                                      int(samples), _lib.C.byref(cf)),
-                       "flm_warp_affine_frames_fmt")
-        return out
-    if out is None:
+    elif out is None:
         out = torch.empty((k, out_h, out_w, 3), dtype=torch.float32, device=frames.device)
     elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (k, out_h, out_w, 3)
           or not out.is_cuda or not out.is_contiguous()):
         raise ValueError("out must be a contiguous CUDA float32 [%d,%d,%d,3] tensor" % (k, out_h, out_w))
-    if k:
-        lib = _lib.load()
-        _lib.check(lib.flm_warp_affine_frames(_lib.stream_ptr(), _lib.ptr(frames), fh * fw * 3, nf, fh, fw,
-                                              None if frame_index_dev is None else _lib.ptr(frame_index_dev),
-                                              None if boxes_dev is None else _lib.ptr(boxes_dev),
-                                              _lib.ptr(m.contiguous()), k, _lib.ptr(out), out_h, out_w, int(samples)),
-                   "flm_warp_affine_frames")
+    if not k:
+        return out
+    lib = _lib.load()
+    cf = None if fmt is None else fmt.struct()
+    head = (_lib.stream_ptr(), _lib.ptr(frames), stride, nf, fh, fw,
+            None if frame_index_dev is None else _lib.ptr(frame_index_dev),
+            None if boxes_dev is None else _lib.ptr(boxes_dev), _lib.ptr(m.contiguous()), k, _lib.ptr(out), out_h, out_w,
+            int(samples))
+    if src is not None:     # one call for every ring and format: it dispatches on a NULL fmt and on BGR24 itself
+        cs = src.struct(frames)
+        _lib.check(lib.flm_warp_affine_frames_src(*head, None if cf is None else _lib.C.byref(cf), _lib.C.byref(cs)),
+                   "flm_warp_affine_frames_src")
+    elif fmt is not None:   # no frame format: the symbols of before
+        _lib.check(lib.flm_warp_affine_frames_fmt(*head, _lib.C.byref(cf)), "flm_warp_affine_frames_fmt")
+    else:
+        _lib.check(lib.flm_warp_affine_frames(*head), "flm_warp_affine_frames")
     return out

@@ -976,4 +976,108 @@ int flm_warp_affine_frames_fmt(flm_stream_t stream, const uint8_t* frames, size_
                                 m, k, dst, hd, wd, samples, fmt);
 }
 
+// ---- frame formats: the ring as the decoder hands it out (flm_frames_nv12.hip) -------------------------------
+
+void flm_frame_format_init(flm_frame_format* src) {
+  if (!src) return;
+  src->struct_size = (uint32_t)sizeof(flm_frame_format);
+  src->pixel = FLM_FRAME_BGR24;
+  src->matrix = FLM_YUV_BT601_LIMITED;
+  src->y_pitch = 0;
+  src->uv_pitch = 0;
+  src->uv_offset = 0;
+}
+
+// FLM_OK, FLM_ERR_ARG (null, struct_size, unknown pixel or matrix) or FLM_ERR_SHAPE (a BGR24 format that is not the
+// dense ring); the sizes of an NV12 format are checked against the frame by the launchers.
+static int check_frame_format(const char* who, const flm_frame_format* src) {
+  if (!src) {
+    set_error("%s: null frame format", who);
+    return FLM_ERR_ARG;
+  }
+  if (src->struct_size < sizeof(flm_frame_format)) {
+    set_error("%s: flm_frame_format struct_size %u is smaller than this library's %zu (initialise with "
+              "flm_frame_format_init)", who, src->struct_size, sizeof(flm_frame_format));
+    return FLM_ERR_ARG;
+  }
+  if (src->pixel != FLM_FRAME_BGR24 && src->pixel != FLM_FRAME_NV12) {
+    set_error("%s: unknown frame pixel format %d", who, src->pixel);
+    return FLM_ERR_ARG;
+  }
+  if (src->matrix != FLM_YUV_BT601_LIMITED && src->matrix != FLM_YUV_BT709_LIMITED) {
+    set_error("%s: unknown YUV matrix %d", who, src->matrix);
+    return FLM_ERR_ARG;
+  }
+  if (src->pixel == FLM_FRAME_BGR24 && (src->y_pitch || src->uv_pitch || src->uv_offset)) {
+    set_error("%s: a BGR24 ring is dense: y_pitch, uv_pitch and uv_offset must be 0 (got %u, %u, %llu)", who,
+              src->y_pitch, src->uv_pitch, (unsigned long long)src->uv_offset);
+    return FLM_ERR_SHAPE;
+  }
+  return FLM_OK;
+}
+
+size_t flm_frame_format_bytes(const flm_frame_format* src, int fh, int fw) {
+  if (check_frame_format("flm_frame_format_bytes", src) != FLM_OK) return 0;
+  if (src->pixel == FLM_FRAME_NV12) return nv12_format_bytes("flm_frame_format_bytes", src, fh, fw);
+  if (fh < 1 || fw < 1) {
+    set_error("flm_frame_format_bytes: frame %dx%d, needs fh, fw >= 1", fh, fw);
+    return 0;
+  }
+  return (size_t)fh * (size_t)fw * 3;
+}
+
+int flm_frames_to_bgr(flm_stream_t stream, const uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
+                      const flm_frame_format* src, uint8_t* out) {
+  if (!frames || !out) {
+    set_error("flm_frames_to_bgr: null argument");
+    return FLM_ERR_ARG;
+  }
+  if (const int rc = check_frame_format("flm_frames_to_bgr", src)) return rc;
+  if (src->pixel != FLM_FRAME_NV12) {
+    set_error("flm_frames_to_bgr: the source is BGR24 already (pixel must be FLM_FRAME_NV12)");
+    return FLM_ERR_ARG;
+  }
+  return launch_frames_to_bgr_nv12(static_cast<hipStream_t>(stream), frames, frame_stride, nframes, fh, fw, src, out);
+}
+
+int flm_crop_resize_frames_src(flm_stream_t stream, const uint8_t* frames, size_t frame_stride, int nframes, int fh,
+                               int fw, const int32_t* boxes, const int32_t* frame_idx, int k, uint8_t* out, int oh,
+                               int ow, const flm_frame_format* src) {
+  if (!frames || !boxes || !frame_idx || !out) {
+    set_error("flm_crop_resize_frames_src: null argument");
+    return FLM_ERR_ARG;
+  }
+  if (const int rc = check_frame_format("flm_crop_resize_frames_src", src)) return rc;
+  if (src->pixel == FLM_FRAME_BGR24)
+    return launch_crop_resize(static_cast<hipStream_t>(stream), frames, fh, fw, boxes, k, out, oh, ow, frame_idx,
+                              frame_stride, nframes);
+  return launch_crop_resize_nv12(static_cast<hipStream_t>(stream), frames, frame_stride, nframes, fh, fw, boxes,
+                                 frame_idx, k, out, oh, ow, src);
+}
+
+int flm_warp_affine_frames_src(flm_stream_t stream, const uint8_t* frames, size_t frame_stride, int nframes, int fh,
+                               int fw, const int32_t* frame_idx, const int32_t* boxes, const float* m, int k, void* dst,
+                               int hd, int wd, int samples, const flm_image_format* fmt, const flm_frame_format* src) {
+  if (!frames || !m || !dst) {  // frame_idx and boxes are optional
+    set_error("flm_warp_affine_frames_src: null argument");
+    return FLM_ERR_ARG;
+  }
+  if (const int rc = check_frame_format("flm_warp_affine_frames_src", src)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (src->pixel == FLM_FRAME_BGR24 && !fmt)  // flm_warp_affine_frames, its checks and no others
+    return launch_warp_frames(s, frames, frame_stride, nframes, fh, fw, frame_idx, boxes, m, k, static_cast<float*>(dst), hd,
+                              wd, samples);
+  flm_image_format plain;  // fmt NULL: float32 NHWC BGR, scale 1, bias 0
+  flm_image_format_init(&plain);
+  if (fmt) {
+    if (const int rc = check_image_format("flm_warp_affine_frames_src", fmt)) return rc;
+  }
+  if (const int rc = check_image_dst("flm_warp_affine_frames_src", dst, fmt ? fmt : &plain)) return rc;
+  if (src->pixel == FLM_FRAME_BGR24)
+    return launch_warp_frames_fmt(s, frames, frame_stride, nframes, fh, fw, frame_idx, boxes, m, k, dst, hd, wd, samples,
+                                  fmt);
+  return launch_warp_frames_nv12(s, frames, frame_stride, nframes, fh, fw, frame_idx, boxes, m, k, dst, hd, wd, samples,
+                                 fmt ? fmt : &plain, src);
+}
+
 }  // extern "C"

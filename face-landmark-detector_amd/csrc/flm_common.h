@@ -263,6 +263,19 @@ int launch_warp_frames_fmt(hipStream_t s, const uint8_t* frames, size_t frame_st
                            const int32_t* frame_idx, const int32_t* boxes, const float* m, int k, void* dst, int hd,
                            int wd, int samples, const flm_image_format* fmt);
 
+// NV12 frame slots as the source (flm_frames_nv12.hip); struct_size, pixel and matrix of `src` and the image format have
+// been checked by the caller
+int launch_frames_to_bgr_nv12(hipStream_t s, const uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
+                              const flm_frame_format* src, uint8_t* out);
+int launch_crop_resize_nv12(hipStream_t s, const uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
+                            const int32_t* boxes, const int32_t* frame_idx, int k, uint8_t* out, int oh, int ow,
+                            const flm_frame_format* src);
+int launch_warp_frames_nv12(hipStream_t s, const uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
+                            const int32_t* frame_idx, const int32_t* boxes, const float* m, int k, void* dst, int hd,
+                            int wd, int samples, const flm_image_format* fmt, const flm_frame_format* src);
+// 0 when the format's sizes are rejected (the reason is in flm_last_error())
+size_t nv12_format_bytes(const char* who, const flm_frame_format* src, int fh, int fw);
+
 // Bijective XCD-aware remap of a 1-D grid: blocks that the dispatcher deals to the same XCD
 // (b % 8) receive consecutive logical ids, so neighbours in logical order share an L2.
 __device__ __forceinline__ int xcd_remap(int b, int nblk) {

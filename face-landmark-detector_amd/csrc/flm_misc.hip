@@ -1,6 +1,7 @@
 // Bandwidth-bound helpers around the forward: standalone preprocess, similarity estimate,
 // alignment warp, crop front-end.
 #include "flm_common.h"
+#include "flm_resize_dev.h"
 
 
 namespace flm {
@@ -534,30 +535,7 @@ int launch_warp(hipStream_t s, const void* src, int src_is_u8, int n, int hs, in
 //                                                                                 fy: only the row indices clamp)
 //   exact 2x downscale in both axes (cw == 2*ow, ch == 2*oh): cv2 switches INTER_LINEAR to the area average
 //   out = (S[2y][2x] + S[2y][2x+1] + S[2y+1][2x] + S[2y+1][2x+1] + 2) >> 2.
-__device__ __forceinline__ void resize_coef(int d, double scale, int n_src, int& s0, int& s1, int& w0, int& w1) {
-  float f = (float)(((double)d + 0.5) * scale - 0.5);
-  int s = (int)floorf(f);
-  f -= (float)s;
-  if (s < 0) { s = 0; f = 0.f; }
-  if (s >= n_src - 1) { s = n_src - 1; f = 0.f; }
-  s0 = s;
-  s1 = min(s + 1, n_src - 1);
-  w0 = (int)rintf((1.f - f) * 2048.f);
-  w1 = (int)rintf(f * 2048.f);
-}
-
-// Along y OpenCV clamps only the ROW INDICES (clip(sy + k, 0, h)) and keeps the split weights of the unclamped
-// position: on the first / last output rows of an upscale both rows are the border row, weighted b0 and b1 separately
-// -- floor(b0*v >> 16) + floor(b1*v >> 16) is not always (2048*v) >> 16, so folding the weights there is off by one LSB.
-__device__ __forceinline__ void resize_coef_y(int d, double scale, int n_src, int& s0, int& s1, int& w0, int& w1) {
-  float f = (float)(((double)d + 0.5) * scale - 0.5);
-  const int s = (int)floorf(f);
-  f -= (float)s;
-  s0 = min(max(s, 0), n_src - 1);
-  s1 = min(max(s + 1, 0), n_src - 1);
-  w0 = (int)rintf((1.f - f) * 2048.f);
-  w1 = (int)rintf(f * 2048.f);
-}
+// resize_coef / resize_coef_y (flm_resize_dev.h) work those out per output column and row.
 
 // frame_idx (may be null): box k is cut from frame frame_idx[k] of `nframes` frames laid out `frame_stride` bytes apart
 // (a ring of stream frames in one allocation): the faces of a whole group of frames in one launch.

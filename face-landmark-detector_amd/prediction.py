@@ -302,7 +302,34 @@ def crop_faces_device(frame, boxes, out_h, out_w, out=None, boxes_dev=None):
     return out
 
 
-def crop_frames_device(frames, faces_per_frame, out_h, out_w, frame_index=None, return_device=False):
+def _frame_format(frame_format):
+    if frame_format is not None and not isinstance(frame_format, alignment.FrameFormat):
+        raise ValueError("frame_format must be an alignment.FrameFormat or None (got %r)" % (frame_format,))
+
+
+def frames_to_bgr_device(frames, frame_format, out=None):
+    """An NV12 ring as a dense BGR ring: frames CUDA uint8 [F,rows,pitch] in `frame_format`
+    (alignment.FrameFormat.nv12(...)) -> CUDA uint8 [F,H,W,3] (flm_frames_to_bgr: the integer conversion include/flm.h
+    states).  The frame-reading calls take the NV12 ring directly (`frame_format=`); this is the frame they compute
+    on, for a consumer that needs the BGR pixels themselves."""
+    import torch
+    _frame_format(frame_format)
+    if frame_format is None or frame_format.pixel != "nv12":
+        raise ValueError("frames_to_bgr_device converts an NV12 ring: frame_format must be FrameFormat.nv12(...)")
+    nf, fh, fw, stride = frame_format.ring(frames)
+    if out is None:
+        out = torch.empty((nf, fh, fw, 3), dtype=torch.uint8, device=frames.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (nf, fh, fw, 3)
+          or not out.is_cuda or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous CUDA uint8 [%d,%d,%d,3] tensor" % (nf, fh, fw))
+    if nf:
+        cs = frame_format.struct(frames)
+        _lib.check(_lib.load().flm_frames_to_bgr(_lib.stream_ptr(), _lib.ptr(frames), stride, nf, fh, fw, _lib.C.byref(cs),
+                                                 _lib.ptr(out)), "flm_frames_to_bgr")
+    return out
+
+
+def crop_frames_device(frames, faces_per_frame, out_h, out_w, frame_index=None, return_device=False, frame_format=None):
     """The faces of several frames as ONE batch: faces_per_frame: per frame a list of detector boxes (x0,y0,x1,y1) ->
     (CUDA uint8 [K_total,out_h,out_w,3], squared boxes per frame).  One upload of all boxes; no per-frame allocation,
     no concatenation: the shape a multi-face stream feeds the landmark model with (prediction.py:99-113 loops per face).
@@ -311,12 +338,17 @@ def crop_frames_device(frames, faces_per_frame, out_h, out_w, frame_index=None, 
     naming the ring slot of every entry of faces_per_frame (default 0, 1, ...): then all faces are cut in one launch.
     `return_device=True` also returns the CUDA int32 tensors of the squared boxes [K_total,4] and of every face's frame
     (ring slot, or position in the list) [K_total], views of the one upload: what the frame-space tail
-    (`align_frames`) reads."""
+    (`align_frames`) reads.
+    `frame_format`: an alignment.FrameFormat -- how the ring holds its pixels (flm_crop_resize_frames_src; then `frames`
+    must be the one ring tensor).  FrameFormat.nv12(H, W, ...): the decoder's CUDA uint8 [F,rows,pitch] ring, the crops
+    bit for bit those of the converted BGR ring.  None: as ever."""
     import torch
+    _frame_format(frame_format)
+    geom = None if frame_format is None else frame_format.ring(frames)   # (before anything is allocated or uploaded)
     boxes = [face_boxes(f) for f in faces_per_frame]
     total = sum(len(b) for b in boxes)
     ring = isinstance(frames, torch.Tensor)
-    if ring and (frames.dim() != 4 or frames.dtype != torch.uint8 or not frames.is_cuda or not frames.is_contiguous()
+    if geom is None and ring and (frames.dim() != 4 or frames.dtype != torch.uint8 or not frames.is_cuda or not frames.is_contiguous()
                  or frames.shape[3] != 3):
         raise ValueError("frames must be a list of CUDA uint8 [H,W,3] tensors or one contiguous CUDA uint8 [F,H,W,3] tensor")
     dev = frames.device if ring else (frames[0].device if len(frames) else _lib.require_gpu())
@@ -334,6 +366,15 @@ def crop_frames_device(frames, faces_per_frame, out_h, out_w, frame_index=None, 
         idx = np.concatenate([np.full(len(b), v, np.int32) for b, v in zip(boxes, slots) if len(b)])
         both = torch.from_numpy(np.concatenate([flat.reshape(-1), idx])).to(dev)   # one upload: boxes, then slots
         lib = _lib.load()
+        if geom is not None:
+            nf, fh, fw, stride = geom
+            cs = frame_format.struct(frames)
+            _lib.check(lib.flm_crop_resize_frames_src(_lib.stream_ptr(), _lib.ptr(frames), stride, nf, fh, fw,
+                                                      _lib.ptr(both), _lib.ptr(both[4 * total:]), total, _lib.ptr(out),
+                                                      out_h, out_w, _lib.C.byref(cs)), "flm_crop_resize_frames_src")
+            if return_device:
+                return out, boxes, both[:4 * total].view(total, 4), both[4 * total:]
+            return out, boxes
         fh, fw = int(frames.shape[1]), int(frames.shape[2])
         _lib.check(lib.flm_crop_resize_frames(_lib.stream_ptr(), _lib.ptr(frames), fh * fw * 3, int(frames.shape[0]), fh, fw,
                                               _lib.ptr(both), _lib.ptr(both[4 * total:]), total, _lib.ptr(out), out_h, out_w),
@@ -361,7 +402,7 @@ _TEMPLATES = {}   # (landmarks, out_h, out_w, device) -> canonical template on t
 
 
 def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 112), n_points=4, thresh=0.0,
-                 frame_index=None, samples=1, weights=None, aligned_format=None):
+                 frame_index=None, samples=1, weights=None, aligned_format=None, frame_format=None):
     """The multi-face stream end to end in FRAME coordinates: detector boxes of a group of frames -> aligned faces
     sampled from the frames themselves.
 
@@ -376,20 +417,27 @@ def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 1
     flm_landmarks_to_frame and feeds the score column to the weighted fit in place; the call then returns the [K,C]
     weights it used as a fifth value.  `aligned_format`: an `alignment.AlignedFormat` for the aligned faces, written by
     the warp itself -- `AlignedFormat.matcher()` gives float16 [K,3,oh,ow], RGB, in [-1,1], what a face-embedding network
-    reads -- instead of float32 [K,oh,ow,3]; the other returned values do not depend on it.
+    reads -- instead of float32 [K,oh,ow,3]; the other returned values do not depend on it.  `frame_format`: an
+    `alignment.FrameFormat` -- `FrameFormat.nv12(H, W, matrix="bt709")` takes the decoder's CUDA uint8 [F,rows,pitch]
+    ring as it is: the crop and the warp convert their taps, nothing between them changes, and all returned tensors
+    equal those of the call on `frames_to_bgr_device(frames, frame_format)`.
     Returns CUDA tensors (aligned float32 [K,oh,ow,3], M float32 [K,2,3] frame px -> aligned px, landmarks float64
     [K,C,2] in frame px with (-1,-1) for rejected points, squared boxes int32 [K,4]); K == 0 launches nothing."""
     import torch
     _fit_weights(weights, False)
     _aligned_format(aligned_format, False)
-    if isinstance(frames, (list, tuple)):
-        if not len(frames) or any(not isinstance(f, torch.Tensor) or f.dim() != 3 or f.dtype != torch.uint8
-                                  or tuple(f.shape) != tuple(frames[0].shape) for f in frames):
-            raise ValueError("frames must be a non-empty list of same-size uint8 [H,W,3] tensors")
-        frames = torch.stack(list(frames), 0)
-    if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.dtype != torch.uint8 or frames.shape[3] != 3:
-        raise ValueError("frames must be one uint8 [F,H,W,3] tensor or a list of uint8 [H,W,3] tensors")
-    nf, fh, fw = [int(v) for v in frames.shape[:3]]
+    _frame_format(frame_format)
+    if frame_format is not None:
+        nf, fh, fw, _ = frame_format.ring(frames)
+    else:
+        if isinstance(frames, (list, tuple)):
+            if not len(frames) or any(not isinstance(f, torch.Tensor) or f.dim() != 3 or f.dtype != torch.uint8
+                                      or tuple(f.shape) != tuple(frames[0].shape) for f in frames):
+                raise ValueError("frames must be a non-empty list of same-size uint8 [H,W,3] tensors")
+            frames = torch.stack(list(frames), 0)
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.dtype != torch.uint8 or frames.shape[3] != 3:
+            raise ValueError("frames must be one uint8 [F,H,W,3] tensor or a list of uint8 [H,W,3] tensors")
+        nf, fh, fw = [int(v) for v in frames.shape[:3]]
     if fw < 2 or fh < 1 or fh * fw * 3 >= 2 ** 31:
         raise ValueError("frames of %dx%d are outside the warp's reach (width >= 2, H*W*3 < 2^31)" % (fh, fw))
     slots = list(range(len(faces_per_frame))) if frame_index is None else [int(v) for v in frame_index]
@@ -406,7 +454,8 @@ def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 1
     dev = frames.device
     c = int(model.n_classes)
     crops, _, boxes_dev, idx_dev = crop_frames_device(frames, faces_per_frame, model.input_height, model.input_width,
-                                                      frame_index=slots, return_device=True)
+                                                      frame_index=slots, return_device=True,
+                                                      frame_format=frame_format)
     k = int(crops.shape[0])
     if k == 0:
         empty = (torch.empty((0, oh, ow, 3), dtype=torch.float32, device=dev) if aligned_format is None else
@@ -436,7 +485,7 @@ def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 1
     lm = alignment.landmarks_to_frame_device(lm, boxes_dev, (model.output_height, model.output_width), (fh, fw))
     m = alignment.similarity_device(lm, tmd, weights=wd)
     aligned = alignment.warp_frames_device(frames, m, oh, ow, frame_index_dev=idx_dev, boxes_dev=boxes_dev,
-                                           samples=samples, fmt=aligned_format)
+                                           samples=samples, fmt=aligned_format, src=frame_format)
     if weights is not None:
         return aligned, m, lm, boxes_dev, wd
     return aligned, m, lm, boxes_dev

@@ -508,6 +508,71 @@ int flm_warp_affine_frames_fmt(flm_stream_t stream, const uint8_t* frames_dev, s
                                const float* m_dev /*[K,2,3] frame px -> aligned px*/, int k, void* dst_dev, int hd,
                                int wd, int samples, const flm_image_format* fmt);
 
+/* ---- the decoder's surface as the ring: NV12 frame slots ------------------------------------------------------
+ * Video decoders hand out NV12: an 8-bit luma plane and an interleaved half-resolution U,V plane, rows `pitch` bytes
+ * apart, the U,V plane at an aligned row offset.  The calls below read such slots directly, so that the one resampling
+ * of the original pixels starts from the decoder's bytes and no BGR copy of a whole frame is made.  Their contract: THE
+ * BITS ARE THOSE OF THE BGR CALL ON THE FRAME THAT THE INTEGER CONVERSION BELOW PRODUCES.
+ *
+ * For pixel (x, y) of an fh x fw slot at byte address s (all arithmetic int32, >> an arithmetic shift):
+ *   Y = s[y*y_pitch + x]
+ *   U = s[uv_offset + (y>>1)*uv_pitch + (x & ~1)];  V = the byte after U
+ *       (chroma is replicated over its 2x2 block, not interpolated)
+ *   yy = max(Y - 16, 0) * CY;   u = U - 128;   v = V - 128
+ *   B = clamp((yy + CUB*u         + (1<<19)) >> 20, 0, 255)
+ *   G = clamp((yy + CVG*v + CUG*u + (1<<19)) >> 20, 0, 255)
+ *   R = clamp((yy + CVR*v         + (1<<19)) >> 20, 0, 255)
+ * with (CY, CUB, CUG, CVG, CVR) =
+ *   FLM_YUV_BT601_LIMITED  (1220542, 2116026, -409993, -852492, 1673527): 1.164 / 2.018 / -0.391 / -0.813 / 1.596 x 2^20,
+ *                          the published fixed-point form of OpenCV's COLOR_YUV2BGR_NV12 (parity with a cv2 binary is
+ *                          unpinned, as for the resize)
+ *   FLM_YUV_BT709_LIMITED  (1220945, 2215014, -223607, -558796, 1879825): round(exact coefficient x 2^20) with
+ *                          Kr = 0.2126, Kb = 0.0722 -- what 1080p decoders tag
+ * Over all 2^24 (Y,U,V) the accumulators stay within +-573,636,921 < 2^31; Y=16, U=V=128 gives 0 and Y=235 gives 255. */
+enum flm_frame_pixel { FLM_FRAME_BGR24 = 0, FLM_FRAME_NV12 = 1 };
+enum flm_yuv_matrix { FLM_YUV_BT601_LIMITED = 0, FLM_YUV_BT709_LIMITED = 1 };
+typedef struct flm_frame_format {
+  uint32_t struct_size; /* as flm_image_format */
+  int32_t pixel, matrix; /* flm_frame_pixel, flm_yuv_matrix (the matrix is not used by FLM_FRAME_BGR24) */
+  uint32_t y_pitch;     /* bytes between luma rows, 0 = fw */
+  uint32_t uv_pitch;    /* bytes between U,V rows, 0 = y_pitch */
+  uint64_t uv_offset;   /* slot start -> first U,V row, 0 = y_pitch*fh */
+} flm_frame_format;
+/* FLM_FRAME_BGR24, everything else 0: the dense uint8 BGR ring of flm_crop_resize_frames. */
+void flm_frame_format_init(flm_frame_format* src);
+/* Bytes of a slot that the kernels may read: fh*fw*3 for BGR24; for NV12 uv_offset + (fh/2 - 1)*uv_pitch + fw with the
+ * defaults resolved (the last U,V row ends after its fw bytes, not after its pitch).  No kernel reads a byte outside
+ * [slot, slot + this).  0 for a format or size the calls below reject. */
+size_t flm_frame_format_bytes(const flm_frame_format* src, int fh, int fw);
+/* flm_frames_to_bgr: slots 0..nframes-1 of an NV12 ring -> out_dev uint8 BGR [nframes,fh,fw,3], dense: B,G,R of the
+ *   conversion above.  The path an NV12 caller has without the two calls below.  (A BGR24 `src` is rejected with
+ *   FLM_ERR_ARG: there is nothing to convert.)
+ * flm_crop_resize_frames_src: flm_crop_resize_frames with the ring in the format `src`.
+ * flm_warp_affine_frames_src: flm_warp_affine_frames_fmt with the ring in the format `src`; fmt NULL = float32 NHWC
+ *   BGR, scale 1, bias 0, the bits of flm_warp_affine_frames.
+ * FLM_FRAME_BGR24: y_pitch, uv_pitch and uv_offset must be 0; the calls are the existing ones, with their limits and
+ *   their bits.
+ * FLM_FRAME_NV12: bit for bit what flm_crop_resize_frames / flm_warp_affine_frames_fmt give on the converted frame --
+ *   samples 1 | 2 | 4, every layout, type, channel order, scale and bias, and the zero fill for a slot outside the
+ *   ring and for an empty clipped box included.
+ * Errors, all found before anything is launched: a null pointer (frames, boxes, frame_idx, out; frames, m, dst; src),
+ *   an unknown pixel or matrix, a struct_size smaller than this library's, and what flm_warp_affine_frames_fmt answers
+ *   with FLM_ERR_ARG -> FLM_ERR_ARG.  FLM_ERR_SHAPE, the limit named in flm_last_error(), unless (NV12)
+ *   fh and fw even and >= 2, y_pitch >= fw, uv_pitch >= fw, uv_offset >= y_pitch*fh, slot bytes < 2^31,
+ *   frame_stride >= flm_frame_format_bytes, nframes >= 1, 1 <= k <= 65535, oh, ow >= 1 and oh*ow*3 < 2^31 (crop),
+ *   hd, wd >= 1 and hd*wd*3*4 < 2^31 (warp); a BGR24 format with a non-zero pitch or offset is FLM_ERR_SHAPE too. */
+int flm_frames_to_bgr(flm_stream_t stream, const uint8_t* frames_dev, size_t frame_stride, int nframes, int fh, int fw,
+                      const flm_frame_format* src, uint8_t* out_dev /*[nframes,fh,fw,3]*/);
+int flm_crop_resize_frames_src(flm_stream_t stream, const uint8_t* frames_dev, size_t frame_stride, int nframes, int fh,
+                               int fw, const int32_t* boxes_dev /*[K,4]*/, const int32_t* frame_idx_dev /*[K]*/, int k,
+                               uint8_t* out_dev, int out_h, int out_w, const flm_frame_format* src);
+int flm_warp_affine_frames_src(flm_stream_t stream, const uint8_t* frames_dev, size_t frame_stride, int nframes, int fh,
+                               int fw, const int32_t* frame_idx_dev /*[K] or NULL = frame 0*/,
+                               const int32_t* boxes_dev /*[K,4] or NULL*/,
+                               const float* m_dev /*[K,2,3] frame px -> aligned px*/, int k, void* dst_dev, int hd,
+                               int wd, int samples, const flm_image_format* fmt /* NULL = float32 NHWC BGR */,
+                               const flm_frame_format* src);
+
 #ifdef __cplusplus
 }
 #endif
