@@ -31,6 +31,7 @@ EXPORTS = [
     "flm_fcn32_packed_bytes", "flm_fcn32_pack", "flm_fcn32_workspace_bytes", "flm_fcn32_forward",
     "flm_fcn_packed_bytes", "flm_fcn_pack", "flm_fcn_workspace_bytes", "flm_fcn_forward",
     "flm_forward_opts_init", "flm_fcn_workspace_bytes_opts", "flm_fcn_forward_opts", "flm_fcn8_workspace_offset_opts",
+    "flm_fcn_workspace_offset_opts", "flm_fcn_encoder_layers", "flm_fcn_encoder_layer",
     "flm_fcn8_workspace_bytes", "flm_fcn8_forward", "flm_fcn8_workspace_offset", "flm_fcn8_run_layer",
     "flm_set_tuning", "flm_get_tuning", "flm_debug_query", "flm_profile_enable", "flm_profile_filter", "flm_profile_reset", "flm_profile_read", "flm_profile_disable",
     "flm_preprocess",
@@ -75,6 +76,15 @@ class ForwardOpts(C.Structure):
 
     def key(self):
         return (self.landmark_candidates, self.candidate_sub_phases, self.candidate_cap_div)
+
+
+class EncLayerInfo(C.Structure):
+    """flm_enc_layer_info: one encoder layer of an architecture and its grids for an h x w input (include/flm.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("kind", "cin", "cout", "kernel", "stride", "activation", "pool", "src", "res",
+                                         "in_h", "in_w", "out_h", "out_w")]
+
+
+ENC_FIRST3, ENC_CONV3, ENC_MB_CONV1, ENC_MB_DW, ENC_MB_PW, ENC_RN_CONV1, ENC_MAXPOOL3, ENC_CONV = range(8)  # flm_enc_kind
 
 
 class ImageFormat(C.Structure):
@@ -141,6 +151,12 @@ def _declare(lib):
     lib.flm_fcn8_workspace_offset_opts.argtypes = [C.c_char_p] + [i] * 8 + [C.POINTER(ForwardOpts)]
     lib.flm_fcn8_workspace_offset.restype = C.c_int64
     lib.flm_fcn8_workspace_offset.argtypes = [C.c_char_p] + [i] * 8
+    lib.flm_fcn_workspace_offset_opts.restype = C.c_int64
+    lib.flm_fcn_workspace_offset_opts.argtypes = [i, C.c_char_p] + [i] * 8 + [C.POINTER(ForwardOpts)]
+    lib.flm_fcn_encoder_layers.restype = i
+    lib.flm_fcn_encoder_layers.argtypes = [i]
+    lib.flm_fcn_encoder_layer.restype = i
+    lib.flm_fcn_encoder_layer.argtypes = [i, i, i, i, C.POINTER(EncLayerInfo)]
     lib.flm_fcn8_run_layer.restype = i
     lib.flm_fcn8_run_layer.argtypes = [vp, vp, C.c_char_p, vp, vp, i, i, i, i, i]
     lib.flm_profile_filter.restype = i

@@ -457,14 +457,27 @@ void flm_forward_opts_init(flm_forward_opts* opts) {
 
 int64_t flm_fcn8_workspace_offset(const char* name, int n, int h, int w, int n_classes, int dtype, int out_mode,
                                   int decode_mode, int n_points) {
-  return flm_fcn8_workspace_offset_opts(name, n, h, w, n_classes, dtype, out_mode, decode_mode, n_points, nullptr);
+  return flm_fcn_workspace_offset_opts(FLM_ARCH_FCN8, name, n, h, w, n_classes, dtype, out_mode, decode_mode, n_points,
+                                       nullptr);
 }
 int64_t flm_fcn8_workspace_offset_opts(const char* name, int n, int h, int w, int n_classes, int dtype, int out_mode,
                                        int decode_mode, int n_points, const flm_forward_opts* opts) {
-  if (!name || check_fcn8_shape(n, h, w, n_classes, dtype)) return -1;
-  const Fcn8Ws W = fcn8_ws_layout(n, h, w, n_classes, dtype, out_mode, decode_mode, n_points, FLM_ARCH_FCN8, opts);
+  return flm_fcn_workspace_offset_opts(FLM_ARCH_FCN8, name, n, h, w, n_classes, dtype, out_mode, decode_mode, n_points,
+                                       opts);
+}
+int64_t flm_fcn_workspace_offset_opts(int arch, const char* name, int n, int h, int w, int n_classes, int dtype,
+                                      int out_mode, int decode_mode, int n_points, const flm_forward_opts* opts) {
+  const ArchSpec A = arch_spec(arch);
+  if (!name || !A.valid || check_fcn8_shape(n, h, w, n_classes, dtype)) return -1;
+  const Fcn8Ws W = fcn8_ws_layout(n, h, w, n_classes, dtype, out_mode, decode_mode, n_points, arch, opts);
   if (W.total == 0) return -1;
   if (name[0] == 'f' && name[1] >= '1' && name[1] <= '5' && name[2] == 0) return (int64_t)W.f[name[1] - '1'];
+  if (!strncmp(name, "act", 3) && name[3] >= '0' && name[3] <= '9') {  // "act<i>": encoder layer i of ArchSpec::enc
+    int i = 0;
+    const char* c = name + 3;
+    for (; *c >= '0' && *c <= '9' && i < kMaxEnc; ++c) i = 10 * i + (*c - '0');
+    return (*c == 0 && i < A.n_enc && !(name[3] == '0' && name[4] != 0)) ? (int64_t)W.act[i] : -1;
+  }
   if (!strcmp(name, "cand_sub")) return W.sub == SIZE_MAX ? -1 : (int64_t)W.sub;
   if (!strcmp(name, "cand_tau")) return W.tau == SIZE_MAX ? -1 : (int64_t)W.tau;
   if (!strcmp(name, "cand_keys")) return W.cand == SIZE_MAX ? -1 : (int64_t)W.cand;
@@ -473,10 +486,64 @@ int64_t flm_fcn8_workspace_offset_opts(const char* name, int n, int h, int w, in
   if (!strcmp(name, "fc6")) return (int64_t)W.fc6;
   if (!strcmp(name, "fc7")) return (int64_t)W.fc7;
   if (!strcmp(name, "score5")) return (int64_t)W.score5;
-  if (!strcmp(name, "fuse4")) return (int64_t)W.fuse4;
-  if (!strcmp(name, "seg_feats")) return (int64_t)W.seg;
+  if (!strcmp(name, "fuse4")) return A.fcn32 ? -1 : (int64_t)W.fuse4;  // (the fcn_32 graphs have no skip stages)
+  if (!strcmp(name, "seg_feats")) return A.fcn32 ? -1 : (int64_t)W.seg;
   if (!strcmp(name, "probs")) return W.probs == SIZE_MAX ? -1 : (int64_t)W.probs;
   return -1;
+}
+
+static_assert((int)FLM_ENC_FIRST3 == (int)ENC_FIRST3 && (int)FLM_ENC_CONV3 == (int)ENC_CONV3 &&
+                  (int)FLM_ENC_MB_CONV1 == (int)ENC_MB_CONV1 && (int)FLM_ENC_MB_DW == (int)ENC_MB_DW &&
+                  (int)FLM_ENC_MB_PW == (int)ENC_MB_PW && (int)FLM_ENC_RN_CONV1 == (int)ENC_RN_CONV1 &&
+                  (int)FLM_ENC_MAXPOOL3 == (int)ENC_MAXPOOL3 && (int)FLM_ENC_CONV == (int)ENC_CONV,
+              "flm_enc_kind mirrors EncKind");
+
+int flm_fcn_encoder_layers(int arch) {
+  const ArchSpec A = arch_spec(arch);
+  if (!A.valid) {
+    set_error("flm_fcn_encoder_layers: unknown architecture %d", arch);
+    return -1;
+  }
+  return A.n_enc;
+}
+
+int flm_fcn_encoder_layer(int arch, int index, int h, int w, flm_enc_layer_info* info) {
+  if (!info) {
+    set_error("flm_fcn_encoder_layer: null argument");
+    return FLM_ERR_ARG;
+  }
+  const ArchSpec A = arch_spec(arch);
+  if (!A.valid) {
+    set_error("flm_fcn_encoder_layer: unknown architecture %d", arch);
+    return FLM_ERR_ARG;
+  }
+  if (index < 0 || index >= A.n_enc) {
+    set_error("flm_fcn_encoder_layer: architecture %d has layers 0..%d (got %d)", arch, A.n_enc - 1, index);
+    return FLM_ERR_ARG;
+  }
+  if (h <= 0 || w <= 0 || (h % 32) || (w % 32) || h > (1 << 15) || w > (1 << 15)) {
+    set_error("flm_fcn_encoder_layer: H and W must be multiples of 32 up to 2^15 (got h=%d w=%d)", h, w);
+    return FLM_ERR_SHAPE;
+  }
+  int hs[kMaxEnc], wsz[kMaxEnc];
+  enc_dims(A, h, w, hs, wsz);
+  const EncLayer& e = A.enc[index];
+  const int src = e.src >= 0 ? e.src : index - 1;
+  info->kind = e.kind;
+  info->cin = e.cin;
+  info->cout = e.cout;
+  info->kernel = e.k;
+  info->stride = e.stride;
+  const bool relu6 = e.kind == ENC_MB_CONV1 || e.kind == ENC_MB_DW || e.kind == ENC_MB_PW;
+  info->activation = e.kind == ENC_MAXPOOL3 ? 0 : (relu6 ? 2 : (e.kind == ENC_CONV ? (e.relu ? 1 : 0) : 1));
+  info->pool = e.pool;
+  info->src = src;
+  info->res = e.res;
+  info->in_h = src >= 0 ? hs[src] : h;
+  info->in_w = src >= 0 ? wsz[src] : w;
+  info->out_h = hs[index];
+  info->out_w = wsz[index];
+  return FLM_OK;
 }
 
 static int forward_impl(flm_stream_t stream, const void* packed_dev, const void* x_dev, int in_format, int n, int h,

@@ -57,6 +57,7 @@ class Fcn8Model:
         # holds (graphs.CapturedPipeline owns its workspace outright, see new_workspace)
         self._ws = collections.OrderedDict()
         self._ws_cap = 4
+        self._level_layer = {}   # "f1".."f5" -> index of the encoder layer (intermediate)
         # per-model defaults of the per-call options that change the workspace layout (include/flm.h: flm_forward_opts)
         self.forward_opts = {}
         # the kernels address activations with 32-bit byte offsets: the largest tensor (f1, 64 channels at
@@ -233,30 +234,67 @@ class Fcn8Model:
                    "flm_fcn_forward_opts")
         return out_tensor
 
+    def encoder_layer_names(self):
+        """The encoder's layers by their Keras names, in network order: index i is the layer whose output is
+        `intermediate("act%d" % i)` (ResNet50: its parameter-free max-pool, unnamed in the reference, is "max_pooling2d")."""
+        names = [name for name, _bn in self._enc_layers]
+        n = _lib.load().flm_fcn_encoder_layers(self._arch)
+        if n == len(names) + 1:
+            names.insert(1, "max_pooling2d")
+        assert n == len(names), (n, len(names))
+        return tuple(names)
+
+    def encoder_layer(self, index):
+        """flm_enc_layer_info of encoder layer `index` at this model's input size (include/flm.h)."""
+        info = _lib.EncLayerInfo()
+        _lib.check(_lib.load().flm_fcn_encoder_layer(self._arch, int(index), self.input_height, self.input_width,
+                                                     C.byref(info)), "flm_fcn_encoder_layer")
+        return info
+
     def intermediate(self, name, n, out="probs", n_points=0, opts=None, workspace=None):
-        """View of a named workspace tensor of the last forward with the same (n, out, n_points, opts) (tests)."""
+        """View of a named workspace tensor of the last forward with the same (n, out, n_points, opts) (tests): "act<i>"
+        (encoder layer i), "f1".."f5", "fc6", "fc7", "score5", "fuse4", "seg_feats", "probs" (include/flm.h:
+        flm_fcn_workspace_offset_opts).  KeyError for a name the layout does not hold."""
         import torch
         lib = _lib.load()
         om = _OUT[out]
         dmode, npts = decode_mode_of(n_points) if om in _DECODING else (0, 0)
         fo = self._opts(opts)
-        off = lib.flm_fcn8_workspace_offset_opts(name.encode(), n, self.input_height, self.input_width, self.n_classes,
-                                                 self._dt, om, dmode, npts, C.byref(fo))
+
+        def offset(nm):
+            return lib.flm_fcn_workspace_offset_opts(self._arch, nm.encode(), n, self.input_height, self.input_width,
+                                                     self.n_classes, self._dt, om, dmode, npts, C.byref(fo))
+        off = offset(name)
         if off < 0:
             raise KeyError(name)
         h, w = self.input_height, self.input_width
         bf = self.dtype == "bf16"
         cp = (72 if bf else 68) if self.n_classes == 68 else 16 * ((self.n_classes + 15) // 16)
-        shapes = {"f1": (h // 2, w // 2, 64), "f2": (h // 4, w // 4, 128), "f3": (h // 8, w // 8, 256),
-                  "f4": (h // 16, w // 16, 256), "f5": (h // 32, w // 32, 256),
-                  "fc6": (h // 32, w // 32, 4096), "fc7": (h // 32, w // 32, 4096),
-                  "score5": (h // 32, w // 32, cp), "fuse4": (h // 16, w // 16, cp),
-                  "seg_feats": (h // 8, w // 8, cp),
-                  "probs": (self.output_height * self.output_width, self.n_classes)}
-        shp = (n,) + shapes[name]
+        operand = True   # stored in the operand type: encoder layers, fc6, fc7
+        if name.startswith("act") or (len(name) == 2 and name[0] == "f"):
+            # f1..f5 are encoder layers: the one whose region this is (every layer has a region of its own); which one
+            # does not depend on the call's shape, so it is looked up once per model
+            if name.startswith("act"):
+                idx = int(name[3:])
+            else:
+                if name not in self._level_layer:
+                    self._level_layer[name] = next((i for i in range(lib.flm_fcn_encoder_layers(self._arch))
+                                                    if offset("act%d" % i) == off), None)
+                idx = self._level_layer[name]
+                if idx is None:
+                    raise KeyError(name)
+            info = self.encoder_layer(idx)
+            shp = (info.out_h, info.out_w, info.cout)
+        elif name in ("fc6", "fc7"):
+            shp = (h // 32, w // 32, 4096)
+        else:
+            operand = False
+            shp = {"score5": (h // 32, w // 32, cp), "fuse4": (h // 16, w // 16, cp), "seg_feats": (h // 8, w // 8, cp),
+                   "probs": (self.output_height * self.output_width, self.n_classes)}[name]
+        shp = (n,) + shp
         ws = workspace if workspace is not None else self._workspace(n, om, dmode, npts, fo)
         cnt = int(np.prod(shp))
-        if bf and name in ("f1", "f2", "f3", "f4", "f5", "fc6", "fc7"):   # stored in the operand type
+        if bf and operand:
             return ws[off:off + 2 * cnt].view(torch.bfloat16).view(shp).float()
         return ws[off:off + 4 * cnt].view(torch.float32).view(shp)
 
@@ -289,9 +327,6 @@ class Fcn32Model(Fcn8Model):
     _grid_growth = 32
     _fcn32 = True
 
-    def intermediate(self, name, n, out="probs", n_points=0, opts=None, workspace=None):
-        raise NotImplementedError("workspace views are exposed for fcn_8 only")
-
 
 _VGG_LAYERS = tuple(("block%d_conv%d" % (b, c), False)
                     for b, k in ((1, 2), (2, 2), (3, 3), (4, 3), (5, 3)) for c in range(1, k + 1))
@@ -305,9 +340,6 @@ class Fcn8VggModel(Fcn8Model):
     model_name = "fcn_8_vgg"
     _arch = _lib.ARCH_FCN8_VGG
     _enc_layers = _VGG_LAYERS
-
-    def intermediate(self, name, n, out="probs", n_points=0, opts=None, workspace=None):
-        raise NotImplementedError("workspace views are exposed for the vanilla fcn_8 only")
 
 
 class Fcn32VggModel(Fcn8VggModel):
@@ -344,9 +376,6 @@ class Fcn8MobilenetModel(Fcn8Model):
     def __init__(self, n_classes, input_height=224, input_width=224, channels=3, dtype="f32"):
         super().__init__(n_classes, input_height, input_width, channels, dtype)
 
-    def intermediate(self, name, n, out="probs", n_points=0, opts=None, workspace=None):
-        raise NotImplementedError("workspace views are exposed for the vanilla fcn_8 only")
-
 
 class Fcn32MobilenetModel(Fcn8MobilenetModel):
     model_name = "fcn_32_mobilenet"
@@ -378,9 +407,6 @@ class Fcn8Resnet50Model(Fcn8Model):
     model_name = "fcn_8_resnet50"
     _arch = _lib.ARCH_FCN8_RESNET50
     _enc_layers = _RESNET_LAYERS
-
-    def intermediate(self, name, n, out="probs", n_points=0, opts=None, workspace=None):
-        raise NotImplementedError("workspace views are exposed for the vanilla fcn_8 only")
 
 
 class Fcn32Resnet50Model(Fcn8Resnet50Model):

@@ -206,6 +206,46 @@ int flm_fcn_forward_opts(flm_stream_t stream, int arch, const void* packed_dev, 
 int64_t flm_fcn8_workspace_offset_opts(const char* name, int n, int h, int w, int n_classes, int dtype,
                                        int out_mode, int decode_mode, int n_points, const flm_forward_opts* opts);
 
+/* ---- where every layer's output lies, for every architecture (tests compare layer by layer) ------------------------
+ * flm_fcn_workspace_offset_opts: byte offset inside the workspace of a named intermediate of `arch`, or -1 (null or
+ * unknown name, unknown architecture, a shape or option struct the workspace query refuses, a tensor this call's layout
+ * does not hold).  Names: "f1".."f5", "fc6", "fc7", "score5", "fuse4", "seg_feats" (both -1 for the fcn_32 graphs, which
+ * have no skip stages), "probs", "cand_sub" / "cand_tau" / "cand_keys" / "cand_cnt" / "cand_cap" (the last returns the
+ * list capacity, not an offset), and "act<i>" (decimal, no leading zeros): the output of encoder layer i -- every layer
+ * has a region of its own, nothing is reused, so all of them survive the forward.  Encoder outputs, fc6 and fc7 are
+ * [n, out_h, out_w, cout] in the operand type (float32 | bfloat16); score5 / fuse4 / seg_feats are float32 with the
+ * padded class count as channel stride.  The flm_fcn8_workspace_offset* calls are this one with FLM_ARCH_FCN8.
+ *
+ * flm_fcn_encoder_layers: the number of encoder layers of `arch` (5 | 13 | 27 | 54: ResNet50's parameter-free max-pool
+ * is layer 1 of its 54), or -1.  flm_fcn_encoder_layer: layer `index` for an h x w input (multiples of 32), in network
+ * order -- the order of flm_fcn_params::enc with the max-pool inserted.  Read-only; launches nothing. */
+enum flm_enc_kind {
+  FLM_ENC_FIRST3 = 0,   /* 3-channel Conv2D 3x3 'same' (+ BatchNorm) + ReLU (+ MaxPool 2x2) */
+  FLM_ENC_CONV3 = 1,    /* Conv2D 3x3 'same' (+ BatchNorm) + ReLU (+ MaxPool 2x2) */
+  FLM_ENC_MB_CONV1 = 2, /* MobileNet conv1: pad 1, 3x3 stride 2, BatchNorm, ReLU6 */
+  FLM_ENC_MB_DW = 3,    /* MobileNet depthwise: pad 1, 3x3 stride 1 | 2, BatchNorm, ReLU6 */
+  FLM_ENC_MB_PW = 4,    /* MobileNet pointwise 1x1, BatchNorm, ReLU6 */
+  FLM_ENC_RN_CONV1 = 5, /* ResNet50 conv1: pad 3, 7x7 stride 2, bias, BatchNorm, ReLU */
+  FLM_ENC_MAXPOOL3 = 6, /* MaxPooling2D 3x3 stride 2 'valid' */
+  FLM_ENC_CONV = 7      /* Conv2D k x k (pad k/2, stride 1 | 2), bias, BatchNorm (+ residual) (+ ReLU) */
+};
+typedef struct flm_enc_layer_info {
+  int32_t kind;          /* enum flm_enc_kind */
+  int32_t cin, cout;
+  int32_t kernel;        /* k of the k x k window */
+  int32_t stride;
+  int32_t activation;    /* 0 none, 1 ReLU, 2 ReLU6 */
+  int32_t pool;          /* 1: a 2x2 max-pool closes the layer (its output grid is the pooled one) */
+  int32_t src;           /* index of the layer whose output this one reads; -1: the network input */
+  int32_t res;           /* index of the layer whose output is added before the activation; -1: none */
+  int32_t in_h, in_w;    /* grid of the input */
+  int32_t out_h, out_w;  /* grid of the stored output */
+} flm_enc_layer_info;
+int64_t flm_fcn_workspace_offset_opts(int arch, const char* name, int n, int h, int w, int n_classes, int dtype,
+                                      int out_mode, int decode_mode, int n_points, const flm_forward_opts* opts);
+int flm_fcn_encoder_layers(int arch);
+int flm_fcn_encoder_layer(int arch, int index, int h, int w, flm_enc_layer_info* info);
+
 /* One named Conv2D layer of the model in isolation ("enc2".."enc5" with BN+ReLU+pool fused,
  * "fc6", "fc7", "score5", "score4", "score3"), exactly the launch the forward makes for it except that no
  * split-K scratch is passed (the layer never splits K here).  For tests and developer tools that run or time one layer.

@@ -38,6 +38,10 @@ the yardstick for what float32 accumulation can move (tests/test_oracle_fcn_bf16
 
 With rounding=False every function performs fcn_ref's float64 operations in fcn_ref's order: bit-identical.
 
+The VGG, MobileNet and ResNet50 encoders are stated ONCE, as chains of Steps (ENCODER_CHAINS, written from the reference's
+network files): run_chain evaluates a chain free running, encoder_layer_ref one step from given inputs -- what the
+teacher-forced gate of tests/test_gpu_encoder_layers.py holds each device layer to.
+
 A third arithmetic, the exact-fp32 configuration's (FLM_F32; layer_f32_ref, or fp32=True): the same packed form of every
 conv -- raw float32 kernel (pack_conv_kernel<float> / pack_convt_kernel<float>), BatchNorm and bias as the float32-stored
 scale / shift of pack_affine_kernel applied to the accumulator (flm_igemm.hip igemm_kernel, flm_enc1.hip) -- with no
@@ -195,8 +199,9 @@ class Arith:
     bias as _fold's float32-stored scale / shift applied to the accumulator) with NO bf16 rounding of weights, inputs
     or outputs; `accum` is honoured (float64: the exact value of that arithmetic; float32: the yardstick)."""
 
-    def __init__(self, rounding=True, accum=F64, fp32=False):
+    def __init__(self, rounding=True, accum=F64, fp32=False, cache=None):
         assert accum in (torch.float64, torch.float32)
+        self.cache = cache                           # see _weight: large operands kept between calls, or None
         self.fp32 = bool(fp32)
         self.rounding = bool(rounding) and not self.fp32
         self.folded = self.rounding or self.fp32     # the packer's scale / shift form instead of fcn_ref's BatchNorm
@@ -234,11 +239,22 @@ def _fold(p, conv, bn):
     return s.astype(np.float32).astype(np.float64), sh.astype(np.float32).astype(np.float64)
 
 
-def _weight(kern, perm, rounded):
-    """A Keras kernel as the torch operand, rounded raw to bf16 where the packer rounds it (flm_pack.hip put())."""
+WEIGHT_CACHE_MIN = 1 << 24
+
+
+def _weight(kern, perm, rounded, cache=None):
+    """A Keras kernel as the torch operand, rounded raw to bf16 where the packer rounds it (flm_pack.hip put()).
+    `cache`: a dict the CALLER owns (Arith.cache); operands of kernels of at least WEIGHT_CACHE_MIN elements are then
+    built once per (array, rounded) -- the float64 fc6 operand of a 2048-channel f5 is 3 GB."""
     k = np.asarray(kern)
-    k = round_bf16(k) if rounded else k.astype(np.float64)
-    return torch.from_numpy(k).permute(*perm).contiguous()
+    key = (id(kern), rounded, tuple(perm))
+    if cache is not None and k.size >= WEIGHT_CACHE_MIN and key in cache and cache[key][0] is kern:
+        return cache[key][1]
+    w = round_bf16(k) if rounded else k.astype(np.float64)
+    w = torch.from_numpy(w).permute(*perm).contiguous()
+    if cache is not None and k.size >= WEIGHT_CACHE_MIN:
+        cache[key] = (kern, w)
+    return w
 
 
 def _act(y, relu):
@@ -270,7 +286,7 @@ def _conv_block(A: Arith, x, p, conv, bn=None, pad=0, stride=1, relu=0, pool=0, 
         if pool:
             y = F.max_pool2d(y, 2, 2)
         return y, y
-    w = _weight(kern, (2, 3, 0, 1) if dw else (3, 2, 0, 1), round_w and A.rounding)
+    w = _weight(kern, (2, 3, 0, 1) if dw else (3, 2, 0, 1), round_w and A.rounding, A.cache)
     xo = A.q(x) if round_x else x
     scale, shift = _fold(p, conv, bn)
     dt = A.accum
@@ -290,7 +306,7 @@ def _convt_block(A: Arith, x, p, name, stride):
     (flm_convt.hip / flm_tail_bf16.hip / flm_up3_wreg.hip; flm_pack.hip pack_convt_kernel<unsigned short>)."""
     if not A.folded:
         return fcn_ref._convT(x, p[name + "/kernel"], stride, F64)
-    w = _weight(p[name + "/kernel"], (3, 2, 0, 1), A.rounding)   # (fp32 configuration: unrounded operands)
+    w = _weight(p[name + "/kernel"], (3, 2, 0, 1), A.rounding, A.cache)   # (fp32 configuration: unrounded operands)
     return F.conv_transpose2d(A.q(x).to(A.accum), w.to(A.accum), None, stride=stride).to(F64)
 
 
@@ -306,49 +322,125 @@ def _vanilla_encoder(A, x, p):
     return levels
 
 
-def _vgg_encoder(A, x, p):
-    levels = []
-    first = True
+class Step:
+    """One layer of an encoder chain: `name` (the Keras layer name; its parameters are p[name + "/..."]), `inputs` (names
+    of the steps whose STORED outputs it reads, "x" = the preprocessed network input; a second input is the shortcut a
+    ResNet `2c` conv adds before its ReLU), and the evaluation: step(A, p, *inputs_nchw) -> (exact, stored) in the
+    arithmetic A.  op "conv": _conv_block with the keyword arguments `kw` (bn, pad, stride, relu, pool, round_w,
+    round_x); op "maxpool3": MaxPooling2D(3x3, stride 2, 'valid'), no parameters, exact in every arithmetic."""
+
+    def __init__(self, name, inputs, op="conv", depthwise=False, **kw):
+        self.name, self.inputs, self.op, self.depthwise, self.kw = name, tuple(inputs), op, depthwise, kw
+        self.stride = 2 if op == "maxpool3" else kw.get("stride", 1)
+        self.relu = 0 if op == "maxpool3" else kw.get("relu", 0)
+        self.pool = kw.get("pool", 0)
+
+    def __call__(self, A, p, *xs):
+        assert len(xs) == len(self.inputs), (self.name, len(xs))
+        if self.op == "maxpool3":
+            y = F.max_pool2d(xs[0], 3, 2)
+            return y, y
+        kw = dict(self.kw)
+        if self.depthwise:
+            kw["groups"] = p[self.name + "/depthwise_kernel"].shape[2]
+        return _conv_block(A, xs[0], p, self.name, res=xs[1] if len(xs) > 1 else None, **kw)
+
+
+def _vgg_chain():
+    """networks/vgg16.py:27-72 (pretrained=None): five blocks of 2, 2, 3, 3, 3 x Conv2D(3x3, 'same', relu), each closed
+    by MaxPooling2D(2x2, stride 2); the kernels fuse the pool into the block's last conv.  The first conv rounds its
+    input and its float32 filter to bf16 itself (flm_enc1.hip enc1_bf16_kernel)."""
+    steps, prev = [], "x"
     for b, k in ((1, 2), (2, 2), (3, 3), (4, 3), (5, 3)):
         for c in range(1, k + 1):
-            e, x = _conv_block(A, x, p, "block%d_conv%d" % (b, c), pad=1, relu=1, pool=int(c == k), round_x=first)
-            first = False
-        levels.append((e, x))
-    return levels
+            name = "block%d_conv%d" % (b, c)
+            steps.append(Step(name, (prev,), pad=1, relu=1, pool=int(c == k), round_x=(prev == "x")))
+            prev = name
+    return tuple(steps)
 
 
-def _mobilenet_encoder(A, x, p):
-    # conv1 and the depthwise convs multiply float32 filters (flm_mobile.hip); conv1 reads the float32 input
-    e, x = _conv_block(A, x, p, "conv1", bn="conv1_bn", pad=1, stride=2, relu=2, round_w=False)
-    levels = []
+def _mobilenet_chain():
+    """networks/mobilenet.py:59-114 (alpha 1): conv1 = ZeroPadding2D(1) + Conv2D(32, 3x3, stride 2, valid, no bias) + BN +
+    ReLU6 (:16-28); blocks 1..13 = ZeroPadding2D(1) + DepthwiseConv2D(3x3, stride s, valid, no bias) + BN + ReLU6, then
+    Conv2D(1x1, no bias) + BN + ReLU6 (:31-56); s = 2 at blocks 2, 4, 6, 12 (:82, 87, 92, 101).  conv1 and the
+    depthwise convs multiply float32 filters, and conv1 reads the float32 input (flm_mobile.hip)."""
+    steps = [Step("conv1", ("x",), bn="conv1_bn", pad=1, stride=2, relu=2, round_w=False)]
+    prev = "conv1"
     for i in range(1, 14):
-        s = 2 if i in (2, 4, 6, 12) else 1
-        c = p["conv_dw_%d/depthwise_kernel" % i].shape[2]
-        e, x = _conv_block(A, x, p, "conv_dw_%d" % i, bn="conv_dw_%d_bn" % i, pad=1, stride=s, relu=2, groups=c,
-                           round_w=False)
-        e, x = _conv_block(A, x, p, "conv_pw_%d" % i, bn="conv_pw_%d_bn" % i, relu=2)
-        if i in (1, 3, 5, 11, 13):
-            levels.append((e, x))
-    return levels
+        dw, pw = "conv_dw_%d" % i, "conv_pw_%d" % i
+        steps.append(Step(dw, (prev,), depthwise=True, bn=dw + "_bn", pad=1, stride=2 if i in (2, 4, 6, 12) else 1, relu=2,
+                          round_w=False))
+        steps.append(Step(pw, (dw,), bn=pw + "_bn", relu=2))
+        prev = pw
+    return tuple(steps)
 
 
-def _resnet50_encoder(A, x, p):
-    def cbn(x, conv, bn, k, stride, relu, res=None, round_w=True):
-        return _conv_block(A, x, p, conv, bn=bn, pad=k // 2, stride=stride, relu=int(relu), res=res, round_w=round_w)[1]
+def _resnet50_chain():
+    """networks/resnet50.py:122-182 (pretrained=None): ZeroPadding2D(3) + Conv2D(64, 7x7, stride 2) + BN + ReLU (:142-148),
+    MaxPooling2D(3x3, stride 2, valid) (:149), then stages 2..5 of 3, 4, 6, 3 bottleneck blocks (:151-172).  A stage's
+    block `a` is a conv_block (:73-119): 1x1 (stride s) + BN + ReLU, 3x3 'same' + BN + ReLU, 1x1 + BN, and the shortcut
+    1x1 (stride s) + BN of the block input, added before the last ReLU; s = 1 in stage 2 (:151), 2 from stage 3 on.  The
+    other blocks are identity_blocks (:32-70): the same three convs at stride 1, the block input itself added.  The
+    library evaluates a conv_block's shortcut before its main path.  conv1 multiplies a float32 filter by the float32
+    input (rn_conv1_kernel); the shortcut is read back from its stored map."""
+    def cbn(name, inputs, k, stride, relu, **kw):
+        return Step(name, inputs, bn=name.replace("res", "bn", 1), pad=k // 2, stride=stride, relu=int(relu), **kw)
 
-    x = cbn(x, "conv1", "bn_conv1", 7, 2, True, round_w=False)   # rn_conv1_kernel: float32 filter and input
-    levels = [(x, x)]
-    x = F.max_pool2d(x, 3, 2)                                    # maxpool3_kernel on bf16 values: exact
+    steps = [Step("conv1", ("x",), bn="bn_conv1", pad=3, stride=2, relu=1, round_w=False),
+             Step("max_pooling2d", ("conv1",), op="maxpool3")]
+    prev = "max_pooling2d"
     for stage, blocks in ((2, "abc"), (3, "abcd"), (4, "abcdef"), (5, "abc")):
         for b in blocks:
-            base, bn = "res%d%s_branch" % (stage, b), "bn%d%s_branch" % (stage, b)
+            base = "res%d%s_branch" % (stage, b)
             s = 2 if (b == "a" and stage > 2) else 1
-            shortcut = cbn(x, base + "1", bn + "1", 1, s, False) if b == "a" else x
-            y = cbn(x, base + "2a", bn + "2a", 1, s, True)
-            y = cbn(y, base + "2b", bn + "2b", 3, 1, True)
-            x = cbn(y, base + "2c", bn + "2c", 1, 1, True, res=shortcut)
-        levels.append((x, x))
+            shortcut = prev
+            if b == "a":
+                steps.append(cbn(base + "1", (prev,), 1, s, False))
+                shortcut = base + "1"
+            steps.append(cbn(base + "2a", (prev,), 1, s, True))
+            steps.append(cbn(base + "2b", (base + "2a",), 3, 1, True))
+            steps.append(cbn(base + "2c", (base + "2b", shortcut), 1, 1, True))
+            prev = base + "2c"
+    return tuple(steps)
+
+
+# The three registry encoders as explicit chains (the vanilla one: tests/bf16_gate.py CHAIN), and the steps whose outputs
+# are the levels f1..f5 the FCN head reads (ResNet50: f1 is its conv1; only f3..f5 are used).
+ENCODER_CHAINS = {"vgg": _vgg_chain(), "mobilenet": _mobilenet_chain(), "resnet50": _resnet50_chain()}
+ENCODER_LEVELS = {"vgg": ("block1_conv2", "block2_conv2", "block3_conv3", "block4_conv3", "block5_conv3"),
+                  "mobilenet": ("conv_pw_1", "conv_pw_3", "conv_pw_5", "conv_pw_11", "conv_pw_13"),
+                  "resnet50": ("conv1", "res2c_branch2c", "res3d_branch2c", "res4f_branch2c", "res5c_branch2c")}
+
+
+def run_chain(chain, A, x, p) -> dict:
+    """Free-running evaluation: every step reads the chain's own stored outputs.  {name: (exact, stored)}, NCHW."""
+    out = {"x": (x, x)}
+    for st in chain:
+        out[st.name] = st(A, p, *[out[i][1] for i in st.inputs])
+    return out
+
+
+def _chain_encoder(encoder):
+    def levels(A, x, p):
+        out = run_chain(ENCODER_CHAINS[encoder], A, x, p)
+        if encoder == "resnet50":   # (its levels have always been reported as stored)
+            return [(out[n][1], out[n][1]) for n in ENCODER_LEVELS[encoder]]
+        return [out[n] for n in ENCODER_LEVELS[encoder]]
     return levels
+
+
+_vgg_encoder, _mobilenet_encoder, _resnet50_encoder = (_chain_encoder(e) for e in ("vgg", "mobilenet", "resnet50"))
+
+
+def encoder_layer_ref(encoder: str, layer: str, inputs, p: dict, rounding=True, accum=F64, fp32=False):
+    """One step of ENCODER_CHAINS[encoder], given its INPUT (NHWC; a tuple (main, shortcut) for ResNet50's `2c` convs):
+    the sibling of layer_bf16_ref for the VGG, MobileNet and ResNet50 encoders, in the same three arithmetics (bf16
+    rounding points; fp32=True: the exact-fp32 folded form; accum=float32: the yardstick).  Returns (exact, stored),
+    NHWC float64.  The head and decoder on these encoders are layer_bf16_ref's (their widths come from `p`)."""
+    st = next(s for s in ENCODER_CHAINS[encoder] if s.name == layer)
+    xs = inputs if isinstance(inputs, tuple) else (inputs,)
+    e, s = st(Arith(rounding, accum, fp32), p, *[_nchw(x) for x in xs])
+    return _nhwc(e), _nhwc(s)
 
 
 _ENCODERS = {"vanilla": _vanilla_encoder, "vgg": _vgg_encoder, "mobilenet": _mobilenet_encoder,
@@ -384,7 +476,7 @@ def _seg(A, fuse4, f3, p):
     return o2 + o                                        # fcn.py:119
 
 
-def layer_bf16_ref(layer: str, inputs, p: dict, rounding=True, accum=F64, fp32=False):
+def layer_bf16_ref(layer: str, inputs, p: dict, rounding=True, accum=F64, fp32=False, cache=None):
     """One layer of the vanilla fcn_8 in the bf16 configuration, given its INPUT (NHWC arrays; a tuple for the
     two-input layers).  Returns (exact, stored), NHWC float64: the unrounded output and the value the layer
     stores (rounded to bf16 for f1..f5 / fc6 / fc7; the float32-stored layers return exact twice).
@@ -392,8 +484,9 @@ def layer_bf16_ref(layer: str, inputs, p: dict, rounding=True, accum=F64, fp32=F
       enc1: preprocessed float32 RGB input    enc2..enc5: f1..f4    fc6: f5    fc7: fc6    score5: fc7
       score4: f4    score3: f3    fuse4: (score5, f4)    seg_feats: (fuse4, f3)    logits: seg_feats
     Class columns beyond n_classes of score5 / fuse4 / seg_feats inputs are ignored (they hold zeros).
-    fp32=True: the same layer in the fp32 configuration's arithmetic (Arith); exact and stored are then equal."""
-    A = Arith(rounding, accum, fp32)
+    fp32=True: the same layer in the fp32 configuration's arithmetic (Arith); exact and stored are then equal.
+    cache: a dict of the caller's that keeps the float64 operands of large kernels between calls (_weight)."""
+    A = Arith(rounding, accum, fp32, cache)
     c = p["score5/kernel"].shape[3]
     if layer in ("enc1", "enc2", "enc3", "enc4", "enc5"):
         e, s = _conv_block(A, _nchw(inputs), p, layer, bn=layer, pad=1, relu=1, pool=1, round_x=(layer == "enc1"))

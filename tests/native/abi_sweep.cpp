@@ -60,7 +60,33 @@ int main() {
                         const int64_t off = flm_fcn8_workspace_offset_opts(nm, n, d[0], d[1], c, dt, om, dm, np, o);
                         CHECK(off >= -1 && (off < 0 || (size_t)off < b || !std::strcmp(nm, "cand_cap")));
                         if (!std::strcmp(nm, "cand_cap") && off >= 0) CHECK(off >= 64);
+                        // the architecture-generic query with FLM_ARCH_FCN8 is the same answer
+                        CHECK(off == flm_fcn_workspace_offset_opts(0, nm, n, d[0], d[1], c, dt, om, dm, np, o));
                       }
+                    if (n == 3) {  // every architecture: the named tensors and one region per encoder layer, in order
+                      const int layers = flm_fcn_encoder_layers(arch);
+                      CHECK(layers >= 5 && layers <= 64);
+                      for (const char* nm : names) {
+                        const int64_t off = flm_fcn_workspace_offset_opts(arch, nm, n, d[0], d[1], c, dt, om, dm, np, o);
+                        CHECK(off >= -1 && (off < 0 || (size_t)off < b || !std::strcmp(nm, "cand_cap")));
+                        if ((arch & 1) && (!std::strcmp(nm, "fuse4") || !std::strcmp(nm, "seg_feats"))) CHECK(off == -1);
+                        if (nm[0] == 'f' && (nm[1] == 'c' || nm[2] == 0)) CHECK(off >= 0);
+                      }
+                      int64_t prev = -1, f_seen = 0;
+                      char act[16];
+                      for (int i = 0; i < layers; ++i) {
+                        std::snprintf(act, sizeof(act), "act%d", i);
+                        const int64_t off = flm_fcn_workspace_offset_opts(arch, act, n, d[0], d[1], c, dt, om, dm, np, o);
+                        CHECK(off > prev && (size_t)off < b && off % 256 == 0);
+                        prev = off;
+                        for (const char* f : {"f1", "f2", "f3", "f4", "f5"})
+                          f_seen += off == flm_fcn_workspace_offset_opts(arch, f, n, d[0], d[1], c, dt, om, dm, np, o);
+                      }
+                      CHECK(f_seen == 5);  // f1..f5 are five of the layers
+                      CHECK(prev < flm_fcn_workspace_offset_opts(arch, "fc6", n, d[0], d[1], c, dt, om, dm, np, o));
+                      std::snprintf(act, sizeof(act), "act%d", layers);
+                      CHECK(flm_fcn_workspace_offset_opts(arch, act, n, d[0], d[1], c, dt, om, dm, np, o) == -1);
+                    }
                   }
                 }
       }
@@ -92,6 +118,37 @@ int main() {
   CHECK(flm_fcn_workspace_bytes_opts(0, 1, 256, 256, 68, 0, 2, 1, 4, &bad) == 0);
   flm_forward_opts_init(nullptr);  // tolerated
   CHECK(flm_fcn8_workspace_offset(nullptr, 1, 256, 256, 68, 0, 0, 0, 0) == -1);
+  // the two layer queries: null, unknown architecture, unknown name, shapes the forward refuses
+  CHECK(flm_fcn_workspace_offset_opts(0, nullptr, 1, 256, 256, 68, 0, 0, 0, 0, nullptr) == -1);
+  CHECK(flm_fcn_workspace_offset_opts(8, "f1", 1, 256, 256, 68, 0, 0, 0, 0, nullptr) == -1);
+  CHECK(flm_fcn_workspace_offset_opts(-1, "act0", 1, 256, 256, 68, 0, 0, 0, 0, nullptr) == -1);
+  CHECK(flm_fcn_workspace_offset_opts(6, "act0", 1, 256, 256, 68, 0, 0, 0, 0, nullptr) == 0);
+  for (const char* nm : {"act", "act-1", "act54", "act99999999999999999999", "act00", "act01", "act1x", "act 1", "ACT1", "f0", "f6", "f10", "fc8"})
+    CHECK(flm_fcn_workspace_offset_opts(6, nm, 1, 256, 256, 68, 0, 0, 0, 0, nullptr) == -1);
+  CHECK(flm_fcn_workspace_offset_opts(6, "act53", 1, 256, 256, 68, 0, 0, 0, 0, nullptr) > 0);
+  CHECK(flm_fcn_workspace_offset_opts(0, "act5", 1, 256, 256, 68, 0, 0, 0, 0, nullptr) == -1);
+  CHECK(flm_fcn_workspace_offset_opts(6, "act1", 1, 250, 256, 68, 0, 0, 0, 0, nullptr) == -1);
+  CHECK(flm_fcn_workspace_offset_opts(6, "act1", 0, 256, 256, 68, 0, 0, 0, 0, nullptr) == -1);
+  CHECK(flm_fcn_workspace_offset_opts(6, "act1", 1, 256, 256, 68, 2, 0, 0, 0, nullptr) == -1);
+  CHECK(flm_fcn_workspace_offset_opts(6, "act1", 1, 256, 256, 68, 0, 2, 1, 4, &bad) == -1);  // (an option struct the layout refuses)
+  CHECK(flm_fcn_encoder_layers(0) == 5 && flm_fcn_encoder_layers(3) == 13 && flm_fcn_encoder_layers(4) == 27 && flm_fcn_encoder_layers(7) == 54);
+  CHECK(flm_fcn_encoder_layers(8) == -1 && flm_fcn_encoder_layers(-1) == -1 && std::strstr(flm_last_error(), "unknown architecture"));
+  flm_enc_layer_info li;
+  CHECK(flm_fcn_encoder_layer(6, 0, 64, 96, nullptr) == FLM_ERR_ARG && flm_fcn_encoder_layer(8, 0, 64, 96, &li) == FLM_ERR_ARG);
+  CHECK(flm_fcn_encoder_layer(6, -1, 64, 96, &li) == FLM_ERR_ARG && flm_fcn_encoder_layer(6, 54, 64, 96, &li) == FLM_ERR_ARG);
+  CHECK(flm_fcn_encoder_layer(6, 0, 60, 96, &li) == FLM_ERR_SHAPE && flm_fcn_encoder_layer(6, 0, 64, 0, &li) == FLM_ERR_SHAPE);
+  CHECK(flm_fcn_encoder_layer(6, 0, 1 << 20, 96, &li) == FLM_ERR_SHAPE && flm_fcn_encoder_layer(6, 0, -32, 96, &li) == FLM_ERR_SHAPE);
+  for (int arch = 0; arch < 8; ++arch)
+    for (auto& d : hw)
+      for (int i = 0; i < flm_fcn_encoder_layers(arch); ++i) {
+        CHECK(flm_fcn_encoder_layer(arch, i, d[0], d[1], &li) == FLM_OK);
+        CHECK(li.kind >= FLM_ENC_FIRST3 && li.kind <= FLM_ENC_CONV && li.cin >= 3 && li.cout >= 32 && li.cout <= 2048);
+        CHECK((li.kernel == 1 || li.kernel == 3 || li.kernel == 7) && (li.stride == 1 || li.stride == 2));
+        CHECK(li.activation >= 0 && li.activation <= 2 && (li.pool == 0 || li.pool == 1));
+        CHECK(li.src >= -1 && li.src < i && (li.src == -1) == (i == 0) && li.res >= -1 && li.res < i);
+        CHECK(li.in_h >= 1 && li.in_w >= 1 && li.out_h >= 1 && li.out_w >= 1 && li.out_h <= li.in_h && li.out_w <= li.in_w);
+        if (i == flm_fcn_encoder_layers(arch) - 1) CHECK(li.out_h == d[0] / 32 && li.out_w == d[1] / 32);
+      }
   // null pointers and bad enums reach no kernel launch
   CHECK(flm_fcn_forward(nullptr, 0, nullptr, nullptr, 0, 1, 32, 32, 68, 0, 0, 0, 0, 0.f, nullptr, nullptr, 0) == FLM_ERR_ARG);
   CHECK(flm_fcn_forward_opts(nullptr, 0, nullptr, nullptr, 0, 1, 32, 32, 68, 0, 0, 0, 0, 0.f, nullptr, nullptr, 0, &bad) < 0);

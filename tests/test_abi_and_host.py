@@ -156,6 +156,62 @@ def test_null_arguments_are_rejected_not_dereferenced():
     assert lib.flm_warp_affine(None, None, 1, 1, 8, 8, None, None, 8, 8) == -1
 
 
+def test_layer_queries_reject_null_unknown_arch_and_unknown_name():
+    """flm_fcn_workspace_offset_opts / flm_fcn_encoder_layers / flm_fcn_encoder_layer: host arithmetic only.  The fcn8 calls
+    are the generic one with FLM_ARCH_FCN8; every encoder layer of every architecture has a region of its own; null, an
+    unknown architecture, an unknown or malformed name and a refused shape answer -1 / an error, never an offset."""
+    import ctypes as C
+    lib = _lib.load()
+    shape = (3, 64, 96, 68)
+    for dt in (_lib.FLM_F32, _lib.FLM_BF16):
+        tail = (dt, _lib.OUT_PROBS, 0, 0)
+        for name in (b"f1", b"f2", b"f3", b"f4", b"f5", b"fc6", b"fc7", b"score5", b"fuse4", b"seg_feats", b"probs", b"cand_keys"):
+            assert lib.flm_fcn_workspace_offset_opts(_lib.ARCH_FCN8, name, *shape, *tail, None) == \
+                lib.flm_fcn8_workspace_offset_opts(name, *shape, *tail, None) == lib.flm_fcn8_workspace_offset(name, *shape, *tail)
+        for arch, layers in ((0, 5), (1, 5), (2, 13), (3, 13), (4, 27), (5, 27), (6, 54), (7, 54)):
+            assert lib.flm_fcn_encoder_layers(arch) == layers
+            q = lambda name: lib.flm_fcn_workspace_offset_opts(arch, name, *shape, *tail, None)
+            offs = [q(b"act%d" % i) for i in range(layers)]
+            total = lib.flm_fcn_workspace_bytes(arch, *shape, *tail)
+            assert offs[0] == 0 and offs == sorted(set(offs)) and offs[-1] < q(b"fc6") < q(b"fc7") < q(b"score5") < total
+            assert {q(b"f%d" % k) for k in range(1, 6)} <= set(offs) and q(b"f5") == offs[-1]
+            assert (q(b"fuse4"), q(b"seg_feats")) == (-1, -1) if arch & 1 else q(b"score5") < q(b"fuse4") < q(b"seg_feats")
+            # regions do not overlap: each holds its [n, out_h, out_w, cout] tensor in the operand type
+            info = _lib.EncLayerInfo()
+            for i in range(layers):
+                assert lib.flm_fcn_encoder_layer(arch, i, 64, 96, C.byref(info)) == 0
+                end = offs[i] + (2 if dt else 4) * 3 * info.out_h * info.out_w * info.cout
+                assert end <= (offs[i + 1] if i + 1 < layers else q(b"fc6")), (arch, i)
+            for name in (b"act%d" % layers, b"act", b"act-1", b"act01", b"act1 ", b"act1x", b"ACT1", b"f0", b"f6", b"nonsense", b""):
+                assert q(name) == -1, (arch, name)
+            assert lib.flm_fcn_workspace_offset_opts(arch, None, *shape, *tail, None) == -1
+    for arch in (-1, 8, 1 << 30):
+        assert lib.flm_fcn_workspace_offset_opts(arch, b"f1", *shape, 0, 0, 0, 0, None) == -1
+        assert lib.flm_fcn_encoder_layers(arch) == -1 and b"unknown architecture" in lib.flm_last_error()
+        assert lib.flm_fcn_encoder_layer(arch, 0, 64, 96, C.byref(info)) == -1
+    assert lib.flm_fcn_workspace_offset_opts(6, b"act1", 3, 60, 96, 68, 0, 0, 0, 0, None) == -1
+    assert lib.flm_fcn_workspace_offset_opts(6, b"act1", 3, 64, 96, 68, 5, 0, 0, 0, None) == -1
+    assert lib.flm_fcn_encoder_layer(6, 0, 64, 96, None) == -1 and b"null" in lib.flm_last_error()
+    assert lib.flm_fcn_encoder_layer(6, 54, 64, 96, C.byref(info)) == -1 and lib.flm_fcn_encoder_layer(6, -1, 64, 96, C.byref(info)) == -1
+    assert lib.flm_fcn_encoder_layer(6, 0, 60, 96, C.byref(info)) == -2 and b"multiples of 32" in lib.flm_last_error()
+    # ResNet50 at 32 x 32: 16 x 16 -> max-pool 7 x 7 -> 4 x 4 -> 2 x 2 -> 1 x 1; the shortcut of a `2c` conv is an earlier layer
+    grids = []
+    for i in range(54):
+        assert lib.flm_fcn_encoder_layer(6, i, 32, 32, C.byref(info)) == 0
+        grids.append((info.out_h, info.out_w))
+        assert info.res < i and info.src < i
+    assert grids[0] == (16, 16) and grids[1] == (7, 7) and sorted(set(grids), reverse=True) == [(16, 16), (7, 7), (4, 4), (2, 2), (1, 1)]
+    # the model objects: names in network order, KeyError for an unknown name without touching a GPU
+    m = LANDMARKS_MODELS["fcn_8_resnet50"](68, input_height=32, input_width=32)
+    names = m.encoder_layer_names()
+    assert len(names) == 54 and names[:4] == ("conv1", "max_pooling2d", "res2a_branch1", "res2a_branch2a") and names[-1] == "res5c_branch2c"
+    assert LANDMARKS_MODELS["fcn_8_mobilenet"](68).encoder_layer_names()[:3] == ("conv1", "conv_dw_1", "conv_pw_1")
+    assert LANDMARKS_MODELS["fcn_8"](68).encoder_layer_names() == ("enc1", "enc2", "enc3", "enc4", "enc5")
+    for bad in ("act54", "nonsense", "act"):
+        with pytest.raises(KeyError):
+            m.intermediate(bad, 1)
+
+
 def test_product_path_fails_loudly_without_gpu():
     import torch
     if torch.cuda.is_available():

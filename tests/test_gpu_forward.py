@@ -407,8 +407,9 @@ def test_vgg_variants(flm):
 
 
 def _gate_against_the_rounding_oracle(label, got, img, params, encoder, fcn32):
-    """End-to-end gate of a bf16 model whose layers are not exposed: the device's probabilities against the free-running
-    bf16-rounding oracle (oracle/fcn_bf16_ref.py).  The bar is measured on the reference alone: the oracle with float64
+    """End-to-end gate of a bf16 model (its layers are held one by one, teacher-forced, in tests/test_gpu_bf16_layers.py and
+    tests/test_gpu_encoder_layers.py): the device's probabilities against the free-running bf16-rounding oracle
+    (oracle/fcn_bf16_ref.py).  The bar is measured on the reference alone: the oracle with float64
     and with float32 accumulation has identical rounding points, so the two differ only by rounding flips and what they
     grow into; the kernels, a third summation order, must stay within 4 x that distance (mean and max) -- and be
     strictly closer (mean) to the bf16 oracle than to the fp32 one."""
