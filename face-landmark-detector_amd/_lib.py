@@ -24,6 +24,7 @@ LAYOUT_NHWC, LAYOUT_NCHW = 0, 1                      # flm_pixel_layout
 PIX_F32, PIX_F16, PIX_BF16, PIX_U8 = 0, 1, 2, 3      # flm_pixel_type
 FRAME_BGR24, FRAME_NV12 = 0, 1                       # flm_frame_pixel
 YUV_BT601_LIMITED, YUV_BT709_LIMITED = 0, 1          # flm_yuv_matrix
+TRACK_DEAD, TRACK_FEW_POINTS, TRACK_LOW_SCORE, TRACK_SCALE, TRACK_OUTSIDE = 1, 2, 4, 8, 16   # flm_track_status
 
 EXPORTS = [
     "flm_abi_version", "flm_last_error",
@@ -43,6 +44,7 @@ EXPORTS = [
     "flm_image_format_init", "flm_image_format_bytes", "flm_warp_affine_fmt", "flm_warp_affine_frames_fmt",
     "flm_frame_format_init", "flm_frame_format_bytes", "flm_frames_to_bgr", "flm_crop_resize_frames_src",
     "flm_warp_affine_frames_src",
+    "flm_track_opts_init", "flm_track_seed", "flm_landmarks_from_crop", "flm_track_step",
 ]
 
 
@@ -97,6 +99,22 @@ class FrameFormat(C.Structure):
     """flm_frame_format: how a ring slot holds its pixels -- dense BGR, or the NV12 surface of a decoder (include/flm.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("pixel", C.c_int32), ("matrix", C.c_int32), ("y_pitch", C.c_uint32),
                 ("uv_pitch", C.c_uint32), ("uv_offset", C.c_uint64)]
+
+
+class TrackOpts(C.Structure):
+    """flm_track_opts: when flm_track_step gives a track up (include/flm.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("min_points", C.c_int32), ("min_score", C.c_double),
+                ("min_side", C.c_double), ("max_side", C.c_double)]
+
+    @classmethod
+    def make(cls, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf")):
+        o = cls()
+        load().flm_track_opts_init(C.byref(o))
+        o.min_points = int(min_points)
+        o.min_score = float(min_score)
+        o.min_side = float(min_side)
+        o.max_side = float(max_side)
+        return o
 
 
 class FcnParams(C.Structure):
@@ -228,6 +246,16 @@ def _declare(lib):
     lib.flm_warp_affine_frames_src.restype = i
     lib.flm_warp_affine_frames_src.argtypes = [vp, vp, C.c_size_t, i, i, i, vp, vp, vp, i, vp, i, i, i,
                                                C.POINTER(ImageFormat), C.POINTER(FrameFormat)]
+    d = C.c_double
+    lib.flm_track_opts_init.restype = None
+    lib.flm_track_opts_init.argtypes = [C.POINTER(TrackOpts)]
+    lib.flm_track_seed.restype = i
+    lib.flm_track_seed.argtypes = [vp, vp, i, i, i, i, i, vp, vp]
+    lib.flm_landmarks_from_crop.restype = i
+    lib.flm_landmarks_from_crop.argtypes = [vp, vp, sz, vp, i, i, d, d, vp]
+    lib.flm_track_step.restype = i
+    lib.flm_track_step.argtypes = [vp, vp, sz, vp, sz, vp, vp, i, i, d, d, i, i, i, i, vp, vp, C.POINTER(TrackOpts),
+                                   vp, vp, vp, vp, vp]
 
 
 def load():

@@ -461,3 +461,152 @@ def warp_frames_device(frames, m, out_h, out_w, frame_index_dev=None, boxes_dev=
     else:
         _lib.check(lib.flm_warp_affine_frames(*head), "flm_warp_affine_frames")
     return out
+
+
+# ---- tracking: the next frame's crop from this frame's landmarks (include/flm.h, "tracking") --------------------------
+def _check_matrices(m, k, what="m"):
+    import torch
+    if (not isinstance(m, torch.Tensor) or m.dtype != torch.float32 or not m.is_cuda or not m.is_contiguous()
+            or m.dim() != 3 or tuple(m.shape[1:]) != (2, 3) or (k is not None and int(m.shape[0]) != k)):
+        raise ValueError("%s must be a contiguous CUDA float32 [%s,2,3] tensor" % (what, "K" if k is None else k))
+
+
+def _check_out(t, dtype, shape, what):
+    import torch
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_cuda
+            or not t.is_contiguous()):
+        raise ValueError("%s must be a contiguous CUDA %s %s tensor" % (what, str(dtype).replace("torch.", ""), list(shape)))
+
+
+def _sizes(hw, what):
+    h, w = [int(v) for v in hw]
+    if h < 1 or w < 1:
+        raise ValueError("%s must be positive" % what)
+    return h, w
+
+
+def _strided_points(lm, what="lm"):
+    """(tensor, element stride) of a CUDA float64 [K,C,2] tensor or view read in place: rec[..., :2] of a landmark
+    record tensor keeps its stride of 6, any other non-uniform view is copied."""
+    import torch
+    if not isinstance(lm, torch.Tensor) or lm.dtype != torch.float64 or lm.dim() != 3 or lm.shape[2] != 2 or not lm.is_cuda:
+        raise ValueError("%s must be a CUDA float64 [K,C,2] tensor" % what)
+    st = _uniform_stride(lm, 2)
+    return (lm.contiguous(), 2) if st is None else (lm, st)
+
+
+def track_seed_device(boxes_dev, in_hw, frame_hw, m_out=None, status_out=None):
+    """boxes_dev: CUDA int32 [K,4] squared detector boxes -> (m CUDA float32 [K,2,3] frame px -> network-input px,
+    status CUDA int32 [K]) (flm_track_seed: the matrix under which the uint8 frame warp cuts the box as
+    flm_crop_resize does; a box without pixels in the frame gives the identity and TRACK_DEAD)."""
+    import torch
+    if not isinstance(boxes_dev, torch.Tensor) or boxes_dev.dim() != 2:
+        raise ValueError("boxes_dev must be a contiguous CUDA int32 [K,4] tensor")
+    k = int(boxes_dev.shape[0])
+    _check_boxes(boxes_dev, k)
+    ih, iw = _sizes(in_hw, "in_hw")
+    fh, fw = _sizes(frame_hw, "frame_hw")
+    if m_out is None:
+        m_out = torch.empty((k, 2, 3), dtype=torch.float32, device=boxes_dev.device)
+    else:
+        _check_matrices(m_out, k, "m_out")
+    if status_out is None:
+        status_out = torch.empty((k,), dtype=torch.int32, device=boxes_dev.device)
+    else:
+        _check_out(status_out, torch.int32, (k,), "status_out")
+    if k:
+        _lib.check(_lib.load().flm_track_seed(_lib.stream_ptr(), _lib.ptr(boxes_dev), k, ih, iw, fh, fw, _lib.ptr(m_out),
+                                              _lib.ptr(status_out)), "flm_track_seed")
+    return m_out, status_out
+
+
+def landmarks_from_crop_device(lm, m, grid_hw, in_hw, out=None):
+    """lm: CUDA float64 [K,C,2] in output-grid pixels (rec[..., :2] of a landmark record tensor is read in place);
+    m: CUDA float32 [K,2,3], the matrices the crops were cut with (frame px -> input px) -> CUDA float64 [K,C,2] in frame
+    pixels (flm_landmarks_from_crop: the float64 inverse of m; rejected points, points that land at a negative frame
+    coordinate and the points of a face with a singular matrix are (-1,-1))."""
+    import torch
+    lm, ls = _strided_points(lm)
+    k, c = int(lm.shape[0]), int(lm.shape[1])
+    _check_matrices(m, k)
+    gh, gw = _sizes(grid_hw, "grid_hw")
+    ih, iw = _sizes(in_hw, "in_hw")
+    if out is None:
+        out = torch.empty((k, c, 2), dtype=torch.float64, device=lm.device)
+    else:
+        _check_out(out, torch.float64, (k, c, 2), "out")
+    if k and c:
+        _lib.check(_lib.load().flm_landmarks_from_crop(_lib.stream_ptr(), _lib.ptr(lm), ls, _lib.ptr(m), k, c, iw / gw,
+                                                       ih / gh, _lib.ptr(out)), "flm_landmarks_from_crop")
+    return out
+
+
+def track_step_device(lm, m_crop, boxes_dev, grid_hw, in_hw, frame_hw, tmpl_crop, tmpl_align=None, weights=None,
+                      min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"), lm_frame=None, m_align=None,
+                      m_next=None, boxes_next=None, status=None):
+    """The per-frame update of a set of tracks in one launch (flm_track_step; include/flm.h states it line by line).
+
+    lm: CUDA float64 [K,C,2] on the output grid and `weights`: None or CUDA float64 [K,C] (both may be views of a
+    landmark record tensor, read in place); m_crop CUDA float32 [K,2,3] and boxes_dev CUDA int32 [K,4]: what this frame's
+    crops were cut with; tmpl_crop CUDA float64 [C,2] in input px: where the landmarks should sit in the next crop;
+    tmpl_align CUDA float64 [C,2] in aligned px, or None: no aligned fit.
+    Returns (lm_frame float64 [K,C,2] frame px, m_align float32 [K,2,3] frame px -> aligned px or None, m_next float32
+    [K,2,3] frame px -> input px of the next crop, boxes_next int32 [K,4], status int32 [K]: 0 or TRACK_* bits; a lost
+    track has an empty box and the identity as m_next).  The five keyword tensors name where to write; `m_next` may be
+    `m_crop` and `boxes_next` may be `boxes_dev`."""
+    import torch
+    lm, ls = _strided_points(lm)
+    k, c = int(lm.shape[0]), int(lm.shape[1])
+    _check_matrices(m_crop, k, "m_crop")
+    _check_boxes(boxes_dev, k)
+    gh, gw = _sizes(grid_hw, "grid_hw")
+    ih, iw = _sizes(in_hw, "in_hw")
+    fh, fw = _sizes(frame_hw, "frame_hw")
+    _check_out(tmpl_crop, torch.float64, (c, 2), "tmpl_crop")
+    if tmpl_align is not None:
+        _check_out(tmpl_align, torch.float64, (c, 2), "tmpl_align")
+    wst = 1
+    if weights is not None:
+        if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64 or tuple(weights.shape) != (k, c)
+                or not weights.is_cuda):
+            raise ValueError("weights must be a CUDA float64 [%d,%d] tensor" % (k, c))
+        wst = _uniform_stride(weights, 1)
+        if wst is None:
+            weights, wst = weights.contiguous(), 1
+    if m_align is not None and tmpl_align is None:
+        raise ValueError("m_align needs tmpl_align")
+    if int(min_points) < 2:
+        raise ValueError("min_points must be 2 or more")
+    if any(v != v for v in (float(min_score), float(min_side), float(max_side))):
+        raise ValueError("min_score, min_side and max_side must not be NaN")
+    dev = lm.device
+    if lm_frame is None:
+        lm_frame = torch.empty((k, c, 2), dtype=torch.float64, device=dev)
+    else:
+        _check_out(lm_frame, torch.float64, (k, c, 2), "lm_frame")
+    if tmpl_align is not None:
+        if m_align is None:
+            m_align = torch.empty((k, 2, 3), dtype=torch.float32, device=dev)
+        else:
+            _check_matrices(m_align, k, "m_align")
+    if m_next is None:
+        m_next = torch.empty((k, 2, 3), dtype=torch.float32, device=dev)
+    else:
+        _check_matrices(m_next, k, "m_next")
+    if boxes_next is None:
+        boxes_next = torch.empty((k, 4), dtype=torch.int32, device=dev)
+    else:
+        _check_boxes(boxes_next, k)
+    if status is None:
+        status = torch.empty((k,), dtype=torch.int32, device=dev)
+    else:
+        _check_out(status, torch.int32, (k,), "status")
+    if k and c:
+        opts = _lib.TrackOpts.make(min_points, min_score, min_side, max_side)
+        _lib.check(_lib.load().flm_track_step(
+            _lib.stream_ptr(), _lib.ptr(lm), ls, None if weights is None else _lib.ptr(weights), wst, _lib.ptr(m_crop),
+            _lib.ptr(boxes_dev), k, c, iw / gw, ih / gh, ih, iw, fh, fw, _lib.ptr(tmpl_crop),
+            None if tmpl_align is None else _lib.ptr(tmpl_align), _lib.C.byref(opts), _lib.ptr(lm_frame),
+            None if m_align is None else _lib.ptr(m_align), _lib.ptr(m_next), _lib.ptr(boxes_next), _lib.ptr(status)),
+            "flm_track_step")
+    return lm_frame, m_align, m_next, boxes_next, status

@@ -1147,4 +1147,66 @@ int flm_warp_affine_frames_src(flm_stream_t stream, const uint8_t* frames, size_
                                  fmt ? fmt : &plain, src);
 }
 
+// ---- tracking (flm_track.hip) ------------------------------------------------------------------------------------
+
+void flm_track_opts_init(flm_track_opts* opts) {
+  if (!opts) return;
+  opts->struct_size = (uint32_t)sizeof(flm_track_opts);
+  opts->min_points = 2;
+  opts->min_score = 0.0;
+  opts->min_side = 0.0;
+  opts->max_side = HUGE_VAL;
+}
+
+int flm_track_seed(flm_stream_t stream, const int32_t* boxes, int k, int in_h, int in_w, int fh, int fw, float* m,
+                   int32_t* status) {
+  if (!boxes || !m || !status) {
+    set_error("flm_track_seed: null argument");
+    return FLM_ERR_ARG;
+  }
+  return launch_track_seed(static_cast<hipStream_t>(stream), boxes, k, in_h, in_w, fh, fw, m, status);
+}
+
+int flm_landmarks_from_crop(flm_stream_t stream, const double* lm, size_t lm_stride, const float* m, int k, int c,
+                            double sx, double sy, double* out) {
+  if (!lm || !m || !out) {
+    set_error("flm_landmarks_from_crop: null argument");
+    return FLM_ERR_ARG;
+  }
+  return launch_landmarks_from_crop(static_cast<hipStream_t>(stream), lm, lm_stride, m, k, c, sx, sy, out);
+}
+
+int flm_track_step(flm_stream_t stream, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
+                   const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h, int in_w,
+                   int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
+                   double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status) {
+  if (!lm || !m_crop || !boxes || !tmpl_crop || !lm_frame || !m_next || !boxes_next || !status) {  // (wt is optional)
+    set_error("flm_track_step: null argument");
+    return FLM_ERR_ARG;
+  }
+  if ((tmpl_align == nullptr) != (m_align == nullptr)) {
+    set_error("flm_track_step: tmpl_align_dev and m_align_dev go together (both or neither)");
+    return FLM_ERR_ARG;
+  }
+  flm_track_opts defaults;
+  flm_track_opts_init(&defaults);
+  if (!opts) opts = &defaults;
+  if (opts->struct_size < sizeof(flm_track_opts)) {
+    set_error("flm_track_step: flm_track_opts struct_size %u is smaller than this library's %zu (initialise with "
+              "flm_track_opts_init)", opts->struct_size, sizeof(flm_track_opts));
+    return FLM_ERR_ARG;
+  }
+  if (opts->min_points < 2) {
+    set_error("flm_track_step: min_points=%d, needs min_points >= 2 (a similarity takes two points)", opts->min_points);
+    return FLM_ERR_ARG;
+  }
+  if (std::isnan(opts->min_score) || std::isnan(opts->min_side) || std::isnan(opts->max_side)) {
+    set_error("flm_track_step: min_score, min_side and max_side must not be NaN (got %g, %g, %g)", opts->min_score,
+              opts->min_side, opts->max_side);
+    return FLM_ERR_ARG;
+  }
+  return launch_track_step(static_cast<hipStream_t>(stream), lm, lm_stride, wt, w_stride, m_crop, boxes, k, c, sx, sy, in_h,
+                           in_w, fh, fw, tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next, status);
+}
+
 }  // extern "C"

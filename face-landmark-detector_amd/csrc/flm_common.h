@@ -276,6 +276,16 @@ int launch_warp_frames_nv12(hipStream_t s, const uint8_t* frames, size_t frame_s
 // 0 when the format's sizes are rejected (the reason is in flm_last_error())
 size_t nv12_format_bytes(const char* who, const flm_frame_format* src, int fh, int fw);
 
+// tracking (flm_track.hip); null pointers and the option struct have been checked by the caller, `opts` is never null
+int launch_track_seed(hipStream_t s, const int32_t* boxes, int k, int in_h, int in_w, int fh, int fw, float* m,
+                      int32_t* status);
+int launch_landmarks_from_crop(hipStream_t s, const double* lm, size_t lm_stride, const float* m, int k, int c, double sx,
+                               double sy, double* out);
+int launch_track_step(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
+                      const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h, int in_w,
+                      int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
+                      double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status);
+
 // Bijective XCD-aware remap of a 1-D grid: blocks that the dispatcher deals to the same XCD
 // (b % 8) receive consecutive logical ids, so neighbours in logical order share an L2.
 __device__ __forceinline__ int xcd_remap(int b, int nblk) {

@@ -1,0 +1,283 @@
+// Tracking: the crop of the next frame from the landmarks of this one (include/flm.h states every operation; the
+// comments here only say how the work is laid out).  float64 throughout, -ffp-contract=off: nothing fuses.
+#include "flm_common.h"
+
+namespace flm {
+
+__device__ __forceinline__ bool box_empty(int x0, int y0, int x1, int y1, int fh, int fw) {
+  const int cx0 = min(max(x0, 0), fw), cy0 = min(max(y0, 0), fh);
+  const int cx1 = min(max(x1, 0), fw), cy1 = min(max(y1, 0), fh);
+  return cx1 - cx0 <= 0 || cy1 - cy0 <= 0;
+}
+
+// A 2x3 matrix widened to double, and the back-projection through it.
+struct Affine {
+  double m00, m01, m02, m10, m11, m12, det;
+  bool ok;  // det finite and not zero
+};
+__device__ __forceinline__ Affine make_affine(float f00, float f01, float f02, float f10, float f11, float f12) {
+  Affine a;
+  a.m00 = (double)f00; a.m01 = (double)f01; a.m02 = (double)f02;
+  a.m10 = (double)f10; a.m11 = (double)f11; a.m12 = (double)f12;
+  a.det = a.m00 * a.m11 - a.m01 * a.m10;
+  a.ok = __builtin_isfinite(a.det) && a.det != 0.0;
+  return a;
+}
+__device__ __forceinline__ void affine_back(const Affine& a, double x, double y, double& xf, double& yf) {
+  const double u = x - a.m02, v = y - a.m12;
+  xf = (a.m11 * u - a.m01 * v) / a.det;
+  yf = (a.m00 * v - a.m10 * u) / a.det;
+}
+// One landmark on the output grid -> frame px, (-1,-1) for every reason the header lists.
+__device__ __forceinline__ void landmark_back(const Affine& a, double x, double y, double sx, double sy, double& xf,
+                                              double& yf) {
+  xf = -1.0;
+  yf = -1.0;
+  if (!a.ok || x < 0.0 || y < 0.0) return;
+  double tx, ty;
+  affine_back(a, x * sx, y * sy, tx, ty);
+  if (tx < 0.0 || ty < 0.0 || !__builtin_isfinite(tx) || !__builtin_isfinite(ty)) return;
+  xf = tx;
+  yf = ty;
+}
+
+// ---- flm_track_seed: a thread per face -----------------------------------------------------------------
+__global__ __launch_bounds__(64) void track_seed_kernel(const int32_t* __restrict__ boxes, int k, int in_h, int in_w,
+                                                        int fh, int fw, float* __restrict__ m,
+                                                        int32_t* __restrict__ status) {
+  const int f = blockIdx.x * 64 + threadIdx.x;
+  if (f >= k) return;
+  const int x0 = boxes[4 * f + 0], y0 = boxes[4 * f + 1], x1 = boxes[4 * f + 2], y1 = boxes[4 * f + 3];
+  float a = 1.f, d = 1.f, tx = 0.f, ty = 0.f;
+  const bool dead = box_empty(x0, y0, x1, y1, fh, fw);
+  if (!dead) {  // (a box with pixels has x1 > x0 and y1 > y0)
+    const double sx = (double)in_w / (double)(x1 - x0), sy = (double)in_h / (double)(y1 - y0);
+    a = (float)sx;
+    d = (float)sy;
+    tx = (float)((0.5 - (double)x0) * sx - 0.5);
+    ty = (float)((0.5 - (double)y0) * sy - 0.5);
+  }
+  float* o = m + (size_t)f * 6;
+  o[0] = a;   o[1] = 0.f; o[2] = tx;
+  o[3] = 0.f; o[4] = d;   o[5] = ty;
+  status[f] = dead ? FLM_TRACK_DEAD : 0;
+}
+
+// ---- flm_landmarks_from_crop: a workgroup (one wave) per face, a thread per point ----------------------------
+__global__ __launch_bounds__(64) void landmarks_from_crop_kernel(const double* __restrict__ lm, size_t lm_stride,
+                                                                 const float* __restrict__ m, int c, double sx, double sy,
+                                                                 double* __restrict__ out) {
+  const int f = blockIdx.x;
+  const float* mm = m + (size_t)f * 6;
+  const Affine a = make_affine(mm[0], mm[1], mm[2], mm[3], mm[4], mm[5]);
+  for (int i = threadIdx.x; i < c; i += 64) {
+    const double* p = lm + ((size_t)f * c + i) * lm_stride;
+    double xf, yf;
+    landmark_back(a, p[0], p[1], sx, sy, xf, yf);
+    out[((size_t)f * c + i) * 2] = xf;
+    out[((size_t)f * c + i) * 2 + 1] = yf;
+  }
+}
+
+// ---- flm_track_step ---------------------------------------------------------------------------------------
+// The shape of similarity_weighted_kernel (csrc/flm_misc.hip): one wave per face stages the face in LDS -- here the
+// points already back-projected to frame px, a thread each -- and the sequential sums of the fit run in landmark order
+// on LDS latency.  The two fits (onto tmpl_crop and onto tmpl_align) walk the same participating set, so lanes 0 and 1
+// run them in lockstep, a template each: one pass of the serial loops for both matrices.  Lane 0 then owns the status
+// tests and the box, lane 1 the aligned matrix.  m_next / boxes_next may be m_crop / boxes: every lane has read both
+// before the barrier, the writes come after it.
+struct TrackStepArgs {
+  const double* lm;
+  size_t lm_stride;
+  const double* wt;
+  size_t w_stride;
+  const float* m_crop;
+  const int32_t* boxes;
+  int c;
+  double sx, sy;
+  int in_h, in_w, fh, fw;
+  const double* tmpl_crop;
+  const double* tmpl_align;
+  int min_points;
+  double min_score, min_side, max_side;
+  double* lm_frame;
+  float* m_align;
+  float* m_next;
+  int32_t* boxes_next;
+  int32_t* status;
+};
+
+__device__ __forceinline__ int box_coord(double t) {
+  const double lim = 1073741824.0;  // 2^30
+  return (int)fmin(fmax(t, -lim), lim);
+}
+
+__global__ __launch_bounds__(64) void track_step_kernel(const TrackStepArgs g) {
+  extern __shared__ __attribute__((aligned(16))) double trk_s[];  // [c][2] frame px, [c][2] x 2 templates, [c] weights
+  const int f = blockIdx.x, c = g.c;
+  double* p = trk_s;
+  double* tc = trk_s + 2 * c;   // tmpl_crop, then tmpl_align: lane l of the fit reads tc + l*2c
+  double* w = trk_s + 6 * c;
+  const int32_t* bx = g.boxes + 4 * (size_t)f;
+  const bool dead = box_empty(bx[0], bx[1], bx[2], bx[3], g.fh, g.fw);
+  const float* mm = g.m_crop + (size_t)f * 6;
+  const Affine crop = make_affine(mm[0], mm[1], mm[2], mm[3], mm[4], mm[5]);
+  for (int i = threadIdx.x; i < c; i += 64) {
+    const double* q = g.lm + ((size_t)f * c + i) * g.lm_stride;
+    double xf = -1.0, yf = -1.0;
+    if (!dead) landmark_back(crop, q[0], q[1], g.sx, g.sy, xf, yf);
+    p[2 * i] = xf;
+    p[2 * i + 1] = yf;
+    g.lm_frame[((size_t)f * c + i) * 2] = xf;
+    g.lm_frame[((size_t)f * c + i) * 2 + 1] = yf;
+    w[i] = g.wt ? g.wt[((size_t)f * c + i) * g.w_stride] : 1.0;
+    tc[2 * i] = g.tmpl_crop[2 * i];
+    tc[2 * i + 1] = g.tmpl_crop[2 * i + 1];
+    if (g.tmpl_align) {
+      tc[2 * c + 2 * i] = g.tmpl_align[2 * i];
+      tc[2 * c + 2 * i + 1] = g.tmpl_align[2 * i + 1];
+    }
+  }
+  __syncthreads();
+  const int lane = threadIdx.x;
+  if (lane > (g.tmpl_align ? 1 : 0)) return;
+  // the weighted fit of similarity_weighted_kernel with sx = sy = 1 (p * 1 is p), operation for operation
+  const double* t = tc + (size_t)lane * 2 * c;
+  double mpx = 0, mpy = 0, mqx = 0, mqy = 0, wsum = 0;
+  int cnt = 0;
+  for (int i = 0; i < c; ++i) {
+    if (!(p[2 * i] >= 0.0 && p[2 * i + 1] >= 0.0 && w[i] > 0.0)) continue;
+    mpx += w[i] * p[2 * i]; mpy += w[i] * p[2 * i + 1];
+    mqx += w[i] * t[2 * i]; mqy += w[i] * t[2 * i + 1];
+    wsum += w[i];
+    ++cnt;
+  }
+  double a = 1.0, b = 0.0, tx = 0.0, ty = 0.0;
+  if (cnt >= 2) {
+    mpx /= wsum; mpy /= wsum; mqx /= wsum; mqy /= wsum;
+    double sa = 0, sb = 0, var = 0;
+    for (int i = 0; i < c; ++i) {
+      if (!(p[2 * i] >= 0.0 && p[2 * i + 1] >= 0.0 && w[i] > 0.0)) continue;
+      const double px = p[2 * i] - mpx, py = p[2 * i + 1] - mpy;
+      const double qx = t[2 * i] - mqx, qy = t[2 * i + 1] - mqy;
+      sa += w[i] * (px * qx + py * qy);
+      sb += w[i] * (px * qy - py * qx);
+      var += w[i] * (px * px + py * py);
+    }
+    if (var > 0.0) {
+      a = sa / var;
+      b = sb / var;
+      tx = mqx - (a * mpx - b * mpy);
+      ty = mqy - (b * mpx + a * mpy);
+    }
+  }
+  const float f00 = (float)a, f01 = (float)(-b), f02 = (float)tx, f10 = (float)b, f11 = (float)a, f12 = (float)ty;
+  if (lane == 1) {
+    float* o = g.m_align + (size_t)f * 6;
+    o[0] = f00; o[1] = f01; o[2] = f02;
+    o[3] = f10; o[4] = f11; o[5] = f12;
+    return;
+  }
+  int st = dead ? FLM_TRACK_DEAD : 0;
+  if (cnt < g.min_points) st |= FLM_TRACK_FEW_POINTS;
+  if (g.wt && !(wsum / (double)cnt >= g.min_score)) st |= FLM_TRACK_LOW_SCORE;
+  const double da = (double)f00, db = (double)f10;
+  const double side = (double)g.in_w / sqrt(da * da + db * db);
+  if (!(side >= g.min_side && side <= g.max_side)) st |= FLM_TRACK_SCALE;
+  const Affine nx = make_affine(f00, f01, f02, f10, f11, f12);
+  const double ex = (double)(g.in_w - 1), ey = (double)(g.in_h - 1);
+  double cx, cy;
+  affine_back(nx, ex / 2.0, ey / 2.0, cx, cy);
+  if (!(nx.ok && cx >= 0.0 && cx <= (double)(g.fw - 1) && cy >= 0.0 && cy <= (double)(g.fh - 1))) st |= FLM_TRACK_OUTSIDE;
+  int b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+  float o0 = 1.f, o1 = 0.f, o2 = 0.f, o3 = 0.f, o4 = 1.f, o5 = 0.f;
+  if (st == 0) {
+    double mnx, mny, mxx, mxy, x, y;
+    affine_back(nx, 0.0, 0.0, mnx, mny);
+    mxx = mnx;
+    mxy = mny;
+    affine_back(nx, ex, 0.0, x, y);
+    mnx = x < mnx ? x : mnx; mny = y < mny ? y : mny; mxx = x > mxx ? x : mxx; mxy = y > mxy ? y : mxy;
+    affine_back(nx, 0.0, ey, x, y);
+    mnx = x < mnx ? x : mnx; mny = y < mny ? y : mny; mxx = x > mxx ? x : mxx; mxy = y > mxy ? y : mxy;
+    affine_back(nx, ex, ey, x, y);
+    mnx = x < mnx ? x : mnx; mny = y < mny ? y : mny; mxx = x > mxx ? x : mxx; mxy = y > mxy ? y : mxy;
+    b0 = box_coord(floor(mnx));
+    b1 = box_coord(floor(mny));
+    b2 = box_coord(ceil(mxx) + 1.0);
+    b3 = box_coord(ceil(mxy) + 1.0);
+    o0 = f00; o1 = f01; o2 = f02; o3 = f10; o4 = f11; o5 = f12;
+  }
+  float* o = g.m_next + (size_t)f * 6;
+  o[0] = o0; o[1] = o1; o[2] = o2;
+  o[3] = o3; o[4] = o4; o[5] = o5;
+  int32_t* bo = g.boxes_next + 4 * (size_t)f;
+  bo[0] = b0; bo[1] = b1; bo[2] = b2; bo[3] = b3;
+  g.status[f] = st;
+}
+
+// ---- launchers: the sizes every entry point shares ----------------------------------------------------------
+static int check_track_sizes(const char* who, int k, int c, int in_h, int in_w, int fh, int fw) {
+  if (k < 1 || k > 65535) {
+    set_error("%s: k=%d, needs 1 <= k <= 65535", who, k);
+    return FLM_ERR_SHAPE;
+  }
+  if (c < 1 || c > 1024) {
+    set_error("%s: c=%d, needs 1 <= c <= 1024", who, c);
+    return FLM_ERR_SHAPE;
+  }
+  if (in_h < 1 || in_w < 1 || fh < 1 || fw < 1) {
+    set_error("%s: input %dx%d, frame %dx%d, needs in_h, in_w, fh, fw >= 1", who, in_h, in_w, fh, fw);
+    return FLM_ERR_SHAPE;
+  }
+  return FLM_OK;
+}
+
+static int check_track_points(const char* who, size_t lm_stride, size_t w_stride, double sx, double sy) {
+  if (lm_stride < 2 || w_stride < 1) {
+    set_error("%s: needs lm_stride >= 2 and w_stride >= 1 (got %zu, %zu)", who, lm_stride, w_stride);
+    return FLM_ERR_SHAPE;
+  }
+  if (!(sx > 0.0 && sy > 0.0)) {
+    set_error("%s: needs sx, sy > 0 (got %g, %g)", who, sx, sy);
+    return FLM_ERR_SHAPE;
+  }
+  return FLM_OK;
+}
+
+int launch_track_seed(hipStream_t s, const int32_t* boxes, int k, int in_h, int in_w, int fh, int fw, float* m,
+                      int32_t* status) {
+  if (const int rc = check_track_sizes("flm_track_seed", k, 1, in_h, in_w, fh, fw)) return rc;
+  track_seed_kernel<<<cdiv(k, 64), 64, 0, s>>>(boxes, k, in_h, in_w, fh, fw, m, status);
+  FLM_LAUNCH_CHECK("track_seed_kernel");
+  return FLM_OK;
+}
+
+int launch_landmarks_from_crop(hipStream_t s, const double* lm, size_t lm_stride, const float* m, int k, int c, double sx,
+                               double sy, double* out) {
+  if (const int rc = check_track_sizes("flm_landmarks_from_crop", k, c, 1, 1, 1, 1)) return rc;
+  if (const int rc = check_track_points("flm_landmarks_from_crop", lm_stride, 1, sx, sy)) return rc;
+  landmarks_from_crop_kernel<<<k, 64, 0, s>>>(lm, lm_stride, m, c, sx, sy, out);
+  FLM_LAUNCH_CHECK("landmarks_from_crop_kernel");
+  return FLM_OK;
+}
+
+int launch_track_step(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
+                      const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h, int in_w,
+                      int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
+                      double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status) {
+  if (const int rc = check_track_sizes("flm_track_step", k, c, in_h, in_w, fh, fw)) return rc;
+  if (const int rc = check_track_points("flm_track_step", lm_stride, w_stride, sx, sy)) return rc;
+  TrackStepArgs g;
+  g.lm = lm; g.lm_stride = lm_stride; g.wt = wt; g.w_stride = w_stride;
+  g.m_crop = m_crop; g.boxes = boxes; g.c = c; g.sx = sx; g.sy = sy;
+  g.in_h = in_h; g.in_w = in_w; g.fh = fh; g.fw = fw;
+  g.tmpl_crop = tmpl_crop; g.tmpl_align = tmpl_align;
+  g.min_points = opts->min_points; g.min_score = opts->min_score; g.min_side = opts->min_side; g.max_side = opts->max_side;
+  g.lm_frame = lm_frame; g.m_align = m_align; g.m_next = m_next; g.boxes_next = boxes_next; g.status = status;
+  track_step_kernel<<<k, 64, sizeof(double) * 7 * c, s>>>(g);   // (at most 56 KiB: c <= 1024)
+  FLM_LAUNCH_CHECK("track_step_kernel");
+  return FLM_OK;
+}
+
+}  // namespace flm

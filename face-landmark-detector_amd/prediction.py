@@ -540,3 +540,144 @@ def video_predict(facedetector_fn, landmark_model, frames=None, on_frame=None, n
         if on_frame is not None and on_frame(img, marks) is False:
             break
     return count
+
+
+# ---- tracking: faces followed across frames from their own landmarks ---------------------------------------------------
+class FaceTracker:
+    """Faces followed across the frames of a stream on the device: the landmarks of frame t place the crop of frame t+1.
+
+    The detector seeds a track and re-seeds one that was lost; between those the per-frame step makes no host transfer
+    and no synchronisation.  The tracker owns the device state of `capacity` slots: the crop matrix of every slot (frame
+    px -> network-input px), its box (the frame region the crop covers; empty = no face), the ring slot its frame lies
+    in, and its status (0 or `_lib.TRACK_*` bits); it is allocated by the first seed, step or lost.
+
+    model: a landmark model of this package; frame_hw: (H, W) of the frames; out_size, template, samples,
+    aligned_format, frame_format, n_points, thresh: as `align_frames` takes them; weights: None or "score" (the forward
+    runs in its "landmark_stats" mode and both fits read the record tensor in place); crop_template float64 [C,2] in
+    network-input px: where the landmarks sit in the next crop -- upright, centred, at a fixed scale (default
+    `alignment.canonical_template(C, in_h, in_w)`); crop_samples: 1, 2 or 4 samples per axis and crop pixel, for faces
+    much larger than the network input; min_points, min_score, min_side, max_side: when a track is given up
+    (flm_track_opts; the defaults leave that to the geometric tests)."""
+
+    def __init__(self, model, frame_hw, capacity, out_size=(112, 112), template=None, crop_template=None, n_points=4,
+                 thresh=0.0, weights=None, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"),
+                 crop_samples=1, samples=1, aligned_format=None, frame_format=None):
+        import torch
+        if weights is not None and weights != "score":
+            raise ValueError("weights must be None or \"score\" (got %r)" % (weights,))
+        _aligned_format(aligned_format, False)
+        _frame_format(frame_format)
+        fh, fw = [int(v) for v in frame_hw]
+        if fw < 2 or fh < 1 or fh * fw * 3 >= 2 ** 31:
+            raise ValueError("frames of %dx%d are outside the warp's reach (width >= 2, H*W*3 < 2^31)" % (fh, fw))
+        capacity = int(capacity)
+        if not 1 <= capacity <= 65535:
+            raise ValueError("capacity must be in [1, 65535] (got %d)" % capacity)
+        oh, ow = [int(v) for v in out_size]
+        if oh < 1 or ow < 1:
+            raise ValueError("out_size must be positive")
+        if samples not in (1, 2, 4) or crop_samples not in (1, 2, 4):
+            raise ValueError("samples and crop_samples must be 1, 2 or 4")
+        if int(min_points) < 2:
+            raise ValueError("min_points must be 2 or more")
+        if any(v != v for v in (float(min_score), float(min_side), float(max_side))):
+            raise ValueError("min_score, min_side and max_side must not be NaN")
+        c = int(model.n_classes)
+        ih, iw = int(model.input_height), int(model.input_width)
+        tm = alignment.canonical_template(c, oh, ow) if template is None else template
+        tc = alignment.canonical_template(c, ih, iw) if crop_template is None else crop_template
+        tm, tc = [t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in (tm, tc)]
+        if tm.shape != (c, 2) or tc.shape != (c, 2):
+            raise ValueError("template and crop_template must be [%d,2]" % c)
+        self.model, self.capacity, self.frame_hw, self.out_size = model, capacity, (fh, fw), (oh, ow)
+        self.n_points, self.thresh, self.weights = n_points, thresh, weights
+        self.limits = dict(min_points=int(min_points), min_score=float(min_score), min_side=float(min_side),
+                           max_side=float(max_side))
+        self.crop_samples, self.samples = crop_samples, samples
+        self.aligned_format, self.frame_format = aligned_format, frame_format
+        self._crop_format = alignment.AlignedFormat("nhwc", "uint8")
+        self._templates = (np.ascontiguousarray(tm, np.float64), np.ascontiguousarray(tc, np.float64))
+        self.m_crop = None    # the device state, allocated by the first call that needs it (_state)
+
+    def _state(self):
+        """The device state: every slot starts dead -- an empty box, the identity, TRACK_DEAD."""
+        import torch
+        if self.m_crop is not None:
+            return
+        dev = _lib.require_gpu()
+        n = self.capacity
+        self.template, self.crop_template = [torch.from_numpy(t).to(dev) for t in self._templates]
+        self.boxes = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+        self._boxes_spare = torch.zeros_like(self.boxes)
+        self.frame_slots = torch.zeros((n,), dtype=torch.int32, device=dev)
+        self.status = torch.full((n,), _lib.TRACK_DEAD, dtype=torch.int32, device=dev)
+        self.m_crop = torch.eye(2, 3, dtype=torch.float32, device=dev).repeat(n, 1, 1).contiguous()
+
+    def seed(self, slots, boxes):
+        """Start (or restart) the tracks `slots` from the detector boxes `boxes` (x0,y0,x1,y1), one per slot: the host
+        box maths of `face_boxes`, one upload, flm_track_seed, and the results placed in those slots on the device."""
+        import torch
+        slots = [int(v) for v in slots]
+        boxes = [list(b) for b in boxes]
+        if len(slots) != len(boxes) or any(len(b) != 4 for b in boxes):
+            raise ValueError("seed takes one (x0,y0,x1,y1) box per slot")
+        if any(not 0 <= v < self.capacity for v in slots) or len(set(slots)) != len(slots):
+            raise ValueError("slots must be distinct and in [0, %d)" % self.capacity)
+        n = len(slots)
+        if not n:
+            return
+        self._state()
+        sq = np.asarray(face_boxes(boxes), np.int32).reshape(n, 4)
+        both = torch.from_numpy(np.concatenate([sq.reshape(-1), np.asarray(slots, np.int32)])).to(self.boxes.device)
+        bdev, idx = both[:4 * n].view(n, 4), both[4 * n:].to(torch.int64)
+        m, st = alignment.track_seed_device(bdev, (self.model.input_height, self.model.input_width), self.frame_hw)
+        self.m_crop.index_copy_(0, idx, m)
+        self.boxes.index_copy_(0, idx, bdev)
+        self.status.index_copy_(0, idx, st)
+
+    def step(self, ring, frame_index):
+        """One frame for every slot: `ring` is the frame ring (`frame_format` says how it holds its pixels),
+        `frame_index` the ring slot of the new frame.  Sequence: the uint8 crop warp with the slots' matrices ->
+        model.forward_device -> alignment.track_step_device (landmarks to frame px, the aligned fit, the next crop's
+        matrix and box, the status) -> the aligned warp.  Returns CUDA tensors (aligned [capacity,oh,ow,3] float32 or in
+        `aligned_format`, M float32 [capacity,2,3] frame px -> aligned px, landmarks float64 [capacity,C,2] in frame px,
+        status int32 [capacity]); `status` is the tracker's own tensor, overwritten by the next step or seed.  A slot
+        without a face returns zero crops and zero aligned faces, the identity and TRACK_DEAD; a track lost in this
+        frame still returns this frame's aligned face, with the reason in its status, and is dead from the next step
+        on."""
+        fh, fw = self.frame_hw
+        if self.frame_format is not None:
+            nf, rh, rw, _ = self.frame_format.ring(ring)
+        else:
+            nf, rh, rw, _ = alignment.FrameFormat.bgr().ring(ring)
+        if (rh, rw) != (fh, fw):
+            raise ValueError("the ring holds %dx%d frames, the tracker was made for %dx%d" % (rh, rw, fh, fw))
+        frame_index = int(frame_index)
+        if not 0 <= frame_index < nf:
+            raise ValueError("frame_index must name a ring slot in [0, %d)" % nf)
+        self._state()
+        model = self.model
+        ih, iw = model.input_height, model.input_width
+        self.frame_slots.fill_(frame_index)
+        crops = alignment.warp_frames_device(ring, self.m_crop, ih, iw, frame_index_dev=self.frame_slots,
+                                             boxes_dev=self.boxes, samples=self.crop_samples, fmt=self._crop_format,
+                                             src=self.frame_format)
+        if self.weights is None:
+            lm, wd = model.forward_device(crops, "landmarks", n_points=self.n_points, thresh=self.thresh), None
+        else:
+            rec = model.forward_device(crops, "landmark_stats", n_points=self.n_points, thresh=self.thresh)
+            lm, wd = rec[..., :2], rec[..., 2]
+        lm_frame, m_align, _, _, _ = alignment.track_step_device(
+            lm, self.m_crop, self.boxes, (model.output_height, model.output_width), (ih, iw), (fh, fw), self.crop_template,
+            self.template, weights=wd, m_next=self.m_crop, boxes_next=self._boxes_spare, status=self.status, **self.limits)
+        aligned = alignment.warp_frames_device(ring, m_align, self.out_size[0], self.out_size[1],
+                                               frame_index_dev=self.frame_slots, boxes_dev=self.boxes, samples=self.samples,
+                                               fmt=self.aligned_format, src=self.frame_format)
+        self.boxes, self._boxes_spare = self._boxes_spare, self.boxes
+        return aligned, m_align, lm_frame, self.status
+
+    def lost(self):
+        """The slots whose status is not 0, as a host list: the one call of the tracker that synchronises.  The caller
+        re-seeds them from its detector (or leaves them empty)."""
+        self._state()
+        return [int(v) for v in (self.status != 0).nonzero().flatten().tolist()]

@@ -613,6 +613,108 @@ int flm_warp_affine_frames_src(flm_stream_t stream, const uint8_t* frames_dev, s
                                int wd, int samples, const flm_image_format* fmt /* NULL = float32 NHWC BGR */,
                                const flm_frame_format* src);
 
+/* ---- tracking: the next frame's crop from this frame's landmarks --------------------------------------------------
+ * The stream above starts every frame from detector boxes on the host.  The calls below keep a face's crop on the
+ * device instead: the network input of frame t+1 is cut from the frame by the similarity that takes the landmarks of
+ * frame t onto a template in input pixels (upright, centred, at a fixed scale), sampled by flm_warp_affine_frames_src
+ * with a uint8 NHWC flm_image_format.  A detector is needed to seed a track and to re-seed one that was lost.  Per
+ * face the state is a crop matrix M (float32 [2,3], FRAME px -> network-INPUT px), a box (int32 x0,y0,x1,y1: the frame
+ * region the crop covers; empty = the slot holds no face, and the frame warps fill such a face with zeros) and a status
+ * word.  Everything below is float64, one IEEE operation per written operator, in the written order, no fused
+ * multiply-add; (float) and (double) are the conversions, (float) rounding to nearest even.  "Clipped" is the clip of
+ * flm_landmarks_to_frame: cx0 = min(max(x0,0),fw), cx1 = min(max(x1,0),fw), cy0, cy1 with fh; empty: cx1-cx0 <= 0 or
+ * cy1-cy0 <= 0. */
+enum flm_track_status {      /* bits of a status word; 0 = the face is tracked */
+  FLM_TRACK_DEAD = 1,        /* the incoming box, clipped, is empty: the slot held no face */
+  FLM_TRACK_FEW_POINTS = 2,  /* fewer than min_points landmarks took part in the fit */
+  FLM_TRACK_LOW_SCORE = 4,   /* mean weight of the participating landmarks below min_score */
+  FLM_TRACK_SCALE = 8,       /* the next crop's side in frame px outside [min_side, max_side] */
+  FLM_TRACK_OUTSIDE = 16     /* the next crop's centre lies outside the frame */
+};
+typedef struct flm_track_opts {
+  uint32_t struct_size;      /* as flm_forward_opts: lets the struct grow */
+  int32_t min_points;        /* >= 2 */
+  double min_score, min_side, max_side;
+} flm_track_opts;
+/* min_points = 2, min_score = 0, min_side = 0, max_side = +inf: only the geometric tests can lose a track. */
+void flm_track_opts_init(flm_track_opts* opts);
+
+/* flm_track_seed: detector boxes (squared by the host-side box maths, as for flm_crop_resize) -> crop matrices.
+ *   bw = x1-x0, bh = y1-y0;  sx = (double)in_w / (double)bw;  sy = (double)in_h / (double)bh
+ *   M = [[(float)sx, 0, (float)((0.5 - (double)x0)*sx - 0.5)], [0, (float)sy, (float)((0.5 - (double)y0)*sy - 0.5)]]
+ * -- the pixel-centre convention of the resize that flm_crop_resize restates: input pixel xd samples the frame at
+ * x0 + (xd+0.5)/sx - 0.5.  status = 0.  A box that is empty after clipping gives the identity matrix and
+ * status = FLM_TRACK_DEAD.  (For a box inside the frame and no smaller than the input the uint8 warp with M samples
+ * where flm_crop_resize samples; float bilinear against 11-bit fixed-point weights can differ by one in a pixel's
+ * value.  A smaller box is enlarged: its outermost input pixels sample up to half a source pixel beyond the box, where
+ * flm_crop_resize replicates the box's edge and the warp reads the frame.)
+ * Errors: null pointer -> FLM_ERR_ARG; FLM_ERR_SHAPE unless 1 <= k <= 65535 and in_h, in_w, fh, fw >= 1. */
+int flm_track_seed(flm_stream_t stream, const int32_t* boxes_dev /*[K,4]*/, int k, int in_h, int in_w, int fh, int fw,
+                   float* m_dev /*[K,2,3]*/, int32_t* status_dev /*[K]*/);
+
+/* flm_landmarks_from_crop: landmarks on the model's output grid -> frame pixels through a crop matrix; the affine
+ * counterpart of flm_landmarks_to_frame.  Point i of face f is the two doubles at lm_dev + (f*c + i)*lm_stride (2 for
+ * plain landmarks, FLM_LANDMARK_REC for landmark records, as the weighted fit reads them); sx = in_w/grid_w and
+ * sy = in_h/grid_h take grid px to input px; out_dev is dense float64 [K,C,2] and must not overlap lm_dev.
+ *   per face:   m00..m12 = (double) of the six floats;  det = m00*m11 - m01*m10
+ *   per point:  xi = x*sx;  yi = y*sy;  u = xi - m02;  v = yi - m12
+ *               xf = (m11*u - m01*v) / det;   yf = (m00*v - m10*u) / det
+ * A point is written as (-1,-1) when the decode rejected it (x < 0 or y < 0), when xf or yf is negative or not finite
+ * (a rotated crop may reach past the frame's edge: "negative means rejected" holds in frame px too), and -- every
+ * point of the face -- when det is zero or not finite.
+ * The warp that cut the crop inverts M in float32 (csrc/flm_misc.hip states it), this call inverts it in float64: on
+ * a 1080p frame the two positions of one input pixel differ at the 1e-4 px level.
+ * Errors: null pointer -> FLM_ERR_ARG; FLM_ERR_SHAPE unless 1 <= k <= 65535, 1 <= c <= 1024, lm_stride >= 2 and
+ * sx, sy > 0. */
+int flm_landmarks_from_crop(flm_stream_t stream, const double* lm_dev, size_t lm_stride, const float* m_dev /*[K,2,3]*/,
+                            int k, int c, double sx, double sy, double* out_dev /*[K,C,2]*/);
+
+/* flm_track_step: everything between the forward of frame t and the two warps that follow it, in ONE launch (a
+ * workgroup of one wave per face).
+ * In:  lm_dev at lm_stride and w_dev at w_stride (NULL = unit weights), as flm_similarity_from_landmarks_weighted takes
+ *      them; m_crop_dev [K,2,3] and boxes_dev [K,4], the matrices and boxes this frame's crops were cut with; sx, sy as
+ *      above; tmpl_crop_dev float64 [C,2] in input px, where the landmarks should sit in the NEXT crop; tmpl_align_dev
+ *      float64 [C,2] in aligned px (NULL together with m_align_dev: no aligned fit); opts (NULL = the defaults).
+ * Out: lm_frame_dev float64 [K,C,2]; m_align_dev float32 [K,2,3] frame px -> aligned px; m_next_dev float32 [K,2,3]
+ *      frame px -> input px of the next crop (may be m_crop_dev); boxes_next_dev int32 [K,4] (may be boxes_dev);
+ *      status_dev int32 [K].  No other overlap of an output with an input or another output is allowed.
+ * Contract, in this order:
+ *  1. dead = the clipped boxes_dev[f] is empty.  lm_frame = what flm_landmarks_from_crop writes, bit for bit; (-1,-1)
+ *     everywhere for a dead face.
+ *  2. m_align, m_next = what flm_similarity_from_landmarks_weighted writes for lm_frame (stride 2) with these weights,
+ *     sx = sy = 1 and tmpl_align, tmpl_crop, bit for bit.  cnt is that fit's number of participating points and W its
+ *     sequential weight sum (the same for both templates; cnt = 0, W = 0 for a dead face, whose fits are the identity).
+ *  3. status = the OR of
+ *       FLM_TRACK_DEAD        dead
+ *       FLM_TRACK_FEW_POINTS  cnt < min_points
+ *       FLM_TRACK_LOW_SCORE   w_dev given and !(W / (double)cnt >= min_score)            (0/0 = NaN sets it)
+ *       FLM_TRACK_SCALE       a = (double)m_next[0][0], b = (double)m_next[1][0];
+ *                             side = (double)in_w / sqrt(a*a + b*b);  !(side >= min_side && side <= max_side)
+ *       FLM_TRACK_OUTSIDE     the centre ((double)(in_w-1)/2, (double)(in_h-1)/2) taken to the frame by back(), is not
+ *                             inside: !(det finite, det != 0, 0 <= xf <= fw-1 and 0 <= yf <= fh-1)
+ *     every test made on m_next as fitted in 2, whatever the other tests say.  back(x, y), with m00..m12 the floats of
+ *     m_next widened: det = m00*m11 - m01*m10; u = x - m02; v = y - m12; xf = (m11*u - m01*v)/det;
+ *     yf = (m00*v - m10*u)/det -- the formula of flm_landmarks_from_crop.
+ *  4. status == 0: with back() of the corner centres (0,0), (in_w-1,0), (0,in_h-1), (in_w-1,in_h-1), in that order,
+ *       mn = first; mn = (next < mn) ? next : mn; ... likewise mx with >, per coordinate
+ *       boxes_next = ((int32)cl(floor(mnx)), (int32)cl(floor(mny)), (int32)cl(ceil(mxx) + 1.0), (int32)cl(ceil(mxy) + 1.0))
+ *       cl(t) = min(max(t, -2^30), 2^30)
+ *     -- the crop's bounding box in the frame; it holds the centre, which is inside, so its clip is never empty.
+ *  5. status != 0, the track is lost: boxes_next = (0,0,0,0) and m_next is the identity; m_align keeps the fit of 2
+ *     (the identity for a dead face).  The empty box makes the slot dead at the next step, and harmless: the frame
+ *     warps fill a face whose clipped box is empty with zeros, and its matrix is finite.
+ * Errors, all found before anything is launched: a null lm, m_crop, boxes, tmpl_crop, lm_frame, m_next, boxes_next or
+ * status, m_align_dev without tmpl_align_dev or the reverse, a struct_size smaller than this library's ("struct_size"
+ * in the message), min_points < 2, or a NaN min_score, min_side or max_side -> FLM_ERR_ARG.  FLM_ERR_SHAPE, the limit
+ * named in flm_last_error(), unless 1 <= k <= 65535, 1 <= c <= 1024, lm_stride >= 2, w_stride >= 1, sx, sy > 0 and
+ * in_h, in_w, fh, fw >= 1. */
+int flm_track_step(flm_stream_t stream, const double* lm_dev, size_t lm_stride, const double* w_dev, size_t w_stride,
+                   const float* m_crop_dev /*[K,2,3]*/, const int32_t* boxes_dev /*[K,4]*/, int k, int c, double sx,
+                   double sy, int in_h, int in_w, int fh, int fw, const double* tmpl_crop_dev /*[C,2]*/,
+                   const double* tmpl_align_dev /*[C,2] or NULL*/, const flm_track_opts* opts,
+                   double* lm_frame_dev /*[K,C,2]*/, float* m_align_dev /*[K,2,3] or NULL*/,
+                   float* m_next_dev /*[K,2,3]*/, int32_t* boxes_next_dev /*[K,4]*/, int32_t* status_dev /*[K]*/);
+
 #ifdef __cplusplus
 }
 #endif
