@@ -45,6 +45,7 @@ EXPORTS = [
     "flm_frame_format_init", "flm_frame_format_bytes", "flm_frames_to_bgr", "flm_crop_resize_frames_src",
     "flm_warp_affine_frames_src",
     "flm_track_opts_init", "flm_track_seed", "flm_landmarks_from_crop", "flm_track_step",
+    "flm_track_filter_init", "flm_track_step_filtered",
 ]
 
 
@@ -114,6 +115,21 @@ class TrackOpts(C.Structure):
         o.min_score = float(min_score)
         o.min_side = float(min_side)
         o.max_side = float(max_side)
+        return o
+
+
+class TrackFilter(C.Structure):
+    """flm_track_filter: the One-Euro filter of flm_track_step_filtered (include/flm.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("min_cutoff", C.c_double), ("beta", C.c_double),
+                ("d_cutoff", C.c_double)]
+
+    @classmethod
+    def make(cls, min_cutoff=1.0, beta=15.0, d_cutoff=1.0):
+        o = cls()
+        load().flm_track_filter_init(C.byref(o))
+        o.min_cutoff = float(min_cutoff)
+        o.beta = float(beta)
+        o.d_cutoff = float(d_cutoff)
         return o
 
 
@@ -256,6 +272,10 @@ def _declare(lib):
     lib.flm_track_step.restype = i
     lib.flm_track_step.argtypes = [vp, vp, sz, vp, sz, vp, vp, i, i, d, d, i, i, i, i, vp, vp, C.POINTER(TrackOpts),
                                    vp, vp, vp, vp, vp]
+    lib.flm_track_filter_init.restype = None
+    lib.flm_track_filter_init.argtypes = [C.POINTER(TrackFilter)]
+    lib.flm_track_step_filtered.restype = i
+    lib.flm_track_step_filtered.argtypes = lib.flm_track_step.argtypes + [C.POINTER(TrackFilter), d, vp, vp]
 
 
 def load():

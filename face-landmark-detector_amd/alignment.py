@@ -541,9 +541,41 @@ def landmarks_from_crop_device(lm, m, grid_hw, in_hw, out=None):
     return out
 
 
+class LandmarkFilter:
+    """The One-Euro filter of flm_track_step_filtered (include/flm.h): a low-pass on every tracked landmark whose cutoff
+    is min_cutoff [Hz] at rest and rises by beta per crop side and second of speed; d_cutoff [Hz] smooths the velocity;
+    fps gives the time step 1/fps where a caller names none.  min_cutoff may be +inf: no smoothing.  The defaults keep
+    the lag of a moving point below side/(2 pi beta) = 1.06 % of the crop side and pass 0.31 of white noise at rest."""
+
+    def __init__(self, min_cutoff=1.0, beta=15.0, d_cutoff=1.0, fps=30.0):
+        import math
+        min_cutoff, beta, d_cutoff, fps = float(min_cutoff), float(beta), float(d_cutoff), float(fps)
+        if not min_cutoff > 0.0:
+            raise ValueError("min_cutoff must be > 0 (+inf switches the smoothing off), got %r" % min_cutoff)
+        if not (beta >= 0.0 and math.isfinite(beta)):
+            raise ValueError("beta must be finite and >= 0, got %r" % beta)
+        if not (d_cutoff > 0.0 and math.isfinite(d_cutoff)):
+            raise ValueError("d_cutoff must be finite and > 0, got %r" % d_cutoff)
+        if not (fps > 0.0 and math.isfinite(fps)):
+            raise ValueError("fps must be finite and > 0, got %r" % fps)
+        self.min_cutoff, self.beta, self.d_cutoff, self.fps = min_cutoff, beta, d_cutoff, fps
+
+    def time_step(self, dt=None):
+        """dt in seconds, checked; 1/fps for None."""
+        import math
+        dt = 1.0 / self.fps if dt is None else float(dt)
+        if not (dt > 0.0 and math.isfinite(dt)):
+            raise ValueError("dt must be finite and > 0, got %r" % dt)
+        return dt
+
+    def __repr__(self):
+        return "LandmarkFilter(min_cutoff=%r, beta=%r, d_cutoff=%r, fps=%r)" % (self.min_cutoff, self.beta, self.d_cutoff,
+                                                                                 self.fps)
+
+
 def track_step_device(lm, m_crop, boxes_dev, grid_hw, in_hw, frame_hw, tmpl_crop, tmpl_align=None, weights=None,
                       min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"), lm_frame=None, m_align=None,
-                      m_next=None, boxes_next=None, status=None):
+                      m_next=None, boxes_next=None, status=None, filter=None, dt=None, state=None, lm_raw=None):
     """The per-frame update of a set of tracks in one launch (flm_track_step; include/flm.h states it line by line).
 
     lm: CUDA float64 [K,C,2] on the output grid and `weights`: None or CUDA float64 [K,C] (both may be views of a
@@ -553,10 +585,30 @@ def track_step_device(lm, m_crop, boxes_dev, grid_hw, in_hw, frame_hw, tmpl_crop
     Returns (lm_frame float64 [K,C,2] frame px, m_align float32 [K,2,3] frame px -> aligned px or None, m_next float32
     [K,2,3] frame px -> input px of the next crop, boxes_next int32 [K,4], status int32 [K]: 0 or TRACK_* bits; a lost
     track has an empty box and the identity as m_next).  The five keyword tensors name where to write; `m_next` may be
-    `m_crop` and `boxes_next` may be `boxes_dev`."""
+    `m_crop` and `boxes_next` may be `boxes_dev`.
+
+    filter: None, or a `LandmarkFilter`: the landmarks pass through its One-Euro filter inside the same launch
+    (flm_track_step_filtered), and lm_frame, both fits, the status and the box are those of the filtered points.  Then
+    `state` is the CUDA float64 [K,C,6] filter state, read and written (filled with -1: no history), `dt` the seconds
+    since the previous step (None: 1/filter.fps), and `lm_raw`, if given, a CUDA float64 [K,C,2] tensor that receives
+    the unfiltered points."""
     import torch
+    if filter is None:
+        if dt is not None or state is not None or lm_raw is not None:
+            raise ValueError("dt, state and lm_raw go with filter")
+    else:                           # (the filter's own arguments first: they need no tensor to be judged)
+        if not isinstance(filter, LandmarkFilter):
+            raise ValueError("filter must be None or a LandmarkFilter (got %r)" % (filter,))
+        dt = filter.time_step(dt)
+        if (not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or state.dim() != 3
+                or int(state.shape[2]) != 6):
+            raise ValueError("state must be a contiguous CUDA float64 [K,C,6] tensor")
     lm, ls = _strided_points(lm)
     k, c = int(lm.shape[0]), int(lm.shape[1])
+    if filter is not None:
+        _check_out(state, torch.float64, (k, c, 6), "state")
+        if lm_raw is not None:
+            _check_out(lm_raw, torch.float64, (k, c, 2), "lm_raw")
     _check_matrices(m_crop, k, "m_crop")
     _check_boxes(boxes_dev, k)
     gh, gw = _sizes(grid_hw, "grid_hw")
@@ -603,10 +655,15 @@ def track_step_device(lm, m_crop, boxes_dev, grid_hw, in_hw, frame_hw, tmpl_crop
         _check_out(status, torch.int32, (k,), "status")
     if k and c:
         opts = _lib.TrackOpts.make(min_points, min_score, min_side, max_side)
-        _lib.check(_lib.load().flm_track_step(
-            _lib.stream_ptr(), _lib.ptr(lm), ls, None if weights is None else _lib.ptr(weights), wst, _lib.ptr(m_crop),
-            _lib.ptr(boxes_dev), k, c, iw / gw, ih / gh, ih, iw, fh, fw, _lib.ptr(tmpl_crop),
-            None if tmpl_align is None else _lib.ptr(tmpl_align), _lib.C.byref(opts), _lib.ptr(lm_frame),
-            None if m_align is None else _lib.ptr(m_align), _lib.ptr(m_next), _lib.ptr(boxes_next), _lib.ptr(status)),
-            "flm_track_step")
+        args = (_lib.stream_ptr(), _lib.ptr(lm), ls, None if weights is None else _lib.ptr(weights), wst, _lib.ptr(m_crop),
+                _lib.ptr(boxes_dev), k, c, iw / gw, ih / gh, ih, iw, fh, fw, _lib.ptr(tmpl_crop),
+                None if tmpl_align is None else _lib.ptr(tmpl_align), _lib.C.byref(opts), _lib.ptr(lm_frame),
+                None if m_align is None else _lib.ptr(m_align), _lib.ptr(m_next), _lib.ptr(boxes_next), _lib.ptr(status))
+        if filter is None:
+            _lib.check(_lib.load().flm_track_step(*args), "flm_track_step")
+        else:
+            fo = _lib.TrackFilter.make(filter.min_cutoff, filter.beta, filter.d_cutoff)
+            _lib.check(_lib.load().flm_track_step_filtered(*args, _lib.C.byref(fo), dt, _lib.ptr(state),
+                                                           None if lm_raw is None else _lib.ptr(lm_raw)),
+                       "flm_track_step_filtered")
     return lm_frame, m_align, m_next, boxes_next, status

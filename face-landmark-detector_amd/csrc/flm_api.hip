@@ -1176,37 +1176,104 @@ int flm_landmarks_from_crop(flm_stream_t stream, const double* lm, size_t lm_str
   return launch_landmarks_from_crop(static_cast<hipStream_t>(stream), lm, lm_stride, m, k, c, sx, sy, out);
 }
 
+// The argument checks flm_track_step and flm_track_step_filtered share; *opts is replaced by `defaults` when null.
+static int check_track_step_args(const char* who, const double* lm, const float* m_crop, const int32_t* boxes,
+                                 const double* tmpl_crop, const double* tmpl_align, const flm_track_opts** opts,
+                                 flm_track_opts* defaults, const double* lm_frame, const float* m_align,
+                                 const float* m_next, const int32_t* boxes_next, const int32_t* status) {
+  if (!lm || !m_crop || !boxes || !tmpl_crop || !lm_frame || !m_next || !boxes_next || !status) {  // (wt is optional)
+    set_error("%s: null argument", who);
+    return FLM_ERR_ARG;
+  }
+  if ((tmpl_align == nullptr) != (m_align == nullptr)) {
+    set_error("%s: tmpl_align_dev and m_align_dev go together (both or neither)", who);
+    return FLM_ERR_ARG;
+  }
+  flm_track_opts_init(defaults);
+  if (!*opts) *opts = defaults;
+  const flm_track_opts* o = *opts;
+  if (o->struct_size < sizeof(flm_track_opts)) {
+    set_error("%s: flm_track_opts struct_size %u is smaller than this library's %zu (initialise with "
+              "flm_track_opts_init)", who, o->struct_size, sizeof(flm_track_opts));
+    return FLM_ERR_ARG;
+  }
+  if (o->min_points < 2) {
+    set_error("%s: min_points=%d, needs min_points >= 2 (a similarity takes two points)", who, o->min_points);
+    return FLM_ERR_ARG;
+  }
+  if (std::isnan(o->min_score) || std::isnan(o->min_side) || std::isnan(o->max_side)) {
+    set_error("%s: min_score, min_side and max_side must not be NaN (got %g, %g, %g)", who, o->min_score, o->min_side,
+              o->max_side);
+    return FLM_ERR_ARG;
+  }
+  return FLM_OK;
+}
+
 int flm_track_step(flm_stream_t stream, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
                    const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h, int in_w,
                    int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
                    double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status) {
-  if (!lm || !m_crop || !boxes || !tmpl_crop || !lm_frame || !m_next || !boxes_next || !status) {  // (wt is optional)
-    set_error("flm_track_step: null argument");
-    return FLM_ERR_ARG;
-  }
-  if ((tmpl_align == nullptr) != (m_align == nullptr)) {
-    set_error("flm_track_step: tmpl_align_dev and m_align_dev go together (both or neither)");
-    return FLM_ERR_ARG;
-  }
   flm_track_opts defaults;
-  flm_track_opts_init(&defaults);
-  if (!opts) opts = &defaults;
-  if (opts->struct_size < sizeof(flm_track_opts)) {
-    set_error("flm_track_step: flm_track_opts struct_size %u is smaller than this library's %zu (initialise with "
-              "flm_track_opts_init)", opts->struct_size, sizeof(flm_track_opts));
+  if (const int rc = check_track_step_args("flm_track_step", lm, m_crop, boxes, tmpl_crop, tmpl_align, &opts, &defaults,
+                                           lm_frame, m_align, m_next, boxes_next, status))
+    return rc;
+  return launch_track_step(static_cast<hipStream_t>(stream), lm, lm_stride, wt, w_stride, m_crop, boxes, k, c, sx, sy, in_h,
+                           in_w, fh, fw, tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next, status,
+                           nullptr, 0.0, nullptr, nullptr);
+}
+
+void flm_track_filter_init(flm_track_filter* filt) {
+  if (!filt) return;
+  filt->struct_size = (uint32_t)sizeof(flm_track_filter);
+  filt->reserved = 0;
+  filt->min_cutoff = 1.0;
+  filt->beta = 15.0;
+  filt->d_cutoff = 1.0;
+}
+
+int flm_track_step_filtered(flm_stream_t stream, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
+                            const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h,
+                            int in_w, int fh, int fw, const double* tmpl_crop, const double* tmpl_align,
+                            const flm_track_opts* opts, double* lm_frame, float* m_align, float* m_next,
+                            int32_t* boxes_next, int32_t* status, const flm_track_filter* filt, double dt, double* state,
+                            double* lm_raw) {
+  const char* who = "flm_track_step_filtered";
+  flm_track_opts defaults;
+  if (const int rc = check_track_step_args(who, lm, m_crop, boxes, tmpl_crop, tmpl_align, &opts, &defaults, lm_frame,
+                                           m_align, m_next, boxes_next, status))
+    return rc;
+  if (!filt || !state) {  // (lm_raw is optional)
+    set_error("%s: null %s", who, !filt ? "filt" : "state_dev");
     return FLM_ERR_ARG;
   }
-  if (opts->min_points < 2) {
-    set_error("flm_track_step: min_points=%d, needs min_points >= 2 (a similarity takes two points)", opts->min_points);
+  if (filt->struct_size < sizeof(flm_track_filter)) {
+    set_error("%s: flm_track_filter struct_size %u is smaller than this library's %zu (initialise with "
+              "flm_track_filter_init)", who, filt->struct_size, sizeof(flm_track_filter));
     return FLM_ERR_ARG;
   }
-  if (std::isnan(opts->min_score) || std::isnan(opts->min_side) || std::isnan(opts->max_side)) {
-    set_error("flm_track_step: min_score, min_side and max_side must not be NaN (got %g, %g, %g)", opts->min_score,
-              opts->min_side, opts->max_side);
+  if (filt->reserved != 0) {
+    set_error("%s: flm_track_filter reserved=%u, must be 0", who, filt->reserved);
+    return FLM_ERR_ARG;
+  }
+  if (!(filt->min_cutoff > 0.0)) {
+    set_error("%s: min_cutoff=%g, needs min_cutoff > 0 (+inf switches the smoothing off)", who, filt->min_cutoff);
+    return FLM_ERR_ARG;
+  }
+  if (!(filt->beta >= 0.0 && std::isfinite(filt->beta))) {
+    set_error("%s: beta=%g, needs a finite beta >= 0", who, filt->beta);
+    return FLM_ERR_ARG;
+  }
+  if (!(filt->d_cutoff > 0.0 && std::isfinite(filt->d_cutoff))) {
+    set_error("%s: d_cutoff=%g, needs a finite d_cutoff > 0", who, filt->d_cutoff);
+    return FLM_ERR_ARG;
+  }
+  if (!(dt > 0.0 && std::isfinite(dt))) {
+    set_error("%s: dt=%g, needs a finite dt > 0 (seconds since the previous step)", who, dt);
     return FLM_ERR_ARG;
   }
   return launch_track_step(static_cast<hipStream_t>(stream), lm, lm_stride, wt, w_stride, m_crop, boxes, k, c, sx, sy, in_h,
-                           in_w, fh, fw, tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next, status);
+                           in_w, fh, fw, tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next, status, filt,
+                           dt, state, lm_raw);
 }
 
 }  // extern "C"

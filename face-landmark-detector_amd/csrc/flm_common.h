@@ -284,7 +284,8 @@ int launch_landmarks_from_crop(hipStream_t s, const double* lm, size_t lm_stride
 int launch_track_step(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
                       const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h, int in_w,
                       int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
-                      double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status);
+                      double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status,
+                      const flm_track_filter* filt /*null = flm_track_step*/, double dt, double* state, double* lm_raw);
 
 // Bijective XCD-aware remap of a 1-D grid: blocks that the dispatcher deals to the same XCD
 // (b % 8) receive consecutive logical ids, so neighbours in logical order share an L2.

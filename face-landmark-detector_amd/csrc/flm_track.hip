@@ -105,6 +105,10 @@ struct TrackStepArgs {
   float* m_next;
   int32_t* boxes_next;
   int32_t* status;
+  // the One-Euro filter of flm_track_step_filtered; read by the filtered instantiation alone
+  double min_cutoff, beta, d_cutoff, dt;
+  double* state;   // [K,C,6]
+  double* lm_raw;  // [K,C,2] or null
 };
 
 __device__ __forceinline__ int box_coord(double t) {
@@ -112,6 +116,40 @@ __device__ __forceinline__ int box_coord(double t) {
   return (int)fmin(fmax(t, -lim), lim);
 }
 
+// One point's six doubles of filter state (flm_track_step_filtered), in registers.
+struct EuroState {
+  double xh, yh, vx, vy, xr, yr;
+};
+// One point through the One-Euro filter of the header: (x, y) is the raw point in frame px, s its state as read; (x, y)
+// leaves as what the fits and lm_frame get, s as the state to write back.
+__device__ __forceinline__ void one_euro_point(const TrackStepArgs& g, double side, double& x, double& y, EuroState& s) {
+  const double TWO_PI = 6.283185307179586;
+  const double xraw = x, yraw = y;
+  if (xraw < 0.0) {  // rejected (landmark_back writes exactly (-1,-1)): the point's history ends
+    s.xh = -1.0; s.yh = -1.0; s.vx = 0.0; s.vy = 0.0; s.xr = -1.0; s.yr = -1.0;
+    return;
+  }
+  const bool hist = s.xh >= 0.0 && s.yh >= 0.0 && __builtin_isfinite(s.xh) && __builtin_isfinite(s.yh) &&
+                    __builtin_isfinite(s.vx) && __builtin_isfinite(s.vy) && __builtin_isfinite(s.xr) &&
+                    __builtin_isfinite(s.yr);
+  double nvx = 0.0, nvy = 0.0;
+  if (hist) {
+    const double rx = (xraw - s.xr) / g.dt, ry = (yraw - s.yr) / g.dt;
+    const double ad = 1.0 / (1.0 + (1.0 / (TWO_PI * g.d_cutoff)) / g.dt);
+    const double vx1 = ad * rx + (1.0 - ad) * s.vx, vy1 = ad * ry + (1.0 - ad) * s.vy;
+    const double fc = g.min_cutoff + g.beta * (sqrt(vx1 * vx1 + vy1 * vy1) / side);
+    const double a = 1.0 / (1.0 + (1.0 / (TWO_PI * fc)) / g.dt);
+    const double xh1 = a * xraw + (1.0 - a) * s.xh, yh1 = a * yraw + (1.0 - a) * s.yh;
+    if (__builtin_isfinite(xh1) && __builtin_isfinite(yh1) && __builtin_isfinite(vx1) && __builtin_isfinite(vy1)) {
+      x = xh1; y = yh1; nvx = vx1; nvy = vy1;
+    }
+  }
+  s.xh = x; s.yh = y; s.vx = nvx; s.vy = nvy; s.xr = xraw; s.yr = yraw;
+}
+
+// FILT: the staging loop passes every point through the filter before it reaches LDS (flm_track_step_filtered); all
+// that follows the barrier is the same code on the filtered points.
+template <bool FILT>
 __global__ __launch_bounds__(64) void track_step_kernel(const TrackStepArgs g) {
   extern __shared__ __attribute__((aligned(16))) double trk_s[];  // [c][2] frame px, [c][2] x 2 templates, [c] weights
   const int f = blockIdx.x, c = g.c;
@@ -122,14 +160,31 @@ __global__ __launch_bounds__(64) void track_step_kernel(const TrackStepArgs g) {
   const bool dead = box_empty(bx[0], bx[1], bx[2], bx[3], g.fh, g.fw);
   const float* mm = g.m_crop + (size_t)f * 6;
   const Affine crop = make_affine(mm[0], mm[1], mm[2], mm[3], mm[4], mm[5]);
+  double crop_side = 0.0;  // this frame's crop side in frame px: what the filter measures speed in
+  if constexpr (FILT) crop_side = (double)g.in_w / sqrt(crop.m00 * crop.m00 + crop.m10 * crop.m10);
   for (int i = threadIdx.x; i < c; i += 64) {
     const double* q = g.lm + ((size_t)f * c + i) * g.lm_stride;
     double xf = -1.0, yf = -1.0;
     if (!dead) landmark_back(crop, q[0], q[1], g.sx, g.sy, xf, yf);
+    const double xraw = xf, yraw = yf;
+    double* sp = nullptr;
+    EuroState es;
+    if constexpr (FILT) {
+      sp = g.state + ((size_t)f * c + i) * 6;
+      es.xh = sp[0]; es.yh = sp[1]; es.vx = sp[2]; es.vy = sp[3]; es.xr = sp[4]; es.yr = sp[5];
+      one_euro_point(g, crop_side, xf, yf, es);
+    }
     p[2 * i] = xf;
     p[2 * i + 1] = yf;
     g.lm_frame[((size_t)f * c + i) * 2] = xf;
     g.lm_frame[((size_t)f * c + i) * 2 + 1] = yf;
+    if constexpr (FILT) {
+      sp[0] = es.xh; sp[1] = es.yh; sp[2] = es.vx; sp[3] = es.vy; sp[4] = es.xr; sp[5] = es.yr;
+      if (g.lm_raw) {
+        g.lm_raw[((size_t)f * c + i) * 2] = xraw;
+        g.lm_raw[((size_t)f * c + i) * 2 + 1] = yraw;
+      }
+    }
     w[i] = g.wt ? g.wt[((size_t)f * c + i) * g.w_stride] : 1.0;
     tc[2 * i] = g.tmpl_crop[2 * i];
     tc[2 * i + 1] = g.tmpl_crop[2 * i + 1];
@@ -265,9 +320,11 @@ int launch_landmarks_from_crop(hipStream_t s, const double* lm, size_t lm_stride
 int launch_track_step(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
                       const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h, int in_w,
                       int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
-                      double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status) {
-  if (const int rc = check_track_sizes("flm_track_step", k, c, in_h, in_w, fh, fw)) return rc;
-  if (const int rc = check_track_points("flm_track_step", lm_stride, w_stride, sx, sy)) return rc;
+                      double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status,
+                      const flm_track_filter* filt, double dt, double* state, double* lm_raw) {
+  const char* who = filt ? "flm_track_step_filtered" : "flm_track_step";
+  if (const int rc = check_track_sizes(who, k, c, in_h, in_w, fh, fw)) return rc;
+  if (const int rc = check_track_points(who, lm_stride, w_stride, sx, sy)) return rc;
   TrackStepArgs g;
   g.lm = lm; g.lm_stride = lm_stride; g.wt = wt; g.w_stride = w_stride;
   g.m_crop = m_crop; g.boxes = boxes; g.c = c; g.sx = sx; g.sy = sy;
@@ -275,7 +332,15 @@ int launch_track_step(hipStream_t s, const double* lm, size_t lm_stride, const d
   g.tmpl_crop = tmpl_crop; g.tmpl_align = tmpl_align;
   g.min_points = opts->min_points; g.min_score = opts->min_score; g.min_side = opts->min_side; g.max_side = opts->max_side;
   g.lm_frame = lm_frame; g.m_align = m_align; g.m_next = m_next; g.boxes_next = boxes_next; g.status = status;
-  track_step_kernel<<<k, 64, sizeof(double) * 7 * c, s>>>(g);   // (at most 56 KiB: c <= 1024)
+  g.min_cutoff = g.beta = g.d_cutoff = g.dt = 0.0;
+  g.state = nullptr; g.lm_raw = nullptr;
+  if (filt) {
+    g.min_cutoff = filt->min_cutoff; g.beta = filt->beta; g.d_cutoff = filt->d_cutoff; g.dt = dt;
+    g.state = state; g.lm_raw = lm_raw;
+    track_step_kernel<true><<<k, 64, sizeof(double) * 7 * c, s>>>(g);
+  } else {
+    track_step_kernel<false><<<k, 64, sizeof(double) * 7 * c, s>>>(g);   // (at most 56 KiB: c <= 1024)
+  }
   FLM_LAUNCH_CHECK("track_step_kernel");
   return FLM_OK;
 }

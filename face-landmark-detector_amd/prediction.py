@@ -557,14 +557,21 @@ class FaceTracker:
     network-input px: where the landmarks sit in the next crop -- upright, centred, at a fixed scale (default
     `alignment.canonical_template(C, in_h, in_w)`); crop_samples: 1, 2 or 4 samples per axis and crop pixel, for faces
     much larger than the network input; min_points, min_score, min_side, max_side: when a track is given up
-    (flm_track_opts; the defaults leave that to the geometric tests)."""
+    (flm_track_opts; the defaults leave that to the geometric tests); smooth: None, True (the defaults) or an
+    `alignment.LandmarkFilter`: every landmark passes through a One-Euro filter inside the step's own launch, and the
+    returned landmarks, the aligned fit and the next crop are those of the smoothed points.  The tracker then also owns
+    `filter_state` float64 [capacity,C,6]; a seed clears the history of its slots."""
 
     def __init__(self, model, frame_hw, capacity, out_size=(112, 112), template=None, crop_template=None, n_points=4,
                  thresh=0.0, weights=None, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"),
-                 crop_samples=1, samples=1, aligned_format=None, frame_format=None):
+                 crop_samples=1, samples=1, aligned_format=None, frame_format=None, smooth=None):
         import torch
         if weights is not None and weights != "score":
             raise ValueError("weights must be None or \"score\" (got %r)" % (weights,))
+        if smooth is True:
+            smooth = alignment.LandmarkFilter()
+        if smooth is not None and not isinstance(smooth, alignment.LandmarkFilter):
+            raise ValueError("smooth must be None, True or an alignment.LandmarkFilter (got %r)" % (smooth,))
         _aligned_format(aligned_format, False)
         _frame_format(frame_format)
         fh, fw = [int(v) for v in frame_hw]
@@ -595,6 +602,7 @@ class FaceTracker:
                            max_side=float(max_side))
         self.crop_samples, self.samples = crop_samples, samples
         self.aligned_format, self.frame_format = aligned_format, frame_format
+        self.smooth, self.filter_state = smooth, None
         self._crop_format = alignment.AlignedFormat("nhwc", "uint8")
         self._templates = (np.ascontiguousarray(tm, np.float64), np.ascontiguousarray(tc, np.float64))
         self.m_crop = None    # the device state, allocated by the first call that needs it (_state)
@@ -612,6 +620,8 @@ class FaceTracker:
         self.frame_slots = torch.zeros((n,), dtype=torch.int32, device=dev)
         self.status = torch.full((n,), _lib.TRACK_DEAD, dtype=torch.int32, device=dev)
         self.m_crop = torch.eye(2, 3, dtype=torch.float32, device=dev).repeat(n, 1, 1).contiguous()
+        if self.smooth is not None:     # -1: no landmark has a history
+            self.filter_state = torch.full((n, int(self.model.n_classes), 6), -1.0, dtype=torch.float64, device=dev)
 
     def seed(self, slots, boxes):
         """Start (or restart) the tracks `slots` from the detector boxes `boxes` (x0,y0,x1,y1), one per slot: the host
@@ -634,8 +644,10 @@ class FaceTracker:
         self.m_crop.index_copy_(0, idx, m)
         self.boxes.index_copy_(0, idx, bdev)
         self.status.index_copy_(0, idx, st)
+        if self.filter_state is not None:
+            self.filter_state.index_fill_(0, idx, -1.0)
 
-    def step(self, ring, frame_index):
+    def step(self, ring, frame_index, dt=None):
         """One frame for every slot: `ring` is the frame ring (`frame_format` says how it holds its pixels),
         `frame_index` the ring slot of the new frame.  Sequence: the uint8 crop warp with the slots' matrices ->
         model.forward_device -> alignment.track_step_device (landmarks to frame px, the aligned fit, the next crop's
@@ -644,8 +656,12 @@ class FaceTracker:
         status int32 [capacity]); `status` is the tracker's own tensor, overwritten by the next step or seed.  A slot
         without a face returns zero crops and zero aligned faces, the identity and TRACK_DEAD; a track lost in this
         frame still returns this frame's aligned face, with the reason in its status, and is dead from the next step
-        on."""
+        on.  `dt`, for a tracker that smooths: the seconds since the previous step, a host number (None: 1/fps of the
+        filter)."""
         fh, fw = self.frame_hw
+        if self.smooth is None and dt is not None:
+            raise ValueError("dt goes with smooth")
+        dt = None if self.smooth is None else self.smooth.time_step(dt)
         if self.frame_format is not None:
             nf, rh, rw, _ = self.frame_format.ring(ring)
         else:
@@ -656,6 +672,7 @@ class FaceTracker:
         if not 0 <= frame_index < nf:
             raise ValueError("frame_index must name a ring slot in [0, %d)" % nf)
         self._state()
+        filt = {} if self.smooth is None else dict(filter=self.smooth, dt=dt, state=self.filter_state)
         model = self.model
         ih, iw = model.input_height, model.input_width
         self.frame_slots.fill_(frame_index)
@@ -669,7 +686,8 @@ class FaceTracker:
             lm, wd = rec[..., :2], rec[..., 2]
         lm_frame, m_align, _, _, _ = alignment.track_step_device(
             lm, self.m_crop, self.boxes, (model.output_height, model.output_width), (ih, iw), (fh, fw), self.crop_template,
-            self.template, weights=wd, m_next=self.m_crop, boxes_next=self._boxes_spare, status=self.status, **self.limits)
+            self.template, weights=wd, m_next=self.m_crop, boxes_next=self._boxes_spare, status=self.status, **self.limits,
+            **filt)
         aligned = alignment.warp_frames_device(ring, m_align, self.out_size[0], self.out_size[1],
                                                frame_index_dev=self.frame_slots, boxes_dev=self.boxes, samples=self.samples,
                                                fmt=self.aligned_format, src=self.frame_format)

@@ -715,6 +715,58 @@ int flm_track_step(flm_stream_t stream, const double* lm_dev, size_t lm_stride, 
                    double* lm_frame_dev /*[K,C,2]*/, float* m_align_dev /*[K,2,3] or NULL*/,
                    float* m_next_dev /*[K,2,3]*/, int32_t* boxes_next_dev /*[K,4]*/, int32_t* status_dev /*[K]*/);
 
+/* flm_track_step_filtered: flm_track_step with a One-Euro filter (Casiez, Roussel, Vogel 2012: a first-order low-pass
+ * whose cutoff rises with the point's speed) on every landmark, inside the same single launch: between step 1 and step 2
+ * of flm_track_step's contract.  The filter runs per landmark in 2-D, in frame px, in float64; speed is the length of
+ * the 2-D velocity (a rolled head is treated like an upright one), measured in CROP SIDES per second (beta means the
+ * same at every face size); the velocity is taken from the previous RAW position, as the authors' implementation does.
+ * State per point, state_dev float64 [K,C,6], read and written: (xh, yh, vx, vy, xr, yr) -- the previous filtered
+ * position, the filtered velocity in px/s, the previous raw position.  A point HAS NO HISTORY when xh < 0, yh < 0 or any
+ * of the six is not finite: a state buffer filled with -1 is a reset.  dt is the time since the previous step in
+ * seconds.  lm_raw_dev float64 [K,C,2] (or NULL) receives the raw points.
+ * Contract: one IEEE float64 operation per written operator, in the written order, nothing fused;
+ * TWO_PI is the double 6.283185307179586.
+ *   raw (x, y) = what step 1 of flm_track_step writes for this point (frame px; (-1,-1) = rejected, or a dead face)
+ *   side       = (double)in_w / sqrt(m00*m00 + m10*m10)        m00, m10 of THIS frame's m_crop, widened
+ *   rejected raw:        out = (-1,-1);  state = (-1,-1,0,0,-1,-1)
+ *   raw ok, no history:  out = (x, y);   state = (x, y, 0, 0, x, y)
+ *   raw ok, history:
+ *     rx = (x - xr) / dt;  ry = (y - yr) / dt
+ *     ad = 1.0 / (1.0 + (1.0 / (TWO_PI * d_cutoff)) / dt)
+ *     vx' = ad*rx + (1.0 - ad)*vx;   vy' = ad*ry + (1.0 - ad)*vy
+ *     fc = min_cutoff + beta * (sqrt(vx'*vx' + vy'*vy') / side)
+ *     a  = 1.0 / (1.0 + (1.0 / (TWO_PI * fc)) / dt)
+ *     xh' = a*x + (1.0 - a)*xh;      yh' = a*y + (1.0 - a)*yh
+ *     xh', yh', vx', vy' all finite:  out = (xh', yh');  state = (xh', yh', vx', vy', x, y)
+ *     otherwise:                      as "no history"
+ * lm_frame = out, lm_raw = raw, and steps 2 to 5 of flm_track_step (both fits, the status tests, the box) run on out.
+ * out is a convex combination of non-negative numbers, so "negative means rejected" still holds in frame px.
+ * Two properties follow from the arithmetic and are part of the contract: when no point has history (the first frame
+ * after a seed), and at every step when min_cutoff = +inf (1/(TWO_PI*inf) = 0, so a = 1 and 1*x + 0*xh = x), the five
+ * outputs of flm_track_step are flm_track_step's, bit for bit.
+ * Defaults (flm_track_filter_init): min_cutoff = 1 Hz, beta = 15, d_cutoff = 1 Hz.  A point moving steadily at v sides/s
+ * lags by side*v / (2 pi (min_cutoff + beta*v)) < side / (2 pi beta): 1.06 % of the crop side at any speed.  At rest and
+ * 30 frames/s a = 0.173: white noise leaves with sqrt(a/(2-a)) = 0.31 of its standard deviation.
+ * state_dev and lm_raw_dev must not overlap each other or any other argument.
+ * Errors, all found before anything is launched: those of flm_track_step; a null filt or state_dev, a struct_size
+ * smaller than this library's or a non-zero reserved -> FLM_ERR_ARG; FLM_ERR_ARG, the field named in flm_last_error(),
+ * unless min_cutoff > 0 (+inf allowed), beta >= 0 and finite, d_cutoff > 0 and finite, dt > 0 and finite. */
+typedef struct flm_track_filter {
+  uint32_t struct_size;      /* as flm_track_opts */
+  uint32_t reserved;         /* 0 */
+  double min_cutoff, beta, d_cutoff;
+} flm_track_filter;
+void flm_track_filter_init(flm_track_filter* filt);   /* min_cutoff = 1.0, beta = 15.0, d_cutoff = 1.0 */
+int flm_track_step_filtered(flm_stream_t stream, const double* lm_dev, size_t lm_stride, const double* w_dev,
+                            size_t w_stride, const float* m_crop_dev /*[K,2,3]*/, const int32_t* boxes_dev /*[K,4]*/,
+                            int k, int c, double sx, double sy, int in_h, int in_w, int fh, int fw,
+                            const double* tmpl_crop_dev /*[C,2]*/, const double* tmpl_align_dev /*[C,2] or NULL*/,
+                            const flm_track_opts* opts, double* lm_frame_dev /*[K,C,2]*/,
+                            float* m_align_dev /*[K,2,3] or NULL*/, float* m_next_dev /*[K,2,3]*/,
+                            int32_t* boxes_next_dev /*[K,4]*/, int32_t* status_dev /*[K]*/,
+                            const flm_track_filter* filt, double dt, double* state_dev /*[K,C,6]*/,
+                            double* lm_raw_dev /*[K,C,2] or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif

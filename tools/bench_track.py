@@ -16,10 +16,24 @@ windows, median and range over the windows; the method of tools/bench_frames_nv1
            the same faces (68 landmarks): three of the launches it replaces -- the status tests and the box have no
            launch of their own to compare with.  Thousands of back-to-back launches per window: the time per call is
            launch-bound, which is the point of fusing.
+  --smooth adds to every stream row
+             S   FaceTracker(smooth=True).step, put back to the seeded state like T (the filter state keeps its
+                 history: every step filters); the same launches as T, the track step with its One-Euro filter
+           and to every fused row flm_track_step_filtered on the same faces.
+  --still N  (instead of the timings) a still scene: one 1080p BGR frame repeated N times with fresh noise of +-2 grey
+           levels on every repeat, 8 faces, bf16; a tracker with smooth=True and one without follow it from the same
+           seed, twice: in closed loop (every crop placed by the landmarks before it), and with the crop held (matrices
+           and boxes put back to the seeded state before every step, as in the stream rows: the decode's answer to the
+           pixel noise on a fixed crop is then the filter's only input).  Reports, over the repeats after the first 10
+           and over the tracks both trackers kept throughout, the standard deviation over time of the landmarks (frame
+           px) and of the entries of m_align (its translation in aligned px), filtered against unfiltered, and how
+           many tracks were alive after 1, 2, 5, ... repeats (with random weights the closed loop loses them).
 
 Prints one JSON line, and writes it to --out.
 
     python tools/bench_track.py --out profiles/track_step.json
+    python tools/bench_track.py --smooth --out profiles/track_step_smooth.json
+    python tools/bench_track.py --still 200 --out profiles/track_still.json
 """
 import argparse
 import json
@@ -89,33 +103,44 @@ def alternate(variants, rounds, window_ms):
     return res
 
 
-def stream(model, ring, ff, k, rounds, window_ms, samples):
+def stream(model, ring, ff, k, rounds, window_ms, samples, smooth=False):
     faces = boxes_for(k, 11 + k)
     tr = prediction.FaceTracker(model, (FH, FW), k, out_size=(OUT, OUT), samples=samples, frame_format=ff)
     tr.seed(range(k), faces)
     m0, b0 = tr.m_crop.clone(), tr.boxes.clone()
     state = {"t": 0}
 
-    def t():
-        tr.m_crop.copy_(m0)
-        tr.boxes.copy_(b0)
-        state["t"] += 1
-        return tr.step(ring, state["t"] % 8)
+    def stepper(tracker):
+        def fn():
+            tracker.m_crop.copy_(m0)
+            tracker.boxes.copy_(b0)
+            state["t"] += 1
+            return tracker.step(ring, state["t"] % 8)
+        return fn
+
+    t = stepper(tr)
 
     def a():
         state["t"] += 1
         return prediction.align_frames(ring, [faces], model, out_size=(OUT, OUT), n_points=4, frame_index=[state["t"] % 8],
                                        samples=samples, frame_format=ff)
 
-    res = alternate([("T", t), ("A", a), ("T2", t)], rounds, window_ms)
+    variants = [("T", t), ("A", a), ("T2", t)]
+    if smooth:
+        ts = prediction.FaceTracker(model, (FH, FW), k, out_size=(OUT, OUT), samples=samples, frame_format=ff, smooth=True)
+        ts.seed(range(k), faces)
+        variants.insert(1, ("S", stepper(ts)))
+    res = alternate(variants, rounds, window_ms)
     res["tracked_after_one_step"] = int((t()[3] == 0).sum())
     res["faces"] = k
     res["T_vs_A_ms"] = res["T"]["median_ms"] - res["A"]["median_ms"]
     res["spread_T_vs_T2_ms"] = res["T2"]["median_ms"] - res["T"]["median_ms"]
+    if smooth:
+        res["S_vs_T_ms"] = res["S"]["median_ms"] - res["T"]["median_ms"]
     return res
 
 
-def fused(k, c, rounds, window_ms):
+def fused(k, c, rounds, window_ms, smooth=False):
     rng = np.random.default_rng(3)
     tc = torch.from_numpy(alignment.canonical_template(c, 256, 256)).cuda()
     ta = torch.from_numpy(alignment.canonical_template(c, OUT, OUT)).cuda()
@@ -139,6 +164,16 @@ def fused(k, c, rounds, window_ms):
                                       _lib.ptr(o["m_align"]), _lib.ptr(o["m_next"]), _lib.ptr(o["boxes_next"]),
                                       _lib.ptr(o["status"])), "flm_track_step")
 
+    filt = _lib.TrackFilter.make()
+    fstate = torch.full((k, c, 6), -1.0, dtype=torch.float64, device="cuda")
+
+    def filtered():
+        _lib.check(lib.flm_track_step_filtered(_lib.stream_ptr(), _lib.ptr(lm), 2, _lib.ptr(w), 1, _lib.ptr(m), _lib.ptr(boxes), k,
+                                               c, s, s, 256, 256, FH, FW, _lib.ptr(tc), _lib.ptr(ta), C.byref(opts),
+                                               _lib.ptr(o["lm_frame"]), _lib.ptr(o["m_align"]), _lib.ptr(o["m_next"]),
+                                               _lib.ptr(o["boxes_next"]), _lib.ptr(o["status"]), C.byref(filt), 1.0 / 30.0,
+                                               _lib.ptr(fstate), None), "flm_track_step_filtered")
+
     def three():
         sp = _lib.stream_ptr()
         _lib.check(lib.flm_landmarks_from_crop(sp, _lib.ptr(lm), 2, _lib.ptr(m), k, c, s, s, _lib.ptr(sep_lm)), "from_crop")
@@ -152,10 +187,71 @@ def fused(k, c, rounds, window_ms):
     ok = o["status"] == 0
     if not (torch.equal(o["lm_frame"], sep_lm) and torch.equal(o["m_align"], sep_a) and torch.equal(o["m_next"][ok], sep_n[ok])):
         sys.exit("bench_track: the fused step does not return the separate calls' tensors: nothing is timed")
-    res = alternate([("fused", one), ("three_launches", three), ("fused2", one)], rounds, window_ms)
+    variants = [("fused", one), ("three_launches", three), ("fused2", one)]
+    if smooth:
+        variants.insert(1, ("filtered", filtered))
+    res = alternate(variants, rounds, window_ms)
+    if smooth:
+        res["filtered_vs_fused_ms"] = res["filtered"]["median_ms"] - res["fused"]["median_ms"]
     res.update(faces=k, landmarks=c, tracked=int(ok.sum()),
                fused_vs_three_ms=res["fused"]["median_ms"] - res["three_launches"]["median_ms"],
                spread_fused_vs_fused2_ms=res["fused2"]["median_ms"] - res["fused"]["median_ms"])
+    return res
+
+
+def still(model, n, k, samples, hold, skip=10, seed=17):
+    """The still scene of the module's docstring -> the jitter of both trackers; hold: the crop is held."""
+    g = torch.Generator(device="cuda")
+    g.manual_seed(seed)
+    # a textured frame: blocks of 8 px of random colour under fine grain, so that the bilinear crops have structure
+    coarse = torch.randint(32, 224, (1, 3, FH // 8, FW // 8), device="cuda", generator=g).float()
+    base = torch.nn.functional.interpolate(coarse, size=(FH, FW), mode="bilinear", align_corners=False)[0].permute(1, 2, 0)
+    base = base + torch.randint(-12, 13, (FH, FW, 3), device="cuda", generator=g).float()
+    ring = torch.zeros((8, FH, FW, 3), dtype=torch.uint8, device="cuda")
+    faces = boxes_for(k, 11 + k)
+    trackers = {}
+    for name, smooth in (("filtered", True), ("unfiltered", None)):
+        tr = prediction.FaceTracker(model, (FH, FW), k, out_size=(OUT, OUT), samples=samples, smooth=smooth)
+        tr.seed(range(k), faces)
+        trackers[name] = (tr, [], [], [])
+    m0, b0 = tr.m_crop.clone(), tr.boxes.clone()
+    for r in range(n):
+        noise = torch.randint(-2, 3, (FH, FW, 3), device="cuda", generator=g).float()
+        ring[r % 8] = (base + noise).clamp_(0, 255).to(torch.uint8)
+        for tr, lms, ms, sts in trackers.values():
+            if hold:
+                tr.m_crop.copy_(m0)
+                tr.boxes.copy_(b0)
+            _, m_align, lm, st = tr.step(ring, r % 8)
+            lms.append(lm.clone())
+            ms.append(m_align.clone())
+            sts.append(st.clone())
+    kept = torch.ones((k,), dtype=torch.bool, device="cuda")
+    for _, _, _, sts in trackers.values():
+        kept &= (torch.stack(sts) == 0).all(0)
+    res = {"repeats": n, "skipped": skip, "faces": k, "tracks_kept_by_both": int(kept.sum()), "noise_grey_levels": 2}
+    marks = [r for r in (1, 2, 3, 5, 10, 20, 50, 100, 200, 500, 1000) if r <= n]
+    for name, (_, lms, ms, sts) in trackers.items():
+        alive = (torch.stack(sts) == 0).cumprod(0).sum(1).tolist()
+        res["alive_after_" + name] = {str(r): int(alive[r - 1]) for r in marks}
+    for name, (_, lms, ms, _) in trackers.items():
+        lm = torch.stack(lms[skip:])[:, kept]                  # [T, kept, C, 2]
+        ma = torch.stack(ms[skip:])[:, kept].double()          # [T, kept, 2, 3]
+        row = {}
+        if int(kept.sum()):
+            ok = (lm >= 0).all(0).all(-1)                      # points never rejected
+            sd = lm.std(0)[ok]                                 # [points, 2]
+            row["landmark_std_px_mean"] = float(sd.mean())
+            row["landmark_std_px_median"] = float(sd.median())
+            row["landmark_std_px_max"] = float(sd.max())
+            row["points"] = int(ok.sum())
+            msd = ma.std(0)
+            row["m_align_translation_std_px_mean"] = float(msd[:, :, 2].mean())
+            row["m_align_linear_std_mean"] = float(msd[:, :, :2].mean())
+        res[name] = row
+    if res["filtered"] and res["unfiltered"]:
+        for key in ("landmark_std_px_mean", "m_align_translation_std_px_mean", "m_align_linear_std_mean"):
+            res["ratio_" + key] = res["filtered"][key] / max(res["unfiltered"][key], 1e-300)
     return res
 
 
@@ -167,10 +263,22 @@ def main():
     ap.add_argument("--rounds", type=int, default=5, help="alternating rounds (timed windows per variant)")
     ap.add_argument("--window-ms", type=float, default=250.0, help="least length of one timed window")
     ap.add_argument("--samples", type=int, default=2, help="samples per axis of the aligned warp")
+    ap.add_argument("--smooth", action="store_true", help="add the rows of the smoothing tracker and the filtered step")
+    ap.add_argument("--still", type=int, default=0, metavar="N",
+                    help="instead of the timings: the jitter over N noisy repeats of one frame, filtered against unfiltered")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_track: no GPU visible (there is nothing to measure on a CPU)")
+    if args.still:
+        model = LANDMARKS_MODELS["fcn_8"](68, input_height=256, input_width=256, dtype="bf16")
+        model.load_weights(synth_fcn8_weights(68, seed=2))
+        rec = {"bench": "track_still", "device": torch.cuda.get_device_name(0), "out_size": [OUT, OUT], "frame": [FH, FW],
+               "model": "fcn_8 68 classes 256x256 bf16", "aligned_samples": args.samples,
+               "closed_loop": still(model, args.still, 8, args.samples, False),
+               "held_crop": still(model, args.still, 8, args.samples, True)}
+        emit(rec, args.out)
+        return
     ks = [int(v) for v in args.faces.split(",")]
     rec = {"bench": "track_step", "device": torch.cuda.get_device_name(0), "out_size": [OUT, OUT], "frame": [FH, FW],
            "model": "fcn_8 68 classes 256x256", "aligned_samples": args.samples, "stream": {}, "fused": {}}
@@ -181,16 +289,20 @@ def main():
         for name in args.sources.split(","):
             ring, ff = src[name]
             for k in ks:
-                rec["stream"]["%s_%s_k%d" % (dt, name, k)] = stream(model, ring, ff, k, args.rounds, args.window_ms, args.samples)
+                rec["stream"]["%s_%s_k%d" % (dt, name, k)] = stream(model, ring, ff, k, args.rounds, args.window_ms, args.samples,
+                                                                        args.smooth)
                 print("# %s %s k=%d done" % (dt, name, k), file=sys.stderr, flush=True)
         del model
     for k in ks:
-        rec["fused"]["k%d" % k] = fused(k, 68, args.rounds, args.window_ms)
-    line = json.dumps(rec)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
+        rec["fused"]["k%d" % k] = fused(k, 68, args.rounds, args.window_ms, args.smooth)
+    emit(rec, args.out)
+
+
+def emit(rec, out):
+    print(json.dumps(rec), flush=True)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
             f.write(json.dumps(rec, indent=1) + "\n")
 
 
