@@ -25,6 +25,7 @@ PIX_F32, PIX_F16, PIX_BF16, PIX_U8 = 0, 1, 2, 3      # flm_pixel_type
 FRAME_BGR24, FRAME_NV12 = 0, 1                       # flm_frame_pixel
 YUV_BT601_LIMITED, YUV_BT709_LIMITED = 0, 1          # flm_yuv_matrix
 TRACK_DEAD, TRACK_FEW_POINTS, TRACK_LOW_SCORE, TRACK_SCALE, TRACK_OUTSIDE = 1, 2, 4, 8, 16   # flm_track_status
+TRACK_DUPLICATE, TRACK_UNCONFIRMED = 32, 64          # flm_track_status, set by flm_track_associate alone
 
 EXPORTS = [
     "flm_abi_version", "flm_last_error",
@@ -46,6 +47,7 @@ EXPORTS = [
     "flm_warp_affine_frames_src",
     "flm_track_opts_init", "flm_track_seed", "flm_landmarks_from_crop", "flm_track_step",
     "flm_track_filter_init", "flm_track_step_filtered",
+    "flm_track_assoc_opts_init", "flm_track_associate",
 ]
 
 
@@ -130,6 +132,23 @@ class TrackFilter(C.Structure):
         o.min_cutoff = float(min_cutoff)
         o.beta = float(beta)
         o.d_cutoff = float(d_cutoff)
+        return o
+
+
+class TrackAssocOpts(C.Structure):
+    """flm_track_assoc_opts: how flm_track_associate pairs detections with tracks (include/flm.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_misses", C.c_int32), ("square", C.c_int32), ("reserved", C.c_int32),
+                ("match_iou", C.c_double), ("dup_iou", C.c_double), ("refresh_iou", C.c_double)]
+
+    @classmethod
+    def make(cls, match_iou=0.3, dup_iou=0.7, refresh_iou=0.0, max_misses=0, square=True):
+        o = cls()
+        load().flm_track_assoc_opts_init(C.byref(o))
+        o.match_iou = float(match_iou)
+        o.dup_iou = float(dup_iou)
+        o.refresh_iou = float(refresh_iou)
+        o.max_misses = int(max_misses)
+        o.square = 1 if square else 0
         return o
 
 
@@ -276,6 +295,11 @@ def _declare(lib):
     lib.flm_track_filter_init.argtypes = [C.POINTER(TrackFilter)]
     lib.flm_track_step_filtered.restype = i
     lib.flm_track_step_filtered.argtypes = lib.flm_track_step.argtypes + [C.POINTER(TrackFilter), d, vp, vp]
+    lib.flm_track_assoc_opts_init.restype = None
+    lib.flm_track_assoc_opts_init.argtypes = [C.POINTER(TrackAssocOpts)]
+    lib.flm_track_associate.restype = i
+    lib.flm_track_associate.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, C.POINTER(TrackAssocOpts), vp, vp, vp, vp, vp, vp,
+                                        vp, vp]
 
 
 def load():

@@ -667,3 +667,103 @@ def track_step_device(lm, m_crop, boxes_dev, grid_hw, in_hw, frame_hw, tmpl_crop
                                                            None if lm_raw is None else _lib.ptr(lm_raw)),
                        "flm_track_step_filtered")
     return lm_frame, m_align, m_next, boxes_next, status
+
+
+# ---- association: detector boxes against live tracks (include/flm.h, "association") ----------------------------------
+ASSOC_MAX = 1024      # slots and detections per flm_track_associate call
+
+
+class TrackAssociation:
+    """How flm_track_associate pairs detector boxes with live tracks (include/flm.h): a detection and a track may pair
+    when their IoU is at least match_iou; two live tracks with an IoU of at least dup_iou are one face, and the higher
+    slot ends (above 1: never); a matched pair whose IoU is below refresh_iou restarts the track from the detection
+    (0: never); a track no detection has matched in max_misses consecutive updates ends (0: never); square: the
+    detections pass through the box maths of `prediction.face_boxes` first, as `FaceTracker.seed` does on the host.
+    The defaults are the customary gate of box trackers and a guess; none has been tuned against a trained model."""
+
+    def __init__(self, match_iou=0.3, dup_iou=0.7, refresh_iou=0.0, max_misses=0, square=True):
+        match_iou, dup_iou, refresh_iou = float(match_iou), float(dup_iou), float(refresh_iou)
+        for name, v in (("match_iou", match_iou), ("dup_iou", dup_iou), ("refresh_iou", refresh_iou)):
+            if v != v:
+                raise ValueError("%s must not be NaN" % name)
+        if int(max_misses) != max_misses or int(max_misses) < 0:
+            raise ValueError("max_misses must be an integer >= 0 (0 = never), got %r" % (max_misses,))
+        self.match_iou, self.dup_iou, self.refresh_iou = match_iou, dup_iou, refresh_iou
+        self.max_misses, self.square = int(max_misses), bool(square)
+
+    def struct(self):
+        return _lib.TrackAssocOpts.make(self.match_iou, self.dup_iou, self.refresh_iou, self.max_misses, self.square)
+
+    def __repr__(self):
+        return "TrackAssociation(match_iou=%r, dup_iou=%r, refresh_iou=%r, max_misses=%r, square=%r)" % (
+            self.match_iou, self.dup_iou, self.refresh_iou, self.max_misses, self.square)
+
+
+def track_associate_device(det, m_crop, boxes, status, misses, in_hw, frame_hw, n_det=None, state=None, assoc=None,
+                           det_slot=None, slot_det=None, counts=None):
+    """Detector boxes against the live tracks of a tracker in one launch (flm_track_associate; include/flm.h states it
+    line by line).
+
+    det: CUDA int32 [D,4] boxes (x0,y0,x1,y1), D <= 1024; n_det: None, or a CUDA int32 tensor of one element that says
+    how many rows of `det` are valid.  m_crop CUDA float32 [K,2,3], boxes CUDA int32 [K,4], status and misses CUDA int32
+    [K], and `state`, None or the CUDA float64 [K,C,6] filter state, are the tracker's own tensors, K <= 1024: read and
+    written in place.  assoc: None (the defaults) or a `TrackAssociation`.
+    Returns (det_slot int32 [D]: the slot a detection matched or was born into, -1 for a void or unread row, -2 when no
+    slot was free; slot_det int32 [K]: the detection of a matched or born slot, else -1; counts int32 [8]: matched,
+    born, restarted, duplicates, unconfirmed, dropped, void, 0).  The three keyword tensors name where to write."""
+    import torch
+    if assoc is None:
+        assoc = TrackAssociation()
+    elif not isinstance(assoc, TrackAssociation):
+        raise ValueError("assoc must be None or a TrackAssociation (got %r)" % (assoc,))
+    if not isinstance(det, torch.Tensor) or det.dim() != 2:
+        raise ValueError("det must be a contiguous CUDA int32 [D,4] tensor")
+    d = int(det.shape[0])
+    if (det.dtype != torch.int32 or not det.is_cuda or not det.is_contiguous() or int(det.shape[1]) != 4):
+        raise ValueError("det must be a contiguous CUDA int32 [D,4] tensor")
+    _check_matrices(m_crop, None, "m_crop")
+    k = int(m_crop.shape[0])
+    if not 1 <= d <= ASSOC_MAX or not 1 <= k <= ASSOC_MAX:
+        raise ValueError("track_associate_device takes 1..%d detections and 1..%d slots (got %d, %d)"
+                         % (ASSOC_MAX, ASSOC_MAX, d, k))
+    _check_boxes(boxes, k)
+    _check_out(status, torch.int32, (k,), "status")
+    _check_out(misses, torch.int32, (k,), "misses")
+    if n_det is not None:
+        if (not isinstance(n_det, torch.Tensor) or n_det.dtype != torch.int32 or not n_det.is_cuda or n_det.numel() != 1
+                or not n_det.is_contiguous()):
+            raise ValueError("n_det must be None or a CUDA int32 tensor of one element")
+    c = 1
+    if state is not None:
+        if not isinstance(state, torch.Tensor) or state.dim() != 3:
+            raise ValueError("state must be a contiguous CUDA float64 [K,C,6] tensor")
+        c = int(state.shape[1])
+        _check_out(state, torch.float64, (k, c, 6), "state")
+        if not 1 <= c <= 1024:
+            raise ValueError("state must have 1..1024 landmarks (got %d)" % c)
+    ih, iw = _sizes(in_hw, "in_hw")
+    fh, fw = _sizes(frame_hw, "frame_hw")
+    if fh * fw > 2 ** 30:
+        raise ValueError("frames of %dx%d are outside the association's reach (H*W <= 2^30)" % (fh, fw))
+    tensors = [det, m_crop, boxes, status, misses] + [t for t in (n_det, state) if t is not None]
+    if det_slot is None:
+        det_slot = torch.empty((d,), dtype=torch.int32, device=det.device)
+    else:
+        _check_out(det_slot, torch.int32, (d,), "det_slot")
+    if slot_det is None:
+        slot_det = torch.empty((k,), dtype=torch.int32, device=det.device)
+    else:
+        _check_out(slot_det, torch.int32, (k,), "slot_det")
+    if counts is None:
+        counts = torch.empty((8,), dtype=torch.int32, device=det.device)
+    else:
+        _check_out(counts, torch.int32, (8,), "counts")
+    if any(t.device != det.device for t in tensors + [det_slot, slot_det, counts]):
+        raise ValueError("every tensor of track_associate_device must lie on the device of det")
+    opts = assoc.struct()
+    _lib.check(_lib.load().flm_track_associate(
+        _lib.stream_ptr(), _lib.ptr(det), None if n_det is None else _lib.ptr(n_det), d, k, c, ih, iw, fh, fw,
+        _lib.C.byref(opts), _lib.ptr(m_crop), _lib.ptr(boxes), _lib.ptr(status), _lib.ptr(misses),
+        None if state is None else _lib.ptr(state), _lib.ptr(det_slot), _lib.ptr(slot_det), _lib.ptr(counts)),
+        "flm_track_associate")
+    return det_slot, slot_det, counts

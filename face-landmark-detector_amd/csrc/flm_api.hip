@@ -1276,4 +1276,71 @@ int flm_track_step_filtered(flm_stream_t stream, const double* lm, size_t lm_str
                            dt, state, lm_raw);
 }
 
+// ---- association (flm_track_assoc.hip) ------------------------------------------------------------------------------
+
+void flm_track_assoc_opts_init(flm_track_assoc_opts* opts) {
+  if (!opts) return;
+  opts->struct_size = (uint32_t)sizeof(flm_track_assoc_opts);
+  opts->max_misses = 0;
+  opts->square = 1;
+  opts->reserved = 0;
+  opts->match_iou = 0.3;
+  opts->dup_iou = 0.7;
+  opts->refresh_iou = 0.0;
+}
+
+int flm_track_associate(flm_stream_t stream, const int32_t* det, const int32_t* n_det, int d, int k, int c, int in_h,
+                        int in_w, int fh, int fw, const flm_track_assoc_opts* opts, float* m_crop, int32_t* boxes,
+                        int32_t* status, int32_t* misses, double* state, int32_t* det_slot, int32_t* slot_det,
+                        int32_t* counts) {
+  const char* who = "flm_track_associate";
+  if (!det || !m_crop || !boxes || !status || !misses || !det_slot || !slot_det || !counts) {
+    set_error("%s: null argument", who);  // (n_det_dev, state_dev and opts are optional)
+    return FLM_ERR_ARG;
+  }
+  flm_track_assoc_opts defaults;
+  flm_track_assoc_opts_init(&defaults);
+  if (!opts) opts = &defaults;
+  if (opts->struct_size < sizeof(flm_track_assoc_opts)) {
+    set_error("%s: flm_track_assoc_opts struct_size %u is smaller than this library's %zu (initialise with "
+              "flm_track_assoc_opts_init)", who, opts->struct_size, sizeof(flm_track_assoc_opts));
+    return FLM_ERR_ARG;
+  }
+  if (opts->reserved != 0) {
+    set_error("%s: flm_track_assoc_opts reserved=%d, must be 0", who, opts->reserved);
+    return FLM_ERR_ARG;
+  }
+  if (k < 1 || k > 1024) {
+    set_error("%s: k=%d, needs 1 <= k <= 1024", who, k);
+    return FLM_ERR_SHAPE;
+  }
+  if (d < 1 || d > 1024) {
+    set_error("%s: d=%d, needs 1 <= d <= 1024", who, d);
+    return FLM_ERR_SHAPE;
+  }
+  if (state && (c < 1 || c > 1024)) {
+    set_error("%s: c=%d, needs 1 <= c <= 1024", who, c);
+    return FLM_ERR_SHAPE;
+  }
+  if (in_h < 1 || in_w < 1 || fh < 1 || fw < 1) {
+    set_error("%s: input %dx%d, frame %dx%d, needs in_h, in_w, fh, fw >= 1", who, in_h, in_w, fh, fw);
+    return FLM_ERR_SHAPE;
+  }
+  if ((int64_t)fh * (int64_t)fw > (int64_t(1) << 30)) {
+    set_error("%s: frame %dx%d, needs fh*fw <= 2^30 (the pair order is exact in int64 up to there)", who, fh, fw);
+    return FLM_ERR_SHAPE;
+  }
+  if (opts->max_misses < 0) {
+    set_error("%s: max_misses=%d, needs max_misses >= 0 (0 = never)", who, opts->max_misses);
+    return FLM_ERR_SHAPE;
+  }
+  if (std::isnan(opts->match_iou) || std::isnan(opts->dup_iou) || std::isnan(opts->refresh_iou)) {
+    set_error("%s: match_iou, dup_iou and refresh_iou must not be NaN (got %g, %g, %g)", who, opts->match_iou,
+              opts->dup_iou, opts->refresh_iou);
+    return FLM_ERR_SHAPE;
+  }
+  return launch_track_associate(static_cast<hipStream_t>(stream), det, n_det, d, k, c, in_h, in_w, fh, fw, opts, m_crop,
+                                boxes, status, misses, state, det_slot, slot_det, counts);
+}
+
 }  // extern "C"

@@ -287,6 +287,11 @@ int launch_track_step(hipStream_t s, const double* lm, size_t lm_stride, const d
                       double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status,
                       const flm_track_filter* filt /*null = flm_track_step*/, double dt, double* state, double* lm_raw);
 
+// association (flm_track_assoc.hip); pointers, sizes and the option struct have been checked by the caller
+int launch_track_associate(hipStream_t s, const int32_t* det, const int32_t* n_det, int d, int k, int c, int in_h, int in_w,
+                           int fh, int fw, const flm_track_assoc_opts* opts, float* m_crop, int32_t* boxes, int32_t* status,
+                           int32_t* misses, double* state, int32_t* det_slot, int32_t* slot_det, int32_t* counts);
+
 // Bijective XCD-aware remap of a 1-D grid: blocks that the dispatcher deals to the same XCD
 // (b % 8) receive consecutive logical ids, so neighbours in logical order share an L2.
 __device__ __forceinline__ int xcd_remap(int b, int nblk) {

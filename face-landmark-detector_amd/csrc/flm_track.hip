@@ -1,6 +1,7 @@
 // Tracking: the crop of the next frame from the landmarks of this one (include/flm.h states every operation; the
 // comments here only say how the work is laid out).  float64 throughout, -ffp-contract=off: nothing fuses.
 #include "flm_common.h"
+#include "flm_track_seed_dev.h"
 
 namespace flm {
 
@@ -41,26 +42,16 @@ __device__ __forceinline__ void landmark_back(const Affine& a, double x, double 
   yf = ty;
 }
 
-// ---- flm_track_seed: a thread per face -----------------------------------------------------------------
+// ---- flm_track_seed: a thread per face (the arithmetic: flm_track_seed_dev.h) --------------------------------
 __global__ __launch_bounds__(64) void track_seed_kernel(const int32_t* __restrict__ boxes, int k, int in_h, int in_w,
                                                         int fh, int fw, float* __restrict__ m,
                                                         int32_t* __restrict__ status) {
   const int f = blockIdx.x * 64 + threadIdx.x;
   if (f >= k) return;
   const int x0 = boxes[4 * f + 0], y0 = boxes[4 * f + 1], x1 = boxes[4 * f + 2], y1 = boxes[4 * f + 3];
-  float a = 1.f, d = 1.f, tx = 0.f, ty = 0.f;
-  const bool dead = box_empty(x0, y0, x1, y1, fh, fw);
-  if (!dead) {  // (a box with pixels has x1 > x0 and y1 > y0)
-    const double sx = (double)in_w / (double)(x1 - x0), sy = (double)in_h / (double)(y1 - y0);
-    a = (float)sx;
-    d = (float)sy;
-    tx = (float)((0.5 - (double)x0) * sx - 0.5);
-    ty = (float)((0.5 - (double)y0) * sy - 0.5);
-  }
-  float* o = m + (size_t)f * 6;
-  o[0] = a;   o[1] = 0.f; o[2] = tx;
-  o[3] = 0.f; o[4] = d;   o[5] = ty;
-  status[f] = dead ? FLM_TRACK_DEAD : 0;
+  const TrackSeed sd = track_seed_one(x0, y0, x1, y1, box_empty(x0, y0, x1, y1, fh, fw), in_h, in_w);
+  track_seed_store(sd, m + (size_t)f * 6);
+  status[f] = sd.status;
 }
 
 // ---- flm_landmarks_from_crop: a workgroup (one wave) per face, a thread per point ----------------------------

@@ -560,12 +560,18 @@ class FaceTracker:
     (flm_track_opts; the defaults leave that to the geometric tests); smooth: None, True (the defaults) or an
     `alignment.LandmarkFilter`: every landmark passes through a One-Euro filter inside the step's own launch, and the
     returned landmarks, the aligned fit and the next crop are those of the smoothed points.  The tracker then also owns
-    `filter_state` float64 [capacity,C,6]; a seed clears the history of its slots."""
+    `filter_state` float64 [capacity,C,6]; a seed clears the history of its slots.  associate: None (the defaults) or an
+    `alignment.TrackAssociation`: how `update` pairs the boxes of a detector with the live tracks; the tracker owns
+    `misses` int32 [capacity], the updates in a row that found no detection for a slot."""
 
     def __init__(self, model, frame_hw, capacity, out_size=(112, 112), template=None, crop_template=None, n_points=4,
                  thresh=0.0, weights=None, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"),
-                 crop_samples=1, samples=1, aligned_format=None, frame_format=None, smooth=None):
+                 crop_samples=1, samples=1, aligned_format=None, frame_format=None, smooth=None, associate=None):
         import torch
+        if associate is None:
+            associate = alignment.TrackAssociation()
+        elif not isinstance(associate, alignment.TrackAssociation):
+            raise ValueError("associate must be None or an alignment.TrackAssociation (got %r)" % (associate,))
         if weights is not None and weights != "score":
             raise ValueError("weights must be None or \"score\" (got %r)" % (weights,))
         if smooth is True:
@@ -603,6 +609,7 @@ class FaceTracker:
         self.crop_samples, self.samples = crop_samples, samples
         self.aligned_format, self.frame_format = aligned_format, frame_format
         self.smooth, self.filter_state = smooth, None
+        self.associate = associate
         self._crop_format = alignment.AlignedFormat("nhwc", "uint8")
         self._templates = (np.ascontiguousarray(tm, np.float64), np.ascontiguousarray(tc, np.float64))
         self.m_crop = None    # the device state, allocated by the first call that needs it (_state)
@@ -620,6 +627,7 @@ class FaceTracker:
         self.frame_slots = torch.zeros((n,), dtype=torch.int32, device=dev)
         self.status = torch.full((n,), _lib.TRACK_DEAD, dtype=torch.int32, device=dev)
         self.m_crop = torch.eye(2, 3, dtype=torch.float32, device=dev).repeat(n, 1, 1).contiguous()
+        self.misses = torch.zeros((n,), dtype=torch.int32, device=dev)
         if self.smooth is not None:     # -1: no landmark has a history
             self.filter_state = torch.full((n, int(self.model.n_classes), 6), -1.0, dtype=torch.float64, device=dev)
 
@@ -644,8 +652,45 @@ class FaceTracker:
         self.m_crop.index_copy_(0, idx, m)
         self.boxes.index_copy_(0, idx, bdev)
         self.status.index_copy_(0, idx, st)
+        self.misses.index_fill_(0, idx, 0)
         if self.filter_state is not None:
             self.filter_state.index_fill_(0, idx, -1.0)
+
+    def update(self, detections, n=None):
+        """The boxes of a detector against the tracks, on the device (alignment.track_associate_device with the
+        tracker's `associate`): a detection that overlaps a live track confirms it (and restarts it where the two have
+        drifted apart, if `refresh_iou` says so); of two tracks on one face the higher slot ends with TRACK_DUPLICATE; a
+        track no detection has confirmed in `max_misses` updates ends with TRACK_UNCONFIRMED; every other detection
+        starts a track in the lowest slot that holds none.  `detections`: a CUDA int32 [D,4] tensor (x0,y0,x1,y1) --
+        nothing is transferred; `n`, a CUDA int32 tensor of one element, then says how many of its rows are valid -- or
+        a host list or array of integer boxes: one upload.  Returns CUDA tensors (det_slot int32 [D], slot_det int32
+        [capacity], counts int32 [8]) as `track_associate_device` describes them.  No download, no synchronisation.
+        May be called between any two steps: it edits the matrices and boxes the NEXT step cuts its crops with, not the
+        ones the last aligned warp used."""
+        import torch
+        if self.capacity > alignment.ASSOC_MAX:
+            raise ValueError("update takes a tracker of at most %d slots (capacity %d)" % (alignment.ASSOC_MAX, self.capacity))
+        if isinstance(detections, torch.Tensor):
+            det = detections
+        else:
+            arr = np.asarray(detections)
+            if arr.ndim != 2 or arr.shape[1] != 4 or arr.dtype.kind not in "iu":
+                raise ValueError("update takes a CUDA int32 [D,4] tensor or a list of integer (x0,y0,x1,y1) boxes")
+            if arr.size and (arr.min() < -2 ** 31 or arr.max() >= 2 ** 31):
+                raise ValueError("a box coordinate does not fit int32")
+            det = arr.astype(np.int32)
+        if int(det.shape[0]) > alignment.ASSOC_MAX:
+            raise ValueError("update takes at most %d detections (got %d)" % (alignment.ASSOC_MAX, int(det.shape[0])))
+        if int(det.shape[0]) < 1:
+            raise ValueError("update takes at least one row of detections (n says how many are valid)")
+        if n is not None and not isinstance(n, torch.Tensor):
+            raise ValueError("n must be None or a CUDA int32 tensor of one element")
+        self._state()
+        if not isinstance(det, torch.Tensor):
+            det = torch.from_numpy(np.ascontiguousarray(det)).to(self.boxes.device)
+        return alignment.track_associate_device(det, self.m_crop, self.boxes, self.status, self.misses,
+                                                (self.model.input_height, self.model.input_width), self.frame_hw,
+                                                n_det=n, state=self.filter_state, assoc=self.associate)
 
     def step(self, ring, frame_index, dt=None):
         """One frame for every slot: `ring` is the frame ring (`frame_format` says how it holds its pixels),

@@ -617,7 +617,8 @@ int flm_warp_affine_frames_src(flm_stream_t stream, const uint8_t* frames_dev, s
  * The stream above starts every frame from detector boxes on the host.  The calls below keep a face's crop on the
  * device instead: the network input of frame t+1 is cut from the frame by the similarity that takes the landmarks of
  * frame t onto a template in input pixels (upright, centred, at a fixed scale), sampled by flm_warp_affine_frames_src
- * with a uint8 NHWC flm_image_format.  A detector is needed to seed a track and to re-seed one that was lost.  Per
+ * with a uint8 NHWC flm_image_format.  A detector is needed to seed a track and to re-seed one that was lost
+ * (flm_track_associate, at the end of this section, does both from boxes on the device).  Per
  * face the state is a crop matrix M (float32 [2,3], FRAME px -> network-INPUT px), a box (int32 x0,y0,x1,y1: the frame
  * region the crop covers; empty = the slot holds no face, and the frame warps fill such a face with zeros) and a status
  * word.  Everything below is float64, one IEEE operation per written operator, in the written order, no fused
@@ -629,7 +630,10 @@ enum flm_track_status {      /* bits of a status word; 0 = the face is tracked *
   FLM_TRACK_FEW_POINTS = 2,  /* fewer than min_points landmarks took part in the fit */
   FLM_TRACK_LOW_SCORE = 4,   /* mean weight of the participating landmarks below min_score */
   FLM_TRACK_SCALE = 8,       /* the next crop's side in frame px outside [min_side, max_side] */
-  FLM_TRACK_OUTSIDE = 16     /* the next crop's centre lies outside the frame */
+  FLM_TRACK_OUTSIDE = 16,    /* the next crop's centre lies outside the frame */
+  /* set by flm_track_associate alone (below); flm_track_step never sets them */
+  FLM_TRACK_DUPLICATE = 32,  /* a live track in a lower slot covers the same face */
+  FLM_TRACK_UNCONFIRMED = 64 /* no detection matched the track in max_misses consecutive calls */
 };
 typedef struct flm_track_opts {
   uint32_t struct_size;      /* as flm_forward_opts: lets the struct grow */
@@ -766,6 +770,83 @@ int flm_track_step_filtered(flm_stream_t stream, const double* lm_dev, size_t lm
                             int32_t* boxes_next_dev /*[K,4]*/, int32_t* status_dev /*[K]*/,
                             const flm_track_filter* filt, double dt, double* state_dev /*[K,C,6]*/,
                             double* lm_raw_dev /*[K,C,2] or NULL*/);
+
+/* ---- association: detector boxes against live tracks --------------------------------------------------------------
+ * flm_track_associate: what a tracker does at the moment a detector has run again -- pair its boxes with the live
+ * slots, end the slots that sit on the same face as a lower one, end the slots no detection has confirmed for a while,
+ * and start a track in a free slot for every detection nobody claimed -- in ONE launch of one workgroup, on boxes that
+ * never leave the device.  It edits the state flm_track_step carries from frame to frame (m_crop, boxes, status, and
+ * the filter state of flm_track_step_filtered) plus a miss counter per slot, between any two steps.
+ * Integers only, except the two places marked (F): int32 coordinates, int64 areas and products.
+ * In:  det_dev int32 [D,4] x0,y0,x1,y1; n_det_dev NULL or one int32 on the device (a detector with a fixed output
+ *      buffer says here how many rows it filled); opts (NULL = the defaults).
+ * In/out: m_crop_dev [K,2,3], boxes_dev [K,4], status_dev [K], misses_dev int32 [K], state_dev NULL or float64 [K,C,6].
+ * Out: det_slot_dev int32 [D], slot_det_dev int32 [K], counts_dev int32 [8].  No two arguments may overlap.
+ * Contract, in this order:
+ *  1. nd = n_det_dev ? min(max(*n_det_dev, 0), d) : d.  Rows j >= nd are never read; their det_slot is -1.
+ *  2. Detection j < nd is VOID when a coordinate lies outside [-2^28, 2^28].  Otherwise, with opts->square, it passes
+ *     through the box maths of the reference's detect_marks (what the host does before flm_track_seed):
+ *       off = (int)fabs((double)(y1-y0) * 0.1)                                                              (F)
+ *       y0 += off;  y1 += off;  diff = (y1-y0) - (x1-x0);  delta = |diff| >> 1;  odd = |diff| & 1
+ *       diff > 0:  x0 -= delta;  x1 += delta + odd          diff < 0:  y0 -= delta;  y1 += delta + odd
+ *     (every intermediate stays inside int32).  A detection whose box is then empty after the clip of the tracking
+ *     section is void too.  A void detection takes no part below; its det_slot is -1.
+ *  3. All boxes are clipped first.  area(a) = (int64)(cx1-cx0)*(cy1-cy0); inter(a,b) = the area of the intersection of
+ *     the clipped boxes (0 when they do not overlap); uni = area(a) + area(b) - inter.
+ *       "IoU(a,b) >= t"  means  inter > 0 && (double)inter >= t * (double)uni                               (F)
+ *     -- one float64 multiplication.  ORDER: pair p = (slot, detection) comes before pair q when
+ *     inter_p*uni_q > inter_q*uni_p, exact in int64 (fh*fw <= 2^30 keeps every product below 2^61); on equality the
+ *     lower slot comes first, then the lower detection.
+ *  4. A slot is LIVE when its clipped box is not empty (the test of flm_track_step), whatever its status says.
+ *  5. A live slot t is a DUPLICATE when any live slot s < t has IoU(s,t) >= dup_iou; s counts whether or not it is a
+ *     duplicate itself (no serial dependence).  A duplicate is killed: boxes = (0,0,0,0), m_crop = the identity,
+ *     status |= FLM_TRACK_DUPLICATE, misses = 0, slot_det = -1.
+ *  6. MATCHING, among the live slots that survived 5 and the detections that are not void: over the pairs with
+ *     IoU >= match_iou, in the ORDER of 3, take the first pair, remove its slot and its detection, repeat until no pair
+ *     is left (greedy assignment).
+ *  7. A matched slot t with detection j: slot_det[t] = j, det_slot[j] = t, misses = 0.  If refresh_iou > 0 and NOT
+ *     IoU(t,j) >= refresh_iou the track RESTARTS from the detection: m_crop[t] and status[t] are what flm_track_seed
+ *     writes for the detection's box of 2 (not clipped), boxes[t] is that box, and the slot's C*6 doubles of state_dev
+ *     become -1.0.  Otherwise m_crop, boxes, status and state of the slot are untouched.
+ *  8. A surviving live slot without a detection: slot_det = -1, misses = (int32)((uint32)misses + 1).  If max_misses > 0
+ *     and misses >= max_misses it is killed as in 5 with FLM_TRACK_UNCONFIRMED, and misses = 0.
+ *  9. BIRTHS: the detections that are neither void nor matched, in ascending index, pair off one to one with the slots
+ *     that were not live at entry, in ascending index (a slot killed in this call is not reused in it: its status stays
+ *     readable).  A born slot t with detection j gets m_crop, boxes and status exactly as in the restart of 7
+ *     (status = 0), misses = 0, its state rows -1.0, slot_det[t] = j and det_slot[j] = t.  A detection left without a
+ *     slot gets det_slot = -2.
+ * 10. Everything else is untouched: a slot that was not live at entry and is not born keeps m_crop, boxes, status and
+ *     misses (its slot_det is -1), and the state rows of every slot neither born nor restarted keep their bits.
+ *     counts = { matched (restarted ones included), born, restarted, duplicates, unconfirmed, dropped (det_slot -2),
+ *     void (among the rows j < nd), 0 }.
+ * Defaults (flm_track_assoc_opts_init): max_misses = 0 (never), square = 1, match_iou = 0.3 (the customary gate of box
+ * trackers), dup_iou = 0.7, refresh_iou = 0 (never).  None of them has been tuned against a trained model: a track's
+ * box is the bounding box of a rotated, template-scaled crop square (twice the square's area at 45 degrees of roll),
+ * a detection's box is the detector's square, and how the two overlap for one face has not been measured.
+ * dup_iou > 1 switches 5 off (inter <= uni).
+ * The call allocates nothing, synchronises nothing and makes one launch whatever the data; the matching inside it takes
+ * as many rounds as the data needs (at most min(k, d); DESIGN 4.5f has the time of the worst case).
+ * Errors, all found before anything is launched: a null pointer other than n_det_dev, state_dev and opts, a
+ * struct_size smaller than this library's or a non-zero reserved -> FLM_ERR_ARG.  FLM_ERR_SHAPE, the limit named in
+ * flm_last_error(), unless 1 <= k <= 1024, 1 <= d <= 1024, 1 <= c <= 1024 (read only when state_dev is given),
+ * in_h, in_w, fh, fw >= 1, (int64)fh*fw <= 2^30, max_misses >= 0 and none of the three thresholds is NaN. */
+typedef struct flm_track_assoc_opts {
+  uint32_t struct_size;      /* as flm_track_opts */
+  int32_t max_misses;        /* 0 = never give a track up for want of a detection */
+  int32_t square;            /* 1: detections pass through the reference's box maths first; 0: used as given */
+  int32_t reserved;          /* 0 */
+  double match_iou;          /* a detection and a track may pair when IoU >= match_iou */
+  double dup_iou;            /* two live tracks with IoU >= dup_iou are one face; > 1 = off */
+  double refresh_iou;        /* a matched pair with IoU below it: the track restarts from the detection; 0 = never */
+} flm_track_assoc_opts;
+void flm_track_assoc_opts_init(flm_track_assoc_opts* opts);
+int flm_track_associate(flm_stream_t stream, const int32_t* det_dev /*[D,4]*/, const int32_t* n_det_dev /*NULL or [1]*/,
+                        int d, int k, int c, int in_h, int in_w, int fh, int fw,
+                        const flm_track_assoc_opts* opts /*NULL = defaults*/, float* m_crop_dev /*[K,2,3] in/out*/,
+                        int32_t* boxes_dev /*[K,4] in/out*/, int32_t* status_dev /*[K] in/out*/,
+                        int32_t* misses_dev /*[K] in/out*/, double* state_dev /*NULL or [K,C,6] in/out*/,
+                        int32_t* det_slot_dev /*[D] out*/, int32_t* slot_det_dev /*[K] out*/,
+                        int32_t* counts_dev /*[8] out*/);
 
 #ifdef __cplusplus
 }
