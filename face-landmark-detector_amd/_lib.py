@@ -16,6 +16,7 @@ FLM_F32, FLM_BF16 = 0, 1
 IN_U8_BGR, IN_F32_RGB = 0, 1
 OUT_PROBS, OUT_CLASSMAP, OUT_LANDMARKS, OUT_LOGITS, OUT_LANDMARKS_STATS = 0, 1, 2, 3, 4
 LANDMARK_REC = 6  # FLM_LANDMARK_REC: x, y, score, var_x, var_y, cov_xy
+QUALITY_REC = 8   # FLM_QUALITY_REC: n_pix, sum Y, sum Y*Y, n_lap, sum L, sum L*L, dark, bright
 DECODE_ALL, DECODE_TOPN = 0, 1
 NORM_SUB_MEAN, NORM_SUB_AND_DIVIDE, NORM_DIVIDE = 0, 1, 2
 ABI_VERSION = 2
@@ -48,6 +49,7 @@ EXPORTS = [
     "flm_track_opts_init", "flm_track_seed", "flm_landmarks_from_crop", "flm_track_step",
     "flm_track_filter_init", "flm_track_step_filtered",
     "flm_track_assoc_opts_init", "flm_track_associate",
+    "flm_quality_opts_init", "flm_face_quality", "flm_best_opts_init", "flm_track_best_update",
 ]
 
 
@@ -149,6 +151,33 @@ class TrackAssocOpts(C.Structure):
         o.refresh_iou = float(refresh_iou)
         o.max_misses = int(max_misses)
         o.square = 1 if square else 0
+        return o
+
+
+class QualityOpts(C.Structure):
+    """flm_quality_opts: the exposure levels of flm_face_quality (include/flm.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("dark", C.c_int32), ("bright", C.c_int32)]
+
+    @classmethod
+    def make(cls, dark=16, bright=239):
+        o = cls()
+        load().flm_quality_opts_init(C.byref(o))
+        o.dark = int(dark)
+        o.bright = int(bright)
+        return o
+
+
+class BestOpts(C.Structure):
+    """flm_best_opts: how flm_track_best_update scores a face (include/flm.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("sharp_ref", C.c_double),
+                ("min_exposed", C.c_double)]
+
+    @classmethod
+    def make(cls, sharp_ref=100.0, min_exposed=0.5):
+        o = cls()
+        load().flm_best_opts_init(C.byref(o))
+        o.sharp_ref = float(sharp_ref)
+        o.min_exposed = float(min_exposed)
         return o
 
 
@@ -300,6 +329,15 @@ def _declare(lib):
     lib.flm_track_associate.restype = i
     lib.flm_track_associate.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, C.POINTER(TrackAssocOpts), vp, vp, vp, vp, vp, vp,
                                         vp, vp]
+    lib.flm_quality_opts_init.restype = None
+    lib.flm_quality_opts_init.argtypes = [C.POINTER(QualityOpts)]
+    lib.flm_face_quality.restype = i
+    lib.flm_face_quality.argtypes = [vp, vp, i, i, i, C.POINTER(ImageFormat), C.POINTER(QualityOpts), vp]
+    lib.flm_best_opts_init.restype = None
+    lib.flm_best_opts_init.argtypes = [C.POINTER(BestOpts)]
+    lib.flm_track_best_update.restype = i
+    lib.flm_track_best_update.argtypes = [vp, vp, sz, i, vp, vp, vp, vp, sz, vp, sz, i, vp, vp, C.c_int64,
+                                          C.POINTER(BestOpts), vp, vp, vp, vp, vp, vp, vp]
 
 
 def load():

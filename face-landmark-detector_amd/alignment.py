@@ -767,3 +767,189 @@ def track_associate_device(det, m_crop, boxes, status, misses, in_hw, frame_hw, 
         None if state is None else _lib.ptr(state), _lib.ptr(det_slot), _lib.ptr(slot_det), _lib.ptr(counts)),
         "flm_track_associate")
     return det_slot, slot_det, counts
+
+
+# ---- the best shot of a track: face quality and gallery (include/flm.h, "the best shot of a track") -------------------
+QUALITY_REC = _lib.QUALITY_REC
+
+
+class QualityOptions:
+    """The exposure levels of flm_face_quality: a pixel whose luma lies below `dark` (above `bright`), in 8-bit levels,
+    counts as under- (over-) exposed.  Integers in [0, 255]."""
+
+    def __init__(self, dark=16, bright=239):
+        for name, v in (("dark", dark), ("bright", bright)):
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= 255:
+                raise ValueError("%s must be an integer in [0, 255] (got %r)" % (name, v))
+        self.dark, self.bright = int(dark), int(bright)
+
+    def struct(self):
+        return _lib.QualityOpts.make(self.dark, self.bright)
+
+    def __repr__(self):
+        return "QualityOptions(dark=%r, bright=%r)" % (self.dark, self.bright)
+
+
+class BestShot:
+    """How a tracker picks the best face of a track (flm_face_quality, flm_track_best_update; include/flm.h): the
+    quality of a face is min(sharpness / sharp_ref, 1) x the share of well-exposed pixels x the mean landmark score (x a
+    factor of the caller's); a face whose exposed share lies below min_exposed never counts.  sharp_ref = 100 is the
+    customary blur threshold of the variance of the Laplacian, min_exposed = 0.5 a guess; neither has been tuned
+    against real footage.  dark, bright: as `QualityOptions`."""
+
+    def __init__(self, sharp_ref=100.0, min_exposed=0.5, dark=16, bright=239):
+        sharp_ref, min_exposed = float(sharp_ref), float(min_exposed)
+        if not sharp_ref > 0.0:
+            raise ValueError("sharp_ref must be > 0 (got %r)" % sharp_ref)
+        if min_exposed != min_exposed:
+            raise ValueError("min_exposed must not be NaN")
+        self.quality = QualityOptions(dark, bright)
+        self.sharp_ref, self.min_exposed = sharp_ref, min_exposed
+
+    @property
+    def dark(self):
+        return self.quality.dark
+
+    @property
+    def bright(self):
+        return self.quality.bright
+
+    def struct(self):
+        return _lib.BestOpts.make(self.sharp_ref, self.min_exposed)
+
+    def __repr__(self):
+        return "BestShot(sharp_ref=%r, min_exposed=%r, dark=%r, bright=%r)" % (self.sharp_ref, self.min_exposed, self.dark,
+                                                                                self.bright)
+
+
+def _faces_of(faces, fmt):
+    """(K, h, w) of a CUDA tensor of aligned faces in `fmt` (None: float32 [K,h,w,3]); ValueError otherwise."""
+    import torch
+    if fmt is None:
+        fmt = AlignedFormat()
+    else:
+        _check_format(fmt)
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 4 or faces.dtype != fmt.torch_dtype:
+        raise ValueError("faces must be a %s tensor of shape %s for %r" % (
+            fmt.dtype, "[K,h,w,3]" if fmt.layout == "nhwc" else "[K,3,h,w]", fmt))
+    k = int(faces.shape[0])
+    h, w = [int(v) for v in (faces.shape[1:3] if fmt.layout == "nhwc" else faces.shape[2:4])]
+    if tuple(faces.shape) != fmt.shape(k, h, w):
+        raise ValueError("faces must be a %s tensor of shape %s for %r" % (
+            fmt.dtype, "[K,h,w,3]" if fmt.layout == "nhwc" else "[K,3,h,w]", fmt))
+    if any(np.float32(s) == 0.0 for s in fmt.scale):    # (the C struct holds float32)
+        raise ValueError("a format with a scale of 0 cannot be undone (scale=%r)" % (fmt.scale,))
+    if not faces.is_cuda or not faces.is_contiguous():
+        raise ValueError("faces must be a contiguous CUDA tensor")
+    return fmt, k, h, w
+
+
+def face_quality_device(faces, fmt=None, opts=None, out=None):
+    """faces: CUDA tensor of K aligned faces as the warps store them under `fmt` (an AlignedFormat; None: float32
+    [K,h,w,3] BGR) -> CUDA int64 [K,8], the exact quality record of every face (flm_face_quality: n_pix, sum Y, sum Y*Y,
+    n_lap, sum L, sum L*L, dark pixels, bright pixels; Y the luma in sixteenths of an 8-bit level, L its 4-neighbour
+    Laplacian).  opts: None or a `QualityOptions`; out: where to write.  `faces` may be a slice of a larger buffer."""
+    import torch
+    if opts is None:
+        opts = QualityOptions()
+    elif not isinstance(opts, QualityOptions):
+        raise ValueError("opts must be None or a QualityOptions (got %r)" % (opts,))
+    fmt, k, h, w = _faces_of(faces, fmt)
+    if out is None:
+        out = torch.empty((k, QUALITY_REC), dtype=torch.int64, device=faces.device)
+    else:
+        _check_out(out, torch.int64, (k, QUALITY_REC), "out")
+    if k:
+        cf, co = fmt.struct(), opts.struct()
+        _lib.check(_lib.load().flm_face_quality(_lib.stream_ptr(), _lib.ptr(faces), k, h, w, _lib.C.byref(cf),
+                                                _lib.C.byref(co), _lib.ptr(out)), "flm_face_quality")
+    return out
+
+
+def quality_scalars(rec):
+    """rec: int64 [K,8] quality records (a tensor on any device, or a numpy array) -> float64 [K,4] of the same kind:
+    sharpness (the variance of the Laplacian in 8-bit levels squared; 0 for a face without interior), mean luma and luma
+    standard deviation in 8-bit levels, and the share of pixels that are neither dark nor bright."""
+    import torch
+    is_np = not isinstance(rec, torch.Tensor)
+    r = torch.as_tensor(np.asarray(rec)) if is_np else rec
+    if r.dtype != torch.int64 or r.dim() != 2 or int(r.shape[1]) != QUALITY_REC:
+        raise ValueError("rec must be int64 [K,%d]" % QUALITY_REC)
+    d = r.to(torch.float64)
+    n_pix, s_y, s_yy, n_lap, s_l, s_ll, dark, bright = d.unbind(1)
+    nl = n_lap.clamp(min=1.0)
+    mu_l = s_l / nl
+    sharp = ((s_ll / nl - mu_l * mu_l) / 256.0).clamp(min=0.0) * (n_lap > 0)
+    mean = s_y / n_pix
+    std = (s_yy / n_pix - mean * mean).clamp(min=0.0).sqrt()
+    out = torch.stack([sharp, mean / 16.0, std / 16.0, (n_pix - dark - bright) / n_pix], dim=1)
+    return out.numpy() if is_np else out
+
+
+def track_best_update_device(faces, rec, lm, best_q_in, best_q_out, gallery, best_frame, frame_id, status=None,
+                             reset=None, weights=None, factor=None, m=None, opts=None, best_m=None, best_lm=None,
+                             best_rec=None):
+    """Per slot, keep the face if it beats the slot's best, in one launch (flm_track_best_update; include/flm.h states it
+    line by line).
+
+    faces: contiguous CUDA tensor of K faces (any format: copied as bytes) and `gallery` a tensor of its dtype and
+    shape; rec CUDA int64 [K,8] from `face_quality_device`; lm CUDA float64 [K,C,2] and `weights` None or CUDA float64
+    [K,C] (both may be views of a landmark record tensor, read in place); status, reset: None or CUDA int32 [K]; factor:
+    None or CUDA float64 [K]; m: None or CUDA float32 [K,2,3]; frame_id: a host integer; opts: None or a `BestShot`.
+    best_q_in, best_q_out CUDA float64 [K], two different buffers (-1: the slot holds no best); best_frame CUDA int64 [K];
+    best_m, best_lm, best_rec: None or CUDA float32 [K,2,3], float64 [K,C,2], int64 [K,8].  A slot that is eligible and
+    strictly better has its face, quality, frame id, matrix, landmarks and record written; any other keeps every bit
+    and best_q_out = its previous best.  Returns best_q_out."""
+    import torch
+    if opts is None:
+        opts = BestShot()
+    elif not isinstance(opts, BestShot):
+        raise ValueError("opts must be None or a BestShot (got %r)" % (opts,))
+    if isinstance(frame_id, bool) or int(frame_id) != frame_id or not -2 ** 63 <= int(frame_id) < 2 ** 63:
+        raise ValueError("frame_id must be an integer that fits int64 (got %r)" % (frame_id,))
+    if not isinstance(faces, torch.Tensor) or faces.dim() < 1 or not faces.is_cuda or not faces.is_contiguous():
+        raise ValueError("faces must be a contiguous CUDA tensor of K faces")
+    k = int(faces.shape[0])
+    if (not isinstance(gallery, torch.Tensor) or gallery.dtype != faces.dtype or gallery.shape != faces.shape
+            or not gallery.is_cuda or not gallery.is_contiguous()):
+        raise ValueError("gallery must be a contiguous CUDA tensor of the dtype and shape of faces")
+    _check_out(rec, torch.int64, (k, QUALITY_REC), "rec")
+    lm, ls = _strided_points(lm)
+    c = int(lm.shape[1])
+    if int(lm.shape[0]) != k:
+        raise ValueError("lm must be a CUDA float64 [%d,C,2] tensor" % k)
+    wst = 1
+    if weights is not None:
+        if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64 or tuple(weights.shape) != (k, c)
+                or not weights.is_cuda):
+            raise ValueError("weights must be a CUDA float64 [%d,%d] tensor" % (k, c))
+        wst = _uniform_stride(weights, 1)
+        if wst is None:
+            weights, wst = weights.contiguous(), 1
+    for t, dt, name in ((status, torch.int32, "status"), (reset, torch.int32, "reset"), (factor, torch.float64, "factor")):
+        if t is not None:
+            _check_out(t, dt, (k,), name)
+    if m is not None:
+        _check_matrices(m, k)
+    _check_out(best_q_in, torch.float64, (k,), "best_q_in")
+    _check_out(best_q_out, torch.float64, (k,), "best_q_out")
+    if k and best_q_in.data_ptr() < best_q_out.data_ptr() + 8 * k and best_q_out.data_ptr() < best_q_in.data_ptr() + 8 * k:
+        raise ValueError("best_q_in and best_q_out must be two buffers that do not overlap")
+    _check_out(best_frame, torch.int64, (k,), "best_frame")
+    if best_m is not None:
+        if m is None:
+            raise ValueError("best_m needs m")
+        _check_matrices(best_m, k, "best_m")
+    if best_lm is not None:
+        _check_out(best_lm, torch.float64, (k, c, 2), "best_lm")
+    if best_rec is not None:
+        _check_out(best_rec, torch.int64, (k, QUALITY_REC), "best_rec")
+    if k and c:
+        face_bytes = faces.numel() // k * faces.element_size()
+        co = opts.struct()
+        p = lambda t: None if t is None else _lib.ptr(t)
+        _lib.check(_lib.load().flm_track_best_update(
+            _lib.stream_ptr(), _lib.ptr(faces), face_bytes, k, _lib.ptr(rec), p(status), p(reset), _lib.ptr(lm), ls,
+            p(weights), wst, c, p(factor), p(m), int(frame_id), _lib.C.byref(co), _lib.ptr(best_q_in), _lib.ptr(best_q_out),
+            _lib.ptr(gallery), _lib.ptr(best_frame), p(best_m), p(best_lm), p(best_rec)), "flm_track_best_update")
+    return best_q_out

@@ -38,6 +38,7 @@ SOURCES = [
     "flm_frames_nv12.hip",
     "flm_track.hip",
     "flm_track_assoc.hip",
+    "flm_quality.hip",
     "flm_mobile.hip",
 ]
 # -ffp-contract=off: only the fma() calls written in the sources fuse, so the arithmetic of the

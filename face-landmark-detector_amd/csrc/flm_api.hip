@@ -1343,4 +1343,126 @@ int flm_track_associate(flm_stream_t stream, const int32_t* det, const int32_t* 
                                 boxes, status, misses, state, det_slot, slot_det, counts);
 }
 
+// ---- best shot (flm_quality.hip) ------------------------------------------------------------------------------------
+
+void flm_quality_opts_init(flm_quality_opts* opts) {
+  if (!opts) return;
+  opts->struct_size = (uint32_t)sizeof(flm_quality_opts);
+  opts->dark = 16;
+  opts->bright = 239;
+}
+
+int flm_face_quality(flm_stream_t stream, const void* faces, int k, int h, int w, const flm_image_format* fmt,
+                     const flm_quality_opts* opts, int64_t* rec) {
+  const char* who = "flm_face_quality";
+  if (!faces || !rec) {
+    set_error("%s: null argument", who);  // (fmt and opts are optional)
+    return FLM_ERR_ARG;
+  }
+  flm_image_format plain;
+  flm_image_format_init(&plain);
+  if (!fmt) fmt = &plain;
+  if (const int rc = check_image_format(who, fmt)) return rc;
+  const uintptr_t esize = fmt->type == FLM_PIX_F32 ? 4 : fmt->type == FLM_PIX_U8 ? 1 : 2;
+  if (reinterpret_cast<uintptr_t>(faces) % esize) {
+    set_error("%s: faces is not aligned to its %d-byte element", who, (int)esize);
+    return FLM_ERR_ARG;
+  }
+  for (int c = 0; c < 3; ++c) {
+    if (fmt->scale[c] == 0.0f) {
+      set_error("%s: scale[%d] is 0, needs a scale that can be undone (scale != 0)", who, c);
+      return FLM_ERR_ARG;
+    }
+  }
+  flm_quality_opts defaults;
+  flm_quality_opts_init(&defaults);
+  if (!opts) opts = &defaults;
+  if (opts->struct_size < sizeof(flm_quality_opts)) {
+    set_error("%s: flm_quality_opts struct_size %u is smaller than this library's %zu (initialise with "
+              "flm_quality_opts_init)", who, opts->struct_size, sizeof(flm_quality_opts));
+    return FLM_ERR_ARG;
+  }
+  if (opts->dark < 0 || opts->dark > 255 || opts->bright < 0 || opts->bright > 255) {
+    set_error("%s: dark=%d, bright=%d, needs both in [0, 255]", who, opts->dark, opts->bright);
+    return FLM_ERR_ARG;
+  }
+  return launch_face_quality(static_cast<hipStream_t>(stream), faces, k, h, w, fmt, opts, rec);
+}
+
+void flm_best_opts_init(flm_best_opts* opts) {
+  if (!opts) return;
+  opts->struct_size = (uint32_t)sizeof(flm_best_opts);
+  opts->reserved = 0;
+  opts->sharp_ref = 100.0;
+  opts->min_exposed = 0.5;
+}
+
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+int flm_track_best_update(flm_stream_t stream, const void* faces, size_t face_bytes, int k, const int64_t* rec,
+                          const int32_t* status, const int32_t* reset, const double* lm, size_t lm_stride,
+                          const double* wt, size_t w_stride, int c, const double* factor, const float* m,
+                          int64_t frame_id, const flm_best_opts* opts, const double* best_q_in, double* best_q_out,
+                          void* gallery, int64_t* best_frame, float* best_m, double* best_lm, int64_t* best_rec) {
+  const char* who = "flm_track_best_update";
+  if (!faces || !rec || !lm || !best_q_in || !best_q_out || !gallery || !best_frame) {
+    set_error("%s: null argument", who);  // (status, reset, w, factor, m, opts and the last three outputs are optional)
+    return FLM_ERR_ARG;
+  }
+  if (best_m && !m) {
+    set_error("%s: best_m_dev needs m_dev", who);
+    return FLM_ERR_ARG;
+  }
+  flm_best_opts defaults;
+  flm_best_opts_init(&defaults);
+  if (!opts) opts = &defaults;
+  if (opts->struct_size < sizeof(flm_best_opts)) {
+    set_error("%s: flm_best_opts struct_size %u is smaller than this library's %zu (initialise with "
+              "flm_best_opts_init)", who, opts->struct_size, sizeof(flm_best_opts));
+    return FLM_ERR_ARG;
+  }
+  if (opts->reserved != 0) {
+    set_error("%s: flm_best_opts reserved=%d, must be 0", who, opts->reserved);
+    return FLM_ERR_ARG;
+  }
+  if (!(opts->sharp_ref > 0.0)) {
+    set_error("%s: sharp_ref=%g, needs sharp_ref > 0", who, opts->sharp_ref);
+    return FLM_ERR_ARG;
+  }
+  if (std::isnan(opts->min_exposed)) {
+    set_error("%s: min_exposed must not be NaN", who);
+    return FLM_ERR_ARG;
+  }
+  if (k < 1 || k > 65535) {
+    set_error("%s: k=%d, needs 1 <= k <= 65535", who, k);
+    return FLM_ERR_SHAPE;
+  }
+  if (c < 1) {
+    set_error("%s: c=%d, needs c >= 1", who, c);
+    return FLM_ERR_SHAPE;
+  }
+  if (face_bytes < 1) {
+    set_error("%s: face_bytes=0, needs face_bytes >= 1", who);
+    return FLM_ERR_SHAPE;
+  }
+  if (lm_stride < 2 || (wt && w_stride < 1)) {
+    set_error("%s: lm_stride=%zu, w_stride=%zu, needs lm_stride >= 2 and w_stride >= 1", who, lm_stride, w_stride);
+    return FLM_ERR_SHAPE;
+  }
+  if (ranges_overlap(best_q_in, (size_t)k * sizeof(double), best_q_out, (size_t)k * sizeof(double))) {
+    set_error("%s: best_q_in and best_q_out overlap (every workgroup of a slot reads best_q_in: swap two buffers)", who);
+    return FLM_ERR_ARG;
+  }
+  if (ranges_overlap(faces, (size_t)k * face_bytes, gallery, (size_t)k * face_bytes)) {
+    set_error("%s: faces_dev and gallery_dev overlap", who);
+    return FLM_ERR_ARG;
+  }
+  return launch_track_best_update(static_cast<hipStream_t>(stream), faces, face_bytes, k, rec, status, reset, lm, lm_stride,
+                                  wt, w_stride, c, factor, m, frame_id, opts, best_q_in, best_q_out, gallery, best_frame,
+                                  best_m, best_lm, best_rec);
+}
+
 }  // extern "C"

@@ -292,6 +292,15 @@ int launch_track_associate(hipStream_t s, const int32_t* det, const int32_t* n_d
                            int fh, int fw, const flm_track_assoc_opts* opts, float* m_crop, int32_t* boxes, int32_t* status,
                            int32_t* misses, double* state, int32_t* det_slot, int32_t* slot_det, int32_t* counts);
 
+// best shot (flm_quality.hip); pointers, the format, the option structs and overlaps have been checked by the caller
+int launch_face_quality(hipStream_t s, const void* faces, int k, int h, int w, const flm_image_format* fmt,
+                        const flm_quality_opts* opts, int64_t* rec);
+int launch_track_best_update(hipStream_t s, const void* faces, size_t face_bytes, int k, const int64_t* rec,
+                             const int32_t* status, const int32_t* reset, const double* lm, size_t lm_stride,
+                             const double* wt, size_t w_stride, int c, const double* factor, const float* m,
+                             int64_t frame_id, const flm_best_opts* opts, const double* best_q_in, double* best_q_out,
+                             void* gallery, int64_t* best_frame, float* best_m, double* best_lm, int64_t* best_rec);
+
 // Bijective XCD-aware remap of a 1-D grid: blocks that the dispatcher deals to the same XCD
 // (b % 8) receive consecutive logical ids, so neighbours in logical order share an L2.
 __device__ __forceinline__ int xcd_remap(int b, int nblk) {

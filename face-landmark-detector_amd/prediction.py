@@ -542,6 +542,22 @@ def video_predict(facedetector_fn, landmark_model, frames=None, on_frame=None, n
     return count
 
 
+def face_quality(faces, aligned_format=None):
+    """The exact quality record of aligned faces and its customary scalars.  faces: K aligned faces as `align` /
+    `align_frames` return them under `aligned_format` (None: float32 [K,h,w,3] BGR), a numpy array (one upload, two
+    downloads) or a CUDA tensor (nothing leaves the device) -> (rec int64 [K,8] as `alignment.face_quality_device`
+    describes it, scalars float64 [K,4]: sharpness, mean luma, luma standard deviation, exposed share), of the kind of
+    `faces`."""
+    import torch
+    numpy_io = not isinstance(faces, torch.Tensor)
+    _aligned_format(aligned_format, numpy_io)
+    if numpy_io:
+        faces = torch.from_numpy(np.ascontiguousarray(faces)).to(_lib.require_gpu())
+    rec = alignment.face_quality_device(faces.contiguous(), aligned_format)
+    sc = alignment.quality_scalars(rec)
+    return (rec.cpu().numpy(), sc.cpu().numpy()) if numpy_io else (rec, sc)
+
+
 # ---- tracking: faces followed across frames from their own landmarks ---------------------------------------------------
 class FaceTracker:
     """Faces followed across the frames of a stream on the device: the landmarks of frame t place the crop of frame t+1.
@@ -562,12 +578,23 @@ class FaceTracker:
     returned landmarks, the aligned fit and the next crop are those of the smoothed points.  The tracker then also owns
     `filter_state` float64 [capacity,C,6]; a seed clears the history of its slots.  associate: None (the defaults) or an
     `alignment.TrackAssociation`: how `update` pairs the boxes of a detector with the live tracks; the tracker owns
-    `misses` int32 [capacity], the updates in a row that found no detection for a slot."""
+    `misses` int32 [capacity], the updates in a row that found no detection for a slot.  best_shot: None, True (the
+    defaults) or an `alignment.BestShot`: after the aligned warp every step scores the aligned faces on the device
+    (flm_face_quality, flm_track_best_update; with weights="score" the landmark scores take part) and keeps, per slot,
+    the best one of its track: the tracker then owns `gallery` [capacity,...] in the aligned format, `best_q` float64
+    [capacity] (-1: none yet), `best_frame` int64, `best_M` float32 [capacity,2,3], `best_landmarks` float64
+    [capacity,C,2] and `best_rec` int64 [capacity,8]; `best()` hands them out.  A seed, and a birth in `update`, make
+    the slot forget its best with the next step; a track that ends keeps its best readable until then."""
 
     def __init__(self, model, frame_hw, capacity, out_size=(112, 112), template=None, crop_template=None, n_points=4,
                  thresh=0.0, weights=None, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"),
-                 crop_samples=1, samples=1, aligned_format=None, frame_format=None, smooth=None, associate=None):
+                 crop_samples=1, samples=1, aligned_format=None, frame_format=None, smooth=None, associate=None,
+                 best_shot=None):
         import torch
+        if best_shot is True:
+            best_shot = alignment.BestShot()
+        if best_shot is not None and not isinstance(best_shot, alignment.BestShot):
+            raise ValueError("best_shot must be None, True or an alignment.BestShot (got %r)" % (best_shot,))
         if associate is None:
             associate = alignment.TrackAssociation()
         elif not isinstance(associate, alignment.TrackAssociation):
@@ -610,6 +637,7 @@ class FaceTracker:
         self.aligned_format, self.frame_format = aligned_format, frame_format
         self.smooth, self.filter_state = smooth, None
         self.associate = associate
+        self.best_shot, self.gallery, self._steps = best_shot, None, 0
         self._crop_format = alignment.AlignedFormat("nhwc", "uint8")
         self._templates = (np.ascontiguousarray(tm, np.float64), np.ascontiguousarray(tc, np.float64))
         self.m_crop = None    # the device state, allocated by the first call that needs it (_state)
@@ -630,6 +658,18 @@ class FaceTracker:
         self.misses = torch.zeros((n,), dtype=torch.int32, device=dev)
         if self.smooth is not None:     # -1: no landmark has a history
             self.filter_state = torch.full((n, int(self.model.n_classes), 6), -1.0, dtype=torch.float64, device=dev)
+        if self.best_shot is not None:  # -1: the slot holds no best
+            fmt = self.aligned_format or alignment.AlignedFormat()
+            c = int(self.model.n_classes)
+            self.gallery = torch.zeros(fmt.shape(n, *self.out_size), dtype=fmt.torch_dtype, device=dev)
+            self.best_q = torch.full((n,), -1.0, dtype=torch.float64, device=dev)
+            self._best_q_spare = torch.full_like(self.best_q, -1.0)
+            self.best_frame = torch.full((n,), -1, dtype=torch.int64, device=dev)
+            self.best_M = torch.zeros((n, 2, 3), dtype=torch.float32, device=dev)
+            self.best_landmarks = torch.full((n, c, 2), -1.0, dtype=torch.float64, device=dev)
+            self.best_rec = torch.zeros((n, alignment.QUALITY_REC), dtype=torch.int64, device=dev)
+            self._quality_rec = torch.zeros_like(self.best_rec)
+            self._best_reset = torch.zeros((n,), dtype=torch.int32, device=dev)
 
     def seed(self, slots, boxes):
         """Start (or restart) the tracks `slots` from the detector boxes `boxes` (x0,y0,x1,y1), one per slot: the host
@@ -655,6 +695,8 @@ class FaceTracker:
         self.misses.index_fill_(0, idx, 0)
         if self.filter_state is not None:
             self.filter_state.index_fill_(0, idx, -1.0)
+        if self.best_shot is not None:
+            self._best_reset.index_fill_(0, idx, 1)
 
     def update(self, detections, n=None):
         """The boxes of a detector against the tracks, on the device (alignment.track_associate_device with the
@@ -688,11 +730,19 @@ class FaceTracker:
         self._state()
         if not isinstance(det, torch.Tensor):
             det = torch.from_numpy(np.ascontiguousarray(det)).to(self.boxes.device)
-        return alignment.track_associate_device(det, self.m_crop, self.boxes, self.status, self.misses,
-                                                (self.model.input_height, self.model.input_width), self.frame_hw,
-                                                n_det=n, state=self.filter_state, assoc=self.associate)
+        if self.best_shot is not None:  # the slots that hold no track now: the association's own test, on the device
+            fh, fw = self.frame_hw
+            b = self.boxes
+            was_empty = ((b[:, 2].clamp(0, fw) - b[:, 0].clamp(0, fw) <= 0)
+                         | (b[:, 3].clamp(0, fh) - b[:, 1].clamp(0, fh) <= 0))
+        out = alignment.track_associate_device(det, self.m_crop, self.boxes, self.status, self.misses,
+                                               (self.model.input_height, self.model.input_width), self.frame_hw,
+                                               n_det=n, state=self.filter_state, assoc=self.associate)
+        if self.best_shot is not None:  # a birth forgets the slot's best; a restart is the same face and keeps it
+            self._best_reset.masked_fill_(was_empty & (out[1] >= 0), 1)
+        return out
 
-    def step(self, ring, frame_index, dt=None):
+    def step(self, ring, frame_index, dt=None, frame_id=None):
         """One frame for every slot: `ring` is the frame ring (`frame_format` says how it holds its pixels),
         `frame_index` the ring slot of the new frame.  Sequence: the uint8 crop warp with the slots' matrices ->
         model.forward_device -> alignment.track_step_device (landmarks to frame px, the aligned fit, the next crop's
@@ -702,8 +752,15 @@ class FaceTracker:
         without a face returns zero crops and zero aligned faces, the identity and TRACK_DEAD; a track lost in this
         frame still returns this frame's aligned face, with the reason in its status, and is dead from the next step
         on.  `dt`, for a tracker that smooths: the seconds since the previous step, a host number (None: 1/fps of the
-        filter)."""
+        filter).  `frame_id`, for a tracker with `best_shot`: the host integer `best_frame` records for a face taken
+        in this step (None: the number of steps this tracker has made before this one)."""
         fh, fw = self.frame_hw
+        if self.best_shot is None and frame_id is not None:
+            raise ValueError("frame_id goes with best_shot")
+        if frame_id is None:
+            frame_id = self._steps
+        elif isinstance(frame_id, bool) or int(frame_id) != frame_id or not -2 ** 63 <= int(frame_id) < 2 ** 63:
+            raise ValueError("frame_id must be an integer that fits int64 (got %r)" % (frame_id,))
         if self.smooth is None and dt is not None:
             raise ValueError("dt goes with smooth")
         dt = None if self.smooth is None else self.smooth.time_step(dt)
@@ -737,7 +794,26 @@ class FaceTracker:
                                                frame_index_dev=self.frame_slots, boxes_dev=self.boxes, samples=self.samples,
                                                fmt=self.aligned_format, src=self.frame_format)
         self.boxes, self._boxes_spare = self._boxes_spare, self.boxes
+        self._steps += 1
+        if self.best_shot is not None:
+            alignment.face_quality_device(aligned, self.aligned_format, self.best_shot.quality, out=self._quality_rec)
+            alignment.track_best_update_device(
+                aligned, self._quality_rec, lm_frame, self.best_q, self._best_q_spare, self.gallery, self.best_frame,
+                int(frame_id), status=self.status, reset=self._best_reset, weights=wd, m=m_align, opts=self.best_shot,
+                best_m=self.best_M, best_lm=self.best_landmarks, best_rec=self.best_rec)
+            self.best_q, self._best_q_spare = self._best_q_spare, self.best_q
+            self._best_reset.zero_()
         return aligned, m_align, lm_frame, self.status
+
+    def best(self):
+        """The best shot of every slot, for a tracker with `best_shot`: CUDA tensors (gallery [capacity,...] in the
+        aligned format, best_q float64 [capacity] -- -1: the slot holds none --, best_frame int64 [capacity], best_M
+        float32 [capacity,2,3], best_landmarks float64 [capacity,C,2]), the tracker's own, overwritten by later steps.
+        No download, no synchronisation."""
+        if self.best_shot is None:
+            raise ValueError("best() needs a tracker made with best_shot")
+        self._state()
+        return self.gallery, self.best_q, self.best_frame, self.best_M, self.best_landmarks
 
     def lost(self):
         """The slots whose status is not 0, as a host list: the one call of the tracker that synchronises.  The caller

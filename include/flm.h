@@ -848,6 +848,97 @@ int flm_track_associate(flm_stream_t stream, const int32_t* det_dev /*[D,4]*/, c
                         int32_t* det_slot_dev /*[D] out*/, int32_t* slot_det_dev /*[K] out*/,
                         int32_t* counts_dev /*[8] out*/);
 
+/* ---- the best shot of a track: face quality and gallery ---------------------------------------------------------------
+ * A matcher embeds a track's best face, not every face.  The two calls below judge the aligned faces where the warp
+ * left them and keep, per slot, the best one seen so far -- three launches per step, no workspace, no allocation, no
+ * synchronisation.  Every reduction is an exact integer sum, so the results do not depend on how they are scheduled.
+ *
+ * flm_face_quality: rec_dev int64 [K,8] from K faces of h x w as flm_warp_affine_fmt / flm_warp_affine_frames_fmt store
+ * them under `fmt` (NULL = what flm_image_format_init gives: NHWC float32 BGR, scale 1, bias 0).  On the host, once:
+ *   inv[c] = 1.0f / fmt->scale[c]                              float32 division
+ * For stored element x of output channel c of a pixel (the element index is that of the warps' contract):
+ *   xf = (float)x                                              exact for uint8, binary16 and bfloat16
+ *   t  = xf - bias[c]                                          float32, rounded
+ *   v  = t * inv[c]                                            float32, rounded: two operations, never fused
+ *   p  = (int32)min(max(rintf(v * 16.0f), 0), 4080)            ties to even; a NaN gives 0; +-inf clamp
+ *        -- the source pixel value in sixteenths of an 8-bit level
+ * The source channel of output channel c is s = reverse_channels ? 2-c : c, and B, G, R are s = 0, 1, 2.  Per pixel
+ *   Y = (1868*B + 9617*G + 4899*R + 8192) >> 14                BT.601 weights x 2^14 (sum 16384); 0 <= Y <= 4080
+ * and for the interior pixels (1 <= row <= h-2 and 1 <= col <= w-2)
+ *   L = Y(row-1,col) + Y(row+1,col) + Y(row,col-1) + Y(row,col+1) - 4*Y(row,col)
+ * The record of a face, every entry an exact int64 sum (the largest stays below 2^56):
+ *   { n_pix = h*w, sum Y, sum Y*Y, n_lap = max(h-2,0)*max(w-2,0), sum L, sum L*L, #(Y < 16*dark), #(Y > 16*bright) }
+ * opts (NULL = the defaults of flm_quality_opts_init: dark = 16, bright = 239): the 8-bit levels below and above which
+ * a pixel counts as under- and over-exposed.
+ * faces_dev needs the alignment of its element and no more: it may be a slice of a larger buffer.  The kernel uses
+ * 16-byte loads where the actual address of a run of elements allows them and element loads elsewhere; no byte
+ * outside the K faces is read.  Two launches (the records' constants and zeros, then the sums).
+ * Errors, all found before anything is launched: a null faces_dev or rec_dev, a format flm_warp_affine_fmt rejects, a
+ * faces_dev that is not aligned to its element, a scale[c] of 0, a struct_size smaller than this library's, or dark or
+ * bright outside [0, 255] -> FLM_ERR_ARG.  FLM_ERR_SHAPE, the limit named in flm_last_error(), unless
+ * 1 <= k <= 65535, h, w >= 1 and h*w*3*4 < 2^31 (the warp's limit). */
+#define FLM_QUALITY_REC 8
+typedef struct flm_quality_opts {
+  uint32_t struct_size;  /* as flm_track_opts */
+  int32_t dark, bright;  /* 8-bit levels: Y < 16*dark is under-exposed, Y > 16*bright over-exposed */
+} flm_quality_opts;
+void flm_quality_opts_init(flm_quality_opts* opts);
+int flm_face_quality(flm_stream_t stream, const void* faces_dev, int k, int h, int w,
+                     const flm_image_format* fmt /*NULL = NHWC f32 BGR*/, const flm_quality_opts* opts /*NULL = defaults*/,
+                     int64_t* rec_dev /*[K,8]*/);
+
+/* flm_track_best_update: per slot, "keep this face if it beats what the slot holds", in ONE launch.
+ * In:  faces_dev, K faces of face_bytes bytes each (any format: they are copied as bytes); rec_dev int64 [K,8], their
+ *      records; status_dev int32 [K] or NULL; reset_dev int32 [K] or NULL (non-zero: the slot forgets its best first);
+ *      lm_dev, lm_stride, w_dev, w_stride, c: the landmarks and their weights as flm_track_step reads them (point i of
+ *      slot f at lm_dev[(f*c+i)*lm_stride + {0,1}], its weight at w_dev[(f*c+i)*w_stride]; w_dev may be NULL);
+ *      factor_dev float64 [K] or NULL: a term of the caller's own (head pose, say); m_dev float32 [K,2,3] or NULL;
+ *      frame_id; best_q_in float64 [K].
+ * Per slot, in float64, one IEEE operation per written operator, in the written order, no contraction; max and min
+ * are fmax and fmin; (double) of an int64 rounds to nearest:
+ *   mu    = (double)S_L / (double)n_lap
+ *   var   = (double)S_LL / (double)n_lap - mu*mu
+ *   sharp = max(var / 256.0, 0.0)        the variance of the Laplacian in 8-bit levels squared: the customary focus measure
+ *   s     = min(sharp / sharp_ref, 1.0)
+ *   e     = (double)(n_pix - n_dark - n_bright) / (double)n_pix
+ *   wbar  = the mean of w over the landmarks whose (x, y) is not (-1,-1), summed in ascending landmark index from 0.0,
+ *           then divided by their number; 1.0 when w_dev is NULL; 0.0 when w_dev is given and no landmark took part
+ *   f     = factor_dev ? factor_dev[slot] : 1.0
+ *   q     = ((s * e) * wbar) * f
+ * The slot is ELIGIBLE when status_dev is NULL or status == 0, n_lap > 0, e >= min_exposed, q is not NaN and q >= 0.
+ * prev = (reset_dev && reset_dev[slot] != 0) ? -1.0 : best_q_in[slot]; -1.0 means "holds no best".
+ * The slot is TAKEN when it is eligible and q > prev (strict: on a tie the earlier frame stays).  Then
+ *   gallery_dev[slot*face_bytes ..] = the face's face_bytes bytes, best_q_out = q, best_frame_dev = frame_id, and, each
+ *   where its pointer is given, best_m_dev = the slot's six floats of m_dev, best_lm_dev = the slot's C*2 doubles of
+ *   lm_dev, best_rec_dev = the slot's record.
+ * Otherwise best_q_out = prev and nothing else of the slot is written: its gallery bytes keep their bits.
+ * best_q_in and best_q_out must not overlap (the launch is race-free because every workgroup of a slot derives the same
+ * decision from inputs nobody writes); no output may overlap an input.  The grid is (chunk, slot); the workgroups of a
+ * slot that is not taken return at once; the copy uses 16-byte accesses where both addresses allow them.
+ * Defaults (flm_best_opts_init): sharp_ref = 100, the customary blur threshold of this measure (a face at or above it
+ * counts as fully sharp), and min_exposed = 0.5, a guess.  Neither has been tuned against real footage.
+ * Errors, all found before anything is launched: a null faces_dev, rec_dev, lm_dev, best_q_in, best_q_out, gallery_dev
+ * or best_frame_dev, a best_m_dev without m_dev, a struct_size smaller than this library's, a non-zero reserved, a
+ * sharp_ref that is not > 0, a NaN min_exposed, best_q_in overlapping best_q_out, or faces_dev overlapping gallery_dev
+ * -> FLM_ERR_ARG.  FLM_ERR_SHAPE, the limit named in flm_last_error(), unless 1 <= k <= 65535, c >= 1, face_bytes >= 1,
+ * lm_stride >= 2 and (with w_dev) w_stride >= 1. */
+typedef struct flm_best_opts {
+  uint32_t struct_size;  /* as flm_track_opts */
+  int32_t reserved;      /* 0 */
+  double sharp_ref;      /* sharpness (8-bit levels squared) at and above which a face counts as fully sharp */
+  double min_exposed;    /* the least share of pixels that are neither dark nor bright */
+} flm_best_opts;
+void flm_best_opts_init(flm_best_opts* opts);
+int flm_track_best_update(flm_stream_t stream, const void* faces_dev, size_t face_bytes, int k,
+                          const int64_t* rec_dev /*[K,8]*/, const int32_t* status_dev /*[K] or NULL*/,
+                          const int32_t* reset_dev /*[K] or NULL*/, const double* lm_dev, size_t lm_stride,
+                          const double* w_dev /*or NULL*/, size_t w_stride, int c,
+                          const double* factor_dev /*[K] or NULL*/, const float* m_dev /*[K,2,3] or NULL*/,
+                          int64_t frame_id, const flm_best_opts* opts /*NULL = defaults*/,
+                          const double* best_q_in /*[K]*/, double* best_q_out /*[K]*/, void* gallery_dev /*[K,face_bytes]*/,
+                          int64_t* best_frame_dev /*[K]*/, float* best_m_dev /*[K,2,3] or NULL*/,
+                          double* best_lm_dev /*[K,C,2] or NULL*/, int64_t* best_rec_dev /*[K,8] or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
