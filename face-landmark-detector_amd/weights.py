@@ -283,6 +283,7 @@ def synth_fcn8_weights(n_classes: int = 68, seed: int = 2, channels: int = 3) ->
     beta ~ N(0,0.1), mean ~ N(0,0.1), var ~ U(0.5,1.5).  The three score convs and
     the transposed convs are scaled so the logits keep an O(1) spread (an
     unsaturated softmax, so argmax / centroid are not degenerate).
+    The saturated regime (peaked maps, zeros, denormals, ties) is built from these in tests/peaked_cases.py.
     """
     rng = np.random.default_rng(seed)
     p = {}

@@ -2,7 +2,8 @@
 materialises [N,264,264,68] and decodes it: the two must agree bit for bit (float64 coordinates),
 because the candidate lists hold every pixel that can enter the top n and the final selection uses
 the same (value, flat index) keys.  Also covered: the overflow fallback (lists too small; flat maps
-where every pixel ties with the threshold) and rejected landmarks (thresh above some of the means)."""
+where every pixel ties with the threshold) and rejected landmarks (thresh above some of the means).  Peaked and saturated
+maps, and batches that mix them with blank crops, live in tests/test_gpu_peaked_maps.py."""
 import numpy as np
 import pytest
 
