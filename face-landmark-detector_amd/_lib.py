@@ -48,7 +48,7 @@ EXPORTS = [
     "flm_warp_affine_frames_src",
     "flm_track_opts_init", "flm_track_seed", "flm_landmarks_from_crop", "flm_track_step",
     "flm_track_filter_init", "flm_track_step_filtered",
-    "flm_track_assoc_opts_init", "flm_track_associate",
+    "flm_track_assoc_opts_init", "flm_track_associate", "flm_track_associate_streams",
     "flm_quality_opts_init", "flm_face_quality", "flm_best_opts_init", "flm_track_best_update",
 ]
 
@@ -329,6 +329,9 @@ def _declare(lib):
     lib.flm_track_associate.restype = i
     lib.flm_track_associate.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, C.POINTER(TrackAssocOpts), vp, vp, vp, vp, vp, vp,
                                         vp, vp]
+    lib.flm_track_associate_streams.restype = i
+    lib.flm_track_associate_streams.argtypes = [vp, vp, vp, i, i, i, i, i, i, i, i, C.POINTER(TrackAssocOpts), vp, vp, vp,
+                                                vp, vp, vp, vp, vp]
     lib.flm_quality_opts_init.restype = None
     lib.flm_quality_opts_init.argtypes = [C.POINTER(QualityOpts)]
     lib.flm_face_quality.restype = i

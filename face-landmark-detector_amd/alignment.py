@@ -769,6 +769,84 @@ def track_associate_device(det, m_crop, boxes, status, misses, in_hw, frame_hw, 
     return det_slot, slot_det, counts
 
 
+def track_associate_streams_device(det, m_crop, boxes, status, misses, slots_per_stream, in_hw, frame_hw, n_det=None,
+                                   state=None, assoc=None, det_slot=None, slot_det=None, counts=None):
+    """The association for S streams (cameras) that share one tracker, in one launch of one workgroup per stream
+    (flm_track_associate_streams; include/flm.h states it).
+
+    det: CUDA int32 [S,D,4], the boxes of stream i in det[i], D <= 1024; n_det: None, or CUDA int32 [S]: how many rows
+    of det[i] are valid -- a negative entry skips the stream (its detector did not run): nothing of its state is read or
+    written.  m_crop CUDA float32 [S*K,2,3], boxes CUDA int32 [S*K,4], status and misses CUDA int32 [S*K], and `state`,
+    None or CUDA float64 [S*K,C,6], are the tracker's own tensors, stream i owning the slots [i*K, (i+1)*K) with
+    K = slots_per_stream <= 1024 and S*K <= 65535: read and written in place.  No pair of two streams is evaluated.
+    Returns (det_slot int32 [S,D]: the GLOBAL slot i*K + t a detection matched or was born into, -1 for a void or
+    unread row or a skipped stream, -2 when no slot of its stream was free; slot_det int32 [S*K]: the row inside det[i]
+    of a matched or born slot, else -1; counts int32 [S,8], per stream as `track_associate_device` lists them, zero for
+    a skipped stream).  The three keyword tensors name where to write."""
+    import torch
+    if assoc is None:
+        assoc = TrackAssociation()
+    elif not isinstance(assoc, TrackAssociation):
+        raise ValueError("assoc must be None or a TrackAssociation (got %r)" % (assoc,))
+    if not isinstance(det, torch.Tensor) or det.dim() != 3 or det.dtype != torch.int32 or int(det.shape[2]) != 4:
+        raise ValueError("det must be a contiguous CUDA int32 [S,D,4] tensor")
+    s, d = int(det.shape[0]), int(det.shape[1])
+    if n_det is not None and (not isinstance(n_det, torch.Tensor) or n_det.dtype != torch.int32
+                              or tuple(n_det.shape) != (s,)):
+        raise ValueError("n_det must be None or a contiguous CUDA int32 [%d] tensor, one count per stream" % s)
+    if not det.is_cuda or not det.is_contiguous():
+        raise ValueError("det must be a contiguous CUDA int32 [S,D,4] tensor")
+    if isinstance(slots_per_stream, bool) or int(slots_per_stream) != slots_per_stream:
+        raise ValueError("slots_per_stream must be an integer (got %r)" % (slots_per_stream,))
+    k = int(slots_per_stream)
+    if s < 1 or not 1 <= d <= ASSOC_MAX or not 1 <= k <= ASSOC_MAX:
+        raise ValueError("track_associate_streams_device takes 1 or more streams of 1..%d detections and 1..%d slots each "
+                         "(got %d streams, %d, %d)" % (ASSOC_MAX, ASSOC_MAX, s, d, k))
+    n = s * k
+    if n > 65535:
+        raise ValueError("%d streams of %d slots exceed the tracker's 65535 slots" % (s, k))
+    _check_matrices(m_crop, n, "m_crop")
+    _check_boxes(boxes, n)
+    _check_out(status, torch.int32, (n,), "status")
+    _check_out(misses, torch.int32, (n,), "misses")
+    if n_det is not None:
+        _check_out(n_det, torch.int32, (s,), "n_det")
+    c = 1
+    if state is not None:
+        if not isinstance(state, torch.Tensor) or state.dim() != 3:
+            raise ValueError("state must be a contiguous CUDA float64 [S*K,C,6] tensor")
+        c = int(state.shape[1])
+        _check_out(state, torch.float64, (n, c, 6), "state")
+        if not 1 <= c <= 1024:
+            raise ValueError("state must have 1..1024 landmarks (got %d)" % c)
+    ih, iw = _sizes(in_hw, "in_hw")
+    fh, fw = _sizes(frame_hw, "frame_hw")
+    if fh * fw > 2 ** 30:
+        raise ValueError("frames of %dx%d are outside the association's reach (H*W <= 2^30)" % (fh, fw))
+    tensors = [det, m_crop, boxes, status, misses] + [t for t in (n_det, state) if t is not None]
+    if det_slot is None:
+        det_slot = torch.empty((s, d), dtype=torch.int32, device=det.device)
+    else:
+        _check_out(det_slot, torch.int32, (s, d), "det_slot")
+    if slot_det is None:
+        slot_det = torch.empty((n,), dtype=torch.int32, device=det.device)
+    else:
+        _check_out(slot_det, torch.int32, (n,), "slot_det")
+    if counts is None:
+        counts = torch.empty((s, 8), dtype=torch.int32, device=det.device)
+    else:
+        _check_out(counts, torch.int32, (s, 8), "counts")
+    if any(t.device != det.device for t in tensors + [det_slot, slot_det, counts]):
+        raise ValueError("every tensor of track_associate_streams_device must lie on the device of det")
+    opts = assoc.struct()
+    _lib.check(_lib.load().flm_track_associate_streams(
+        _lib.stream_ptr(), _lib.ptr(det), None if n_det is None else _lib.ptr(n_det), s, d, k, c, ih, iw, fh, fw,
+        _lib.C.byref(opts), _lib.ptr(m_crop), _lib.ptr(boxes), _lib.ptr(status), _lib.ptr(misses),
+        None if state is None else _lib.ptr(state), _lib.ptr(det_slot), _lib.ptr(slot_det), _lib.ptr(counts)),
+        "flm_track_associate_streams")
+    return det_slot, slot_det, counts
+
+
 # ---- the best shot of a track: face quality and gallery (include/flm.h, "the best shot of a track") -------------------
 QUALITY_REC = _lib.QUALITY_REC
 

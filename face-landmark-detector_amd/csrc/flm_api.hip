@@ -1289,27 +1289,30 @@ void flm_track_assoc_opts_init(flm_track_assoc_opts* opts) {
   opts->refresh_iou = 0.0;
 }
 
-int flm_track_associate(flm_stream_t stream, const int32_t* det, const int32_t* n_det, int d, int k, int c, int in_h,
-                        int in_w, int fh, int fw, const flm_track_assoc_opts* opts, float* m_crop, int32_t* boxes,
-                        int32_t* status, int32_t* misses, double* state, int32_t* det_slot, int32_t* slot_det,
-                        int32_t* counts) {
-  const char* who = "flm_track_associate";
+// The checks flm_track_associate and flm_track_associate_streams share; *opts is replaced by `defaults` when null.
+static int track_assoc_check(const char* who, const void* det, const void* m_crop, const void* boxes, const void* status,
+                             const void* misses, const void* det_slot, const void* slot_det, const void* counts,
+                             const flm_track_assoc_opts** opts, flm_track_assoc_opts* defaults) {
   if (!det || !m_crop || !boxes || !status || !misses || !det_slot || !slot_det || !counts) {
     set_error("%s: null argument", who);  // (n_det_dev, state_dev and opts are optional)
     return FLM_ERR_ARG;
   }
-  flm_track_assoc_opts defaults;
-  flm_track_assoc_opts_init(&defaults);
-  if (!opts) opts = &defaults;
-  if (opts->struct_size < sizeof(flm_track_assoc_opts)) {
+  flm_track_assoc_opts_init(defaults);
+  if (!*opts) *opts = defaults;
+  if ((*opts)->struct_size < sizeof(flm_track_assoc_opts)) {
     set_error("%s: flm_track_assoc_opts struct_size %u is smaller than this library's %zu (initialise with "
-              "flm_track_assoc_opts_init)", who, opts->struct_size, sizeof(flm_track_assoc_opts));
+              "flm_track_assoc_opts_init)", who, (*opts)->struct_size, sizeof(flm_track_assoc_opts));
     return FLM_ERR_ARG;
   }
-  if (opts->reserved != 0) {
-    set_error("%s: flm_track_assoc_opts reserved=%d, must be 0", who, opts->reserved);
+  if ((*opts)->reserved != 0) {
+    set_error("%s: flm_track_assoc_opts reserved=%d, must be 0", who, (*opts)->reserved);
     return FLM_ERR_ARG;
   }
+  return FLM_OK;
+}
+
+static int track_assoc_check_sizes(const char* who, int d, int k, int c, bool has_state, int in_h, int in_w, int fh, int fw,
+                                   const flm_track_assoc_opts* opts) {
   if (k < 1 || k > 1024) {
     set_error("%s: k=%d, needs 1 <= k <= 1024", who, k);
     return FLM_ERR_SHAPE;
@@ -1318,7 +1321,7 @@ int flm_track_associate(flm_stream_t stream, const int32_t* det, const int32_t* 
     set_error("%s: d=%d, needs 1 <= d <= 1024", who, d);
     return FLM_ERR_SHAPE;
   }
-  if (state && (c < 1 || c > 1024)) {
+  if (has_state && (c < 1 || c > 1024)) {
     set_error("%s: c=%d, needs 1 <= c <= 1024", who, c);
     return FLM_ERR_SHAPE;
   }
@@ -1339,8 +1342,43 @@ int flm_track_associate(flm_stream_t stream, const int32_t* det, const int32_t* 
               opts->dup_iou, opts->refresh_iou);
     return FLM_ERR_SHAPE;
   }
+  return FLM_OK;
+}
+
+int flm_track_associate(flm_stream_t stream, const int32_t* det, const int32_t* n_det, int d, int k, int c, int in_h,
+                        int in_w, int fh, int fw, const flm_track_assoc_opts* opts, float* m_crop, int32_t* boxes,
+                        int32_t* status, int32_t* misses, double* state, int32_t* det_slot, int32_t* slot_det,
+                        int32_t* counts) {
+  const char* who = "flm_track_associate";
+  flm_track_assoc_opts defaults;
+  int rc = track_assoc_check(who, det, m_crop, boxes, status, misses, det_slot, slot_det, counts, &opts, &defaults);
+  if (rc != FLM_OK) return rc;
+  rc = track_assoc_check_sizes(who, d, k, c, state != nullptr, in_h, in_w, fh, fw, opts);
+  if (rc != FLM_OK) return rc;
   return launch_track_associate(static_cast<hipStream_t>(stream), det, n_det, d, k, c, in_h, in_w, fh, fw, opts, m_crop,
                                 boxes, status, misses, state, det_slot, slot_det, counts);
+}
+
+int flm_track_associate_streams(flm_stream_t stream, const int32_t* det, const int32_t* n_det, int s, int d, int k, int c,
+                                int in_h, int in_w, int fh, int fw, const flm_track_assoc_opts* opts, float* m_crop,
+                                int32_t* boxes, int32_t* status, int32_t* misses, double* state, int32_t* det_slot,
+                                int32_t* slot_det, int32_t* counts) {
+  const char* who = "flm_track_associate_streams";
+  flm_track_assoc_opts defaults;
+  int rc = track_assoc_check(who, det, m_crop, boxes, status, misses, det_slot, slot_det, counts, &opts, &defaults);
+  if (rc != FLM_OK) return rc;
+  if (s < 1) {
+    set_error("%s: s=%d, needs 1 <= s", who, s);
+    return FLM_ERR_SHAPE;
+  }
+  if (k >= 1 && (int64_t)s * (int64_t)k > 65535) {
+    set_error("%s: s=%d streams of k=%d slots, needs s*k <= 65535 (the capacity of the warps and the tracker)", who, s, k);
+    return FLM_ERR_SHAPE;
+  }
+  rc = track_assoc_check_sizes(who, d, k, c, state != nullptr, in_h, in_w, fh, fw, opts);
+  if (rc != FLM_OK) return rc;
+  return launch_track_associate_streams(static_cast<hipStream_t>(stream), det, n_det, s, d, k, c, in_h, in_w, fh, fw, opts,
+                                        m_crop, boxes, status, misses, state, det_slot, slot_det, counts);
 }
 
 // ---- best shot (flm_quality.hip) ------------------------------------------------------------------------------------

@@ -291,6 +291,10 @@ int launch_track_step(hipStream_t s, const double* lm, size_t lm_stride, const d
 int launch_track_associate(hipStream_t s, const int32_t* det, const int32_t* n_det, int d, int k, int c, int in_h, int in_w,
                            int fh, int fw, const flm_track_assoc_opts* opts, float* m_crop, int32_t* boxes, int32_t* status,
                            int32_t* misses, double* state, int32_t* det_slot, int32_t* slot_det, int32_t* counts);
+int launch_track_associate_streams(hipStream_t s, const int32_t* det, const int32_t* n_det, int n_streams, int d, int k,
+                                   int c, int in_h, int in_w, int fh, int fw, const flm_track_assoc_opts* opts,
+                                   float* m_crop, int32_t* boxes, int32_t* status, int32_t* misses, double* state,
+                                   int32_t* det_slot, int32_t* slot_det, int32_t* counts);
 
 // best shot (flm_quality.hip); pointers, the format, the option structs and overlaps have been checked by the caller
 int launch_face_quality(hipStream_t s, const void* faces, int k, int h, int w, const flm_image_format* fmt,

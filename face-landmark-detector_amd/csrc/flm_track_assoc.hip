@@ -15,6 +15,9 @@
 // overwritten in LDS by the empty box, which intersects nothing: a scan reads one 16-byte box per pair and no flag,
 // four pairs' boxes before it evaluates the first, so the LDS latency is paid once per four pairs.  The number of
 // rounds depends on the data (one round per match at worst: every box the same), the number of launches does not.
+//
+// flm_track_associate_streams runs the same body once per stream, one workgroup each, in one launch of S workgroups,
+// on LDS arrays of 64, 256 or 1024 items -- the smallest that holds max(k, d).
 #include "flm_common.h"
 #include "flm_track_assoc_dev.h"
 #include "flm_track_seed_dev.h"
@@ -97,17 +100,23 @@ __device__ __forceinline__ int assoc_scan(const AssocBox& mine, int64_t my_area,
   return best;
 }
 
-__global__ __launch_bounds__(kAssocMaxItems) void track_assoc_kernel(const TrackAssocArgs g) {
-  __shared__ AssocBox tb[kAssocMaxItems], db[kAssocMaxItems];  // clipped boxes: slots, detections
-  __shared__ int s_free[kAssocMaxItems], d_free[kAssocMaxItems];  // still to be matched
-  __shared__ int s_best[kAssocMaxItems], d_best[kAssocMaxItems];  // a round's choices; later: born-from, the dead list
-  __shared__ int fill[kAssocMaxItems];                            // the slot's state rows are to be reset
-  __shared__ int wave_cnt[2][kAssocMaxItems / 64];
+// One association, by one workgroup of max(k, d) threads rounded up to whole waves, on LDS arrays of CAP >= max(k, d)
+// items: the body of both kernels below.  g names the K slots, the D detection rows and the outputs of THIS association;
+// slot_base is what det_slot adds to a slot's index (the slot's place in a tracker that holds several associations'
+// slots; slot_det and everything else stay local).  Integers and fixed float64 products only, and no loop bound but
+// the wave-count loop depends on CAP: every CAP gives the same bits.
+template <int CAP>
+__device__ __forceinline__ void track_assoc_body(const TrackAssocArgs& g, const int slot_base) {
+  __shared__ AssocBox tb[CAP], db[CAP];    // clipped boxes: slots, detections
+  __shared__ int s_free[CAP], d_free[CAP];  // still to be matched
+  __shared__ int s_best[CAP], d_best[CAP];  // a round's choices; later: born-from, the dead list
+  __shared__ int fill[CAP];                 // the slot's state rows are to be reset
+  __shared__ int wave_cnt[2][CAP / 64];
   __shared__ int cnt[8];
   const int i = threadIdx.x, k = g.k, d = g.d;
   const int lane = i & 63, wave = i >> 6;
   if (i < 8) cnt[i] = 0;
-  if (i < 2 * (kAssocMaxItems / 64)) (&wave_cnt[0][0])[i] = 0;
+  if (i < 2 * (CAP / 64)) (&wave_cnt[0][0])[i] = 0;
   int nd = d;
   if (g.n_det) {
     const int v = *g.n_det;
@@ -175,7 +184,7 @@ __global__ __launch_bounds__(kAssocMaxItems) void track_assoc_kernel(const Track
       my_det = sb;
       m_in = sbi;
       m_un = sbu;
-      g.det_slot[sb] = i;
+      g.det_slot[sb] = slot_base + i;
       sb = -2;
     }
     if (!any) break;
@@ -195,7 +204,7 @@ __global__ __launch_bounds__(kAssocMaxItems) void track_assoc_kernel(const Track
   s_best[i] = -1;  // from here: the detection a slot is born from
   __syncthreads();
   int n_dead = 0;
-  for (int w = 0; w < kAssocMaxItems / 64; ++w) {
+  for (int w = 0; w < CAP / 64; ++w) {
     const int a = wave_cnt[0][w], b = wave_cnt[1][w];
     n_dead += a;
     if (w < wave) {
@@ -209,7 +218,7 @@ __global__ __launch_bounds__(kAssocMaxItems) void track_assoc_kernel(const Track
     if (r_unm < n_dead) {
       const int slot = d_best[r_unm];
       s_best[slot] = i;
-      g.det_slot[i] = slot;
+      g.det_slot[i] = slot_base + slot;
       atomicAdd(&cnt[CNT_BORN], 1);
     } else {
       g.det_slot[i] = -2;
@@ -266,9 +275,44 @@ __global__ __launch_bounds__(kAssocMaxItems) void track_assoc_kernel(const Track
   }
 }
 
-int launch_track_associate(hipStream_t s, const int32_t* det, const int32_t* n_det, int d, int k, int c, int in_h, int in_w,
-                           int fh, int fw, const flm_track_assoc_opts* opts, float* m_crop, int32_t* boxes, int32_t* status,
-                           int32_t* misses, double* state, int32_t* det_slot, int32_t* slot_det, int32_t* counts) {
+// flm_track_associate: one workgroup, the arrays of the largest problem.
+__global__ __launch_bounds__(kAssocMaxItems) void track_assoc_kernel(const TrackAssocArgs g) {
+  track_assoc_body<kAssocMaxItems>(g, 0);
+}
+
+// flm_track_associate_streams: workgroup s is the association of stream s on its own slices -- slots [s*k, (s+1)*k),
+// the rows det[s], n_det[s], det_slot[s], counts[s] -- so no pair of two streams exists.  LDS is dimensioned by CAP
+// (3.4 KB at 64, 13 KB at 256), which is what lets many streams of a camera-sized tracker share a CU.  A stream whose
+// n_det is negative is skipped: its workgroup writes the three outputs and returns before the first barrier, having
+// read and written nothing of the stream's state; the test is uniform over the workgroup.
+template <int CAP>
+__global__ __launch_bounds__(CAP) void track_assoc_streams_kernel(const TrackAssocArgs g) {
+  const int s = blockIdx.x, i = threadIdx.x, k = g.k, d = g.d;
+  const size_t slot0 = (size_t)s * k, det0 = (size_t)s * d;
+  if (g.n_det && g.n_det[s] < 0) {
+    if (i < d) g.det_slot[det0 + i] = -1;
+    if (i < k) g.slot_det[slot0 + i] = -1;
+    if (i < 8) g.counts[(size_t)s * 8 + i] = 0;
+    return;
+  }
+  TrackAssocArgs h = g;
+  h.det = g.det + 4 * det0;
+  h.n_det = g.n_det ? g.n_det + s : nullptr;
+  h.m_crop = g.m_crop + 6 * slot0;
+  h.boxes = g.boxes + 4 * slot0;
+  h.status = g.status + slot0;
+  h.misses = g.misses + slot0;
+  h.state = g.state ? g.state + slot0 * (size_t)g.c * 6 : nullptr;
+  h.det_slot = g.det_slot + det0;
+  h.slot_det = g.slot_det + slot0;
+  h.counts = g.counts + (size_t)s * 8;
+  track_assoc_body<CAP>(h, (int)slot0);
+}
+
+static TrackAssocArgs track_assoc_args(const int32_t* det, const int32_t* n_det, int d, int k, int c, int in_h, int in_w,
+                                       int fh, int fw, const flm_track_assoc_opts* opts, float* m_crop, int32_t* boxes,
+                                       int32_t* status, int32_t* misses, double* state, int32_t* det_slot,
+                                       int32_t* slot_det, int32_t* counts) {
   TrackAssocArgs g;
   g.det = det; g.n_det = n_det; g.d = d; g.k = k; g.c = c;
   g.in_h = in_h; g.in_w = in_w; g.fh = fh; g.fw = fw;
@@ -276,9 +320,36 @@ int launch_track_associate(hipStream_t s, const int32_t* det, const int32_t* n_d
   g.match_iou = opts->match_iou; g.dup_iou = opts->dup_iou; g.refresh_iou = opts->refresh_iou;
   g.m_crop = m_crop; g.boxes = boxes; g.status = status; g.misses = misses; g.state = state;
   g.det_slot = det_slot; g.slot_det = slot_det; g.counts = counts;
+  return g;
+}
+
+int launch_track_associate(hipStream_t s, const int32_t* det, const int32_t* n_det, int d, int k, int c, int in_h, int in_w,
+                           int fh, int fw, const flm_track_assoc_opts* opts, float* m_crop, int32_t* boxes, int32_t* status,
+                           int32_t* misses, double* state, int32_t* det_slot, int32_t* slot_det, int32_t* counts) {
+  const TrackAssocArgs g = track_assoc_args(det, n_det, d, k, c, in_h, in_w, fh, fw, opts, m_crop, boxes, status, misses,
+                                            state, det_slot, slot_det, counts);
   const int n = k > d ? k : d;
   track_assoc_kernel<<<1, cdiv(n, 64) * 64, 0, s>>>(g);
   FLM_LAUNCH_CHECK("track_assoc_kernel");
+  return FLM_OK;
+}
+
+// The smallest item capacity that holds max(k, d); the workgroup has max(k, d) threads rounded up to whole waves.
+int launch_track_associate_streams(hipStream_t s, const int32_t* det, const int32_t* n_det, int n_streams, int d, int k,
+                                   int c, int in_h, int in_w, int fh, int fw, const flm_track_assoc_opts* opts,
+                                   float* m_crop, int32_t* boxes, int32_t* status, int32_t* misses, double* state,
+                                   int32_t* det_slot, int32_t* slot_det, int32_t* counts) {
+  const TrackAssocArgs g = track_assoc_args(det, n_det, d, k, c, in_h, in_w, fh, fw, opts, m_crop, boxes, status, misses,
+                                            state, det_slot, slot_det, counts);
+  const int n = k > d ? k : d;
+  const dim3 grid(n_streams), block(cdiv(n, 64) * 64);
+  if (n <= 64)
+    track_assoc_streams_kernel<64><<<grid, block, 0, s>>>(g);
+  else if (n <= 256)
+    track_assoc_streams_kernel<256><<<grid, block, 0, s>>>(g);
+  else
+    track_assoc_streams_kernel<kAssocMaxItems><<<grid, block, 0, s>>>(g);
+  FLM_LAUNCH_CHECK("track_assoc_streams_kernel");
   return FLM_OK;
 }
 

@@ -584,12 +584,17 @@ class FaceTracker:
     the best one of its track: the tracker then owns `gallery` [capacity,...] in the aligned format, `best_q` float64
     [capacity] (-1: none yet), `best_frame` int64, `best_M` float32 [capacity,2,3], `best_landmarks` float64
     [capacity,C,2] and `best_rec` int64 [capacity,8]; `best()` hands them out.  A seed, and a birth in `update`, make
-    the slot forget its best with the next step; a track that ends keeps its best readable until then."""
+    the slot forget its best with the next step; a track that ends keeps its best readable until then.  streams: how
+    many streams (cameras) share the tracker, an integer in [1, capacity] that divides capacity: slot t belongs to
+    stream t // slots_per_stream, `step` takes one ring slot per stream and `update` one list of detections per stream
+    (alignment.track_associate_streams_device: no pair of two streams is ever evaluated); every tensor the tracker
+    owns or returns stays flat over the `capacity` global slots.  With streams=1 every method is the single-stream
+    code, launch for launch."""
 
     def __init__(self, model, frame_hw, capacity, out_size=(112, 112), template=None, crop_template=None, n_points=4,
                  thresh=0.0, weights=None, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"),
                  crop_samples=1, samples=1, aligned_format=None, frame_format=None, smooth=None, associate=None,
-                 best_shot=None):
+                 best_shot=None, streams=1):
         import torch
         if best_shot is True:
             best_shot = alignment.BestShot()
@@ -613,6 +618,9 @@ class FaceTracker:
         capacity = int(capacity)
         if not 1 <= capacity <= 65535:
             raise ValueError("capacity must be in [1, 65535] (got %d)" % capacity)
+        if isinstance(streams, bool) or int(streams) != streams or not 1 <= int(streams) <= capacity or capacity % int(streams):
+            raise ValueError("streams must be an integer in [1, capacity] that divides capacity (got %r, capacity %d)"
+                             % (streams, capacity))
         oh, ow = [int(v) for v in out_size]
         if oh < 1 or ow < 1:
             raise ValueError("out_size must be positive")
@@ -637,6 +645,7 @@ class FaceTracker:
         self.aligned_format, self.frame_format = aligned_format, frame_format
         self.smooth, self.filter_state = smooth, None
         self.associate = associate
+        self.streams, self.slots_per_stream = int(streams), capacity // int(streams)
         self.best_shot, self.gallery, self._steps = best_shot, None, 0
         self._crop_format = alignment.AlignedFormat("nhwc", "uint8")
         self._templates = (np.ascontiguousarray(tm, np.float64), np.ascontiguousarray(tc, np.float64))
@@ -671,12 +680,19 @@ class FaceTracker:
             self._quality_rec = torch.zeros_like(self.best_rec)
             self._best_reset = torch.zeros((n,), dtype=torch.int32, device=dev)
 
-    def seed(self, slots, boxes):
+    def seed(self, slots, boxes, stream=None):
         """Start (or restart) the tracks `slots` from the detector boxes `boxes` (x0,y0,x1,y1), one per slot: the host
-        box maths of `face_boxes`, one upload, flm_track_seed, and the results placed in those slots on the device."""
+        box maths of `face_boxes`, one upload, flm_track_seed, and the results placed in those slots on the device.
+        `slots` are global slots, or, with `stream` given, slots of that stream counted from its first one."""
         import torch
         slots = [int(v) for v in slots]
         boxes = [list(b) for b in boxes]
+        if stream is not None:
+            if isinstance(stream, bool) or int(stream) != stream or not 0 <= int(stream) < self.streams:
+                raise ValueError("stream must be in [0, %d) (got %r)" % (self.streams, stream))
+            if any(not 0 <= v < self.slots_per_stream for v in slots):
+                raise ValueError("the slots of a stream must be in [0, %d)" % self.slots_per_stream)
+            slots = [int(stream) * self.slots_per_stream + v for v in slots]
         if len(slots) != len(boxes) or any(len(b) != 4 for b in boxes):
             raise ValueError("seed takes one (x0,y0,x1,y1) box per slot")
         if any(not 0 <= v < self.capacity for v in slots) or len(set(slots)) != len(slots):
@@ -708,8 +724,16 @@ class FaceTracker:
         a host list or array of integer boxes: one upload.  Returns CUDA tensors (det_slot int32 [D], slot_det int32
         [capacity], counts int32 [8]) as `track_associate_device` describes them.  No download, no synchronisation.
         May be called between any two steps: it edits the matrices and boxes the NEXT step cuts its crops with, not the
-        ones the last aligned warp used."""
+        ones the last aligned warp used.
+        A tracker of several streams takes a CUDA int32 [streams,D,4] tensor -- `n` is then None or CUDA int32
+        [streams], a negative count skipping the stream (its detector did not run: its tracks are neither confirmed nor
+        charged a miss) -- or a host sequence of one entry per stream, a list of integer boxes (empty: the detector ran
+        and found nothing) or None (skipped): one upload of boxes and counts.  Returns (det_slot int32 [streams,D] in
+        global slots, slot_det int32 [capacity], counts int32 [streams,8]) as `track_associate_streams_device`
+        describes them."""
         import torch
+        if self.streams > 1:
+            return self._update_streams(detections, n)
         if self.capacity > alignment.ASSOC_MAX:
             raise ValueError("update takes a tracker of at most %d slots (capacity %d)" % (alignment.ASSOC_MAX, self.capacity))
         if isinstance(detections, torch.Tensor):
@@ -742,9 +766,97 @@ class FaceTracker:
             self._best_reset.masked_fill_(was_empty & (out[1] >= 0), 1)
         return out
 
+    def _update_streams(self, detections, n):
+        import torch
+        s, k = self.streams, self.slots_per_stream
+        if k > alignment.ASSOC_MAX:
+            raise ValueError("update takes at most %d slots per stream (this tracker has %d)" % (alignment.ASSOC_MAX, k))
+        if isinstance(detections, torch.Tensor):
+            det = detections
+            if det.dim() != 3 or int(det.shape[0]) != s or int(det.shape[2]) != 4 or det.dtype != torch.int32:
+                raise ValueError("update takes a CUDA int32 [%d,D,4] tensor or one list of integer boxes per stream" % s)
+            if n is not None and not isinstance(n, torch.Tensor):
+                raise ValueError("n must be None or a CUDA int32 [%d] tensor" % s)
+            d = int(det.shape[1])
+        else:
+            if n is not None:
+                raise ValueError("n goes with detections on the device; a host entry of None skips its stream")
+            rows = list(detections)
+            if len(rows) != s:
+                raise ValueError("update takes one entry per stream (%d), got %d" % (s, len(rows)))
+            arrs = []
+            for r in rows:
+                if r is None:
+                    arrs.append(None)
+                    continue
+                a = np.asarray(r)
+                if a.size == 0:
+                    a = np.zeros((0, 4), np.int64)
+                if a.ndim != 2 or a.shape[1] != 4 or a.dtype.kind not in "iu":
+                    raise ValueError("every stream's entry is None or a list of integer (x0,y0,x1,y1) boxes")
+                if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+                    raise ValueError("a box coordinate does not fit int32")
+                arrs.append(a)
+            d = max([1] + [len(a) for a in arrs if a is not None])
+        if d > alignment.ASSOC_MAX:
+            raise ValueError("update takes at most %d detections per stream (got %d)" % (alignment.ASSOC_MAX, d))
+        if d < 1:
+            raise ValueError("update takes at least one row of detections per stream (n says how many are valid)")
+        self._state()
+        if not isinstance(detections, torch.Tensor):
+            flat = np.zeros(s * d * 4 + s, np.int32)
+            pad, cnt = flat[:s * d * 4].reshape(s, d, 4), flat[s * d * 4:]
+            for i, a in enumerate(arrs):
+                cnt[i] = -1 if a is None else len(a)
+                if a is not None and len(a):
+                    pad[i, :len(a)] = a
+            both = torch.from_numpy(flat).to(self.boxes.device)
+            det, n = both[:s * d * 4].view(s, d, 4), both[s * d * 4:]
+        if self.best_shot is not None:  # the slots that hold no track now: the association's own test, on the device
+            fh, fw = self.frame_hw
+            b = self.boxes
+            was_empty = ((b[:, 2].clamp(0, fw) - b[:, 0].clamp(0, fw) <= 0)
+                         | (b[:, 3].clamp(0, fh) - b[:, 1].clamp(0, fh) <= 0))
+        out = alignment.track_associate_streams_device(det, self.m_crop, self.boxes, self.status, self.misses, k,
+                                                       (self.model.input_height, self.model.input_width), self.frame_hw,
+                                                       n_det=n, state=self.filter_state, assoc=self.associate)
+        if self.best_shot is not None:  # (a skipped stream has slot_det == -1 and resets nothing)
+            self._best_reset.masked_fill_(was_empty & (out[1] >= 0), 1)
+        return out
+
+    def _stream_frames(self, frame_index, nf):
+        """frame_index of a tracker of several streams -> `frame_slots`, the ring slot of every global slot: a host
+        sequence is checked against the ring and uploaded, a CUDA int32 [streams] tensor is used where it lies; the
+        expansion over the slots of a stream is a device copy."""
+        import torch
+        s, k = self.streams, self.slots_per_stream
+        if isinstance(frame_index, torch.Tensor):
+            if (frame_index.dtype != torch.int32 or not frame_index.is_cuda or not frame_index.is_contiguous()
+                    or tuple(frame_index.shape) != (s,)):
+                raise ValueError("frame_index must be a sequence of %d ring slots or a contiguous CUDA int32 [%d] tensor"
+                                 % (s, s))
+            idx = None
+        else:
+            try:
+                idx = list(frame_index)
+            except TypeError:
+                idx = None
+            if idx is None or len(idx) != s:
+                raise ValueError("frame_index must be a sequence of %d ring slots or a contiguous CUDA int32 [%d] tensor"
+                                 % (s, s))
+            if any(isinstance(v, bool) or int(v) != v or not 0 <= int(v) < nf for v in idx):
+                raise ValueError("frame_index must name ring slots in [0, %d)" % nf)
+        self._state()
+        if idx is not None:
+            frame_index = torch.tensor([int(v) for v in idx], dtype=torch.int32).to(self.boxes.device)
+        self.frame_slots.view(s, k).copy_(frame_index.view(s, 1).expand(s, k))
+
     def step(self, ring, frame_index, dt=None, frame_id=None):
         """One frame for every slot: `ring` is the frame ring (`frame_format` says how it holds its pixels),
-        `frame_index` the ring slot of the new frame.  Sequence: the uint8 crop warp with the slots' matrices ->
+        `frame_index` the ring slot of the new frame -- for a tracker of several streams one ring slot per stream, a
+        host sequence (checked against the ring, one upload) or a contiguous CUDA int32 [streams] tensor (used as it is,
+        nothing transferred; an index outside the ring gives zero crops): slot t reads the frame of stream
+        t // slots_per_stream.  Sequence: the uint8 crop warp with the slots' matrices ->
         model.forward_device -> alignment.track_step_device (landmarks to frame px, the aligned fit, the next crop's
         matrix and box, the status) -> the aligned warp.  Returns CUDA tensors (aligned [capacity,oh,ow,3] float32 or in
         `aligned_format`, M float32 [capacity,2,3] frame px -> aligned px, landmarks float64 [capacity,C,2] in frame px,
@@ -770,14 +882,18 @@ class FaceTracker:
             nf, rh, rw, _ = alignment.FrameFormat.bgr().ring(ring)
         if (rh, rw) != (fh, fw):
             raise ValueError("the ring holds %dx%d frames, the tracker was made for %dx%d" % (rh, rw, fh, fw))
-        frame_index = int(frame_index)
-        if not 0 <= frame_index < nf:
-            raise ValueError("frame_index must name a ring slot in [0, %d)" % nf)
+        if self.streams > 1:
+            self._stream_frames(frame_index, nf)
+        else:
+            frame_index = int(frame_index)
+            if not 0 <= frame_index < nf:
+                raise ValueError("frame_index must name a ring slot in [0, %d)" % nf)
         self._state()
         filt = {} if self.smooth is None else dict(filter=self.smooth, dt=dt, state=self.filter_state)
         model = self.model
         ih, iw = model.input_height, model.input_width
-        self.frame_slots.fill_(frame_index)
+        if self.streams == 1:
+            self.frame_slots.fill_(frame_index)
         crops = alignment.warp_frames_device(ring, self.m_crop, ih, iw, frame_index_dev=self.frame_slots,
                                              boxes_dev=self.boxes, samples=self.crop_samples, fmt=self._crop_format,
                                              src=self.frame_format)

@@ -848,6 +848,43 @@ int flm_track_associate(flm_stream_t stream, const int32_t* det_dev /*[D,4]*/, c
                         int32_t* det_slot_dev /*[D] out*/, int32_t* slot_det_dev /*[K] out*/,
                         int32_t* counts_dev /*[8] out*/);
 
+/* flm_track_associate_streams: the association above for S streams (cameras) that share one tracker of S*K slots, in
+ * ONE launch of S workgroups -- one per stream, on LDS sized to max(k, d) (64, 256 or 1024 items), so that many
+ * streams of a camera-sized tracker share a CU.  opts and every size but s are common to all streams.
+ * In:  det_dev int32 [S,D,4]; n_det_dev NULL or int32 [S] on the device; opts (NULL = the defaults).
+ * In/out: m_crop_dev [S*K,2,3], boxes_dev [S*K,4], status_dev [S*K], misses_dev int32 [S*K], state_dev NULL or float64
+ *      [S*K,C,6].
+ * Out: det_slot_dev int32 [S,D], slot_det_dev int32 [S*K], counts_dev int32 [S,8].  No two arguments may overlap.
+ * Contract:
+ *  1. Stream i owns the slots [i*K, (i+1)*K) of the five state tensors and of slot_det, and the rows det[i], n_det[i],
+ *     det_slot[i] and counts[i].  k is the number of slots PER STREAM.
+ *  2. For every stream that is not skipped (4) the call writes on the stream's blocks what
+ *       flm_track_associate(det[i], n_det ? &n_det[i] : NULL, d, k, ...)
+ *     writes on those slices, bit for bit, with one difference (3).
+ *  3. det_slot[i][j], where it names a slot, holds the GLOBAL slot i*K + t, the index into the [S*K] tensors; -1 (void
+ *     or unread) and -2 (no free slot) keep their meaning.  slot_det[i*K + t] stays the row j inside det[i].
+ *  4. n_det[i] < 0: stream i is SKIPPED -- its detector did not run this time.  Nothing of its state is read or
+ *     written: m_crop, boxes, status, misses and state keep their bits.
+ *  5. A skipped stream's outputs: det_slot[i][:] = -1, slot_det[i*K ..] = -1, counts[i][:] = 0.
+ *  6. With n_det_dev NULL no stream is skipped.  n_det[i] == 0 means "ran and found nothing": item 1 of
+ *     flm_track_associate gives nd = 0, every surviving live slot counts a miss (item 8 there).
+ *  7. No pair of two different streams is ever evaluated: a face at the same pixels of two cameras is two faces, and a
+ *     detection of one stream neither confirms nor restarts nor starts a track of another.
+ *  8. Every stream's result is the same whichever LDS size the launcher picks (integers and fixed float64 products
+ *     only), and does not depend on the other streams.
+ *  9. One launch whatever the data, no workspace, no allocation, no synchronisation.
+ * 10. Errors, all found before anything is launched: the null, struct_size and reserved checks of flm_track_associate
+ *     -> FLM_ERR_ARG.  FLM_ERR_SHAPE, the limit named in flm_last_error(), unless 1 <= s, s*k <= 65535 (the capacity
+ *     cap of the warps and the tracker), 1 <= k <= 1024, 1 <= d <= 1024, and the c, size, 2^30, max_misses and NaN
+ *     rules of flm_track_associate hold. */
+int flm_track_associate_streams(flm_stream_t stream, const int32_t* det_dev /*[S,D,4]*/,
+                                const int32_t* n_det_dev /*NULL or [S]*/, int s, int d, int k /*slots PER STREAM*/, int c,
+                                int in_h, int in_w, int fh, int fw, const flm_track_assoc_opts* opts /*NULL = defaults*/,
+                                float* m_crop_dev /*[S*K,2,3]*/, int32_t* boxes_dev /*[S*K,4]*/,
+                                int32_t* status_dev /*[S*K]*/, int32_t* misses_dev /*[S*K]*/,
+                                double* state_dev /*NULL or [S*K,C,6]*/, int32_t* det_slot_dev /*[S,D] out*/,
+                                int32_t* slot_det_dev /*[S*K] out*/, int32_t* counts_dev /*[S,8] out*/);
+
 /* ---- the best shot of a track: face quality and gallery ---------------------------------------------------------------
  * A matcher embeds a track's best face, not every face.  The two calls below judge the aligned faces where the warp
  * left them and keep, per slot, the best one seen so far -- three launches per step, no workspace, no allocation, no
