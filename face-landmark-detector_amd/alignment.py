@@ -1031,3 +1031,241 @@ def track_best_update_device(faces, rec, lm, best_q_in, best_q_out, gallery, bes
             p(weights), wst, c, p(factor), p(m), int(frame_id), _lib.C.byref(co), _lib.ptr(best_q_in), _lib.ptr(best_q_out),
             _lib.ptr(gallery), _lib.ptr(best_frame), p(best_m), p(best_lm), p(best_rec)), "flm_track_best_update")
     return best_q_out
+
+
+# ---- rows: stepping the streams that delivered a frame, each on its own clock (include/flm.h, "rows") -----------------
+def _check_overlap(a, b, what):
+    if (a is not None and b is not None and a.numel() and b.numel()
+            and a.data_ptr() < b.data_ptr() + b.numel() * b.element_size()
+            and b.data_ptr() < a.data_ptr() + a.numel() * a.element_size()):
+        raise ValueError("%s must be two buffers that do not overlap" % what)
+
+
+def track_gather_streams_device(active, m_crop, boxes, slots_per_stream, frame_index=None, dt=None, best_q=None,
+                                reset=None, out=None):
+    """The snapshot a step of some streams starts from, in one launch (flm_track_gather_streams; include/flm.h states it).
+
+    active: contiguous CUDA int32 [A] stream ids (distinct; an id outside [0, S) gives K inert rows); m_crop CUDA float32
+    [S*K,2,3] and boxes CUDA int32 [S*K,4]: the tracker's state, K = slots_per_stream; frame_index: None (ring slot 0) or
+    CUDA int32 [S]; dt: None or CUDA float64 [S]; best_q: None or CUDA float64 [S*K]; reset: None or CUDA int32 [S*K], read
+    and then cleared for the named streams (the pending reset moves into the snapshot).  Returns a dict of compact CUDA
+    tensors over the A*K rows: slot int32 [A*K] (-1: inert), m float32 [A*K,2,3], boxes int32 [A*K,4], frame_index int32
+    [A*K], and dt float64, best_q float64, reset int32 [A*K], each present when its input is.  out: None or a dict that
+    names where to write (any of those keys); only what it does not name is allocated."""
+    import torch
+    k = int(slots_per_stream)
+    if (not isinstance(active, torch.Tensor) or active.dtype != torch.int32 or active.dim() != 1 or not active.is_cuda
+            or not active.is_contiguous() or int(active.shape[0]) < 1):
+        raise ValueError("active must be a contiguous CUDA int32 [A] tensor with A >= 1")
+    a = int(active.shape[0])
+    _check_matrices(m_crop, None, "m_crop")
+    n = int(m_crop.shape[0])
+    if k < 1 or n < 1 or n % k:
+        raise ValueError("m_crop holds %d slots: slots_per_stream=%d must be >= 1 and divide it" % (n, k))
+    s = n // k
+    if n > 65535 or a * k > 65535:
+        raise ValueError("at most 65535 slots and 65535 rows (got %d slots, %d rows)" % (n, a * k))
+    _check_boxes(boxes, n)
+    if frame_index is not None:
+        _check_out(frame_index, torch.int32, (s,), "frame_index")
+    if dt is not None:
+        _check_out(dt, torch.float64, (s,), "dt")
+    if best_q is not None:
+        _check_out(best_q, torch.float64, (n,), "best_q")
+    if reset is not None:
+        _check_out(reset, torch.int32, (n,), "reset")
+    out = dict(out or {})
+    rows, dev = a * k, m_crop.device
+    spec = (("slot", torch.int32, (rows,), True), ("m", torch.float32, (rows, 2, 3), True),
+            ("boxes", torch.int32, (rows, 4), True), ("frame_index", torch.int32, (rows,), True),
+            ("dt", torch.float64, (rows,), dt is not None), ("best_q", torch.float64, (rows,), best_q is not None),
+            ("reset", torch.int32, (rows,), reset is not None))
+    if set(out) - {name for name, *_ in spec}:
+        raise ValueError("out names %r, which the gather does not write" % sorted(set(out) - {n_ for n_, *_ in spec}))
+    for name, dtype, shape, wanted in spec:
+        if not wanted:
+            if out.get(name) is not None:
+                raise ValueError("out[%r] needs its input" % name)
+            out.pop(name, None)
+        elif out.get(name) is None:
+            out[name] = torch.empty(shape, dtype=dtype, device=dev)
+        else:
+            _check_out(out[name], dtype, shape, "out[%r]" % name)
+    _check_overlap(out["m"], m_crop, "out['m'] and m_crop")
+    _check_overlap(out["boxes"], boxes, "out['boxes'] and boxes")
+    _check_overlap(out.get("best_q"), best_q, "out['best_q'] and best_q")
+    _check_overlap(out.get("reset"), reset, "out['reset'] and reset")
+    p = lambda t: None if t is None else _lib.ptr(t)
+    _lib.check(_lib.load().flm_track_gather_streams(
+        _lib.stream_ptr(), _lib.ptr(active), a, s, k, p(frame_index), p(dt), _lib.ptr(m_crop), _lib.ptr(boxes), p(best_q),
+        p(reset), _lib.ptr(out["slot"]), _lib.ptr(out["m"]), _lib.ptr(out["boxes"]), _lib.ptr(out["frame_index"]),
+        p(out.get("dt")), p(out.get("best_q")), p(out.get("reset"))), "flm_track_gather_streams")
+    return out
+
+
+def track_step_rows_device(lm, m_crop_c, boxes_c, slot, grid_hw, in_hw, frame_hw, tmpl_crop, m_next, boxes_next, status,
+                           tmpl_align=None, weights=None, min_points=2, min_score=0.0, min_side=0.0,
+                           max_side=float("inf"), lm_frame=None, m_align=None, status_rows=None, filter=None, dt=None,
+                           state=None, lm_raw=None):
+    """`track_step_device` on the rows of a compacted batch, in one launch (flm_track_step_rows; include/flm.h).
+
+    lm, weights, m_crop_c CUDA float32 [N,2,3] and boxes_c CUDA int32 [N,4] are read at the row; slot: contiguous CUDA
+    int32 [N], the global slot of every row (outside [0, n_slots): the row is inert).  m_next CUDA float32 [n_slots,2,3],
+    boxes_next CUDA int32 [n_slots,4], status CUDA int32 [n_slots] and, with `filter`, state CUDA float64 [n_slots,C,6]
+    are the tracker's own tensors, written at the slot; slots no row names keep their bits.  m_next and boxes_next may be
+    the tensors m_crop_c and boxes_c were gathered from, but not m_crop_c and boxes_c themselves.  dt: None (1/filter.fps),
+    a host number, or a CUDA float64 [N] tensor of one time step per row (a row whose dt is not > 0 and finite loses its
+    history and nothing else).  Returns (lm_frame float64 [N,C,2], m_align float32 [N,2,3] or None, status_rows int32
+    [N]); lm_frame, m_align, status_rows and lm_raw name where to write."""
+    import torch
+    dt_rows = None
+    if filter is None:
+        if dt is not None or state is not None or lm_raw is not None:
+            raise ValueError("dt, state and lm_raw go with filter")
+    else:
+        if not isinstance(filter, LandmarkFilter):
+            raise ValueError("filter must be None or a LandmarkFilter (got %r)" % (filter,))
+        if isinstance(dt, torch.Tensor):
+            dt_rows, dt = dt, 0.0
+        else:
+            dt = filter.time_step(dt)
+        if (not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or state.dim() != 3
+                or int(state.shape[2]) != 6):
+            raise ValueError("state must be a contiguous CUDA float64 [n_slots,C,6] tensor")
+    lm, ls = _strided_points(lm)
+    n, c = int(lm.shape[0]), int(lm.shape[1])
+    _check_out(slot, torch.int32, (n,), "slot")
+    _check_matrices(m_next, None, "m_next")
+    n_slots = int(m_next.shape[0])
+    if not 1 <= n_slots <= 65535 or n > 65535:
+        raise ValueError("at most 65535 slots and 65535 rows, at least one slot (got %d slots, %d rows)" % (n_slots, n))
+    _check_boxes(boxes_next, n_slots)
+    _check_out(status, torch.int32, (n_slots,), "status")
+    if filter is not None:
+        _check_out(state, torch.float64, (n_slots, c, 6), "state")
+        if dt_rows is not None:
+            _check_out(dt_rows, torch.float64, (n,), "dt")
+        if lm_raw is not None:
+            _check_out(lm_raw, torch.float64, (n, c, 2), "lm_raw")
+    _check_matrices(m_crop_c, n, "m_crop_c")
+    _check_boxes(boxes_c, n)
+    gh, gw = _sizes(grid_hw, "grid_hw")
+    ih, iw = _sizes(in_hw, "in_hw")
+    fh, fw = _sizes(frame_hw, "frame_hw")
+    _check_out(tmpl_crop, torch.float64, (c, 2), "tmpl_crop")
+    if tmpl_align is not None:
+        _check_out(tmpl_align, torch.float64, (c, 2), "tmpl_align")
+    wst = 1
+    if weights is not None:
+        if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64 or tuple(weights.shape) != (n, c)
+                or not weights.is_cuda):
+            raise ValueError("weights must be a CUDA float64 [%d,%d] tensor" % (n, c))
+        wst = _uniform_stride(weights, 1)
+        if wst is None:
+            weights, wst = weights.contiguous(), 1
+    if m_align is not None and tmpl_align is None:
+        raise ValueError("m_align needs tmpl_align")
+    if int(min_points) < 2:
+        raise ValueError("min_points must be 2 or more")
+    if any(v != v for v in (float(min_score), float(min_side), float(max_side))):
+        raise ValueError("min_score, min_side and max_side must not be NaN")
+    dev = lm.device
+    if lm_frame is None:
+        lm_frame = torch.empty((n, c, 2), dtype=torch.float64, device=dev)
+    else:
+        _check_out(lm_frame, torch.float64, (n, c, 2), "lm_frame")
+    if tmpl_align is not None:
+        if m_align is None:
+            m_align = torch.empty((n, 2, 3), dtype=torch.float32, device=dev)
+        else:
+            _check_matrices(m_align, n, "m_align")
+    if status_rows is None:
+        status_rows = torch.empty((n,), dtype=torch.int32, device=dev)
+    else:
+        _check_out(status_rows, torch.int32, (n,), "status_rows")
+    _check_overlap(m_crop_c, m_next, "m_crop_c and m_next")
+    _check_overlap(boxes_c, boxes_next, "boxes_c and boxes_next")
+    _check_overlap(status_rows, status, "status_rows and status")
+    if n and c:
+        opts = _lib.TrackOpts.make(min_points, min_score, min_side, max_side)
+        p = lambda t: None if t is None else _lib.ptr(t)
+        fo = None if filter is None else _lib.TrackFilter.make(filter.min_cutoff, filter.beta, filter.d_cutoff)
+        _lib.check(_lib.load().flm_track_step_rows(
+            _lib.stream_ptr(), _lib.ptr(lm), ls, p(weights), wst, _lib.ptr(m_crop_c), _lib.ptr(boxes_c), n, c, iw / gw,
+            ih / gh, ih, iw, fh, fw, _lib.ptr(tmpl_crop), p(tmpl_align), _lib.C.byref(opts), _lib.ptr(lm_frame), p(m_align),
+            _lib.ptr(m_next), _lib.ptr(boxes_next), _lib.ptr(status), None if fo is None else _lib.C.byref(fo),
+            0.0 if filter is None else dt, p(state), p(lm_raw), _lib.ptr(slot), n_slots, p(dt_rows), _lib.ptr(status_rows)),
+            "flm_track_step_rows")
+    return lm_frame, m_align, status_rows
+
+
+def track_best_update_rows_device(faces, rec, lm, slot, best_q_c, best_q, gallery, best_frame, frame_id, status_rows=None,
+                                  reset_c=None, weights=None, factor=None, m=None, opts=None, best_m=None, best_lm=None,
+                                  best_rec=None):
+    """`track_best_update_device` on the rows of a compacted batch, in one launch (flm_track_best_update_rows).
+
+    faces (N faces), rec int64 [N,8], lm, weights, status_rows, reset_c int32 [N], factor float64 [N], m float32 [N,2,3]
+    and best_q_c float64 [N] -- the snapshot of the slots' best quality, from `track_gather_streams_device` -- are read
+    at the row; slot: contiguous CUDA int32 [N].  best_q float64 [n_slots], gallery [n_slots,...] of the faces' dtype and
+    face shape, best_frame int64 [n_slots] and best_m, best_lm, best_rec (each or None) are the tracker's own, written in
+    place at the slot of a row that is taken; an inert row and a slot no row names write nothing.  best_q_c and best_q
+    must be two buffers.  Returns best_q."""
+    import torch
+    if opts is None:
+        opts = BestShot()
+    elif not isinstance(opts, BestShot):
+        raise ValueError("opts must be None or a BestShot (got %r)" % (opts,))
+    if isinstance(frame_id, bool) or int(frame_id) != frame_id or not -2 ** 63 <= int(frame_id) < 2 ** 63:
+        raise ValueError("frame_id must be an integer that fits int64 (got %r)" % (frame_id,))
+    if not isinstance(faces, torch.Tensor) or faces.dim() < 1 or not faces.is_cuda or not faces.is_contiguous():
+        raise ValueError("faces must be a contiguous CUDA tensor of N faces")
+    n = int(faces.shape[0])
+    if (not isinstance(gallery, torch.Tensor) or gallery.dtype != faces.dtype or gallery.dim() != faces.dim()
+            or gallery.shape[1:] != faces.shape[1:] or not gallery.is_cuda or not gallery.is_contiguous()):
+        raise ValueError("gallery must be a contiguous CUDA tensor of the dtype and face shape of faces")
+    n_slots = int(gallery.shape[0])
+    if not 1 <= n_slots <= 65535 or n > 65535:
+        raise ValueError("at most 65535 slots and 65535 rows, at least one slot (got %d slots, %d rows)" % (n_slots, n))
+    _check_out(slot, torch.int32, (n,), "slot")
+    _check_out(rec, torch.int64, (n, QUALITY_REC), "rec")
+    lm, ls = _strided_points(lm)
+    c = int(lm.shape[1])
+    if int(lm.shape[0]) != n:
+        raise ValueError("lm must be a CUDA float64 [%d,C,2] tensor" % n)
+    wst = 1
+    if weights is not None:
+        if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64 or tuple(weights.shape) != (n, c)
+                or not weights.is_cuda):
+            raise ValueError("weights must be a CUDA float64 [%d,%d] tensor" % (n, c))
+        wst = _uniform_stride(weights, 1)
+        if wst is None:
+            weights, wst = weights.contiguous(), 1
+    for t, dtp, name in ((status_rows, torch.int32, "status_rows"), (reset_c, torch.int32, "reset_c"),
+                         (factor, torch.float64, "factor")):
+        if t is not None:
+            _check_out(t, dtp, (n,), name)
+    if m is not None:
+        _check_matrices(m, n)
+    _check_out(best_q_c, torch.float64, (n,), "best_q_c")
+    _check_out(best_q, torch.float64, (n_slots,), "best_q")
+    _check_overlap(best_q_c, best_q, "best_q_c and best_q")
+    _check_overlap(faces, gallery, "faces and gallery")
+    _check_out(best_frame, torch.int64, (n_slots,), "best_frame")
+    if best_m is not None:
+        if m is None:
+            raise ValueError("best_m needs m")
+        _check_matrices(best_m, n_slots, "best_m")
+    if best_lm is not None:
+        _check_out(best_lm, torch.float64, (n_slots, c, 2), "best_lm")
+    if best_rec is not None:
+        _check_out(best_rec, torch.int64, (n_slots, QUALITY_REC), "best_rec")
+    if n and c:
+        face_bytes = faces.numel() // n * faces.element_size()
+        co = opts.struct()
+        p = lambda t: None if t is None else _lib.ptr(t)
+        _lib.check(_lib.load().flm_track_best_update_rows(
+            _lib.stream_ptr(), _lib.ptr(faces), face_bytes, n, _lib.ptr(rec), p(status_rows), p(reset_c), _lib.ptr(lm), ls,
+            p(weights), wst, c, p(factor), p(m), int(frame_id), _lib.C.byref(co), _lib.ptr(slot), n_slots,
+            _lib.ptr(best_q_c), _lib.ptr(best_q), _lib.ptr(gallery), _lib.ptr(best_frame), p(best_m), p(best_lm),
+            p(best_rec)), "flm_track_best_update_rows")
+    return best_q

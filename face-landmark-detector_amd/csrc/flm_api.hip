@@ -1231,21 +1231,8 @@ void flm_track_filter_init(flm_track_filter* filt) {
   filt->d_cutoff = 1.0;
 }
 
-int flm_track_step_filtered(flm_stream_t stream, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
-                            const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h,
-                            int in_w, int fh, int fw, const double* tmpl_crop, const double* tmpl_align,
-                            const flm_track_opts* opts, double* lm_frame, float* m_align, float* m_next,
-                            int32_t* boxes_next, int32_t* status, const flm_track_filter* filt, double dt, double* state,
-                            double* lm_raw) {
-  const char* who = "flm_track_step_filtered";
-  flm_track_opts defaults;
-  if (const int rc = check_track_step_args(who, lm, m_crop, boxes, tmpl_crop, tmpl_align, &opts, &defaults, lm_frame,
-                                           m_align, m_next, boxes_next, status))
-    return rc;
-  if (!filt || !state) {  // (lm_raw is optional)
-    set_error("%s: null %s", who, !filt ? "filt" : "state_dev");
-    return FLM_ERR_ARG;
-  }
+// The checks of a flm_track_filter that flm_track_step_filtered and flm_track_step_rows share.
+static int check_track_filter(const char* who, const flm_track_filter* filt) {
   if (filt->struct_size < sizeof(flm_track_filter)) {
     set_error("%s: flm_track_filter struct_size %u is smaller than this library's %zu (initialise with "
               "flm_track_filter_init)", who, filt->struct_size, sizeof(flm_track_filter));
@@ -1267,6 +1254,25 @@ int flm_track_step_filtered(flm_stream_t stream, const double* lm, size_t lm_str
     set_error("%s: d_cutoff=%g, needs a finite d_cutoff > 0", who, filt->d_cutoff);
     return FLM_ERR_ARG;
   }
+  return FLM_OK;
+}
+
+int flm_track_step_filtered(flm_stream_t stream, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
+                            const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h,
+                            int in_w, int fh, int fw, const double* tmpl_crop, const double* tmpl_align,
+                            const flm_track_opts* opts, double* lm_frame, float* m_align, float* m_next,
+                            int32_t* boxes_next, int32_t* status, const flm_track_filter* filt, double dt, double* state,
+                            double* lm_raw) {
+  const char* who = "flm_track_step_filtered";
+  flm_track_opts defaults;
+  if (const int rc = check_track_step_args(who, lm, m_crop, boxes, tmpl_crop, tmpl_align, &opts, &defaults, lm_frame,
+                                           m_align, m_next, boxes_next, status))
+    return rc;
+  if (!filt || !state) {  // (lm_raw is optional)
+    set_error("%s: null %s", who, !filt ? "filt" : "state_dev");
+    return FLM_ERR_ARG;
+  }
+  if (const int rc = check_track_filter(who, filt)) return rc;
   if (!(dt > 0.0 && std::isfinite(dt))) {
     set_error("%s: dt=%g, needs a finite dt > 0 (seconds since the previous step)", who, dt);
     return FLM_ERR_ARG;
@@ -1274,6 +1280,72 @@ int flm_track_step_filtered(flm_stream_t stream, const double* lm, size_t lm_str
   return launch_track_step(static_cast<hipStream_t>(stream), lm, lm_stride, wt, w_stride, m_crop, boxes, k, c, sx, sy, in_h,
                            in_w, fh, fw, tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next, status, filt,
                            dt, state, lm_raw);
+}
+
+static bool track_ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+int flm_track_step_rows(flm_stream_t stream, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
+                        const float* m_crop_c, const int32_t* boxes_c, int n, int c, double sx, double sy, int in_h,
+                        int in_w, int fh, int fw, const double* tmpl_crop, const double* tmpl_align,
+                        const flm_track_opts* opts, double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next,
+                        int32_t* status, const flm_track_filter* filt, double dt, double* state, double* lm_raw,
+                        const int32_t* slot, int n_slots, const double* dt_rows, int32_t* status_rows) {
+  const char* who = "flm_track_step_rows";
+  flm_track_opts defaults;
+  if (const int rc = check_track_step_args(who, lm, m_crop_c, boxes_c, tmpl_crop, tmpl_align, &opts, &defaults, lm_frame,
+                                           m_align, m_next, boxes_next, status))
+    return rc;
+  if (!slot || !status_rows) {
+    set_error("%s: null %s", who, !slot ? "slot_dev" : "status_rows_dev");
+    return FLM_ERR_ARG;
+  }
+  if (filt) {
+    if (!state) {  // (lm_raw is optional)
+      set_error("%s: null state_dev", who);
+      return FLM_ERR_ARG;
+    }
+    if (const int rc = check_track_filter(who, filt)) return rc;
+    if (!dt_rows && !(dt > 0.0 && std::isfinite(dt))) {
+      set_error("%s: dt=%g, needs a finite dt > 0 (seconds since the previous step) or dt_dev", who, dt);
+      return FLM_ERR_ARG;
+    }
+  } else if (state || lm_raw || dt_rows) {
+    set_error("%s: state_dev, lm_raw_dev and dt_dev go with filt", who);
+    return FLM_ERR_ARG;
+  }
+  // the compact inputs must not be the tensors the step writes at the slots (the snapshot exists to keep them apart)
+  if (n >= 1 && n <= 65535 && n_slots >= 1 && n_slots <= 65535 &&
+      (track_ranges_overlap(m_crop_c, (size_t)n * 24, m_next, (size_t)n_slots * 24) ||
+       track_ranges_overlap(boxes_c, (size_t)n * 16, boxes_next, (size_t)n_slots * 16) ||
+       track_ranges_overlap(status_rows, (size_t)n * 4, status, (size_t)n_slots * 4))) {
+    set_error("%s: m_crop_c/m_next, boxes_c/boxes_next or status_rows/status overlap (rows are read while slots are "
+              "written: gather a snapshot first)", who);
+    return FLM_ERR_ARG;
+  }
+  return launch_track_step_rows(static_cast<hipStream_t>(stream), lm, lm_stride, wt, w_stride, m_crop_c, boxes_c, n, c, sx,
+                                sy, in_h, in_w, fh, fw, tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next,
+                                status, filt, dt, state, lm_raw, slot, n_slots, dt_rows, status_rows);
+}
+
+int flm_track_gather_streams(flm_stream_t stream, const int32_t* active, int a, int s, int k,
+                             const int32_t* frame_idx_stream, const double* dt_stream, const float* m_crop,
+                             const int32_t* boxes, const double* best_q, int32_t* reset, int32_t* slot_c, float* m_c,
+                             int32_t* boxes_c, int32_t* frame_idx_c, double* dt_c, double* best_q_c, int32_t* reset_c) {
+  const char* who = "flm_track_gather_streams";
+  if (!active || !m_crop || !boxes || !slot_c || !m_c || !boxes_c || !frame_idx_c) {
+    set_error("%s: null argument", who);  // (frame_idx_stream and the three optional groups may be null)
+    return FLM_ERR_ARG;
+  }
+  if ((dt_stream == nullptr) != (dt_c == nullptr) || (best_q == nullptr) != (best_q_c == nullptr) ||
+      (reset == nullptr) != (reset_c == nullptr)) {
+    set_error("%s: dt_stream_dev/dt_c, best_q_dev/best_q_c and reset_dev/reset_c go together (both or neither)", who);
+    return FLM_ERR_ARG;
+  }
+  return launch_track_gather_streams(static_cast<hipStream_t>(stream), active, a, s, k, frame_idx_stream, dt_stream, m_crop,
+                                     boxes, best_q, reset, slot_c, m_c, boxes_c, frame_idx_c, dt_c, best_q_c, reset_c);
 }
 
 // ---- association (flm_track_assoc.hip) ------------------------------------------------------------------------------
@@ -1440,23 +1512,13 @@ static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
   return a0 < b0 + nb && b0 < a0 + na;
 }
 
-int flm_track_best_update(flm_stream_t stream, const void* faces, size_t face_bytes, int k, const int64_t* rec,
-                          const int32_t* status, const int32_t* reset, const double* lm, size_t lm_stride,
-                          const double* wt, size_t w_stride, int c, const double* factor, const float* m,
-                          int64_t frame_id, const flm_best_opts* opts, const double* best_q_in, double* best_q_out,
-                          void* gallery, int64_t* best_frame, float* best_m, double* best_lm, int64_t* best_rec) {
-  const char* who = "flm_track_best_update";
-  if (!faces || !rec || !lm || !best_q_in || !best_q_out || !gallery || !best_frame) {
-    set_error("%s: null argument", who);  // (status, reset, w, factor, m, opts and the last three outputs are optional)
-    return FLM_ERR_ARG;
-  }
-  if (best_m && !m) {
-    set_error("%s: best_m_dev needs m_dev", who);
-    return FLM_ERR_ARG;
-  }
-  flm_best_opts defaults;
-  flm_best_opts_init(&defaults);
-  if (!opts) opts = &defaults;
+// The option and size checks flm_track_best_update and flm_track_best_update_rows share; *popts is replaced by `defaults`
+// when null.  kname: what the call names its number of faces.
+static int check_best_args(const char* who, const flm_best_opts** popts, flm_best_opts* defaults, const char* kname, int k,
+                           int c, size_t face_bytes, size_t lm_stride, const double* wt, size_t w_stride) {
+  flm_best_opts_init(defaults);
+  if (!*popts) *popts = defaults;
+  const flm_best_opts* opts = *popts;
   if (opts->struct_size < sizeof(flm_best_opts)) {
     set_error("%s: flm_best_opts struct_size %u is smaller than this library's %zu (initialise with "
               "flm_best_opts_init)", who, opts->struct_size, sizeof(flm_best_opts));
@@ -1475,7 +1537,7 @@ int flm_track_best_update(flm_stream_t stream, const void* faces, size_t face_by
     return FLM_ERR_ARG;
   }
   if (k < 1 || k > 65535) {
-    set_error("%s: k=%d, needs 1 <= k <= 65535", who, k);
+    set_error("%s: %s=%d, needs 1 <= %s <= 65535", who, kname, k, kname);
     return FLM_ERR_SHAPE;
   }
   if (c < 1) {
@@ -1490,6 +1552,25 @@ int flm_track_best_update(flm_stream_t stream, const void* faces, size_t face_by
     set_error("%s: lm_stride=%zu, w_stride=%zu, needs lm_stride >= 2 and w_stride >= 1", who, lm_stride, w_stride);
     return FLM_ERR_SHAPE;
   }
+  return FLM_OK;
+}
+
+int flm_track_best_update(flm_stream_t stream, const void* faces, size_t face_bytes, int k, const int64_t* rec,
+                          const int32_t* status, const int32_t* reset, const double* lm, size_t lm_stride,
+                          const double* wt, size_t w_stride, int c, const double* factor, const float* m,
+                          int64_t frame_id, const flm_best_opts* opts, const double* best_q_in, double* best_q_out,
+                          void* gallery, int64_t* best_frame, float* best_m, double* best_lm, int64_t* best_rec) {
+  const char* who = "flm_track_best_update";
+  if (!faces || !rec || !lm || !best_q_in || !best_q_out || !gallery || !best_frame) {
+    set_error("%s: null argument", who);  // (status, reset, w, factor, m, opts and the last three outputs are optional)
+    return FLM_ERR_ARG;
+  }
+  if (best_m && !m) {
+    set_error("%s: best_m_dev needs m_dev", who);
+    return FLM_ERR_ARG;
+  }
+  flm_best_opts defaults;
+  if (const int rc = check_best_args(who, &opts, &defaults, "k", k, c, face_bytes, lm_stride, wt, w_stride)) return rc;
   if (ranges_overlap(best_q_in, (size_t)k * sizeof(double), best_q_out, (size_t)k * sizeof(double))) {
     set_error("%s: best_q_in and best_q_out overlap (every workgroup of a slot reads best_q_in: swap two buffers)", who);
     return FLM_ERR_ARG;
@@ -1501,6 +1582,40 @@ int flm_track_best_update(flm_stream_t stream, const void* faces, size_t face_by
   return launch_track_best_update(static_cast<hipStream_t>(stream), faces, face_bytes, k, rec, status, reset, lm, lm_stride,
                                   wt, w_stride, c, factor, m, frame_id, opts, best_q_in, best_q_out, gallery, best_frame,
                                   best_m, best_lm, best_rec);
+}
+
+int flm_track_best_update_rows(flm_stream_t stream, const void* faces, size_t face_bytes, int n, const int64_t* rec,
+                               const int32_t* status_rows, const int32_t* reset_c, const double* lm, size_t lm_stride,
+                               const double* wt, size_t w_stride, int c, const double* factor, const float* m,
+                               int64_t frame_id, const flm_best_opts* opts, const int32_t* slot, int n_slots,
+                               const double* best_q_c, double* best_q, void* gallery, int64_t* best_frame, float* best_m,
+                               double* best_lm, int64_t* best_rec) {
+  const char* who = "flm_track_best_update_rows";
+  if (!faces || !rec || !lm || !slot || !best_q_c || !best_q || !gallery || !best_frame) {
+    set_error("%s: null argument", who);  // (status, reset, w, factor, m, opts and the last three outputs are optional)
+    return FLM_ERR_ARG;
+  }
+  if (best_m && !m) {
+    set_error("%s: best_m_dev needs m_dev", who);
+    return FLM_ERR_ARG;
+  }
+  flm_best_opts defaults;
+  if (const int rc = check_best_args(who, &opts, &defaults, "n", n, c, face_bytes, lm_stride, wt, w_stride)) return rc;
+  if (n_slots < 1 || n_slots > 65535) {
+    set_error("%s: n_slots=%d, needs 1 <= n_slots <= 65535", who, n_slots);
+    return FLM_ERR_SHAPE;
+  }
+  if (ranges_overlap(best_q_c, (size_t)n * sizeof(double), best_q, (size_t)n_slots * sizeof(double))) {
+    set_error("%s: best_q_c and best_q overlap (every workgroup of a row reads best_q_c: it is the snapshot)", who);
+    return FLM_ERR_ARG;
+  }
+  if (ranges_overlap(faces, (size_t)n * face_bytes, gallery, (size_t)n_slots * face_bytes)) {
+    set_error("%s: faces_dev and gallery_dev overlap", who);
+    return FLM_ERR_ARG;
+  }
+  return launch_track_best_update_rows(static_cast<hipStream_t>(stream), faces, face_bytes, n, rec, status_rows, reset_c, lm,
+                                       lm_stride, wt, w_stride, c, factor, m, frame_id, opts, slot, n_slots, best_q_c, best_q,
+                                       gallery, best_frame, best_m, best_lm, best_rec);
 }
 
 }  // extern "C"

@@ -18,6 +18,8 @@
 // decision from the inputs (nobody writes them: the workgroups of a slot agree); a slot that is not taken costs its
 // workgroups that and nothing else.  Chunk 0 writes the slot's scalars; every chunk copies its 4 KiB pieces of the face,
 // cut at 16-byte boundaries as above, with 16-byte accesses where source and destination are congruent modulo 16.
+// flm_track_best_update_rows is the same body on the rows of a compacted batch: everything the decision reads lies at the
+// ROW, everything written at the row's SLOT; an inert row's workgroups return before they read anything else.
 #include "flm_common.h"
 #include "flm_quality_dev.h"
 
@@ -264,35 +266,38 @@ __device__ __forceinline__ double best_quality(const BestArgs& g, int slot, bool
   return q;
 }
 
-__global__ __launch_bounds__(kBestThreads) void track_best_kernel(const BestArgs g) {
+// The body track_best_kernel and track_best_rows_kernel share: `slot` is the ROW the faces, records, landmarks, status,
+// reset, factor, matrices and best_q_in are read at, `gs` the SLOT best_q_out, the gallery and the other outputs are
+// written at (track_best_kernel: the same number).
+__device__ __forceinline__ void track_best_body(const BestArgs& g, int slot, size_t gs) {
   __shared__ int s_taken;
-  const int slot = blockIdx.y, tid = threadIdx.x;
+  const int tid = threadIdx.x;
   if (tid == 0) {
     bool eligible;
     const double q = best_quality(g, slot, &eligible);
     const double prev = (g.reset && g.reset[slot] != 0) ? -1.0 : g.best_q_in[slot];
     const bool taken = eligible && q > prev;
     s_taken = taken;
-    if (blockIdx.x == 0) g.best_q_out[slot] = taken ? q : prev;
+    if (blockIdx.x == 0) g.best_q_out[gs] = taken ? q : prev;
   }
   __syncthreads();
   if (!s_taken) return;
 
   if (blockIdx.x == 0) {  // the slot's scalars
-    if (tid == 0) g.best_frame[slot] = g.frame_id;
-    if (g.best_m && tid < 6) g.best_m[(size_t)slot * 6 + tid] = g.m[(size_t)slot * 6 + tid];
+    if (tid == 0) g.best_frame[gs] = g.frame_id;
+    if (g.best_m && tid < 6) g.best_m[gs * 6 + tid] = g.m[(size_t)slot * 6 + tid];
     if (g.best_rec && tid >= 64 && tid < 64 + FLM_QUALITY_REC)
-      g.best_rec[(size_t)slot * FLM_QUALITY_REC + (tid - 64)] = g.rec[(size_t)slot * FLM_QUALITY_REC + (tid - 64)];
+      g.best_rec[gs * FLM_QUALITY_REC + (tid - 64)] = g.rec[(size_t)slot * FLM_QUALITY_REC + (tid - 64)];
     if (g.best_lm) {
       const double* lm = g.lm + (size_t)slot * g.c * g.lm_stride;
-      double* o = g.best_lm + (size_t)slot * g.c * 2;
+      double* o = g.best_lm + gs * g.c * 2;
       for (int i = tid; i < 2 * g.c; i += kBestThreads) o[i] = lm[(size_t)(i >> 1) * g.lm_stride + (i & 1)];
     }
   }
 
   // the face: pieces of 16 bytes at the 16-byte lines of the SOURCE address
   const unsigned char* src = g.faces + (size_t)slot * g.face_bytes;
-  unsigned char* dst = g.gallery + (size_t)slot * g.face_bytes;
+  unsigned char* dst = g.gallery + gs * g.face_bytes;
   const uintptr_t a0 = reinterpret_cast<uintptr_t>(src), a1 = a0 + g.face_bytes;
   const uintptr_t base = a0 & ~(uintptr_t)15;
   const bool congruent = ((a0 ^ reinterpret_cast<uintptr_t>(dst)) & 15u) == 0;
@@ -309,12 +314,25 @@ __global__ __launch_bounds__(kBestThreads) void track_best_kernel(const BestArgs
   }
 }
 
+__global__ __launch_bounds__(kBestThreads) void track_best_kernel(const BestArgs g) {
+  track_best_body(g, blockIdx.y, blockIdx.y);
+}
+
+// best_q_in is the SNAPSHOT of the rows (nobody writes it), best_q_out the tracker's own tensor, written at the slot.
+__global__ __launch_bounds__(kBestThreads) void track_best_rows_kernel(const BestArgs g, const int32_t* __restrict__ slot,
+                                                                       int n_slots) {
+  const int gs = slot[blockIdx.y];
+  if (gs < 0 || gs >= n_slots) return;  // an inert row: the whole workgroup leaves
+  track_best_body(g, blockIdx.y, (size_t)gs);
+}
+
 // Pointers, options and overlaps are checked by the caller in flm_api.hip.
-int launch_track_best_update(hipStream_t s, const void* faces, size_t face_bytes, int k, const int64_t* rec,
-                             const int32_t* status, const int32_t* reset, const double* lm, size_t lm_stride,
-                             const double* wt, size_t w_stride, int c, const double* factor, const float* m,
-                             int64_t frame_id, const flm_best_opts* opts, const double* best_q_in, double* best_q_out,
-                             void* gallery, int64_t* best_frame, float* best_m, double* best_lm, int64_t* best_rec) {
+// slot == null: flm_track_best_update (k slots, row == slot); else flm_track_best_update_rows (k rows).
+static int launch_best(hipStream_t s, const void* faces, size_t face_bytes, int k, const int64_t* rec, const int32_t* status,
+                       const int32_t* reset, const double* lm, size_t lm_stride, const double* wt, size_t w_stride, int c,
+                       const double* factor, const float* m, int64_t frame_id, const flm_best_opts* opts,
+                       const int32_t* slot, int n_slots, const double* best_q_in, double* best_q_out, void* gallery,
+                       int64_t* best_frame, float* best_m, double* best_lm, int64_t* best_rec) {
   BestArgs g;
   g.faces = static_cast<const unsigned char*>(faces);
   g.face_bytes = face_bytes;
@@ -327,9 +345,33 @@ int launch_track_best_update(hipStream_t s, const void* faces, size_t face_bytes
   g.best_frame = best_frame; g.best_m = best_m; g.best_lm = best_lm; g.best_rec = best_rec;
   size_t chunks = (face_bytes + 15 + kBestChunk - 1) / kBestChunk;  // (+15: the lead-in of an unaligned face)
   if (chunks > 1024) chunks = 1024;
-  track_best_kernel<<<dim3((unsigned)chunks, k), kBestThreads, 0, s>>>(g);
-  FLM_LAUNCH_CHECK("track_best_kernel");
+  if (slot) {
+    track_best_rows_kernel<<<dim3((unsigned)chunks, k), kBestThreads, 0, s>>>(g, slot, n_slots);
+    FLM_LAUNCH_CHECK("track_best_rows_kernel");
+  } else {
+    track_best_kernel<<<dim3((unsigned)chunks, k), kBestThreads, 0, s>>>(g);
+    FLM_LAUNCH_CHECK("track_best_kernel");
+  }
   return FLM_OK;
+}
+
+int launch_track_best_update(hipStream_t s, const void* faces, size_t face_bytes, int k, const int64_t* rec,
+                             const int32_t* status, const int32_t* reset, const double* lm, size_t lm_stride,
+                             const double* wt, size_t w_stride, int c, const double* factor, const float* m,
+                             int64_t frame_id, const flm_best_opts* opts, const double* best_q_in, double* best_q_out,
+                             void* gallery, int64_t* best_frame, float* best_m, double* best_lm, int64_t* best_rec) {
+  return launch_best(s, faces, face_bytes, k, rec, status, reset, lm, lm_stride, wt, w_stride, c, factor, m, frame_id, opts,
+                     nullptr, 0, best_q_in, best_q_out, gallery, best_frame, best_m, best_lm, best_rec);
+}
+
+int launch_track_best_update_rows(hipStream_t s, const void* faces, size_t face_bytes, int n, const int64_t* rec,
+                                  const int32_t* status_rows, const int32_t* reset_c, const double* lm, size_t lm_stride,
+                                  const double* wt, size_t w_stride, int c, const double* factor, const float* m,
+                                  int64_t frame_id, const flm_best_opts* opts, const int32_t* slot, int n_slots,
+                                  const double* best_q_c, double* best_q, void* gallery, int64_t* best_frame, float* best_m,
+                                  double* best_lm, int64_t* best_rec) {
+  return launch_best(s, faces, face_bytes, n, rec, status_rows, reset_c, lm, lm_stride, wt, w_stride, c, factor, m, frame_id,
+                     opts, slot, n_slots, best_q_c, best_q, gallery, best_frame, best_m, best_lm, best_rec);
 }
 
 }  // namespace flm

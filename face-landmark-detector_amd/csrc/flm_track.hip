@@ -112,24 +112,26 @@ struct EuroState {
   double xh, yh, vx, vy, xr, yr;
 };
 // One point through the One-Euro filter of the header: (x, y) is the raw point in frame px, s its state as read; (x, y)
-// leaves as what the fits and lm_frame get, s as the state to write back.
-__device__ __forceinline__ void one_euro_point(const TrackStepArgs& g, double side, double& x, double& y, EuroState& s) {
+// leaves as what the fits and lm_frame get, s as the state to write back.  dt is the row's time step; !dt_ok (a row of
+// flm_track_step_rows whose dt is not > 0 and finite) takes the point's history away.
+__device__ __forceinline__ void one_euro_point(const TrackStepArgs& g, double side, double dt, bool dt_ok, double& x,
+                                               double& y, EuroState& s) {
   const double TWO_PI = 6.283185307179586;
   const double xraw = x, yraw = y;
   if (xraw < 0.0) {  // rejected (landmark_back writes exactly (-1,-1)): the point's history ends
     s.xh = -1.0; s.yh = -1.0; s.vx = 0.0; s.vy = 0.0; s.xr = -1.0; s.yr = -1.0;
     return;
   }
-  const bool hist = s.xh >= 0.0 && s.yh >= 0.0 && __builtin_isfinite(s.xh) && __builtin_isfinite(s.yh) &&
+  const bool hist = dt_ok && s.xh >= 0.0 && s.yh >= 0.0 && __builtin_isfinite(s.xh) && __builtin_isfinite(s.yh) &&
                     __builtin_isfinite(s.vx) && __builtin_isfinite(s.vy) && __builtin_isfinite(s.xr) &&
                     __builtin_isfinite(s.yr);
   double nvx = 0.0, nvy = 0.0;
   if (hist) {
-    const double rx = (xraw - s.xr) / g.dt, ry = (yraw - s.yr) / g.dt;
-    const double ad = 1.0 / (1.0 + (1.0 / (TWO_PI * g.d_cutoff)) / g.dt);
+    const double rx = (xraw - s.xr) / dt, ry = (yraw - s.yr) / dt;
+    const double ad = 1.0 / (1.0 + (1.0 / (TWO_PI * g.d_cutoff)) / dt);
     const double vx1 = ad * rx + (1.0 - ad) * s.vx, vy1 = ad * ry + (1.0 - ad) * s.vy;
     const double fc = g.min_cutoff + g.beta * (sqrt(vx1 * vx1 + vy1 * vy1) / side);
-    const double a = 1.0 / (1.0 + (1.0 / (TWO_PI * fc)) / g.dt);
+    const double a = 1.0 / (1.0 + (1.0 / (TWO_PI * fc)) / dt);
     const double xh1 = a * xraw + (1.0 - a) * s.xh, yh1 = a * yraw + (1.0 - a) * s.yh;
     if (__builtin_isfinite(xh1) && __builtin_isfinite(yh1) && __builtin_isfinite(vx1) && __builtin_isfinite(vy1)) {
       x = xh1; y = yh1; nvx = vx1; nvy = vy1;
@@ -140,10 +142,15 @@ __device__ __forceinline__ void one_euro_point(const TrackStepArgs& g, double si
 
 // FILT: the staging loop passes every point through the filter before it reaches LDS (flm_track_step_filtered); all
 // that follows the barrier is the same code on the filtered points.
+// The body is shared by track_step_kernel and track_step_rows_kernel, the way track_assoc_body is shared between its two
+// kernels: the arithmetic is stated once.  f is the face's ROW -- where its landmarks, weights, matrix and box are read and
+// lm_frame, m_align and lm_raw written --, gs its SLOT -- where the state is read and written and m_next, boxes_next and
+// status are written.  track_step_kernel passes f == gs, its scalar dt and dt_ok = true; status_rows is null there.
 template <bool FILT>
-__global__ __launch_bounds__(64) void track_step_kernel(const TrackStepArgs g) {
+__device__ __forceinline__ void track_step_body(const TrackStepArgs& g, int f, size_t gs, double dt, bool dt_ok,
+                                                int32_t* status_rows) {
   extern __shared__ __attribute__((aligned(16))) double trk_s[];  // [c][2] frame px, [c][2] x 2 templates, [c] weights
-  const int f = blockIdx.x, c = g.c;
+  const int c = g.c;
   double* p = trk_s;
   double* tc = trk_s + 2 * c;   // tmpl_crop, then tmpl_align: lane l of the fit reads tc + l*2c
   double* w = trk_s + 6 * c;
@@ -161,9 +168,9 @@ __global__ __launch_bounds__(64) void track_step_kernel(const TrackStepArgs g) {
     double* sp = nullptr;
     EuroState es;
     if constexpr (FILT) {
-      sp = g.state + ((size_t)f * c + i) * 6;
+      sp = g.state + (gs * c + i) * 6;
       es.xh = sp[0]; es.yh = sp[1]; es.vx = sp[2]; es.vy = sp[3]; es.xr = sp[4]; es.yr = sp[5];
-      one_euro_point(g, crop_side, xf, yf, es);
+      one_euro_point(g, crop_side, dt, dt_ok, xf, yf, es);
     }
     p[2 * i] = xf;
     p[2 * i + 1] = yf;
@@ -254,12 +261,107 @@ __global__ __launch_bounds__(64) void track_step_kernel(const TrackStepArgs g) {
     b3 = box_coord(ceil(mxy) + 1.0);
     o0 = f00; o1 = f01; o2 = f02; o3 = f10; o4 = f11; o5 = f12;
   }
-  float* o = g.m_next + (size_t)f * 6;
+  float* o = g.m_next + gs * 6;
   o[0] = o0; o[1] = o1; o[2] = o2;
   o[3] = o3; o[4] = o4; o[5] = o5;
-  int32_t* bo = g.boxes_next + 4 * (size_t)f;
+  int32_t* bo = g.boxes_next + 4 * gs;
   bo[0] = b0; bo[1] = b1; bo[2] = b2; bo[3] = b3;
-  g.status[f] = st;
+  g.status[gs] = st;
+  if (status_rows) status_rows[f] = st;
+}
+
+template <bool FILT>
+__global__ __launch_bounds__(64) void track_step_kernel(const TrackStepArgs g) {
+  track_step_body<FILT>(g, blockIdx.x, blockIdx.x, g.dt, true, nullptr);
+}
+
+// ---- flm_track_step_rows: the body above on the rows of a compacted batch -------------------------------------------
+// A workgroup of one wave per row, as track_step_kernel.  The row map is read once; an inert row writes its compact
+// outputs and leaves before anything global is touched (the whole wave leaves: the body's barrier is never reached).
+struct TrackRowArgs {
+  const int32_t* slot;    // [N] the global slot of every row
+  int n_slots;
+  const double* dt;       // [N] or null: the scalar dt of TrackStepArgs
+  int32_t* status_rows;   // [N]
+};
+
+template <bool FILT>
+__global__ __launch_bounds__(64) void track_step_rows_kernel(const TrackStepArgs g, const TrackRowArgs r) {
+  const int f = blockIdx.x;
+  const int gs = r.slot[f];
+  if (gs < 0 || gs >= r.n_slots) {
+    for (int i = threadIdx.x; i < 2 * g.c; i += 64) {
+      g.lm_frame[(size_t)f * g.c * 2 + i] = -1.0;
+      if constexpr (FILT) {
+        if (g.lm_raw) g.lm_raw[(size_t)f * g.c * 2 + i] = -1.0;
+      }
+    }
+    if (g.m_align && threadIdx.x < 6) g.m_align[(size_t)f * 6 + threadIdx.x] = (threadIdx.x == 0 || threadIdx.x == 4) ? 1.f : 0.f;
+    if (threadIdx.x == 0) r.status_rows[f] = FLM_TRACK_DEAD;
+    return;
+  }
+  double dt = g.dt;
+  bool dt_ok = true;
+  if constexpr (FILT) {
+    if (r.dt) {
+      dt = r.dt[f];
+      dt_ok = dt > 0.0 && __builtin_isfinite(dt);
+    }
+  }
+  track_step_body<FILT>(g, f, (size_t)gs, dt, dt_ok, r.status_rows);
+}
+
+// ---- flm_track_gather_streams: a thread per row, a copy ---------------------------------------------------------------
+struct TrackGatherArgs {
+  const int32_t* active;   // [A]
+  int n_rows, s, k;        // n_rows = A*k
+  const int32_t* frame_idx_stream;  // [S] or null
+  const double* dt_stream;          // [S] or null
+  const float* m_crop;     // [S*K,2,3]
+  const int32_t* boxes;    // [S*K,4]
+  const double* best_q;    // [S*K] or null
+  int32_t* reset;          // [S*K] or null, in/out
+  int32_t* slot_c;
+  float* m_c;
+  int32_t* boxes_c;
+  int32_t* frame_idx_c;
+  double* dt_c;
+  double* best_q_c;
+  int32_t* reset_c;
+};
+
+__global__ __launch_bounds__(64) void track_gather_streams_kernel(const TrackGatherArgs g) {
+  const int r = blockIdx.x * 64 + threadIdx.x;
+  if (r >= g.n_rows) return;
+  const int a = r / g.k, j = r - a * g.k;
+  const int sid = g.active[a];
+  const bool valid = sid >= 0 && sid < g.s;
+  const size_t gs = valid ? (size_t)sid * g.k + j : 0;
+  float m0 = 1.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 1.f, m5 = 0.f;
+  int b0 = 0, b1 = 0, b2 = 0, b3 = 0, fi = 0, rs = 0;
+  double dt = 0.0, bq = -1.0;
+  if (valid) {
+    const float* mm = g.m_crop + gs * 6;
+    m0 = mm[0]; m1 = mm[1]; m2 = mm[2]; m3 = mm[3]; m4 = mm[4]; m5 = mm[5];
+    const int32_t* bx = g.boxes + gs * 4;
+    b0 = bx[0]; b1 = bx[1]; b2 = bx[2]; b3 = bx[3];
+    if (g.frame_idx_stream) fi = g.frame_idx_stream[sid];
+    if (g.dt_stream) dt = g.dt_stream[sid];
+    if (g.best_q) bq = g.best_q[gs];
+    if (g.reset) {
+      rs = g.reset[gs];
+      g.reset[gs] = 0;
+    }
+  }
+  g.slot_c[r] = valid ? (int)gs : -1;
+  float* mo = g.m_c + (size_t)r * 6;
+  mo[0] = m0; mo[1] = m1; mo[2] = m2; mo[3] = m3; mo[4] = m4; mo[5] = m5;
+  int32_t* bo = g.boxes_c + (size_t)r * 4;
+  bo[0] = b0; bo[1] = b1; bo[2] = b2; bo[3] = b3;
+  g.frame_idx_c[r] = fi;
+  if (g.dt_c) g.dt_c[r] = dt;
+  if (g.best_q_c) g.best_q_c[r] = bq;
+  if (g.reset_c) g.reset_c[r] = rs;
 }
 
 // ---- launchers: the sizes every entry point shares ----------------------------------------------------------
@@ -308,14 +410,13 @@ int launch_landmarks_from_crop(hipStream_t s, const double* lm, size_t lm_stride
   return FLM_OK;
 }
 
-int launch_track_step(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
-                      const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h, int in_w,
-                      int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
-                      double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status,
-                      const flm_track_filter* filt, double dt, double* state, double* lm_raw) {
-  const char* who = filt ? "flm_track_step_filtered" : "flm_track_step";
-  if (const int rc = check_track_sizes(who, k, c, in_h, in_w, fh, fw)) return rc;
-  if (const int rc = check_track_points(who, lm_stride, w_stride, sx, sy)) return rc;
+// The struct the two step launchers fill alike.
+static TrackStepArgs make_track_step_args(const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
+                                          const float* m_crop, const int32_t* boxes, int c, double sx, double sy, int in_h,
+                                          int in_w, int fh, int fw, const double* tmpl_crop, const double* tmpl_align,
+                                          const flm_track_opts* opts, double* lm_frame, float* m_align, float* m_next,
+                                          int32_t* boxes_next, int32_t* status, const flm_track_filter* filt, double dt,
+                                          double* state, double* lm_raw) {
   TrackStepArgs g;
   g.lm = lm; g.lm_stride = lm_stride; g.wt = wt; g.w_stride = w_stride;
   g.m_crop = m_crop; g.boxes = boxes; g.c = c; g.sx = sx; g.sy = sy;
@@ -328,11 +429,82 @@ int launch_track_step(hipStream_t s, const double* lm, size_t lm_stride, const d
   if (filt) {
     g.min_cutoff = filt->min_cutoff; g.beta = filt->beta; g.d_cutoff = filt->d_cutoff; g.dt = dt;
     g.state = state; g.lm_raw = lm_raw;
+  }
+  return g;
+}
+
+int launch_track_step(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
+                      const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h, int in_w,
+                      int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
+                      double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status,
+                      const flm_track_filter* filt, double dt, double* state, double* lm_raw) {
+  const char* who = filt ? "flm_track_step_filtered" : "flm_track_step";
+  if (const int rc = check_track_sizes(who, k, c, in_h, in_w, fh, fw)) return rc;
+  if (const int rc = check_track_points(who, lm_stride, w_stride, sx, sy)) return rc;
+  const TrackStepArgs g = make_track_step_args(lm, lm_stride, wt, w_stride, m_crop, boxes, c, sx, sy, in_h, in_w, fh, fw,
+                                               tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next, status,
+                                               filt, dt, state, lm_raw);
+  if (filt) {
     track_step_kernel<true><<<k, 64, sizeof(double) * 7 * c, s>>>(g);
   } else {
     track_step_kernel<false><<<k, 64, sizeof(double) * 7 * c, s>>>(g);   // (at most 56 KiB: c <= 1024)
   }
   FLM_LAUNCH_CHECK("track_step_kernel");
+  return FLM_OK;
+}
+
+int launch_track_step_rows(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
+                           const float* m_crop, const int32_t* boxes, int n, int c, double sx, double sy, int in_h, int in_w,
+                           int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
+                           double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status,
+                           const flm_track_filter* filt, double dt, double* state, double* lm_raw, const int32_t* slot,
+                           int n_slots, const double* dt_rows, int32_t* status_rows) {
+  const char* who = "flm_track_step_rows";
+  if (n < 1 || n > 65535) {
+    set_error("%s: n=%d, needs 1 <= n <= 65535", who, n);
+    return FLM_ERR_SHAPE;
+  }
+  if (n_slots < 1 || n_slots > 65535) {
+    set_error("%s: n_slots=%d, needs 1 <= n_slots <= 65535", who, n_slots);
+    return FLM_ERR_SHAPE;
+  }
+  if (const int rc = check_track_sizes(who, n, c, in_h, in_w, fh, fw)) return rc;
+  if (const int rc = check_track_points(who, lm_stride, w_stride, sx, sy)) return rc;
+  const TrackStepArgs g = make_track_step_args(lm, lm_stride, wt, w_stride, m_crop, boxes, c, sx, sy, in_h, in_w, fh, fw,
+                                               tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next, status,
+                                               filt, dt, state, lm_raw);
+  TrackRowArgs r;
+  r.slot = slot; r.n_slots = n_slots; r.dt = filt ? dt_rows : nullptr; r.status_rows = status_rows;
+  if (filt)
+    track_step_rows_kernel<true><<<n, 64, sizeof(double) * 7 * c, s>>>(g, r);
+  else
+    track_step_rows_kernel<false><<<n, 64, sizeof(double) * 7 * c, s>>>(g, r);
+  FLM_LAUNCH_CHECK("track_step_rows_kernel");
+  return FLM_OK;
+}
+
+// Pointers and their pairing have been checked by the caller in flm_api.hip.
+int launch_track_gather_streams(hipStream_t s, const int32_t* active, int a, int n_streams, int k,
+                                const int32_t* frame_idx_stream, const double* dt_stream, const float* m_crop,
+                                const int32_t* boxes, const double* best_q, int32_t* reset, int32_t* slot_c, float* m_c,
+                                int32_t* boxes_c, int32_t* frame_idx_c, double* dt_c, double* best_q_c, int32_t* reset_c) {
+  const char* who = "flm_track_gather_streams";
+  if (a < 1 || n_streams < 1 || k < 1) {
+    set_error("%s: a=%d, s=%d, k=%d, needs 1 <= a, 1 <= s and 1 <= k", who, a, n_streams, k);
+    return FLM_ERR_SHAPE;
+  }
+  if ((long long)a * k > 65535 || (long long)n_streams * k > 65535) {
+    set_error("%s: a=%d, s=%d streams of k=%d slots, needs a*k <= 65535 and s*k <= 65535", who, a, n_streams, k);
+    return FLM_ERR_SHAPE;
+  }
+  TrackGatherArgs g;
+  g.active = active; g.n_rows = a * k; g.s = n_streams; g.k = k;
+  g.frame_idx_stream = frame_idx_stream; g.dt_stream = dt_stream; g.m_crop = m_crop; g.boxes = boxes;
+  g.best_q = best_q; g.reset = reset;
+  g.slot_c = slot_c; g.m_c = m_c; g.boxes_c = boxes_c; g.frame_idx_c = frame_idx_c;
+  g.dt_c = dt_c; g.best_q_c = best_q_c; g.reset_c = reset_c;
+  track_gather_streams_kernel<<<cdiv(g.n_rows, 64), 64, 0, s>>>(g);
+  FLM_LAUNCH_CHECK("track_gather_streams_kernel");
   return FLM_OK;
 }
 

@@ -589,7 +589,8 @@ class FaceTracker:
     stream t // slots_per_stream, `step` takes one ring slot per stream and `update` one list of detections per stream
     (alignment.track_associate_streams_device: no pair of two streams is ever evaluated); every tensor the tracker
     owns or returns stays flat over the `capacity` global slots.  With streams=1 every method is the single-stream
-    code, launch for launch."""
+    code, launch for launch.  `step_active` steps only the streams that delivered a frame, each on its own `dt`, and
+    leaves every other stream's state untouched."""
 
     def __init__(self, model, frame_hw, capacity, out_size=(112, 112), template=None, crop_template=None, n_points=4,
                  thresh=0.0, weights=None, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"),
@@ -647,6 +648,7 @@ class FaceTracker:
         self.associate = associate
         self.streams, self.slots_per_stream = int(streams), capacity // int(streams)
         self.best_shot, self.gallery, self._steps = best_shot, None, 0
+        self._ws_active = None   # the forward workspace of step_active (_active_workspace)
         self._crop_format = alignment.AlignedFormat("nhwc", "uint8")
         self._templates = (np.ascontiguousarray(tm, np.float64), np.ascontiguousarray(tc, np.float64))
         self.m_crop = None    # the device state, allocated by the first call that needs it (_state)
@@ -920,6 +922,189 @@ class FaceTracker:
             self.best_q, self._best_q_spare = self._best_q_spare, self.best_q
             self._best_reset.zero_()
         return aligned, m_align, lm_frame, self.status
+
+    def _active_workspace(self, n, out):
+        """The forward workspace `step_active` passes for a batch of n faces, or None (the model's cached path).  The
+        model caches four workspaces keyed by batch, and a tracker of S streams can see S different batches: so the
+        tracker owns ONE, sized for the largest batch it can see in one launch, min(capacity, model.max_batch) -- the
+        forward lays its tensors out for the batch it is given and only asks that the workspace be large enough
+        (workspace_bytes does not decrease with the batch).  A batch beyond model.max_batch takes the cached path, which
+        slices."""
+        if n > self.model.max_batch:
+            return None
+        if self._ws_active is None:
+            self._ws_active = self.model.new_workspace(min(self.capacity, self.model.max_batch), out, self.n_points)
+        return self._ws_active
+
+    def step_active(self, ring, frame_index, active, dt=None, frame_id=None):
+        """One frame for the slots of the streams `active` alone, each stream on its own clock; every other stream keeps
+        every bit of its state (matrices, boxes, status, filter state, best shot, pending best-shot reset).  Works for any
+        `streams` >= 1; `step` and `step_active` may be mixed freely, and both count as a step.
+
+        frame_index: the ring slot of every stream's new frame, a host sequence of `streams` entries (those of streams
+        not in `active` are ignored and may be None) or a contiguous CUDA int32 [streams] tensor; a tracker of one
+        stream also takes a bare integer.  active: a host sequence of distinct stream ids in [0, streams) -- an empty
+        one returns empty tensors, launches nothing and is not counted as a step -- or a contiguous CUDA int32 [A]
+        tensor, 1 <= A <= streams, used where it lies (distinct ids; an id outside the range gives slots_per_stream inert
+        rows: zero faces, the identity, TRACK_DEAD, slot -1).  With `active` on the device the host cannot tell which
+        entries of a host `frame_index` or `dt` are ignored: every entry is then checked, None standing for ring slot 0
+        and not allowed in `dt`.  dt, for a tracker that smooths: None (1/fps of the filter), a host number, a host
+        sequence of `streams` numbers (entries of inactive streams are ignored, those of active ones must be > 0 and
+        finite) or a CUDA float64 [streams] tensor -- the seconds since THAT stream's previous frame (on the device, a
+        value that is not > 0 and finite takes the history of the stream's landmarks away and nothing else).  frame_id:
+        as `step` takes it.
+
+        Whatever arrives on the host goes up in ONE upload, device arguments cause no transfer, nothing synchronises.
+        Sequence: alignment.track_gather_streams_device (the snapshot: the active slots' matrices, boxes, ring slots,
+        time steps, best quality and pending resets in compact rows) -> the uint8 crop warp on the snapshot ->
+        model.forward_device at batch A*slots_per_stream -> alignment.track_step_rows_device (writes the tracker's
+        state at each row's slot) -> the aligned warp (with the snapshot's boxes) -> with best_shot,
+        alignment.face_quality_device and alignment.track_best_update_rows_device.  The forward of a batch up to
+        model.max_batch runs in one workspace the tracker owns, sized for its largest batch (`_active_workspace`); a
+        larger batch takes the model's cached path, which slices.  `frame_slots` keeps what the last `step` wrote.
+
+        Returns CUDA tensors over the N = A*slots_per_stream rows, row a*slots_per_stream + j being slot
+        active[a]*slots_per_stream + j: (aligned [N,...], M float32 [N,2,3], landmarks float64 [N,C,2], status int32 [N],
+        slots int32 [N])."""
+        import math
+        import torch
+        fh, fw = self.frame_hw
+        s, k = self.streams, self.slots_per_stream
+        if self.best_shot is None and frame_id is not None:
+            raise ValueError("frame_id goes with best_shot")
+        if frame_id is None:
+            frame_id = self._steps
+        elif isinstance(frame_id, bool) or int(frame_id) != frame_id or not -2 ** 63 <= int(frame_id) < 2 ** 63:
+            raise ValueError("frame_id must be an integer that fits int64 (got %r)" % (frame_id,))
+        if self.smooth is None and dt is not None:
+            raise ValueError("dt goes with smooth")
+        if self.frame_format is not None:
+            nf, rh, rw, _ = self.frame_format.ring(ring)
+        else:
+            nf, rh, rw, _ = alignment.FrameFormat.bgr().ring(ring)
+        if (rh, rw) != (fh, fw):
+            raise ValueError("the ring holds %dx%d frames, the tracker was made for %dx%d" % (rh, rw, fh, fw))
+        # ---- active
+        act_host = None
+        if isinstance(active, torch.Tensor):
+            if (active.dtype != torch.int32 or not active.is_cuda or not active.is_contiguous() or active.dim() != 1
+                    or not 1 <= int(active.shape[0]) <= s):
+                raise ValueError("active must be a sequence of distinct stream ids in [0, %d) or a contiguous CUDA int32 "
+                                 "[A] tensor with 1 <= A <= %d" % (s, s))
+            a = int(active.shape[0])
+        else:
+            try:
+                act_host = list(active)
+            except TypeError:
+                act_host = None
+            if (act_host is None or any(isinstance(v, bool) or int(v) != v or not 0 <= int(v) < s for v in act_host)
+                    or len(set(int(v) for v in act_host)) != len(act_host)):
+                raise ValueError("active must be a sequence of distinct stream ids in [0, %d) or a contiguous CUDA int32 "
+                                 "[A] tensor with 1 <= A <= %d" % (s, s))
+            act_host = [int(v) for v in act_host]
+            a = len(act_host)
+        named = range(s) if act_host is None else act_host    # the streams whose host entries count
+        # ---- frame_index
+        fi_host = None
+        if isinstance(frame_index, torch.Tensor):
+            if (frame_index.dtype != torch.int32 or not frame_index.is_cuda or not frame_index.is_contiguous()
+                    or tuple(frame_index.shape) != (s,)):
+                raise ValueError("frame_index must be a sequence of %d ring slots or a contiguous CUDA int32 [%d] tensor"
+                                 % (s, s))
+        else:
+            if s == 1 and not isinstance(frame_index, (list, tuple, np.ndarray)):
+                frame_index = [frame_index]
+            try:
+                fi_host = list(frame_index)
+            except TypeError:
+                fi_host = None
+            if fi_host is None or len(fi_host) != s:
+                raise ValueError("frame_index must be a sequence of %d ring slots or a contiguous CUDA int32 [%d] tensor"
+                                 % (s, s))
+            if act_host is None:
+                fi_host = [0 if v is None else v for v in fi_host]
+            if any(fi_host[i] is None or isinstance(fi_host[i], bool) or int(fi_host[i]) != fi_host[i]
+                   or not 0 <= int(fi_host[i]) < nf for i in named):
+                raise ValueError("frame_index must name ring slots in [0, %d)" % nf)
+            keep = set(named)
+            fi_host = [int(v) if i in keep else 0 for i, v in enumerate(fi_host)]
+        # ---- dt
+        dt_host, dt_dev, dt_scalar = None, None, None
+        if self.smooth is not None:
+            if isinstance(dt, torch.Tensor):
+                if (dt.dtype != torch.float64 or not dt.is_cuda or not dt.is_contiguous() or tuple(dt.shape) != (s,)):
+                    raise ValueError("dt must be None, a number, a sequence of %d numbers or a contiguous CUDA float64 "
+                                     "[%d] tensor" % (s, s))
+                dt_dev = dt
+            elif dt is None or isinstance(dt, (int, float, np.integer, np.floating)):
+                dt_scalar = self.smooth.time_step(dt)
+            else:
+                try:
+                    dt_host = list(dt)
+                except TypeError:
+                    dt_host = None
+                if dt_host is None or len(dt_host) != s:
+                    raise ValueError("dt must be None, a number, a sequence of %d numbers or a contiguous CUDA float64 "
+                                     "[%d] tensor" % (s, s))
+                for i in named:
+                    v = dt_host[i]
+                    if v is None or isinstance(v, bool) or not (float(v) > 0.0 and math.isfinite(float(v))):
+                        raise ValueError("dt of stream %d must be finite and > 0, got %r" % (i, v))
+                keep = set(named)
+                dt_host = [float(v) if i in keep else 0.0 for i, v in enumerate(dt_host)]
+        self._state()
+        dev = self.boxes.device
+        model = self.model
+        ih, iw = model.input_height, model.input_width
+        n = a * k
+        if n == 0:
+            c = int(model.n_classes)
+            fmt = self.aligned_format or alignment.AlignedFormat()
+            return (torch.empty(fmt.shape(0, *self.out_size), dtype=fmt.torch_dtype, device=dev),
+                    torch.empty((0, 2, 3), dtype=torch.float32, device=dev),
+                    torch.empty((0, c, 2), dtype=torch.float64, device=dev),
+                    torch.empty((0,), dtype=torch.int32, device=dev), torch.empty((0,), dtype=torch.int32, device=dev))
+        # ---- one upload of everything that arrived on the host: float64 first, so every view is aligned
+        parts = [np.asarray(dt_host, np.float64)] if dt_host is not None else []
+        parts += [np.asarray(x, np.int32) for x in (fi_host, act_host) if x is not None]
+        if parts:
+            up = torch.from_numpy(np.concatenate([x.view(np.uint8) for x in parts])).to(dev)
+            off = 0
+            if dt_host is not None:
+                dt_dev, off = up[:8 * s].view(torch.float64), 8 * s
+            if fi_host is not None:
+                frame_index, off = up[off:off + 4 * s].view(torch.int32), off + 4 * s
+            if act_host is not None:
+                active = up[off:off + 4 * a].view(torch.int32)
+        best = self.best_shot is not None
+        snap = alignment.track_gather_streams_device(
+            active, self.m_crop, self.boxes, k, frame_index=frame_index, dt=dt_dev, best_q=self.best_q if best else None,
+            reset=self._best_reset if best else None)
+        crops = alignment.warp_frames_device(ring, snap["m"], ih, iw, frame_index_dev=snap["frame_index"],
+                                             boxes_dev=snap["boxes"], samples=self.crop_samples, fmt=self._crop_format,
+                                             src=self.frame_format)
+        out = "landmarks" if self.weights is None else "landmark_stats"
+        res = model.forward_device(crops, out, n_points=self.n_points, thresh=self.thresh,
+                                   workspace=self._active_workspace(n, out))
+        lm, wd = (res, None) if self.weights is None else (res[..., :2], res[..., 2])
+        filt = {}
+        if self.smooth is not None:
+            filt = dict(filter=self.smooth, dt=dt_scalar if dt_dev is None else snap["dt"], state=self.filter_state)
+        lm_frame, m_align, status_rows = alignment.track_step_rows_device(
+            lm, snap["m"], snap["boxes"], snap["slot"], (model.output_height, model.output_width), (ih, iw), (fh, fw),
+            self.crop_template, self.m_crop, self.boxes, self.status, tmpl_align=self.template, weights=wd, **self.limits,
+            **filt)
+        aligned = alignment.warp_frames_device(ring, m_align, self.out_size[0], self.out_size[1],
+                                               frame_index_dev=snap["frame_index"], boxes_dev=snap["boxes"],
+                                               samples=self.samples, fmt=self.aligned_format, src=self.frame_format)
+        self._steps += 1
+        if best:
+            rec = alignment.face_quality_device(aligned, self.aligned_format, self.best_shot.quality)
+            alignment.track_best_update_rows_device(
+                aligned, rec, lm_frame, snap["slot"], snap["best_q"], self.best_q, self.gallery, self.best_frame,
+                int(frame_id), status_rows=status_rows, reset_c=snap["reset"], weights=wd, m=m_align, opts=self.best_shot,
+                best_m=self.best_M, best_lm=self.best_landmarks, best_rec=self.best_rec)
+        return aligned, m_align, lm_frame, status_rows, snap["slot"]
 
     def best(self):
         """The best shot of every slot, for a tracker with `best_shot`: CUDA tensors (gallery [capacity,...] in the

@@ -771,6 +771,83 @@ int flm_track_step_filtered(flm_stream_t stream, const double* lm_dev, size_t lm
                             const flm_track_filter* filt, double dt, double* state_dev /*[K,C,6]*/,
                             double* lm_raw_dev /*[K,C,2] or NULL*/);
 
+/* ---- rows: stepping a subset of the slots, each on its own clock --------------------------------------------------------
+ * A tracker of S streams steps, on a tick, only the streams that delivered a frame.  The host knows which; the three
+ * calls below do the rest on the device without a synchronisation.  A ROW r in [0, N) is one face of the compacted
+ * batch; slot_dev int32 [N] names its global SLOT g.  A row is VALID when 0 <= g < n_slots and INERT otherwise.  Rows
+ * must name distinct slots: where two valid rows name one slot, that slot's results are one of the rows' values per
+ * written element, nothing else is affected and nothing is accessed out of bounds.
+ *
+ * flm_track_gather_streams: the step's snapshot, in ONE launch (a thread per row; a copy).  For streams, N = A*K and
+ * row a*K + j is slot active[a]*K + j.
+ * In:  active_dev int32 [A], the stream ids; a, s, k (slots PER STREAM); frame_idx_stream_dev int32 [S] or NULL (ring
+ *      slot 0 for every row); dt_stream_dev float64 [S] or NULL; m_crop_dev float32 [S*K,2,3]; boxes_dev int32 [S*K,4];
+ *      best_q_dev float64 [S*K] or NULL.
+ * In/out: reset_dev int32 [S*K] or NULL.
+ * Out, compact: slot_c int32 [A*K], m_c float32 [A*K,2,3], boxes_c int32 [A*K,4], frame_idx_c int32 [A*K], and, each
+ *      required exactly when its input is given, dt_c float64 [A*K], best_q_c float64 [A*K], reset_c int32 [A*K].
+ * Contract:
+ *  1. active[a] in [0, S): with g = active[a]*K + j and r = a*K + j, slot_c[r] = g, m_c[r], boxes_c[r], best_q_c[r]
+ *     and reset_c[r] are bit copies of the entries at g, frame_idx_c[r] = frame_idx_stream[active[a]] (0 without it)
+ *     and dt_c[r] = dt_stream[active[a]], bit copies too.  reset_dev[g] is then set to 0: the pending reset MOVES into
+ *     the snapshot.
+ *  2. active[a] outside [0, S): slot_c = -1, m_c = the identity, boxes_c = (0,0,0,0), frame_idx_c = 0, dt_c = 0.0,
+ *     best_q_c = -1.0, reset_c = 0 for the K rows; nothing global is read or written for them.
+ *  3. A stream that is not named is neither read nor written.
+ *  4. Stream ids must be distinct.  Where one is repeated, the compact rows are still the copies of 1 except reset_c,
+ *     which is one of (the pending value, 0) per row; nothing else is affected and nothing is accessed out of bounds.
+ *  5. One launch, no workspace, no allocation, no synchronisation.  No two arguments may overlap.
+ * Errors, all found before anything is launched: a null active_dev, m_crop_dev, boxes_dev, slot_c, m_c, boxes_c or
+ * frame_idx_c, or an optional output without its input or the reverse -> FLM_ERR_ARG.  FLM_ERR_SHAPE, the limit named in
+ * flm_last_error(), unless 1 <= a, 1 <= s, 1 <= k, a*k <= 65535 and s*k <= 65535. */
+int flm_track_gather_streams(flm_stream_t stream, const int32_t* active_dev /*[A]*/, int a, int s, int k /*slots PER STREAM*/,
+                             const int32_t* frame_idx_stream_dev /*[S] or NULL*/, const double* dt_stream_dev /*[S] or NULL*/,
+                             const float* m_crop_dev /*[S*K,2,3]*/, const int32_t* boxes_dev /*[S*K,4]*/,
+                             const double* best_q_dev /*[S*K] or NULL*/, int32_t* reset_dev /*[S*K] or NULL, in/out*/,
+                             int32_t* slot_c /*[A*K]*/, float* m_c /*[A*K,2,3]*/, int32_t* boxes_c /*[A*K,4]*/,
+                             int32_t* frame_idx_c /*[A*K]*/, double* dt_c /*[A*K] or NULL*/,
+                             double* best_q_c /*[A*K] or NULL*/, int32_t* reset_c /*[A*K] or NULL*/);
+
+/* flm_track_step_rows: flm_track_step / flm_track_step_filtered on rows, in ONE launch (a workgroup of one wave per row;
+ * the kernel runs the body of the two calls above, so the arithmetic is stated once).
+ * The arguments are those of flm_track_step_filtered with k replaced by n, plus slot_dev int32 [N], n_slots, dt_dev
+ * float64 [N] or NULL (NULL: the scalar dt for every row, checked on the host as there) and status_rows_dev int32 [N].
+ * filt may be NULL: then state_dev, lm_raw_dev and dt_dev are NULL, dt is not read, and the step is flm_track_step's.
+ * Where each argument lives:
+ *   compact, read at row r:      lm_dev, w_dev, m_crop_c_dev [N,2,3], boxes_c_dev [N,4]
+ *   compact, written at row r:   lm_frame_dev [N,C,2], m_align_dev [N,2,3], lm_raw_dev [N,C,2], status_rows_dev [N]
+ *   global, written at slot g:   m_next_dev [n_slots,2,3], boxes_next_dev [n_slots,4], status_dev [n_slots]
+ *   global, read and written at slot g:  state_dev [n_slots,C,6]
+ * Contract:
+ *  1. VALID row: every value written is, bit for bit, what flm_track_step_filtered (flm_track_step without filt) writes
+ *     for ONE face with the inputs of row r, the state rows of slot g and dt = dt_dev ? dt_dev[r] : dt.
+ *     status_rows[r] and status[g] both receive the status.
+ *  2. The one new rule: a row whose dt_dev[r] is not > 0 and finite treats every point as having NO HISTORY -- a raw point
+ *     that is ok gives out = raw and state = (x, y, 0, 0, x, y), a rejected one (-1,-1) and (-1,-1,0,0,-1,-1) as there.
+ *     Nothing else of the row changes.
+ *  3. INERT row: lm_frame and lm_raw are (-1,-1) everywhere, m_align is the identity, status_rows = FLM_TRACK_DEAD;
+ *     nothing global is read or written.
+ *  4. A slot no row names keeps every bit of m_next, boxes_next, status and state.
+ *  5. With slot[r] = r, n = n_slots and dt_dev NULL every output is flm_track_step_filtered's (flm_track_step's), bit for
+ *     bit, and status_rows equals status.
+ *  6. m_next_dev and boxes_next_dev may be the tensors the snapshot m_crop_c_dev / boxes_c_dev was gathered FROM (that is
+ *     what the snapshot is for); no other overlap of two arguments is allowed, and the call refuses m_crop_c_dev inside
+ *     m_next_dev, boxes_c_dev inside boxes_next_dev and status_rows_dev inside status_dev.
+ *  7. One launch, no workspace, no allocation, no synchronisation.
+ * Errors, all found before anything is launched: those of flm_track_step_filtered (of flm_track_step without filt; the
+ * dt test only without dt_dev); a null slot_dev or status_rows_dev, state_dev, lm_raw_dev or dt_dev without filt, or one
+ * of the overlaps of 6 -> FLM_ERR_ARG; FLM_ERR_SHAPE unless 1 <= n <= 65535 and 1 <= n_slots <= 65535. */
+int flm_track_step_rows(flm_stream_t stream, const double* lm_dev, size_t lm_stride, const double* w_dev, size_t w_stride,
+                        const float* m_crop_c_dev /*[N,2,3]*/, const int32_t* boxes_c_dev /*[N,4]*/, int n, int c,
+                        double sx, double sy, int in_h, int in_w, int fh, int fw, const double* tmpl_crop_dev /*[C,2]*/,
+                        const double* tmpl_align_dev /*[C,2] or NULL*/, const flm_track_opts* opts,
+                        double* lm_frame_dev /*[N,C,2]*/, float* m_align_dev /*[N,2,3] or NULL*/,
+                        float* m_next_dev /*[n_slots,2,3]*/, int32_t* boxes_next_dev /*[n_slots,4]*/,
+                        int32_t* status_dev /*[n_slots]*/, const flm_track_filter* filt /*or NULL*/, double dt,
+                        double* state_dev /*[n_slots,C,6] or NULL*/, double* lm_raw_dev /*[N,C,2] or NULL*/,
+                        const int32_t* slot_dev /*[N]*/, int n_slots, const double* dt_dev /*[N] or NULL*/,
+                        int32_t* status_rows_dev /*[N]*/);
+
 /* ---- association: detector boxes against live tracks --------------------------------------------------------------
  * flm_track_associate: what a tracker does at the moment a detector has run again -- pair its boxes with the live
  * slots, end the slots that sit on the same face as a lower one, end the slots no detection has confirmed for a while,
@@ -975,6 +1052,35 @@ int flm_track_best_update(flm_stream_t stream, const void* faces_dev, size_t fac
                           const double* best_q_in /*[K]*/, double* best_q_out /*[K]*/, void* gallery_dev /*[K,face_bytes]*/,
                           int64_t* best_frame_dev /*[K]*/, float* best_m_dev /*[K,2,3] or NULL*/,
                           double* best_lm_dev /*[K,C,2] or NULL*/, int64_t* best_rec_dev /*[K,8] or NULL*/);
+
+/* flm_track_best_update_rows: flm_track_best_update on rows (see "rows" in the tracking section), in ONE launch.
+ *   compact, read at row r:   faces_dev [N,face_bytes], rec_dev [N,8], status_rows_dev [N] or NULL, reset_c_dev [N] or
+ *                             NULL, lm_dev, w_dev, factor_dev [N] or NULL, m_dev [N,2,3] or NULL, and best_q_c float64
+ *                             [N]: the SNAPSHOT of the slots' best quality, the `prev` below, which nobody writes during
+ *                             the launch (flm_track_gather_streams makes it)
+ *   global, written at slot g = slot_dev[r]:  best_q_dev float64 [n_slots], gallery_dev [n_slots,face_bytes],
+ *                             best_frame_dev [n_slots], best_m_dev, best_lm_dev, best_rec_dev (each or NULL)
+ * Contract: q and ELIGIBLE are those of flm_track_best_update, word for word, computed from row r;
+ * prev = (reset_c_dev && reset_c_dev[r] != 0) ? -1.0 : best_q_c[r]; TAKEN = eligible and q > prev.  For a valid row
+ * best_q_dev[g] = taken ? q : prev, and when taken the face's bytes, frame_id and, each where its pointer is given, the
+ * row's matrix, landmarks and record go to slot g.  An inert row, and a slot no row names, write nothing: gallery,
+ * best_q and the rest keep their bits.
+ * Reading prev from the snapshot is what keeps the launch race-free with best_q written IN PLACE: as in
+ * flm_track_best_update, several workgroups of a row each derive the decision again, and they agree because they
+ * derive it from inputs nobody writes -- there best_q_in, a second buffer; here best_q_c.  best_q_c must not overlap
+ * best_q_dev; no output may overlap an input.
+ * Errors, all found before anything is launched: those of flm_track_best_update with n for k and best_q_c, best_q_dev for
+ * best_q_in, best_q_out; a null slot_dev -> FLM_ERR_ARG; FLM_ERR_SHAPE unless 1 <= n_slots <= 65535. */
+int flm_track_best_update_rows(flm_stream_t stream, const void* faces_dev, size_t face_bytes, int n,
+                               const int64_t* rec_dev /*[N,8]*/, const int32_t* status_rows_dev /*[N] or NULL*/,
+                               const int32_t* reset_c_dev /*[N] or NULL*/, const double* lm_dev, size_t lm_stride,
+                               const double* w_dev /*or NULL*/, size_t w_stride, int c,
+                               const double* factor_dev /*[N] or NULL*/, const float* m_dev /*[N,2,3] or NULL*/,
+                               int64_t frame_id, const flm_best_opts* opts /*NULL = defaults*/,
+                               const int32_t* slot_dev /*[N]*/, int n_slots, const double* best_q_c /*[N]*/,
+                               double* best_q_dev /*[n_slots]*/, void* gallery_dev /*[n_slots,face_bytes]*/,
+                               int64_t* best_frame_dev /*[n_slots]*/, float* best_m_dev /*[n_slots,2,3] or NULL*/,
+                               double* best_lm_dev /*[n_slots,C,2] or NULL*/, int64_t* best_rec_dev /*[n_slots,8] or NULL*/);
 
 #ifdef __cplusplus
 }
