@@ -279,6 +279,12 @@ def _uniform_stride(t, inner):
     return int(step)
 
 
+def _strided(t, inner):
+    """(tensor, element stride between points) of a view read in place; a view without a uniform stride is copied."""
+    st = _uniform_stride(t, inner)
+    return (t.contiguous(), inner) if st is None else (t, st)
+
+
 def similarity_device(landmarks, template, landmark_scale=(1.0, 1.0), weights=None):
     """landmarks: CUDA float64 [N,K,2]; template: CUDA float64 [K,2] -> CUDA float32 [N,2,3].
     `landmark_scale` (sx, sy) takes the landmarks to the template's pixel units inside the kernel (float64
@@ -301,12 +307,8 @@ def similarity_device(landmarks, template, landmark_scale=(1.0, 1.0), weights=No
             raise ValueError("weights must be a float64 [%d,%d] tensor on the landmarks' device" % (n, k))
         if landmarks.shape[2] != 2:
             raise ValueError("landmarks must be [N,K,2]")
-        ls = _uniform_stride(landmarks, 2)
-        if ls is None:
-            landmarks, ls = landmarks.contiguous(), 2
-        wst = _uniform_stride(weights, 1)
-        if wst is None:
-            weights, wst = weights.contiguous(), 1
+        landmarks, ls = _strided(landmarks, 2)
+        weights, wst = _strided(weights, 1)
         if n and k:
             _lib.check(lib.flm_similarity_from_landmarks_weighted(_lib.stream_ptr(), _lib.ptr(landmarks), ls,
                                                                   _lib.ptr(weights), wst, _lib.ptr(template.contiguous()),
@@ -484,6 +486,41 @@ def _sizes(hw, what):
         raise ValueError("%s must be positive" % what)
     return h, w
 
+def _check_overlap(a, b, what):
+    if (a is not None and b is not None and a.numel() and b.numel()
+            and a.data_ptr() < b.data_ptr() + b.numel() * b.element_size()
+            and b.data_ptr() < a.data_ptr() + a.numel() * a.element_size()):
+        raise ValueError("%s must be two buffers that do not overlap" % what)
+
+
+def _out(t, dtype, shape, what, device):
+    """An output of a call: `t` checked against dtype and shape, or a new tensor for None.  Matrices (every [k,2,3]
+    output is one) and boxes go through their own checks, which word the error their way (`_check_boxes` calls every
+    box tensor boxes_dev)."""
+    if t is None:
+        import torch
+        return torch.empty(shape, dtype=dtype, device=device)
+    if what == "boxes_dev":
+        _check_boxes(t, shape[0])
+    elif shape[1:] == (2, 3):
+        _check_matrices(t, shape[0], what)
+    else:
+        _check_out(t, dtype, shape, what)
+    return t
+
+
+def _ptr(t):
+    """The pointer of an optional tensor: NULL for None."""
+    return None if t is None else _lib.ptr(t)
+
+
+def _frame_id(frame_id):
+    """frame_id as the int the C calls take; ValueError for what is no integer of int64."""
+    if isinstance(frame_id, bool) or int(frame_id) != frame_id or not -2 ** 63 <= int(frame_id) < 2 ** 63:
+        raise ValueError("frame_id must be an integer that fits int64 (got %r)" % (frame_id,))
+    return int(frame_id)
+
+
 
 def _strided_points(lm, what="lm"):
     """(tensor, element stride) of a CUDA float64 [K,C,2] tensor or view read in place: rec[..., :2] of a landmark
@@ -491,8 +528,19 @@ def _strided_points(lm, what="lm"):
     import torch
     if not isinstance(lm, torch.Tensor) or lm.dtype != torch.float64 or lm.dim() != 3 or lm.shape[2] != 2 or not lm.is_cuda:
         raise ValueError("%s must be a CUDA float64 [K,C,2] tensor" % what)
-    st = _uniform_stride(lm, 2)
-    return (lm.contiguous(), 2) if st is None else (lm, st)
+    return _strided(lm, 2)
+
+
+def _weights_arg(weights, n, c):
+    """(weights, element stride) of the optional CUDA float64 [n,c] weights of a call, a view of a landmark record tensor
+    read in place; (None, 1) for None."""
+    if weights is None:
+        return None, 1
+    import torch
+    if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64 or tuple(weights.shape) != (n, c)
+            or not weights.is_cuda):
+        raise ValueError("weights must be a CUDA float64 [%d,%d] tensor" % (n, c))
+    return _strided(weights, 1)
 
 
 def track_seed_device(boxes_dev, in_hw, frame_hw, m_out=None, status_out=None):
@@ -506,14 +554,8 @@ def track_seed_device(boxes_dev, in_hw, frame_hw, m_out=None, status_out=None):
     _check_boxes(boxes_dev, k)
     ih, iw = _sizes(in_hw, "in_hw")
     fh, fw = _sizes(frame_hw, "frame_hw")
-    if m_out is None:
-        m_out = torch.empty((k, 2, 3), dtype=torch.float32, device=boxes_dev.device)
-    else:
-        _check_matrices(m_out, k, "m_out")
-    if status_out is None:
-        status_out = torch.empty((k,), dtype=torch.int32, device=boxes_dev.device)
-    else:
-        _check_out(status_out, torch.int32, (k,), "status_out")
+    m_out = _out(m_out, torch.float32, (k, 2, 3), "m_out", boxes_dev.device)
+    status_out = _out(status_out, torch.int32, (k,), "status_out", boxes_dev.device)
     if k:
         _lib.check(_lib.load().flm_track_seed(_lib.stream_ptr(), _lib.ptr(boxes_dev), k, ih, iw, fh, fw, _lib.ptr(m_out),
                                               _lib.ptr(status_out)), "flm_track_seed")
@@ -531,10 +573,7 @@ def landmarks_from_crop_device(lm, m, grid_hw, in_hw, out=None):
     _check_matrices(m, k)
     gh, gw = _sizes(grid_hw, "grid_hw")
     ih, iw = _sizes(in_hw, "in_hw")
-    if out is None:
-        out = torch.empty((k, c, 2), dtype=torch.float64, device=lm.device)
-    else:
-        _check_out(out, torch.float64, (k, c, 2), "out")
+    out = _out(out, torch.float64, (k, c, 2), "out", lm.device)
     if k and c:
         _lib.check(_lib.load().flm_landmarks_from_crop(_lib.stream_ptr(), _lib.ptr(lm), ls, _lib.ptr(m), k, c, iw / gw,
                                                        ih / gh, _lib.ptr(out)), "flm_landmarks_from_crop")
@@ -573,6 +612,92 @@ class LandmarkFilter:
                                                                                  self.fps)
 
 
+def _track_step(lm, m_crop, boxes, grid_hw, in_hw, frame_hw, tmpl_crop, tmpl_align, weights, min_points, min_score,
+                min_side, max_side, lm_frame, m_align, m_next, boxes_next, status, filter, dt, state, lm_raw, rows=False,
+                slot=None, status_rows=None, m_what="m_crop", k_what="K"):
+    """The one statement of `track_step_device` and, with rows=True, of `track_step_rows_device`: the rows form adds
+    slot, n_slots (taken from m_next), a per-row dt tensor, status_rows and the three overlap checks.  m_what, k_what:
+    what the caller names the matrices and the size of the tracker's own tensors.  Returns every tensor the call writes:
+    (lm_frame, m_align, m_next, boxes_next, status, status_rows)."""
+    import torch
+    dt_rows = None
+    if filter is None:
+        if dt is not None or state is not None or lm_raw is not None:
+            raise ValueError("dt, state and lm_raw go with filter")
+    else:                           # (the filter's own arguments first: they need no tensor to be judged)
+        if not isinstance(filter, LandmarkFilter):
+            raise ValueError("filter must be None or a LandmarkFilter (got %r)" % (filter,))
+        if rows and isinstance(dt, torch.Tensor):
+            dt_rows, dt = dt, 0.0
+        else:
+            dt = filter.time_step(dt)
+        if (not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or state.dim() != 3
+                or int(state.shape[2]) != 6):
+            raise ValueError("state must be a contiguous CUDA float64 [%s,C,6] tensor" % k_what)
+    lm, ls = _strided_points(lm)
+    n, c = int(lm.shape[0]), int(lm.shape[1])
+    n_slots = n
+    if rows:                        # the tracker's own tensors are written at the slot: they exist, and give n_slots
+        _check_out(slot, torch.int32, (n,), "slot")
+        _check_matrices(m_next, None, "m_next")
+        n_slots = int(m_next.shape[0])
+        if not 1 <= n_slots <= 65535 or n > 65535:
+            raise ValueError("at most 65535 slots and 65535 rows, at least one slot (got %d slots, %d rows)" % (n_slots, n))
+        _check_boxes(boxes_next, n_slots)
+        _check_out(status, torch.int32, (n_slots,), "status")
+    if filter is not None:
+        _check_out(state, torch.float64, (n_slots, c, 6), "state")
+        if dt_rows is not None:
+            _check_out(dt_rows, torch.float64, (n,), "dt")
+        if lm_raw is not None:
+            _check_out(lm_raw, torch.float64, (n, c, 2), "lm_raw")
+    _check_matrices(m_crop, n, m_what)
+    _check_boxes(boxes, n)
+    gh, gw = _sizes(grid_hw, "grid_hw")
+    ih, iw = _sizes(in_hw, "in_hw")
+    fh, fw = _sizes(frame_hw, "frame_hw")
+    _check_out(tmpl_crop, torch.float64, (c, 2), "tmpl_crop")
+    if tmpl_align is not None:
+        _check_out(tmpl_align, torch.float64, (c, 2), "tmpl_align")
+    weights, wst = _weights_arg(weights, n, c)
+    if m_align is not None and tmpl_align is None:
+        raise ValueError("m_align needs tmpl_align")
+    if int(min_points) < 2:
+        raise ValueError("min_points must be 2 or more")
+    if any(v != v for v in (float(min_score), float(min_side), float(max_side))):
+        raise ValueError("min_score, min_side and max_side must not be NaN")
+    dev = lm.device
+    lm_frame = _out(lm_frame, torch.float64, (n, c, 2), "lm_frame", dev)
+    if tmpl_align is not None:
+        m_align = _out(m_align, torch.float32, (n, 2, 3), "m_align", dev)
+    if rows:
+        status_rows = _out(status_rows, torch.int32, (n,), "status_rows", dev)
+        _check_overlap(m_crop, m_next, "m_crop_c and m_next")
+        _check_overlap(boxes, boxes_next, "boxes_c and boxes_next")
+        _check_overlap(status_rows, status, "status_rows and status")
+    else:
+        m_next = _out(m_next, torch.float32, (n, 2, 3), "m_next", dev)
+        boxes_next = _out(boxes_next, torch.int32, (n, 4), "boxes_dev", dev)
+        status = _out(status, torch.int32, (n,), "status", dev)
+    if n and c:
+        lib = _lib.load()
+        opts = _lib.TrackOpts.make(min_points, min_score, min_side, max_side)
+        fo = None if filter is None else _lib.TrackFilter.make(filter.min_cutoff, filter.beta, filter.d_cutoff)
+        args = (_lib.stream_ptr(), _lib.ptr(lm), ls, _ptr(weights), wst, _lib.ptr(m_crop), _lib.ptr(boxes), n, c, iw / gw,
+                ih / gh, ih, iw, fh, fw, _lib.ptr(tmpl_crop), _ptr(tmpl_align), _lib.C.byref(opts), _lib.ptr(lm_frame),
+                _ptr(m_align), _lib.ptr(m_next), _lib.ptr(boxes_next), _lib.ptr(status))
+        if rows:
+            _lib.check(lib.flm_track_step_rows(*args, None if fo is None else _lib.C.byref(fo), 0.0 if fo is None else dt,
+                                               _ptr(state), _ptr(lm_raw), _lib.ptr(slot), n_slots, _ptr(dt_rows),
+                                               _lib.ptr(status_rows)), "flm_track_step_rows")
+        elif fo is None:
+            _lib.check(lib.flm_track_step(*args), "flm_track_step")
+        else:
+            _lib.check(lib.flm_track_step_filtered(*args, _lib.C.byref(fo), dt, _lib.ptr(state), _ptr(lm_raw)),
+                       "flm_track_step_filtered")
+    return lm_frame, m_align, m_next, boxes_next, status, status_rows
+
+
 def track_step_device(lm, m_crop, boxes_dev, grid_hw, in_hw, frame_hw, tmpl_crop, tmpl_align=None, weights=None,
                       min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"), lm_frame=None, m_align=None,
                       m_next=None, boxes_next=None, status=None, filter=None, dt=None, state=None, lm_raw=None):
@@ -592,81 +717,9 @@ def track_step_device(lm, m_crop, boxes_dev, grid_hw, in_hw, frame_hw, tmpl_crop
     `state` is the CUDA float64 [K,C,6] filter state, read and written (filled with -1: no history), `dt` the seconds
     since the previous step (None: 1/filter.fps), and `lm_raw`, if given, a CUDA float64 [K,C,2] tensor that receives
     the unfiltered points."""
-    import torch
-    if filter is None:
-        if dt is not None or state is not None or lm_raw is not None:
-            raise ValueError("dt, state and lm_raw go with filter")
-    else:                           # (the filter's own arguments first: they need no tensor to be judged)
-        if not isinstance(filter, LandmarkFilter):
-            raise ValueError("filter must be None or a LandmarkFilter (got %r)" % (filter,))
-        dt = filter.time_step(dt)
-        if (not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or state.dim() != 3
-                or int(state.shape[2]) != 6):
-            raise ValueError("state must be a contiguous CUDA float64 [K,C,6] tensor")
-    lm, ls = _strided_points(lm)
-    k, c = int(lm.shape[0]), int(lm.shape[1])
-    if filter is not None:
-        _check_out(state, torch.float64, (k, c, 6), "state")
-        if lm_raw is not None:
-            _check_out(lm_raw, torch.float64, (k, c, 2), "lm_raw")
-    _check_matrices(m_crop, k, "m_crop")
-    _check_boxes(boxes_dev, k)
-    gh, gw = _sizes(grid_hw, "grid_hw")
-    ih, iw = _sizes(in_hw, "in_hw")
-    fh, fw = _sizes(frame_hw, "frame_hw")
-    _check_out(tmpl_crop, torch.float64, (c, 2), "tmpl_crop")
-    if tmpl_align is not None:
-        _check_out(tmpl_align, torch.float64, (c, 2), "tmpl_align")
-    wst = 1
-    if weights is not None:
-        if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64 or tuple(weights.shape) != (k, c)
-                or not weights.is_cuda):
-            raise ValueError("weights must be a CUDA float64 [%d,%d] tensor" % (k, c))
-        wst = _uniform_stride(weights, 1)
-        if wst is None:
-            weights, wst = weights.contiguous(), 1
-    if m_align is not None and tmpl_align is None:
-        raise ValueError("m_align needs tmpl_align")
-    if int(min_points) < 2:
-        raise ValueError("min_points must be 2 or more")
-    if any(v != v for v in (float(min_score), float(min_side), float(max_side))):
-        raise ValueError("min_score, min_side and max_side must not be NaN")
-    dev = lm.device
-    if lm_frame is None:
-        lm_frame = torch.empty((k, c, 2), dtype=torch.float64, device=dev)
-    else:
-        _check_out(lm_frame, torch.float64, (k, c, 2), "lm_frame")
-    if tmpl_align is not None:
-        if m_align is None:
-            m_align = torch.empty((k, 2, 3), dtype=torch.float32, device=dev)
-        else:
-            _check_matrices(m_align, k, "m_align")
-    if m_next is None:
-        m_next = torch.empty((k, 2, 3), dtype=torch.float32, device=dev)
-    else:
-        _check_matrices(m_next, k, "m_next")
-    if boxes_next is None:
-        boxes_next = torch.empty((k, 4), dtype=torch.int32, device=dev)
-    else:
-        _check_boxes(boxes_next, k)
-    if status is None:
-        status = torch.empty((k,), dtype=torch.int32, device=dev)
-    else:
-        _check_out(status, torch.int32, (k,), "status")
-    if k and c:
-        opts = _lib.TrackOpts.make(min_points, min_score, min_side, max_side)
-        args = (_lib.stream_ptr(), _lib.ptr(lm), ls, None if weights is None else _lib.ptr(weights), wst, _lib.ptr(m_crop),
-                _lib.ptr(boxes_dev), k, c, iw / gw, ih / gh, ih, iw, fh, fw, _lib.ptr(tmpl_crop),
-                None if tmpl_align is None else _lib.ptr(tmpl_align), _lib.C.byref(opts), _lib.ptr(lm_frame),
-                None if m_align is None else _lib.ptr(m_align), _lib.ptr(m_next), _lib.ptr(boxes_next), _lib.ptr(status))
-        if filter is None:
-            _lib.check(_lib.load().flm_track_step(*args), "flm_track_step")
-        else:
-            fo = _lib.TrackFilter.make(filter.min_cutoff, filter.beta, filter.d_cutoff)
-            _lib.check(_lib.load().flm_track_step_filtered(*args, _lib.C.byref(fo), dt, _lib.ptr(state),
-                                                           None if lm_raw is None else _lib.ptr(lm_raw)),
-                       "flm_track_step_filtered")
-    return lm_frame, m_align, m_next, boxes_next, status
+    return _track_step(lm, m_crop, boxes_dev, grid_hw, in_hw, frame_hw, tmpl_crop, tmpl_align, weights, min_points,
+                       min_score, min_side, max_side, lm_frame, m_align, m_next, boxes_next, status, filter, dt, state,
+                       lm_raw)[:5]
 
 
 # ---- association: detector boxes against live tracks (include/flm.h, "association") ----------------------------------
@@ -699,6 +752,83 @@ class TrackAssociation:
             self.match_iou, self.dup_iou, self.refresh_iou, self.max_misses, self.square)
 
 
+def _track_associate(who, det, m_crop, boxes, status, misses, in_hw, frame_hw, n_det, state, assoc, det_slot, slot_det,
+                     counts, streams=False, slots_per_stream=None):
+    """The one statement of `track_associate_device` and, with streams=True, of `track_associate_streams_device`: the
+    single call is the streams call without the S axis -- det is 2-D, n_det has one element, counts is [8] and the slots
+    are those of m_crop.  who: the caller's name, for its messages."""
+    import torch
+    if assoc is None:
+        assoc = TrackAssociation()
+    elif not isinstance(assoc, TrackAssociation):
+        raise ValueError("assoc must be None or a TrackAssociation (got %r)" % (assoc,))
+    if streams:
+        if not isinstance(det, torch.Tensor) or det.dim() != 3 or det.dtype != torch.int32 or int(det.shape[2]) != 4:
+            raise ValueError("det must be a contiguous CUDA int32 [S,D,4] tensor")
+        s, d = int(det.shape[0]), int(det.shape[1])
+        if n_det is not None and (not isinstance(n_det, torch.Tensor) or n_det.dtype != torch.int32
+                                  or tuple(n_det.shape) != (s,)):
+            raise ValueError("n_det must be None or a contiguous CUDA int32 [%d] tensor, one count per stream" % s)
+        if not det.is_cuda or not det.is_contiguous():
+            raise ValueError("det must be a contiguous CUDA int32 [S,D,4] tensor")
+        if isinstance(slots_per_stream, bool) or int(slots_per_stream) != slots_per_stream:
+            raise ValueError("slots_per_stream must be an integer (got %r)" % (slots_per_stream,))
+        k = int(slots_per_stream)
+        if s < 1 or not 1 <= d <= ASSOC_MAX or not 1 <= k <= ASSOC_MAX:
+            raise ValueError("%s takes 1 or more streams of 1..%d detections and 1..%d slots each "
+                             "(got %d streams, %d, %d)" % (who, ASSOC_MAX, ASSOC_MAX, s, d, k))
+        n = s * k
+        if n > 65535:
+            raise ValueError("%d streams of %d slots exceed the tracker's 65535 slots" % (s, k))
+        _check_matrices(m_crop, n, "m_crop")
+    else:
+        if not isinstance(det, torch.Tensor) or det.dim() != 2:
+            raise ValueError("det must be a contiguous CUDA int32 [D,4] tensor")
+        s, d = 1, int(det.shape[0])
+        if (det.dtype != torch.int32 or not det.is_cuda or not det.is_contiguous() or int(det.shape[1]) != 4):
+            raise ValueError("det must be a contiguous CUDA int32 [D,4] tensor")
+        _check_matrices(m_crop, None, "m_crop")
+        n = k = int(m_crop.shape[0])
+        if not 1 <= d <= ASSOC_MAX or not 1 <= k <= ASSOC_MAX:
+            raise ValueError("%s takes 1..%d detections and 1..%d slots (got %d, %d)" % (who, ASSOC_MAX, ASSOC_MAX, d, k))
+    _check_boxes(boxes, n)
+    _check_out(status, torch.int32, (n,), "status")
+    _check_out(misses, torch.int32, (n,), "misses")
+    if n_det is not None:
+        if streams:
+            _check_out(n_det, torch.int32, (s,), "n_det")
+        elif (not isinstance(n_det, torch.Tensor) or n_det.dtype != torch.int32 or not n_det.is_cuda or n_det.numel() != 1
+                or not n_det.is_contiguous()):
+            raise ValueError("n_det must be None or a CUDA int32 tensor of one element")
+    c = 1
+    if state is not None:
+        if not isinstance(state, torch.Tensor) or state.dim() != 3:
+            raise ValueError("state must be a contiguous CUDA float64 [%s,C,6] tensor" % ("S*K" if streams else "K"))
+        c = int(state.shape[1])
+        _check_out(state, torch.float64, (n, c, 6), "state")
+        if not 1 <= c <= 1024:
+            raise ValueError("state must have 1..1024 landmarks (got %d)" % c)
+    ih, iw = _sizes(in_hw, "in_hw")
+    fh, fw = _sizes(frame_hw, "frame_hw")
+    if fh * fw > 2 ** 30:
+        raise ValueError("frames of %dx%d are outside the association's reach (H*W <= 2^30)" % (fh, fw))
+    tensors = [det, m_crop, boxes, status, misses] + [t for t in (n_det, state) if t is not None]
+    det_slot = _out(det_slot, torch.int32, (s, d) if streams else (d,), "det_slot", det.device)
+    slot_det = _out(slot_det, torch.int32, (n,), "slot_det", det.device)
+    counts = _out(counts, torch.int32, (s, 8) if streams else (8,), "counts", det.device)
+    if any(t.device != det.device for t in tensors + [det_slot, slot_det, counts]):
+        raise ValueError("every tensor of %s must lie on the device of det" % who)
+    opts = assoc.struct()
+    head = (_lib.stream_ptr(), _lib.ptr(det), _ptr(n_det))
+    tail = (d, k, c, ih, iw, fh, fw, _lib.C.byref(opts), _lib.ptr(m_crop), _lib.ptr(boxes), _lib.ptr(status),
+            _lib.ptr(misses), _ptr(state), _lib.ptr(det_slot), _lib.ptr(slot_det), _lib.ptr(counts))
+    if streams:
+        _lib.check(_lib.load().flm_track_associate_streams(*head, s, *tail), "flm_track_associate_streams")
+    else:
+        _lib.check(_lib.load().flm_track_associate(*head, *tail), "flm_track_associate")
+    return det_slot, slot_det, counts
+
+
 def track_associate_device(det, m_crop, boxes, status, misses, in_hw, frame_hw, n_det=None, state=None, assoc=None,
                            det_slot=None, slot_det=None, counts=None):
     """Detector boxes against the live tracks of a tracker in one launch (flm_track_associate; include/flm.h states it
@@ -711,62 +841,8 @@ def track_associate_device(det, m_crop, boxes, status, misses, in_hw, frame_hw, 
     Returns (det_slot int32 [D]: the slot a detection matched or was born into, -1 for a void or unread row, -2 when no
     slot was free; slot_det int32 [K]: the detection of a matched or born slot, else -1; counts int32 [8]: matched,
     born, restarted, duplicates, unconfirmed, dropped, void, 0).  The three keyword tensors name where to write."""
-    import torch
-    if assoc is None:
-        assoc = TrackAssociation()
-    elif not isinstance(assoc, TrackAssociation):
-        raise ValueError("assoc must be None or a TrackAssociation (got %r)" % (assoc,))
-    if not isinstance(det, torch.Tensor) or det.dim() != 2:
-        raise ValueError("det must be a contiguous CUDA int32 [D,4] tensor")
-    d = int(det.shape[0])
-    if (det.dtype != torch.int32 or not det.is_cuda or not det.is_contiguous() or int(det.shape[1]) != 4):
-        raise ValueError("det must be a contiguous CUDA int32 [D,4] tensor")
-    _check_matrices(m_crop, None, "m_crop")
-    k = int(m_crop.shape[0])
-    if not 1 <= d <= ASSOC_MAX or not 1 <= k <= ASSOC_MAX:
-        raise ValueError("track_associate_device takes 1..%d detections and 1..%d slots (got %d, %d)"
-                         % (ASSOC_MAX, ASSOC_MAX, d, k))
-    _check_boxes(boxes, k)
-    _check_out(status, torch.int32, (k,), "status")
-    _check_out(misses, torch.int32, (k,), "misses")
-    if n_det is not None:
-        if (not isinstance(n_det, torch.Tensor) or n_det.dtype != torch.int32 or not n_det.is_cuda or n_det.numel() != 1
-                or not n_det.is_contiguous()):
-            raise ValueError("n_det must be None or a CUDA int32 tensor of one element")
-    c = 1
-    if state is not None:
-        if not isinstance(state, torch.Tensor) or state.dim() != 3:
-            raise ValueError("state must be a contiguous CUDA float64 [K,C,6] tensor")
-        c = int(state.shape[1])
-        _check_out(state, torch.float64, (k, c, 6), "state")
-        if not 1 <= c <= 1024:
-            raise ValueError("state must have 1..1024 landmarks (got %d)" % c)
-    ih, iw = _sizes(in_hw, "in_hw")
-    fh, fw = _sizes(frame_hw, "frame_hw")
-    if fh * fw > 2 ** 30:
-        raise ValueError("frames of %dx%d are outside the association's reach (H*W <= 2^30)" % (fh, fw))
-    tensors = [det, m_crop, boxes, status, misses] + [t for t in (n_det, state) if t is not None]
-    if det_slot is None:
-        det_slot = torch.empty((d,), dtype=torch.int32, device=det.device)
-    else:
-        _check_out(det_slot, torch.int32, (d,), "det_slot")
-    if slot_det is None:
-        slot_det = torch.empty((k,), dtype=torch.int32, device=det.device)
-    else:
-        _check_out(slot_det, torch.int32, (k,), "slot_det")
-    if counts is None:
-        counts = torch.empty((8,), dtype=torch.int32, device=det.device)
-    else:
-        _check_out(counts, torch.int32, (8,), "counts")
-    if any(t.device != det.device for t in tensors + [det_slot, slot_det, counts]):
-        raise ValueError("every tensor of track_associate_device must lie on the device of det")
-    opts = assoc.struct()
-    _lib.check(_lib.load().flm_track_associate(
-        _lib.stream_ptr(), _lib.ptr(det), None if n_det is None else _lib.ptr(n_det), d, k, c, ih, iw, fh, fw,
-        _lib.C.byref(opts), _lib.ptr(m_crop), _lib.ptr(boxes), _lib.ptr(status), _lib.ptr(misses),
-        None if state is None else _lib.ptr(state), _lib.ptr(det_slot), _lib.ptr(slot_det), _lib.ptr(counts)),
-        "flm_track_associate")
-    return det_slot, slot_det, counts
+    return _track_associate("track_associate_device", det, m_crop, boxes, status, misses, in_hw, frame_hw, n_det, state,
+                            assoc, det_slot, slot_det, counts)
 
 
 def track_associate_streams_device(det, m_crop, boxes, status, misses, slots_per_stream, in_hw, frame_hw, n_det=None,
@@ -783,68 +859,8 @@ def track_associate_streams_device(det, m_crop, boxes, status, misses, slots_per
     unread row or a skipped stream, -2 when no slot of its stream was free; slot_det int32 [S*K]: the row inside det[i]
     of a matched or born slot, else -1; counts int32 [S,8], per stream as `track_associate_device` lists them, zero for
     a skipped stream).  The three keyword tensors name where to write."""
-    import torch
-    if assoc is None:
-        assoc = TrackAssociation()
-    elif not isinstance(assoc, TrackAssociation):
-        raise ValueError("assoc must be None or a TrackAssociation (got %r)" % (assoc,))
-    if not isinstance(det, torch.Tensor) or det.dim() != 3 or det.dtype != torch.int32 or int(det.shape[2]) != 4:
-        raise ValueError("det must be a contiguous CUDA int32 [S,D,4] tensor")
-    s, d = int(det.shape[0]), int(det.shape[1])
-    if n_det is not None and (not isinstance(n_det, torch.Tensor) or n_det.dtype != torch.int32
-                              or tuple(n_det.shape) != (s,)):
-        raise ValueError("n_det must be None or a contiguous CUDA int32 [%d] tensor, one count per stream" % s)
-    if not det.is_cuda or not det.is_contiguous():
-        raise ValueError("det must be a contiguous CUDA int32 [S,D,4] tensor")
-    if isinstance(slots_per_stream, bool) or int(slots_per_stream) != slots_per_stream:
-        raise ValueError("slots_per_stream must be an integer (got %r)" % (slots_per_stream,))
-    k = int(slots_per_stream)
-    if s < 1 or not 1 <= d <= ASSOC_MAX or not 1 <= k <= ASSOC_MAX:
-        raise ValueError("track_associate_streams_device takes 1 or more streams of 1..%d detections and 1..%d slots each "
-                         "(got %d streams, %d, %d)" % (ASSOC_MAX, ASSOC_MAX, s, d, k))
-    n = s * k
-    if n > 65535:
-        raise ValueError("%d streams of %d slots exceed the tracker's 65535 slots" % (s, k))
-    _check_matrices(m_crop, n, "m_crop")
-    _check_boxes(boxes, n)
-    _check_out(status, torch.int32, (n,), "status")
-    _check_out(misses, torch.int32, (n,), "misses")
-    if n_det is not None:
-        _check_out(n_det, torch.int32, (s,), "n_det")
-    c = 1
-    if state is not None:
-        if not isinstance(state, torch.Tensor) or state.dim() != 3:
-            raise ValueError("state must be a contiguous CUDA float64 [S*K,C,6] tensor")
-        c = int(state.shape[1])
-        _check_out(state, torch.float64, (n, c, 6), "state")
-        if not 1 <= c <= 1024:
-            raise ValueError("state must have 1..1024 landmarks (got %d)" % c)
-    ih, iw = _sizes(in_hw, "in_hw")
-    fh, fw = _sizes(frame_hw, "frame_hw")
-    if fh * fw > 2 ** 30:
-        raise ValueError("frames of %dx%d are outside the association's reach (H*W <= 2^30)" % (fh, fw))
-    tensors = [det, m_crop, boxes, status, misses] + [t for t in (n_det, state) if t is not None]
-    if det_slot is None:
-        det_slot = torch.empty((s, d), dtype=torch.int32, device=det.device)
-    else:
-        _check_out(det_slot, torch.int32, (s, d), "det_slot")
-    if slot_det is None:
-        slot_det = torch.empty((n,), dtype=torch.int32, device=det.device)
-    else:
-        _check_out(slot_det, torch.int32, (n,), "slot_det")
-    if counts is None:
-        counts = torch.empty((s, 8), dtype=torch.int32, device=det.device)
-    else:
-        _check_out(counts, torch.int32, (s, 8), "counts")
-    if any(t.device != det.device for t in tensors + [det_slot, slot_det, counts]):
-        raise ValueError("every tensor of track_associate_streams_device must lie on the device of det")
-    opts = assoc.struct()
-    _lib.check(_lib.load().flm_track_associate_streams(
-        _lib.stream_ptr(), _lib.ptr(det), None if n_det is None else _lib.ptr(n_det), s, d, k, c, ih, iw, fh, fw,
-        _lib.C.byref(opts), _lib.ptr(m_crop), _lib.ptr(boxes), _lib.ptr(status), _lib.ptr(misses),
-        None if state is None else _lib.ptr(state), _lib.ptr(det_slot), _lib.ptr(slot_det), _lib.ptr(counts)),
-        "flm_track_associate_streams")
-    return det_slot, slot_det, counts
+    return _track_associate("track_associate_streams_device", det, m_crop, boxes, status, misses, in_hw, frame_hw, n_det,
+                            state, assoc, det_slot, slot_det, counts, streams=True, slots_per_stream=slots_per_stream)
 
 
 # ---- the best shot of a track: face quality and gallery (include/flm.h, "the best shot of a track") -------------------
@@ -933,10 +949,7 @@ def face_quality_device(faces, fmt=None, opts=None, out=None):
     elif not isinstance(opts, QualityOptions):
         raise ValueError("opts must be None or a QualityOptions (got %r)" % (opts,))
     fmt, k, h, w = _faces_of(faces, fmt)
-    if out is None:
-        out = torch.empty((k, QUALITY_REC), dtype=torch.int64, device=faces.device)
-    else:
-        _check_out(out, torch.int64, (k, QUALITY_REC), "out")
+    out = _out(out, torch.int64, (k, QUALITY_REC), "out", faces.device)
     if k:
         cf, co = fmt.struct(), opts.struct()
         _lib.check(_lib.load().flm_face_quality(_lib.stream_ptr(), _lib.ptr(faces), k, h, w, _lib.C.byref(cf),
@@ -964,6 +977,74 @@ def quality_scalars(rec):
     return out.numpy() if is_np else out
 
 
+def _track_best_update(faces, rec, lm, best_q_in, best_q_out, gallery, best_frame, frame_id, status, reset, weights, factor,
+                       m, opts, best_m, best_lm, best_rec, rows=False, slot=None,
+                       names=("K", "status", "reset", "best_q_in", "best_q_out")):
+    """The one statement of `track_best_update_device` and, with rows=True, of `track_best_update_rows_device`.  The
+    dense form: the gallery has the faces' full shape and best_q_in, best_q_out are two buffers of the faces' length.
+    The rows form: gallery, best_q_out and the three optional outputs have n_slots entries and are written at `slot`.
+    names: what the caller names the number of faces, status, reset and the two quality buffers."""
+    import torch
+    k_what, status_what, reset_what, q_in_what, q_out_what = names
+    if opts is None:
+        opts = BestShot()
+    elif not isinstance(opts, BestShot):
+        raise ValueError("opts must be None or a BestShot (got %r)" % (opts,))
+    frame_id = _frame_id(frame_id)
+    if not isinstance(faces, torch.Tensor) or faces.dim() < 1 or not faces.is_cuda or not faces.is_contiguous():
+        raise ValueError("faces must be a contiguous CUDA tensor of %s faces" % k_what)
+    n = n_slots = int(faces.shape[0])
+    if rows:
+        if (not isinstance(gallery, torch.Tensor) or gallery.dtype != faces.dtype or gallery.dim() != faces.dim()
+                or gallery.shape[1:] != faces.shape[1:] or not gallery.is_cuda or not gallery.is_contiguous()):
+            raise ValueError("gallery must be a contiguous CUDA tensor of the dtype and face shape of faces")
+        n_slots = int(gallery.shape[0])
+        if not 1 <= n_slots <= 65535 or n > 65535:
+            raise ValueError("at most 65535 slots and 65535 rows, at least one slot (got %d slots, %d rows)" % (n_slots, n))
+        _check_out(slot, torch.int32, (n,), "slot")
+    elif (not isinstance(gallery, torch.Tensor) or gallery.dtype != faces.dtype or gallery.shape != faces.shape
+            or not gallery.is_cuda or not gallery.is_contiguous()):
+        raise ValueError("gallery must be a contiguous CUDA tensor of the dtype and shape of faces")
+    _check_out(rec, torch.int64, (n, QUALITY_REC), "rec")
+    lm, ls = _strided_points(lm)
+    c = int(lm.shape[1])
+    if int(lm.shape[0]) != n:
+        raise ValueError("lm must be a CUDA float64 [%d,C,2] tensor" % n)
+    weights, wst = _weights_arg(weights, n, c)
+    for t, dtype, name in ((status, torch.int32, status_what), (reset, torch.int32, reset_what),
+                           (factor, torch.float64, "factor")):
+        if t is not None:
+            _check_out(t, dtype, (n,), name)
+    if m is not None:
+        _check_matrices(m, n)
+    _check_out(best_q_in, torch.float64, (n,), q_in_what)
+    _check_out(best_q_out, torch.float64, (n_slots,), q_out_what)
+    _check_overlap(best_q_in, best_q_out, "%s and %s" % (q_in_what, q_out_what))
+    if rows:
+        _check_overlap(faces, gallery, "faces and gallery")
+    _check_out(best_frame, torch.int64, (n_slots,), "best_frame")
+    if best_m is not None:
+        if m is None:
+            raise ValueError("best_m needs m")
+        _check_matrices(best_m, n_slots, "best_m")
+    if best_lm is not None:
+        _check_out(best_lm, torch.float64, (n_slots, c, 2), "best_lm")
+    if best_rec is not None:
+        _check_out(best_rec, torch.int64, (n_slots, QUALITY_REC), "best_rec")
+    if n and c:
+        co = opts.struct()
+        head = (_lib.stream_ptr(), _lib.ptr(faces), faces.numel() // n * faces.element_size(), n, _lib.ptr(rec), _ptr(status),
+                _ptr(reset), _lib.ptr(lm), ls, _ptr(weights), wst, c, _ptr(factor), _ptr(m), frame_id, _lib.C.byref(co))
+        tail = (_lib.ptr(best_q_in), _lib.ptr(best_q_out), _lib.ptr(gallery), _lib.ptr(best_frame), _ptr(best_m),
+                _ptr(best_lm), _ptr(best_rec))
+        if rows:
+            _lib.check(_lib.load().flm_track_best_update_rows(*head, _lib.ptr(slot), n_slots, *tail),
+                       "flm_track_best_update_rows")
+        else:
+            _lib.check(_lib.load().flm_track_best_update(*head, *tail), "flm_track_best_update")
+    return best_q_out
+
+
 def track_best_update_device(faces, rec, lm, best_q_in, best_q_out, gallery, best_frame, frame_id, status=None,
                              reset=None, weights=None, factor=None, m=None, opts=None, best_m=None, best_lm=None,
                              best_rec=None):
@@ -978,68 +1059,11 @@ def track_best_update_device(faces, rec, lm, best_q_in, best_q_out, gallery, bes
     best_m, best_lm, best_rec: None or CUDA float32 [K,2,3], float64 [K,C,2], int64 [K,8].  A slot that is eligible and
     strictly better has its face, quality, frame id, matrix, landmarks and record written; any other keeps every bit
     and best_q_out = its previous best.  Returns best_q_out."""
-    import torch
-    if opts is None:
-        opts = BestShot()
-    elif not isinstance(opts, BestShot):
-        raise ValueError("opts must be None or a BestShot (got %r)" % (opts,))
-    if isinstance(frame_id, bool) or int(frame_id) != frame_id or not -2 ** 63 <= int(frame_id) < 2 ** 63:
-        raise ValueError("frame_id must be an integer that fits int64 (got %r)" % (frame_id,))
-    if not isinstance(faces, torch.Tensor) or faces.dim() < 1 or not faces.is_cuda or not faces.is_contiguous():
-        raise ValueError("faces must be a contiguous CUDA tensor of K faces")
-    k = int(faces.shape[0])
-    if (not isinstance(gallery, torch.Tensor) or gallery.dtype != faces.dtype or gallery.shape != faces.shape
-            or not gallery.is_cuda or not gallery.is_contiguous()):
-        raise ValueError("gallery must be a contiguous CUDA tensor of the dtype and shape of faces")
-    _check_out(rec, torch.int64, (k, QUALITY_REC), "rec")
-    lm, ls = _strided_points(lm)
-    c = int(lm.shape[1])
-    if int(lm.shape[0]) != k:
-        raise ValueError("lm must be a CUDA float64 [%d,C,2] tensor" % k)
-    wst = 1
-    if weights is not None:
-        if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64 or tuple(weights.shape) != (k, c)
-                or not weights.is_cuda):
-            raise ValueError("weights must be a CUDA float64 [%d,%d] tensor" % (k, c))
-        wst = _uniform_stride(weights, 1)
-        if wst is None:
-            weights, wst = weights.contiguous(), 1
-    for t, dt, name in ((status, torch.int32, "status"), (reset, torch.int32, "reset"), (factor, torch.float64, "factor")):
-        if t is not None:
-            _check_out(t, dt, (k,), name)
-    if m is not None:
-        _check_matrices(m, k)
-    _check_out(best_q_in, torch.float64, (k,), "best_q_in")
-    _check_out(best_q_out, torch.float64, (k,), "best_q_out")
-    if k and best_q_in.data_ptr() < best_q_out.data_ptr() + 8 * k and best_q_out.data_ptr() < best_q_in.data_ptr() + 8 * k:
-        raise ValueError("best_q_in and best_q_out must be two buffers that do not overlap")
-    _check_out(best_frame, torch.int64, (k,), "best_frame")
-    if best_m is not None:
-        if m is None:
-            raise ValueError("best_m needs m")
-        _check_matrices(best_m, k, "best_m")
-    if best_lm is not None:
-        _check_out(best_lm, torch.float64, (k, c, 2), "best_lm")
-    if best_rec is not None:
-        _check_out(best_rec, torch.int64, (k, QUALITY_REC), "best_rec")
-    if k and c:
-        face_bytes = faces.numel() // k * faces.element_size()
-        co = opts.struct()
-        p = lambda t: None if t is None else _lib.ptr(t)
-        _lib.check(_lib.load().flm_track_best_update(
-            _lib.stream_ptr(), _lib.ptr(faces), face_bytes, k, _lib.ptr(rec), p(status), p(reset), _lib.ptr(lm), ls,
-            p(weights), wst, c, p(factor), p(m), int(frame_id), _lib.C.byref(co), _lib.ptr(best_q_in), _lib.ptr(best_q_out),
-            _lib.ptr(gallery), _lib.ptr(best_frame), p(best_m), p(best_lm), p(best_rec)), "flm_track_best_update")
-    return best_q_out
+    return _track_best_update(faces, rec, lm, best_q_in, best_q_out, gallery, best_frame, frame_id, status, reset, weights,
+                              factor, m, opts, best_m, best_lm, best_rec)
 
 
 # ---- rows: stepping the streams that delivered a frame, each on its own clock (include/flm.h, "rows") -----------------
-def _check_overlap(a, b, what):
-    if (a is not None and b is not None and a.numel() and b.numel()
-            and a.data_ptr() < b.data_ptr() + b.numel() * b.element_size()
-            and b.data_ptr() < a.data_ptr() + a.numel() * a.element_size()):
-        raise ValueError("%s must be two buffers that do not overlap" % what)
-
 
 def track_gather_streams_device(active, m_crop, boxes, slots_per_stream, frame_index=None, dt=None, best_q=None,
                                 reset=None, out=None):
@@ -1095,7 +1119,7 @@ def track_gather_streams_device(active, m_crop, boxes, slots_per_stream, frame_i
     _check_overlap(out["boxes"], boxes, "out['boxes'] and boxes")
     _check_overlap(out.get("best_q"), best_q, "out['best_q'] and best_q")
     _check_overlap(out.get("reset"), reset, "out['reset'] and reset")
-    p = lambda t: None if t is None else _lib.ptr(t)
+    p = _ptr
     _lib.check(_lib.load().flm_track_gather_streams(
         _lib.stream_ptr(), _lib.ptr(active), a, s, k, p(frame_index), p(dt), _lib.ptr(m_crop), _lib.ptr(boxes), p(best_q),
         p(reset), _lib.ptr(out["slot"]), _lib.ptr(out["m"]), _lib.ptr(out["boxes"]), _lib.ptr(out["frame_index"]),
@@ -1117,85 +1141,10 @@ def track_step_rows_device(lm, m_crop_c, boxes_c, slot, grid_hw, in_hw, frame_hw
     a host number, or a CUDA float64 [N] tensor of one time step per row (a row whose dt is not > 0 and finite loses its
     history and nothing else).  Returns (lm_frame float64 [N,C,2], m_align float32 [N,2,3] or None, status_rows int32
     [N]); lm_frame, m_align, status_rows and lm_raw name where to write."""
-    import torch
-    dt_rows = None
-    if filter is None:
-        if dt is not None or state is not None or lm_raw is not None:
-            raise ValueError("dt, state and lm_raw go with filter")
-    else:
-        if not isinstance(filter, LandmarkFilter):
-            raise ValueError("filter must be None or a LandmarkFilter (got %r)" % (filter,))
-        if isinstance(dt, torch.Tensor):
-            dt_rows, dt = dt, 0.0
-        else:
-            dt = filter.time_step(dt)
-        if (not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or state.dim() != 3
-                or int(state.shape[2]) != 6):
-            raise ValueError("state must be a contiguous CUDA float64 [n_slots,C,6] tensor")
-    lm, ls = _strided_points(lm)
-    n, c = int(lm.shape[0]), int(lm.shape[1])
-    _check_out(slot, torch.int32, (n,), "slot")
-    _check_matrices(m_next, None, "m_next")
-    n_slots = int(m_next.shape[0])
-    if not 1 <= n_slots <= 65535 or n > 65535:
-        raise ValueError("at most 65535 slots and 65535 rows, at least one slot (got %d slots, %d rows)" % (n_slots, n))
-    _check_boxes(boxes_next, n_slots)
-    _check_out(status, torch.int32, (n_slots,), "status")
-    if filter is not None:
-        _check_out(state, torch.float64, (n_slots, c, 6), "state")
-        if dt_rows is not None:
-            _check_out(dt_rows, torch.float64, (n,), "dt")
-        if lm_raw is not None:
-            _check_out(lm_raw, torch.float64, (n, c, 2), "lm_raw")
-    _check_matrices(m_crop_c, n, "m_crop_c")
-    _check_boxes(boxes_c, n)
-    gh, gw = _sizes(grid_hw, "grid_hw")
-    ih, iw = _sizes(in_hw, "in_hw")
-    fh, fw = _sizes(frame_hw, "frame_hw")
-    _check_out(tmpl_crop, torch.float64, (c, 2), "tmpl_crop")
-    if tmpl_align is not None:
-        _check_out(tmpl_align, torch.float64, (c, 2), "tmpl_align")
-    wst = 1
-    if weights is not None:
-        if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64 or tuple(weights.shape) != (n, c)
-                or not weights.is_cuda):
-            raise ValueError("weights must be a CUDA float64 [%d,%d] tensor" % (n, c))
-        wst = _uniform_stride(weights, 1)
-        if wst is None:
-            weights, wst = weights.contiguous(), 1
-    if m_align is not None and tmpl_align is None:
-        raise ValueError("m_align needs tmpl_align")
-    if int(min_points) < 2:
-        raise ValueError("min_points must be 2 or more")
-    if any(v != v for v in (float(min_score), float(min_side), float(max_side))):
-        raise ValueError("min_score, min_side and max_side must not be NaN")
-    dev = lm.device
-    if lm_frame is None:
-        lm_frame = torch.empty((n, c, 2), dtype=torch.float64, device=dev)
-    else:
-        _check_out(lm_frame, torch.float64, (n, c, 2), "lm_frame")
-    if tmpl_align is not None:
-        if m_align is None:
-            m_align = torch.empty((n, 2, 3), dtype=torch.float32, device=dev)
-        else:
-            _check_matrices(m_align, n, "m_align")
-    if status_rows is None:
-        status_rows = torch.empty((n,), dtype=torch.int32, device=dev)
-    else:
-        _check_out(status_rows, torch.int32, (n,), "status_rows")
-    _check_overlap(m_crop_c, m_next, "m_crop_c and m_next")
-    _check_overlap(boxes_c, boxes_next, "boxes_c and boxes_next")
-    _check_overlap(status_rows, status, "status_rows and status")
-    if n and c:
-        opts = _lib.TrackOpts.make(min_points, min_score, min_side, max_side)
-        p = lambda t: None if t is None else _lib.ptr(t)
-        fo = None if filter is None else _lib.TrackFilter.make(filter.min_cutoff, filter.beta, filter.d_cutoff)
-        _lib.check(_lib.load().flm_track_step_rows(
-            _lib.stream_ptr(), _lib.ptr(lm), ls, p(weights), wst, _lib.ptr(m_crop_c), _lib.ptr(boxes_c), n, c, iw / gw,
-            ih / gh, ih, iw, fh, fw, _lib.ptr(tmpl_crop), p(tmpl_align), _lib.C.byref(opts), _lib.ptr(lm_frame), p(m_align),
-            _lib.ptr(m_next), _lib.ptr(boxes_next), _lib.ptr(status), None if fo is None else _lib.C.byref(fo),
-            0.0 if filter is None else dt, p(state), p(lm_raw), _lib.ptr(slot), n_slots, p(dt_rows), _lib.ptr(status_rows)),
-            "flm_track_step_rows")
+    lm_frame, m_align, _, _, _, status_rows = _track_step(
+        lm, m_crop_c, boxes_c, grid_hw, in_hw, frame_hw, tmpl_crop, tmpl_align, weights, min_points, min_score, min_side,
+        max_side, lm_frame, m_align, m_next, boxes_next, status, filter, dt, state, lm_raw, rows=True, slot=slot,
+        status_rows=status_rows, m_what="m_crop_c", k_what="n_slots")
     return lm_frame, m_align, status_rows
 
 
@@ -1210,62 +1159,6 @@ def track_best_update_rows_device(faces, rec, lm, slot, best_q_c, best_q, galler
     face shape, best_frame int64 [n_slots] and best_m, best_lm, best_rec (each or None) are the tracker's own, written in
     place at the slot of a row that is taken; an inert row and a slot no row names write nothing.  best_q_c and best_q
     must be two buffers.  Returns best_q."""
-    import torch
-    if opts is None:
-        opts = BestShot()
-    elif not isinstance(opts, BestShot):
-        raise ValueError("opts must be None or a BestShot (got %r)" % (opts,))
-    if isinstance(frame_id, bool) or int(frame_id) != frame_id or not -2 ** 63 <= int(frame_id) < 2 ** 63:
-        raise ValueError("frame_id must be an integer that fits int64 (got %r)" % (frame_id,))
-    if not isinstance(faces, torch.Tensor) or faces.dim() < 1 or not faces.is_cuda or not faces.is_contiguous():
-        raise ValueError("faces must be a contiguous CUDA tensor of N faces")
-    n = int(faces.shape[0])
-    if (not isinstance(gallery, torch.Tensor) or gallery.dtype != faces.dtype or gallery.dim() != faces.dim()
-            or gallery.shape[1:] != faces.shape[1:] or not gallery.is_cuda or not gallery.is_contiguous()):
-        raise ValueError("gallery must be a contiguous CUDA tensor of the dtype and face shape of faces")
-    n_slots = int(gallery.shape[0])
-    if not 1 <= n_slots <= 65535 or n > 65535:
-        raise ValueError("at most 65535 slots and 65535 rows, at least one slot (got %d slots, %d rows)" % (n_slots, n))
-    _check_out(slot, torch.int32, (n,), "slot")
-    _check_out(rec, torch.int64, (n, QUALITY_REC), "rec")
-    lm, ls = _strided_points(lm)
-    c = int(lm.shape[1])
-    if int(lm.shape[0]) != n:
-        raise ValueError("lm must be a CUDA float64 [%d,C,2] tensor" % n)
-    wst = 1
-    if weights is not None:
-        if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float64 or tuple(weights.shape) != (n, c)
-                or not weights.is_cuda):
-            raise ValueError("weights must be a CUDA float64 [%d,%d] tensor" % (n, c))
-        wst = _uniform_stride(weights, 1)
-        if wst is None:
-            weights, wst = weights.contiguous(), 1
-    for t, dtp, name in ((status_rows, torch.int32, "status_rows"), (reset_c, torch.int32, "reset_c"),
-                         (factor, torch.float64, "factor")):
-        if t is not None:
-            _check_out(t, dtp, (n,), name)
-    if m is not None:
-        _check_matrices(m, n)
-    _check_out(best_q_c, torch.float64, (n,), "best_q_c")
-    _check_out(best_q, torch.float64, (n_slots,), "best_q")
-    _check_overlap(best_q_c, best_q, "best_q_c and best_q")
-    _check_overlap(faces, gallery, "faces and gallery")
-    _check_out(best_frame, torch.int64, (n_slots,), "best_frame")
-    if best_m is not None:
-        if m is None:
-            raise ValueError("best_m needs m")
-        _check_matrices(best_m, n_slots, "best_m")
-    if best_lm is not None:
-        _check_out(best_lm, torch.float64, (n_slots, c, 2), "best_lm")
-    if best_rec is not None:
-        _check_out(best_rec, torch.int64, (n_slots, QUALITY_REC), "best_rec")
-    if n and c:
-        face_bytes = faces.numel() // n * faces.element_size()
-        co = opts.struct()
-        p = lambda t: None if t is None else _lib.ptr(t)
-        _lib.check(_lib.load().flm_track_best_update_rows(
-            _lib.stream_ptr(), _lib.ptr(faces), face_bytes, n, _lib.ptr(rec), p(status_rows), p(reset_c), _lib.ptr(lm), ls,
-            p(weights), wst, c, p(factor), p(m), int(frame_id), _lib.C.byref(co), _lib.ptr(slot), n_slots,
-            _lib.ptr(best_q_c), _lib.ptr(best_q), _lib.ptr(gallery), _lib.ptr(best_frame), p(best_m), p(best_lm),
-            p(best_rec)), "flm_track_best_update_rows")
-    return best_q
+    return _track_best_update(faces, rec, lm, best_q_c, best_q, gallery, best_frame, frame_id, status_rows, reset_c, weights,
+                              factor, m, opts, best_m, best_lm, best_rec, rows=True, slot=slot,
+                              names=("N", "status_rows", "reset_c", "best_q_c", "best_q"))

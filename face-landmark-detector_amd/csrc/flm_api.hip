@@ -1176,7 +1176,7 @@ int flm_landmarks_from_crop(flm_stream_t stream, const double* lm, size_t lm_str
   return launch_landmarks_from_crop(static_cast<hipStream_t>(stream), lm, lm_stride, m, k, c, sx, sy, out);
 }
 
-// The argument checks flm_track_step and flm_track_step_filtered share; *opts is replaced by `defaults` when null.
+// The pointer and option checks of the three step entry points; *opts is replaced by `defaults` when null.
 static int check_track_step_args(const char* who, const double* lm, const float* m_crop, const int32_t* boxes,
                                  const double* tmpl_crop, const double* tmpl_align, const flm_track_opts** opts,
                                  flm_track_opts* defaults, const double* lm_frame, const float* m_align,
@@ -1209,19 +1209,6 @@ static int check_track_step_args(const char* who, const double* lm, const float*
   return FLM_OK;
 }
 
-int flm_track_step(flm_stream_t stream, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
-                   const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h, int in_w,
-                   int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
-                   double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status) {
-  flm_track_opts defaults;
-  if (const int rc = check_track_step_args("flm_track_step", lm, m_crop, boxes, tmpl_crop, tmpl_align, &opts, &defaults,
-                                           lm_frame, m_align, m_next, boxes_next, status))
-    return rc;
-  return launch_track_step(static_cast<hipStream_t>(stream), lm, lm_stride, wt, w_stride, m_crop, boxes, k, c, sx, sy, in_h,
-                           in_w, fh, fw, tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next, status,
-                           nullptr, 0.0, nullptr, nullptr);
-}
-
 void flm_track_filter_init(flm_track_filter* filt) {
   if (!filt) return;
   filt->struct_size = (uint32_t)sizeof(flm_track_filter);
@@ -1231,7 +1218,7 @@ void flm_track_filter_init(flm_track_filter* filt) {
   filt->d_cutoff = 1.0;
 }
 
-// The checks of a flm_track_filter that flm_track_step_filtered and flm_track_step_rows share.
+// The checks of a flm_track_filter.
 static int check_track_filter(const char* who, const flm_track_filter* filt) {
   if (filt->struct_size < sizeof(flm_track_filter)) {
     set_error("%s: flm_track_filter struct_size %u is smaller than this library's %zu (initialise with "
@@ -1257,34 +1244,74 @@ static int check_track_filter(const char* who, const flm_track_filter* filt) {
   return FLM_OK;
 }
 
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+// The three step entry points, stated once.  need_filt: filt must be given (flm_track_step_filtered; flm_track_step has
+// none to give, flm_track_step_rows may or may not).  rows: the call is flm_track_step_rows -- slot and status_rows
+// must be given, dt_rows may replace the scalar dt, and the compact inputs must not overlap what is written at the slots.
+static int track_step(const char* who, bool need_filt, bool rows, flm_stream_t stream, const double* lm, size_t lm_stride,
+                      const double* wt, size_t w_stride, const float* m_crop, const int32_t* boxes, int k, int c, double sx,
+                      double sy, int in_h, int in_w, int fh, int fw, const double* tmpl_crop, const double* tmpl_align,
+                      const flm_track_opts* opts, double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next,
+                      int32_t* status, const flm_track_filter* filt, double dt, double* state, double* lm_raw,
+                      const int32_t* slot, int n_slots, const double* dt_rows, int32_t* status_rows) {
+  flm_track_opts defaults;
+  if (const int rc = check_track_step_args(who, lm, m_crop, boxes, tmpl_crop, tmpl_align, &opts, &defaults, lm_frame, m_align,
+                                           m_next, boxes_next, status))
+    return rc;
+  if (rows && (!slot || !status_rows)) {
+    set_error("%s: null %s", who, !slot ? "slot_dev" : "status_rows_dev");
+    return FLM_ERR_ARG;
+  }
+  if (filt || need_filt) {
+    if (!filt || !state) {  // (lm_raw is optional)
+      set_error("%s: null %s", who, !filt ? "filt" : "state_dev");
+      return FLM_ERR_ARG;
+    }
+    if (const int rc = check_track_filter(who, filt)) return rc;
+    if (!dt_rows && !(dt > 0.0 && std::isfinite(dt))) {
+      set_error("%s: dt=%g, needs a finite dt > 0 (seconds since the previous step)%s", who, dt, rows ? " or dt_dev" : "");
+      return FLM_ERR_ARG;
+    }
+  } else if (state || lm_raw || dt_rows) {
+    set_error("%s: state_dev, lm_raw_dev and dt_dev go with filt", who);
+    return FLM_ERR_ARG;
+  }
+  // the compact inputs must not be the tensors the step writes at the slots (the snapshot exists to keep them apart)
+  if (rows && k >= 1 && k <= 65535 && n_slots >= 1 && n_slots <= 65535 &&
+      (ranges_overlap(m_crop, (size_t)k * 24, m_next, (size_t)n_slots * 24) ||
+       ranges_overlap(boxes, (size_t)k * 16, boxes_next, (size_t)n_slots * 16) ||
+       ranges_overlap(status_rows, (size_t)k * 4, status, (size_t)n_slots * 4))) {
+    set_error("%s: m_crop_c/m_next, boxes_c/boxes_next or status_rows/status overlap (rows are read while slots are "
+              "written: gather a snapshot first)", who);
+    return FLM_ERR_ARG;
+  }
+  return launch_track_step(static_cast<hipStream_t>(stream), who, lm, lm_stride, wt, w_stride, m_crop, boxes, k, c, sx, sy, in_h,
+                           in_w, fh, fw, tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next, status, filt, dt,
+                           state, lm_raw, slot, n_slots, dt_rows, status_rows);
+}
+
+int flm_track_step(flm_stream_t stream, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
+                   const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h, int in_w,
+                   int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
+                   double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status) {
+  return track_step("flm_track_step", false, false, stream, lm, lm_stride, wt, w_stride, m_crop, boxes, k, c, sx, sy, in_h,
+                    in_w, fh, fw, tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next, status, nullptr, 0.0,
+                    nullptr, nullptr, nullptr, 0, nullptr, nullptr);
+}
+
 int flm_track_step_filtered(flm_stream_t stream, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
                             const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h,
                             int in_w, int fh, int fw, const double* tmpl_crop, const double* tmpl_align,
                             const flm_track_opts* opts, double* lm_frame, float* m_align, float* m_next,
                             int32_t* boxes_next, int32_t* status, const flm_track_filter* filt, double dt, double* state,
                             double* lm_raw) {
-  const char* who = "flm_track_step_filtered";
-  flm_track_opts defaults;
-  if (const int rc = check_track_step_args(who, lm, m_crop, boxes, tmpl_crop, tmpl_align, &opts, &defaults, lm_frame,
-                                           m_align, m_next, boxes_next, status))
-    return rc;
-  if (!filt || !state) {  // (lm_raw is optional)
-    set_error("%s: null %s", who, !filt ? "filt" : "state_dev");
-    return FLM_ERR_ARG;
-  }
-  if (const int rc = check_track_filter(who, filt)) return rc;
-  if (!(dt > 0.0 && std::isfinite(dt))) {
-    set_error("%s: dt=%g, needs a finite dt > 0 (seconds since the previous step)", who, dt);
-    return FLM_ERR_ARG;
-  }
-  return launch_track_step(static_cast<hipStream_t>(stream), lm, lm_stride, wt, w_stride, m_crop, boxes, k, c, sx, sy, in_h,
-                           in_w, fh, fw, tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next, status, filt,
-                           dt, state, lm_raw);
-}
-
-static bool track_ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + nb && b0 < a0 + na;
+  return track_step("flm_track_step_filtered", true, false, stream, lm, lm_stride, wt, w_stride, m_crop, boxes, k, c, sx, sy,
+                    in_h, in_w, fh, fw, tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next, status, filt, dt,
+                    state, lm_raw, nullptr, 0, nullptr, nullptr);
 }
 
 int flm_track_step_rows(flm_stream_t stream, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
@@ -1293,41 +1320,9 @@ int flm_track_step_rows(flm_stream_t stream, const double* lm, size_t lm_stride,
                         const flm_track_opts* opts, double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next,
                         int32_t* status, const flm_track_filter* filt, double dt, double* state, double* lm_raw,
                         const int32_t* slot, int n_slots, const double* dt_rows, int32_t* status_rows) {
-  const char* who = "flm_track_step_rows";
-  flm_track_opts defaults;
-  if (const int rc = check_track_step_args(who, lm, m_crop_c, boxes_c, tmpl_crop, tmpl_align, &opts, &defaults, lm_frame,
-                                           m_align, m_next, boxes_next, status))
-    return rc;
-  if (!slot || !status_rows) {
-    set_error("%s: null %s", who, !slot ? "slot_dev" : "status_rows_dev");
-    return FLM_ERR_ARG;
-  }
-  if (filt) {
-    if (!state) {  // (lm_raw is optional)
-      set_error("%s: null state_dev", who);
-      return FLM_ERR_ARG;
-    }
-    if (const int rc = check_track_filter(who, filt)) return rc;
-    if (!dt_rows && !(dt > 0.0 && std::isfinite(dt))) {
-      set_error("%s: dt=%g, needs a finite dt > 0 (seconds since the previous step) or dt_dev", who, dt);
-      return FLM_ERR_ARG;
-    }
-  } else if (state || lm_raw || dt_rows) {
-    set_error("%s: state_dev, lm_raw_dev and dt_dev go with filt", who);
-    return FLM_ERR_ARG;
-  }
-  // the compact inputs must not be the tensors the step writes at the slots (the snapshot exists to keep them apart)
-  if (n >= 1 && n <= 65535 && n_slots >= 1 && n_slots <= 65535 &&
-      (track_ranges_overlap(m_crop_c, (size_t)n * 24, m_next, (size_t)n_slots * 24) ||
-       track_ranges_overlap(boxes_c, (size_t)n * 16, boxes_next, (size_t)n_slots * 16) ||
-       track_ranges_overlap(status_rows, (size_t)n * 4, status, (size_t)n_slots * 4))) {
-    set_error("%s: m_crop_c/m_next, boxes_c/boxes_next or status_rows/status overlap (rows are read while slots are "
-              "written: gather a snapshot first)", who);
-    return FLM_ERR_ARG;
-  }
-  return launch_track_step_rows(static_cast<hipStream_t>(stream), lm, lm_stride, wt, w_stride, m_crop_c, boxes_c, n, c, sx,
-                                sy, in_h, in_w, fh, fw, tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next,
-                                status, filt, dt, state, lm_raw, slot, n_slots, dt_rows, status_rows);
+  return track_step("flm_track_step_rows", false, true, stream, lm, lm_stride, wt, w_stride, m_crop_c, boxes_c, n, c, sx, sy,
+                    in_h, in_w, fh, fw, tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next, status, filt, dt,
+                    state, lm_raw, slot, n_slots, dt_rows, status_rows);
 }
 
 int flm_track_gather_streams(flm_stream_t stream, const int32_t* active, int a, int s, int k,
@@ -1507,11 +1502,6 @@ void flm_best_opts_init(flm_best_opts* opts) {
   opts->min_exposed = 0.5;
 }
 
-static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
 // The option and size checks flm_track_best_update and flm_track_best_update_rows share; *popts is replaced by `defaults`
 // when null.  kname: what the call names its number of faces.
 static int check_best_args(const char* who, const flm_best_opts** popts, flm_best_opts* defaults, const char* kname, int k,
@@ -1580,8 +1570,8 @@ int flm_track_best_update(flm_stream_t stream, const void* faces, size_t face_by
     return FLM_ERR_ARG;
   }
   return launch_track_best_update(static_cast<hipStream_t>(stream), faces, face_bytes, k, rec, status, reset, lm, lm_stride,
-                                  wt, w_stride, c, factor, m, frame_id, opts, best_q_in, best_q_out, gallery, best_frame,
-                                  best_m, best_lm, best_rec);
+                                  wt, w_stride, c, factor, m, frame_id, opts, nullptr, 0, best_q_in, best_q_out, gallery,
+                                  best_frame, best_m, best_lm, best_rec);
 }
 
 int flm_track_best_update_rows(flm_stream_t stream, const void* faces, size_t face_bytes, int n, const int64_t* rec,
@@ -1613,9 +1603,9 @@ int flm_track_best_update_rows(flm_stream_t stream, const void* faces, size_t fa
     set_error("%s: faces_dev and gallery_dev overlap", who);
     return FLM_ERR_ARG;
   }
-  return launch_track_best_update_rows(static_cast<hipStream_t>(stream), faces, face_bytes, n, rec, status_rows, reset_c, lm,
-                                       lm_stride, wt, w_stride, c, factor, m, frame_id, opts, slot, n_slots, best_q_c, best_q,
-                                       gallery, best_frame, best_m, best_lm, best_rec);
+  return launch_track_best_update(static_cast<hipStream_t>(stream), faces, face_bytes, n, rec, status_rows, reset_c, lm,
+                                  lm_stride, wt, w_stride, c, factor, m, frame_id, opts, slot, n_slots, best_q_c, best_q,
+                                  gallery, best_frame, best_m, best_lm, best_rec);
 }
 
 }  // extern "C"

@@ -281,17 +281,14 @@ int launch_track_seed(hipStream_t s, const int32_t* boxes, int k, int in_h, int 
                       int32_t* status);
 int launch_landmarks_from_crop(hipStream_t s, const double* lm, size_t lm_stride, const float* m, int k, int c, double sx,
                                double sy, double* out);
-int launch_track_step(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
+// who: the entry point, for the messages
+int launch_track_step(hipStream_t s, const char* who, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
                       const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h, int in_w,
                       int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
                       double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status,
-                      const flm_track_filter* filt /*null = flm_track_step*/, double dt, double* state, double* lm_raw);
-int launch_track_step_rows(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
-                           const float* m_crop, const int32_t* boxes, int n, int c, double sx, double sy, int in_h, int in_w,
-                           int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
-                           double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status,
-                           const flm_track_filter* filt /*null = unfiltered*/, double dt, double* state, double* lm_raw,
-                           const int32_t* slot, int n_slots, const double* dt_rows, int32_t* status_rows);
+                      const flm_track_filter* filt /*null = unfiltered*/, double dt, double* state, double* lm_raw,
+                      const int32_t* slot /*null = the dense step: row == slot, the next three unused*/, int n_slots,
+                      const double* dt_rows, int32_t* status_rows);
 int launch_track_gather_streams(hipStream_t s, const int32_t* active, int a, int n_streams, int k,
                                 const int32_t* frame_idx_stream, const double* dt_stream, const float* m_crop,
                                 const int32_t* boxes, const double* best_q, int32_t* reset, int32_t* slot_c, float* m_c,
@@ -312,14 +309,10 @@ int launch_face_quality(hipStream_t s, const void* faces, int k, int h, int w, c
 int launch_track_best_update(hipStream_t s, const void* faces, size_t face_bytes, int k, const int64_t* rec,
                              const int32_t* status, const int32_t* reset, const double* lm, size_t lm_stride,
                              const double* wt, size_t w_stride, int c, const double* factor, const float* m,
-                             int64_t frame_id, const flm_best_opts* opts, const double* best_q_in, double* best_q_out,
-                             void* gallery, int64_t* best_frame, float* best_m, double* best_lm, int64_t* best_rec);
-int launch_track_best_update_rows(hipStream_t s, const void* faces, size_t face_bytes, int n, const int64_t* rec,
-                                  const int32_t* status_rows, const int32_t* reset_c, const double* lm, size_t lm_stride,
-                                  const double* wt, size_t w_stride, int c, const double* factor, const float* m,
-                                  int64_t frame_id, const flm_best_opts* opts, const int32_t* slot, int n_slots,
-                                  const double* best_q_c, double* best_q, void* gallery, int64_t* best_frame, float* best_m,
-                                  double* best_lm, int64_t* best_rec);
+                             int64_t frame_id, const flm_best_opts* opts,
+                             const int32_t* slot /*null = flm_track_best_update: k slots, row == slot*/, int n_slots,
+                             const double* best_q_in, double* best_q_out, void* gallery, int64_t* best_frame, float* best_m,
+                             double* best_lm, int64_t* best_rec);
 
 // Bijective XCD-aware remap of a 1-D grid: blocks that the dispatcher deals to the same XCD
 // (b % 8) receive consecutive logical ids, so neighbours in logical order share an L2.

@@ -328,11 +328,12 @@ __global__ __launch_bounds__(kBestThreads) void track_best_rows_kernel(const Bes
 
 // Pointers, options and overlaps are checked by the caller in flm_api.hip.
 // slot == null: flm_track_best_update (k slots, row == slot); else flm_track_best_update_rows (k rows).
-static int launch_best(hipStream_t s, const void* faces, size_t face_bytes, int k, const int64_t* rec, const int32_t* status,
-                       const int32_t* reset, const double* lm, size_t lm_stride, const double* wt, size_t w_stride, int c,
-                       const double* factor, const float* m, int64_t frame_id, const flm_best_opts* opts,
-                       const int32_t* slot, int n_slots, const double* best_q_in, double* best_q_out, void* gallery,
-                       int64_t* best_frame, float* best_m, double* best_lm, int64_t* best_rec) {
+int launch_track_best_update(hipStream_t s, const void* faces, size_t face_bytes, int k, const int64_t* rec,
+                             const int32_t* status, const int32_t* reset, const double* lm, size_t lm_stride,
+                             const double* wt, size_t w_stride, int c, const double* factor, const float* m,
+                             int64_t frame_id, const flm_best_opts* opts, const int32_t* slot, int n_slots,
+                             const double* best_q_in, double* best_q_out, void* gallery, int64_t* best_frame, float* best_m,
+                             double* best_lm, int64_t* best_rec) {
   BestArgs g;
   g.faces = static_cast<const unsigned char*>(faces);
   g.face_bytes = face_bytes;
@@ -353,25 +354,6 @@ static int launch_best(hipStream_t s, const void* faces, size_t face_bytes, int 
     FLM_LAUNCH_CHECK("track_best_kernel");
   }
   return FLM_OK;
-}
-
-int launch_track_best_update(hipStream_t s, const void* faces, size_t face_bytes, int k, const int64_t* rec,
-                             const int32_t* status, const int32_t* reset, const double* lm, size_t lm_stride,
-                             const double* wt, size_t w_stride, int c, const double* factor, const float* m,
-                             int64_t frame_id, const flm_best_opts* opts, const double* best_q_in, double* best_q_out,
-                             void* gallery, int64_t* best_frame, float* best_m, double* best_lm, int64_t* best_rec) {
-  return launch_best(s, faces, face_bytes, k, rec, status, reset, lm, lm_stride, wt, w_stride, c, factor, m, frame_id, opts,
-                     nullptr, 0, best_q_in, best_q_out, gallery, best_frame, best_m, best_lm, best_rec);
-}
-
-int launch_track_best_update_rows(hipStream_t s, const void* faces, size_t face_bytes, int n, const int64_t* rec,
-                                  const int32_t* status_rows, const int32_t* reset_c, const double* lm, size_t lm_stride,
-                                  const double* wt, size_t w_stride, int c, const double* factor, const float* m,
-                                  int64_t frame_id, const flm_best_opts* opts, const int32_t* slot, int n_slots,
-                                  const double* best_q_c, double* best_q, void* gallery, int64_t* best_frame, float* best_m,
-                                  double* best_lm, int64_t* best_rec) {
-  return launch_best(s, faces, face_bytes, n, rec, status_rows, reset_c, lm, lm_stride, wt, w_stride, c, factor, m, frame_id,
-                     opts, slot, n_slots, best_q_c, best_q, gallery, best_frame, best_m, best_lm, best_rec);
 }
 
 }  // namespace flm

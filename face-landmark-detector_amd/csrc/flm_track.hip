@@ -410,13 +410,25 @@ int launch_landmarks_from_crop(hipStream_t s, const double* lm, size_t lm_stride
   return FLM_OK;
 }
 
-// The struct the two step launchers fill alike.
-static TrackStepArgs make_track_step_args(const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
-                                          const float* m_crop, const int32_t* boxes, int c, double sx, double sy, int in_h,
-                                          int in_w, int fh, int fw, const double* tmpl_crop, const double* tmpl_align,
-                                          const flm_track_opts* opts, double* lm_frame, float* m_align, float* m_next,
-                                          int32_t* boxes_next, int32_t* status, const flm_track_filter* filt, double dt,
-                                          double* state, double* lm_raw) {
+// slot == null: flm_track_step / flm_track_step_filtered (k slots, row == slot); else flm_track_step_rows (k rows).
+int launch_track_step(hipStream_t s, const char* who, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
+                      const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h, int in_w,
+                      int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
+                      double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status,
+                      const flm_track_filter* filt, double dt, double* state, double* lm_raw, const int32_t* slot,
+                      int n_slots, const double* dt_rows, int32_t* status_rows) {
+  if (slot) {
+    if (k < 1 || k > 65535) {
+      set_error("%s: n=%d, needs 1 <= n <= 65535", who, k);
+      return FLM_ERR_SHAPE;
+    }
+    if (n_slots < 1 || n_slots > 65535) {
+      set_error("%s: n_slots=%d, needs 1 <= n_slots <= 65535", who, n_slots);
+      return FLM_ERR_SHAPE;
+    }
+  }
+  if (const int rc = check_track_sizes(who, k, c, in_h, in_w, fh, fw)) return rc;
+  if (const int rc = check_track_points(who, lm_stride, w_stride, sx, sy)) return rc;
   TrackStepArgs g;
   g.lm = lm; g.lm_stride = lm_stride; g.wt = wt; g.w_stride = w_stride;
   g.m_crop = m_crop; g.boxes = boxes; g.c = c; g.sx = sx; g.sy = sy;
@@ -430,55 +442,21 @@ static TrackStepArgs make_track_step_args(const double* lm, size_t lm_stride, co
     g.min_cutoff = filt->min_cutoff; g.beta = filt->beta; g.d_cutoff = filt->d_cutoff; g.dt = dt;
     g.state = state; g.lm_raw = lm_raw;
   }
-  return g;
-}
-
-int launch_track_step(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
-                      const float* m_crop, const int32_t* boxes, int k, int c, double sx, double sy, int in_h, int in_w,
-                      int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
-                      double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status,
-                      const flm_track_filter* filt, double dt, double* state, double* lm_raw) {
-  const char* who = filt ? "flm_track_step_filtered" : "flm_track_step";
-  if (const int rc = check_track_sizes(who, k, c, in_h, in_w, fh, fw)) return rc;
-  if (const int rc = check_track_points(who, lm_stride, w_stride, sx, sy)) return rc;
-  const TrackStepArgs g = make_track_step_args(lm, lm_stride, wt, w_stride, m_crop, boxes, c, sx, sy, in_h, in_w, fh, fw,
-                                               tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next, status,
-                                               filt, dt, state, lm_raw);
-  if (filt) {
-    track_step_kernel<true><<<k, 64, sizeof(double) * 7 * c, s>>>(g);
-  } else {
-    track_step_kernel<false><<<k, 64, sizeof(double) * 7 * c, s>>>(g);   // (at most 56 KiB: c <= 1024)
+  const size_t lds = sizeof(double) * 7 * c;   // (at most 56 KiB: c <= 1024)
+  if (!slot) {
+    if (filt)
+      track_step_kernel<true><<<k, 64, lds, s>>>(g);
+    else
+      track_step_kernel<false><<<k, 64, lds, s>>>(g);
+    FLM_LAUNCH_CHECK("track_step_kernel");
+    return FLM_OK;
   }
-  FLM_LAUNCH_CHECK("track_step_kernel");
-  return FLM_OK;
-}
-
-int launch_track_step_rows(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride,
-                           const float* m_crop, const int32_t* boxes, int n, int c, double sx, double sy, int in_h, int in_w,
-                           int fh, int fw, const double* tmpl_crop, const double* tmpl_align, const flm_track_opts* opts,
-                           double* lm_frame, float* m_align, float* m_next, int32_t* boxes_next, int32_t* status,
-                           const flm_track_filter* filt, double dt, double* state, double* lm_raw, const int32_t* slot,
-                           int n_slots, const double* dt_rows, int32_t* status_rows) {
-  const char* who = "flm_track_step_rows";
-  if (n < 1 || n > 65535) {
-    set_error("%s: n=%d, needs 1 <= n <= 65535", who, n);
-    return FLM_ERR_SHAPE;
-  }
-  if (n_slots < 1 || n_slots > 65535) {
-    set_error("%s: n_slots=%d, needs 1 <= n_slots <= 65535", who, n_slots);
-    return FLM_ERR_SHAPE;
-  }
-  if (const int rc = check_track_sizes(who, n, c, in_h, in_w, fh, fw)) return rc;
-  if (const int rc = check_track_points(who, lm_stride, w_stride, sx, sy)) return rc;
-  const TrackStepArgs g = make_track_step_args(lm, lm_stride, wt, w_stride, m_crop, boxes, c, sx, sy, in_h, in_w, fh, fw,
-                                               tmpl_crop, tmpl_align, opts, lm_frame, m_align, m_next, boxes_next, status,
-                                               filt, dt, state, lm_raw);
   TrackRowArgs r;
   r.slot = slot; r.n_slots = n_slots; r.dt = filt ? dt_rows : nullptr; r.status_rows = status_rows;
   if (filt)
-    track_step_rows_kernel<true><<<n, 64, sizeof(double) * 7 * c, s>>>(g, r);
+    track_step_rows_kernel<true><<<k, 64, lds, s>>>(g, r);
   else
-    track_step_rows_kernel<false><<<n, 64, sizeof(double) * 7 * c, s>>>(g, r);
+    track_step_rows_kernel<false><<<k, 64, lds, s>>>(g, r);
   FLM_LAUNCH_CHECK("track_step_rows_kernel");
   return FLM_OK;
 }

@@ -716,6 +716,31 @@ class FaceTracker:
         if self.best_shot is not None:
             self._best_reset.index_fill_(0, idx, 1)
 
+    @staticmethod
+    def _host_boxes(boxes, what):
+        """Detector boxes from the host as an integer [D,4] array whose values fit int32; ValueError(what) otherwise."""
+        arr = np.asarray(boxes)
+        if arr.ndim != 2 or arr.shape[1] != 4 or arr.dtype.kind not in "iu":
+            raise ValueError(what)
+        if arr.size and (arr.min() < -2 ** 31 or arr.max() >= 2 ** 31):
+            raise ValueError("a box coordinate does not fit int32")
+        return arr
+
+    def _was_empty(self):
+        """For a tracker with best_shot, the slots that hold no track now: the association's own test, on the device."""
+        if self.best_shot is None:
+            return None
+        fh, fw = self.frame_hw
+        b = self.boxes
+        return ((b[:, 2].clamp(0, fw) - b[:, 0].clamp(0, fw) <= 0)
+                | (b[:, 3].clamp(0, fh) - b[:, 1].clamp(0, fh) <= 0))
+
+    def _mark_births(self, was_empty, slot_det):
+        """A birth forgets the slot's best with the next step; a restart is the same face and keeps it, and a skipped
+        stream has slot_det == -1 and resets nothing."""
+        if self.best_shot is not None:
+            self._best_reset.masked_fill_(was_empty & (slot_det >= 0), 1)
+
     def update(self, detections, n=None):
         """The boxes of a detector against the tracks, on the device (alignment.track_associate_device with the
         tracker's `associate`): a detection that overlaps a live track confirms it (and restarts it where the two have
@@ -741,12 +766,8 @@ class FaceTracker:
         if isinstance(detections, torch.Tensor):
             det = detections
         else:
-            arr = np.asarray(detections)
-            if arr.ndim != 2 or arr.shape[1] != 4 or arr.dtype.kind not in "iu":
-                raise ValueError("update takes a CUDA int32 [D,4] tensor or a list of integer (x0,y0,x1,y1) boxes")
-            if arr.size and (arr.min() < -2 ** 31 or arr.max() >= 2 ** 31):
-                raise ValueError("a box coordinate does not fit int32")
-            det = arr.astype(np.int32)
+            det = self._host_boxes(detections, "update takes a CUDA int32 [D,4] tensor or a list of integer (x0,y0,x1,y1) "
+                                               "boxes").astype(np.int32)
         if int(det.shape[0]) > alignment.ASSOC_MAX:
             raise ValueError("update takes at most %d detections (got %d)" % (alignment.ASSOC_MAX, int(det.shape[0])))
         if int(det.shape[0]) < 1:
@@ -756,16 +777,11 @@ class FaceTracker:
         self._state()
         if not isinstance(det, torch.Tensor):
             det = torch.from_numpy(np.ascontiguousarray(det)).to(self.boxes.device)
-        if self.best_shot is not None:  # the slots that hold no track now: the association's own test, on the device
-            fh, fw = self.frame_hw
-            b = self.boxes
-            was_empty = ((b[:, 2].clamp(0, fw) - b[:, 0].clamp(0, fw) <= 0)
-                         | (b[:, 3].clamp(0, fh) - b[:, 1].clamp(0, fh) <= 0))
+        was_empty = self._was_empty()
         out = alignment.track_associate_device(det, self.m_crop, self.boxes, self.status, self.misses,
                                                (self.model.input_height, self.model.input_width), self.frame_hw,
                                                n_det=n, state=self.filter_state, assoc=self.associate)
-        if self.best_shot is not None:  # a birth forgets the slot's best; a restart is the same face and keeps it
-            self._best_reset.masked_fill_(was_empty & (out[1] >= 0), 1)
+        self._mark_births(was_empty, out[1])
         return out
 
     def _update_streams(self, detections, n):
@@ -786,19 +802,9 @@ class FaceTracker:
             rows = list(detections)
             if len(rows) != s:
                 raise ValueError("update takes one entry per stream (%d), got %d" % (s, len(rows)))
-            arrs = []
-            for r in rows:
-                if r is None:
-                    arrs.append(None)
-                    continue
-                a = np.asarray(r)
-                if a.size == 0:
-                    a = np.zeros((0, 4), np.int64)
-                if a.ndim != 2 or a.shape[1] != 4 or a.dtype.kind not in "iu":
-                    raise ValueError("every stream's entry is None or a list of integer (x0,y0,x1,y1) boxes")
-                if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
-                    raise ValueError("a box coordinate does not fit int32")
-                arrs.append(a)
+            arrs = [None if r is None else
+                    self._host_boxes(r if np.size(r) else np.zeros((0, 4), np.int64),
+                                     "every stream's entry is None or a list of integer (x0,y0,x1,y1) boxes") for r in rows]
             d = max([1] + [len(a) for a in arrs if a is not None])
         if d > alignment.ASSOC_MAX:
             raise ValueError("update takes at most %d detections per stream (got %d)" % (alignment.ASSOC_MAX, d))
@@ -814,17 +820,42 @@ class FaceTracker:
                     pad[i, :len(a)] = a
             both = torch.from_numpy(flat).to(self.boxes.device)
             det, n = both[:s * d * 4].view(s, d, 4), both[s * d * 4:]
-        if self.best_shot is not None:  # the slots that hold no track now: the association's own test, on the device
-            fh, fw = self.frame_hw
-            b = self.boxes
-            was_empty = ((b[:, 2].clamp(0, fw) - b[:, 0].clamp(0, fw) <= 0)
-                         | (b[:, 3].clamp(0, fh) - b[:, 1].clamp(0, fh) <= 0))
+        was_empty = self._was_empty()
         out = alignment.track_associate_streams_device(det, self.m_crop, self.boxes, self.status, self.misses, k,
                                                        (self.model.input_height, self.model.input_width), self.frame_hw,
                                                        n_det=n, state=self.filter_state, assoc=self.associate)
-        if self.best_shot is not None:  # (a skipped stream has slot_det == -1 and resets nothing)
-            self._best_reset.masked_fill_(was_empty & (out[1] >= 0), 1)
+        self._mark_births(was_empty, out[1])
         return out
+
+    def _stream_frame_index(self, frame_index, nf, named):
+        """A per-stream `frame_index`, parsed: None for a contiguous CUDA int32 [streams] tensor, which is used where it
+        lies, or the host list of `streams` ring slots, checked against the ring.  named: the streams whose host entries
+        count -- the other entries are ignored and come back as 0 -- or None where the host cannot tell: every entry
+        counts then, None standing for ring slot 0.  A tracker of one stream also takes a bare integer."""
+        import torch
+        s = self.streams
+        if isinstance(frame_index, torch.Tensor):
+            if (frame_index.dtype != torch.int32 or not frame_index.is_cuda or not frame_index.is_contiguous()
+                    or tuple(frame_index.shape) != (s,)):
+                raise ValueError("frame_index must be a sequence of %d ring slots or a contiguous CUDA int32 [%d] tensor"
+                                 % (s, s))
+            return None
+        if s == 1 and not isinstance(frame_index, (list, tuple, np.ndarray)):
+            frame_index = [frame_index]
+        try:
+            idx = list(frame_index)
+        except TypeError:
+            idx = None
+        if idx is None or len(idx) != s:
+            raise ValueError("frame_index must be a sequence of %d ring slots or a contiguous CUDA int32 [%d] tensor"
+                             % (s, s))
+        if named is None:
+            idx, named = [0 if v is None else v for v in idx], range(s)
+        keep = set(named)
+        if any(idx[i] is None or isinstance(idx[i], bool) or int(idx[i]) != idx[i] or not 0 <= int(idx[i]) < nf
+               for i in named):
+            raise ValueError("frame_index must name ring slots in [0, %d)" % nf)
+        return [int(v) if i in keep else 0 for i, v in enumerate(idx)]
 
     def _stream_frames(self, frame_index, nf):
         """frame_index of a tracker of several streams -> `frame_slots`, the ring slot of every global slot: a host
@@ -832,26 +863,57 @@ class FaceTracker:
         expansion over the slots of a stream is a device copy."""
         import torch
         s, k = self.streams, self.slots_per_stream
-        if isinstance(frame_index, torch.Tensor):
-            if (frame_index.dtype != torch.int32 or not frame_index.is_cuda or not frame_index.is_contiguous()
-                    or tuple(frame_index.shape) != (s,)):
-                raise ValueError("frame_index must be a sequence of %d ring slots or a contiguous CUDA int32 [%d] tensor"
-                                 % (s, s))
-            idx = None
-        else:
-            try:
-                idx = list(frame_index)
-            except TypeError:
-                idx = None
-            if idx is None or len(idx) != s:
-                raise ValueError("frame_index must be a sequence of %d ring slots or a contiguous CUDA int32 [%d] tensor"
-                                 % (s, s))
-            if any(isinstance(v, bool) or int(v) != v or not 0 <= int(v) < nf for v in idx):
-                raise ValueError("frame_index must name ring slots in [0, %d)" % nf)
+        idx = self._stream_frame_index(frame_index, nf, range(s))
         self._state()
         if idx is not None:
-            frame_index = torch.tensor([int(v) for v in idx], dtype=torch.int32).to(self.boxes.device)
+            frame_index = torch.tensor(idx, dtype=torch.int32).to(self.boxes.device)
         self.frame_slots.view(s, k).copy_(frame_index.view(s, 1).expand(s, k))
+
+    def _step_prologue(self, ring, dt, frame_id, host_dt=False):
+        """What `step` and `step_active` check before anything else: frame_id (None: the steps made so far), "dt goes
+        with smooth" -- and, for host_dt, dt as the one host number `step` takes -- and the ring's geometry against
+        frame_hw.  Returns (frame_id, dt, the slots of the ring)."""
+        if self.best_shot is None and frame_id is not None:
+            raise ValueError("frame_id goes with best_shot")
+        frame_id = self._steps if frame_id is None else alignment._frame_id(frame_id)
+        if self.smooth is None and dt is not None:
+            raise ValueError("dt goes with smooth")
+        if host_dt:
+            dt = None if self.smooth is None else self.smooth.time_step(dt)
+        nf, rh, rw, _ = (self.frame_format or alignment.FrameFormat.bgr()).ring(ring)
+        if (rh, rw) != self.frame_hw:
+            raise ValueError("the ring holds %dx%d frames, the tracker was made for %dx%d" % ((rh, rw) + self.frame_hw))
+        return frame_id, dt, nf
+
+    def _sequence(self, ring, src, step, best_update, workspace, frame_id, quality_out=None):
+        """The step sequence, stated once for `step` and `step_active`: the uint8 crop warp -> model.forward_device ->
+        (lm, wd) -> the step call -> the aligned warp -> with best_shot, the quality call and the best update.
+        src: where the matrices ("m"), boxes and ring slots ("frame_index") of the faces are read -- the state itself or
+        the snapshot; step, best_update: the caller's wrapper of the two, with what only that wrapper takes bound;
+        workspace(batch, mode): the forward workspace, or None for the model's cached ones.  Returns (aligned, m_align,
+        lm_frame, status)."""
+        model = self.model
+        ih, iw = model.input_height, model.input_width
+        where = dict(frame_index_dev=src["frame_index"], boxes_dev=src["boxes"], src=self.frame_format)
+        crops = alignment.warp_frames_device(ring, src["m"], ih, iw, samples=self.crop_samples, fmt=self._crop_format, **where)
+        out = "landmarks" if self.weights is None else "landmark_stats"
+        res = model.forward_device(crops, out, n_points=self.n_points, thresh=self.thresh,
+                                   workspace=workspace(int(crops.shape[0]), out))
+        lm, wd = (res, None) if self.weights is None else (res[..., :2], res[..., 2])
+        filt = {} if self.smooth is None else dict(filter=self.smooth, state=self.filter_state)
+        stepped = step(lm, src["m"], src["boxes"], grid_hw=(model.output_height, model.output_width), in_hw=(ih, iw),
+                       frame_hw=self.frame_hw, tmpl_crop=self.crop_template, tmpl_align=self.template, weights=wd,
+                       **self.limits, **filt)
+        lm_frame, m_align, status = stepped[0], stepped[1], stepped[-1]
+        aligned = alignment.warp_frames_device(ring, m_align, self.out_size[0], self.out_size[1], samples=self.samples,
+                                               fmt=self.aligned_format, **where)
+        self._steps += 1
+        if self.best_shot is not None:
+            rec = alignment.face_quality_device(aligned, self.aligned_format, self.best_shot.quality, out=quality_out)
+            best_update(aligned, rec, lm_frame, status, gallery=self.gallery, best_frame=self.best_frame, frame_id=frame_id,
+                        weights=wd, m=m_align, opts=self.best_shot, best_m=self.best_M, best_lm=self.best_landmarks,
+                        best_rec=self.best_rec)
+        return aligned, m_align, lm_frame, status
 
     def step(self, ring, frame_index, dt=None, frame_id=None):
         """One frame for every slot: `ring` is the frame ring (`frame_format` says how it holds its pixels),
@@ -868,22 +930,8 @@ class FaceTracker:
         on.  `dt`, for a tracker that smooths: the seconds since the previous step, a host number (None: 1/fps of the
         filter).  `frame_id`, for a tracker with `best_shot`: the host integer `best_frame` records for a face taken
         in this step (None: the number of steps this tracker has made before this one)."""
-        fh, fw = self.frame_hw
-        if self.best_shot is None and frame_id is not None:
-            raise ValueError("frame_id goes with best_shot")
-        if frame_id is None:
-            frame_id = self._steps
-        elif isinstance(frame_id, bool) or int(frame_id) != frame_id or not -2 ** 63 <= int(frame_id) < 2 ** 63:
-            raise ValueError("frame_id must be an integer that fits int64 (got %r)" % (frame_id,))
-        if self.smooth is None and dt is not None:
-            raise ValueError("dt goes with smooth")
-        dt = None if self.smooth is None else self.smooth.time_step(dt)
-        if self.frame_format is not None:
-            nf, rh, rw, _ = self.frame_format.ring(ring)
-        else:
-            nf, rh, rw, _ = alignment.FrameFormat.bgr().ring(ring)
-        if (rh, rw) != (fh, fw):
-            raise ValueError("the ring holds %dx%d frames, the tracker was made for %dx%d" % (rh, rw, fh, fw))
+        import functools
+        frame_id, dt, nf = self._step_prologue(ring, dt, frame_id, host_dt=True)
         if self.streams > 1:
             self._stream_frames(frame_index, nf)
         else:
@@ -891,37 +939,23 @@ class FaceTracker:
             if not 0 <= frame_index < nf:
                 raise ValueError("frame_index must name a ring slot in [0, %d)" % nf)
         self._state()
-        filt = {} if self.smooth is None else dict(filter=self.smooth, dt=dt, state=self.filter_state)
-        model = self.model
-        ih, iw = model.input_height, model.input_width
         if self.streams == 1:
             self.frame_slots.fill_(frame_index)
-        crops = alignment.warp_frames_device(ring, self.m_crop, ih, iw, frame_index_dev=self.frame_slots,
-                                             boxes_dev=self.boxes, samples=self.crop_samples, fmt=self._crop_format,
-                                             src=self.frame_format)
-        if self.weights is None:
-            lm, wd = model.forward_device(crops, "landmarks", n_points=self.n_points, thresh=self.thresh), None
-        else:
-            rec = model.forward_device(crops, "landmark_stats", n_points=self.n_points, thresh=self.thresh)
-            lm, wd = rec[..., :2], rec[..., 2]
-        lm_frame, m_align, _, _, _ = alignment.track_step_device(
-            lm, self.m_crop, self.boxes, (model.output_height, model.output_width), (ih, iw), (fh, fw), self.crop_template,
-            self.template, weights=wd, m_next=self.m_crop, boxes_next=self._boxes_spare, status=self.status, **self.limits,
-            **filt)
-        aligned = alignment.warp_frames_device(ring, m_align, self.out_size[0], self.out_size[1],
-                                               frame_index_dev=self.frame_slots, boxes_dev=self.boxes, samples=self.samples,
-                                               fmt=self.aligned_format, src=self.frame_format)
+
+        def best_update(faces, rec, lm, status, **kw):
+            alignment.track_best_update_device(faces, rec, lm, self.best_q, self._best_q_spare, status=status,
+                                               reset=self._best_reset, **kw)
+
+        res = self._sequence(
+            ring, dict(m=self.m_crop, boxes=self.boxes, frame_index=self.frame_slots),
+            functools.partial(alignment.track_step_device, m_next=self.m_crop, boxes_next=self._boxes_spare,
+                              status=self.status, dt=dt),
+            best_update, lambda n, out: None, frame_id, quality_out=self._quality_rec if self.best_shot is not None else None)
         self.boxes, self._boxes_spare = self._boxes_spare, self.boxes
-        self._steps += 1
         if self.best_shot is not None:
-            alignment.face_quality_device(aligned, self.aligned_format, self.best_shot.quality, out=self._quality_rec)
-            alignment.track_best_update_device(
-                aligned, self._quality_rec, lm_frame, self.best_q, self._best_q_spare, self.gallery, self.best_frame,
-                int(frame_id), status=self.status, reset=self._best_reset, weights=wd, m=m_align, opts=self.best_shot,
-                best_m=self.best_M, best_lm=self.best_landmarks, best_rec=self.best_rec)
             self.best_q, self._best_q_spare = self._best_q_spare, self.best_q
             self._best_reset.zero_()
-        return aligned, m_align, lm_frame, self.status
+        return res
 
     def _active_workspace(self, n, out):
         """The forward workspace `step_active` passes for a batch of n faces, or None (the model's cached path).  The
@@ -966,24 +1000,11 @@ class FaceTracker:
         Returns CUDA tensors over the N = A*slots_per_stream rows, row a*slots_per_stream + j being slot
         active[a]*slots_per_stream + j: (aligned [N,...], M float32 [N,2,3], landmarks float64 [N,C,2], status int32 [N],
         slots int32 [N])."""
+        import functools
         import math
         import torch
-        fh, fw = self.frame_hw
         s, k = self.streams, self.slots_per_stream
-        if self.best_shot is None and frame_id is not None:
-            raise ValueError("frame_id goes with best_shot")
-        if frame_id is None:
-            frame_id = self._steps
-        elif isinstance(frame_id, bool) or int(frame_id) != frame_id or not -2 ** 63 <= int(frame_id) < 2 ** 63:
-            raise ValueError("frame_id must be an integer that fits int64 (got %r)" % (frame_id,))
-        if self.smooth is None and dt is not None:
-            raise ValueError("dt goes with smooth")
-        if self.frame_format is not None:
-            nf, rh, rw, _ = self.frame_format.ring(ring)
-        else:
-            nf, rh, rw, _ = alignment.FrameFormat.bgr().ring(ring)
-        if (rh, rw) != (fh, fw):
-            raise ValueError("the ring holds %dx%d frames, the tracker was made for %dx%d" % (rh, rw, fh, fw))
+        frame_id, _, nf = self._step_prologue(ring, dt, frame_id)
         # ---- active
         act_host = None
         if isinstance(active, torch.Tensor):
@@ -1005,29 +1026,7 @@ class FaceTracker:
             a = len(act_host)
         named = range(s) if act_host is None else act_host    # the streams whose host entries count
         # ---- frame_index
-        fi_host = None
-        if isinstance(frame_index, torch.Tensor):
-            if (frame_index.dtype != torch.int32 or not frame_index.is_cuda or not frame_index.is_contiguous()
-                    or tuple(frame_index.shape) != (s,)):
-                raise ValueError("frame_index must be a sequence of %d ring slots or a contiguous CUDA int32 [%d] tensor"
-                                 % (s, s))
-        else:
-            if s == 1 and not isinstance(frame_index, (list, tuple, np.ndarray)):
-                frame_index = [frame_index]
-            try:
-                fi_host = list(frame_index)
-            except TypeError:
-                fi_host = None
-            if fi_host is None or len(fi_host) != s:
-                raise ValueError("frame_index must be a sequence of %d ring slots or a contiguous CUDA int32 [%d] tensor"
-                                 % (s, s))
-            if act_host is None:
-                fi_host = [0 if v is None else v for v in fi_host]
-            if any(fi_host[i] is None or isinstance(fi_host[i], bool) or int(fi_host[i]) != fi_host[i]
-                   or not 0 <= int(fi_host[i]) < nf for i in named):
-                raise ValueError("frame_index must name ring slots in [0, %d)" % nf)
-            keep = set(named)
-            fi_host = [int(v) if i in keep else 0 for i, v in enumerate(fi_host)]
+        fi_host = self._stream_frame_index(frame_index, nf, act_host)
         # ---- dt
         dt_host, dt_dev, dt_scalar = None, None, None
         if self.smooth is not None:
@@ -1055,7 +1054,6 @@ class FaceTracker:
         self._state()
         dev = self.boxes.device
         model = self.model
-        ih, iw = model.input_height, model.input_width
         n = a * k
         if n == 0:
             c = int(model.n_classes)
@@ -1080,31 +1078,17 @@ class FaceTracker:
         snap = alignment.track_gather_streams_device(
             active, self.m_crop, self.boxes, k, frame_index=frame_index, dt=dt_dev, best_q=self.best_q if best else None,
             reset=self._best_reset if best else None)
-        crops = alignment.warp_frames_device(ring, snap["m"], ih, iw, frame_index_dev=snap["frame_index"],
-                                             boxes_dev=snap["boxes"], samples=self.crop_samples, fmt=self._crop_format,
-                                             src=self.frame_format)
-        out = "landmarks" if self.weights is None else "landmark_stats"
-        res = model.forward_device(crops, out, n_points=self.n_points, thresh=self.thresh,
-                                   workspace=self._active_workspace(n, out))
-        lm, wd = (res, None) if self.weights is None else (res[..., :2], res[..., 2])
-        filt = {}
-        if self.smooth is not None:
-            filt = dict(filter=self.smooth, dt=dt_scalar if dt_dev is None else snap["dt"], state=self.filter_state)
-        lm_frame, m_align, status_rows = alignment.track_step_rows_device(
-            lm, snap["m"], snap["boxes"], snap["slot"], (model.output_height, model.output_width), (ih, iw), (fh, fw),
-            self.crop_template, self.m_crop, self.boxes, self.status, tmpl_align=self.template, weights=wd, **self.limits,
-            **filt)
-        aligned = alignment.warp_frames_device(ring, m_align, self.out_size[0], self.out_size[1],
-                                               frame_index_dev=snap["frame_index"], boxes_dev=snap["boxes"],
-                                               samples=self.samples, fmt=self.aligned_format, src=self.frame_format)
-        self._steps += 1
-        if best:
-            rec = alignment.face_quality_device(aligned, self.aligned_format, self.best_shot.quality)
-            alignment.track_best_update_rows_device(
-                aligned, rec, lm_frame, snap["slot"], snap["best_q"], self.best_q, self.gallery, self.best_frame,
-                int(frame_id), status_rows=status_rows, reset_c=snap["reset"], weights=wd, m=m_align, opts=self.best_shot,
-                best_m=self.best_M, best_lm=self.best_landmarks, best_rec=self.best_rec)
-        return aligned, m_align, lm_frame, status_rows, snap["slot"]
+
+        def best_update(faces, rec, lm, status_rows, **kw):
+            alignment.track_best_update_rows_device(faces, rec, lm, snap["slot"], snap["best_q"], self.best_q,
+                                                    status_rows=status_rows, reset_c=snap["reset"], **kw)
+
+        res = self._sequence(
+            ring, snap,
+            functools.partial(alignment.track_step_rows_device, slot=snap["slot"], m_next=self.m_crop, boxes_next=self.boxes,
+                              status=self.status, dt=dt_scalar if dt_dev is None else snap["dt"]),
+            best_update, self._active_workspace, frame_id)
+        return res + (snap["slot"],)
 
     def best(self):
         """The best shot of every slot, for a tracker with `best_shot`: CUDA tensors (gallery [capacity,...] in the
