@@ -50,7 +50,7 @@ EXPORTS = [
     "flm_track_filter_init", "flm_track_step_filtered",
     "flm_track_assoc_opts_init", "flm_track_associate", "flm_track_associate_streams",
     "flm_quality_opts_init", "flm_face_quality", "flm_best_opts_init", "flm_track_best_update",
-    "flm_track_gather_streams", "flm_track_step_rows", "flm_track_best_update_rows",
+    "flm_track_gather_streams", "flm_track_step_rows", "flm_track_best_update_rows", "flm_track_gather_live",
 ]
 
 
@@ -349,6 +349,8 @@ def _declare(lib):
     lib.flm_track_best_update_rows.restype = i
     lib.flm_track_best_update_rows.argtypes = [vp, vp, sz, i, vp, vp, vp, vp, sz, vp, sz, i, vp, vp, C.c_int64,
                                                C.POINTER(BestOpts), vp, i, vp, vp, vp, vp, vp, vp, vp]
+    lib.flm_track_gather_live.restype = i
+    lib.flm_track_gather_live.argtypes = [vp, vp, i, i, i, i, i, vp, vp, d] + [vp] * 14
 
 
 def load():

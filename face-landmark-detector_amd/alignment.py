@@ -1127,6 +1127,81 @@ def track_gather_streams_device(active, m_crop, boxes, slots_per_stream, frame_i
     return out
 
 
+def track_gather_live_device(m_crop, boxes, slots_per_stream, frame_hw, budget, stream_on=None, frame_index=None,
+                             dt=None, best_q=None, reset=None, age=None, cursor=None, out=None):
+    """The snapshot a step of the LIVE slots starts from, in one launch (flm_track_gather_live; include/flm.h states it):
+    `track_gather_streams_device` with the row map made on the device from the slots' boxes.
+
+    m_crop CUDA float32 [S*K,2,3] and boxes CUDA int32 [S*K,4]: the tracker's state, K = slots_per_stream; frame_hw:
+    (H, W) of the frames, what a box is clipped to; budget: a host integer, the number of rows.  stream_on: None (every
+    stream) or CUDA int32 [S], non-zero for the streams whose slots may be served; frame_index: None (ring slot 0) or
+    CUDA int32 [S]; best_q: None or CUDA float64 [S*K]; reset: None or CUDA int32 [S*K], read and then cleared for the
+    slots that are served.  age: None or CUDA float64 [S*K], the seconds every slot has waited unserved, read and
+    written; with it `dt` is required, a host number or a CUDA float64 [S] tensor -- the time step of every stream -- and
+    a served row's dt is its stream's plus its slot's age.  cursor: None or CUDA int32 [1], the slot the order starts
+    from, read and written: live slots beyond the budget are served first by the next call.  Returns a dict of compact
+    CUDA tensors over the `budget` rows, as `track_gather_streams_device` returns them -- slot int32 (-1: inert), m,
+    boxes, frame_index, and dt (with age), best_q, reset, each present when its input is -- plus counts int32 [4]:
+    (eligible slots, rows served, eligible slots left out, the next cursor).  out: None or a dict that names where to
+    write (any of those keys); only what it does not name is allocated."""
+    import torch
+    k, n_rows = int(slots_per_stream), int(budget)
+    fh, fw = [int(v) for v in frame_hw]
+    _check_matrices(m_crop, None, "m_crop")
+    n = int(m_crop.shape[0])
+    if k < 1 or n < 1 or n % k:
+        raise ValueError("m_crop holds %d slots: slots_per_stream=%d must be >= 1 and divide it" % (n, k))
+    s = n // k
+    if n > 65535 or not 1 <= n_rows <= 65535:
+        raise ValueError("at most 65535 slots and a budget in [1, 65535] (got %d slots, budget %d)" % (n, n_rows))
+    _check_boxes(boxes, n)
+    dt_dev, dt_host = None, 0.0
+    if age is None:
+        if dt is not None:
+            raise ValueError("dt goes with age")
+    elif isinstance(dt, torch.Tensor):
+        dt_dev = dt
+    elif dt is None or isinstance(dt, bool) or not (float(dt) > 0.0 and float(dt) < float("inf")):
+        raise ValueError("with age, dt must be a finite number > 0 or a CUDA float64 [%d] tensor (got %r)" % (s, dt))
+    else:
+        dt_host = float(dt)
+    for x, dtype, shape, what in ((stream_on, torch.int32, (s,), "stream_on"), (frame_index, torch.int32, (s,), "frame_index"),
+                                  (dt_dev, torch.float64, (s,), "dt"), (best_q, torch.float64, (n,), "best_q"),
+                                  (reset, torch.int32, (n,), "reset"), (age, torch.float64, (n,), "age"),
+                                  (cursor, torch.int32, (1,), "cursor")):
+        if x is not None:
+            _check_out(x, dtype, shape, what)
+    out = dict(out or {})
+    dev = m_crop.device
+    spec = (("slot", torch.int32, (n_rows,), True), ("m", torch.float32, (n_rows, 2, 3), True),
+            ("boxes", torch.int32, (n_rows, 4), True), ("frame_index", torch.int32, (n_rows,), True),
+            ("dt", torch.float64, (n_rows,), age is not None), ("best_q", torch.float64, (n_rows,), best_q is not None),
+            ("reset", torch.int32, (n_rows,), reset is not None), ("counts", torch.int32, (4,), True))
+    if set(out) - {name for name, *_ in spec}:
+        raise ValueError("out names %r, which the gather does not write" % sorted(set(out) - {n_ for n_, *_ in spec}))
+    for name, dtype, shape, wanted in spec:
+        if not wanted:
+            if out.get(name) is not None:
+                raise ValueError("out[%r] needs its input" % name)
+            out.pop(name, None)
+        elif out.get(name) is None:
+            out[name] = torch.empty(shape, dtype=dtype, device=dev)
+        else:
+            _check_out(out[name], dtype, shape, "out[%r]" % name)
+    _check_overlap(out["m"], m_crop, "out['m'] and m_crop")
+    _check_overlap(out["boxes"], boxes, "out['boxes'] and boxes")
+    _check_overlap(out.get("best_q"), best_q, "out['best_q'] and best_q")
+    _check_overlap(out.get("reset"), reset, "out['reset'] and reset")
+    _check_overlap(out.get("dt"), age, "out['dt'] and age")
+    p = _ptr
+    _lib.check(_lib.load().flm_track_gather_live(
+        _lib.stream_ptr(), p(stream_on), s, k, fh, fw, n_rows, p(frame_index), p(dt_dev), dt_host, _lib.ptr(m_crop),
+        _lib.ptr(boxes), p(best_q), p(reset), p(age), p(cursor), _lib.ptr(out["slot"]), _lib.ptr(out["m"]),
+        _lib.ptr(out["boxes"]), _lib.ptr(out["frame_index"]), p(out.get("dt")), p(out.get("best_q")), p(out.get("reset")),
+        _lib.ptr(out["counts"])), "flm_track_gather_live")
+    return out
+
+
 def track_step_rows_device(lm, m_crop_c, boxes_c, slot, grid_hw, in_hw, frame_hw, tmpl_crop, m_next, boxes_next, status,
                            tmpl_align=None, weights=None, min_points=2, min_score=0.0, min_side=0.0,
                            max_side=float("inf"), lm_frame=None, m_align=None, status_rows=None, filter=None, dt=None,

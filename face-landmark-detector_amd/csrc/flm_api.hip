@@ -1343,6 +1343,38 @@ int flm_track_gather_streams(flm_stream_t stream, const int32_t* active, int a, 
                                      boxes, best_q, reset, slot_c, m_c, boxes_c, frame_idx_c, dt_c, best_q_c, reset_c);
 }
 
+int flm_track_gather_live(flm_stream_t stream, const int32_t* stream_on, int s, int k, int fh, int fw, int n,
+                          const int32_t* frame_idx_stream, const double* dt_stream, double dt, const float* m_crop,
+                          const int32_t* boxes, const double* best_q, int32_t* reset, double* age, int32_t* cursor,
+                          int32_t* slot_c, float* m_c, int32_t* boxes_c, int32_t* frame_idx_c, double* dt_c,
+                          double* best_q_c, int32_t* reset_c, int32_t* counts) {
+  const char* who = "flm_track_gather_live";
+  if (!m_crop || !boxes || !slot_c || !m_c || !boxes_c || !frame_idx_c || !counts) {
+    set_error("%s: null argument", who);  // (stream_on, frame_idx_stream, cursor and the three optional groups may be null)
+    return FLM_ERR_ARG;
+  }
+  if ((age == nullptr) != (dt_c == nullptr) || (best_q == nullptr) != (best_q_c == nullptr) ||
+      (reset == nullptr) != (reset_c == nullptr)) {
+    set_error("%s: age_dev/dt_c, best_q_dev/best_q_c and reset_dev/reset_c go together (both or neither)", who);
+    return FLM_ERR_ARG;
+  }
+  if (dt_stream && !age) {
+    set_error("%s: dt_stream_dev goes with age_dev", who);
+    return FLM_ERR_ARG;
+  }
+  if (age && !dt_stream && !(dt > 0.0 && std::isfinite(dt))) {
+    set_error("%s: dt=%g, needs a finite dt > 0 (seconds since the previous step) or dt_stream_dev", who, dt);
+    return FLM_ERR_ARG;
+  }
+  TrackLiveArgs g;
+  g.boxes = boxes; g.m_crop = m_crop; g.s = s; g.k = k; g.fh = fh; g.fw = fw; g.n = n;
+  g.stream_on = stream_on; g.frame_idx_stream = frame_idx_stream; g.dt_stream = dt_stream; g.dt = dt;
+  g.best_q = best_q; g.reset = reset; g.age = age; g.cursor = cursor;
+  g.slot_c = slot_c; g.m_c = m_c; g.boxes_c = boxes_c; g.frame_idx_c = frame_idx_c;
+  g.dt_c = dt_c; g.best_q_c = best_q_c; g.reset_c = reset_c; g.counts = counts;
+  return launch_track_gather_live(static_cast<hipStream_t>(stream), g);
+}
+
 // ---- association (flm_track_assoc.hip) ------------------------------------------------------------------------------
 
 void flm_track_assoc_opts_init(flm_track_assoc_opts* opts) {

@@ -293,6 +293,29 @@ int launch_track_gather_streams(hipStream_t s, const int32_t* active, int a, int
                                 const int32_t* frame_idx_stream, const double* dt_stream, const float* m_crop,
                                 const int32_t* boxes, const double* best_q, int32_t* reset, int32_t* slot_c, float* m_c,
                                 int32_t* boxes_c, int32_t* frame_idx_c, double* dt_c, double* best_q_c, int32_t* reset_c);
+// flm_track_gather_live's arguments under the names of include/flm.h (the kernel takes the struct as it is)
+struct TrackLiveArgs {
+  const int32_t* boxes;             // [S*K,4]
+  const float* m_crop;              // [S*K,2,3]
+  int s, k, fh, fw, n;              // n: the budget, the number of rows
+  const int32_t* stream_on;         // [S] or null
+  const int32_t* frame_idx_stream;  // [S] or null
+  const double* dt_stream;          // [S] or null
+  double dt;
+  const double* best_q;             // [S*K] or null
+  int32_t* reset;                   // [S*K] or null, in/out
+  double* age;                      // [S*K] or null, in/out
+  int32_t* cursor;                  // [1] or null, in/out
+  int32_t* slot_c;
+  float* m_c;
+  int32_t* boxes_c;
+  int32_t* frame_idx_c;
+  double* dt_c;
+  double* best_q_c;
+  int32_t* reset_c;
+  int32_t* counts;                  // [4]
+};
+int launch_track_gather_live(hipStream_t s, const TrackLiveArgs& g);
 
 // association (flm_track_assoc.hip); pointers, sizes and the option struct have been checked by the caller
 int launch_track_associate(hipStream_t s, const int32_t* det, const int32_t* n_det, int d, int k, int c, int in_h, int in_w,

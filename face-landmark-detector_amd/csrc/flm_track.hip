@@ -364,6 +364,101 @@ __global__ __launch_bounds__(64) void track_gather_streams_kernel(const TrackGat
   if (g.reset_c) g.reset_c[r] = rs;
 }
 
+// ---- flm_track_gather_live: flm_track_gather_streams with the row map computed from the slots' liveness ----------------
+// ONE workgroup walks the slots in the cyclic order of the contract -- position p is slot (c0 + p) mod S*K -- a chunk of
+// blockDim.x positions at a time, so an eligible slot's exclusive prefix count IS its rank and no second pass is needed:
+// a ballot and mbcnt give the prefix within the wave, the waves' totals meet in LDS, and a carry every thread keeps for
+// itself (the same sum in all of them) runs from chunk to chunk.  No atomics: the order is a function of the inputs.  A
+// thread owns its slot: it copies the row when the rank fits the budget and settles reset and age either way.  E is known
+// after the last chunk; the inert rows, the counts and the cursor are written then.  The cursor is read by every thread
+// before the first barrier and written by thread 0 after the last.
+__global__ __launch_bounds__(1024) void track_gather_live_kernel(const TrackLiveArgs g) {
+  __shared__ int wave_total[16];
+  __shared__ int last_served;
+  const int n_slots = g.s * g.k, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n_waves = blockDim.x >> 6;
+  int c0 = g.cursor ? g.cursor[0] : 0;
+  if (c0 < 0 || c0 >= n_slots) c0 = 0;
+  int carry = 0;   // eligible slots at the positions before this chunk
+  for (int base = 0; base < n_slots; base += blockDim.x) {
+    const int p = base + tid;
+    int gs = c0 + p;
+    if (gs >= n_slots) gs -= n_slots;
+    bool on = false, elig = false;
+    int sid = 0, b0 = 0, b1 = 0, b2 = 0, b3 = 0;
+    if (p < n_slots) {
+      sid = gs / g.k;
+      on = !g.stream_on || g.stream_on[sid] != 0;
+      if (on) {
+        const int32_t* bx = g.boxes + (size_t)gs * 4;
+        b0 = bx[0]; b1 = bx[1]; b2 = bx[2]; b3 = bx[3];
+        elig = !box_empty(b0, b1, b2, b3, g.fh, g.fw);
+      }
+    }
+    const unsigned long long mask = __ballot(elig);
+    const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+    if (lane == 0) wave_total[wave] = __popcll(mask);
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int w = 0; w < n_waves; ++w) {
+      const int t = wave_total[w];
+      before += w < wave ? t : 0;
+      total += t;
+    }
+    const int rank = carry + before + below;
+    carry += total;
+    if (on) {
+      const bool served = elig && rank < g.n;
+      double d = 0.0;
+      bool good = false;
+      if (g.age) {
+        d = g.dt_stream ? g.dt_stream[sid] : g.dt;
+        good = d > 0.0 && __builtin_isfinite(d);
+      }
+      if (served) {
+        const int r = rank;
+        g.slot_c[r] = gs;
+        const float* mm = g.m_crop + (size_t)gs * 6;
+        float* mo = g.m_c + (size_t)r * 6;
+        mo[0] = mm[0]; mo[1] = mm[1]; mo[2] = mm[2]; mo[3] = mm[3]; mo[4] = mm[4]; mo[5] = mm[5];
+        int32_t* bo = g.boxes_c + (size_t)r * 4;
+        bo[0] = b0; bo[1] = b1; bo[2] = b2; bo[3] = b3;
+        g.frame_idx_c[r] = g.frame_idx_stream ? g.frame_idx_stream[sid] : 0;
+        if (g.best_q) g.best_q_c[r] = g.best_q[gs];
+        if (g.reset) {
+          g.reset_c[r] = g.reset[gs];
+          g.reset[gs] = 0;
+        }
+        if (g.age) {
+          g.dt_c[r] = good ? d + g.age[gs] : d;
+          g.age[gs] = 0.0;
+        }
+        if (rank == g.n - 1) last_served = gs;
+      } else if (g.age) {
+        g.age[gs] = !elig ? 0.0 : good ? g.age[gs] + d : __builtin_nan("");
+      }
+    }
+    __syncthreads();   // wave_total is rewritten by the next chunk; last_served is read below
+  }
+  const int served = min(carry, g.n);
+  for (int r = served + tid; r < g.n; r += blockDim.x) {
+    g.slot_c[r] = -1;
+    float* mo = g.m_c + (size_t)r * 6;
+    mo[0] = 1.f; mo[1] = 0.f; mo[2] = 0.f; mo[3] = 0.f; mo[4] = 1.f; mo[5] = 0.f;
+    int32_t* bo = g.boxes_c + (size_t)r * 4;
+    bo[0] = 0; bo[1] = 0; bo[2] = 0; bo[3] = 0;
+    g.frame_idx_c[r] = 0;
+    if (g.dt_c) g.dt_c[r] = 0.0;
+    if (g.best_q_c) g.best_q_c[r] = -1.0;
+    if (g.reset_c) g.reset_c[r] = 0;
+  }
+  if (tid == 0) {
+    int next = c0;
+    if (carry > g.n) next = last_served + 1 == n_slots ? 0 : last_served + 1;
+    g.counts[0] = carry; g.counts[1] = served; g.counts[2] = carry - served; g.counts[3] = next;
+    if (g.cursor) g.cursor[0] = next;
+  }
+}
+
 // ---- launchers: the sizes every entry point shares ----------------------------------------------------------
 static int check_track_sizes(const char* who, int k, int c, int in_h, int in_w, int fh, int fw) {
   if (k < 1 || k > 65535) {
@@ -483,6 +578,28 @@ int launch_track_gather_streams(hipStream_t s, const int32_t* active, int a, int
   g.dt_c = dt_c; g.best_q_c = best_q_c; g.reset_c = reset_c;
   track_gather_streams_kernel<<<cdiv(g.n_rows, 64), 64, 0, s>>>(g);
   FLM_LAUNCH_CHECK("track_gather_streams_kernel");
+  return FLM_OK;
+}
+
+// Pointers, their pairing and the scalar dt have been checked by the caller in flm_api.hip.
+int launch_track_gather_live(hipStream_t s, const TrackLiveArgs& g) {
+  const char* who = "flm_track_gather_live";
+  if (g.n < 1 || g.n > 65535) {
+    set_error("%s: n=%d, needs 1 <= n <= 65535", who, g.n);
+    return FLM_ERR_SHAPE;
+  }
+  if (g.s < 1 || g.k < 1 || (long long)g.s * g.k > 65535) {
+    set_error("%s: s=%d streams of k=%d slots, needs 1 <= s, 1 <= k and s*k <= 65535", who, g.s, g.k);
+    return FLM_ERR_SHAPE;
+  }
+  if (g.fh < 1 || g.fw < 1) {
+    set_error("%s: frame %dx%d, needs fh, fw >= 1", who, g.fh, g.fw);
+    return FLM_ERR_SHAPE;
+  }
+  const int waves = cdiv(g.s * g.k, 64);   // whole waves, 16 at the most: the kernel walks the rest in chunks
+  const int threads = 64 * (waves < 16 ? waves : 16);
+  track_gather_live_kernel<<<1, threads, 0, s>>>(g);
+  FLM_LAUNCH_CHECK("track_gather_live_kernel");
   return FLM_OK;
 }
 

@@ -590,7 +590,9 @@ class FaceTracker:
     (alignment.track_associate_streams_device: no pair of two streams is ever evaluated); every tensor the tracker
     owns or returns stays flat over the `capacity` global slots.  With streams=1 every method is the single-stream
     code, launch for launch.  `step_active` steps only the streams that delivered a frame, each on its own `dt`, and
-    leaves every other stream's state untouched."""
+    leaves every other stream's state untouched; `step_live` steps only the slots that hold a face, at most a `budget`
+    of them, and leaves every other slot untouched (the tracker then also owns `live_counts`, `live_cursor` and, with
+    `smooth`, `slot_age`)."""
 
     def __init__(self, model, frame_hw, capacity, out_size=(112, 112), template=None, crop_template=None, n_points=4,
                  thresh=0.0, weights=None, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"),
@@ -649,6 +651,7 @@ class FaceTracker:
         self.streams, self.slots_per_stream = int(streams), capacity // int(streams)
         self.best_shot, self.gallery, self._steps = best_shot, None, 0
         self._ws_active = None   # the forward workspace of step_active (_active_workspace)
+        self._waiting = False    # step_live has run below capacity: slot_age may hold a wait (_served)
         self._crop_format = alignment.AlignedFormat("nhwc", "uint8")
         self._templates = (np.ascontiguousarray(tm, np.float64), np.ascontiguousarray(tc, np.float64))
         self.m_crop = None    # the device state, allocated by the first call that needs it (_state)
@@ -669,6 +672,9 @@ class FaceTracker:
         self.misses = torch.zeros((n,), dtype=torch.int32, device=dev)
         if self.smooth is not None:     # -1: no landmark has a history
             self.filter_state = torch.full((n, int(self.model.n_classes), 6), -1.0, dtype=torch.float64, device=dev)
+            self.slot_age = torch.zeros((n,), dtype=torch.float64, device=dev)   # step_live: seconds waited unserved
+        self.live_cursor = torch.zeros((1,), dtype=torch.int32, device=dev)      # step_live: where its order starts
+        self.live_counts = torch.zeros((4,), dtype=torch.int32, device=dev)      # step_live: what its last gather counted
         if self.best_shot is not None:  # -1: the slot holds no best
             fmt = self.aligned_format or alignment.AlignedFormat()
             c = int(self.model.n_classes)
@@ -955,7 +961,24 @@ class FaceTracker:
         if self.best_shot is not None:
             self.best_q, self._best_q_spare = self._best_q_spare, self.best_q
             self._best_reset.zero_()
+        self._served()
         return res
+
+    def _served(self, slot=None):
+        """`step` (slot None: every slot) or `step_active` (the rows' slots, -1 for an inert row) has served slots that
+        `step_live` may have left waiting: their wait ends here, so the next `step_live` does not add it to their dt.
+        Launches nothing for a tracker whose `step_live` never ran below capacity."""
+        import torch
+        if self.smooth is None or not self._waiting:
+            return
+        if slot is None:
+            self.slot_age.zero_()
+            self._waiting = False
+            return
+        n = self.capacity
+        age = torch.cat([self.slot_age, self.slot_age.new_zeros(1)])       # (an inert row clears the spare entry)
+        age.index_fill_(0, torch.where(slot < 0, n, slot).to(torch.int64), 0.0)
+        self.slot_age.copy_(age[:n])
 
     def _active_workspace(self, n, out):
         """The forward workspace `step_active` passes for a batch of n faces, or None (the model's cached path).  The
@@ -969,6 +992,53 @@ class FaceTracker:
         if self._ws_active is None:
             self._ws_active = self.model.new_workspace(min(self.capacity, self.model.max_batch), out, self.n_points)
         return self._ws_active
+
+    def _stream_dt(self, dt, named):
+        """The `dt` of `step_active` and `step_live`, parsed -> (a host list of `streams` numbers to upload, the CUDA
+        float64 [streams] tensor to use where it lies, the one host number for every stream): exactly one is not None
+        for a tracker that smooths, all three are None for one that does not.  named: the streams whose host entries
+        count; the other entries are ignored and come back as 0."""
+        import math
+        import torch
+        s = self.streams
+        dt_host, dt_dev, dt_scalar = None, None, None
+        if self.smooth is not None:
+            if isinstance(dt, torch.Tensor):
+                if (dt.dtype != torch.float64 or not dt.is_cuda or not dt.is_contiguous() or tuple(dt.shape) != (s,)):
+                    raise ValueError("dt must be None, a number, a sequence of %d numbers or a contiguous CUDA float64 "
+                                     "[%d] tensor" % (s, s))
+                dt_dev = dt
+            elif dt is None or isinstance(dt, (int, float, np.integer, np.floating)):
+                dt_scalar = self.smooth.time_step(dt)
+            else:
+                try:
+                    dt_host = list(dt)
+                except TypeError:
+                    dt_host = None
+                if dt_host is None or len(dt_host) != s:
+                    raise ValueError("dt must be None, a number, a sequence of %d numbers or a contiguous CUDA float64 "
+                                     "[%d] tensor" % (s, s))
+                for i in named:
+                    v = dt_host[i]
+                    if v is None or isinstance(v, bool) or not (float(v) > 0.0 and math.isfinite(float(v))):
+                        raise ValueError("dt of stream %d must be finite and > 0, got %r" % (i, v))
+                keep = set(named)
+                dt_host = [float(v) if i in keep else 0.0 for i, v in enumerate(dt_host)]
+        return dt_host, dt_dev, dt_scalar
+
+    def _upload(self, dt_host, *ints):
+        """One upload of everything that arrived on the host -- dt_host float64, every list of `ints` int32; None: nothing
+        to send -- float64 first, so every view is aligned.  Returns the device views in the order given, None for None."""
+        import torch
+        parts = [None if x is None else np.asarray(x, t) for x, t in [(dt_host, np.float64)] + [(x, np.int32) for x in ints]]
+        if all(x is None for x in parts):
+            return parts
+        up = torch.from_numpy(np.concatenate([x.view(np.uint8) for x in parts if x is not None])).to(self.boxes.device)
+        views, off = [], 0
+        for x in parts:
+            views.append(None if x is None else up[off:off + x.nbytes].view(torch.float64 if x.dtype == np.float64 else torch.int32))
+            off += 0 if x is None else x.nbytes
+        return views
 
     def step_active(self, ring, frame_index, active, dt=None, frame_id=None):
         """One frame for the slots of the streams `active` alone, each stream on its own clock; every other stream keeps
@@ -1001,7 +1071,6 @@ class FaceTracker:
         active[a]*slots_per_stream + j: (aligned [N,...], M float32 [N,2,3], landmarks float64 [N,C,2], status int32 [N],
         slots int32 [N])."""
         import functools
-        import math
         import torch
         s, k = self.streams, self.slots_per_stream
         frame_id, _, nf = self._step_prologue(ring, dt, frame_id)
@@ -1027,30 +1096,7 @@ class FaceTracker:
         named = range(s) if act_host is None else act_host    # the streams whose host entries count
         # ---- frame_index
         fi_host = self._stream_frame_index(frame_index, nf, act_host)
-        # ---- dt
-        dt_host, dt_dev, dt_scalar = None, None, None
-        if self.smooth is not None:
-            if isinstance(dt, torch.Tensor):
-                if (dt.dtype != torch.float64 or not dt.is_cuda or not dt.is_contiguous() or tuple(dt.shape) != (s,)):
-                    raise ValueError("dt must be None, a number, a sequence of %d numbers or a contiguous CUDA float64 "
-                                     "[%d] tensor" % (s, s))
-                dt_dev = dt
-            elif dt is None or isinstance(dt, (int, float, np.integer, np.floating)):
-                dt_scalar = self.smooth.time_step(dt)
-            else:
-                try:
-                    dt_host = list(dt)
-                except TypeError:
-                    dt_host = None
-                if dt_host is None or len(dt_host) != s:
-                    raise ValueError("dt must be None, a number, a sequence of %d numbers or a contiguous CUDA float64 "
-                                     "[%d] tensor" % (s, s))
-                for i in named:
-                    v = dt_host[i]
-                    if v is None or isinstance(v, bool) or not (float(v) > 0.0 and math.isfinite(float(v))):
-                        raise ValueError("dt of stream %d must be finite and > 0, got %r" % (i, v))
-                keep = set(named)
-                dt_host = [float(v) if i in keep else 0.0 for i, v in enumerate(dt_host)]
+        dt_host, dt_dev, dt_scalar = self._stream_dt(dt, named)
         self._state()
         dev = self.boxes.device
         model = self.model
@@ -1062,18 +1108,8 @@ class FaceTracker:
                     torch.empty((0, 2, 3), dtype=torch.float32, device=dev),
                     torch.empty((0, c, 2), dtype=torch.float64, device=dev),
                     torch.empty((0,), dtype=torch.int32, device=dev), torch.empty((0,), dtype=torch.int32, device=dev))
-        # ---- one upload of everything that arrived on the host: float64 first, so every view is aligned
-        parts = [np.asarray(dt_host, np.float64)] if dt_host is not None else []
-        parts += [np.asarray(x, np.int32) for x in (fi_host, act_host) if x is not None]
-        if parts:
-            up = torch.from_numpy(np.concatenate([x.view(np.uint8) for x in parts])).to(dev)
-            off = 0
-            if dt_host is not None:
-                dt_dev, off = up[:8 * s].view(torch.float64), 8 * s
-            if fi_host is not None:
-                frame_index, off = up[off:off + 4 * s].view(torch.int32), off + 4 * s
-            if act_host is not None:
-                active = up[off:off + 4 * a].view(torch.int32)
+        up = self._upload(dt_host, fi_host, act_host)
+        dt_dev, frame_index, active = [b if a is None else a for a, b in zip(up, (dt_dev, frame_index, active))]
         best = self.best_shot is not None
         snap = alignment.track_gather_streams_device(
             active, self.m_crop, self.boxes, k, frame_index=frame_index, dt=dt_dev, best_q=self.best_q if best else None,
@@ -1087,6 +1123,82 @@ class FaceTracker:
             ring, snap,
             functools.partial(alignment.track_step_rows_device, slot=snap["slot"], m_next=self.m_crop, boxes_next=self.boxes,
                               status=self.status, dt=dt_scalar if dt_dev is None else snap["dt"]),
+            best_update, self._active_workspace, frame_id)
+        self._served(snap["slot"])
+        return res + (snap["slot"],)
+
+    def step_live(self, ring, frame_index, budget, active=None, dt=None, frame_id=None):
+        """One frame for the slots that HOLD A FACE, at most `budget` of them: the empty slots of the stepped streams,
+        which `step` and `step_active` carry through the forward as zero crops, are no rows here.  A camera sized for 16
+        faces usually sees one or two, and the forward is nearly all of a step.  Which slots are live is known only on the
+        device; alignment.track_gather_live_device compacts them there into a batch of the fixed size `budget`, a host
+        integer in [1, capacity], so nothing is downloaded and nothing synchronises.  Live slots beyond the budget sit the
+        tick out with everything intact -- crop, filter history, best shot, pending best-shot reset -- and are served
+        first on the next tick (`live_cursor`); the `dt` of a slot that waited includes its wait (`slot_age`).
+        `live_counts` int32 [4], the tracker's own, holds (live slots, rows served, live slots left out, the next cursor)
+        of the last call: a caller may look at it now and then to size its budget.  Works for any `streams` >= 1;
+        `step`, `step_active` and `step_live` may be mixed freely, and all three count as a step.
+
+        frame_index, dt, frame_id: as `step_active` takes them.  active: None (every stream), a host sequence of distinct
+        stream ids as `step_active` takes it (an empty one steps no stream: every row is inert), or a contiguous CUDA
+        int32 [streams] MASK, non-zero for the streams that delivered a frame, used where it lies; with a mask on the
+        device every entry of a host `frame_index` or `dt` is checked.  The slots of a stream that is not active are
+        neither read nor written.  Whatever arrives on the host goes up in ONE upload.
+
+        Sequence: alignment.track_gather_live_device, then what `step_active` runs on its snapshot -- the uint8 crop warp
+        -> model.forward_device at batch `budget`, in the workspace of `_active_workspace` ->
+        alignment.track_step_rows_device -> the aligned warp -> with best_shot, alignment.face_quality_device and
+        alignment.track_best_update_rows_device.  `frame_slots` keeps what the last `step` wrote.
+
+        Returns CUDA tensors over the `budget` rows (aligned, M float32 [budget,2,3], landmarks float64 [budget,C,2],
+        status int32 [budget], slots int32 [budget]); rows past the served ones are zero faces, the identity, TRACK_DEAD
+        and slot -1.  A dead slot is no row, so its `status` keeps the reason it was lost where `step` would overwrite it
+        with TRACK_DEAD; `lost()` still names it."""
+        import functools
+        import torch
+        s, k = self.streams, self.slots_per_stream
+        frame_id, _, nf = self._step_prologue(ring, dt, frame_id)
+        if isinstance(budget, bool) or int(budget) != budget or not 1 <= int(budget) <= self.capacity:
+            raise ValueError("budget must be an integer in [1, %d] (got %r)" % (self.capacity, budget))
+        budget = int(budget)
+        what = ("active must be None, a sequence of distinct stream ids in [0, %d) or a contiguous CUDA int32 [%d] mask"
+                % (s, s))
+        on_host, named = None, range(s)
+        if isinstance(active, torch.Tensor):
+            if active.dtype != torch.int32 or not active.is_cuda or not active.is_contiguous() or tuple(active.shape) != (s,):
+                raise ValueError(what)
+            named = None                                          # the host cannot tell: every host entry counts
+        elif active is not None:
+            try:
+                named = list(active)
+            except TypeError:
+                raise ValueError(what) from None
+            if (any(isinstance(v, bool) or int(v) != v or not 0 <= int(v) < s for v in named)
+                    or len(set(int(v) for v in named)) != len(named)):
+                raise ValueError(what)
+            named = [int(v) for v in named]
+            on_host = [1 if i in set(named) else 0 for i in range(s)]
+        fi_host = self._stream_frame_index(frame_index, nf, named)
+        dt_host, dt_dev, dt_scalar = self._stream_dt(dt, range(s) if named is None else named)
+        self._state()
+        up = self._upload(dt_host, fi_host, on_host)
+        dt_dev, frame_index, active = [b if a is None else a for a, b in zip(up, (dt_dev, frame_index, active))]
+        best, smooth = self.best_shot is not None, self.smooth is not None
+        self._waiting = self._waiting or budget < self.capacity
+        snap = alignment.track_gather_live_device(
+            self.m_crop, self.boxes, k, self.frame_hw, budget, stream_on=active, frame_index=frame_index,
+            dt=(dt_scalar if dt_dev is None else dt_dev) if smooth else None, best_q=self.best_q if best else None,
+            reset=self._best_reset if best else None, age=self.slot_age if smooth else None, cursor=self.live_cursor,
+            out=dict(counts=self.live_counts))
+
+        def best_update(faces, rec, lm, status_rows, **kw):
+            alignment.track_best_update_rows_device(faces, rec, lm, snap["slot"], snap["best_q"], self.best_q,
+                                                    status_rows=status_rows, reset_c=snap["reset"], **kw)
+
+        res = self._sequence(
+            ring, snap,
+            functools.partial(alignment.track_step_rows_device, slot=snap["slot"], m_next=self.m_crop, boxes_next=self.boxes,
+                              status=self.status, dt=snap.get("dt")),
             best_update, self._active_workspace, frame_id)
         return res + (snap["slot"],)
 

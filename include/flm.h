@@ -808,6 +808,57 @@ int flm_track_gather_streams(flm_stream_t stream, const int32_t* active_dev /*[A
                              int32_t* frame_idx_c /*[A*K]*/, double* dt_c /*[A*K] or NULL*/,
                              double* best_q_c /*[A*K] or NULL*/, int32_t* reset_c /*[A*K] or NULL*/);
 
+/* flm_track_gather_live: flm_track_gather_streams with the row map computed from the slots' LIVENESS instead of read from
+ * active_dev, in ONE launch (one workgroup; a prefix count over the slots, no atomics: the row order is a function of the
+ * inputs alone).  Which slots hold a face is known only on the device -- flm_track_step loses tracks there,
+ * flm_track_associate* starts them there --, so the map is made there: the live slots are compacted into a batch of the
+ * fixed size N (the BUDGET, a host number: every launch shape that follows is known without a synchronisation).  Live
+ * slots beyond the budget sit the call out with their state intact and are served first by the next call.
+ * In:  stream_on_dev int32 [S] or NULL (NULL: every stream is on); s, k (slots PER STREAM), fh, fw; n, the budget = the
+ *      number of rows; frame_idx_stream_dev int32 [S] or NULL; dt_stream_dev float64 [S] or NULL, with the scalar dt;
+ *      m_crop_dev float32 [S*K,2,3]; boxes_dev int32 [S*K,4]; best_q_dev float64 [S*K] or NULL.
+ * In/out: reset_dev int32 [S*K] or NULL; age_dev float64 [S*K] or NULL, the seconds every slot has waited unserved;
+ *      cursor_dev int32 [1] or NULL, the slot the order starts from.
+ * Out, compact: slot_c int32 [N], m_c float32 [N,2,3], boxes_c int32 [N,4], frame_idx_c int32 [N], and, each required
+ *      exactly when its input is given, dt_c float64 [N] (age_dev), best_q_c float64 [N] (best_q_dev), reset_c int32 [N]
+ *      (reset_dev); counts_dev int32 [4].
+ * Contract:
+ *  1. Slot g belongs to stream i = g / K.  It is ELIGIBLE when (stream_on_dev is NULL or stream_on_dev[i] != 0) and the
+ *     clip of boxes_dev[g] to fh x fw -- the clip of flm_landmarks_to_frame -- is not empty: the negation of the DEAD test
+ *     of flm_track_step, step 1.  E = the number of eligible slots.
+ *  2. c0 = cursor_dev[0]; 0 without a cursor or when the value lies outside [0, S*K).  The eligible slots are ranked in
+ *     the cyclic order c0, c0+1, ..., S*K-1, 0, ..., c0-1; the first served = min(E, N) of them become the rows
+ *     0 .. served-1, in that order.
+ *  3. A served row r of slot g: slot_c[r] = g; m_c[r], boxes_c[r], best_q_c[r] and reset_c[r] are bit copies of the
+ *     entries at g; frame_idx_c[r] = frame_idx_stream[i] (0 without it).  reset_dev[g] is then set to 0: the pending reset
+ *     MOVES into the snapshot, as in flm_track_gather_streams.
+ *  4. A row r >= served is inert exactly as rule 2 there: slot_c = -1, m_c = the identity, boxes_c = (0,0,0,0),
+ *     frame_idx_c = 0, dt_c = 0.0, best_q_c = -1.0, reset_c = 0; nothing global is read or written for it.
+ *  5. Time, only with age_dev.  d = dt_stream_dev ? dt_stream_dev[i] : dt; d is GOOD when it is > 0 and finite.
+ *       served slot:                 dt_c[r] = good ? d + age[g] : d   (one IEEE add);  then age[g] = 0.0
+ *       eligible, not served:        age[g] = good ? age[g] + d : NaN  (the quiet NaN 0x7ff8000000000000)
+ *       on, not eligible:            age[g] = 0.0
+ *       slot of a stream that is off: neither read nor written -- boxes_dev included
+ *     A NaN age reaches dt_c when the slot is served later, and rule 2 of flm_track_step_rows then restarts that slot's
+ *     filter history: a wait of unknown length is no history.
+ *  6. counts = (E, served, E - served, cursor_out); cursor_out = (the last served slot + 1) mod S*K when E > N, otherwise
+ *     c0; cursor_dev[0] = cursor_out.  Over consecutive calls on an unchanged set of E > N eligible slots
+ *     every one of them is served within ceil(E/N) calls.
+ *  7. A slot that is not served keeps every bit of m_crop, boxes, best_q and reset.  No two arguments may overlap.  One
+ *     launch, no workspace, no allocation, no synchronisation.
+ * Errors, all found before anything is launched: a null m_crop_dev, boxes_dev, slot_c, m_c, boxes_c, frame_idx_c or
+ * counts_dev, an optional output without its input or the reverse, dt_stream_dev without age_dev, or, with age_dev and
+ * without dt_stream_dev, a dt that is not > 0 and finite -> FLM_ERR_ARG.  FLM_ERR_SHAPE, the limit named in
+ * flm_last_error(), unless 1 <= n <= 65535, 1 <= s, 1 <= k, s*k <= 65535 and fh, fw >= 1. */
+int flm_track_gather_live(flm_stream_t stream, const int32_t* stream_on_dev /*[S] or NULL*/, int s, int k /*slots PER STREAM*/,
+                          int fh, int fw, int n /*the budget*/, const int32_t* frame_idx_stream_dev /*[S] or NULL*/,
+                          const double* dt_stream_dev /*[S] or NULL*/, double dt, const float* m_crop_dev /*[S*K,2,3]*/,
+                          const int32_t* boxes_dev /*[S*K,4]*/, const double* best_q_dev /*[S*K] or NULL*/,
+                          int32_t* reset_dev /*[S*K] or NULL, in/out*/, double* age_dev /*[S*K] or NULL, in/out*/,
+                          int32_t* cursor_dev /*[1] or NULL, in/out*/, int32_t* slot_c /*[N]*/, float* m_c /*[N,2,3]*/,
+                          int32_t* boxes_c /*[N,4]*/, int32_t* frame_idx_c /*[N]*/, double* dt_c /*[N] or NULL*/,
+                          double* best_q_c /*[N] or NULL*/, int32_t* reset_c /*[N] or NULL*/, int32_t* counts_dev /*[4]*/);
+
 /* flm_track_step_rows: flm_track_step / flm_track_step_filtered on rows, in ONE launch (a workgroup of one wave per row;
  * the kernel runs the body of the two calls above, so the arithmetic is stated once).
  * The arguments are those of flm_track_step_filtered with k replaced by n, plus slot_dev int32 [N], n_slots, dt_dev
