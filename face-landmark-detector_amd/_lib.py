@@ -17,6 +17,7 @@ IN_U8_BGR, IN_F32_RGB = 0, 1
 OUT_PROBS, OUT_CLASSMAP, OUT_LANDMARKS, OUT_LOGITS, OUT_LANDMARKS_STATS = 0, 1, 2, 3, 4
 LANDMARK_REC = 6  # FLM_LANDMARK_REC: x, y, score, var_x, var_y, cov_xy
 QUALITY_REC = 8   # FLM_QUALITY_REC: n_pix, sum Y, sum Y*Y, n_lap, sum L, sum L*L, dark, bright
+POSE_REC = 18     # FLM_POSE_REC: R row by row, s, mx, my, rms, cnt, ok, yaw, pitch, roll
 DECODE_ALL, DECODE_TOPN = 0, 1
 NORM_SUB_MEAN, NORM_SUB_AND_DIVIDE, NORM_DIVIDE = 0, 1, 2
 ABI_VERSION = 2
@@ -51,6 +52,7 @@ EXPORTS = [
     "flm_track_assoc_opts_init", "flm_track_associate", "flm_track_associate_streams",
     "flm_quality_opts_init", "flm_face_quality", "flm_best_opts_init", "flm_track_best_update",
     "flm_track_gather_streams", "flm_track_step_rows", "flm_track_best_update_rows", "flm_track_gather_live",
+    "flm_pose_opts_init", "flm_head_pose",
 ]
 
 
@@ -179,6 +181,20 @@ class BestOpts(C.Structure):
         load().flm_best_opts_init(C.byref(o))
         o.sharp_ref = float(sharp_ref)
         o.min_exposed = float(min_exposed)
+        return o
+
+
+class PoseOpts(C.Structure):
+    """flm_pose_opts: when flm_head_pose accepts a fit and when a face counts as frontal (include/flm.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("min_volume", C.c_double),
+                ("min_frontal", C.c_double)]
+
+    @classmethod
+    def make(cls, min_volume=1e-6, min_frontal=0.0):
+        o = cls()
+        load().flm_pose_opts_init(C.byref(o))
+        o.min_volume = float(min_volume)
+        o.min_frontal = float(min_frontal)
         return o
 
 
@@ -351,6 +367,10 @@ def _declare(lib):
                                                C.POINTER(BestOpts), vp, i, vp, vp, vp, vp, vp, vp, vp]
     lib.flm_track_gather_live.restype = i
     lib.flm_track_gather_live.argtypes = [vp, vp, i, i, i, i, i, vp, vp, d] + [vp] * 14
+    lib.flm_pose_opts_init.restype = None
+    lib.flm_pose_opts_init.argtypes = [C.POINTER(PoseOpts)]
+    lib.flm_head_pose.restype = i
+    lib.flm_head_pose.argtypes = [vp, vp, sz, vp, sz, i, i, vp, vp, i, C.POINTER(PoseOpts), vp, i, vp, vp]
 
 
 def load():

@@ -1237,3 +1237,137 @@ def track_best_update_rows_device(faces, rec, lm, slot, best_q_c, best_q, galler
     return _track_best_update(faces, rec, lm, best_q_c, best_q, gallery, best_frame, frame_id, status_rows, reset_c, weights,
                               factor, m, opts, best_m, best_lm, best_rec, rows=True, slot=slot,
                               names=("N", "status_rows", "reset_c", "best_q_c", "best_q"))
+
+
+# ---- head pose: where a face looks, from its landmarks (include/flm.h, "head pose") -----------------------------------
+POSE_REC = _lib.POSE_REC
+
+
+class HeadModel:
+    """A rigid 3-D model of a face for flm_head_pose: `indices`, P distinct landmark numbers, and `points` float64 [P,3],
+    their coordinates in the model frame -- X to the image's right, Y down, Z away from the camera, any unit -- with
+    4 <= P <= 256.  The points must not be coplanar (the fit reports a coplanar set as not ok).  The two tensors are
+    uploaded once per device and cached."""
+
+    def __init__(self, indices, points):
+        idx = np.asarray(indices)
+        xyz = np.asarray(points, np.float64)
+        if idx.ndim != 1 or idx.dtype.kind not in "iu" or xyz.shape != (idx.shape[0], 3):
+            raise ValueError("a head model is P integer landmark indices and float64 [P,3] points")
+        if not 4 <= idx.shape[0] <= 256:
+            raise ValueError("a head model has 4 to 256 points (got %d)" % idx.shape[0])
+        if idx.size and (idx.min() < 0 or idx.max() >= 2 ** 31):
+            raise ValueError("a landmark index must be in [0, 2^31)")
+        if len(set(int(v) for v in idx)) != idx.shape[0]:
+            raise ValueError("the landmark indices of a head model must be distinct")
+        if not np.isfinite(xyz).all():
+            raise ValueError("the points of a head model must be finite")
+        self.indices = np.ascontiguousarray(idx, np.int32)
+        self.points = np.ascontiguousarray(xyz)
+        self._dev = {}
+
+    @classmethod
+    def default(cls, n_landmarks):
+        """The six-point model of the 68-landmark layout: nose tip, chin, the outer eye corners, the mouth corners."""
+        if int(n_landmarks) != 68:
+            raise ValueError("the default head model is defined for 68 landmarks; pass an alignment.HeadModel for %d"
+                             % int(n_landmarks))
+        return cls([30, 8, 36, 45, 48, 54],
+                   [[0.0, 0.0, 0.0], [0.0, 330.0, 65.0], [-225.0, -170.0, 135.0], [225.0, -170.0, 135.0],
+                    [-150.0, 150.0, 125.0], [150.0, 150.0, 125.0]])
+
+    def __len__(self):
+        return int(self.indices.shape[0])
+
+    def tensors(self, device):
+        """(indices int32 [P], points float64 [P,3]) on `device`."""
+        import torch
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = (torch.from_numpy(self.indices).to(device), torch.from_numpy(self.points).to(device))
+        return self._dev[key]
+
+    def __repr__(self):
+        return "HeadModel(%d points)" % len(self)
+
+
+class HeadPose:
+    """The options of flm_head_pose (include/flm.h): `model`, a HeadModel (None: HeadModel.default of the landmark count
+    at hand); min_volume: the least normalised volume of the participating model points at which a fit counts (0 for
+    coplanar points, at most 1); min_frontal in [0, 1]: a face whose R[2][2] -- the cosine between its normal and the
+    optical axis -- lies below it gets a best-shot factor of 0."""
+
+    def __init__(self, model=None, min_volume=1e-6, min_frontal=0.0):
+        if model is not None and not isinstance(model, HeadModel):
+            raise ValueError("model must be None or an alignment.HeadModel (got %r)" % (model,))
+        min_volume, min_frontal = float(min_volume), float(min_frontal)
+        if not min_volume >= 0.0:
+            raise ValueError("min_volume must be >= 0 (got %r)" % min_volume)
+        if not 0.0 <= min_frontal <= 1.0:
+            raise ValueError("min_frontal must be in [0, 1] (got %r)" % min_frontal)
+        self.model, self.min_volume, self.min_frontal = model, min_volume, min_frontal
+
+    def model_for(self, n_landmarks):
+        return self.model if self.model is not None else HeadModel.default(n_landmarks)
+
+    def struct(self):
+        return _lib.PoseOpts.make(self.min_volume, self.min_frontal)
+
+    def __repr__(self):
+        return "HeadPose(model=%r, min_volume=%r, min_frontal=%r)" % (self.model, self.min_volume, self.min_frontal)
+
+
+def _check_span_overlap(a, b, what):
+    """`_check_overlap` for views: the bytes from a view's first element to its last count, gaps included."""
+    def span(t):
+        last = sum((int(n) - 1) * int(st) for n, st in zip(t.shape, t.stride()))
+        return t.data_ptr(), t.data_ptr() + (last + 1) * t.element_size()
+    if a is None or b is None or not a.numel() or not b.numel():
+        return
+    (a0, a1), (b0, b1) = span(a), span(b)
+    if a0 < b1 and b0 < a1:
+        raise ValueError("%s must be two buffers that do not overlap" % what)
+
+
+def head_pose_device(lm, model, weights=None, opts=None, slot=None, out=None, factor_out=None):
+    """The head pose of N faces from their landmarks, in one launch (flm_head_pose; include/flm.h states it line by line).
+
+    lm: CUDA float64 [N,C,2] and `weights` None or CUDA float64 [N,C] (both may be views of a landmark record tensor, read
+    in place); model: a `HeadModel`; opts: None or a `HeadPose` (its own model is not read here).  slot: None -- `out` is
+    float64 [N,18] and row r writes record r -- or CUDA int32 [N]: `out`, required, is float64 [n_slots,18], a row
+    writes at its slot, an inert row (slot outside [0, n_slots)) writes nothing and a slot no row names keeps its bits.
+    factor_out: None or CUDA float64 [N], written by row: R[2][2] of a fit that is ok and at least min_frontal, else 0.
+    Returns `out`: {R row by row, s, mx, my, rms, count, ok, yaw, pitch, roll} per face."""
+    import torch
+    if not isinstance(model, HeadModel):
+        raise ValueError("model must be an alignment.HeadModel (got %r)" % (model,))
+    if opts is None:
+        opts = HeadPose()
+    elif not isinstance(opts, HeadPose):
+        raise ValueError("opts must be None or a HeadPose (got %r)" % (opts,))
+    lm, ls = _strided_points(lm)
+    n, c = int(lm.shape[0]), int(lm.shape[1])
+    weights, wst = _weights_arg(weights, n, c)
+    if slot is None:
+        out = _out(out, torch.float64, (n, POSE_REC), "out", lm.device)
+        n_slots = 0
+    else:
+        _check_out(slot, torch.int32, (n,), "slot")
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.dim() != 2 or int(out.shape[1]) != POSE_REC
+                or not out.is_cuda or not out.is_contiguous() or not 1 <= int(out.shape[0]) <= 65535):
+            raise ValueError("with slot, out must be a contiguous CUDA float64 [n_slots,%d] tensor of 1 to 65535 slots"
+                             % POSE_REC)
+        n_slots = int(out.shape[0])
+    if factor_out is not None:
+        _check_out(factor_out, torch.float64, (n,), "factor_out")
+    for a, what in ((lm, "lm"), (weights, "weights"), (slot, "slot")):
+        _check_span_overlap(a, out, "%s and out" % what)
+        _check_span_overlap(a, factor_out, "%s and factor_out" % what)
+    _check_span_overlap(out, factor_out, "out and factor_out")
+    if n and c:
+        idx, xyz = model.tensors(lm.device)
+        co = opts.struct()
+        _lib.check(_lib.load().flm_head_pose(_lib.stream_ptr(), _lib.ptr(lm), ls, _ptr(weights), wst, n, c, _lib.ptr(idx),
+                                             _lib.ptr(xyz), len(model), _lib.C.byref(co), _ptr(slot), n_slots,
+                                             _lib.ptr(out), _ptr(factor_out)), "flm_head_pose")
+    return out

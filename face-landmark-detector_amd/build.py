@@ -39,6 +39,7 @@ SOURCES = [
     "flm_track.hip",
     "flm_track_assoc.hip",
     "flm_quality.hip",
+    "flm_pose.hip",
     "flm_mobile.hip",
 ]
 # -ffp-contract=off: only the fma() calls written in the sources fuse, so the arithmetic of the

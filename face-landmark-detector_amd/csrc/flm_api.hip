@@ -1640,4 +1640,86 @@ int flm_track_best_update_rows(flm_stream_t stream, const void* faces, size_t fa
                                   gallery, best_frame, best_m, best_lm, best_rec);
 }
 
+// ---- head pose (flm_pose.hip) ---------------------------------------------------------------------------------------
+
+void flm_pose_opts_init(flm_pose_opts* opts) {
+  if (!opts) return;
+  opts->struct_size = (uint32_t)sizeof(flm_pose_opts);
+  opts->reserved = 0;
+  opts->min_volume = 1e-6;
+  opts->min_frontal = 0.0;
+}
+
+int flm_head_pose(flm_stream_t stream, const double* lm, size_t lm_stride, const double* wt, size_t w_stride, int n, int c,
+                  const int32_t* idx, const double* xyz, int p, const flm_pose_opts* opts, const int32_t* slot,
+                  int n_slots, double* pose, double* factor) {
+  const char* who = "flm_head_pose";
+  if (!lm || !idx || !xyz || !pose) {
+    set_error("%s: null argument", who);  // (w, opts, slot and factor_out are optional)
+    return FLM_ERR_ARG;
+  }
+  flm_pose_opts defaults;
+  flm_pose_opts_init(&defaults);
+  if (!opts) opts = &defaults;
+  if (opts->struct_size < sizeof(flm_pose_opts)) {
+    set_error("%s: flm_pose_opts struct_size %u is smaller than this library's %zu (initialise with "
+              "flm_pose_opts_init)", who, opts->struct_size, sizeof(flm_pose_opts));
+    return FLM_ERR_ARG;
+  }
+  if (opts->reserved != 0) {
+    set_error("%s: flm_pose_opts reserved=%u, must be 0", who, opts->reserved);
+    return FLM_ERR_ARG;
+  }
+  if (!(opts->min_volume >= 0.0)) {
+    set_error("%s: min_volume=%g, needs min_volume >= 0", who, opts->min_volume);
+    return FLM_ERR_ARG;
+  }
+  if (!(opts->min_frontal >= 0.0 && opts->min_frontal <= 1.0)) {
+    set_error("%s: min_frontal=%g, needs 0 <= min_frontal <= 1", who, opts->min_frontal);
+    return FLM_ERR_ARG;
+  }
+  if (n < 1 || n > 65535) {
+    set_error("%s: n=%d, needs 1 <= n <= 65535", who, n);
+    return FLM_ERR_SHAPE;
+  }
+  if (c < 1 || c > 1024) {
+    set_error("%s: c=%d, needs 1 <= c <= 1024", who, c);
+    return FLM_ERR_SHAPE;
+  }
+  if (p < 4 || p > 256) {
+    set_error("%s: p=%d, needs 4 <= p <= 256", who, p);
+    return FLM_ERR_SHAPE;
+  }
+  if (lm_stride < 2 || (wt && w_stride < 1)) {
+    set_error("%s: lm_stride=%zu, w_stride=%zu, needs lm_stride >= 2 and w_stride >= 1", who, lm_stride, w_stride);
+    return FLM_ERR_SHAPE;
+  }
+  if (slot && (n_slots < 1 || n_slots > 65535)) {
+    set_error("%s: n_slots=%d, needs 1 <= n_slots <= 65535", who, n_slots);
+    return FLM_ERR_SHAPE;
+  }
+  const size_t last = (size_t)n * c - 1;  // the last landmark read
+  const struct { const void* p; size_t bytes; const char* name; } in[] = {
+      {lm, (last * lm_stride + 2) * sizeof(double), "lm_dev"},
+      {wt, wt ? (last * w_stride + 1) * sizeof(double) : 0, "w_dev"},
+      {idx, (size_t)p * sizeof(int32_t), "idx_dev"},
+      {xyz, (size_t)p * 3 * sizeof(double), "xyz_dev"},
+      {slot, slot ? (size_t)n * sizeof(int32_t) : 0, "slot_dev"}};
+  const size_t pose_bytes = (size_t)(slot ? n_slots : n) * FLM_POSE_REC * sizeof(double);
+  const size_t factor_bytes = factor ? (size_t)n * sizeof(double) : 0;
+  for (const auto& a : in) {
+    if (!a.p) continue;
+    if (ranges_overlap(pose, pose_bytes, a.p, a.bytes) || (factor && ranges_overlap(factor, factor_bytes, a.p, a.bytes))) {
+      set_error("%s: pose_dev or factor_out overlaps %s", who, a.name);
+      return FLM_ERR_ARG;
+    }
+  }
+  if (factor && ranges_overlap(pose, pose_bytes, factor, factor_bytes)) {
+    set_error("%s: pose_dev and factor_out overlap", who);
+    return FLM_ERR_ARG;
+  }
+  return launch_head_pose(static_cast<hipStream_t>(stream), lm, lm_stride, wt, w_stride, n, c, idx, xyz, p, opts, slot,
+                          n_slots, pose, factor);
+}
+
 }  // extern "C"

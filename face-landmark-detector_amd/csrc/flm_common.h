@@ -337,6 +337,11 @@ int launch_track_best_update(hipStream_t s, const void* faces, size_t face_bytes
                              const double* best_q_in, double* best_q_out, void* gallery, int64_t* best_frame, float* best_m,
                              double* best_lm, int64_t* best_rec);
 
+// head pose (flm_pose.hip); pointers, the option struct, sizes, strides and overlaps have been checked by the caller
+int launch_head_pose(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride, int n, int c,
+                     const int32_t* idx, const double* xyz, int p, const flm_pose_opts* opts,
+                     const int32_t* slot /*null: row r writes record r*/, int n_slots, double* pose, double* factor);
+
 // Bijective XCD-aware remap of a 1-D grid: blocks that the dispatcher deals to the same XCD
 // (b % 8) receive consecutive logical ids, so neighbours in logical order share an L2.
 __device__ __forceinline__ int xcd_remap(int b, int nblk) {

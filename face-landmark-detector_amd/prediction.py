@@ -558,6 +558,46 @@ def face_quality(faces, aligned_format=None):
     return (rec.cpu().numpy(), sc.cpu().numpy()) if numpy_io else (rec, sc)
 
 
+def head_pose(landmarks, weights=None, pose=None):
+    """Where every face looks, from its landmarks (alignment.head_pose_device: a scaled-orthographic fit of a rigid 3-D
+    face model, one launch).  landmarks: float64 [N,C,2] in any pixel unit, (-1,-1) for a rejected point; weights: None
+    or float64 [N,C]; both numpy arrays (one upload, one download) or CUDA tensors (nothing leaves the device; views of a
+    landmark record tensor are read in place).  pose: None or an `alignment.HeadPose`; without a model of its own the
+    default one is used, which exists for 68 landmarks.  Returns a dict of the kind of `landmarks`, every entry a view
+    of "record" float64 [N,18]: "R" [N,3,3] (model frame -> camera frame; the identity for a face that looks straight
+    into the camera), "scale" [N] (pixels per model unit), "centre" [N,2] (the weighted mean of the landmarks used),
+    "rms" [N] (the fit's residual in pixels), "count" [N], "ok" [N] (1.0 or 0.0) and "angles" [N,3] (yaw, pitch, roll in
+    radians, R = Rz(roll) Rx(pitch) Ry(yaw)).  A face whose fit is not ok -- fewer than four usable model points, or
+    coplanar ones -- has the identity, scale 0, centre (-1,-1) and angles 0."""
+    import torch
+    if pose is None:
+        pose = alignment.HeadPose()
+    elif not isinstance(pose, alignment.HeadPose):
+        raise ValueError("pose must be None or an alignment.HeadPose (got %r)" % (pose,))
+    numpy_io = not isinstance(landmarks, torch.Tensor)
+    if numpy_io:
+        lm_np = np.ascontiguousarray(landmarks, np.float64)
+        if lm_np.ndim != 3 or lm_np.shape[2] != 2:
+            raise ValueError("landmarks must be float64 [N,C,2]")
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, np.float64)
+            if weights.shape != lm_np.shape[:2]:
+                raise ValueError("weights must be float64 [%d,%d]" % lm_np.shape[:2])
+    elif landmarks.dim() != 3:
+        raise ValueError("landmarks must be float64 [N,C,2]")
+    model = pose.model_for(int(landmarks.shape[1]))
+    if numpy_io:
+        dev = _lib.require_gpu()
+        landmarks = torch.from_numpy(lm_np).to(dev)
+        weights = None if weights is None else torch.from_numpy(weights).to(dev)
+    rec = alignment.head_pose_device(landmarks, model, weights=weights, opts=pose)
+    if numpy_io:
+        rec = rec.cpu().numpy()
+    n = int(rec.shape[0])
+    return dict(record=rec, R=rec[:, :9].reshape(n, 3, 3), scale=rec[:, 9], centre=rec[:, 10:12], rms=rec[:, 12],
+                count=rec[:, 13], ok=rec[:, 14], angles=rec[:, 15:18])
+
+
 # ---- tracking: faces followed across frames from their own landmarks ---------------------------------------------------
 class FaceTracker:
     """Faces followed across the frames of a stream on the device: the landmarks of frame t place the crop of frame t+1.
@@ -592,13 +632,25 @@ class FaceTracker:
     code, launch for launch.  `step_active` steps only the streams that delivered a frame, each on its own `dt`, and
     leaves every other stream's state untouched; `step_live` steps only the slots that hold a face, at most a `budget`
     of them, and leaves every other slot untouched (the tracker then also owns `live_counts`, `live_cursor` and, with
-    `smooth`, `slot_age`)."""
+    `smooth`, `slot_age`).  pose: None, True (the defaults) or an `alignment.HeadPose`: after the step call every step
+    fits the head pose of its faces (alignment.head_pose_device, one more launch) to the landmarks the step returns --
+    the smoothed ones with `smooth` -- weighted by the scores with weights="score"; the tracker then owns `pose` float64
+    [capacity,18], one record per slot ({R row by row, s, mx, my, rms, count, ok, yaw, pitch, roll}; the not-ok record
+    of an empty face until a step writes it).  `step` writes every slot, `step_active` and `step_live` the slots they
+    serve; every other slot keeps its bits.  With `best_shot` as well, the frontality of the pose (R[2][2], or 0 below
+    the `min_frontal` of the HeadPose, or for a fit that is not ok) multiplies the quality of the face.  The pose of a
+    kept best shot is not stored: it is `head_pose(best_landmarks)`.  A model with other than 68 landmarks needs a
+    HeadPose with a model of its own."""
 
     def __init__(self, model, frame_hw, capacity, out_size=(112, 112), template=None, crop_template=None, n_points=4,
                  thresh=0.0, weights=None, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"),
                  crop_samples=1, samples=1, aligned_format=None, frame_format=None, smooth=None, associate=None,
-                 best_shot=None, streams=1):
+                 best_shot=None, streams=1, pose=None):
         import torch
+        if pose is True:
+            pose = alignment.HeadPose()
+        if pose is not None and not isinstance(pose, alignment.HeadPose):
+            raise ValueError("pose must be None, True or an alignment.HeadPose (got %r)" % (pose,))
         if best_shot is True:
             best_shot = alignment.BestShot()
         if best_shot is not None and not isinstance(best_shot, alignment.BestShot):
@@ -650,6 +702,8 @@ class FaceTracker:
         self.associate = associate
         self.streams, self.slots_per_stream = int(streams), capacity // int(streams)
         self.best_shot, self.gallery, self._steps = best_shot, None, 0
+        self.head_pose, self.pose = pose, None
+        self._head_model = None if pose is None else pose.model_for(c)
         self._ws_active = None   # the forward workspace of step_active (_active_workspace)
         self._waiting = False    # step_live has run below capacity: slot_age may hold a wait (_served)
         self._crop_format = alignment.AlignedFormat("nhwc", "uint8")
@@ -687,6 +741,10 @@ class FaceTracker:
             self.best_rec = torch.zeros((n, alignment.QUALITY_REC), dtype=torch.int64, device=dev)
             self._quality_rec = torch.zeros_like(self.best_rec)
             self._best_reset = torch.zeros((n,), dtype=torch.int32, device=dev)
+        if self.head_pose is not None:  # the not-ok record of a face without landmarks
+            empty = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, -1.0, -1.0] + [0.0] * 6
+            self.pose = torch.tensor(empty, dtype=torch.float64, device=dev).repeat(n, 1).contiguous()
+            self._pose_factor = torch.zeros((n,), dtype=torch.float64, device=dev) if self.best_shot is not None else None
 
     def seed(self, slots, boxes, stream=None):
         """Start (or restart) the tracks `slots` from the detector boxes `boxes` (x0,y0,x1,y1), one per slot: the host
@@ -893,7 +951,8 @@ class FaceTracker:
 
     def _sequence(self, ring, src, step, best_update, workspace, frame_id, quality_out=None):
         """The step sequence, stated once for `step` and `step_active`: the uint8 crop warp -> model.forward_device ->
-        (lm, wd) -> the step call -> the aligned warp -> with best_shot, the quality call and the best update.
+        (lm, wd) -> the step call -> with pose, the head-pose call (at the rows' slots where src has a "slot") -> the
+        aligned warp -> with best_shot, the quality call and the best update (with pose, times its factor).
         src: where the matrices ("m"), boxes and ring slots ("frame_index") of the faces are read -- the state itself or
         the snapshot; step, best_update: the caller's wrapper of the two, with what only that wrapper takes bound;
         workspace(batch, mode): the forward workspace, or None for the model's cached ones.  Returns (aligned, m_align,
@@ -911,6 +970,12 @@ class FaceTracker:
                        frame_hw=self.frame_hw, tmpl_crop=self.crop_template, tmpl_align=self.template, weights=wd,
                        **self.limits, **filt)
         lm_frame, m_align, status = stepped[0], stepped[1], stepped[-1]
+        factor = {}
+        if self.head_pose is not None:
+            if self.best_shot is not None:
+                factor = dict(factor=self._pose_factor[:int(lm_frame.shape[0])])
+            alignment.head_pose_device(lm_frame, self._head_model, weights=wd, opts=self.head_pose, slot=src.get("slot"),
+                                       out=self.pose, factor_out=factor.get("factor"))
         aligned = alignment.warp_frames_device(ring, m_align, self.out_size[0], self.out_size[1], samples=self.samples,
                                                fmt=self.aligned_format, **where)
         self._steps += 1
@@ -918,7 +983,7 @@ class FaceTracker:
             rec = alignment.face_quality_device(aligned, self.aligned_format, self.best_shot.quality, out=quality_out)
             best_update(aligned, rec, lm_frame, status, gallery=self.gallery, best_frame=self.best_frame, frame_id=frame_id,
                         weights=wd, m=m_align, opts=self.best_shot, best_m=self.best_M, best_lm=self.best_landmarks,
-                        best_rec=self.best_rec)
+                        best_rec=self.best_rec, **factor)
         return aligned, m_align, lm_frame, status
 
     def step(self, ring, frame_index, dt=None, frame_id=None):

@@ -1133,6 +1133,68 @@ int flm_track_best_update_rows(flm_stream_t stream, const void* faces_dev, size_
                                int64_t* best_frame_dev /*[n_slots]*/, float* best_m_dev /*[n_slots,2,3] or NULL*/,
                                double* best_lm_dev /*[n_slots,C,2] or NULL*/, int64_t* best_rec_dev /*[n_slots,8] or NULL*/);
 
+/* ---- head pose: where a face looks, from its landmarks ------------------------------------------------------------------
+ * flm_head_pose: a scaled-orthographic pose (the linear step of POS: DeMenthon, Davis 1995) of every face from its 2-D
+ * landmarks and a rigid 3-D model of P points, in ONE launch (a workgroup of one wave per row), no workspace, no
+ * allocation, no atomics, no synchronisation.  It produces the `factor_dev` of flm_track_best_update.
+ * Model frame: X to the image's right, Y down, Z away from the camera; a face looking straight into the camera has
+ * R = identity.  Model point p names landmark idx_dev[p] and has the coordinates X[p] = xyz_dev[3p .. 3p+2] (any unit).
+ * Landmarks and weights are read at element strides exactly as flm_similarity_from_landmarks_weighted reads them: point
+ * i of row r is the two doubles at lm_dev + (r*c + i)*lm_stride, its weight the double at w_dev + (r*c + i)*w_stride;
+ * w_dev == NULL: every weight is 1.  Model point p TAKES PART when 0 <= idx[p] < c, both coordinates of landmark idx[p]
+ * are >= 0 and its weight is > 0 (a NaN weight fails that test); cnt is the number of participating points.
+ * float64, one IEEE operation per written operator, in the written order, nothing fused; every sum runs sequentially from
+ * 0.0 in ascending model index p over the participating points:
+ *   W = sum w;  mX = sum(w*X)/W (three means);  mx = sum(w*x)/W;  my = sum(w*y)/W
+ *   X' = X - mX;  x' = x - mx;  y' = y - my
+ *   a00 = sum w*(X'0*X'0), likewise a01, a02, a11, a12, a22
+ *   bxk = sum w*(X'k*x');  byk = sum w*(X'k*y')                                              k = 0, 1, 2
+ *   c00 = a11*a22 - a12*a12;  c01 = a02*a12 - a01*a22;  c02 = a01*a12 - a02*a11
+ *   c11 = a00*a22 - a02*a02;  c12 = a01*a02 - a00*a12;  c22 = a00*a11 - a01*a01             (c symmetric: ckl = clk)
+ *   det = (a00*c00 + a01*c01) + a02*c02;   vol = det / ((a00*a11)*a22)
+ *   Ik = ((ck0*bx0 + ck1*bx1) + ck2*bx2) / det;  Jk likewise from by
+ *   nI = sqrt((I0*I0 + I1*I1) + I2*I2);  nJ likewise;  s = sqrt(nI*nJ)
+ *   i = I/nI;  j = J/nJ;  e = i + j;  f = i - j;  ne = |e|, nf = |f| (as nI);  e = e/ne;  f = f/nf
+ *   r1 = (e + f)*H;  r2 = (e - f)*H;  H = 0.7071067811865476
+ *   r3 = (r1[1]*r2[2] - r1[2]*r2[1], r1[2]*r2[0] - r1[0]*r2[2], r1[0]*r2[1] - r1[1]*r2[0]);   R = rows r1, r2, r3
+ *   ex = s*((r1[0]*X'0 + r1[1]*X'1) + r1[2]*X'2) - x';  ey likewise with r2 and y'
+ *   rms = sqrt(sum w*(ex*ex + ey*ey) / W)
+ *   yaw = atan2(-R[2][0], R[2][2]);  pitch = asin(min(max(R[2][1], -1), 1));  roll = atan2(-R[0][1], R[1][1])
+ * i.e. R = Rz(roll) Rx(pitch) Ry(yaw), and x = s*(r1 . X') + mx, y = s*(r2 . X') + my is the model in the image.  |i| =
+ * |j| = 1 makes e and f orthogonal, so the bisector step returns an orthonormal R in closed form: up to the three angles
+ * (the platform's atan2 and asin) the record is made of + - * / sqrt alone and is the same on every conforming machine.
+ * The fit is OK when cnt >= 4; W, det, nI, nJ, ne and nf are all finite and > 0; vol >= min_volume; and all of R, s and
+ * rms are finite.  By Hadamard's inequality vol lies in [0, 1] and does not depend on the model's unit; it is 0 for
+ * coplanar points.
+ * The record, FLM_POSE_REC doubles per face:
+ *   { R[0][0..2], R[1][0..2], R[2][0..2], s, mx, my, rms, (double)cnt, ok ? 1.0 : 0.0, yaw, pitch, roll }
+ * A fit that is not ok gives the identity for R, s = 0, mx = my = -1, rms = 0, the true cnt, ok = 0 and three angles of 0.
+ * Frontality is R[2][2], the cosine between the face's normal and the optical axis:
+ *   factor_out[r] = (ok && R[2][2] >= min_frontal) ? R[2][2] : 0.0
+ * Without slot_dev row r writes the record pose_dev[r].  With slot_dev int32 [N] the "rows" rules of the tracking section
+ * hold: a valid row writes its record at slot g = slot_dev[r] of pose_dev [n_slots,18], an inert row writes no record, a
+ * slot no row names keeps its bits.  factor_out is written by ROW in both cases -- where flm_track_best_update and
+ * flm_track_best_update_rows read factor_dev --, 0.0 for an inert row.
+ * Defaults (flm_pose_opts_init): min_volume = 1e-6 (the six points of a frontal face model give 0.9, their worst
+ * non-planar four 6e-3, four coplanar ones 0 up to rounding), min_frontal = 0.
+ * Errors, all found before anything is launched: a null lm_dev, idx_dev, xyz_dev or pose_dev (n_slots is not
+ * read without slot_dev), a struct_size smaller than this library's, a non-zero reserved, a min_volume or min_frontal that is NaN or
+ * negative, min_frontal > 1, or pose_dev or factor_out overlapping an input or each other -> FLM_ERR_ARG.  FLM_ERR_SHAPE,
+ * the limit named in flm_last_error(), unless 1 <= n <= 65535, 1 <= c <= 1024, 4 <= p <= 256, lm_stride >= 2, w_stride >= 1
+ * (with w_dev) and, with slot_dev, 1 <= n_slots <= 65535. */
+#define FLM_POSE_REC 18
+typedef struct flm_pose_opts {
+  uint32_t struct_size;  /* as flm_track_opts */
+  uint32_t reserved;     /* 0 */
+  double min_volume;     /* the least vol at which the model's participating points count as non-planar */
+  double min_frontal;    /* in [0, 1]: below this R[2][2] the factor is 0 */
+} flm_pose_opts;
+void flm_pose_opts_init(flm_pose_opts* opts);   /* min_volume = 1e-6, min_frontal = 0.0 */
+int flm_head_pose(flm_stream_t stream, const double* lm_dev, size_t lm_stride, const double* w_dev /*or NULL*/,
+                  size_t w_stride, int n, int c, const int32_t* idx_dev /*[P]*/, const double* xyz_dev /*[P,3]*/, int p,
+                  const flm_pose_opts* opts /*NULL = defaults*/, const int32_t* slot_dev /*[N] or NULL*/, int n_slots,
+                  double* pose_dev /*[N or n_slots,18]*/, double* factor_out /*[N] or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
