@@ -53,6 +53,7 @@ EXPORTS = [
     "flm_quality_opts_init", "flm_face_quality", "flm_best_opts_init", "flm_track_best_update",
     "flm_track_gather_streams", "flm_track_step_rows", "flm_track_best_update_rows", "flm_track_gather_live",
     "flm_pose_opts_init", "flm_head_pose",
+    "flm_exit_opts_init", "flm_track_retire",
 ]
 
 
@@ -195,6 +196,18 @@ class PoseOpts(C.Structure):
         load().flm_pose_opts_init(C.byref(o))
         o.min_volume = float(min_volume)
         o.min_frontal = float(min_frontal)
+        return o
+
+
+class ExitOpts(C.Structure):
+    """flm_exit_opts: which finished tracks flm_track_retire queues (include/flm.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("min_q", C.c_double)]
+
+    @classmethod
+    def make(cls, min_q=0.0):
+        o = cls()
+        load().flm_exit_opts_init(C.byref(o))
+        o.min_q = float(min_q)
         return o
 
 
@@ -371,6 +384,11 @@ def _declare(lib):
     lib.flm_pose_opts_init.argtypes = [C.POINTER(PoseOpts)]
     lib.flm_head_pose.restype = i
     lib.flm_head_pose.argtypes = [vp, vp, sz, vp, sz, i, i, vp, vp, i, C.POINTER(PoseOpts), vp, i, vp, vp]
+    lib.flm_exit_opts_init.restype = None
+    lib.flm_exit_opts_init.argtypes = [C.POINTER(ExitOpts)]
+    lib.flm_track_retire.restype = i
+    lib.flm_track_retire.argtypes = [vp, vp, vp, i, i, i, vp, vp, sz, vp, vp, vp, i, vp, C.c_int64, i, C.POINTER(ExitOpts),
+                                     vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp]
 
 
 def load():

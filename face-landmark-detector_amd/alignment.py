@@ -1371,3 +1371,123 @@ def head_pose_device(lm, model, weights=None, opts=None, slot=None, out=None, fa
                                              _lib.ptr(xyz), len(model), _lib.C.byref(co), _ptr(slot), n_slots,
                                              _lib.ptr(out), _ptr(factor_out)), "flm_head_pose")
     return out
+
+
+# ---- finished tracks: track ids and the exit queue of best shots (include/flm.h, flm_track_retire) ---------------------
+EXIT_META = 8   # FLM_EXIT_META: track_id, slot, born_frame, frame_id of the end, best_frame, end, seq, 0
+
+
+class TrackExits:
+    """The exit queue of a tracker (flm_track_retire; include/flm.h): a ring of `capacity` rows, 1 to 65535, one per
+    finished track, holding its best shot; min_q >= 0: a track whose best quality lies below it -- or that never had a
+    best shot -- is discarded and only counted."""
+
+    def __init__(self, capacity=256, min_q=0.0):
+        if isinstance(capacity, bool) or int(capacity) != capacity or not 1 <= int(capacity) <= 65535:
+            raise ValueError("capacity must be an integer in [1, 65535] (got %r)" % (capacity,))
+        min_q = float(min_q)
+        if not min_q >= 0.0:
+            raise ValueError("min_q must be >= 0 and not NaN (got %r)" % min_q)
+        self.capacity, self.min_q = int(capacity), min_q
+
+    def struct(self):
+        return _lib.ExitOpts.make(self.min_q)
+
+    def __repr__(self):
+        return "TrackExits(capacity=%r, min_q=%r)" % (self.capacity, self.min_q)
+
+
+def track_retire_device(boxes, status, frame_hw, best_q, gallery, best_frame, born, track_id, born_frame, head, x_faces,
+                        x_meta, x_q, exit_row, frame_id, flush=False, opts=None, best_m=None, best_lm=None, best_rec=None,
+                        x_m=None, x_lm=None, x_rec=None):
+    """Retire the tracks that have ended and name the ones that have begun, in two launches (flm_track_retire;
+    include/flm.h states it line by line).
+
+    Read: boxes CUDA int32 [K,4], status CUDA int32 [K], frame_hw; best_q CUDA float64 [K], gallery a contiguous CUDA
+    tensor of K faces (any format: copied as bytes), best_frame CUDA int64 [K]; best_m, best_lm, best_rec: None or CUDA
+    float32 [K,2,3], float64 [K,C,2], int64 [K,8], each together with x_m, x_lm, x_rec over the Q ring rows.  In/out:
+    born CUDA int32 [K] (non-zero: a track was started in the slot since the last call; cleared), track_id CUDA int64 [K]
+    (-1: no track), born_frame CUDA int64 [K], head CUDA int64 [4] = (seq, next_id, discarded, overrun).  Out: the ring
+    x_faces (Q faces of the gallery's dtype and face shape), x_meta CUDA int64 [Q,8], x_q CUDA float64 [Q]; exit_row CUDA
+    int32 [K]: -1 nothing ended, -2 discarded, -3 overrun, else the ring row.  frame_id: a host integer; flush: end every
+    held track; opts: None or a `TrackExits` (its capacity must be Q).  No two tensors may overlap.  Returns exit_row."""
+    import torch
+    if opts is None:
+        opts = TrackExits(capacity=int(x_meta.shape[0]) if isinstance(x_meta, torch.Tensor) and x_meta.dim() else 256)
+    elif not isinstance(opts, TrackExits):
+        raise ValueError("opts must be None or a TrackExits (got %r)" % (opts,))
+    frame_id = _frame_id(frame_id)
+    fh, fw = _sizes(frame_hw, "frame_hw")
+    if not isinstance(boxes, torch.Tensor) or boxes.dim() != 2 or not 1 <= int(boxes.shape[0]) <= 65535:
+        raise ValueError("boxes must be a contiguous CUDA int32 [K,4] tensor of 1 to 65535 slots")
+    k = int(boxes.shape[0])
+    _check_boxes(boxes, k)
+    if (not isinstance(gallery, torch.Tensor) or gallery.dim() < 1 or int(gallery.shape[0]) != k or not gallery.is_cuda
+            or not gallery.is_contiguous() or gallery.numel() < k):
+        raise ValueError("gallery must be a contiguous CUDA tensor of %d faces" % k)
+    if (not isinstance(x_faces, torch.Tensor) or x_faces.dtype != gallery.dtype or x_faces.dim() != gallery.dim()
+            or x_faces.shape[1:] != gallery.shape[1:] or not x_faces.is_cuda or not x_faces.is_contiguous()):
+        raise ValueError("x_faces must be a contiguous CUDA tensor of the dtype and face shape of gallery")
+    q = int(x_faces.shape[0])
+    if not 1 <= q <= 65535 or q != opts.capacity:
+        raise ValueError("the ring must have the %d rows of opts, 1 to 65535 (x_faces has %d)" % (opts.capacity, q))
+    _check_out(status, torch.int32, (k,), "status")
+    _check_out(best_q, torch.float64, (k,), "best_q")
+    _check_out(best_frame, torch.int64, (k,), "best_frame")
+    _check_out(born, torch.int32, (k,), "born")
+    _check_out(track_id, torch.int64, (k,), "track_id")
+    _check_out(born_frame, torch.int64, (k,), "born_frame")
+    _check_out(head, torch.int64, (4,), "head")
+    _check_out(x_meta, torch.int64, (q, EXIT_META), "x_meta")
+    _check_out(x_q, torch.float64, (q,), "x_q")
+    _check_out(exit_row, torch.int32, (k,), "exit_row")
+    for a, b, what in ((best_m, x_m, "best_m and x_m"), (best_lm, x_lm, "best_lm and x_lm"), (best_rec, x_rec, "best_rec and x_rec")):
+        if (a is None) != (b is None):
+            raise ValueError("%s go together: both or neither" % what)
+    c = 1
+    if best_m is not None:
+        _check_matrices(best_m, k, "best_m")
+        _check_matrices(x_m, q, "x_m")
+    if best_lm is not None:
+        if not isinstance(best_lm, torch.Tensor) or best_lm.dim() != 3 or not 1 <= int(best_lm.shape[1]) <= 1024:
+            raise ValueError("best_lm must be a contiguous CUDA float64 [%d,C,2] tensor, 1 <= C <= 1024" % k)
+        c = int(best_lm.shape[1])
+        _check_out(best_lm, torch.float64, (k, c, 2), "best_lm")
+        _check_out(x_lm, torch.float64, (q, c, 2), "x_lm")
+    if best_rec is not None:
+        _check_out(best_rec, torch.int64, (k, QUALITY_REC), "best_rec")
+        _check_out(x_rec, torch.int64, (q, QUALITY_REC), "x_rec")
+    named = [(boxes, "boxes"), (status, "status"), (best_q, "best_q"), (gallery, "gallery"), (best_frame, "best_frame"),
+             (best_m, "best_m"), (best_lm, "best_lm"), (best_rec, "best_rec"), (born, "born"), (track_id, "track_id"),
+             (born_frame, "born_frame"), (head, "head"), (x_faces, "x_faces"), (x_meta, "x_meta"), (x_q, "x_q"), (x_m, "x_m"),
+             (x_lm, "x_lm"), (x_rec, "x_rec"), (exit_row, "exit_row")]
+    spans = sorted((t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), name) for t, name in named if t is not None)
+    for (_, end, an), (start, _, bn) in zip(spans, spans[1:]):         # sorted by address: neighbours are enough
+        if start < end:
+            raise ValueError("%s and %s must be two buffers that do not overlap" % (an, bn))
+    co = opts.struct()
+    _lib.check(_lib.load().flm_track_retire(
+        _lib.stream_ptr(), _lib.ptr(boxes), _lib.ptr(status), k, fh, fw, _lib.ptr(best_q), _lib.ptr(gallery),
+        gallery.numel() // k * gallery.element_size(), _lib.ptr(best_frame), _ptr(best_m), _ptr(best_lm), c, _ptr(best_rec),
+        frame_id, 1 if flush else 0, _lib.C.byref(co), _lib.ptr(born), _lib.ptr(track_id), _lib.ptr(born_frame),
+        _lib.ptr(head), q, _lib.ptr(x_faces), _lib.ptr(x_meta), _lib.ptr(x_q), _ptr(x_m), _ptr(x_lm), _ptr(x_rec),
+        _lib.ptr(exit_row)), "flm_track_retire")
+    return exit_row
+
+
+def exit_rows(seq, cursor, capacity):
+    """The consumer's side of the exit ring, on the host: `seq` is head[0] as the consumer downloaded it, `cursor` the
+    sequence number it has read up to (0 at the start; afterwards the `seq` of its previous look), `capacity` the ring's
+    rows.  Returns (rows, lost): the ring rows of the exits that are new and still in the ring, oldest first, as an int64
+    array, and how many new exits were overwritten before they were read (wrap-around).  The exit of sequence number s
+    lies in row s % capacity; the ring keeps the last `capacity` of them."""
+    for v, what in ((seq, "seq"), (cursor, "cursor"), (capacity, "capacity")):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError("%s must be an integer (got %r)" % (what, v))
+    seq, cursor, capacity = int(seq), int(cursor), int(capacity)
+    if not 1 <= capacity <= 65535:
+        raise ValueError("capacity must be in [1, 65535] (got %d)" % capacity)
+    if not 0 <= cursor <= seq:
+        raise ValueError("0 <= cursor <= seq is needed (got cursor %d, seq %d)" % (cursor, seq))
+    lost = max(seq - cursor - capacity, 0)
+    return np.arange(cursor + lost, seq, dtype=np.int64) % capacity, lost

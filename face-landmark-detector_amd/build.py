@@ -39,6 +39,7 @@ SOURCES = [
     "flm_track.hip",
     "flm_track_assoc.hip",
     "flm_quality.hip",
+    "flm_track_exit.hip",
     "flm_pose.hip",
     "flm_mobile.hip",
 ]

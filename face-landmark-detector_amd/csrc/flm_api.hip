@@ -1640,6 +1640,95 @@ int flm_track_best_update_rows(flm_stream_t stream, const void* faces, size_t fa
                                   gallery, best_frame, best_m, best_lm, best_rec);
 }
 
+// ---- finished tracks (flm_track_exit.hip) -----------------------------------------------------------------------------
+
+void flm_exit_opts_init(flm_exit_opts* opts) {
+  if (!opts) return;
+  opts->struct_size = (uint32_t)sizeof(flm_exit_opts);
+  opts->reserved = 0;
+  opts->min_q = 0.0;
+}
+
+int flm_track_retire(flm_stream_t stream, const int32_t* boxes, const int32_t* status, int k, int fh, int fw,
+                     const double* best_q, const void* gallery, size_t face_bytes, const int64_t* best_frame,
+                     const float* best_m, const double* best_lm, int c, const int64_t* best_rec, int64_t frame_id,
+                     int flush, const flm_exit_opts* opts, int32_t* born, int64_t* track_id, int64_t* born_frame,
+                     int64_t* head, int q, void* x_gallery, int64_t* x_meta, double* x_q, float* x_m, double* x_lm,
+                     int64_t* x_rec, int32_t* exit_row) {
+  const char* who = "flm_track_retire";
+  if (!boxes || !status || !best_q || !gallery || !best_frame || !born || !track_id || !born_frame || !head ||
+      !x_gallery || !x_meta || !x_q || !exit_row) {
+    set_error("%s: null argument", who);  // (opts and the three pairs best_m/x_m, best_lm/x_lm, best_rec/x_rec are optional)
+    return FLM_ERR_ARG;
+  }
+  if (!best_m != !x_m || !best_lm != !x_lm || !best_rec != !x_rec) {
+    set_error("%s: best_m_dev goes with x_m, best_lm_dev with x_lm and best_rec_dev with x_rec: both or neither", who);
+    return FLM_ERR_ARG;
+  }
+  flm_exit_opts defaults;
+  flm_exit_opts_init(&defaults);
+  if (!opts) opts = &defaults;
+  if (opts->struct_size < sizeof(flm_exit_opts)) {
+    set_error("%s: flm_exit_opts struct_size %u is smaller than this library's %zu (initialise with "
+              "flm_exit_opts_init)", who, opts->struct_size, sizeof(flm_exit_opts));
+    return FLM_ERR_ARG;
+  }
+  if (opts->reserved != 0) {
+    set_error("%s: flm_exit_opts reserved=%u, must be 0", who, opts->reserved);
+    return FLM_ERR_ARG;
+  }
+  if (!(opts->min_q >= 0.0)) {
+    set_error("%s: min_q=%g, needs min_q >= 0", who, opts->min_q);
+    return FLM_ERR_ARG;
+  }
+  if (k < 1 || k > 65535) {
+    set_error("%s: k=%d, needs 1 <= k <= 65535", who, k);
+    return FLM_ERR_SHAPE;
+  }
+  if (q < 1 || q > 65535) {
+    set_error("%s: q=%d, needs 1 <= q <= 65535", who, q);
+    return FLM_ERR_SHAPE;
+  }
+  if (c < 1 || c > 1024) {
+    set_error("%s: c=%d, needs 1 <= c <= 1024", who, c);
+    return FLM_ERR_SHAPE;
+  }
+  if (face_bytes < 1) {
+    set_error("%s: face_bytes=0, needs face_bytes >= 1", who);
+    return FLM_ERR_SHAPE;
+  }
+  if (fh < 1 || fw < 1) {
+    set_error("%s: frame %dx%d, needs fh, fw >= 1", who, fh, fw);
+    return FLM_ERR_SHAPE;
+  }
+  const size_t sk = (size_t)k, sq = (size_t)q, sc = (size_t)c;
+  const struct { const void* p; size_t bytes; const char* name; } bufs[] = {
+      {boxes, sk * 16, "boxes_dev"}, {status, sk * 4, "status_dev"}, {best_q, sk * 8, "best_q_dev"},
+      {gallery, sk * face_bytes, "gallery_dev"}, {best_frame, sk * 8, "best_frame_dev"}, {best_m, sk * 24, "best_m_dev"},
+      {best_lm, sk * sc * 16, "best_lm_dev"}, {best_rec, sk * FLM_QUALITY_REC * 8, "best_rec_dev"},
+      {born, sk * 4, "born_dev"}, {track_id, sk * 8, "track_id_dev"}, {born_frame, sk * 8, "born_frame_dev"},
+      {head, 4 * 8, "head_dev"}, {x_gallery, sq * face_bytes, "x_gallery"}, {x_meta, sq * FLM_EXIT_META * 8, "x_meta"},
+      {x_q, sq * 8, "x_q"}, {x_m, sq * 24, "x_m"}, {x_lm, sq * sc * 16, "x_lm"},
+      {x_rec, sq * FLM_QUALITY_REC * 8, "x_rec"}, {exit_row, sk * 4, "exit_row_dev"}};
+  const int nb = (int)(sizeof(bufs) / sizeof(bufs[0]));
+  for (int i = 0; i < nb; ++i)
+    for (int j = i + 1; j < nb; ++j)
+      if (bufs[i].p && bufs[j].p && ranges_overlap(bufs[i].p, bufs[i].bytes, bufs[j].p, bufs[j].bytes)) {
+        set_error("%s: %s and %s overlap (no two arguments may)", who, bufs[i].name, bufs[j].name);
+        return FLM_ERR_ARG;
+      }
+  TrackExitArgs g;
+  g.boxes = boxes; g.status = status; g.k = k; g.fh = fh; g.fw = fw; g.c = c; g.q = q;
+  g.face_bytes = face_bytes;
+  g.best_q = best_q; g.gallery = static_cast<const unsigned char*>(gallery); g.best_frame = best_frame;
+  g.best_m = best_m; g.best_lm = best_lm; g.best_rec = best_rec;
+  g.frame_id = frame_id; g.flush = flush; g.min_q = opts->min_q;
+  g.born = born; g.track_id = track_id; g.born_frame = born_frame; g.head = head;
+  g.x_gallery = static_cast<unsigned char*>(x_gallery); g.x_meta = x_meta; g.x_q = x_q;
+  g.x_m = x_m; g.x_lm = x_lm; g.x_rec = x_rec; g.exit_row = exit_row;
+  return launch_track_retire(static_cast<hipStream_t>(stream), g);
+}
+
 // ---- head pose (flm_pose.hip) ---------------------------------------------------------------------------------------
 
 void flm_pose_opts_init(flm_pose_opts* opts) {

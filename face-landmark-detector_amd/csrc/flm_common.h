@@ -337,6 +337,36 @@ int launch_track_best_update(hipStream_t s, const void* faces, size_t face_bytes
                              const double* best_q_in, double* best_q_out, void* gallery, int64_t* best_frame, float* best_m,
                              double* best_lm, int64_t* best_rec);
 
+// flm_track_retire's arguments under the names of include/flm.h (flm_track_exit.hip; both kernels take the struct as it
+// is); pointers, their pairing, the option struct, sizes and overlaps have been checked by the caller
+struct TrackExitArgs {
+  const int32_t* boxes;        // [K,4]
+  const int32_t* status;       // [K]
+  int k, fh, fw, c, q;
+  size_t face_bytes;
+  const double* best_q;        // [K]
+  const unsigned char* gallery;
+  const int64_t* best_frame;   // [K]
+  const float* best_m;         // [K,2,3] or null, with x_m
+  const double* best_lm;       // [K,C,2] or null, with x_lm
+  const int64_t* best_rec;     // [K,8] or null, with x_rec
+  int64_t frame_id;
+  int flush;
+  double min_q;
+  int32_t* born;               // [K] in/out
+  int64_t* track_id;           // [K] in/out
+  int64_t* born_frame;         // [K] in/out
+  int64_t* head;               // [4] in/out
+  unsigned char* x_gallery;    // [Q,face_bytes]
+  int64_t* x_meta;             // [Q,8]
+  double* x_q;                 // [Q]
+  float* x_m;
+  double* x_lm;
+  int64_t* x_rec;
+  int32_t* exit_row;           // [K]
+};
+int launch_track_retire(hipStream_t s, const TrackExitArgs& g);
+
 // head pose (flm_pose.hip); pointers, the option struct, sizes, strides and overlaps have been checked by the caller
 int launch_head_pose(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride, int n, int c,
                      const int32_t* idx, const double* xyz, int p, const flm_pose_opts* opts,

@@ -640,13 +640,35 @@ class FaceTracker:
     serve; every other slot keeps its bits.  With `best_shot` as well, the frontality of the pose (R[2][2], or 0 below
     the `min_frontal` of the HeadPose, or for a fit that is not ok) multiplies the quality of the face.  The pose of a
     kept best shot is not stored: it is `head_pose(best_landmarks)`.  A model with other than 68 landmarks needs a
-    HeadPose with a model of its own."""
+    HeadPose with a model of its own.  exits: None, a ring size Q or an `alignment.TrackExits`, for a tracker with
+    `best_shot`: the tracker then says who a slot is and that a track is over (alignment.track_retire_device, two more
+    launches first thing in `step`, `step_active` and `step_live`, over all slots whichever of them the tick serves).  It
+    owns `track_id` int64 [capacity] (-1: the slot holds no track; ids count up from 0 in the order the tracks began, by
+    ascending slot within a tick), `born_frame` int64 [capacity], `exit_row` int32 [capacity] (what the last retire did
+    with the slot: -1 nothing, -2 discarded, -3 overrun, else the ring row) and the exit ring of Q rows, one per finished
+    track and each delivered once: `exit_faces` in the aligned format, `exit_meta` int64 [Q,8] (track_id, slot,
+    born_frame, the frame_id of the tick that saw the end, best_frame, end, seq, 0; end = the status that lost the track,
+    -1 for a slot restarted before its end was seen, -2 for a flush), `exit_q`, `exit_M`, `exit_landmarks`, `exit_rec`,
+    and `exit_head` int64 [4] = (exits queued so far, ids given so far, tracks discarded for having no best shot of at
+    least min_q, exits overrun within one tick).  `exits()` hands them out, `alignment.exit_rows` turns a downloaded
+    `exit_head[0]` and the consumer's own cursor into the ring rows to read, and `retire(flush=True)` ends every held
+    track at the end of a video.  A track ends when its slot is found empty, or restarted, at the start of the next tick.
+    A reborn slot's `best()` row is the previous track's until that slot's first step (true without `exits` too); with
+    `exits` the previous track has been queued by then, and a track that ends before its slot was ever stepped has no
+    best shot of its own and is discarded (the retire call reads a best_q of -1 for such a slot).  Without `exits` the tracker makes no additional launch and no additional
+    allocation."""
 
     def __init__(self, model, frame_hw, capacity, out_size=(112, 112), template=None, crop_template=None, n_points=4,
                  thresh=0.0, weights=None, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"),
                  crop_samples=1, samples=1, aligned_format=None, frame_format=None, smooth=None, associate=None,
-                 best_shot=None, streams=1, pose=None):
+                 best_shot=None, streams=1, pose=None, exits=None):
         import torch
+        if exits is not None and not isinstance(exits, alignment.TrackExits):
+            if isinstance(exits, bool) or not isinstance(exits, (int, np.integer)):
+                raise ValueError("exits must be None, a ring size or an alignment.TrackExits (got %r)" % (exits,))
+            exits = alignment.TrackExits(capacity=int(exits))
+        if exits is not None and (best_shot is None or best_shot is False):
+            raise ValueError("exits needs best_shot: the exit queue holds the best shot of every finished track")
         if pose is True:
             pose = alignment.HeadPose()
         if pose is not None and not isinstance(pose, alignment.HeadPose):
@@ -703,6 +725,7 @@ class FaceTracker:
         self.streams, self.slots_per_stream = int(streams), capacity // int(streams)
         self.best_shot, self.gallery, self._steps = best_shot, None, 0
         self.head_pose, self.pose = pose, None
+        self.exit_opts, self.track_id = exits, None
         self._head_model = None if pose is None else pose.model_for(c)
         self._ws_active = None   # the forward workspace of step_active (_active_workspace)
         self._waiting = False    # step_live has run below capacity: slot_age may hold a wait (_served)
@@ -741,6 +764,22 @@ class FaceTracker:
             self.best_rec = torch.zeros((n, alignment.QUALITY_REC), dtype=torch.int64, device=dev)
             self._quality_rec = torch.zeros_like(self.best_rec)
             self._best_reset = torch.zeros((n,), dtype=torch.int32, device=dev)
+        if self.exit_opts is not None:  # -1: the slot holds no track; the ring starts empty
+            q = self.exit_opts.capacity
+            self.track_id = torch.full((n,), -1, dtype=torch.int64, device=dev)
+            self.born_frame = torch.full((n,), -1, dtype=torch.int64, device=dev)
+            self._born = torch.zeros((n,), dtype=torch.int32, device=dev)
+            self.exit_row = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            self.exit_head = torch.zeros((4,), dtype=torch.int64, device=dev)
+            self.exit_faces = torch.zeros(fmt.shape(q, *self.out_size), dtype=fmt.torch_dtype, device=dev)
+            self.exit_meta = torch.zeros((q, alignment.EXIT_META), dtype=torch.int64, device=dev)
+            self.exit_q = torch.full((q,), -1.0, dtype=torch.float64, device=dev)
+            self.exit_M = torch.zeros((q, 2, 3), dtype=torch.float32, device=dev)
+            self.exit_landmarks = torch.full((q, c, 2), -1.0, dtype=torch.float64, device=dev)
+            self.exit_rec = torch.zeros((q, alignment.QUALITY_REC), dtype=torch.int64, device=dev)
+            self._exit_stale = torch.zeros((n,), dtype=torch.bool, device=dev)   # best_q is an earlier track's (_retire)
+            self._exit_q_in = torch.full((n,), -1.0, dtype=torch.float64, device=dev)
+            self._no_best = torch.full((), -1.0, dtype=torch.float64, device=dev)
         if self.head_pose is not None:  # the not-ok record of a face without landmarks
             empty = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, -1.0, -1.0] + [0.0] * 6
             self.pose = torch.tensor(empty, dtype=torch.float64, device=dev).repeat(n, 1).contiguous()
@@ -779,6 +818,8 @@ class FaceTracker:
             self.filter_state.index_fill_(0, idx, -1.0)
         if self.best_shot is not None:
             self._best_reset.index_fill_(0, idx, 1)
+        if self.exit_opts is not None:
+            self._born.index_fill_(0, idx, 1)
 
     @staticmethod
     def _host_boxes(boxes, what):
@@ -803,7 +844,10 @@ class FaceTracker:
         """A birth forgets the slot's best with the next step; a restart is the same face and keeps it, and a skipped
         stream has slot_det == -1 and resets nothing."""
         if self.best_shot is not None:
-            self._best_reset.masked_fill_(was_empty & (slot_det >= 0), 1)
+            births = was_empty & (slot_det >= 0)
+            self._best_reset.masked_fill_(births, 1)
+            if self.exit_opts is not None:
+                self._born.masked_fill_(births, 1)
 
     def update(self, detections, n=None):
         """The boxes of a detector against the tracks, on the device (alignment.track_associate_device with the
@@ -1010,6 +1054,7 @@ class FaceTracker:
             if not 0 <= frame_index < nf:
                 raise ValueError("frame_index must name a ring slot in [0, %d)" % nf)
         self._state()
+        self._retire(frame_id)
         if self.streams == 1:
             self.frame_slots.fill_(frame_index)
 
@@ -1026,6 +1071,7 @@ class FaceTracker:
         if self.best_shot is not None:
             self.best_q, self._best_q_spare = self._best_q_spare, self.best_q
             self._best_reset.zero_()
+        self._retire_served()
         self._served()
         return res
 
@@ -1173,6 +1219,7 @@ class FaceTracker:
                     torch.empty((0, 2, 3), dtype=torch.float32, device=dev),
                     torch.empty((0, c, 2), dtype=torch.float64, device=dev),
                     torch.empty((0,), dtype=torch.int32, device=dev), torch.empty((0,), dtype=torch.int32, device=dev))
+        self._retire(frame_id)
         up = self._upload(dt_host, fi_host, act_host)
         dt_dev, frame_index, active = [b if a is None else a for a, b in zip(up, (dt_dev, frame_index, active))]
         best = self.best_shot is not None
@@ -1189,6 +1236,7 @@ class FaceTracker:
             functools.partial(alignment.track_step_rows_device, slot=snap["slot"], m_next=self.m_crop, boxes_next=self.boxes,
                               status=self.status, dt=dt_scalar if dt_dev is None else snap["dt"]),
             best_update, self._active_workspace, frame_id)
+        self._retire_served()
         self._served(snap["slot"])
         return res + (snap["slot"],)
 
@@ -1246,6 +1294,7 @@ class FaceTracker:
         fi_host = self._stream_frame_index(frame_index, nf, named)
         dt_host, dt_dev, dt_scalar = self._stream_dt(dt, range(s) if named is None else named)
         self._state()
+        self._retire(frame_id)
         up = self._upload(dt_host, fi_host, on_host)
         dt_dev, frame_index, active = [b if a is None else a for a, b in zip(up, (dt_dev, frame_index, active))]
         best, smooth = self.best_shot is not None, self.smooth is not None
@@ -1265,7 +1314,54 @@ class FaceTracker:
             functools.partial(alignment.track_step_rows_device, slot=snap["slot"], m_next=self.m_crop, boxes_next=self.boxes,
                               status=self.status, dt=snap.get("dt")),
             best_update, self._active_workspace, frame_id)
+        self._retire_served()
         return res + (snap["slot"],)
+
+    def _retire(self, frame_id, flush=False):
+        """The retire call of a tracker with `exits`, over all slots: before the gather and before anything can overwrite
+        a gallery row.  `_exit_stale` marks the slots whose track no step has served since a retire named it: their best_q
+        is still the previous track's, which was queued at that birth, so the call reads -1 for them -- a retire that
+        sees a birth sets the mark, the step that serves the slot's pending best-shot reset clears it (_retire_served).
+        Launches nothing for a tracker without `exits`."""
+        import torch
+        if self.exit_opts is None:
+            return
+        torch.where(self._exit_stale, self._no_best, self.best_q, out=self._exit_q_in)
+        torch.logical_or(self._exit_stale, self._born, out=self._exit_stale)
+        alignment.track_retire_device(
+            self.boxes, self.status, self.frame_hw, self._exit_q_in, self.gallery, self.best_frame, self._born,
+            self.track_id, self.born_frame, self.exit_head, self.exit_faces, self.exit_meta, self.exit_q, self.exit_row,
+            frame_id, flush=flush, opts=self.exit_opts, best_m=self.best_M, best_lm=self.best_landmarks,
+            best_rec=self.best_rec, x_m=self.exit_M, x_lm=self.exit_landmarks, x_rec=self.exit_rec)
+
+    def _retire_served(self):
+        """After the best update of a step: a slot whose pending best-shot reset the step has used holds its own track's
+        best (or none) from here on."""
+        if self.exit_opts is not None:
+            self._exit_stale.logical_and_(self._best_reset)
+
+    def retire(self, flush=False, frame_id=None):
+        """The retire call on demand, for a tracker with `exits`: queues the tracks that have ended since the last tick
+        and names the ones that have begun, without stepping.  flush=True ends every held track as well -- the end of a
+        video; a later step finds the slots without a track, and only an `update` or a `seed` starts one again.
+        frame_id: what the exits record as the frame of their end (None: the number of steps made so far).  Returns
+        `exit_head`.  No download, no synchronisation."""
+        if self.exit_opts is None:
+            raise ValueError("retire() needs a tracker made with exits")
+        frame_id = self._steps if frame_id is None else alignment._frame_id(frame_id)
+        self._state()
+        self._retire(frame_id, flush=bool(flush))
+        return self.exit_head
+
+    def exits(self):
+        """The exit ring of a tracker with `exits`: CUDA tensors (faces [Q,...] in the aligned format, meta int64 [Q,8],
+        q float64 [Q], M float32 [Q,2,3], landmarks float64 [Q,C,2], head int64 [4]), the tracker's own, rows overwritten
+        as later tracks end.  No download, no synchronisation: download `head` when convenient and let
+        `alignment.exit_rows(head[0], cursor, Q)` name the rows that are new."""
+        if self.exit_opts is None:
+            raise ValueError("exits() needs a tracker made with exits")
+        self._state()
+        return self.exit_faces, self.exit_meta, self.exit_q, self.exit_M, self.exit_landmarks, self.exit_head
 
     def best(self):
         """The best shot of every slot, for a tracker with `best_shot`: CUDA tensors (gallery [capacity,...] in the

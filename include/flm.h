@@ -1133,6 +1133,68 @@ int flm_track_best_update_rows(flm_stream_t stream, const void* faces_dev, size_
                                int64_t* best_frame_dev /*[n_slots]*/, float* best_m_dev /*[n_slots,2,3] or NULL*/,
                                double* best_lm_dev /*[n_slots,C,2] or NULL*/, int64_t* best_rec_dev /*[n_slots,8] or NULL*/);
 
+/* flm_track_retire: retires the tracks that have ended and gives identities to the ones that have begun -- the exit
+ * queue of the best shots.  A slot is an index; this call says WHO a slot is (track_id) and THAT a track is over (one ring
+ * row per finished track, holding its best face, delivered once).  At most two launches (the decision, one workgroup;
+ * the copy of the faces), no atomics, no workspace, no allocation, no synchronisation; every launch shape is a host number.
+ * Read:   boxes_dev int32 [K,4], status_dev int32 [K], fh, fw: the tracker's state; best_q_dev float64 [K], gallery_dev
+ *         [K,face_bytes], best_frame_dev int64 [K]: the best shots as flm_track_best_update* keep them; best_m_dev float32
+ *         [K,2,3], best_lm_dev float64 [K,C,2], best_rec_dev int64 [K,8]: each may be NULL, but only together with its ring
+ *         counterpart x_m, x_lm, x_rec; frame_id; flush; opts (NULL = the defaults).
+ * In/out: born_dev int32 [K]: non-zero means a track was started in the slot since the last call (the caller sets it
+ *         where it starts a track; the call clears it); track_id_dev int64 [K]: -1 means the slot holds no track;
+ *         born_frame_dev int64 [K]; head_dev int64 [4] = {seq, next_id, discarded, overrun}, all zero before the first call.
+ * Out:    the exit ring of Q rows: x_gallery [Q,face_bytes], x_meta int64 [Q,FLM_EXIT_META], x_q float64 [Q], and x_m
+ *         float32 [Q,2,3], x_lm float64 [Q,C,2], x_rec int64 [Q,8] (each may be NULL); exit_row_dev int32 [K].
+ * No two arguments may overlap.
+ * Contract, per slot t, in this order; everything is a function of the inputs at entry:
+ *  1. live = the clipped boxes_dev[t] is not empty: the clip of this section, the negation of the DEAD test of
+ *     flm_track_step, step 1, and the test of item 4 of flm_track_associate.  born = born_dev[t] != 0.
+ *     held = track_id_dev[t] >= 0.
+ *  2. The slot's track ENDS when held && (born || !live || flush != 0).
+ *  3. An ending track is EMITTED when best_q_dev[t] >= min_q.  Otherwise it is DISCARDED: exit_row = -2, and it is counted
+ *     in head[2].  The comparison is false for NaN, and false for the -1 of a slot without a best, since min_q >= 0.
+ *  4. The E emitted tracks of the call are ranked by ascending slot: r = 0 .. E-1.  With seq0 = head[0] at entry, the
+ *     track of rank r has sequence number seq0 + r and ring row (seq0 + r) % Q (the non-negative remainder).  It is
+ *     WRITTEN when r >= E - Q, so that no two tracks of one call share a row; then exit_row = its row.  Otherwise it is
+ *     OVERRUN: exit_row = -3, and it is counted in head[3].  head[0] += E: overrun tracks are included, so a consumer that
+ *     keeps its own cursor sees what it missed.
+ *  5. A written row receives the slot's face_bytes gallery bytes; x_q = best_q_dev[t]; each of the matrix, the landmarks and
+ *     the record where its pointer is given; and
+ *       x_meta = { track_id, t, born_frame[t], frame_id, best_frame[t], end, seq0 + r, 0 }
+ *     end = status_dev[t] for a track that ended dead and was not born; -1 when the slot was restarted before its end was
+ *     seen (born); -2 for a live, not born track ended by flush.
+ *  6. Births: the slots with born && live are ranked by ascending slot, b = 0 .. B-1, and next_id = head[1] at entry.  For
+ *     these track_id[t] = next_id + b and born_frame[t] = frame_id; head[1] += B.  A slot that ended and was not born so
+ *     gets track_id = -1; so does a slot that was born with an empty box.  born_dev[t] = 0 for every slot.  A slot that
+ *     neither ends nor is born keeps every bit and has exit_row = -1 (a born slot that held no track has exit_row = -1 too);
+ *     born_frame is written for births alone.
+ *  7. Ring rows that no track of this call was written to keep their bits.
+ * gallery_dev and x_gallery need byte alignment only: the copy uses 16-byte accesses where both addresses allow them and
+ * element accesses elsewhere, and no byte outside a row is read or written.
+ * Defaults (flm_exit_opts_init): min_q = 0: every track that has a best shot is emitted.
+ * Errors, all found before any launch: a null pointer other than the optional triples and opts, an optional source
+ * without its ring buffer or the reverse, a struct_size smaller than this library's, a non-zero reserved, a min_q that is
+ * negative or NaN, or two arguments that overlap -> FLM_ERR_ARG.  FLM_ERR_SHAPE, the limit named in flm_last_error(),
+ * unless 1 <= k <= 65535, 1 <= q <= 65535, 1 <= c <= 1024, face_bytes >= 1 and fh, fw >= 1. */
+#define FLM_EXIT_META 8
+typedef struct flm_exit_opts {
+  uint32_t struct_size;  /* as flm_track_opts */
+  uint32_t reserved;     /* 0 */
+  double min_q;          /* >= 0: an ending track whose best quality lies below it is discarded */
+} flm_exit_opts;
+void flm_exit_opts_init(flm_exit_opts* opts);   /* min_q = 0.0 */
+int flm_track_retire(flm_stream_t stream, const int32_t* boxes_dev /*[K,4]*/, const int32_t* status_dev /*[K]*/, int k,
+                     int fh, int fw, const double* best_q_dev /*[K]*/, const void* gallery_dev /*[K,face_bytes]*/,
+                     size_t face_bytes, const int64_t* best_frame_dev /*[K]*/, const float* best_m_dev /*[K,2,3] or NULL*/,
+                     const double* best_lm_dev /*[K,C,2] or NULL*/, int c, const int64_t* best_rec_dev /*[K,8] or NULL*/,
+                     int64_t frame_id, int flush, const flm_exit_opts* opts /*NULL = defaults*/,
+                     int32_t* born_dev /*[K] in/out*/, int64_t* track_id_dev /*[K] in/out*/,
+                     int64_t* born_frame_dev /*[K] in/out*/, int64_t* head_dev /*[4] in/out*/, int q,
+                     void* x_gallery /*[Q,face_bytes]*/, int64_t* x_meta /*[Q,8]*/, double* x_q /*[Q]*/,
+                     float* x_m /*[Q,2,3] or NULL*/, double* x_lm /*[Q,C,2] or NULL*/, int64_t* x_rec /*[Q,8] or NULL*/,
+                     int32_t* exit_row_dev /*[K]*/);
+
 /* ---- head pose: where a face looks, from its landmarks ------------------------------------------------------------------
  * flm_head_pose: a scaled-orthographic pose (the linear step of POS: DeMenthon, Davis 1995) of every face from its 2-D
  * landmarks and a rigid 3-D model of P points, in ONE launch (a workgroup of one wave per row), no workspace, no
