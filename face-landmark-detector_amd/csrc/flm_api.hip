@@ -46,6 +46,7 @@ static Knob g_knobs[] = {
     {"up3_cand8", {1}, [](int v) { return v >= 0 && v <= 7; }, "in [0,7]"},
     {"up3_cand8_rows", {0}, [](int v) { return v >= 0 && v <= 8 && !(v & (v - 1)); }, "0, 1, 2, 4 or 8"},
     {"up3_wreg", {0}, [](int v) { return v == 0 || v == 1; }, "0 or 1"},
+    {"f32_fc6_rows", {0}, [](int v) { return v == 0 || v == 64 || v == 128; }, "0, 64 or 128"},
 };
 static_assert(sizeof(g_knobs) / sizeof(g_knobs[0]) == KNOB_COUNT, "one row per KnobId");
 int tuning(KnobId id) { return g_knobs[id].value.load(std::memory_order_relaxed); }
@@ -284,6 +285,7 @@ int flm_abi_version(void) { return FLM_ABI_VERSION; }
 
 int flm_debug_query(const char* key, int arg) {
   if (key && !strcmp(key, "igemm_occupancy")) return igemm_occupancy((size_t)arg);
+  if (key && !strcmp(key, "igemm_posmajor_rows")) return igemm_posmajor_rows_last();
   return -1;
 }
 

@@ -151,7 +151,8 @@ Fcn8Ws fcn8_ws_layout(int n, int h, int w, int C, int dtype, int out_mode, int d
 enum KnobId {
   KNOB_BF16_BIG_TILES, KNOB_BF16_LDS_DMA, KNOB_BF16_MFMA16, KNOB_BF16_HALO_MFMA16, KNOB_F32_TWO_LEVEL, KNOB_F32_LEAN_TILE,
   KNOB_BF16_GROUP_N, KNOB_BF16_CONV3_HALO, KNOB_BF16_SCORE1X1, KNOB_BF16_FUSED_TAIL, KNOB_DECODE_LDS_DMA,
-  KNOB_POSMAJOR_ORDER, KNOB_WARP_ROWS, KNOB_UP3_CAND8, KNOB_UP3_CAND8_ROWS, KNOB_UP3_WREG, KNOB_COUNT
+  KNOB_POSMAJOR_ORDER, KNOB_WARP_ROWS, KNOB_UP3_CAND8, KNOB_UP3_CAND8_ROWS, KNOB_UP3_WREG, KNOB_F32_FC6_ROWS,
+  KNOB_COUNT
 };
 int tuning(KnobId id);  // the knob's current value (relaxed load)
 
@@ -182,6 +183,8 @@ struct IgemmDesc {
 };
 int launch_igemm(hipStream_t s, const IgemmDesc& d);
 int igemm_occupancy(size_t lds_bytes);
+// rows per tile (64 | 128) of the most recent fp32 position-major launch of this process, 0 before the first (tests)
+int igemm_posmajor_rows_last();
 // seg_feats = crop(up4(fuse4)) + score3(f3) in one launch (flm_tail_bf16.hip; bf16, 68 classes, 256-channel f3):
 // 1 launched, 0 shape left to the two-launch form, < 0 error
 int launch_seg_fused_bf16(hipStream_t s, const float* fuse4, const void* w4_packed, const void* f3, const void* w3,

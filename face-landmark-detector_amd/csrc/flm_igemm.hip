@@ -63,7 +63,8 @@ __device__ __forceinline__ float f4c(const float4& v, int i) { return i == 0 ? v
 // One of the 16 MFMA slots of a k-step.
 //   fp32: component IDX of the four 16-byte fragments feeds all four 32x32 tiles (k = 8t+4h+IDX);
 //   bf16: the whole fragments (8 bf16 = k 8h..8h+7 of a 16-deep step) feed tile IDX = 2*i + j.
-template <bool BF, int IDX>
+// HALF (the 64-row form: one A fragment per wave): only the tiles c00, c01 of the first fragment exist.
+template <bool BF, int IDX, bool HALF = false>
 __device__ __forceinline__ void mfma_slot(const float4& a0, const float4& a1, const float4& b0, const float4& b1,
                                           f32x16& c00, f32x16& c01, f32x16& c10, f32x16& c11) {
   if constexpr (BF) {
@@ -77,8 +78,10 @@ __device__ __forceinline__ void mfma_slot(const float4& a0, const float4& a1, co
   } else {
     c00 = __builtin_amdgcn_mfma_f32_32x32x2f32(f4c(a0, IDX), f4c(b0, IDX), c00, 0, 0, 0);
     c01 = __builtin_amdgcn_mfma_f32_32x32x2f32(f4c(a0, IDX), f4c(b1, IDX), c01, 0, 0, 0);
-    c10 = __builtin_amdgcn_mfma_f32_32x32x2f32(f4c(a1, IDX), f4c(b0, IDX), c10, 0, 0, 0);
-    c11 = __builtin_amdgcn_mfma_f32_32x32x2f32(f4c(a1, IDX), f4c(b1, IDX), c11, 0, 0, 0);
+    if constexpr (!HALF) {
+      c10 = __builtin_amdgcn_mfma_f32_32x32x2f32(f4c(a1, IDX), f4c(b0, IDX), c10, 0, 0, 0);
+      c11 = __builtin_amdgcn_mfma_f32_32x32x2f32(f4c(a1, IDX), f4c(b1, IDX), c11, 0, 0, 0);
+    }
   }
 }
 
@@ -90,15 +93,34 @@ __device__ __forceinline__ void mfma_slot(const float4& a0, const float4& a1, co
 //   write-out a full tile of an unsplit launch stores through one scalar base and 32-bit offsets with no per-element
 //             test, the residual variant chosen once; partial tiles and split-K slices take the guarded path below.
 // The k-loop, the summation tree and every arithmetic operation of the write-out are those of LEAN = false: same bits.
-template <bool BF, int MMAP, bool RELU, bool TWO = false, bool LEAN = false>
-__global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
+//
+// BMT = 64 (fp32 TWO form, position-major; knob "f32_fc6_rows"): the same kernel on tiles of 64 pixels x 128 channels.  The
+// four waves are still 2 x 2, each 32 x 64: ONE A fragment, two B fragments, two 32x32 accumulators per set -- 8 MFMAs per
+// k-group, 32 per step, fed by 2 A and 4 B requests per wave.  BK, the swizzle, the k permutation, the two-stage ring, the
+// one barrier per step and the three accumulator sets with their group cuts on the dense (chunk, tap) index are those of
+// the 128-row form, so every output is the same sum in the same order: same bits.  What the shape buys is on the host's
+// side of the launch (flm_igemm_args.h, posmajor_pick_rows): at 64 faces a tile is ONE position of fc6's map -- no union of
+// two positions' taps -- and the tile list is twice as long and half as coarse for the list schedule.  48 KiB of LDS and
+// 137 registers: THREE workgroups per CU.  Measured against two (the same kernel asking for 64 KiB; -DFLM_IGEMM_ROWS64_WAVES=2
+// with tools/ab_variants.py; profiles/igemm_rows64_ab.json): fc6 at 64 faces 2.04 ms with 128 rows, 1.96 with 64 rows and
+// two workgroups per CU, 1.91 with three -- the third resident covers the form's extra operand requests; at 32 faces two
+// are better (1.24 / 1.04 / 1.13 ms).  The headline batch decides: three.  Four do not fit (LDS, and 128 registers).
+#ifndef FLM_IGEMM_ROWS64_WAVES
+#define FLM_IGEMM_ROWS64_WAVES 3  // workgroups per CU the 64-row form is built for: 3, or 2 (developer variant)
+#endif
+template <bool BF, int MMAP, bool RELU, bool TWO = false, bool LEAN = false, int BMT = BM>
+__global__ __launch_bounds__(256, BMT == BM ? 2 : FLM_IGEMM_ROWS64_WAVES) void igemm_kernel(IgemmArgs a) {
   static_assert(!TWO || !BF, "the multi-level accumulation is the fp32 (parity) form");
   static_assert(!LEAN || (TWO && MMAP != 2), "the lean set-up / write-out is built for the fp32 form, row-major and quad order");
+  static_assert(BMT == BM || (BMT == 64 && TWO && MMAP == 2), "64-row tiles are built for the fp32 position-major form");
   constexpr int ES = BF ? 2 : 4;    // operand element size
   constexpr int EPC = 16 / ES;      // elements per 16-byte chunk
+  constexpr bool HALF = BMT != BM;  // one A fragment per wave
+  constexpr int AJ = BMT / 32;      // A rows a staging thread owns: r0 + 32 j, j < AJ
+  constexpr int TILE_A = BMT * BK;  // 4-byte units per A stage
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* As = reinterpret_cast<float*>(smem_raw);  // [2][TILE_F]
-  float* Bs = As + 2 * TILE_F;                     // [2][TILE_F]
+  float* As = reinterpret_cast<float*>(smem_raw);  // [2][TILE_A]
+  float* Bs = As + 2 * TILE_A;                     // [2][TILE_F]
   unsigned long long* s_mask = reinterpret_cast<unsigned long long*>(Bs + 2 * TILE_F);  // [4]
 
   const int tid = threadIdx.x;
@@ -134,9 +156,9 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
     int* ord = wk + a.mtiles;
     for (int t = tid; t < a.mtiles; t += 256) tmask[t] = 0ull;
     __syncthreads();
-    const int npp = (BM - 1) / a.n + 2;
+    const int npp = (BMT - 1) / a.n + 2;
     for (int idx = tid; idx < a.mtiles * npp; idx += 256) {
-      const int t = idx / npp, m_lo = t * BM, m_hi = (m_lo + BM < a.M ? m_lo + BM : a.M) - 1;
+      const int t = idx / npp, m_lo = t * BMT, m_hi = (m_lo + BMT < a.M ? m_lo + BMT : a.M) - 1;
       const int p = m_lo / a.n + (idx - t * npp);
       if (p <= m_hi / a.n) atomicOr(&tmask[t], posmajor_posmask(posmajor_pos(a, p), a.h, a.w, a.kh, a.kw, a.pad));
     }
@@ -156,7 +178,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
   }
   for (int pass = 0; pass < npass; ++pass) {
   const int mt = pair_mt[pass];
-  const int m0 = mt * BM;
+  const int m0 = mt * BMT;
   if (pass) __syncthreads();  // the previous tile's last fragment reads are done before LDS is refilled
 
   // ---- staging role: rows r0+32j, 16-byte chunk c8 of the 128-byte k-run ----------------------
@@ -166,7 +188,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
   int pn[4], py[4], px[4];
   bool pv[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
+  for (int j = 0; j < AJ; ++j) {
     const int m = m0 + r0 + 32 * j;
     pv[j] = m < a.M;
     const int mm = pv[j] ? m : 0;
@@ -214,7 +236,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
       const int ky = t / a.kw - a.pad, kx = t % a.kw - a.pad;
       bool any = false;
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
+      for (int j = 0; j < AJ; ++j)
         any |= pv[j] && (unsigned)(py[j] + ky) < (unsigned)a.h && (unsigned)(px[j] + kx) < (unsigned)a.w;
       if (__any(any)) mymask |= 1ull << t;
     }
@@ -257,7 +279,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
   // per-row BYTE offset of the centre pixel; per-tap displacement is wave-uniform
   unsigned rowoff[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j)
+  for (int j = 0; j < AJ; ++j)
     rowoff[j] = ((unsigned)(((pn[j] * a.h + py[j]) * a.w + px[j]) * a.cin) + EPC * c8) * ES;
   const char* wrow[4];
 #pragma unroll
@@ -265,8 +287,8 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
     wrow[j] = reinterpret_cast<const char*>(a.wt) + ((size_t)(n0 + r0 + 32 * j) * a.K + EPC * c8) * ES;
   const char* xbase = reinterpret_cast<const char*>(a.x);
 
-  // fragment read offsets (floats): rows 64*wr + 32*i + lr of A, 64*wc + 32*j + lr of B; the XOR term of
-  // the swizzle depends on lr only, the chunk is 2*t + lh
+  // fragment read offsets (floats): rows 64*wr + 32*i + lr of A (64-row form: 32*wr + lr), 64*wc + 32*j + lr of B; the
+  // XOR term of the swizzle depends on lr only, the chunk is 2*t + lh
   // (LEAN: behind the first two stages' requests, see FLM_FRAG_OFFSETS below)
   int fa0, fa1, fb0, fb1, fc0, fc1, fc2, fc3;
 #define FLM_FRAG_OFFSETS()                                                                                              \
@@ -274,7 +296,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
     const int wr = wave >> 1, wc = wave & 1;                                                                            \
     const int lr = lane & 31, lh = lane >> 5;                                                                           \
     const int swx = (lr >> 1) & 7;                                                                                      \
-    fa0 = (64 * wr + lr) * BK, fa1 = fa0 + 32 * BK;                                                                     \
+    fa0 = ((BMT / 2) * wr + lr) * BK, fa1 = fa0 + 32 * BK;                                                              \
     fb0 = (64 * wc + lr) * BK, fb1 = fb0 + 32 * BK;                                                                     \
     fc0 = ((0 + lh) ^ swx) << 2, fc1 = ((2 + lh) ^ swx) << 2, fc2 = ((4 + lh) ^ swx) << 2, fc3 = ((6 + lh) ^ swx) << 2; \
   }
@@ -317,7 +339,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
     typedef __attribute__((address_space(3))) char lds_char;
     const int wave_s = __builtin_amdgcn_readfirstlane(wave);
     const unsigned dma_a = (unsigned)(size_t)((lds_char*)smem_raw) + wave_s * 8 * 128;  // this wave's 8 rows of A stage 0
-    const unsigned dma_b = dma_a + 2 * TILE_F * 4;
+    const unsigned dma_b = dma_a + 2 * TILE_A * 4;
     const int xbias = (a.pad * a.w + a.pad) * a.cin * 4;  // largest negative tap displacement, in bytes
     const dma_srd xdma = dma_make_srd(reinterpret_cast<const char*>(a.x) - xbias);
     const dma_srd wdma = dma_make_srd(reinterpret_cast<const char*>(a.wt) + (size_t)n0 * a.K * 4);
@@ -326,7 +348,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
     // (py << 16) | px of the filter centre; rows past M get py = 0x7000: out of bounds for every tap, they never load
     int pyx[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) pyx[j] = ((pv[j] ? py[j] : 0x7000) << 16) | px[j];
+    for (int j = 0; j < AJ; ++j) pyx[j] = ((pv[j] ? py[j] : 0x7000) << 16) | px[j];
 
     unsigned long long rem = rem0;
     int cur_chunk = chunk0 < a.cpt ? chunk0 : 0;
@@ -351,10 +373,10 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
     cur_tap = __builtin_ctzll(rem);                                          \
   }
 #define FLM_DMA_A(J, STG)                                                                                    \
-  {                                                                                                          \
+  if constexpr ((J) < AJ) {                                                                                  \
     const int iy = (pyx[J] >> 16) + ld_ky, ix = (pyx[J] & 0xffff) + ld_kx;                                   \
     const bool ok_ = (unsigned)iy < (unsigned)a.h && (unsigned)ix < (unsigned)a.w;                          \
-    dma_load16(xdma, dma_a + (STG) * (TILE_F * 4) + (J) * 32 * 128, ok_ ? rowoff[J] : kOobOffset, ld_delta); \
+    dma_load16(xdma, dma_a + (STG) * (TILE_A * 4) + (J) * 32 * 128, ok_ ? rowoff[J] : kOobOffset, ld_delta); \
   }
 #define FLM_DMA_B(J, STG) dma_load16(wdma, dma_b + (STG) * (TILE_F * 4) + (J) * 32 * 128, wrow0, (J) * wstep + ld_koff);
 #define FLM_READ_FRAGS(AF0, AF1, BF0, BF1, T, STG)                                                          \
@@ -362,12 +384,12 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
     int oa_ = off_a, ob_ = off_b;                                                                           \
     if (FLM_IGEMM_VAR & 2) asm volatile("" : "+v"(oa_), "+v"(ob_)); /* (opaque, or the sums are hoisted) */ \
     const int fct_ = (T) == 0 ? fc0 : ((T) == 1 ? fc1 : ((T) == 2 ? fc2 : fc3));                            \
-    const char* pa_ = !(FLM_IGEMM_VAR & 2) ? smem_raw + (fa0 + fct_) * 4 + (STG) * (TILE_F * 4)             \
-                                           : smem_raw + ((oa_ ^ ((T) << 5)) + (STG) * (TILE_F * 4));        \
-    const char* pb_ = !(FLM_IGEMM_VAR & 2) ? smem_raw + (fb0 + fct_) * 4 + (STG) * (TILE_F * 4) + 2 * TILE_F * 4 \
-                                           : smem_raw + ((ob_ ^ ((T) << 5)) + (STG) * (TILE_F * 4) + 2 * TILE_F * 4); \
+    const char* pa_ = !(FLM_IGEMM_VAR & 2) ? smem_raw + (fa0 + fct_) * 4 + (STG) * (TILE_A * 4)             \
+                                           : smem_raw + ((oa_ ^ ((T) << 5)) + (STG) * (TILE_A * 4));        \
+    const char* pb_ = !(FLM_IGEMM_VAR & 2) ? smem_raw + (fb0 + fct_) * 4 + (STG) * (TILE_F * 4) + 2 * TILE_A * 4 \
+                                           : smem_raw + ((ob_ ^ ((T) << 5)) + (STG) * (TILE_F * 4) + 2 * TILE_A * 4); \
     AF0 = *reinterpret_cast<const float4*>(pa_);                                                            \
-    AF1 = *reinterpret_cast<const float4*>(pa_ + 32 * BK * 4);                                              \
+    if constexpr (!HALF) AF1 = *reinterpret_cast<const float4*>(pa_ + 32 * BK * 4);                         \
     BF0 = *reinterpret_cast<const float4*>(pb_);                                                            \
     BF1 = *reinterpret_cast<const float4*>(pb_ + 32 * BK * 4);                                              \
   }
@@ -376,7 +398,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
 #define FLM_SLOT_z 2
 #define FLM_SLOT_w 3
 #define FLM_MFMA4(AF0, AF1, BF0, BF1, E)                                                     \
-  mfma_slot<false, FLM_SLOT_##E>(AF0, AF1, BF0, BF1, acc00, acc01, acc10, acc11);            \
+  mfma_slot<false, FLM_SLOT_##E, HALF>(AF0, AF1, BF0, BF1, acc00, acc01, acc10, acc11);      \
   __builtin_amdgcn_sched_barrier(0);
   // first slot of a step: close the previous step tile by tile and restart the tile from C = 0
 #define FLM_FLUSH1(SUM, ACC, AV, BV)                                                         \
@@ -386,8 +408,10 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
 #define FLM_MFMA4_FLUSH(AF0, AF1, BF0, BF1)                                                  \
   FLM_FLUSH1(sum00, acc00, AF0.x, BF0.x)                                                     \
   FLM_FLUSH1(sum01, acc01, AF0.x, BF1.x)                                                     \
-  FLM_FLUSH1(sum10, acc10, AF1.x, BF0.x)                                                     \
-  FLM_FLUSH1(sum11, acc11, AF1.x, BF1.x)
+  if constexpr (!HALF) {                                                                     \
+    FLM_FLUSH1(sum10, acc10, AF1.x, BF0.x)                                                   \
+    FLM_FLUSH1(sum11, acc11, AF1.x, BF1.x)                                                   \
+  }
 
   // One step on stage BUF (compile-time).
 #define FLM_STEP2(BUF)                                                                                \
@@ -416,8 +440,12 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
     /* third level, right behind the barrier: the second set holds the steps before this one; if this step opened */ \
     /* a new group they are a closed group */                                                         \
     if (!(FLM_IGEMM_VAR & 1) && g_prev != g_cur) {                                                    \
-      top00 += sum00; top01 += sum01; top10 += sum10; top11 += sum11;                                 \
-      sum00 = zero16; sum01 = zero16; sum10 = zero16; sum11 = zero16;                                 \
+      top00 += sum00; top01 += sum01;                                                                 \
+      sum00 = zero16; sum01 = zero16;                                                                 \
+      if constexpr (!HALF) {                                                                          \
+        top10 += sum10; top11 += sum11;                                                               \
+        sum10 = zero16; sum11 = zero16;                                                               \
+      }                                                                                               \
     }                                                                                                 \
     /* group 3: the next step's first fragments come from the next stage; tile it+2 is requested into this one */ \
     {                                                                                                 \
@@ -456,6 +484,7 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
     __syncthreads();
     float4 afx0, afx1, bfx0, bfx1, afy0, afy1, bfy0, bfy1;
     afy0 = afy1 = bfy0 = bfy1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (HALF) afx1 = afy0;  // (never read: the second A fragment of the 128-row form)
     FLM_READ_FRAGS(afx0, afx1, bfx0, bfx1, 0, 0)
     for (int it = 0; it < nit; it += 2) {
       FLM_STEP2(0)
@@ -464,8 +493,10 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
     __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0): the requests past the last tile still write LDS
     acc00 = top00 + (sum00 + acc00);
     acc01 = top01 + (sum01 + acc01);
-    acc10 = top10 + (sum10 + acc10);
-    acc11 = top11 + (sum11 + acc11);
+    if constexpr (!HALF) {
+      acc10 = top10 + (sum10 + acc10);
+      acc11 = top11 + (sum11 + acc11);
+    }
 #undef FLM_TILE_PARAMS
 #undef FLM_DMA_A
 #undef FLM_DMA_B
@@ -720,8 +751,8 @@ __global__ __launch_bounds__(256, 2) void igemm_kernel(IgemmArgs a) {
     const bool cok = col < a.cout;
     const float sc = a.scale[col], sh = a.shift[col];  // coutpad-long arrays: always in bounds
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int mbase = m0 + 64 * wr + 32 * i;
+    for (int i = 0; i < BMT / 64; ++i) {
+      const int mbase = m0 + (BMT / 2) * wr + 32 * i;
       if (MMAP == 1 && a.ksplit > 1) {  // raw partial sums in quad order; BN / ReLU / pool happen in the reduce
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -797,16 +828,24 @@ void posperm_cache_put(const PospermEntry& e) {
 }
 
 
-template <bool BF, int MMAP, bool RELU, bool TWO = false, bool LEAN = false>
+// Dynamic LDS of a launch.  The 64-row form needs 48 KiB; the developer variant for two workgroups per CU
+// (FLM_IGEMM_ROWS64_WAVES == 2) asks for the 128-row form's 64 KiB, so that no third moves in.
+template <int BMT>
+constexpr size_t igemm_lds_bytes() {
+  return sizeof(float) * (2 * (BMT == BM || FLM_IGEMM_ROWS64_WAVES == 2 ? BM : BMT) * BK + 2 * TILE_F) + 64;
+}
+
+template <bool BF, int MMAP, bool RELU, bool TWO = false, bool LEAN = false, int BMT = BM>
 static int launch_t(hipStream_t s, const IgemmArgs& a_in) {
   IgemmArgs a = a_in;
-  if (MMAP == 2) posmajor_fill_perm(a, BM);
+  if (BMT != BM) a.mtiles = cdiv(a.M, BMT);  // (the slices of a split-K launch were chosen from the 128-row grid and stay)
+  if (MMAP == 2) posmajor_fill_perm(a, BMT);
   if (LEAN) igemm_fill_lean(a, MMAP == 1, BM);
-  const size_t lds = sizeof(float) * 4 * TILE_F + 64;
+  const size_t lds = igemm_lds_bytes<BMT>();
   static FuncAttrOnce attr;
-  FLM_FUNC_ATTR_ONCE(attr, (&igemm_kernel<BF, MMAP, RELU, TWO, LEAN>), lds);
+  FLM_FUNC_ATTR_ONCE(attr, (&igemm_kernel<BF, MMAP, RELU, TWO, LEAN, BMT>), lds);
   const int mslots = (MMAP == 2 && !TWO) ? (a.mtiles + 1) / 2 : a.mtiles;
-  igemm_kernel<BF, MMAP, RELU, TWO, LEAN><<<dim3(mslots * a.ntiles, a.ksplit > 1 ? a.ksplit : 1), 256, lds, s>>>(a);
+  igemm_kernel<BF, MMAP, RELU, TWO, LEAN, BMT><<<dim3(mslots * a.ntiles, a.ksplit > 1 ? a.ksplit : 1), 256, lds, s>>>(a);
   FLM_LAUNCH_CHECK("igemm_kernel");
   return FLM_OK;
 }
@@ -859,8 +898,50 @@ int igemm_occupancy(size_t lds_bytes) {
   return nb;
 }
 
+// ---- knob "f32_fc6_rows": 64 or 128 rows per tile for a position-major launch of the fp32 TWO form ------------------------
+// 0 (default): posmajor_pick_rows (flm_igemm_args.h) on the slots this device really has -- compute units per XCD x the
+// workgroups per CU the occupancy query reports for either form --, once per geometry, batch and device (the model walks a
+// list schedule: a few thousand operations).  64 / 128: that form wherever it can run.
+struct RowsEntry {
+  int h, w, kh, kw, pad, n, ntiles, dev, rows;
+};
+static std::mutex g_rows_mu;
+static std::vector<RowsEntry> g_rows_cache;
+static std::atomic<int> g_rows_last{0};
+int igemm_posmajor_rows_last() { return g_rows_last.load(std::memory_order_relaxed); }
+
+static int posmajor_rows_for(const IgemmArgs& a) {
+  const int knob = tuning(KNOB_F32_FC6_ROWS);
+  if (knob == 128 || cdiv(a.M, 64) > kRows64MaxTiles) return 128;
+  if (knob == 64) return 64;
+  if (a.ksplit > 1 || a.n >= BM) return 128;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 128;
+  std::lock_guard<std::mutex> lock(g_rows_mu);
+  for (const RowsEntry& c : g_rows_cache)
+    if (c.h == a.h && c.w == a.w && c.kh == a.kh && c.kw == a.kw && c.pad == a.pad && c.n == a.n && c.ntiles == a.ntiles && c.dev == dev)
+      return c.rows;
+  int cus = 0, occ128 = 0, occ64 = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ128, reinterpret_cast<const void*>(&igemm_kernel<false, 2, true, true, false, BM>),
+                                                   256, igemm_lds_bytes<BM>()) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ64, reinterpret_cast<const void*>(&igemm_kernel<false, 2, true, true, false, 64>),
+                                                   256, igemm_lds_bytes<64>()) != hipSuccess)
+    return 128;
+  const int rows = posmajor_pick_rows(a, cus / 8 * occ128, cus / 8 * occ64);  // (xcd_remap: eight XCDs)
+  if (g_rows_cache.size() < 256) g_rows_cache.push_back({a.h, a.w, a.kh, a.kw, a.pad, a.n, a.ntiles, dev, rows});
+  return rows;
+}
+
 template <bool BF, bool TWO = false>
 static int dispatch(hipStream_t s, const IgemmDesc& d, const IgemmArgs& a) {
+  if constexpr (TWO) {
+    if (d.posmajor) {
+      const int rows = posmajor_rows_for(a);
+      g_rows_last.store(rows, std::memory_order_relaxed);
+      if (rows == 64) return d.relu ? launch_t<BF, 2, true, TWO, false, 64>(s, a) : launch_t<BF, 2, false, TWO, false, 64>(s, a);
+    }
+  }
   // knob "f32_lean_tile": the fp32 TWO form with the lean set-up and write-out (1, default) or without (0); same bits
   if constexpr (TWO) {  // (position-major tiles keep their set-up: masks and ranking are what make fc6's tiles unequal)
     if (!d.posmajor && tuning(KNOB_F32_LEAN_TILE)) {

@@ -1,6 +1,9 @@
 // Kernel-argument block and index helpers shared by the implicit-GEMM kernels (flm_igemm.hip: 128x128 tiles,
-// fp32 and bf16; flm_igemm_bf16.hip: 256-row tiles for bf16).
+// fp32 and bf16, and the 64x128 tiles of the fp32 position-major form; flm_igemm_bf16.hip: 256-row tiles for bf16).
 #pragma once
+#include <algorithm>
+#include <vector>
+
 #include "flm_common.h"
 
 namespace flm {
@@ -83,7 +86,7 @@ inline void igemm_fill_lean(IgemmArgs& a, bool quads, int bm) {
 }
 
 // place -> map position (see IgemmArgs::posperm).  The table sits in scalar registers: eight selects and a shift.
-__device__ __forceinline__ int posmajor_pos(const IgemmArgs& a, int place) {
+__host__ __device__ __forceinline__ int posmajor_pos(const IgemmArgs& a, int place) {
   if (!a.posperm_on) return place;
   unsigned long long w = a.posperm[0];
 #pragma unroll
@@ -109,7 +112,7 @@ __device__ __forceinline__ unsigned long long posmajor_tapmask(int t, int M, int
 }
 
 // Taps that see an in-bounds pixel from position p = y*w + x alone: rows ky of kx_lo..kx_hi.
-__device__ __forceinline__ unsigned long long posmajor_posmask(int p, int h, int w, int kh, int kw, int pad) {
+__host__ __device__ __forceinline__ unsigned long long posmajor_posmask(int p, int h, int w, int kh, int kw, int pad) {
   const int y = p / w, x = p - y * w;
   const int kx_lo = pad - x > 0 ? pad - x : 0, kx_hi = pad + w - 1 - x < kw - 1 ? pad + w - 1 - x : kw - 1;
   const int ky_lo = pad - y > 0 ? pad - y : 0, ky_hi = pad + h - 1 - y < kh - 1 ? pad + h - 1 - y : kh - 1;
@@ -235,6 +238,72 @@ inline void posmajor_fill_perm(IgemmArgs& a, int bm) {
   }
   a.posperm_on = ent.on;
   for (int k = 0; k < 8; ++k) a.posperm[k] = ent.table[k];
+}
+
+// ---- 64 or 128 rows per tile for a position-major fp32 launch (fc6; knob "f32_fc6_rows") ---------------------------------
+// Both forms of igemm_kernel<false, 2, RELU, TWO> give every output the same bits; they differ in what the tile list costs.
+// A tile issues the UNION of its positions' taps on all of its rows, and the workgroups of an XCD (ntiles / 8 weight
+// panels x all tiles, heaviest first) are a list schedule on the XCD's resident slots.  At 64 faces on fc6's 8 x 8 map a
+// 128-row tile is two positions (useful / issued 0.955 at best) and there are two tiles per slot: the schedule cannot end
+// before heaviest + lightest = 49 + 20 = 69 tap-units where the mean is 63.75.  A 64-row tile is ONE position and costs
+// half a unit per tap: four jobs per slot, the schedule ends at 61.5 against a mean of 60.5.  The price is operand
+// traffic: (64 + 128) / (64 x 128) rows fetched per output where 128 x 128 fetches 256 / (128 x 128), 1.5 x the LDS-DMA
+// requests and fragment reads per MFMA.  The model below is exactly that: the list schedule's makespan for either form,
+// and a fixed surcharge on the 64-row form.  tests/native/igemm_rows64_host.cpp checks it on the host.
+
+// Tap mask of m-tile t of a launch with bm rows per tile; places -> positions through a.posperm (posmajor_fill_perm(a, bm)
+// has run).  What the kernel's set-up computes for the same tile.
+inline unsigned long long posmajor_tile_mask(const IgemmArgs& a, int bm, int t) {
+  const int m_lo = t * bm, m_hi = (m_lo + bm < a.M ? m_lo + bm : a.M) - 1;
+  unsigned long long mask = 0ull;
+  for (int p = m_lo / a.n; p <= m_hi / a.n; ++p) mask |= posmajor_posmask(posmajor_pos(a, p), a.h, a.w, a.kh, a.kw, a.pad);
+  return mask;
+}
+
+// Makespan of the launch's list schedule with bm rows per tile on slots_per_xcd resident workgroups per XCD, in HALF
+// tap-units of a 128-row tile (a 64-row tile of t taps costs t, a 128-row tile 2 t; a partial last tile issues all of its
+// rows).  ntiles a multiple of 8: the kernel's own order -- an XCD gets ntiles / 8 panels x all tiles, rank-major, and
+// every XCD's list is the same.  Otherwise (no layer of the shipped models) workgroups are panel-major, heaviest first
+// inside a panel, and the eight XCDs are modelled as one pool.  A job goes to the slot that frees first.
+inline long long posmajor_makespan(IgemmArgs a, int bm, int slots_per_xcd) {
+  a.mtiles = (a.M + bm - 1) / bm;
+  posmajor_fill_perm(a, bm);
+  std::vector<int> wk((size_t)a.mtiles);
+  for (int t = 0; t < a.mtiles; ++t) wk[(size_t)t] = __builtin_popcountll(posmajor_tile_mask(a, bm, t)) * (bm / 64);
+  std::sort(wk.begin(), wk.end(), [](int x, int y) { return x > y; });
+  const bool by_xcd = (a.ntiles & 7) == 0;
+  const int copies = by_xcd ? a.ntiles >> 3 : 1, rounds = by_xcd ? 1 : a.ntiles;
+  std::vector<long long> load((size_t)(by_xcd ? slots_per_xcd : 8 * slots_per_xcd), 0ll);
+  for (int round = 0; round < rounds; ++round)
+    for (int t = 0; t < a.mtiles; ++t)
+      for (int c = 0; c < copies; ++c) *std::min_element(load.begin(), load.end()) += wk[(size_t)t];
+  return *std::max_element(load.begin(), load.end());
+}
+
+// Extra cost of a 64-row tile's k-step over half a 128-row tile's, in 1/1000: the 1.5 x operand requests and fragment
+// reads per MFMA.  DESIGN.md section 4.1a prices ALL of the 128-row form's requests at 4-6 % of a layer (timing ablation
+// FLM_IGEMM_VAR 8), so half as many again was expected to cost 2-3 %.  Calibrated from the forced-knob A/B of
+// profiles/igemm_rows64_ab.json, fc6 at 64 faces on one MI355X (measured 64 rows / 128 rows, divided by the model's ratio):
+//   two workgroups per CU    1.962 / 2.042 = 0.961 against 123 x 64 / (138 x 64) = 0.891: +79
+//   three (the shipped form) 1.914 / 2.040 = 0.938 against  88 x 96 / (138 x 64) = 0.957: -20
+// With two residents the requests cost three times the estimate; the third resident hides them and a little more.  The
+// shipped figure is 0, not -20: the model never credits the form with more than its schedule.  (At 32 faces the model is
+// optimistic for both forms -- the k-loops are short and the per-tile set-up counts --, 0.80 against a measured 0.91, but
+// ranks them as measured.)
+constexpr int kRows64SurchargePermille = 0;
+// Tiles the 64-row form ranks in its 48 KiB of LDS (16 bytes per tile), with room to spare.
+constexpr int kRows64MaxTiles = 2048;
+
+// 64 when the model prefers 64-row tiles for this launch, else 128.  Candidates are the unsplit launches whose 128-row
+// tiles span more than one position (n < 128): at 128 faces and more a tile is one position either way and the tile list
+// is long.  Split-K launches (up to 16 faces) keep their form.
+inline int posmajor_pick_rows(const IgemmArgs& a, int slots128_per_xcd, int slots64_per_xcd) {
+  if (a.ksplit > 1 || a.n >= 128 || (a.M + 63) / 64 > kRows64MaxTiles || slots128_per_xcd < 1 || slots64_per_xcd < 1) return 128;
+  // (a slot is one of the workgroups that share a CU's matrix pipe: with s slots per CU a tap-unit takes s / 2 times as
+  // long, so makespans of different slot counts compare as makespan x slots)
+  const long long m128 = posmajor_makespan(a, 128, slots128_per_xcd) * slots128_per_xcd,
+                  m64 = posmajor_makespan(a, 64, slots64_per_xcd) * slots64_per_xcd;
+  return m64 * (1000 + kRows64SurchargePermille) < m128 * 1000 ? 64 : 128;
 }
 
 __device__ __forceinline__ unsigned short f2bf(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }

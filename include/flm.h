@@ -327,12 +327,20 @@ int flm_profile_filter(const char* layer);
  *                           one phase's weights for its whole life, the input streams past through LDS) where its
  *                           conditions hold (stride 8, 68 classes; the probability region of the workspace is its
  *                           scratch); 0 (default).  Same keys
+ * One knob is a size, not a switch (0, 64 or 128; anything else is rejected):
+ *     "f32_fc6_rows"        rows per tile of the fp32 position-major implicit GEMM (fc6; csrc/flm_igemm.hip, BMT): 0
+ *                           (default) the launcher's model decides per launch -- the list schedule of the tile weights on
+ *                           the resident workgroups for both forms plus a surcharge on the 64-row form's extra operand
+ *                           requests (csrc/flm_igemm_args.h, posmajor_pick_rows); split-K launches and batches of 128
+ *                           faces and more keep 128 rows --; 64 or 128: that form wherever it can run (a forced 64 also
+ *                           in split-K launches, whose slices do not move).  Same bits
  * The options that change the workspace layout ("landmark_candidates", "candidate_*") are per-call arguments:
  * flm_forward_opts above. */
 int flm_set_tuning(const char* key, int value);
 /* The current value of a knob listed above: FLM_OK, or FLM_ERR_ARG (null pointer, unknown key) with a message. */
 int flm_get_tuning(const char* key, int* value);
-/* Diagnostics for developers ("igemm_occupancy", arg = dynamic LDS bytes -> workgroups per CU). */
+/* Diagnostics for developers ("igemm_occupancy", arg = dynamic LDS bytes -> workgroups per CU; "igemm_posmajor_rows" ->
+ * rows per tile, 64 or 128, of this process's most recent fp32 position-major launch, 0 before the first). */
 int flm_debug_query(const char* key, int arg);
 int flm_profile_reset(void);
 int flm_profile_read(int index, char* name_out, int name_cap, float* ms_out);
