@@ -23,6 +23,19 @@ _OUT = {"probs": _lib.OUT_PROBS, "classmap": _lib.OUT_CLASSMAP, "landmarks": _li
 _DECODING = (_lib.OUT_LANDMARKS, _lib.OUT_LANDMARKS_STATS)   # the output modes that take n_points / thresh
 
 
+def _check_packed(packed, nbytes):
+    """ValueError unless `packed` can hold a blob of `nbytes`: set_weights(packed=)."""
+    import torch
+    if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8 or packed.dim() != 1 or not packed.is_contiguous():
+        raise ValueError("packed must be a contiguous one-dimensional uint8 tensor")
+    if packed.numel() < nbytes:
+        raise ValueError("packed holds %d bytes, the blob needs %d" % (packed.numel(), nbytes))
+    if packed.data_ptr() % 256:
+        raise ValueError("packed must start at a 256-byte aligned address")
+    if not packed.is_cuda:
+        raise ValueError("packed must be a CUDA tensor")
+
+
 def decode_mode_of(n_points: int):
     """n_points < 1 -> all-pixel centroid (utils/metrics.py:58), else top-n (:66)."""
     return (_lib.DECODE_ALL, 0) if n_points < 1 else (_lib.DECODE_TOPN, int(n_points))
@@ -76,9 +89,22 @@ class Fcn8Model:
         self.set_weights(params)
         return None
 
-    def set_weights(self, params: dict):
+    def packed_bytes(self):
+        """Bytes of this model's packed weight blob (flm_fcn_packed_bytes)."""
+        nbytes = _lib.load().flm_fcn_packed_bytes(self._arch, self.n_classes, self._dt)
+        if nbytes == 0:
+            raise _lib.FlmError("n_classes=%d is outside what the kernels cover" % self.n_classes)
+        return int(nbytes)
+
+    def set_weights(self, params: dict, packed=None):
+        """Pack the Keras-layout tensors of `params` for the kernels.  `packed`: a caller-owned buffer for the blob -- a
+        contiguous CUDA uint8 tensor of at least packed_bytes() bytes whose start is 256-byte aligned (include/flm.h, the
+        buffer contract), whatever it held before; the model keeps it and the caller must not write it while the model
+        lives.  None (default): the model allocates the blob itself, as ever."""
         import torch
         lib = _lib.load()
+        if packed is not None:
+            _check_packed(packed, self.packed_bytes())
         dev = _lib.require_gpu()
         W.check_params(params, self.n_classes, arch=self.model_name)
         held = []
@@ -120,10 +146,9 @@ class Fcn8Model:
             p.up3 = up("up3/kernel")
         else:  # fcn_32: the single 64x64 stride-32 transposed conv travels in the up3 slot
             p.up3 = up("up32/kernel")
-        nbytes = lib.flm_fcn_packed_bytes(self._arch, self.n_classes, self._dt)
-        if nbytes == 0:
-            raise _lib.FlmError("n_classes=%d is outside what the kernels cover" % self.n_classes)
-        packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        nbytes = self.packed_bytes()
+        if packed is None:
+            packed = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         _lib.check(lib.flm_fcn_pack(_lib.stream_ptr(), self._arch, C.byref(p), self.n_classes, self._dt,
                                     _lib.ptr(packed), nbytes), "flm_fcn_pack")
         torch.cuda.current_stream().synchronize()  # the Keras-layout copies die with `held`

@@ -39,8 +39,33 @@ def _resolve(n_points, thresh, as_shipped, dflt_n, dflt_t):
     return (dflt_n if n_points is _UNSET else n_points), (dflt_t if thresh is _UNSET else thresh)
 
 
-def decode_device(hm, n_points=4, thresh=0.0, out=None):
-    """hm: CUDA float32 [N,H,W,L] contiguous -> CUDA float64 [N,L,2] (x,y)."""
+def _check_workspace(workspace, nbytes, device):
+    """A caller-owned `workspace=` of the decode wrappers: a contiguous uint8 tensor on the maps' device of at least
+    `nbytes` bytes (the call's *_workspace_bytes) that starts at a 256-byte aligned address; what it held before does not
+    matter (include/flm.h, the buffer contract).  ValueError otherwise."""
+    import torch
+    if (not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.dim() != 1
+            or not workspace.is_contiguous()):
+        raise ValueError("workspace must be a contiguous one-dimensional uint8 tensor")
+    if workspace.numel() < nbytes:
+        raise ValueError("workspace holds %d bytes, the call needs %d" % (workspace.numel(), nbytes))
+    if workspace.data_ptr() % 256:
+        raise ValueError("workspace must start at a 256-byte aligned address")
+    if workspace.device != device:
+        raise ValueError("workspace must lie on the maps' device %s (got %s)" % (device, workspace.device))
+    return workspace
+
+
+def _decode_workspace(workspace, nbytes, device):
+    import torch
+    if workspace is None:
+        return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+    return _check_workspace(workspace, nbytes, device)
+
+
+def decode_device(hm, n_points=4, thresh=0.0, out=None, workspace=None):
+    """hm: CUDA float32 [N,H,W,L] contiguous -> CUDA float64 [N,L,2] (x,y).  `workspace`: a caller-owned scratch buffer
+    (_check_workspace; flm_decode_workspace_bytes); None: allocated here, as ever."""
     import torch
     lib = _lib.load()
     if hm.dim() != 4 or hm.dtype != torch.float32 or not hm.is_cuda or not hm.is_contiguous():
@@ -49,8 +74,7 @@ def decode_device(hm, n_points=4, thresh=0.0, out=None):
     if n == 0:
         return torch.empty((0, l, 2), dtype=torch.float64, device=hm.device)
     mode, npts = (_lib.DECODE_ALL, 0) if n_points < 1 else (_lib.DECODE_TOPN, int(n_points))
-    nbytes = lib.flm_decode_workspace_bytes(n, h, w, l, mode, npts)
-    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=hm.device)
+    ws = _decode_workspace(workspace, lib.flm_decode_workspace_bytes(n, h, w, l, mode, npts), hm.device)
     if out is None:
         out = torch.empty((n, l, 2), dtype=torch.float64, device=hm.device)
     _lib.check(lib.flm_decode(_lib.stream_ptr(), _lib.ptr(hm), n, h, w, l, mode, npts, float(thresh),
@@ -58,11 +82,12 @@ def decode_device(hm, n_points=4, thresh=0.0, out=None):
     return out
 
 
-def decode_stats_device(hm, n_points=4, thresh=0.0, out=None):
+def decode_stats_device(hm, n_points=4, thresh=0.0, out=None, workspace=None):
     """hm: CUDA float32 [N,H,W,L] contiguous -> CUDA float64 [N,L,6] landmark records (flm_decode_stats): per landmark
     x, y, score, var_x, var_y, cov_xy.  x, y are decode_device's bits; score is the mean selected value the reject test of
     utils/metrics.py:78-79 compares (the reference computes it and keeps only the verdict); the moments are the
-    value-weighted spread of the selected pixels about (x, y) in px^2.  A rejected landmark reads (-1, -1, score, -1, -1, 0)."""
+    value-weighted spread of the selected pixels about (x, y) in px^2.  A rejected landmark reads (-1, -1, score, -1, -1, 0).
+    `workspace`: as decode_device (flm_decode_stats_workspace_bytes)."""
     import torch
     lib = _lib.load()
     if hm.dim() != 4 or hm.dtype != torch.float32 or not hm.is_cuda or not hm.is_contiguous():
@@ -76,8 +101,7 @@ def decode_stats_device(hm, n_points=4, thresh=0.0, out=None):
     if n == 0:
         return out
     mode, npts = (_lib.DECODE_ALL, 0) if n_points < 1 else (_lib.DECODE_TOPN, int(n_points))
-    nbytes = lib.flm_decode_stats_workspace_bytes(n, h, w, l, mode, npts)
-    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=hm.device)
+    ws = _decode_workspace(workspace, lib.flm_decode_stats_workspace_bytes(n, h, w, l, mode, npts), hm.device)
     _lib.check(lib.flm_decode_stats(_lib.stream_ptr(), _lib.ptr(hm), n, h, w, l, mode, npts, float(thresh),
                                     _lib.ptr(out), _lib.ptr(ws), ws.numel()), "flm_decode_stats")
     return out
@@ -144,9 +168,10 @@ RMSE_LABELS = ("(x,y) from est heatmap  VS (x,y) from true heatmap",
                "(x,y) from true heatmap VS true (x,y)")
 
 
-def decode_sweep_device(hm, n_points_list, thresh=0.0):
+def decode_sweep_device(hm, n_points_list, thresh=0.0, workspace=None):
     """hm: CUDA float32 [N,H,W,L] contiguous -> CUDA float64 [S,N,L,2]: slice s is decode_device(hm, n_points_list[s],
-    thresh) (top-n bit for bit, all-pixel within 1e-9 px), every 16 modes from one read of the maps (flm_decode_sweep)."""
+    thresh) (top-n bit for bit, all-pixel within 1e-9 px), every 16 modes from one read of the maps (flm_decode_sweep).
+    `workspace`: as decode_device; it must hold flm_decode_sweep_workspace_bytes of every group of 16 modes."""
     import torch
     lib = _lib.load()
     if hm.dim() != 4 or hm.dtype != torch.float32 or not hm.is_cuda or not hm.is_contiguous():
@@ -161,8 +186,7 @@ def decode_sweep_device(hm, n_points_list, thresh=0.0):
     for lo in range(0, len(modes), _lib.SWEEP_MAX_MODES):
         part = modes[lo:lo + _lib.SWEEP_MAX_MODES]
         arr = _lib.int_array(part)
-        nbytes = lib.flm_decode_sweep_workspace_bytes(n, h, w, l, arr, len(part))
-        ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=hm.device)
+        ws = _decode_workspace(workspace, lib.flm_decode_sweep_workspace_bytes(n, h, w, l, arr, len(part)), hm.device)
         _lib.check(lib.flm_decode_sweep(_lib.stream_ptr(), _lib.ptr(hm), n, h, w, l, arr, len(part), float(thresh),
                                         _lib.ptr(out[lo:lo + len(part)]), _lib.ptr(ws), ws.numel()), "flm_decode_sweep")
     return out

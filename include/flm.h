@@ -124,6 +124,26 @@ int flm_fcn8_pack(flm_stream_t stream, const flm_fcn8_params* params_dev_ptrs, i
  * call site prediction.py:208), optionally continued through the argmax of
  * prediction.py:209 or the decode of utils/metrics.py:102-109.
  * H and W must be multiples of 32; the output grid is H' = H+8, W' = W+8.
+ *
+ * What a call may assume about its buffers -- and what it may not.  A workspace is a recycled block, not a fresh page.
+ * In one call of a forward (every flm_fcn*_forward*), of a pack (flm_fcn*_pack) or of a decode (flm_decode,
+ * flm_decode_stats, flm_decode_sweep):
+ *  1. the result does not depend on what the workspace held before the call;
+ *  2. it does not depend on what the output held;
+ *  3. it does not depend on what the gaps between the regions of the packed blob hold (a pack writes every byte a
+ *     forward reads and leaves the rest of packed_dev as it found it);
+ *  4. it does not depend on memory adjacent to any operand: nothing before the first or after the last byte of the
+ *     input, the blob, the workspace or the output is read into a result, not even multiplied by a packed zero;
+ *  5. nothing outside [workspace_dev, workspace_dev + workspace_bytes) and the output is written; packed_dev and x_dev
+ *     are read only.
+ * "The result" is the output and every intermediate flm_fcn_workspace_offset_opts names, pad class columns included.
+ * Alignment: workspace_dev and packed_dev must be 256-byte aligned (their layouts count in 256-byte steps from the
+ * start), x_dev and out_dev 16-byte aligned; the decodes' maps 16-byte aligned as stated there, their workspaces
+ * 256-byte and their outputs 8-byte aligned.  The image calls further down (warps, crops, frame conversion) take 16-byte
+ * aligned sources and float32 destinations -- every face of a batch then starts wherever its size puts it -- and, in the
+ * *_fmt calls, a destination aligned to its element, as stated there; they use no workspace, and points 2, 4 and 5 hold
+ * for them too.  tests/test_gpu_buffer_independence.py holds all of this with the operands carved from one allocation
+ * pre-filled with 0x00, 0x4B and 0xFF, each between 4 MiB guards, at exactly these alignments and no better.
  */
 size_t flm_fcn8_workspace_bytes(int n, int h, int w, int n_classes, int dtype, int out_mode,
                                 int decode_mode, int n_points);
