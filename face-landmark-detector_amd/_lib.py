@@ -54,6 +54,7 @@ EXPORTS = [
     "flm_track_gather_streams", "flm_track_step_rows", "flm_track_best_update_rows", "flm_track_gather_live",
     "flm_pose_opts_init", "flm_head_pose",
     "flm_exit_opts_init", "flm_track_retire",
+    "flm_views_opts_init", "flm_track_views_update", "flm_track_exit_views",
 ]
 
 
@@ -208,6 +209,31 @@ class ExitOpts(C.Structure):
         o = cls()
         load().flm_exit_opts_init(C.byref(o))
         o.min_q = float(min_q)
+        return o
+
+
+VIEWS_MAX_EDGES = 7   # FLM_VIEWS_MAX_EDGES
+
+
+class ViewsOpts(C.Structure):
+    """flm_views_opts: how flm_track_views_update scores a face and which pose bin it falls into (include/flm.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("sharp_ref", C.c_double),
+                ("min_exposed", C.c_double), ("n_u", C.c_int32), ("n_v", C.c_int32),
+                ("u_edge", C.c_double * VIEWS_MAX_EDGES), ("v_edge", C.c_double * VIEWS_MAX_EDGES)]
+
+    @classmethod
+    def make(cls, u_edges=None, v_edges=(), sharp_ref=100.0, min_exposed=0.5):
+        """u_edges None: the library's default edges."""
+        o = cls()
+        load().flm_views_opts_init(C.byref(o))
+        o.sharp_ref = float(sharp_ref)
+        o.min_exposed = float(min_exposed)
+        for count, arr, edges in (("n_u", o.u_edge, u_edges), ("n_v", o.v_edge, v_edges)):
+            if edges is None:
+                continue
+            setattr(o, count, len(edges))
+            for i in range(VIEWS_MAX_EDGES):
+                arr[i] = float(edges[i]) if i < min(len(edges), VIEWS_MAX_EDGES) else 0.0
         return o
 
 
@@ -389,6 +415,13 @@ def _declare(lib):
     lib.flm_track_retire.restype = i
     lib.flm_track_retire.argtypes = [vp, vp, vp, i, i, i, vp, vp, sz, vp, vp, vp, i, vp, C.c_int64, i, C.POINTER(ExitOpts),
                                      vp, vp, vp, vp, i, vp, vp, vp, vp, vp, vp, vp]
+    lib.flm_views_opts_init.restype = None
+    lib.flm_views_opts_init.argtypes = [C.POINTER(ViewsOpts)]
+    lib.flm_track_views_update.restype = i
+    lib.flm_track_views_update.argtypes = [vp, vp, sz, i, vp, vp, vp, vp, sz, vp, sz, i, vp, C.c_int64, C.POINTER(ViewsOpts),
+                                           vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.flm_track_exit_views.restype = i
+    lib.flm_track_exit_views.argtypes = [vp, vp, i, i, i, sz, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
 
 
 def load():

@@ -8,6 +8,8 @@ bilinear, edge clamp -- but keeps pixel units (no [0,1] rescale) and float32.
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 from . import _lib
@@ -1491,3 +1493,228 @@ def exit_rows(seq, cursor, capacity):
         raise ValueError("0 <= cursor <= seq is needed (got cursor %d, seq %d)" % (cursor, seq))
     lost = max(seq - cursor - capacity, 0)
     return np.arange(cursor + lost, seq, dtype=np.int64) % capacity, lost
+
+
+# ---- pose-binned best shots: one best face per view of every track (include/flm.h, flm_track_views_update) -------------
+VIEWS_MAX_EDGES = _lib.VIEWS_MAX_EDGES
+
+
+class PoseViews:
+    """The pose bins of a tracker's multi-view gallery (flm_track_views_update; include/flm.h): `yaw` and `pitch`, each a
+    strictly ascending sequence of at most 7 edges in DEGREES inside (-90, 90), cut the faces of a track into
+    (len(yaw)+1) x (len(pitch)+1) bins, and the tracker keeps the best face of every bin.  The default, yaw=(-20, 20) and
+    no pitch edge, gives three views: bin 0 a face turned to the image's right (yaw < -20), bin 1 frontal, bin 2 turned to
+    the image's left.  An edge d becomes math.sin(math.radians(d)), in float64 on the host, and is compared on the device
+    with u = -R[2][0] = cos(pitch)*sin(yaw) (yaw edges) or v = R[2][1] = sin(pitch) (pitch edges) of the head-pose record:
+    a pitch edge is exact, a yaw edge is exact at pitch 0 and lies at a slightly larger yaw on a face that also looks up
+    or down.  u >= edge falls into the upper bin; bin = iv*(len(yaw)+1) + iu.  sharp_ref, min_exposed: as `BestShot`; the
+    quality of a view is min(sharpness/sharp_ref, 1) x the exposed share x the mean landmark score, WITHOUT the
+    frontality factor of the best shot -- the bin accounts for pose.  `from_edges` takes raw u and v edges."""
+
+    def __init__(self, yaw=(-20.0, 20.0), pitch=(), sharp_ref=100.0, min_exposed=0.5):
+        edges = []
+        for name, deg in (("yaw", yaw), ("pitch", pitch)):
+            try:
+                deg = [float(d) for d in deg]
+            except (TypeError, ValueError):
+                raise ValueError("%s must be a sequence of edges in degrees (got %r)" % (name, deg)) from None
+            if any(not -90.0 < d < 90.0 for d in deg):
+                raise ValueError("%s edges must lie inside (-90, 90) degrees (got %r)" % (name, deg))
+            edges.append([math.sin(math.radians(d)) for d in deg])
+        self._set(edges[0], edges[1], sharp_ref, min_exposed)
+
+    @classmethod
+    def from_edges(cls, u_edges, v_edges=(), sharp_ref=100.0, min_exposed=0.5):
+        """Raw edges: u_edges on u = -R[2][0], v_edges on v = R[2][1], each strictly ascending inside (-1, 1)."""
+        o = cls.__new__(cls)
+        o._set(u_edges, v_edges, sharp_ref, min_exposed)
+        return o
+
+    def _set(self, u_edges, v_edges, sharp_ref, min_exposed):
+        out = []
+        for name, e in (("u", u_edges), ("v", v_edges)):
+            try:
+                e = [float(x) for x in e]
+            except (TypeError, ValueError):
+                raise ValueError("%s edges must be a sequence of numbers (got %r)" % (name, e)) from None
+            if len(e) > VIEWS_MAX_EDGES:
+                raise ValueError("at most %d %s edges (got %d)" % (VIEWS_MAX_EDGES, name, len(e)))
+            if any(not -1.0 < x < 1.0 for x in e):
+                raise ValueError("%s edges must be finite and inside (-1, 1) (got %r)" % (name, e))
+            if any(not b > a for a, b in zip(e, e[1:])):
+                raise ValueError("%s edges must be strictly ascending (got %r)" % (name, e))
+            out.append(tuple(e))
+        sharp_ref, min_exposed = float(sharp_ref), float(min_exposed)
+        if not sharp_ref > 0.0:
+            raise ValueError("sharp_ref must be > 0 (got %r)" % sharp_ref)
+        if min_exposed != min_exposed:
+            raise ValueError("min_exposed must not be NaN")
+        self.u_edges, self.v_edges = out
+        self.sharp_ref, self.min_exposed = sharp_ref, min_exposed
+
+    @property
+    def bins(self):
+        return (len(self.u_edges) + 1) * (len(self.v_edges) + 1)
+
+    def struct(self):
+        return _lib.ViewsOpts.make(self.u_edges, self.v_edges, self.sharp_ref, self.min_exposed)
+
+    def __repr__(self):
+        return "PoseViews.from_edges(%r, %r, sharp_ref=%r, min_exposed=%r)" % (self.u_edges, self.v_edges, self.sharp_ref,
+                                                                               self.min_exposed)
+
+
+def _check_no_overlap(named):
+    """No two of the (tensor or None, name) pairs may share a byte."""
+    spans = sorted((t.data_ptr(), t.data_ptr() + t.numel() * t.element_size(), name) for t, name in named
+                   if t is not None and t.numel())
+    for (_, end, an), (start, _, bn) in zip(spans, spans[1:]):         # sorted by address: neighbours are enough
+        if start < end:
+            raise ValueError("%s and %s must be two buffers that do not overlap" % (an, bn))
+
+
+def _check_view_faces(t, lead, like, what):
+    """`t` is a contiguous CUDA tensor [*lead, face...] of the dtype and face shape of `like` ([N, face...])."""
+    import torch
+    nl = len(lead)
+    if (not isinstance(t, torch.Tensor) or t.dtype != like.dtype or t.dim() != like.dim() - 1 + nl
+            or tuple(t.shape[:nl]) != tuple(lead) or t.shape[nl:] != like.shape[1:] or not t.is_cuda or not t.is_contiguous()):
+        raise ValueError("%s must be a contiguous CUDA tensor [%s,...] of the dtype and face shape of the faces"
+                         % (what, ",".join(str(v) for v in lead)))
+
+
+def track_views_update_device(faces, rec, lm, pose, view_q, view_frame, view_gallery, take, frame_id, status=None,
+                              reset=None, weights=None, m=None, opts=None, slot=None, view_m=None, view_lm=None,
+                              view_pose=None):
+    """Per row, keep the face if it beats what its slot holds in the face's POSE BIN, in two launches
+    (flm_track_views_update; include/flm.h states it line by line).
+
+    faces: contiguous CUDA tensor of N faces (any format: copied as bytes); rec CUDA int64 [N,8] from
+    `face_quality_device`; lm CUDA float64 [N,C,2] and `weights` None or CUDA float64 [N,C] (both may be views of a
+    landmark record tensor, read in place); status, reset: None or CUDA int32 [N]; m: None or CUDA float32 [N,2,3];
+    frame_id: a host integer; opts: None or a `PoseViews`, B = opts.bins.  slot: None -- row r is slot r and
+    n_slots = N -- or contiguous CUDA int32 [N]: a row writes at its slot, an inert row (slot outside [0, n_slots)) and a
+    slot no row names write nothing.  pose: CUDA float64 [n_slots,18], the records `head_pose_device` wrote, read at
+    the slot.  In/out: view_q CUDA float64 [n_slots,B] (-1: the bin holds nothing), view_frame CUDA int64 [n_slots,B],
+    view_gallery [n_slots,B,...] of the faces' dtype and face shape, and view_m float32 [n_slots,B,2,3], view_lm float64
+    [n_slots,B,C,2], view_pose float64 [n_slots,B,18], each or None.  Out: take CUDA int32 [N]: the bin a row's face was
+    taken into, or -1.  A non-zero reset empties the slot's bins first; a face is taken when it is eligible, its pose is
+    ok, and its quality -- the best shot's without the pose factor -- is strictly above its bin's.  No output may
+    overlap an input or another output.  Returns take."""
+    import torch
+    if opts is None:
+        opts = PoseViews()
+    elif not isinstance(opts, PoseViews):
+        raise ValueError("opts must be None or a PoseViews (got %r)" % (opts,))
+    frame_id = _frame_id(frame_id)
+    b = opts.bins
+    if not isinstance(faces, torch.Tensor) or faces.dim() < 1 or not faces.is_cuda or not faces.is_contiguous():
+        raise ValueError("faces must be a contiguous CUDA tensor of N faces")
+    n = int(faces.shape[0])
+    if not 1 <= n <= 65535:
+        raise ValueError("1 to 65535 rows (got %d)" % n)
+    if (not isinstance(pose, torch.Tensor) or pose.dtype != torch.float64 or pose.dim() != 2 or int(pose.shape[1]) != POSE_REC
+            or not pose.is_cuda or not pose.is_contiguous() or not 1 <= int(pose.shape[0]) <= 65535):
+        raise ValueError("pose must be a contiguous CUDA float64 [n_slots,%d] tensor of 1 to 65535 slots" % POSE_REC)
+    n_slots = int(pose.shape[0])
+    if slot is None:
+        if n_slots != n:
+            raise ValueError("without slot, pose must have one record per face ([%d,%d], got %d)" % (n, POSE_REC, n_slots))
+    else:
+        _check_out(slot, torch.int32, (n,), "slot")
+    _check_out(rec, torch.int64, (n, QUALITY_REC), "rec")
+    lm, ls = _strided_points(lm)
+    c = int(lm.shape[1])
+    if int(lm.shape[0]) != n or not 1 <= c <= 1024:
+        raise ValueError("lm must be a CUDA float64 [%d,C,2] tensor, 1 <= C <= 1024" % n)
+    weights, wst = _weights_arg(weights, n, c)
+    for t, name in ((status, "status"), (reset, "reset")):
+        if t is not None:
+            _check_out(t, torch.int32, (n,), name)
+    if m is not None:
+        _check_matrices(m, n)
+    _check_out(view_q, torch.float64, (n_slots, b), "view_q")
+    _check_out(view_frame, torch.int64, (n_slots, b), "view_frame")
+    _check_view_faces(view_gallery, (n_slots, b), faces, "view_gallery")
+    _check_out(take, torch.int32, (n,), "take")
+    if view_m is not None:
+        if m is None:
+            raise ValueError("view_m needs m")
+        _check_out(view_m, torch.float32, (n_slots, b, 2, 3), "view_m")
+    if view_lm is not None:
+        _check_out(view_lm, torch.float64, (n_slots, b, c, 2), "view_lm")
+    if view_pose is not None:
+        _check_out(view_pose, torch.float64, (n_slots, b, POSE_REC), "view_pose")
+    outs = [(view_q, "view_q"), (view_frame, "view_frame"), (view_gallery, "view_gallery"), (view_m, "view_m"),
+            (view_lm, "view_lm"), (view_pose, "view_pose"), (take, "take")]
+    _check_no_overlap(outs)
+    for a, an in ((faces, "faces"), (rec, "rec"), (lm, "lm"), (weights, "weights"), (status, "status"), (reset, "reset"),
+                  (m, "m"), (slot, "slot"), (pose, "pose")):
+        for o, on in outs:
+            _check_span_overlap(a, o, "%s and %s" % (an, on))
+    co = opts.struct()
+    _lib.check(_lib.load().flm_track_views_update(
+        _lib.stream_ptr(), _lib.ptr(faces), faces.numel() // n * faces.element_size(), n, _lib.ptr(rec), _ptr(status),
+        _ptr(reset), _lib.ptr(lm), ls, _ptr(weights), wst, c, _ptr(m), frame_id, _lib.C.byref(co), _ptr(slot), n_slots,
+        _lib.ptr(pose), _lib.ptr(view_q), _lib.ptr(view_frame), _lib.ptr(view_gallery), _ptr(view_m), _ptr(view_lm),
+        _ptr(view_pose), _lib.ptr(take)), "flm_track_views_update")
+    return take
+
+
+def track_exit_views_device(exit_row, view_q, view_frame, view_gallery, x_view_q, x_view_frame, x_view_gallery, view_m=None,
+                            view_lm=None, view_pose=None, x_view_m=None, x_view_lm=None, x_view_pose=None):
+    """The views of the tracks `track_retire_device` has just written, into the exit ring, in one launch
+    (flm_track_exit_views; include/flm.h).
+
+    exit_row: CUDA int32 [K], what that retire call returned.  view_q CUDA float64 [K,B], view_frame CUDA int64 [K,B],
+    view_gallery a contiguous CUDA tensor [K,B,...] (any format: copied as bytes): the views as
+    `track_views_update_device` keeps them; view_m float32 [K,B,2,3], view_lm float64 [K,B,C,2], view_pose float64
+    [K,B,18]: each None or given together with its ring counterpart.  The ring of Q rows: x_view_q [Q,B], x_view_frame
+    [Q,B], x_view_gallery [Q,B,...] of the gallery's dtype and face shape, x_view_m, x_view_lm, x_view_pose.  Ring row
+    exit_row[t] >= 0 receives slot t's B qualities and frame ids and, for every bin whose quality is >= 0, the bin's
+    face, matrix, landmarks and pose; an empty bin leaves its ring bytes as they were, and so does every slot whose
+    exit_row is negative.  No two tensors may overlap.  Returns x_view_q."""
+    import torch
+    if (not isinstance(view_q, torch.Tensor) or view_q.dim() != 2 or not 1 <= int(view_q.shape[0]) <= 65535
+            or not 1 <= int(view_q.shape[1]) <= 64):
+        raise ValueError("view_q must be a contiguous CUDA float64 [K,B] tensor, 1 <= K <= 65535, 1 <= B <= 64")
+    k, b = int(view_q.shape[0]), int(view_q.shape[1])
+    _check_out(view_q, torch.float64, (k, b), "view_q")
+    _check_out(exit_row, torch.int32, (k,), "exit_row")
+    _check_out(view_frame, torch.int64, (k, b), "view_frame")
+    if (not isinstance(x_view_q, torch.Tensor) or x_view_q.dim() != 2 or not 1 <= int(x_view_q.shape[0]) <= 65535):
+        raise ValueError("x_view_q must be a contiguous CUDA float64 [Q,%d] tensor, 1 <= Q <= 65535" % b)
+    q = int(x_view_q.shape[0])
+    _check_out(x_view_q, torch.float64, (q, b), "x_view_q")
+    _check_out(x_view_frame, torch.int64, (q, b), "x_view_frame")
+    if (not isinstance(view_gallery, torch.Tensor) or view_gallery.dim() < 2 or tuple(view_gallery.shape[:2]) != (k, b)
+            or not view_gallery.is_cuda or not view_gallery.is_contiguous() or view_gallery.numel() < k * b):
+        raise ValueError("view_gallery must be a contiguous CUDA tensor of [%d,%d] faces" % (k, b))
+    _check_view_faces(x_view_gallery, (q, b), view_gallery[:, 0], "x_view_gallery")
+    for s, x, what in ((view_m, x_view_m, "view_m and x_view_m"), (view_lm, x_view_lm, "view_lm and x_view_lm"),
+                       (view_pose, x_view_pose, "view_pose and x_view_pose")):
+        if (s is None) != (x is None):
+            raise ValueError("%s go together: both or neither" % what)
+    c = 1
+    if view_m is not None:
+        _check_out(view_m, torch.float32, (k, b, 2, 3), "view_m")
+        _check_out(x_view_m, torch.float32, (q, b, 2, 3), "x_view_m")
+    if view_lm is not None:
+        if not isinstance(view_lm, torch.Tensor) or view_lm.dim() != 4 or not 1 <= int(view_lm.shape[2]) <= 1024:
+            raise ValueError("view_lm must be a contiguous CUDA float64 [%d,%d,C,2] tensor, 1 <= C <= 1024" % (k, b))
+        c = int(view_lm.shape[2])
+        _check_out(view_lm, torch.float64, (k, b, c, 2), "view_lm")
+        _check_out(x_view_lm, torch.float64, (q, b, c, 2), "x_view_lm")
+    if view_pose is not None:
+        _check_out(view_pose, torch.float64, (k, b, POSE_REC), "view_pose")
+        _check_out(x_view_pose, torch.float64, (q, b, POSE_REC), "x_view_pose")
+    _check_no_overlap([(exit_row, "exit_row"), (view_q, "view_q"), (view_frame, "view_frame"), (view_gallery, "view_gallery"),
+                       (view_m, "view_m"), (view_lm, "view_lm"), (view_pose, "view_pose"), (x_view_q, "x_view_q"),
+                       (x_view_frame, "x_view_frame"), (x_view_gallery, "x_view_gallery"), (x_view_m, "x_view_m"),
+                       (x_view_lm, "x_view_lm"), (x_view_pose, "x_view_pose")])
+    _lib.check(_lib.load().flm_track_exit_views(
+        _lib.stream_ptr(), _lib.ptr(exit_row), k, q, b, view_gallery.numel() // (k * b) * view_gallery.element_size(), c,
+        _lib.ptr(view_q), _lib.ptr(view_frame), _lib.ptr(view_gallery), _ptr(view_m), _ptr(view_lm), _ptr(view_pose),
+        _lib.ptr(x_view_q), _lib.ptr(x_view_frame), _lib.ptr(x_view_gallery), _ptr(x_view_m), _ptr(x_view_lm),
+        _ptr(x_view_pose)), "flm_track_exit_views")
+    return x_view_q

@@ -40,6 +40,7 @@ SOURCES = [
     "flm_track_assoc.hip",
     "flm_quality.hip",
     "flm_track_exit.hip",
+    "flm_track_views.hip",
     "flm_pose.hip",
     "flm_mobile.hip",
 ]

@@ -1813,4 +1813,201 @@ int flm_head_pose(flm_stream_t stream, const double* lm, size_t lm_stride, const
                           n_slots, pose, factor);
 }
 
+// ---- pose-binned best shots (flm_track_views.hip) -------------------------------------------------------------------
+
+void flm_views_opts_init(flm_views_opts* opts) {
+  if (!opts) return;
+  memset(opts, 0, sizeof(*opts));
+  opts->struct_size = (uint32_t)sizeof(flm_views_opts);
+  opts->sharp_ref = 100.0;
+  opts->min_exposed = 0.5;
+  opts->n_u = 2;
+  opts->u_edge[0] = -0.3420201433256687;  // -+sin(20 degrees): right, frontal, left
+  opts->u_edge[1] = 0.3420201433256687;
+  opts->n_v = 0;
+}
+
+static int check_view_edges(const char* who, const char* axis, int n, const double* edge) {
+  if (n < 0 || n > FLM_VIEWS_MAX_EDGES) {
+    set_error("%s: n_%s=%d, needs 0 <= n_%s <= %d", who, axis, n, axis, FLM_VIEWS_MAX_EDGES);
+    return FLM_ERR_ARG;
+  }
+  for (int i = 0; i < n; ++i) {
+    if (!(edge[i] > -1.0 && edge[i] < 1.0)) {  // (false for a NaN and for an infinity)
+      set_error("%s: %s_edge[%d]=%g, needs a finite edge inside (-1, 1)", who, axis, i, edge[i]);
+      return FLM_ERR_ARG;
+    }
+    if (i > 0 && !(edge[i] > edge[i - 1])) {
+      set_error("%s: %s_edge[%d]=%g after %g, needs strictly ascending edges", who, axis, i, edge[i], edge[i - 1]);
+      return FLM_ERR_ARG;
+    }
+  }
+  return FLM_OK;
+}
+
+struct NamedRange {
+  const void* p;
+  size_t bytes;
+  const char* name;
+};
+
+int flm_track_views_update(flm_stream_t stream, const void* faces, size_t face_bytes, int n, const int64_t* rec,
+                           const int32_t* status_rows, const int32_t* reset, const double* lm, size_t lm_stride,
+                           const double* wt, size_t w_stride, int c, const float* m, int64_t frame_id,
+                           const flm_views_opts* opts, const int32_t* slot, int n_slots, const double* pose, double* view_q,
+                           int64_t* view_frame, void* view_gallery, float* view_m, double* view_lm, double* view_pose,
+                           int32_t* take) {
+  const char* who = "flm_track_views_update";
+  if (!faces || !rec || !lm || !pose || !view_q || !view_frame || !view_gallery || !take) {
+    set_error("%s: null argument", who);  // (status, reset, w, m, opts, slot and the three view_m/lm/pose are optional)
+    return FLM_ERR_ARG;
+  }
+  if (view_m && !m) {
+    set_error("%s: view_m needs m_dev", who);
+    return FLM_ERR_ARG;
+  }
+  flm_views_opts defaults;
+  flm_views_opts_init(&defaults);
+  if (!opts) opts = &defaults;
+  if (opts->struct_size < sizeof(flm_views_opts)) {
+    set_error("%s: flm_views_opts struct_size %u is smaller than this library's %zu (initialise with "
+              "flm_views_opts_init)", who, opts->struct_size, sizeof(flm_views_opts));
+    return FLM_ERR_ARG;
+  }
+  if (opts->reserved != 0) {
+    set_error("%s: flm_views_opts reserved=%u, must be 0", who, opts->reserved);
+    return FLM_ERR_ARG;
+  }
+  if (!(opts->sharp_ref > 0.0)) {
+    set_error("%s: sharp_ref=%g, needs sharp_ref > 0", who, opts->sharp_ref);
+    return FLM_ERR_ARG;
+  }
+  if (std::isnan(opts->min_exposed)) {
+    set_error("%s: min_exposed must not be NaN", who);
+    return FLM_ERR_ARG;
+  }
+  if (const int rc = check_view_edges(who, "u", opts->n_u, opts->u_edge)) return rc;
+  if (const int rc = check_view_edges(who, "v", opts->n_v, opts->v_edge)) return rc;
+  if (n < 1 || n > 65535) {
+    set_error("%s: n=%d, needs 1 <= n <= 65535", who, n);
+    return FLM_ERR_SHAPE;
+  }
+  if (slot && (n_slots < 1 || n_slots > 65535)) {
+    set_error("%s: n_slots=%d, needs 1 <= n_slots <= 65535", who, n_slots);
+    return FLM_ERR_SHAPE;
+  }
+  if (!slot) n_slots = n;
+  if (c < 1 || c > 1024) {
+    set_error("%s: c=%d, needs 1 <= c <= 1024", who, c);
+    return FLM_ERR_SHAPE;
+  }
+  if (face_bytes < 1) {
+    set_error("%s: face_bytes=0, needs face_bytes >= 1", who);
+    return FLM_ERR_SHAPE;
+  }
+  if (lm_stride < 2 || (wt && w_stride < 1)) {
+    set_error("%s: lm_stride=%zu, w_stride=%zu, needs lm_stride >= 2 and w_stride >= 1", who, lm_stride, w_stride);
+    return FLM_ERR_SHAPE;
+  }
+  const int bins = (opts->n_u + 1) * (opts->n_v + 1);
+  const size_t sn = (size_t)n, ss = (size_t)n_slots * bins, sc = (size_t)c;
+  const size_t last = sn * sc - 1;  // the last landmark read
+  const NamedRange in[] = {
+      {faces, sn * face_bytes, "faces_dev"}, {rec, sn * FLM_QUALITY_REC * 8, "rec_dev"},
+      {status_rows, sn * 4, "status_rows_dev"}, {reset, sn * 4, "reset_dev"},
+      {lm, (last * lm_stride + 2) * sizeof(double), "lm_dev"}, {wt, (last * w_stride + 1) * sizeof(double), "w_dev"},
+      {m, sn * 24, "m_dev"}, {slot, sn * 4, "slot_dev"}, {pose, (size_t)n_slots * FLM_POSE_REC * 8, "pose_dev"}};
+  const NamedRange out[] = {
+      {view_q, ss * 8, "view_q"}, {view_frame, ss * 8, "view_frame"}, {view_gallery, ss * face_bytes, "view_gallery"},
+      {view_m, ss * 24, "view_m"}, {view_lm, ss * sc * 16, "view_lm"}, {view_pose, ss * FLM_POSE_REC * 8, "view_pose"},
+      {take, sn * 4, "take_dev"}};
+  const int n_out = (int)(sizeof(out) / sizeof(out[0]));
+  for (int i = 0; i < n_out; ++i) {
+    if (!out[i].p) continue;
+    for (const auto& a : in)
+      if (a.p && ranges_overlap(out[i].p, out[i].bytes, a.p, a.bytes)) {
+        set_error("%s: %s and %s overlap (no output may overlap an input)", who, out[i].name, a.name);
+        return FLM_ERR_ARG;
+      }
+    for (int j = i + 1; j < n_out; ++j)
+      if (out[j].p && ranges_overlap(out[i].p, out[i].bytes, out[j].p, out[j].bytes)) {
+        set_error("%s: %s and %s overlap (no two outputs may)", who, out[i].name, out[j].name);
+        return FLM_ERR_ARG;
+      }
+  }
+  TrackViewsArgs g;
+  g.faces = static_cast<const unsigned char*>(faces);
+  g.face_bytes = face_bytes;
+  g.n = n; g.n_slots = n_slots; g.c = c; g.bins = bins;
+  g.rec = rec; g.status = status_rows; g.reset = reset;
+  g.lm = lm; g.lm_stride = lm_stride; g.wt = wt; g.w_stride = w_stride; g.m = m; g.frame_id = frame_id;
+  g.sharp_ref = opts->sharp_ref; g.min_exposed = opts->min_exposed;
+  g.n_u = opts->n_u; g.n_v = opts->n_v;
+  for (int i = 0; i < FLM_VIEWS_MAX_EDGES; ++i) {  // (the edges not in use are never compared: zeros keep the struct defined)
+    g.u_edge[i] = i < opts->n_u ? opts->u_edge[i] : 0.0;
+    g.v_edge[i] = i < opts->n_v ? opts->v_edge[i] : 0.0;
+  }
+  g.slot = slot; g.pose = pose;
+  g.view_q = view_q; g.view_frame = view_frame; g.view_gallery = static_cast<unsigned char*>(view_gallery);
+  g.view_m = view_m; g.view_lm = view_lm; g.view_pose = view_pose; g.take = take;
+  return launch_track_views_update(static_cast<hipStream_t>(stream), g);
+}
+
+int flm_track_exit_views(flm_stream_t stream, const int32_t* exit_row, int k, int q, int bins, size_t face_bytes, int c,
+                         const double* view_q, const int64_t* view_frame, const void* view_gallery, const float* view_m,
+                         const double* view_lm, const double* view_pose, double* x_view_q, int64_t* x_view_frame,
+                         void* x_view_gallery, float* x_view_m, double* x_view_lm, double* x_view_pose) {
+  const char* who = "flm_track_exit_views";
+  if (!exit_row || !view_q || !view_frame || !view_gallery || !x_view_q || !x_view_frame || !x_view_gallery) {
+    set_error("%s: null argument", who);  // (the three pairs view_m/x_view_m, view_lm/x_view_lm, view_pose/x_view_pose are optional)
+    return FLM_ERR_ARG;
+  }
+  if (!view_m != !x_view_m || !view_lm != !x_view_lm || !view_pose != !x_view_pose) {
+    set_error("%s: view_m goes with x_view_m, view_lm with x_view_lm and view_pose with x_view_pose: both or neither", who);
+    return FLM_ERR_ARG;
+  }
+  if (k < 1 || k > 65535) {
+    set_error("%s: k=%d, needs 1 <= k <= 65535", who, k);
+    return FLM_ERR_SHAPE;
+  }
+  if (q < 1 || q > 65535) {
+    set_error("%s: q=%d, needs 1 <= q <= 65535", who, q);
+    return FLM_ERR_SHAPE;
+  }
+  if (bins < 1 || bins > 64) {
+    set_error("%s: bins=%d, needs 1 <= bins <= 64", who, bins);
+    return FLM_ERR_SHAPE;
+  }
+  if (c < 1 || c > 1024) {
+    set_error("%s: c=%d, needs 1 <= c <= 1024", who, c);
+    return FLM_ERR_SHAPE;
+  }
+  if (face_bytes < 1) {
+    set_error("%s: face_bytes=0, needs face_bytes >= 1", who);
+    return FLM_ERR_SHAPE;
+  }
+  const size_t sk = (size_t)k * bins, sq = (size_t)q * bins, sc = (size_t)c;
+  const NamedRange bufs[] = {
+      {exit_row, (size_t)k * 4, "exit_row_dev"}, {view_q, sk * 8, "view_q"}, {view_frame, sk * 8, "view_frame"},
+      {view_gallery, sk * face_bytes, "view_gallery"}, {view_m, sk * 24, "view_m"}, {view_lm, sk * sc * 16, "view_lm"},
+      {view_pose, sk * FLM_POSE_REC * 8, "view_pose"}, {x_view_q, sq * 8, "x_view_q"},
+      {x_view_frame, sq * 8, "x_view_frame"}, {x_view_gallery, sq * face_bytes, "x_view_gallery"},
+      {x_view_m, sq * 24, "x_view_m"}, {x_view_lm, sq * sc * 16, "x_view_lm"},
+      {x_view_pose, sq * FLM_POSE_REC * 8, "x_view_pose"}};
+  const int nb = (int)(sizeof(bufs) / sizeof(bufs[0]));
+  for (int i = 0; i < nb; ++i)
+    for (int j = i + 1; j < nb; ++j)
+      if (bufs[i].p && bufs[j].p && ranges_overlap(bufs[i].p, bufs[i].bytes, bufs[j].p, bufs[j].bytes)) {
+        set_error("%s: %s and %s overlap (no two arguments may)", who, bufs[i].name, bufs[j].name);
+        return FLM_ERR_ARG;
+      }
+  TrackExitViewsArgs g;
+  g.exit_row = exit_row; g.k = k; g.q = q; g.bins = bins; g.c = c; g.face_bytes = face_bytes;
+  g.view_q = view_q; g.view_frame = view_frame; g.view_gallery = static_cast<const unsigned char*>(view_gallery);
+  g.view_m = view_m; g.view_lm = view_lm; g.view_pose = view_pose;
+  g.x_view_q = x_view_q; g.x_view_frame = x_view_frame; g.x_view_gallery = static_cast<unsigned char*>(x_view_gallery);
+  g.x_view_m = x_view_m; g.x_view_lm = x_view_lm; g.x_view_pose = x_view_pose;
+  return launch_track_exit_views(static_cast<hipStream_t>(stream), g);
+}
+
 }  // extern "C"

@@ -375,6 +375,55 @@ int launch_head_pose(hipStream_t s, const double* lm, size_t lm_stride, const do
                      const int32_t* idx, const double* xyz, int p, const flm_pose_opts* opts,
                      const int32_t* slot /*null: row r writes record r*/, int n_slots, double* pose, double* factor);
 
+// pose-binned best shots (flm_track_views.hip): the arguments of the two calls under the names of include/flm.h; pointers,
+// their pairing, the option struct, sizes and overlaps have been checked by the caller
+struct TrackViewsArgs {
+  const unsigned char* faces;  // [N,face_bytes]
+  size_t face_bytes;
+  int n, n_slots, c, bins;
+  const int64_t* rec;          // [N,8]
+  const int32_t* status;       // [N] or null
+  const int32_t* reset;        // [N] or null
+  const double* lm;
+  size_t lm_stride;
+  const double* wt;            // or null
+  size_t w_stride;
+  const float* m;              // [N,2,3] or null
+  int64_t frame_id;
+  double sharp_ref, min_exposed;
+  int n_u, n_v;
+  double u_edge[FLM_VIEWS_MAX_EDGES], v_edge[FLM_VIEWS_MAX_EDGES];
+  const int32_t* slot;         // [N] or null: row == slot
+  const double* pose;          // [n_slots,18]
+  double* view_q;              // [n_slots,B] in/out
+  int64_t* view_frame;         // [n_slots,B]
+  unsigned char* view_gallery; // [n_slots,B,face_bytes]
+  float* view_m;               // [n_slots,B,2,3] or null
+  double* view_lm;             // [n_slots,B,C,2] or null
+  double* view_pose;           // [n_slots,B,18] or null
+  int32_t* take;               // [N]
+};
+int launch_track_views_update(hipStream_t s, const TrackViewsArgs& g);
+
+struct TrackExitViewsArgs {
+  const int32_t* exit_row;     // [K]
+  int k, q, bins, c;
+  size_t face_bytes;
+  const double* view_q;        // [K,B]
+  const int64_t* view_frame;   // [K,B]
+  const unsigned char* view_gallery;
+  const float* view_m;         // [K,B,2,3] or null, with x_view_m
+  const double* view_lm;       // [K,B,C,2] or null, with x_view_lm
+  const double* view_pose;     // [K,B,18] or null, with x_view_pose
+  double* x_view_q;            // [Q,B]
+  int64_t* x_view_frame;       // [Q,B]
+  unsigned char* x_view_gallery;
+  float* x_view_m;
+  double* x_view_lm;
+  double* x_view_pose;
+};
+int launch_track_exit_views(hipStream_t s, const TrackExitViewsArgs& g);
+
 // Bijective XCD-aware remap of a 1-D grid: blocks that the dispatcher deals to the same XCD
 // (b % 8) receive consecutive logical ids, so neighbours in logical order share an L2.
 __device__ __forceinline__ int xcd_remap(int b, int nblk) {

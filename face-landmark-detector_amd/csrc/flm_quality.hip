@@ -20,7 +20,9 @@
 // cut at 16-byte boundaries as above, with 16-byte accesses where source and destination are congruent modulo 16.
 // flm_track_best_update_rows is the same body on the rows of a compacted batch: everything the decision reads lies at the
 // ROW, everything written at the row's SLOT; an inert row's workgroups return before they read anything else.
+#include "flm_best_dev.h"
 #include "flm_common.h"
+#include "flm_copy_dev.h"
 #include "flm_quality_dev.h"
 
 namespace flm {
@@ -232,37 +234,15 @@ struct BestArgs {
 
 constexpr int kBestThreads = 256, kBestChunk = kBestThreads * 16;  // bytes a workgroup copies per trip
 
-// The quality of slot `slot` as the header states it, one float64 operation per line; *eligible says whether it counts.
+// The quality of slot `slot` as the header states it, one float64 operation per line (flm_best_dev.h holds the terms
+// flm_track_views_update shares); *eligible says whether it counts.
 __device__ __forceinline__ double best_quality(const BestArgs& g, int slot, bool* eligible) {
-  const int64_t* r = g.rec + (size_t)slot * FLM_QUALITY_REC;
-  const int64_t n_pix = r[0], n_lap = r[3], s_l = r[4], s_ll = r[5], n_dark = r[6], n_bright = r[7];
-  const double nl = (double)n_lap;
-  const double mu = (double)s_l / nl;
-  const double m2 = (double)s_ll / nl;
-  const double mm = mu * mu;
-  const double var = m2 - mm;
-  const double sharp = fmax(var / 256.0, 0.0);
-  const double sh = fmin(sharp / g.sharp_ref, 1.0);
-  const double e = (double)(n_pix - n_dark - n_bright) / (double)n_pix;
-  double wbar = 1.0;
-  if (g.wt) {
-    double sum = 0.0;
-    int n = 0;
-    const double* lm = g.lm + (size_t)slot * g.c * g.lm_stride;
-    const double* wt = g.wt + (size_t)slot * g.c * g.w_stride;
-    for (int i = 0; i < g.c; ++i) {
-      const double x = lm[(size_t)i * g.lm_stride], y = lm[(size_t)i * g.lm_stride + 1];
-      if (x == -1.0 && y == -1.0) continue;
-      sum = sum + wt[(size_t)i * g.w_stride];
-      ++n;
-    }
-    wbar = n ? sum / (double)n : 0.0;
-  }
+  const BestTerms t = best_terms(g.rec + (size_t)slot * FLM_QUALITY_REC, g.lm + (size_t)slot * g.c * g.lm_stride,
+                                 g.lm_stride, g.wt ? g.wt + (size_t)slot * g.c * g.w_stride : nullptr, g.w_stride, g.c,
+                                 g.sharp_ref);
   const double f = g.factor ? g.factor[slot] : 1.0;
-  const double se = sh * e;
-  const double sew = se * wbar;
-  const double q = sew * f;
-  *eligible = (!g.status || g.status[slot] == 0) && n_lap > 0 && e >= g.min_exposed && q >= 0.0;  // (q >= 0: no NaN)
+  const double q = t.sew * f;
+  *eligible = (!g.status || g.status[slot] == 0) && t.n_lap > 0 && t.e >= g.min_exposed && q >= 0.0;  // (q >= 0: no NaN)
   return q;
 }
 
@@ -295,23 +275,9 @@ __device__ __forceinline__ void track_best_body(const BestArgs& g, int slot, siz
     }
   }
 
-  // the face: pieces of 16 bytes at the 16-byte lines of the SOURCE address
-  const unsigned char* src = g.faces + (size_t)slot * g.face_bytes;
-  unsigned char* dst = g.gallery + gs * g.face_bytes;
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(src), a1 = a0 + g.face_bytes;
-  const uintptr_t base = a0 & ~(uintptr_t)15;
-  const bool congruent = ((a0 ^ reinterpret_cast<uintptr_t>(dst)) & 15u) == 0;
-  const size_t pieces = (size_t)((a1 - base + 15) >> 4);
-  for (size_t j = (size_t)blockIdx.x * kBestThreads + tid; j < pieces; j += (size_t)gridDim.x * kBestThreads) {
-    const uintptr_t lo = base + 16 * j, hi = lo + 16;
-    if (congruent && lo >= a0 && hi <= a1) {
-      const q4v v = *reinterpret_cast<const q4v*>(lo);
-      *reinterpret_cast<q4v*>(dst + (lo - a0)) = v;
-    } else {
-      const uintptr_t s = lo > a0 ? lo : a0, e = hi < a1 ? hi : a1;
-      for (uintptr_t q = s; q < e; ++q) dst[q - a0] = *reinterpret_cast<const unsigned char*>(q);
-    }
-  }
+  // the face: pieces of 16 bytes at the 16-byte lines of the SOURCE address (flm_copy_dev.h)
+  copy_row_bytes(g.faces + (size_t)slot * g.face_bytes, g.gallery + gs * g.face_bytes, g.face_bytes,
+                 (size_t)blockIdx.x * kBestThreads + tid, (size_t)gridDim.x * kBestThreads);
 }
 
 __global__ __launch_bounds__(kBestThreads) void track_best_kernel(const BestArgs g) {

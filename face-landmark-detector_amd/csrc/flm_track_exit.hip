@@ -12,11 +12,10 @@
 //       others move the slot's gallery bytes -- and, workgroup 0 of the slot, its landmarks -- into the ring row.  It
 //       reads exit_row and buffers no launch writes meanwhile.
 #include "flm_common.h"
+#include "flm_copy_dev.h"
 #include "flm_track_exit_dev.h"
 
 namespace flm {
-
-typedef unsigned x4v __attribute__((ext_vector_type(4)));
 
 constexpr int kExitCopyThreads = 256, kExitCopyChunk = kExitCopyThreads * 16 * 4;  // bytes a workgroup is dealt
 
@@ -105,7 +104,8 @@ __global__ __launch_bounds__(1024) void track_exit_decide_kernel(const TrackExit
 }
 
 // The face of every written track, and its landmarks: pieces of 16 bytes at the 16-byte lines of the SOURCE address, as
-// track_best_body copies them; element accesses where the two addresses are not congruent and at the row's two ends.
+// track_best_body copies them (flm_copy_dev.h); element accesses where the two addresses are not congruent and at the
+// row's two ends.
 __global__ __launch_bounds__(kExitCopyThreads) void track_exit_copy_kernel(const TrackExitArgs g) {
   const int t = blockIdx.y, tid = threadIdx.x;
   const int row = g.exit_row[t];
@@ -115,22 +115,8 @@ __global__ __launch_bounds__(kExitCopyThreads) void track_exit_copy_kernel(const
     double* lo = g.x_lm + (size_t)row * g.c * 2;
     for (int i = tid; i < 2 * g.c; i += kExitCopyThreads) lo[i] = li[i];
   }
-  const unsigned char* src = g.gallery + (size_t)t * g.face_bytes;
-  unsigned char* dst = g.x_gallery + (size_t)row * g.face_bytes;
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(src), a1 = a0 + g.face_bytes;
-  const uintptr_t base = a0 & ~(uintptr_t)15;
-  const bool congruent = ((a0 ^ reinterpret_cast<uintptr_t>(dst)) & 15u) == 0;
-  const size_t pieces = (size_t)((a1 - base + 15) >> 4);
-  for (size_t j = (size_t)blockIdx.x * kExitCopyThreads + tid; j < pieces; j += (size_t)gridDim.x * kExitCopyThreads) {
-    const uintptr_t lo = base + 16 * j, hi = lo + 16;
-    if (congruent && lo >= a0 && hi <= a1) {
-      const x4v v = *reinterpret_cast<const x4v*>(lo);
-      *reinterpret_cast<x4v*>(dst + (lo - a0)) = v;
-    } else {
-      const uintptr_t s = lo > a0 ? lo : a0, e = hi < a1 ? hi : a1;
-      for (uintptr_t p = s; p < e; ++p) dst[p - a0] = *reinterpret_cast<const unsigned char*>(p);
-    }
-  }
+  copy_row_bytes(g.gallery + (size_t)t * g.face_bytes, g.x_gallery + (size_t)row * g.face_bytes, g.face_bytes,
+                 (size_t)blockIdx.x * kExitCopyThreads + tid, (size_t)gridDim.x * kExitCopyThreads);
 }
 
 int launch_track_retire(hipStream_t s, const TrackExitArgs& g) {

@@ -656,13 +656,31 @@ class FaceTracker:
     A reborn slot's `best()` row is the previous track's until that slot's first step (true without `exits` too); with
     `exits` the previous track has been queued by then, and a track that ends before its slot was ever stepped has no
     best shot of its own and is discarded (the retire call reads a best_q of -1 for such a slot).  Without `exits` the tracker makes no additional launch and no additional
-    allocation."""
+    allocation.  views: None, True (the defaults: right, frontal and left at a yaw of 20 degrees) or an
+    `alignment.PoseViews`, for a tracker with both `best_shot` and `pose`: beside the one best shot the tracker keeps the
+    best face of every POSE BIN of a track (alignment.track_views_update_device, two more launches per step, after the
+    best update and with its pending resets; the quality of a view is the best shot's without the frontality factor, so a
+    sharp profile wins its own bin).  It then owns, over the B = views.bins bins of every slot, `view_gallery`
+    [capacity,B,...] in the aligned format, `view_q` float64 [capacity,B] (-1: the bin holds nothing), `view_frame` int64
+    [capacity,B], `view_M` float32 [capacity,B,2,3], `view_landmarks` float64 [capacity,B,C,2] and `view_pose` float64
+    [capacity,B,18]; `views()` hands them out.  A reborn slot's first served step starts from empty bins.  With `exits`
+    every retire call is followed by alignment.track_exit_views_device (one more launch), which moves the views of the
+    tracks that call queued into `exit_view_gallery` [Q,B,...], `exit_view_q`, `exit_view_frame`, `exit_view_M`,
+    `exit_view_landmarks` and `exit_view_pose`, row for row beside the exit ring; `exit_views()` hands them out, and a
+    consumer enrols the bins of a row whose `exit_view_q` is >= 0.  A tracker made without `views` launches nothing more,
+    allocates nothing more and returns the same bits."""
 
     def __init__(self, model, frame_hw, capacity, out_size=(112, 112), template=None, crop_template=None, n_points=4,
                  thresh=0.0, weights=None, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"),
                  crop_samples=1, samples=1, aligned_format=None, frame_format=None, smooth=None, associate=None,
-                 best_shot=None, streams=1, pose=None, exits=None):
+                 best_shot=None, streams=1, pose=None, exits=None, views=None):
         import torch
+        if views is True:
+            views = alignment.PoseViews()
+        if views is not None and not isinstance(views, alignment.PoseViews):
+            raise ValueError("views must be None, True or an alignment.PoseViews (got %r)" % (views,))
+        if views is not None and (best_shot is None or best_shot is False or pose is None or pose is False):
+            raise ValueError("views needs both best_shot and pose: a view is the best face of a pose bin")
         if exits is not None and not isinstance(exits, alignment.TrackExits):
             if isinstance(exits, bool) or not isinstance(exits, (int, np.integer)):
                 raise ValueError("exits must be None, a ring size or an alignment.TrackExits (got %r)" % (exits,))
@@ -726,6 +744,7 @@ class FaceTracker:
         self.best_shot, self.gallery, self._steps = best_shot, None, 0
         self.head_pose, self.pose = pose, None
         self.exit_opts, self.track_id = exits, None
+        self.view_opts, self.view_q = views, None
         self._head_model = None if pose is None else pose.model_for(c)
         self._ws_active = None   # the forward workspace of step_active (_active_workspace)
         self._waiting = False    # step_live has run below capacity: slot_age may hold a wait (_served)
@@ -784,6 +803,24 @@ class FaceTracker:
             empty = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, -1.0, -1.0] + [0.0] * 6
             self.pose = torch.tensor(empty, dtype=torch.float64, device=dev).repeat(n, 1).contiguous()
             self._pose_factor = torch.zeros((n,), dtype=torch.float64, device=dev) if self.best_shot is not None else None
+        if self.view_opts is not None:  # -1: the bin holds nothing
+            b = self.view_opts.bins
+            face = tuple(self.gallery.shape[1:])
+
+            def ring(rows):
+                return dict(gallery=torch.zeros(fmt.shape(rows * b, *self.out_size), dtype=fmt.torch_dtype,
+                                                device=dev).view((rows, b) + face),
+                            q=torch.full((rows, b), -1.0, dtype=torch.float64, device=dev),
+                            frame=torch.full((rows, b), -1, dtype=torch.int64, device=dev),
+                            M=torch.zeros((rows, b, 2, 3), dtype=torch.float32, device=dev),
+                            landmarks=torch.full((rows, b, c, 2), -1.0, dtype=torch.float64, device=dev),
+                            pose=self.pose[:1].repeat(rows * b, 1).view(rows, b, alignment.POSE_REC).contiguous())
+            for name, t in ring(n).items():
+                setattr(self, "view_" + name, t)
+            self._view_take = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            if self.exit_opts is not None:
+                for name, t in ring(self.exit_opts.capacity).items():
+                    setattr(self, "exit_view_" + name, t)
 
     def seed(self, slots, boxes, stream=None):
         """Start (or restart) the tracks `slots` from the detector boxes `boxes` (x0,y0,x1,y1), one per slot: the host
@@ -1028,6 +1065,13 @@ class FaceTracker:
             best_update(aligned, rec, lm_frame, status, gallery=self.gallery, best_frame=self.best_frame, frame_id=frame_id,
                         weights=wd, m=m_align, opts=self.best_shot, best_m=self.best_M, best_lm=self.best_landmarks,
                         best_rec=self.best_rec, **factor)
+            if self.view_opts is not None:   # the best update's own pending resets: the caller zeroes them after this
+                n = int(aligned.shape[0])
+                alignment.track_views_update_device(
+                    aligned, rec, lm_frame, self.pose, self.view_q, self.view_frame, self.view_gallery, self._view_take[:n],
+                    frame_id, status=status, reset=src.get("reset", self._best_reset), weights=wd, m=m_align,
+                    opts=self.view_opts, slot=src.get("slot"), view_m=self.view_M, view_lm=self.view_landmarks,
+                    view_pose=self.view_pose)
         return aligned, m_align, lm_frame, status
 
     def step(self, ring, frame_index, dt=None, frame_id=None):
@@ -1322,7 +1366,10 @@ class FaceTracker:
         a gallery row.  `_exit_stale` marks the slots whose track no step has served since a retire named it: their best_q
         is still the previous track's, which was queued at that birth, so the call reads -1 for them -- a retire that
         sees a birth sets the mark, the step that serves the slot's pending best-shot reset clears it (_retire_served).
-        Launches nothing for a tracker without `exits`."""
+        With `views` the exit-views call follows at once and reads this call's exit_row.  The stale mark covers the views
+        too: a slot whose bins are still an earlier track's is one whose best_q the retire call reads as -1, so it is
+        discarded, gets a negative exit_row, and nothing stale is copied -- the bins are emptied by the same pending reset,
+        in the same step, as the best shot.  Launches nothing for a tracker without `exits`."""
         import torch
         if self.exit_opts is None:
             return
@@ -1333,6 +1380,11 @@ class FaceTracker:
             self.track_id, self.born_frame, self.exit_head, self.exit_faces, self.exit_meta, self.exit_q, self.exit_row,
             frame_id, flush=flush, opts=self.exit_opts, best_m=self.best_M, best_lm=self.best_landmarks,
             best_rec=self.best_rec, x_m=self.exit_M, x_lm=self.exit_landmarks, x_rec=self.exit_rec)
+        if self.view_opts is not None:
+            alignment.track_exit_views_device(
+                self.exit_row, self.view_q, self.view_frame, self.view_gallery, self.exit_view_q, self.exit_view_frame,
+                self.exit_view_gallery, view_m=self.view_M, view_lm=self.view_landmarks, view_pose=self.view_pose,
+                x_view_m=self.exit_view_M, x_view_lm=self.exit_view_landmarks, x_view_pose=self.exit_view_pose)
 
     def _retire_served(self):
         """After the best update of a step: a slot whose pending best-shot reset the step has used holds its own track's
@@ -1362,6 +1414,30 @@ class FaceTracker:
             raise ValueError("exits() needs a tracker made with exits")
         self._state()
         return self.exit_faces, self.exit_meta, self.exit_q, self.exit_M, self.exit_landmarks, self.exit_head
+
+    def views(self):
+        """The pose-binned best shots of every slot, for a tracker with `views`: CUDA tensors (view_gallery
+        [capacity,B,...] in the aligned format, view_q float64 [capacity,B] -- -1: the bin holds nothing --, view_frame
+        int64 [capacity,B], view_M float32 [capacity,B,2,3], view_landmarks float64 [capacity,B,C,2], view_pose float64
+        [capacity,B,18]), the tracker's own, overwritten by later steps.  No download, no synchronisation."""
+        if self.view_opts is None:
+            raise ValueError("views() needs a tracker made with views")
+        self._state()
+        return self.view_gallery, self.view_q, self.view_frame, self.view_M, self.view_landmarks, self.view_pose
+
+    def exit_views(self):
+        """The views of the finished tracks, for a tracker with `views` and `exits`: CUDA tensors over the Q ring rows of
+        `exits()`, row for row (exit_view_gallery [Q,B,...], exit_view_q float64 [Q,B], exit_view_frame int64 [Q,B],
+        exit_view_M float32 [Q,B,2,3], exit_view_landmarks float64 [Q,B,C,2], exit_view_pose float64 [Q,B,18]).  A bin
+        whose exit_view_q is negative held no face: its other entries are whatever the ring row held before.  No
+        download, no synchronisation."""
+        if self.view_opts is None:
+            raise ValueError("exit_views() needs a tracker made with views")
+        if self.exit_opts is None:
+            raise ValueError("exit_views() needs a tracker made with exits")
+        self._state()
+        return (self.exit_view_gallery, self.exit_view_q, self.exit_view_frame, self.exit_view_M, self.exit_view_landmarks,
+                self.exit_view_pose)
 
     def best(self):
         """The best shot of every slot, for a tracker with `best_shot`: CUDA tensors (gallery [capacity,...] in the

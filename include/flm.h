@@ -1285,6 +1285,99 @@ int flm_head_pose(flm_stream_t stream, const double* lm_dev, size_t lm_stride, c
                   const flm_pose_opts* opts /*NULL = defaults*/, const int32_t* slot_dev /*[N] or NULL*/, int n_slots,
                   double* pose_dev /*[N or n_slots,18]*/, double* factor_out /*[N] or NULL*/);
 
+/* ---- pose-binned best shots: one best face per view of every track ------------------------------------------------------
+ * A matcher that enrols from video wants the best frontal face of a track AND its best left and right (up and down) views,
+ * so that a profile probe meets a profile template.  flm_track_views_update keeps, per slot, one best face per POSE BIN;
+ * flm_track_exit_views moves the bins of a finished track into the exit ring beside the row flm_track_retire wrote.
+ *
+ * The bin of a face, from the slot's pose record as flm_head_pose wrote it, by comparisons of doubles alone (the
+ * platform's atan2 and asin play no part, so the bin is the same on every machine):
+ *   ok = pose[14] == 1.0
+ *   u  = -pose[6]        -R[2][0] = cos(pitch)*sin(yaw): the sign of yaw.  u > 0: the face is turned to the image's LEFT
+ *   v  =  pose[7]         R[2][1] = sin(pitch).                            v > 0: the face looks DOWN in the image
+ *   iu = the number of edges e among u_edge[0 .. n_u) with u >= e;  iv likewise from v_edge[0 .. n_v)
+ *   B  = (n_u + 1) * (n_v + 1)  (at most 64);   bin = iv * (n_u + 1) + iu
+ * A face is NOT BINNED when !ok, or when u or v is NaN.  The edges are strictly ascending finite numbers in (-1, 1), at
+ * most FLM_VIEWS_MAX_EDGES per axis; an edge sin(a) on u is the yaw a exactly at pitch 0.
+ *
+ * flm_track_views_update: at most two launches, no atomics, no workspace, no allocation, no synchronisation; every launch
+ * shape is a host number.
+ * In, read at row r as flm_track_best_update_rows reads them: faces_dev [N,face_bytes], rec_dev int64 [N,8],
+ *   status_rows_dev int32 [N] or NULL, reset_dev int32 [N] or NULL, lm_dev, lm_stride, w_dev (or NULL), w_stride, c, m_dev
+ *   float32 [N,2,3] or NULL, frame_id; slot_dev int32 [N] or NULL.  NULL: g = r and n_slots = n (the argument is not read).
+ *   Otherwise the "rows" rules of the tracking section hold: a valid row writes at slot g = slot_dev[r], an inert row and a
+ *   slot no row names write nothing.  pose_dev float64 [n_slots,18], read at slot g, where flm_head_pose wrote it.
+ * In/out, indexed [g][b]: view_q float64 [n_slots,B] (-1: the bin holds nothing), view_frame int64 [n_slots,B],
+ *   view_gallery [n_slots,B,face_bytes], and, each optional, view_m float32 [n_slots,B,2,3], view_lm float64
+ *   [n_slots,B,C,2], view_pose float64 [n_slots,B,18].
+ * Out: take_dev int32 [N].
+ * Per valid row r, in float64, one IEEE operation per written operator, in the written order, nothing fused:
+ *   if reset_dev && reset_dev[r] != 0: every view_q[g][*] = -1.0 first; nothing else of the slot is cleared.
+ *   q = (s * e) * wbar, with s, e and wbar word for word those of flm_track_best_update.  There is NO caller factor: the
+ *       bin is what accounts for pose, and a sharp profile must be able to win its own bin.
+ *   ELIGIBLE: status_rows_dev is NULL or status == 0, n_lap > 0, e >= min_exposed, q is not NaN and q >= 0, and the face
+ *       is binned.
+ *   TAKEN: eligible and q > view_q[g][bin] (strict: on a tie the earlier frame stays).  Then view_q[g][bin] = q,
+ *       view_frame[g][bin] = frame_id, the face's bytes go to view_gallery[g][bin], the row's matrix and landmarks and the
+ *       slot's 18 pose doubles go where their pointers are given, and take_dev[r] = bin.
+ *   Otherwise take_dev[r] = -1 and the bin keeps every bit.  An inert row has take_dev[r] = -1.
+ * Launch 1, the decision, one thread per row: thread r is the only reader and writer of slot g's [B] entries -- which is
+ * why view_q is updated IN PLACE, without the snapshot or second buffer of flm_track_best_update* -- and writes take,
+ * view_frame, view_m, view_lm and view_pose.  Launch 2, the copy, grid (chunk, row): it reads take_dev and returns at
+ * once for take < 0; 16-byte accesses where both addresses allow them and element accesses elsewhere; no byte outside
+ * the bin's row is touched.  faces_dev and view_gallery need byte alignment only.
+ * Defaults (flm_views_opts_init): sharp_ref = 100 and min_exposed = 0.5 as flm_best_opts; n_u = 2, u_edge = -+sin(20 deg)
+ * (right, frontal, left); n_v = 0.
+ * Errors, all found before any launch: a null faces_dev, rec_dev, lm_dev, pose_dev, view_q, view_frame, view_gallery or
+ * take_dev; a view_m without m_dev; a struct_size smaller than this library's; a non-zero reserved; a sharp_ref that is
+ * not > 0; a NaN min_exposed; n_u or n_v outside [0, 7]; edges that are not finite, not inside (-1, 1) or not strictly
+ * ascending; an output overlapping an input or another output -> FLM_ERR_ARG.  FLM_ERR_SHAPE, the limit named in
+ * flm_last_error(), unless 1 <= n <= 65535, (with slot_dev) 1 <= n_slots <= 65535, 1 <= c <= 1024, face_bytes >= 1,
+ * lm_stride >= 2 and (with w_dev) w_stride >= 1. */
+#define FLM_VIEWS_MAX_EDGES 7
+typedef struct flm_views_opts {
+  uint32_t struct_size;  /* as flm_track_opts */
+  uint32_t reserved;     /* 0 */
+  double sharp_ref;      /* as flm_best_opts */
+  double min_exposed;    /* as flm_best_opts */
+  int32_t n_u, n_v;      /* edges in use per axis, 0 .. FLM_VIEWS_MAX_EDGES */
+  double u_edge[FLM_VIEWS_MAX_EDGES]; /* strictly ascending, in (-1, 1) */
+  double v_edge[FLM_VIEWS_MAX_EDGES];
+} flm_views_opts;
+void flm_views_opts_init(flm_views_opts* opts);
+int flm_track_views_update(flm_stream_t stream, const void* faces_dev, size_t face_bytes, int n,
+                           const int64_t* rec_dev /*[N,8]*/, const int32_t* status_rows_dev /*[N] or NULL*/,
+                           const int32_t* reset_dev /*[N] or NULL*/, const double* lm_dev, size_t lm_stride,
+                           const double* w_dev /*or NULL*/, size_t w_stride, int c, const float* m_dev /*[N,2,3] or NULL*/,
+                           int64_t frame_id, const flm_views_opts* opts /*NULL = defaults*/,
+                           const int32_t* slot_dev /*[N] or NULL*/, int n_slots, const double* pose_dev /*[n_slots,18]*/,
+                           double* view_q /*[n_slots,B]*/, int64_t* view_frame /*[n_slots,B]*/,
+                           void* view_gallery /*[n_slots,B,face_bytes]*/, float* view_m /*[n_slots,B,2,3] or NULL*/,
+                           double* view_lm /*[n_slots,B,C,2] or NULL*/, double* view_pose /*[n_slots,B,18] or NULL*/,
+                           int32_t* take_dev /*[N]*/);
+
+/* flm_track_exit_views: the views of the tracks flm_track_retire has just written, into the exit ring, in ONE launch.
+ * Called directly after flm_track_retire, it reads that call's exit_row_dev int32 [K].  For every slot t with
+ * 0 <= exit_row[t] < Q, ring row exit_row[t] receives all `bins` values of view_q[t] and view_frame[t], and for each bin
+ * with view_q[t][b] >= 0 also the bin's face bytes and, where given, its matrix, landmarks and pose.  A bin with
+ * view_q < 0 (or NaN) leaves its ring bytes as they were: the consumer reads x_view_q.  Slots with a negative exit_row
+ * (nothing ended, discarded, overrun) write nothing, and ring rows no slot was written to keep every bit.
+ * flm_track_retire guarantees that the rows written in one call are distinct.  The ring: x_view_q float64 [Q,bins],
+ * x_view_frame int64 [Q,bins], x_view_gallery [Q,bins,face_bytes], and x_view_m, x_view_lm, x_view_pose, each given
+ * together with its source and only so.  The grid is (chunk x bin, slot); the copy is that of flm_track_retire.
+ * Errors, found before the launch: a null exit_row_dev, view_q, view_frame, view_gallery, x_view_q, x_view_frame or
+ * x_view_gallery, an optional source without its ring buffer or the reverse, or two arguments that overlap ->
+ * FLM_ERR_ARG.  FLM_ERR_SHAPE, the limit named in flm_last_error(), unless 1 <= k <= 65535, 1 <= q <= 65535,
+ * 1 <= bins <= 64, 1 <= c <= 1024 and face_bytes >= 1. */
+int flm_track_exit_views(flm_stream_t stream, const int32_t* exit_row_dev /*[K]*/, int k, int q, int bins,
+                         size_t face_bytes, int c, const double* view_q /*[K,bins]*/,
+                         const int64_t* view_frame /*[K,bins]*/, const void* view_gallery /*[K,bins,face_bytes]*/,
+                         const float* view_m /*[K,bins,2,3] or NULL*/, const double* view_lm /*[K,bins,C,2] or NULL*/,
+                         const double* view_pose /*[K,bins,18] or NULL*/, double* x_view_q /*[Q,bins]*/,
+                         int64_t* x_view_frame /*[Q,bins]*/, void* x_view_gallery /*[Q,bins,face_bytes]*/,
+                         float* x_view_m /*[Q,bins,2,3] or NULL*/, double* x_view_lm /*[Q,bins,C,2] or NULL*/,
+                         double* x_view_pose /*[Q,bins,18] or NULL*/);
+
 #ifdef __cplusplus
 }
 #endif
