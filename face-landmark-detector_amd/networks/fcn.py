@@ -12,6 +12,7 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import threading
 
 import numpy as np
 
@@ -66,10 +67,15 @@ class Fcn8Model:
         self.output_height = self.input_height + self._grid_growth
         self.output_width = self.input_width + self._grid_growth
         self._packed = None
-        # cached workspaces, least recently used first; one entry is dropped at a time and never one a caller still
-        # holds (graphs.CapturedPipeline owns its workspace outright, see new_workspace)
+        # cached workspaces, keyed by (stream, call) and least recently used first.  A cached workspace belongs to (model,
+        # stream): it is allocated on, used on and returned to the allocator from that one stream, so two streams that
+        # call the same model at the same batch size never share intermediates, and an eviction never hands a block back
+        # while another stream runs in it.  At most _ws_cap entries per stream; one entry is dropped at a time and never
+        # one a caller still holds (graphs.CapturedPipeline owns its workspace outright, see new_workspace).  The lock
+        # makes lookup, insert and eviction one step for callers on different threads.
         self._ws = collections.OrderedDict()
         self._ws_cap = 4
+        self._ws_lock = threading.Lock()
         self._level_layer = {}   # "f1".."f5" -> index of the encoder layer (intermediate)
         # per-model defaults of the per-call options that change the workspace layout (include/flm.h: flm_forward_opts)
         self.forward_opts = {}
@@ -179,23 +185,30 @@ class Fcn8Model:
 
     def _workspace(self, n, out_mode, dmode, npts, fo):
         import torch
-        key = (n, out_mode, dmode, npts) + fo.key()
-        ws = self._ws.get(key)
-        if ws is not None:
-            self._ws.move_to_end(key)
-            return ws
+        stream = torch.cuda.current_stream().cuda_stream
+        key = (stream, n, out_mode, dmode, npts) + fo.key()
+        with self._ws_lock:
+            ws = self._ws.get(key)
+            if ws is not None:
+                self._ws.move_to_end(key)
+                return ws
         nbytes = _lib.load().flm_fcn_workspace_bytes_opts(self._arch, n, self.input_height, self.input_width,
                                                           self.n_classes, self._dt, out_mode, dmode, npts, C.byref(fo))
         if nbytes == 0:
             raise _lib.FlmError("workspace query failed: %s" % _lib.load().flm_last_error().decode())
-        while len(self._ws) >= self._ws_cap:   # single-entry LRU eviction
-            self._ws.popitem(last=False)
+        with self._ws_lock:
+            mine = [k for k in self._ws if k[0] == stream]   # this stream's entries, least recently used first
+            for k in mine[:max(0, len(mine) - self._ws_cap + 1)]:
+                del self._ws[k]
         ws = torch.empty(nbytes, dtype=torch.uint8, device=_lib.require_gpu())
-        self._ws[key] = ws
+        with self._ws_lock:
+            self._ws[key] = ws
         return ws
 
     def forward_device(self, x, out="probs", n_points=0, thresh=0.0, out_tensor=None, workspace=None, opts=None):
-        """One launch sequence on the current stream; everything stays in HBM.
+        """One launch sequence on the current stream; everything stays in HBM.  Streams may call one model concurrently,
+        from one thread or several: a cached workspace belongs to (model, current stream) and is never shared between
+        streams.  A holder of raw pointers (a captured graph) passes its own `workspace=`: cached ones may be evicted.
 
         x: torch CUDA tensor [N,H,W,3], uint8 (raw BGR crop: preprocess fused) or float32
            (already preprocessed, what model.predict receives).
