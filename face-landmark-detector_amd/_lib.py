@@ -55,6 +55,7 @@ EXPORTS = [
     "flm_pose_opts_init", "flm_head_pose",
     "flm_exit_opts_init", "flm_track_retire",
     "flm_views_opts_init", "flm_track_views_update", "flm_track_exit_views",
+    "flm_annotate_opts_init", "flm_bgr_to_yuv", "flm_frames_annotate",
 ]
 
 
@@ -234,6 +235,25 @@ class ViewsOpts(C.Structure):
             setattr(o, count, len(edges))
             for i in range(VIEWS_MAX_EDGES):
                 arr[i] = float(edges[i]) if i < min(len(edges), VIEWS_MAX_EDGES) else 0.0
+        return o
+
+
+class AnnotateOpts(C.Structure):
+    """flm_annotate_opts: which layers flm_frames_annotate writes into the ring, and how (include/flm.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("marks", C.c_int32), ("box", C.c_int32), ("redact", C.c_int32),
+                ("margin", C.c_double * 4), ("mark_bgr", C.c_uint8 * 3), ("box_bgr", C.c_uint8 * 3),
+                ("reserved", C.c_uint8 * 2)]
+
+    @classmethod
+    def make(cls, marks=1, box=0, redact=0, margin=None, mark_bgr=None, box_bgr=None):
+        """margin, mark_bgr, box_bgr None: the library's defaults."""
+        o = cls()
+        load().flm_annotate_opts_init(C.byref(o))
+        o.marks, o.box, o.redact = int(marks), int(box), int(redact)
+        for arr, values, conv in ((o.margin, margin, float), (o.mark_bgr, mark_bgr, int), (o.box_bgr, box_bgr, int)):
+            if values is not None:
+                for i, v in enumerate(values):
+                    arr[i] = conv(v)
         return o
 
 
@@ -422,6 +442,13 @@ def _declare(lib):
                                            vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.flm_track_exit_views.restype = i
     lib.flm_track_exit_views.argtypes = [vp, vp, i, i, i, sz, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.flm_annotate_opts_init.restype = None
+    lib.flm_annotate_opts_init.argtypes = [C.POINTER(AnnotateOpts)]
+    lib.flm_bgr_to_yuv.restype = i
+    lib.flm_bgr_to_yuv.argtypes = [i, vp, vp]
+    lib.flm_frames_annotate.restype = i
+    lib.flm_frames_annotate.argtypes = [vp, vp, sz, i, i, i, C.POINTER(FrameFormat), vp, vp, sz, i, i,
+                                        C.POINTER(AnnotateOpts), vp]
 
 
 def load():

@@ -1718,3 +1718,98 @@ def track_exit_views_device(exit_row, view_q, view_frame, view_gallery, x_view_q
         _lib.ptr(x_view_q), _lib.ptr(x_view_frame), _lib.ptr(x_view_gallery), _ptr(x_view_m), _ptr(x_view_lm),
         _ptr(x_view_pose)), "flm_track_exit_views")
     return x_view_q
+
+
+# ---- frame annotation: marks, boxes and mosaics written into the ring (include/flm.h, flm_frames_annotate) ------------------
+class FrameAnnotation:
+    """What `annotate_frames_device` writes into the ring for every face (flm_annotate_opts; include/flm.h states each
+    layer): marks: the 21-pixel disc of `utils.plots.draw_marks` at every accepted landmark; box: the thickness in
+    pixels of an outline of the face's region (0: none, at most 16); redact: the cell size in pixels of a mosaic over
+    the region (0: none, else even and 2..64); margin (left, top, right, bottom): how far the region reaches beyond the
+    box of the accepted landmarks, as fractions of that box's longer side, each in [0, 4]; mark_color, box_color: (B,G,R)
+    bytes.  The default margins (0.1, 0.35, 0.1, 0.1) are guesses at "the face, forehead included" on the 68-point
+    layout, whose topmost points are the eyebrows: nobody has measured them.  A caller who must not leak a face sets
+    them generously."""
+
+    def __init__(self, marks=True, box=0, redact=0, margin=(0.1, 0.35, 0.1, 0.1), mark_color=(0, 255, 0),
+                 box_color=(0, 255, 0)):
+        if not isinstance(marks, (bool, np.bool_)):
+            raise ValueError("marks must be True or False (got %r)" % (marks,))
+        for name, v in (("box", box), ("redact", redact)):
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+                raise ValueError("%s must be an integer (got %r)" % (name, v))
+        if not 0 <= box <= 16:
+            raise ValueError("box must be in [0, 16] (got %r)" % (box,))
+        if redact != 0 and (redact < 2 or redact > 64 or redact % 2):
+            raise ValueError("redact must be 0, or even and in [2, 64] (got %r)" % (redact,))
+        try:
+            margin = tuple(float(v) for v in margin)
+        except (TypeError, ValueError):
+            raise ValueError("margin must be four numbers (left, top, right, bottom) (got %r)" % (margin,)) from None
+        if len(margin) != 4 or any(not 0.0 <= v <= 4.0 for v in margin):
+            raise ValueError("margin must be four numbers in [0, 4] (got %r)" % (margin,))
+        colors = []
+        for name, col in (("mark_color", mark_color), ("box_color", box_color)):
+            try:
+                col = tuple(col)
+            except TypeError:
+                raise ValueError("%s must be three bytes (B, G, R) (got %r)" % (name, col)) from None
+            if len(col) != 3 or any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer))
+                                    or not 0 <= v <= 255 for v in col):
+                raise ValueError("%s must be three bytes (B, G, R) (got %r)" % (name, col))
+            colors.append(tuple(int(v) for v in col))
+        self.marks, self.box, self.redact, self.margin = bool(marks), int(box), int(redact), margin
+        self.mark_color, self.box_color = colors
+
+    def struct(self):
+        return _lib.AnnotateOpts.make(int(self.marks), self.box, self.redact, self.margin, self.mark_color, self.box_color)
+
+    def __repr__(self):
+        return "FrameAnnotation(marks=%r, box=%r, redact=%r, margin=%r, mark_color=%r, box_color=%r)" % (
+            self.marks, self.box, self.redact, self.margin, self.mark_color, self.box_color)
+
+
+def annotate_frames_device(frames, lm, frame_index_dev=None, opts=None, src=None, regions_out=None):
+    """Marks, outlines and mosaics of K faces written INTO the ring (flm_frames_annotate; include/flm.h states every
+    layer and the order they are applied in).
+
+    frames: the ring, as `src` (a FrameFormat; None: FrameFormat.bgr()) holds it -- a contiguous CUDA uint8 [F,H,W,3]
+    tensor, or the decoder's [F,rows,pitch] NV12 ring; lm: CUDA float64 [K,C,2] landmarks in FRAME pixels (a view of a
+    landmark record tensor is read in place), rejected points (-1,-1) are skipped; frame_index_dev: None (every face lies
+    in slot 0) or a contiguous CUDA int32 [K] tensor, a face whose index lies outside the ring is left out; opts: None or
+    a `FrameAnnotation`; regions_out: None or a contiguous CUDA int32 [K,4] tensor.  Neither the landmarks nor
+    regions_out may overlap the ring.  The slots are changed for every later reader: annotate a frame after the calls
+    that still need its pixels.  No download, no synchronisation.  Returns the regions int32 [K,4] (x0,y0,x1,y1), unclipped."""
+    import torch
+    if opts is None:
+        opts = FrameAnnotation()
+    elif not isinstance(opts, FrameAnnotation):
+        raise ValueError("opts must be None or a FrameAnnotation (got %r)" % (opts,))
+    if src is None:
+        src = FrameFormat.bgr()
+    _check_frame_format(src)
+    nf, fh, fw, stride = src.ring(frames)
+    if src.pixel == "bgr" and (fw < 2 or fh < 1 or fh * fw * 3 >= 2 ** 31):
+        raise ValueError("frames of %dx%d are outside the kernels' reach (width >= 2, H*W*3 < 2^31)" % (fh, fw))
+    lm, ls = _strided_points(lm)
+    k, c = int(lm.shape[0]), int(lm.shape[1])
+    if k > 65535 or (opts.redact and k > 4096):
+        raise ValueError("at most 65535 faces per call, 4096 with redact (got %d)" % k)
+    if c > 1024:
+        raise ValueError("at most 1024 landmarks per face (got %d)" % c)
+    if frame_index_dev is not None:
+        _check_out(frame_index_dev, torch.int32, (k,), "frame_index_dev")
+    regions = _out(regions_out, torch.int32, (k, 4), "regions_out", frames.device)
+    _check_span_overlap(lm, frames, "lm and the ring")
+    _check_overlap(regions, frames, "regions_out and the ring")
+    _check_span_overlap(lm, regions, "lm and regions_out")
+    _check_overlap(frame_index_dev, frames, "frame_index_dev and the ring")
+    _check_overlap(frame_index_dev, regions, "frame_index_dev and regions_out")
+    if k and c:
+        co, cs = opts.struct(), src.struct(frames)
+        _lib.check(_lib.load().flm_frames_annotate(_lib.stream_ptr(), _lib.ptr(frames), stride, nf, fh, fw, _lib.C.byref(cs),
+                                                   _ptr(frame_index_dev), _lib.ptr(lm), ls, k, c, _lib.C.byref(co),
+                                                   _lib.ptr(regions)), "flm_frames_annotate")
+    elif k:
+        regions.zero_()
+    return regions

@@ -42,6 +42,7 @@ SOURCES = [
     "flm_track_exit.hip",
     "flm_track_views.hip",
     "flm_pose.hip",
+    "flm_annotate.hip",
     "flm_mobile.hip",
 ]
 # -ffp-contract=off: only the fma() calls written in the sources fuse, so the arithmetic of the

@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "flm_annotate_dev.h"
 #include "flm_common.h"
 
 namespace flm {
@@ -2008,6 +2009,134 @@ int flm_track_exit_views(flm_stream_t stream, const int32_t* exit_row, int k, in
   g.x_view_q = x_view_q; g.x_view_frame = x_view_frame; g.x_view_gallery = static_cast<unsigned char*>(x_view_gallery);
   g.x_view_m = x_view_m; g.x_view_lm = x_view_lm; g.x_view_pose = x_view_pose;
   return launch_track_exit_views(static_cast<hipStream_t>(stream), g);
+}
+
+// ---- frame annotation (flm_annotate.hip) ------------------------------------------------------------------------------
+
+void flm_annotate_opts_init(flm_annotate_opts* opts) {
+  if (!opts) return;
+  memset(opts, 0, sizeof(*opts));
+  opts->struct_size = (uint32_t)sizeof(flm_annotate_opts);
+  opts->marks = 1;
+  opts->box = 0;
+  opts->redact = 0;
+  opts->margin[0] = 0.1; opts->margin[1] = 0.35; opts->margin[2] = 0.1; opts->margin[3] = 0.1;
+  opts->mark_bgr[0] = 0; opts->mark_bgr[1] = 255; opts->mark_bgr[2] = 0;
+  opts->box_bgr[0] = 0; opts->box_bgr[1] = 255; opts->box_bgr[2] = 0;
+}
+
+int flm_bgr_to_yuv(int matrix, const uint8_t bgr[3], uint8_t yuv[3]) {
+  if (!bgr || !yuv) {
+    set_error("flm_bgr_to_yuv: null argument");
+    return FLM_ERR_ARG;
+  }
+  if (matrix != FLM_YUV_BT601_LIMITED && matrix != FLM_YUV_BT709_LIMITED) {
+    set_error("flm_bgr_to_yuv: unknown YUV matrix %d", matrix);
+    return FLM_ERR_ARG;
+  }
+  annot_bgr_to_yuv(matrix, bgr, yuv);
+  return FLM_OK;
+}
+
+int flm_frames_annotate(flm_stream_t stream, uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
+                        const flm_frame_format* src, const int32_t* frame_idx, const double* lm, size_t lm_stride, int k,
+                        int c, const flm_annotate_opts* opts, int32_t* regions) {
+  const char* who = "flm_frames_annotate";
+  if (!frames || !lm || !regions) {  // src, frame_idx and opts are optional
+    set_error("%s: null argument", who);
+    return FLM_ERR_ARG;
+  }
+  flm_frame_format bgr;
+  flm_frame_format_init(&bgr);
+  if (!src) src = &bgr;
+  const int rc_fmt = check_frame_format(who, src);
+  if (rc_fmt == FLM_ERR_ARG) return rc_fmt;  // (a BGR24 format with a pitch is a shape error: after the options)
+  flm_annotate_opts defaults;
+  flm_annotate_opts_init(&defaults);
+  if (!opts) opts = &defaults;
+  if (opts->struct_size < sizeof(flm_annotate_opts)) {
+    set_error("%s: flm_annotate_opts struct_size %u is smaller than this library's %zu (initialise with "
+              "flm_annotate_opts_init)", who, opts->struct_size, sizeof(flm_annotate_opts));
+    return FLM_ERR_ARG;
+  }
+  if (opts->marks != 0 && opts->marks != 1) {
+    set_error("%s: marks=%d (must be 0 or 1)", who, opts->marks);
+    return FLM_ERR_ARG;
+  }
+  if (opts->box < 0 || opts->box > 16) {
+    set_error("%s: box=%d outside 0 <= box <= 16", who, opts->box);
+    return FLM_ERR_ARG;
+  }
+  if (opts->redact != 0 && (opts->redact < 2 || opts->redact > 64 || (opts->redact & 1))) {
+    set_error("%s: redact=%d (must be 0, or even and 2 <= redact <= 64)", who, opts->redact);
+    return FLM_ERR_ARG;
+  }
+  for (int i = 0; i < 4; ++i)
+    if (!(opts->margin[i] >= 0.0 && opts->margin[i] <= 4.0)) {  // (NaN fails the test)
+      set_error("%s: margin[%d]=%g outside 0 <= margin <= 4", who, i, opts->margin[i]);
+      return FLM_ERR_ARG;
+    }
+  if (k < 1 || k > 65535) {
+    set_error("%s: k=%d outside 1 <= k <= 65535", who, k);
+    return FLM_ERR_SHAPE;
+  }
+  if (opts->redact && k > 4096) {
+    set_error("%s: k=%d with redact, needs k <= 4096 (every workgroup of the mosaic scans the faces before its own)", who,
+              k);
+    return FLM_ERR_SHAPE;
+  }
+  if (c < 1 || c > 1024) {
+    set_error("%s: c=%d outside 1 <= c <= 1024", who, c);
+    return FLM_ERR_SHAPE;
+  }
+  if (lm_stride < 2) {
+    set_error("%s: lm_stride=%zu, needs lm_stride >= 2", who, lm_stride);
+    return FLM_ERR_SHAPE;
+  }
+  if (rc_fmt) return check_frame_format(who, src);  // (sets the message again)
+  if (nframes < 1) {
+    set_error("%s: nframes=%d, needs nframes >= 1", who, nframes);
+    return FLM_ERR_SHAPE;
+  }
+  AnnotateArgs g;
+  memset(&g, 0, sizeof(g));
+  if (src->pixel == FLM_FRAME_NV12) {
+    const size_t bytes = nv12_format_bytes(who, src, fh, fw);  // fh, fw even and >= 2, the pitches, slot bytes < 2^31
+    if (!bytes) return FLM_ERR_SHAPE;
+    if (frame_stride < bytes) {
+      set_error("%s: frame_stride=%zu, needs frame_stride >= flm_frame_format_bytes = %zu", who, frame_stride, bytes);
+      return FLM_ERR_SHAPE;
+    }
+    g.nv12 = 1;
+    g.y_pitch = src->y_pitch ? src->y_pitch : (unsigned)fw;
+    g.uv_pitch = src->uv_pitch ? src->uv_pitch : g.y_pitch;
+    g.uv_off = src->uv_offset ? (unsigned)src->uv_offset : g.y_pitch * (unsigned)fh;
+    annot_bgr_to_yuv(src->matrix, opts->mark_bgr, g.mark_px);
+    annot_bgr_to_yuv(src->matrix, opts->box_bgr, g.box_px);
+  } else {
+    if (fh < 1 || fw < 2) {
+      set_error("%s: frame %dx%d, needs fh >= 1 and fw >= 2", who, fh, fw);
+      return FLM_ERR_SHAPE;
+    }
+    if ((long long)fh * fw * 3 >= (1ll << 31)) {
+      set_error("%s: frame %dx%d, needs fh*fw*3 < 2^31", who, fh, fw);
+      return FLM_ERR_SHAPE;
+    }
+    if (frame_stride < (size_t)fh * fw * 3) {
+      set_error("%s: frame_stride=%zu, needs frame_stride >= fh*fw*3 = %zu", who, frame_stride, (size_t)fh * fw * 3);
+      return FLM_ERR_SHAPE;
+    }
+    for (int i = 0; i < 3; ++i) {
+      g.mark_px[i] = opts->mark_bgr[i];
+      g.box_px[i] = opts->box_bgr[i];
+    }
+  }
+  g.frames = frames; g.frame_stride = frame_stride; g.nframes = nframes; g.fh = fh; g.fw = fw;
+  g.frame_idx = frame_idx; g.lm = lm; g.lm_stride = lm_stride; g.k = k; g.c = c;
+  g.marks = opts->marks; g.box = opts->box; g.redact = opts->redact;
+  for (int i = 0; i < 4; ++i) g.margin[i] = opts->margin[i];
+  g.regions = regions;
+  return launch_frames_annotate(static_cast<hipStream_t>(stream), g);
 }
 
 }  // extern "C"

@@ -424,6 +424,25 @@ struct TrackExitViewsArgs {
 };
 int launch_track_exit_views(hipStream_t s, const TrackExitViewsArgs& g);
 
+// flm_frames_annotate (flm_annotate.hip); every argument has been checked by the caller (flm_api.hip), which resolves the
+// frame format's defaults and converts the two colours for an NV12 ring
+struct AnnotateArgs {
+  uint8_t* frames;
+  size_t frame_stride;
+  int nframes, fh, fw;
+  int nv12;                           // 0: dense BGR24; 1: y_pitch, uv_pitch, uv_off below hold
+  unsigned y_pitch, uv_pitch, uv_off;
+  const int32_t* frame_idx;           // [K] or null = slot 0
+  const double* lm;
+  size_t lm_stride;
+  int k, c;
+  int marks, box, redact;
+  double margin[4];
+  uint8_t mark_px[3], box_px[3];      // B,G,R for a BGR ring, Y,U,V for an NV12 ring
+  int32_t* regions;                   // [K,4]
+};
+int launch_frames_annotate(hipStream_t s, const AnnotateArgs& g);
+
 // Bijective XCD-aware remap of a 1-D grid: blocks that the dispatcher deals to the same XCD
 // (b % 8) receive consecutive logical ids, so neighbours in logical order share an L2.
 __device__ __forceinline__ int xcd_remap(int b, int nblk) {

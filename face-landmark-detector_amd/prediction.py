@@ -491,6 +491,29 @@ def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 1
     return aligned, m, lm, boxes_dev
 
 
+def annotate_frames(ring, landmarks, frame_index=None, frame_format=None, **options):
+    """`draw_marks(img, marks)`, the last line of the reference's frame loop (prediction.py:99-113), for the faces of a
+    ring that stays on the device -- and an outline and a mosaic of every face beside the marks.
+
+    ring: the frame ring as `align_frames` takes it (`frame_format`: an alignment.FrameFormat, None for the CUDA uint8
+    [F,H,W,3] ring); landmarks: CUDA float64 [K,C,2] in frame pixels, what `align_frames` returns third; frame_index:
+    None (every face lies in slot 0), a host sequence of K ring slots (one upload) or a CUDA int32 [K] tensor (used where
+    it lies), what `crop_frames_device` returns last.  options: the arguments of `alignment.FrameAnnotation` -- marks,
+    box, redact, margin, mark_color, box_color.  The ring slots are WRITTEN: run it after the calls that read the frame.
+    Returns the regions, CUDA int32 [K,4]."""
+    import torch
+    _frame_format(frame_format)
+    opts = alignment.FrameAnnotation(**options)
+    if frame_index is not None and not isinstance(frame_index, torch.Tensor):
+        if not isinstance(landmarks, torch.Tensor) or not landmarks.is_cuda:
+            raise ValueError("landmarks must be a CUDA float64 [K,C,2] tensor")
+        idx = [int(v) for v in frame_index]
+        if len(idx) != int(landmarks.shape[0]):
+            raise ValueError("frame_index must name a ring slot for each of the %d faces" % int(landmarks.shape[0]))
+        frame_index = torch.tensor(idx, dtype=torch.int32).to(landmarks.device)
+    return alignment.annotate_frames_device(ring, landmarks, frame_index_dev=frame_index, opts=opts, src=frame_format)
+
+
 def detect_marks_batch(img, model, faces, n_points=4, thresh=0.0):
     """All faces of one frame in one batch: crop -> FCN -> decode -> back-projection
     (prediction.py:76-94).  Returns uint [K,C,2] image coordinates."""
@@ -1118,6 +1141,37 @@ class FaceTracker:
         self._retire_served()
         self._served()
         return res
+
+    def annotate(self, ring, landmarks, frame_index=None, annotation=None):
+        """Draw what the tracker knows into the frames themselves (alignment.annotate_frames_device, flm_frames_annotate):
+        the marks of `utils.plots.draw_marks` at every landmark, an outline and a mosaic of every face, as `annotation`
+        (an alignment.FrameAnnotation; None: its defaults, marks alone) says.  `ring`: the ring the step read, in the
+        tracker's `frame_format` and of its `frame_hw`; `landmarks`: the landmarks the step returned, CUDA float64
+        [rows,C,2] in frame px -- the rejected points and the slots without a face are (-1,-1) and draw nothing;
+        `frame_index`: None -- `frame_slots`, the ring slots `step` cut from, one per slot -- or a contiguous CUDA int32
+        [rows] tensor.  After `step_active` or `step_live` the landmarks are ROWS, and `frame_slots` is not theirs: pass
+        the rows' ring slots as such a tensor.  Nothing is downloaded, nothing synchronises, and the call runs inside
+        torch.cuda.set_sync_debug_mode("error").  Returns the regions, CUDA int32 [rows,4] (x0,y0,x1,y1), unclipped.
+
+        The call WRITES the ring: the slot is changed for every later reader -- a later step that cuts from it sees the
+        marks, a recorder sees the mosaic.  So call it after the step of that frame, and before the decoder reuses the
+        slot.  `prediction.frames_to_bgr_device` of an annotated NV12 slot gives the displayable picture."""
+        import torch
+        if annotation is not None and not isinstance(annotation, alignment.FrameAnnotation):
+            raise ValueError("annotation must be None or an alignment.FrameAnnotation (got %r)" % (annotation,))
+        fmt = self.frame_format or alignment.FrameFormat.bgr()
+        _, rh, rw, _ = fmt.ring(ring)
+        if (rh, rw) != self.frame_hw:
+            raise ValueError("the ring holds %dx%d frames, the tracker was made for %dx%d" % ((rh, rw) + self.frame_hw))
+        if not isinstance(landmarks, torch.Tensor) or landmarks.dim() != 3:
+            raise ValueError("landmarks must be a CUDA float64 [rows,C,2] tensor")
+        if frame_index is None:
+            self._state()
+            frame_index = self.frame_slots
+            if int(landmarks.shape[0]) != int(frame_index.shape[0]):
+                raise ValueError("frame_index=None goes with the landmarks of `step`, one face per slot (%d): pass the "
+                                 "rows' ring slots as a CUDA int32 tensor" % int(frame_index.shape[0]))
+        return alignment.annotate_frames_device(ring, landmarks, frame_index_dev=frame_index, opts=annotation, src=fmt)
 
     def _served(self, slot=None):
         """`step` (slot None: every slot) or `step_active` (the rows' slots, -1 for an inert row) has served slots that

@@ -1378,6 +1378,75 @@ int flm_track_exit_views(flm_stream_t stream, const int32_t* exit_row_dev /*[K]*
                          float* x_view_m /*[Q,bins,2,3] or NULL*/, double* x_view_lm /*[Q,bins,C,2] or NULL*/,
                          double* x_view_pose /*[Q,bins,18] or NULL*/);
 
+/* ---- frame annotation: marks, boxes and mosaics written into the ring ---------------------------------------------------
+ * The reference's frame loop (prediction.py:99-113) ends every frame with draw_marks(img, marks) (utils/plots.py) on a
+ * host frame.  flm_frames_annotate writes the same marks -- and an outline and a mosaic of every face -- into the ring
+ * slots themselves, BGR24 or NV12, from the landmarks in frame pixels that flm_track_step (or flm_landmarks_to_frame)
+ * left on the device: at most four launches, no atomics, no download, no synchronisation, no allocation, no workspace.
+ * It is the one call of this library that WRITES a frame: the slot is changed for every later reader.
+ *
+ *  1. Accepted landmark.  A landmark (x, y) is accepted when x >= 0 && y >= 0 && x <= 2^30 && y <= 2^30.  The rejected
+ *     point (-1,-1) of flm_landmarks_from_crop fails this test, and so do NaN and +-inf.  Point i of face f is the two
+ *     doubles at lm_dev + (f*c + i)*lm_stride, as flm_track_step reads it; lm_stride is 2 or FLM_LANDMARK_REC.
+ *  2. Region of a face, float64, one IEEE operation per written operator, nothing fused:
+ *       mnx, mny, mxx, mxy = min and max over the accepted points;  side = max(mxx - mnx, mxy - mny)
+ *       R = (floor(mnx - margin[0]*side), floor(mny - margin[1]*side),
+ *            ceil(mxx + margin[2]*side) + 1, ceil(mxy + margin[3]*side) + 1)
+ *     each value clamped to +-2^30 and cast to int32, the form of boxes_next in flm_track_step.  A face without an
+ *     accepted point has R = (0,0,0,0).  regions_dev receives R of every face, whatever its frame index.
+ *     P = R intersected with [0,fw) x [0,fh).  A face TAKES PART when P is not empty and its frame index
+ *     (frame_idx_dev[f], or 0 for a NULL frame_idx_dev) lies in [0, nframes).
+ *  3. Layer 1, the mosaic (redact = s).  Cells lie on a grid anchored at the frame's origin: cell (cx,cy) covers
+ *     [cx*s, min((cx+1)*s, fw)) x [cy*s, min((cy+1)*s, fh)).  A cell is mosaicked when it intersects P of at least one
+ *     face of that frame that takes part.  Every such cell is replaced ONCE, by (sum + (n>>1)) / n of its ORIGINAL bytes,
+ *     n its pixel count.  BGR24: per channel.  NV12: the luma bytes of the cell as above; the U bytes and the V bytes of
+ *     the m = n/4 chroma samples under it each by (sum + (m>>1)) / m (sizes and s are even: a cell never splits a sample).
+ *  4. Layer 2, the outline (box = t): the pixels (x,y) of P with x < R.x0+t || x >= R.x1-t || y < R.y0+t || y >= R.y1-t,
+ *     in box_bgr.  R is the unclipped region: a face cut by the frame's border shows no edge along that border.
+ *  5. Layer 3, the marks: for every accepted landmark of a face that takes part, the pixels ((int)x + dx, (int)y + dy)
+ *     with dx*dx + dy*dy <= 5 -- rows of 3, 5, 5, 5, 3 pixels, what utils/plots.draw_marks paints -- clipped to the
+ *     frame, in mark_bgr.
+ *  6. Order: all mosaics, then all outlines, then all marks, over all faces.  A layer has one colour per call, so a
+ *     pixel's final value does not depend on the order of the faces: the call is deterministic without atomics.
+ *  7. Painting NV12.  The colour's (Y,U,V) is computed once, on the host, by flm_bgr_to_yuv with the format's matrix.  A
+ *     painted pixel gets the luma byte Y, and the U,V pair of its 2x2 block gets U,V; a later layer that paints any pixel
+ *     of the block overwrites the pair.
+ *  8. flm_bgr_to_yuv (host only, no GPU), int32 throughout, >> an arithmetic shift:
+ *       Y = clamp(16  + ((cB*B + cG*G + cR*R + 2^15) >> 16), 16, 235);  U, V likewise with 128, clamped to [16, 240]
+ *     coefficients round(exact x 2^16) of the limited-range forward matrix with the format's Kr and Kb, over (B,G,R):
+ *       FLM_YUV_BT601_LIMITED  Y (6416, 33039, 16829)  U (28784, -19071, -9714)  V (-4681, -24103, 28784)
+ *       FLM_YUV_BT709_LIMITED  Y (4064, 40254, 11966)  U (28784, -22189, -6596)  V (-2639, -26145, 28784)
+ *     Through the conversion of the NV12 section above, every one of the 2^24 colours returns within 2 per channel, for
+ *     both matrices (tests/native/annotate_host.cpp runs all of them).
+ *  9. Bytes left alone.  No byte of the ring outside the cells, outlines and discs above is written: not the pitch
+ *     padding, not the rows between the luma plane and uv_offset, not a slot that no face that takes part names.  With
+ *     marks = 0, box = 0 and redact = 0 only regions_dev is written.
+ * 10. Errors, all found before any launch.  FLM_ERR_ARG: a null frames_dev, lm_dev or regions_dev; a struct_size smaller
+ *     than this library's (either struct); an unknown pixel or matrix; marks outside {0, 1}; box outside [0, 16]; a redact
+ *     that is neither 0 nor even and in [2, 64]; a margin outside [0, 4] or NaN.  FLM_ERR_SHAPE, the limit named in
+ *     flm_last_error(), unless 1 <= k <= 65535 (k <= 4096 when redact != 0: every workgroup of the mosaic scans the faces
+ *     before its own), 1 <= c <= 1024, lm_stride >= 2, and the frame geometry flm_warp_affine_frames_src accepts for the
+ *     same src: nframes >= 1 and (BGR24) fh >= 1, fw >= 2, fh*fw*3 < 2^31, frame_stride >= fh*fw*3, pitches and offset 0,
+ *     (NV12) fh and fw even and >= 2, y_pitch >= fw, uv_pitch >= fw, uv_offset >= y_pitch*fh, slot bytes < 2^31,
+ *     frame_stride >= flm_frame_format_bytes.
+ * lm_dev and regions_dev must not overlap the ring or each other; frames_dev needs byte alignment only. */
+typedef struct flm_annotate_opts {
+  uint32_t struct_size;  /* as flm_forward_opts: lets the struct grow */
+  int32_t marks;         /* 0 or 1: the 21-pixel disc of the reference's draw_marks at every accepted landmark */
+  int32_t box;           /* outline thickness in px, 0 = none, <= 16 */
+  int32_t redact;        /* mosaic cell in px, 0 = none, else even and 2..64 */
+  double margin[4];      /* left, top, right, bottom, as fractions of the landmark box's longer side; each in [0, 4] */
+  uint8_t mark_bgr[3], box_bgr[3];
+  uint8_t reserved[2];   /* pads the colours to 8 bytes */
+} flm_annotate_opts;
+/* marks 1, box 0, redact 0, margin {0.1, 0.35, 0.1, 0.1}, both colours (0,255,0). */
+void flm_annotate_opts_init(flm_annotate_opts* opts);
+int flm_bgr_to_yuv(int matrix, const uint8_t bgr[3], uint8_t yuv[3]);
+int flm_frames_annotate(flm_stream_t stream, uint8_t* frames_dev, size_t frame_stride, int nframes, int fh, int fw,
+                        const flm_frame_format* src /* NULL = BGR24 */, const int32_t* frame_idx_dev /*[K] or NULL = 0*/,
+                        const double* lm_dev, size_t lm_stride, int k, int c,
+                        const flm_annotate_opts* opts /* NULL = defaults */, int32_t* regions_dev /*[K,4], out*/);
+
 #ifdef __cplusplus
 }
 #endif
