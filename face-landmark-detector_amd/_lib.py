@@ -47,6 +47,7 @@ EXPORTS = [
     "flm_image_format_init", "flm_image_format_bytes", "flm_warp_affine_fmt", "flm_warp_affine_frames_fmt",
     "flm_frame_format_init", "flm_frame_format_bytes", "flm_frames_to_bgr", "flm_crop_resize_frames_src",
     "flm_warp_affine_frames_src",
+    "flm_mesh_map", "flm_mesh_affines", "flm_warp_mesh_frames",
     "flm_track_opts_init", "flm_track_seed", "flm_landmarks_from_crop", "flm_track_step",
     "flm_track_filter_init", "flm_track_step_filtered",
     "flm_track_assoc_opts_init", "flm_track_associate", "flm_track_associate_streams",
@@ -387,6 +388,13 @@ def _declare(lib):
     lib.flm_warp_affine_frames_src.argtypes = [vp, vp, C.c_size_t, i, i, i, vp, vp, vp, i, vp, i, i, i,
                                                C.POINTER(ImageFormat), C.POINTER(FrameFormat)]
     d = C.c_double
+    lib.flm_mesh_map.restype = i
+    lib.flm_mesh_map.argtypes = [vp, vp, vp, i, i, i, i, vp]
+    lib.flm_mesh_affines.restype = i
+    lib.flm_mesh_affines.argtypes = [vp, vp, i, vp, vp, vp, i, i, i, i, d, vp]
+    lib.flm_warp_mesh_frames.restype = i
+    lib.flm_warp_mesh_frames.argtypes = [vp, vp, C.c_size_t, i, i, i, vp, vp, vp, i, vp, vp, vp, i, i, i, vp, i, vp, i, i, i,
+                                         C.POINTER(ImageFormat), C.POINTER(FrameFormat), d, vp]
     lib.flm_track_opts_init.restype = None
     lib.flm_track_opts_init.argtypes = [C.POINTER(TrackOpts)]
     lib.flm_track_seed.restype = i

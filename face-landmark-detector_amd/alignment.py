@@ -467,6 +467,287 @@ def warp_frames_device(frames, m, out_h, out_w, frame_index_dev=None, boxes_dev=
     return out
 
 
+# ---- shape-normalised faces: the piecewise-affine warp over the landmark mesh (include/flm.h) ---------------------------
+def _cross2(a, b, c):
+    """(bx-ax)*(cy-ay) - (by-ay)*(cx-ax): the doubled signed area of (a, b, c), the edge function of include/flm.h."""
+    return (b[0] - a[0]) * (c[1] - a[1]) - (b[1] - a[1]) * (c[0] - a[0])
+
+
+def _in_circumcircle(a, b, c, d):
+    """Is d strictly inside the circumcircle of the positively oriented triangle (a, b, c)?  The in-circle determinant
+    in float64 against 1e-12 of the sum of its terms' magnitudes: points that are cocircular up to rounding (the
+    template is mirror-symmetric, so every isosceles trapezoid of it is) count as outside, whichever way they round."""
+    ax, ay, bx, by, cx, cy = a[0] - d[0], a[1] - d[1], b[0] - d[0], b[1] - d[1], c[0] - d[0], c[1] - d[1]
+    a2, b2, c2 = ax * ax + ay * ay, bx * bx + by * by, cx * cx + cy * cy
+    terms = (ax * by * c2, -ax * cy * b2, -ay * bx * c2, ay * cx * b2, a2 * bx * cy, -a2 * by * cx)
+    return sum(terms) > 1e-12 * sum(abs(t) for t in terms)
+
+
+def _delaunay_in_rectangle(points, corners):
+    """Delaunay triangulation (Bowyer-Watson, float64) of `points`, four of which -- `corners`, in order around the
+    rectangle -- are the corners of an axis-aligned rectangle that holds all the others.  The rectangle's two triangles
+    are the start, so there is no super-triangle to remove; a point on the rectangle's border (exactly collinear with
+    two corners) splits the border edge, and the triangle of zero area that the cavity's border edge would make is
+    dropped.  -> list of (i, j, k), each positively oriented."""
+    pts = [(float(x), float(y)) for x, y in points]
+    c0, c1, c2, c3 = corners
+    tris = [(c0, c1, c2), (c0, c2, c3)]
+    if _cross2(pts[c0], pts[c1], pts[c2]) < 0:
+        tris = [(c0, c2, c1), (c0, c3, c2)]
+    for i, q in enumerate(pts):
+        if i in corners:
+            continue
+        bad = [t for t in tris if _in_circumcircle(pts[t[0]], pts[t[1]], pts[t[2]], q)]
+        if not bad:          # on the border, and cocircular with the triangle there: the triangle that holds the point
+            bad = [t for t in tris if min(_cross2(pts[t[0]], pts[t[1]], q), _cross2(pts[t[1]], pts[t[2]], q),
+                                          _cross2(pts[t[2]], pts[t[0]], q)) >= 0][:1]
+        edges = {}
+        for t in bad:
+            for e in ((t[0], t[1]), (t[1], t[2]), (t[2], t[0])):
+                if (e[1], e[0]) in edges:
+                    del edges[(e[1], e[0])]
+                else:
+                    edges[e] = True
+        tris = [t for t in tris if t not in bad]
+        for a, b in edges:
+            if _cross2(pts[a], pts[b], q) > 0:      # == 0: q lies on the border edge a-b
+                tris.append((a, b, i))
+    return tris
+
+
+class FaceMesh:
+    """The mesh of the piecewise-affine warp (flm_warp_mesh_frames): `points`, float64 [P,2] template positions in aligned
+    pixels -- the first P - n_anchors those of the landmarks, in landmark order, the last `n_anchors` ANCHORS, template
+    positions without a landmark that a face places in its frame through the inverse of its similarity M -- and
+    `triangles`, int [T,3] of point indices.  3 <= P <= 256, 1 <= T <= 255.  The constructor turns every triangle to
+    positive orientation and rejects an index outside [0,P), a repeated vertex and a triangle whose doubled template
+    area is below 1e-9.  `points` and `triangles` are the mesh's own read-only copies.  The device tensors and the triangle map of every
+    (device, aligned size) are made once, by the first call that needs them, and cached for the callers of every stream:
+    that call synchronises its stream once, so that what the cache holds is finished data (a `FaceTracker` does it when
+    it allocates its state)."""
+
+    MAX_POINTS, MAX_TRIANGLES, MIN_AREA2 = 256, 255, 1e-9
+
+    def __init__(self, points, triangles, n_anchors=0):
+        pts = np.asarray(points, np.float64)
+        tri = np.asarray(triangles)
+        if pts.ndim != 2 or pts.shape[1] != 2 or tri.ndim != 2 or tri.shape[1] != 3 or tri.dtype.kind not in "iu":
+            raise ValueError("a face mesh is float64 [P,2] points and integer [T,3] triangles")
+        p, t = int(pts.shape[0]), int(tri.shape[0])
+        if not 3 <= p <= self.MAX_POINTS:
+            raise ValueError("a face mesh has 3 to %d points (got %d)" % (self.MAX_POINTS, p))
+        if not 1 <= t <= self.MAX_TRIANGLES:
+            raise ValueError("a face mesh has 1 to %d triangles (got %d)" % (self.MAX_TRIANGLES, t))
+        if isinstance(n_anchors, bool) or int(n_anchors) != n_anchors or not 0 <= int(n_anchors) <= p:
+            raise ValueError("n_anchors must be an integer in [0, %d] (got %r)" % (p, n_anchors))
+        if not np.isfinite(pts).all():
+            raise ValueError("the points of a face mesh must be finite")
+        if tri.min() < 0 or tri.max() >= p:
+            raise ValueError("a triangle names a point outside [0, %d)" % p)
+        tri = tri.astype(np.int32)
+        if ((tri[:, 0] == tri[:, 1]) | (tri[:, 1] == tri[:, 2]) | (tri[:, 0] == tri[:, 2])).any():
+            raise ValueError("a triangle repeats a vertex")
+        a, b, c = pts[tri[:, 0]], pts[tri[:, 1]], pts[tri[:, 2]]
+        area2 = (b[:, 0] - a[:, 0]) * (c[:, 1] - a[:, 1]) - (b[:, 1] - a[:, 1]) * (c[:, 0] - a[:, 0])
+        if (np.abs(area2) < self.MIN_AREA2).any():
+            raise ValueError("template triangle %d is degenerate (doubled area below %g)"
+                             % (int(np.argmax(np.abs(area2) < self.MIN_AREA2)), self.MIN_AREA2))
+        flip = area2 < 0
+        tri[flip] = tri[flip][:, [0, 2, 1]]
+        self.points = np.array(pts, np.float64, order="C")        # the mesh's own copies, read-only: the device tensors
+        self.triangles = np.array(tri, np.int32, order="C")       # and maps cached below are made from them once
+        self.points.setflags(write=False)
+        self.triangles.setflags(write=False)
+        self.n_anchors = int(n_anchors)
+        self._dev, self._maps = {}, {}
+
+    @classmethod
+    def default(cls, n_landmarks, out_h, out_w):
+        """canonical_template(n_landmarks, out_h, out_w) plus eight anchors -- the corners and edge midpoints of
+        [0,out_w-1] x [0,out_h-1] -- under their Delaunay triangulation: the mesh covers every output pixel and is
+        continuous with the similarity warp at the border."""
+        n, h, w = int(n_landmarks), int(out_h), int(out_w)
+        if n < 1 or h < 2 or w < 2:
+            raise ValueError("the default mesh needs n_landmarks >= 1 and an aligned size of 2 x 2 or more")
+        x1, y1 = float(w - 1), float(h - 1)
+        anchors = np.array([[0, 0], [x1, 0], [x1, y1], [0, y1], [x1 / 2, 0], [x1, y1 / 2], [x1 / 2, y1], [0, y1 / 2]], np.float64)
+        pts = np.concatenate([canonical_template(n, h, w), anchors])
+        tris = np.array(sorted(_delaunay_in_rectangle(pts, (n, n + 1, n + 2, n + 3))), np.int32)
+        # a triangulation of P points of which the 8 anchors lie on the hull has 2P - 2 - 8 triangles that tile the rectangle
+        a, b, c = pts[tris[:, 0]], pts[tris[:, 1]], pts[tris[:, 2]]
+        area2 = (b[:, 0] - a[:, 0]) * (c[:, 1] - a[:, 1]) - (b[:, 1] - a[:, 1]) * (c[:, 0] - a[:, 0])
+        if len(tris) != 2 * (n + 8) - 10 or not (area2 > 0).all() or abs(area2.sum() / 2 - x1 * y1) > 1e-9 * x1 * y1:
+            raise ValueError("the default mesh of %d landmarks at %dx%d does not tile the aligned rectangle (landmark "
+                             "positions that coincide or lie on its border?): pass an alignment.FaceMesh" % (n, h, w))
+        return cls(pts, tris, 8)
+
+    @property
+    def n_points(self):
+        return int(self.points.shape[0])
+
+    @property
+    def n_triangles(self):
+        return int(self.triangles.shape[0])
+
+    @property
+    def n_landmarks(self):
+        return self.n_points - self.n_anchors
+
+    @staticmethod
+    def _device(device):
+        """`device` with its index spelled out: "cuda" and "cuda:0" are one cache entry."""
+        import torch
+        d = torch.device(device)
+        if d.type == "cuda" and d.index is None:
+            d = torch.device("cuda", torch.cuda.current_device())
+        return d
+
+    @staticmethod
+    def _finished(device):
+        """What the caches below hold is shared by every stream of the device, so it is FINISHED read-only data before
+        it gets there: the stream that produced it is synchronised, once per entry, by the caller that made it."""
+        import torch
+        if device.type == "cuda":
+            torch.cuda.current_stream(device).synchronize()
+
+    def tensors(self, device):
+        """(points float64 [P,2], triangles int32 [T,3]) on `device`, uploaded and finished at the first call."""
+        import torch
+        d = self._device(device)
+        if d not in self._dev:
+            made = (torch.from_numpy(self.points.copy()).to(d), torch.from_numpy(self.triangles.copy()).to(d))
+            self._finished(d)
+            self._dev[d] = made
+        return self._dev[d]
+
+    def map(self, device, out_h, out_w):
+        """The triangle map uint8 [out_h,out_w] on `device` (flm_mesh_map), made at the first call of any stream and
+        finished -- the launching stream is synchronised once -- before any caller, on any stream, can find it here."""
+        d = self._device(device)
+        key = (d, int(out_h), int(out_w))
+        if key not in self._maps:
+            made = mesh_map_device(self, out_h, out_w, d)
+            self._finished(d)
+            self._maps[key] = made
+        return self._maps[key]
+
+    def __repr__(self):
+        return "FaceMesh(%d points, %d anchors, %d triangles)" % (self.n_points, self.n_anchors, self.n_triangles)
+
+
+def _check_mesh(mesh):
+    if not isinstance(mesh, FaceMesh):
+        raise ValueError("mesh must be an alignment.FaceMesh (got %r)" % (mesh,))
+
+
+def _check_min_det(min_det):
+    min_det = float(min_det)
+    if not min_det >= 0.0:
+        raise ValueError("min_det must be >= 0 (got %r)" % min_det)
+    return min_det
+
+
+def mesh_map_device(mesh, out_h, out_w, device="cuda", out=None):
+    """The triangle of every aligned pixel: CUDA uint8 [out_h,out_w], the lowest triangle of `mesh` whose three edge
+    functions at the pixel's integer position are >= 0, 255 where there is none (flm_mesh_map).  FaceMesh.map caches it."""
+    import torch
+    _check_mesh(mesh)
+    out_h, out_w = _sizes((out_h, out_w), "out_h and out_w")
+    if out is None:
+        out = torch.empty((out_h, out_w), dtype=torch.uint8, device=device)
+    else:
+        _check_out(out, torch.uint8, (out_h, out_w), "out")
+    pts, tris = mesh.tensors(out.device)
+    _lib.check(_lib.load().flm_mesh_map(_lib.stream_ptr(), _lib.ptr(pts), _lib.ptr(tris), mesh.n_points, mesh.n_triangles,
+                                        out_h, out_w, _lib.ptr(out)), "flm_mesh_map")
+    return out
+
+
+def _mesh_faces(lm, m, mesh):
+    """The checks that flm_mesh_affines and flm_warp_mesh_frames share: (lm, its element stride, K)."""
+    _check_mesh(mesh)
+    lm, ls = _strided_points(lm)
+    k, c = int(lm.shape[0]), int(lm.shape[1])
+    if c != mesh.n_landmarks:
+        raise ValueError("lm has %d landmarks per face, the mesh %d" % (c, mesh.n_landmarks))
+    _check_matrices(m, k)
+    if m.device != lm.device:
+        raise ValueError("lm and m must be on one device")
+    return lm, ls, k
+
+
+def mesh_affines_device(lm, m, mesh, min_det=1e-6, out=None):
+    """lm: CUDA float64 [K,C,2] frame-space landmarks (or the x,y view of a landmark record tensor, read in place);
+    m: contiguous CUDA float32 [K,2,3], every face's similarity frame px -> aligned px -> CUDA float32 [K,T,2,3], the
+    affine frame px -> aligned px of every triangle of every face (flm_mesh_affines; a triangle whose landmarks span
+    less than `min_det` doubled area, or hold a NaN, takes the face's m)."""
+    import torch
+    lm, ls, k = _mesh_faces(lm, m, mesh)
+    min_det = _check_min_det(min_det)
+    out = _out(out, torch.float32, (k, mesh.n_triangles, 2, 3), "out", lm.device)
+    if k:
+        pts, tris = mesh.tensors(lm.device)
+        _lib.check(_lib.load().flm_mesh_affines(_lib.stream_ptr(), _lib.ptr(lm), ls, _lib.ptr(m), _lib.ptr(pts),
+                                                _lib.ptr(tris), mesh.n_points, mesh.n_anchors, mesh.n_triangles, k,
+                                                min_det, _lib.ptr(out)), "flm_mesh_affines")
+    return out
+
+
+def warp_mesh_frames_device(frames, lm, m, mesh, out_h, out_w, frame_index_dev=None, boxes_dev=None, samples=1, fmt=None,
+                            src=None, out=None, affines_out=None, min_det=1e-6):
+    """Shape-normalised faces in one launch (flm_warp_mesh_frames): every triangle of `mesh` is filled from the frame by
+    the affine that takes the face's landmarks onto the triangle's template corners, so each landmark's texture lands
+    on its template pixel.  frames, frame_index_dev, boxes_dev, samples, fmt, src, out: as warp_frames_device takes them
+    (and with its result for a ring slot outside the ring and an empty box: a zero face); lm: CUDA float64 [K,C,2]
+    FRAME-space landmarks, C the mesh's landmark count (a view of a landmark record tensor is read in place); m: contiguous
+    CUDA float32 [K,2,3], the faces' similarity frame px -> aligned px, which places the mesh's anchors and stands in for
+    a triangle whose landmarks collapse; affines_out: None or contiguous CUDA float32 [K,T,2,3], receives the matrices of
+    mesh_affines_device.  A pixel of triangle t has the bits warp_frames_device gives with m = affines[:, t]."""
+    import torch
+    if fmt is not None:
+        _check_format(fmt)
+    if src is not None:
+        _check_frame_format(src)
+        ring = src.ring(frames)
+    elif (not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8
+            or not frames.is_cuda or not frames.is_contiguous()):
+        raise ValueError("frames must be a contiguous CUDA uint8 [F,H,W,3] tensor")
+    lm, ls, k = _mesh_faces(lm, m, mesh)
+    if lm.device != frames.device:
+        raise ValueError("lm and m must be on the device of frames (%s, got %s)" % (frames.device, lm.device))
+    if samples not in (1, 2, 4):
+        raise ValueError("samples must be 1, 2 or 4")
+    min_det = _check_min_det(min_det)
+    out_h, out_w = _sizes((out_h, out_w), "out_h and out_w")
+    if src is not None:
+        nf, fh, fw, stride = ring
+    else:
+        nf, fh, fw = [int(v) for v in frames.shape[:3]]
+        stride = fh * fw * 3
+    if frame_index_dev is not None:
+        _check_out(frame_index_dev, torch.int32, (k,), "frame_index_dev")
+    if boxes_dev is not None:
+        _check_boxes(boxes_dev, k)
+    if fmt is not None:
+        out = _format_out(fmt, out, k, out_h, out_w, frames.device)
+    else:
+        out = _out(out, torch.float32, (k, out_h, out_w, 3), "out", frames.device)
+    if affines_out is not None:
+        _check_out(affines_out, torch.float32, (k, mesh.n_triangles, 2, 3), "affines_out")
+    if not k:
+        return out
+    pts, tris = mesh.tensors(frames.device)
+    tmap = mesh.map(frames.device, out_h, out_w)
+    cf = None if fmt is None else fmt.struct()
+    cs = None if src is None else src.struct(frames)
+    _lib.check(_lib.load().flm_warp_mesh_frames(
+        _lib.stream_ptr(), _lib.ptr(frames), stride, nf, fh, fw, _ptr(frame_index_dev), _ptr(boxes_dev), _lib.ptr(lm), ls,
+        _lib.ptr(m), _lib.ptr(pts), _lib.ptr(tris), mesh.n_points, mesh.n_anchors, mesh.n_triangles, _lib.ptr(tmap), k,
+        _lib.ptr(out), out_h, out_w, int(samples), None if cf is None else _lib.C.byref(cf),
+        None if cs is None else _lib.C.byref(cs), min_det, _ptr(affines_out)), "flm_warp_mesh_frames")
+    return out
+
+
 # ---- tracking: the next frame's crop from this frame's landmarks (include/flm.h, "tracking") --------------------------
 def _check_matrices(m, k, what="m"):
     import torch

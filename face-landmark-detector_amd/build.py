@@ -36,6 +36,7 @@ SOURCES = [
     "flm_frames.hip",
     "flm_warp_fmt.hip",
     "flm_frames_nv12.hip",
+    "flm_mesh.hip",
     "flm_track.hip",
     "flm_track_assoc.hip",
     "flm_quality.hip",

@@ -1150,6 +1150,51 @@ int flm_warp_affine_frames_src(flm_stream_t stream, const uint8_t* frames, size_
                                  fmt ? fmt : &plain, src);
 }
 
+// ---- the piecewise-affine warp over the landmark mesh (flm_mesh.hip) -------------------------------------------------
+
+int flm_mesh_map(flm_stream_t stream, const double* pts, const int32_t* tris, int p, int t, int hd, int wd,
+                 uint8_t* map) {
+  if (!pts || !tris || !map) {
+    set_error("flm_mesh_map: null argument");
+    return FLM_ERR_ARG;
+  }
+  return launch_mesh_map(static_cast<hipStream_t>(stream), pts, tris, p, t, hd, wd, map);
+}
+
+int flm_mesh_affines(flm_stream_t stream, const double* lm, int lm_stride, const float* m, const double* pts,
+                     const int32_t* tris, int p, int a, int t, int k, double min_det, float* aff) {
+  if (!lm || !m || !pts || !tris || !aff) {
+    set_error("flm_mesh_affines: null argument");
+    return FLM_ERR_ARG;
+  }
+  return launch_mesh_affines(static_cast<hipStream_t>(stream), lm, lm_stride, m, pts, tris, p, a, t, k, min_det, aff);
+}
+
+int flm_warp_mesh_frames(flm_stream_t stream, const uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
+                         const int32_t* frame_idx, const int32_t* boxes, const double* lm, int lm_stride, const float* m,
+                         const double* pts, const int32_t* tris, int p, int a, int t, const uint8_t* map, int k,
+                         void* dst, int hd, int wd, int samples, const flm_image_format* fmt,
+                         const flm_frame_format* src, double min_det, float* aff_out) {
+  if (!frames || !lm || !m || !pts || !tris || !map || !dst) {  // frame_idx, boxes, fmt, src and aff_out are optional
+    set_error("flm_warp_mesh_frames: null argument");
+    return FLM_ERR_ARG;
+  }
+  flm_frame_format bgr;  // src NULL: the dense BGR ring
+  flm_frame_format_init(&bgr);
+  if (src) {
+    if (const int rc = check_frame_format("flm_warp_mesh_frames", src)) return rc;
+  }
+  flm_image_format plain;  // fmt NULL: float32 NHWC BGR, scale 1, bias 0
+  flm_image_format_init(&plain);
+  if (fmt) {
+    if (const int rc = check_image_format("flm_warp_mesh_frames", fmt)) return rc;
+  }
+  if (const int rc = check_image_dst("flm_warp_mesh_frames", dst, fmt ? fmt : &plain)) return rc;
+  return launch_warp_mesh_frames(static_cast<hipStream_t>(stream), frames, frame_stride, nframes, fh, fw, frame_idx, boxes,
+                                 lm, lm_stride, m, pts, tris, p, a, t, map, k, dst, hd, wd, samples, fmt ? fmt : &plain,
+                                 src ? src : &bgr, min_det, aff_out);
+}
+
 // ---- tracking (flm_track.hip) ------------------------------------------------------------------------------------
 
 void flm_track_opts_init(flm_track_opts* opts) {

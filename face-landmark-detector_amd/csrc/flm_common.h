@@ -266,6 +266,9 @@ int launch_warp_frames_fmt(hipStream_t s, const uint8_t* frames, size_t frame_st
                            const int32_t* frame_idx, const int32_t* boxes, const float* m, int k, void* dst, int hd,
                            int wd, int samples, const flm_image_format* fmt);
 
+// the limits of a dense BGR24 ring (flm_warp_fmt.hip): FLM_OK or FLM_ERR_SHAPE with the limit named after `who`
+int bgr_ring_check(const char* who, size_t frame_stride, int nframes, int fh, int fw);
+
 // NV12 frame slots as the source (flm_frames_nv12.hip); struct_size, pixel and matrix of `src` and the image format have
 // been checked by the caller
 int launch_frames_to_bgr_nv12(hipStream_t s, const uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
@@ -278,6 +281,21 @@ int launch_warp_frames_nv12(hipStream_t s, const uint8_t* frames, size_t frame_s
                             int wd, int samples, const flm_image_format* fmt, const flm_frame_format* src);
 // 0 when the format's sizes are rejected (the reason is in flm_last_error())
 size_t nv12_format_bytes(const char* who, const flm_frame_format* src, int fh, int fw);
+// the ring's checks of the calls above, and the slot geometry with the defaults resolved (flm_nv12_dev.h)
+struct Nv12Geom;
+int nv12_ring_geometry(const char* who, const flm_frame_format* src, size_t frame_stride, int nframes, int fh, int fw,
+                       Nv12Geom* g);
+
+// the piecewise-affine warp over the landmark mesh (flm_mesh.hip); null pointers, the image format (never null here)
+// and struct_size, pixel and matrix of `src` have been checked by the caller
+int launch_mesh_map(hipStream_t s, const double* pts, const int32_t* tris, int p, int t, int hd, int wd, uint8_t* map);
+int launch_mesh_affines(hipStream_t s, const double* lm, int lm_stride, const float* m, const double* pts,
+                        const int32_t* tris, int p, int a, int t, int k, double min_det, float* aff);
+int launch_warp_mesh_frames(hipStream_t s, const uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
+                            const int32_t* frame_idx, const int32_t* boxes, const double* lm, int lm_stride,
+                            const float* m, const double* pts, const int32_t* tris, int p, int a, int t,
+                            const uint8_t* map, int k, void* dst, int hd, int wd, int samples,
+                            const flm_image_format* fmt, const flm_frame_format* src, double min_det, float* aff_out);
 
 // tracking (flm_track.hip); null pointers and the option struct have been checked by the caller, `opts` is never null
 int launch_track_seed(hipStream_t s, const int32_t* boxes, int k, int in_h, int in_w, int fh, int fw, float* m,

@@ -269,6 +269,12 @@ static int check_ring(const char* who, const flm_frame_format* src, size_t frame
   return FLM_OK;
 }
 
+// check_ring for the launchers of other files that read NV12 slots (flm_mesh.hip)
+int nv12_ring_geometry(const char* who, const flm_frame_format* src, size_t frame_stride, int nframes, int fh, int fw,
+                       Nv12Geom* g) {
+  return check_ring(who, src, frame_stride, nframes, fh, fw, g);
+}
+
 int launch_frames_to_bgr_nv12(hipStream_t s, const uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
                               const flm_frame_format* src, uint8_t* out) {
   Nv12Geom g;

@@ -184,6 +184,28 @@ int launch_warp_fmt(hipStream_t s, const void* src, int src_is_u8, int n, int hs
   return FLM_OK;
 }
 
+// The limits of a dense BGR24 ring, stated once for every launcher that reads one (here and flm_mesh.hip); `who` names
+// the call in the message.
+int bgr_ring_check(const char* who, size_t frame_stride, int nframes, int fh, int fw) {
+  if (nframes < 1) {
+    set_error("%s: nframes=%d, needs nframes >= 1", who, nframes);
+    return FLM_ERR_SHAPE;
+  }
+  if (fh < 1 || fw < 2) {
+    set_error("%s: frame %dx%d, needs fh >= 1 and fw >= 2", who, fh, fw);
+    return FLM_ERR_SHAPE;
+  }
+  if ((long long)fh * fw * 3 >= (1ll << 31)) {
+    set_error("%s: frame %dx%d, needs fh*fw*3 < 2^31", who, fh, fw);
+    return FLM_ERR_SHAPE;
+  }
+  if (frame_stride < (size_t)fh * fw * 3) {
+    set_error("%s: frame_stride=%zu, needs frame_stride >= fh*fw*3 = %zu", who, frame_stride, (size_t)fh * fw * 3);
+    return FLM_ERR_SHAPE;
+  }
+  return FLM_OK;
+}
+
 int launch_warp_frames_fmt(hipStream_t s, const uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
                            const int32_t* frame_idx, const int32_t* boxes, const float* m, int k, void* dst, int hd,
                            int wd, int samples, const flm_image_format* fmt) {
@@ -195,23 +217,7 @@ int launch_warp_frames_fmt(hipStream_t s, const uint8_t* frames, size_t frame_st
     set_error("warp_affine_frames_fmt: k=%d outside 1 <= k <= 65535", k);
     return FLM_ERR_SHAPE;
   }
-  if (nframes < 1) {
-    set_error("warp_affine_frames_fmt: nframes=%d, needs nframes >= 1", nframes);
-    return FLM_ERR_SHAPE;
-  }
-  if (fh < 1 || fw < 2) {
-    set_error("warp_affine_frames_fmt: frame %dx%d, needs fh >= 1 and fw >= 2", fh, fw);
-    return FLM_ERR_SHAPE;
-  }
-  if ((long long)fh * fw * 3 >= (1ll << 31)) {
-    set_error("warp_affine_frames_fmt: frame %dx%d, needs fh*fw*3 < 2^31", fh, fw);
-    return FLM_ERR_SHAPE;
-  }
-  if (frame_stride < (size_t)fh * fw * 3) {
-    set_error("warp_affine_frames_fmt: frame_stride=%zu, needs frame_stride >= fh*fw*3 = %zu", frame_stride,
-              (size_t)fh * fw * 3);
-    return FLM_ERR_SHAPE;
-  }
+  if (const int rc = bgr_ring_check("warp_affine_frames_fmt", frame_stride, nframes, fh, fw)) return rc;
   if (hd < 1 || wd < 1 || (long long)hd * wd * 12 >= (1ll << 31)) {
     set_error("warp_affine_frames_fmt: aligned size %dx%d, needs hd, wd >= 1 and hd*wd*3*4 < 2^31", hd, wd);
     return FLM_ERR_SHAPE;

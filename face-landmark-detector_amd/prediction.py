@@ -491,6 +491,51 @@ def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 1
     return aligned, m, lm, boxes_dev
 
 
+_MESHES = {}
+
+
+def _default_mesh(n_landmarks, oh, ow):
+    key = (int(n_landmarks), int(oh), int(ow))
+    if key not in _MESHES:
+        _MESHES[key] = alignment.FaceMesh.default(*key)
+    return _MESHES[key]
+
+
+def normalize_frames(ring, landmarks, m, mesh=None, out_size=(112, 112), frame_index=None, samples=1, aligned_format=None,
+                     frame_format=None):
+    """Shape-normalised faces for landmarks and matrices that `align_frames` returned: every face is warped piecewise
+    affinely over the landmark mesh, so that each landmark's texture lands on its template pixel -- what
+    `skimage.transform.PiecewiseAffineTransform` + `warp` do on the host, in one launch from the ring
+    (alignment.warp_mesh_frames_device).
+
+    ring, frame_format: as `align_frames` takes them; landmarks: CUDA float64 [K,C,2] in frame pixels (third value of
+    `align_frames`); m: CUDA float32 [K,2,3] frame px -> aligned px (its second); mesh: an `alignment.FaceMesh` whose
+    landmark points are the template the matrices were fitted to, None for `FaceMesh.default(C, *out_size)` (the mesh of
+    `align_frames`' default template); frame_index: None (every face lies in slot 0), a host sequence of K ring slots
+    (one upload) or a CUDA int32 [K] tensor, what `crop_frames_device` returns last; samples, aligned_format: as
+    `align_frames` takes them.  Returns the faces, float32 [K,oh,ow,3] or the format's tensor."""
+    import torch
+    _aligned_format(aligned_format, False)
+    _frame_format(frame_format)
+    if mesh is not None and not isinstance(mesh, alignment.FaceMesh):
+        raise ValueError("mesh must be None or an alignment.FaceMesh (got %r)" % (mesh,))
+    if samples not in (1, 2, 4):
+        raise ValueError("samples must be 1, 2 or 4")
+    oh, ow = [int(v) for v in out_size]
+    if not isinstance(landmarks, torch.Tensor) or landmarks.dim() != 3 or not landmarks.is_cuda:
+        raise ValueError("landmarks must be a CUDA float64 [K,C,2] tensor")
+    k, c = int(landmarks.shape[0]), int(landmarks.shape[1])
+    if mesh is None:
+        mesh = _default_mesh(c, oh, ow)
+    if frame_index is not None and not isinstance(frame_index, torch.Tensor):
+        idx = [int(v) for v in frame_index]
+        if len(idx) != k:
+            raise ValueError("frame_index must name a ring slot for each of the %d faces" % k)
+        frame_index = torch.tensor(idx, dtype=torch.int32).to(landmarks.device)
+    return alignment.warp_mesh_frames_device(ring, landmarks, m, mesh, oh, ow, frame_index_dev=frame_index,
+                                             samples=samples, fmt=aligned_format, src=frame_format)
+
+
 def annotate_frames(ring, landmarks, frame_index=None, frame_format=None, **options):
     """`draw_marks(img, marks)`, the last line of the reference's frame loop (prediction.py:99-113), for the faces of a
     ring that stays on the device -- and an outline and a mosaic of every face beside the marks.
@@ -691,13 +736,23 @@ class FaceTracker:
     tracks that call queued into `exit_view_gallery` [Q,B,...], `exit_view_q`, `exit_view_frame`, `exit_view_M`,
     `exit_view_landmarks` and `exit_view_pose`, row for row beside the exit ring; `exit_views()` hands them out, and a
     consumer enrols the bins of a row whose `exit_view_q` is >= 0.  A tracker made without `views` launches nothing more,
-    allocates nothing more and returns the same bits."""
+    allocates nothing more and returns the same bits.  mesh: None, True (`alignment.FaceMesh.default` of the landmark
+    count and out_size, for the default template) or an `alignment.FaceMesh` whose landmark points are `template`: after
+    the aligned warp of `step`, `step_active` and `step_live` there is one more launch
+    (alignment.warp_mesh_frames_device, from the landmarks and the M that call returns, with `samples`), and
+    `mesh_faces` then holds the SHAPE-NORMALISED faces -- every landmark's texture on its template pixel -- row for row
+    with the aligned faces that call returned, in `aligned_format`: a view of a [capacity,...] buffer the tracker owns,
+    overwritten by the next step, with no download and no synchronisation.  A landmark the decode rejected is (-1,-1)
+    and drags its triangles there; a slot without a face gives a zero face, as in `aligned`.  Without `mesh` the tracker
+    makes the launches it makes without it and returns the same bits."""
 
     def __init__(self, model, frame_hw, capacity, out_size=(112, 112), template=None, crop_template=None, n_points=4,
                  thresh=0.0, weights=None, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"),
                  crop_samples=1, samples=1, aligned_format=None, frame_format=None, smooth=None, associate=None,
-                 best_shot=None, streams=1, pose=None, exits=None, views=None):
+                 best_shot=None, streams=1, pose=None, mesh=None, exits=None, views=None):
         import torch
+        if mesh is not None and mesh is not False and mesh is not True and not isinstance(mesh, alignment.FaceMesh):
+            raise ValueError("mesh must be None, True or an alignment.FaceMesh (got %r)" % (mesh,))
         if views is True:
             views = alignment.PoseViews()
         if views is not None and not isinstance(views, alignment.PoseViews):
@@ -768,6 +823,16 @@ class FaceTracker:
         self.head_pose, self.pose = pose, None
         self.exit_opts, self.track_id = exits, None
         self.view_opts, self.view_q = views, None
+        if mesh is True:
+            if template is not None:
+                raise ValueError("mesh=True is the mesh of the default template: pass an alignment.FaceMesh whose "
+                                 "landmark points are `template`")
+            mesh = alignment.FaceMesh.default(c, oh, ow)
+        elif mesh is False:
+            mesh = None
+        if mesh is not None and mesh.n_landmarks != c:
+            raise ValueError("the mesh has %d landmark points, the model %d landmarks" % (mesh.n_landmarks, c))
+        self.mesh, self.mesh_faces, self._mesh_buf = mesh, None, None
         self._head_model = None if pose is None else pose.model_for(c)
         self._ws_active = None   # the forward workspace of step_active (_active_workspace)
         self._waiting = False    # step_live has run below capacity: slot_age may hold a wait (_served)
@@ -826,6 +891,11 @@ class FaceTracker:
             empty = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, -1.0, -1.0] + [0.0] * 6
             self.pose = torch.tensor(empty, dtype=torch.float64, device=dev).repeat(n, 1).contiguous()
             self._pose_factor = torch.zeros((n,), dtype=torch.float64, device=dev) if self.best_shot is not None else None
+        if self.mesh is not None:       # the faces of the last step, and the mesh's tensors and map made once, here
+            mfmt = self.aligned_format or alignment.AlignedFormat()
+            self._mesh_buf = torch.zeros(mfmt.shape(n, *self.out_size), dtype=mfmt.torch_dtype, device=dev)
+            self.mesh.tensors(dev)
+            self.mesh.map(dev, *self.out_size)
         if self.view_opts is not None:  # -1: the bin holds nothing
             b = self.view_opts.bins
             face = tuple(self.gallery.shape[1:])
@@ -1082,6 +1152,11 @@ class FaceTracker:
                                        out=self.pose, factor_out=factor.get("factor"))
         aligned = alignment.warp_frames_device(ring, m_align, self.out_size[0], self.out_size[1], samples=self.samples,
                                                fmt=self.aligned_format, **where)
+        if self.mesh is not None:   # one more launch, into the tracker's own buffer: the rows of `aligned`
+            n = int(m_align.shape[0])
+            self.mesh_faces = alignment.warp_mesh_frames_device(
+                ring, lm_frame, m_align, self.mesh, self.out_size[0], self.out_size[1], samples=self.samples,
+                fmt=self.aligned_format, out=self._mesh_buf[:n], **where)
         self._steps += 1
         if self.best_shot is not None:
             rec = alignment.face_quality_device(aligned, self.aligned_format, self.best_shot.quality, out=quality_out)

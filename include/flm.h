@@ -641,6 +641,73 @@ int flm_warp_affine_frames_src(flm_stream_t stream, const uint8_t* frames_dev, s
                                int wd, int samples, const flm_image_format* fmt /* NULL = float32 NHWC BGR */,
                                const flm_frame_format* src);
 
+/* ---- shape-normalised faces: a piecewise-affine warp over the landmark mesh -------------------------------------------
+ * The similarity warps above use four degrees of freedom of a face's landmarks.  The calls below use all of them: the
+ * aligned rectangle is cut into triangles whose corners are the landmarks' TEMPLATE positions, and every triangle is
+ * filled from the frame by the affine that takes this face's landmarks in this frame onto its three corners -- so every
+ * landmark's texture lands on its template pixel, whatever the expression and the pose the similarity left.  (An
+ * addition to ABI version 2: no existing call, struct or bit changes.)
+ *
+ * A MESH is P = C + A points, float64 [P,2] in aligned pixels, and T triangles, int32 [T,3] of point indices, with
+ * 3 <= P <= 256, 0 <= A <= P, 1 <= T <= 255.  Points 0..C-1 are the template positions of landmarks 0..C-1; points
+ * C..P-1 are ANCHORS, template positions without a landmark, whose place in the frame is M^-1 of their template
+ * position -- with anchors on the border of the aligned rectangle the mesh covers it and meets the similarity warp there.
+ * Triangles are positively oriented ((bx-ax)*(cy-ay) - (by-ay)*(cx-ax) > 0) and not degenerate in the template; the
+ * Python class alignment.FaceMesh checks both.  A triangle that names a point outside [0,P) is never dereferenced: the
+ * map skips it and its matrix is the face's M.
+ *
+ * All mesh arithmetic is float64, one IEEE operation per written operator, in the written order, no fused multiply-add.
+ *
+ * flm_mesh_map, once per mesh and aligned size: map[y][x] = the LOWEST t whose three edge functions at the integer
+ *   point q = (x, y) are all >= 0, 255 if none is.  For corners a, b, c of triangle t, in that order, the edges are
+ *   a->b, b->c, c->a and
+ *     E_ab(q) = (bx-ax)*(qy-ay) - (by-ay)*(qx-ax)          two products, one subtraction, in that order
+ *   (a point on a shared edge or vertex has E = 0 in every triangle that shares it: the lowest index wins).
+ *
+ * flm_mesh_affines: aff[f][t], float32 [K,T,2,3], the forward matrix FRAME px -> ALIGNED px of every (face, triangle).
+ *   Landmark j of face f is lm_dev[(f*C + j)*lm_stride + {0,1}] (lm_stride float64 elements between points, >= 2: a
+ *   dense [K,C,2] tensor has 2, the x,y of a landmark record tensor FLM_LANDMARK_REC).  m_dev is the face's similarity M,
+ *   float32 [K,2,3], frame px -> aligned px (flm_similarity_from_landmarks*, flm_track_step).  The source s_v of mesh
+ *   vertex v with template position d_v:
+ *     v < C    s_v = the face's landmark v
+ *     v >= C   det = m00*m11 - m01*m10;  i00 = m11/det, i01 = (-m01)/det, i10 = (-m10)/det, i11 = m00/det
+ *              sx = i00*(dx-m02) + i01*(dy-m12);  sy = i10*(dx-m02) + i11*(dy-m12)      (M widened to float64 first)
+ *   and for triangle (v0, v1, v2) with e1 = s1-s0, e2 = s2-s0, g1 = d1-d0, g2 = d2-d0, det = e1x*e2y - e1y*e2x:
+ *     a00 = (g1x*e2y - g2x*e1y)/det     a01 = (g2x*e1x - g1x*e2x)/det     a02 = d0x - (a00*s0x + a01*s0y)
+ *     a10 = (g1y*e2y - g2y*e1y)/det     a11 = (g2y*e1x - g1y*e2x)/det     a12 = d0y - (a10*s0x + a11*s0y)
+ *   each of the six rounded to float32 (nearest even).  When !(fabs(det) >= min_det) -- collapsed, collinear or NaN
+ *   landmarks -- the triangle takes the face's M unchanged.  min_det >= 0; 1e-6 is the Python default.
+ *
+ * flm_warp_mesh_frames: the faces, in ONE launch.  THE CONTRACT: for output pixel (x, y) of face f with
+ *   map[y][x] = t < T, the stored element has the bits that flm_warp_affine_frames_src stores at (x, y) of face f when
+ *   it is given m = aff[f][t] and the same frames, frame_idx, boxes, samples, fmt and src.  A pixel's triangle is chosen
+ *   at its centre and used for all its samples x samples sub-samples.  A pixel with map[y][x] >= T (255: no triangle)
+ *   stores what a zero face stores: v = 0 through the format's epilogue.  A ring slot outside [0,nframes) and an empty
+ *   clipped box give a zero face as they do there.  fmt NULL = float32 NHWC BGR, scale 1, bias 0; src NULL = the dense
+ *   BGR24 ring.  map_dev is flm_mesh_map's for this mesh at hd x wd.  aff_out_dev, when not NULL, receives
+ *   [K,T,2,3]: the bits of flm_mesh_affines, zero faces included.  No atomics, no allocation, no byte outside the K
+ *   faces (and aff_out) written.
+ *
+ * Errors, all found before anything is launched: those of flm_warp_affine_frames_src with their codes (null frames / m /
+ *   dst, formats, samples -> FLM_ERR_ARG; ring, k and aligned-size limits -> FLM_ERR_SHAPE); in addition a null
+ *   lm / pts / tris / map (aff for flm_mesh_affines), t outside [1,255], p outside [3,256], a outside [0,p],
+ *   lm_stride < 2 and a min_det that is negative or NaN -> FLM_ERR_ARG.  flm_mesh_map: hd, wd >= 1 and
+ *   hd*wd*3*4 < 2^31, else FLM_ERR_SHAPE; flm_mesh_affines: 1 <= k <= 65535, else FLM_ERR_SHAPE. */
+int flm_mesh_map(flm_stream_t stream, const double* pts_dev /*[P,2]*/, const int32_t* tris_dev /*[T,3]*/, int p, int t,
+                 int hd, int wd, uint8_t* map_dev /*[hd,wd]*/);
+int flm_mesh_affines(flm_stream_t stream, const double* lm_dev, int lm_stride, const float* m_dev /*[K,2,3]*/,
+                     const double* pts_dev /*[P,2]*/, const int32_t* tris_dev /*[T,3]*/, int p, int a, int t, int k,
+                     double min_det, float* aff_dev /*[K,T,2,3]*/);
+int flm_warp_mesh_frames(flm_stream_t stream, const uint8_t* frames_dev, size_t frame_stride, int nframes, int fh, int fw,
+                         const int32_t* frame_idx_dev /*[K] or NULL = frame 0*/,
+                         const int32_t* boxes_dev /*[K,4] or NULL*/, const double* lm_dev, int lm_stride,
+                         const float* m_dev /*[K,2,3] frame px -> aligned px*/, const double* pts_dev /*[P,2]*/,
+                         const int32_t* tris_dev /*[T,3]*/, int p, int a, int t, const uint8_t* map_dev /*[hd,wd]*/,
+                         int k, void* dst_dev, int hd, int wd, int samples,
+                         const flm_image_format* fmt /* NULL = float32 NHWC BGR */,
+                         const flm_frame_format* src /* NULL = BGR24 */, double min_det,
+                         float* aff_out_dev /*[K,T,2,3] or NULL*/);
+
 /* ---- tracking: the next frame's crop from this frame's landmarks --------------------------------------------------
  * The stream above starts every frame from detector boxes on the host.  The calls below keep a face's crop on the
  * device instead: the network input of frame t+1 is cut from the frame by the similarity that takes the landmarks of
