@@ -28,6 +28,7 @@ FRAME_BGR24, FRAME_NV12 = 0, 1                       # flm_frame_pixel
 YUV_BT601_LIMITED, YUV_BT709_LIMITED = 0, 1          # flm_yuv_matrix
 TRACK_DEAD, TRACK_FEW_POINTS, TRACK_LOW_SCORE, TRACK_SCALE, TRACK_OUTSIDE = 1, 2, 4, 8, 16   # flm_track_status
 TRACK_DUPLICATE, TRACK_UNCONFIRMED = 32, 64          # flm_track_status, set by flm_track_associate alone
+FLOW_NO_HISTORY, FLOW_LOW_TEXTURE, FLOW_RESIDUAL, FLOW_OUTSIDE, FLOW_MOVED, FLOW_NOT_FINITE = 1, 2, 4, 8, 16, 32  # FLM_FLOW_*
 
 EXPORTS = [
     "flm_abi_version", "flm_last_error",
@@ -57,6 +58,7 @@ EXPORTS = [
     "flm_exit_opts_init", "flm_track_retire",
     "flm_views_opts_init", "flm_track_views_update", "flm_track_exit_views",
     "flm_annotate_opts_init", "flm_bgr_to_yuv", "flm_frames_annotate",
+    "flm_flow_pyramid_bytes", "flm_flow_pyramid", "flm_flow_opts_init", "flm_landmark_flow",
 ]
 
 
@@ -255,6 +257,21 @@ class AnnotateOpts(C.Structure):
             if values is not None:
                 for i, v in enumerate(values):
                     arr[i] = conv(v)
+        return o
+
+
+class FlowOpts(C.Structure):
+    """flm_flow_opts: the pyramid, the window and the gates of flm_landmark_flow (include/flm.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("levels", C.c_int32), ("radius", C.c_int32),
+                ("max_iter", C.c_int32), ("pad", C.c_int32), ("eps", C.c_double), ("min_eig", C.c_double),
+                ("max_err", C.c_double), ("max_move", C.c_double)]
+
+    @classmethod
+    def make(cls, levels=4, radius=7, max_iter=10, eps=0.03, min_eig=0.5, max_err=12.0, max_move=64.0):
+        o = cls()
+        load().flm_flow_opts_init(C.byref(o))
+        o.levels, o.radius, o.max_iter = int(levels), int(radius), int(max_iter)
+        o.eps, o.min_eig, o.max_err, o.max_move = float(eps), float(min_eig), float(max_err), float(max_move)
         return o
 
 
@@ -457,6 +474,14 @@ def _declare(lib):
     lib.flm_frames_annotate.restype = i
     lib.flm_frames_annotate.argtypes = [vp, vp, sz, i, i, i, C.POINTER(FrameFormat), vp, vp, sz, i, i,
                                         C.POINTER(AnnotateOpts), vp]
+    lib.flm_flow_pyramid_bytes.restype = sz
+    lib.flm_flow_pyramid_bytes.argtypes = [i, i, i]
+    lib.flm_flow_pyramid.restype = i
+    lib.flm_flow_pyramid.argtypes = [vp, vp, i, i, i, i, i, vp]
+    lib.flm_flow_opts_init.restype = None
+    lib.flm_flow_opts_init.argtypes = [C.POINTER(FlowOpts)]
+    lib.flm_landmark_flow.restype = i
+    lib.flm_landmark_flow.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, i, C.POINTER(FlowOpts), vp, vp, vp, vp]
 
 
 def load():

@@ -2094,3 +2094,130 @@ def annotate_frames_device(frames, lm, frame_index_dev=None, opts=None, src=None
     elif k:
         regions.zero_()
     return regions
+
+
+# ---- landmark flow: the landmarks carried between two forwards (include/flm.h, "landmark flow") -------------------------
+FLOW_NO_HISTORY, FLOW_LOW_TEXTURE, FLOW_RESIDUAL = _lib.FLOW_NO_HISTORY, _lib.FLOW_LOW_TEXTURE, _lib.FLOW_RESIDUAL
+FLOW_OUTSIDE, FLOW_MOVED, FLOW_NOT_FINITE = _lib.FLOW_OUTSIDE, _lib.FLOW_MOVED, _lib.FLOW_NOT_FINITE
+
+
+class LandmarkFlow:
+    """flm_flow_opts: the pyramid, the window and the gates of flm_landmark_flow (include/flm.h).  levels: pyramid levels,
+    1..6 (the crop's sides are multiples of 2^(levels-1)); radius: the window is (2*radius+1)^2 pixels, 1..7; max_iter:
+    iterations per level, 1..64; eps: a level stops when its update is shorter than this, in px; min_eig: the least
+    eigenvalue per pixel (grey levels squared) at which a level is solved; max_err: the largest mean absolute residual
+    (grey levels) and max_move: the longest move (crop px) of an accepted point -- both defaults are guesses that no
+    measurement on real faces backs.  levels=4 rests on a synthetic prototype (three levels lost 14 px shifts in a 256 px
+    crop); radius, max_iter, eps and min_eig are the customary values of such trackers, unmeasured here."""
+
+    def __init__(self, levels=4, radius=7, max_iter=10, eps=0.03, min_eig=0.5, max_err=12.0, max_move=64.0):
+        for name, v, lo, hi in (("levels", levels, 1, 6), ("radius", radius, 1, 7), ("max_iter", max_iter, 1, 64)):
+            if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= hi:
+                raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
+        eps, min_eig, max_err, max_move = float(eps), float(min_eig), float(max_err), float(max_move)
+        if not eps > 0.0:
+            raise ValueError("eps must be > 0, got %r" % eps)
+        if not min_eig >= 0.0:
+            raise ValueError("min_eig must be >= 0, got %r" % min_eig)
+        if not max_err >= 0.0:
+            raise ValueError("max_err must be >= 0, got %r" % max_err)
+        if not max_move > 0.0:
+            raise ValueError("max_move must be > 0, got %r" % max_move)
+        self.levels, self.radius, self.max_iter = int(levels), int(radius), int(max_iter)
+        self.eps, self.min_eig, self.max_err, self.max_move = eps, min_eig, max_err, max_move
+
+    def check_crop(self, h, w):
+        """ValueError unless crops of h x w have a pyramid of `levels` levels."""
+        t = 1 << (self.levels - 1)
+        if h % t or w % t or (h >> (self.levels - 1)) < 2 or (w >> (self.levels - 1)) < 2 or h > 32768 or w > 32768:
+            raise ValueError("crops of %dx%d have no pyramid of %d levels: the sides must be multiples of %d, at least %d "
+                             "and at most 32768" % (h, w, self.levels, t, 2 * t))
+
+    def pyramid_bytes(self, h, w):
+        return sum((h >> l) * (w >> l) for l in range(self.levels))
+
+    def struct(self):
+        return _lib.FlowOpts.make(self.levels, self.radius, self.max_iter, self.eps, self.min_eig, self.max_err, self.max_move)
+
+    def __repr__(self):
+        return ("LandmarkFlow(levels=%r, radius=%r, max_iter=%r, eps=%r, min_eig=%r, max_err=%r, max_move=%r)"
+                % (self.levels, self.radius, self.max_iter, self.eps, self.min_eig, self.max_err, self.max_move))
+
+
+def _check_flow(flow):
+    if not isinstance(flow, LandmarkFlow):
+        raise ValueError("flow must be an alignment.LandmarkFlow (got %r)" % (flow,))
+
+
+def flow_pyramid_device(crops, levels, out=None):
+    """The luma pyramids of N crops in one launch (flm_flow_pyramid).  crops: a contiguous CUDA uint8 [N,H,W,3] (B,G,R) or
+    [N,H,W] (luma) tensor; levels: 1..6, H and W multiples of 2^(levels-1) and at least twice that -> CUDA uint8
+    [N, bytes]: per crop its levels 0 .. levels-1 one after the other, level l of (H >> l) x (W >> l) bytes."""
+    import torch
+    if (not isinstance(crops, torch.Tensor) or crops.dtype != torch.uint8 or crops.dim() not in (3, 4)
+            or (crops.dim() == 4 and int(crops.shape[3]) != 3) or not crops.is_contiguous()):
+        raise ValueError("crops must be a contiguous CUDA uint8 [N,H,W,3] or [N,H,W] tensor")
+    if isinstance(levels, bool) or int(levels) != levels or not 1 <= int(levels) <= 6:
+        raise ValueError("levels must be an integer in [1, 6], got %r" % (levels,))
+    flow = LandmarkFlow(levels=int(levels))
+    n, h, w = [int(v) for v in crops.shape[:3]]
+    flow.check_crop(h, w)
+    if n > 131070:
+        raise ValueError("at most 131070 crops per call (got %d)" % n)
+    if not crops.is_cuda:
+        raise ValueError("crops must be a contiguous CUDA uint8 [N,H,W,3] or [N,H,W] tensor")
+    out = _out(out, torch.uint8, (n, flow.pyramid_bytes(h, w)), "out", crops.device)
+    _check_overlap(crops, out, "crops and out")
+    if n:
+        _lib.check(_lib.load().flm_flow_pyramid(_lib.stream_ptr(), _lib.ptr(crops), n, h, w, 1 if crops.dim() == 3 else 3,
+                                                int(levels), _lib.ptr(out)), "flm_flow_pyramid")
+    return out
+
+
+def landmark_flow_device(pyr_prev, pyr_cur, lm_prev, m, hw, flow, weights=None, out=None):
+    """The landmarks of K faces carried from the previous crops to the current ones in one launch (flm_landmark_flow;
+    include/flm.h states it line by line).
+
+    pyr_prev, pyr_cur: CUDA uint8 [K, bytes] as `flow_pyramid_device` makes them with flow.levels, of crops of hw = (H, W)
+    cut from the two frames with the SAME matrices m (CUDA float32 [K,2,3] frame px -> crop px); lm_prev: contiguous CUDA
+    float64 [K,C,2] in FRAME px, a negative or non-finite point has no history; weights: None or contiguous CUDA float64
+    [K,C]; out: None or a tuple (lm, w, err, flags) of tensors to write, any of them None.
+    Returns (lm float64 [K,C,2] in CROP px, (-1,-1) for a rejected point; w float64 [K,C], the point's weight (1.0
+    without weights), 0 for a rejected point; err int32 [K,C], the window's sum of absolute differences, -1 where it was
+    not reached; flags int32 [K,C], 0 or the FLOW_* bits that rejected the point).  The landmarks are what
+    `track_step_device` takes with grid_hw = in_hw = hw."""
+    import torch
+    _check_flow(flow)
+    h, w = _sizes(hw, "hw")
+    flow.check_crop(h, w)
+    if not isinstance(lm_prev, torch.Tensor) or lm_prev.dim() != 3 or int(lm_prev.shape[2]) != 2:
+        raise ValueError("lm_prev must be a contiguous CUDA float64 [K,C,2] tensor")
+    k, c = int(lm_prev.shape[0]), int(lm_prev.shape[1])
+    _check_out(lm_prev, torch.float64, (k, c, 2), "lm_prev")
+    if k > 65535 or c > 1024:
+        raise ValueError("at most 65535 faces of 1024 landmarks per call (got %d of %d)" % (k, c))
+    nb = flow.pyramid_bytes(h, w)
+    _check_out(pyr_prev, torch.uint8, (k, nb), "pyr_prev")
+    _check_out(pyr_cur, torch.uint8, (k, nb), "pyr_cur")
+    _check_matrices(m, k)
+    if weights is not None:
+        _check_out(weights, torch.float64, (k, c), "weights")
+    o_lm, o_w, o_err, o_flags = (None,) * 4 if out is None else out
+    dev = lm_prev.device
+    o_lm = _out(o_lm, torch.float64, (k, c, 2), "out lm", dev)
+    o_w = _out(o_w, torch.float64, (k, c), "out w", dev)
+    o_err = _out(o_err, torch.int32, (k, c), "out err", dev)
+    o_flags = _out(o_flags, torch.int32, (k, c), "out flags", dev)
+    outs = (o_lm, o_w, o_err, o_flags)
+    for a, t in enumerate(outs):
+        for src in (pyr_prev, pyr_cur, lm_prev, m, weights):
+            _check_overlap(t, src, "an output and an input")
+        for u in outs[a + 1:]:
+            _check_overlap(t, u, "two outputs")
+    if k and c:
+        fo = flow.struct()
+        _lib.check(_lib.load().flm_landmark_flow(_lib.stream_ptr(), _lib.ptr(pyr_prev), _lib.ptr(pyr_cur), k, h, w,
+                                                 _lib.ptr(lm_prev), _ptr(weights), _lib.ptr(m), c, _lib.C.byref(fo),
+                                                 _lib.ptr(o_lm), _lib.ptr(o_w), _lib.ptr(o_err), _lib.ptr(o_flags)),
+                   "flm_landmark_flow")
+    return outs

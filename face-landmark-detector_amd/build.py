@@ -44,6 +44,7 @@ SOURCES = [
     "flm_track_views.hip",
     "flm_pose.hip",
     "flm_annotate.hip",
+    "flm_flow.hip",
     "flm_mobile.hip",
 ]
 # -ffp-contract=off: only the fma() calls written in the sources fuse, so the arithmetic of the

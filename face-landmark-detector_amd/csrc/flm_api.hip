@@ -2184,4 +2184,148 @@ int flm_frames_annotate(flm_stream_t stream, uint8_t* frames, size_t frame_strid
   return launch_frames_annotate(static_cast<hipStream_t>(stream), g);
 }
 
+// ---- landmark flow (flm_flow.hip) -----------------------------------------------------------------------------------
+
+size_t flm_flow_pyramid_bytes(int h, int w, int levels) {
+  if (h < 1 || w < 1 || levels < 1 || levels > 6) return 0;
+  size_t bytes = 0;
+  for (int l = 0; l < levels; ++l) bytes += (size_t)(h >> l) * (size_t)(w >> l);
+  return bytes;
+}
+
+// The geometry both flow calls share.
+static int check_flow_geometry(const char* who, int h, int w, int levels) {
+  if (levels < 1 || levels > 6) {
+    set_error("%s: levels=%d, needs 1 <= levels <= 6", who, levels);
+    return FLM_ERR_SHAPE;
+  }
+  const int t = 1 << (levels - 1);
+  if (h < 1 || w < 1 || h > 32768 || w > 32768 || h % t || w % t || (h >> (levels - 1)) < 2 || (w >> (levels - 1)) < 2) {
+    set_error("%s: crop %dx%d with %d levels, needs h and w <= 32768, multiples of 2^(levels-1) = %d and at least %d",
+              who, h, w, levels, t, 2 * t);
+    return FLM_ERR_SHAPE;
+  }
+  return FLM_OK;
+}
+
+int flm_flow_pyramid(flm_stream_t stream, const uint8_t* src, int n, int h, int w, int ch, int levels, uint8_t* pyr) {
+  const char* who = "flm_flow_pyramid";
+  if (!src || !pyr) {
+    set_error("%s: null argument", who);
+    return FLM_ERR_ARG;
+  }
+  if (n < 1 || n > 131070) {
+    set_error("%s: n=%d, needs 1 <= n <= 131070", who, n);
+    return FLM_ERR_SHAPE;
+  }
+  if (ch != 1 && ch != 3) {
+    set_error("%s: ch=%d, needs ch 1 (luma) or 3 (BGR)", who, ch);
+    return FLM_ERR_SHAPE;
+  }
+  if (int rc = check_flow_geometry(who, h, w, levels)) return rc;
+  const long long tiles = (long long)((h + 31) / 32) * ((w + 31) / 32) * n;
+  if (tiles >= (1ll << 31)) {
+    set_error("%s: %d crops of %dx%d are %lld tiles of 32x32, needs fewer than 2^31", who, n, h, w, tiles);
+    return FLM_ERR_SHAPE;
+  }
+  if (ranges_overlap(src, (size_t)n * h * w * ch, pyr, (size_t)n * flm_flow_pyramid_bytes(h, w, levels))) {
+    set_error("%s: pyr_dev overlaps src_dev", who);
+    return FLM_ERR_ARG;
+  }
+  return launch_flow_pyramid(static_cast<hipStream_t>(stream), src, n, h, w, ch, levels, pyr);
+}
+
+void flm_flow_opts_init(flm_flow_opts* opts) {
+  if (!opts) return;
+  opts->struct_size = (uint32_t)sizeof(flm_flow_opts);
+  opts->reserved = 0;
+  opts->levels = 4;
+  opts->radius = 7;
+  opts->max_iter = 10;
+  opts->pad = 0;
+  opts->eps = 0.03;
+  opts->min_eig = 0.5;
+  opts->max_err = 12.0;
+  opts->max_move = 64.0;
+}
+
+int flm_landmark_flow(flm_stream_t stream, const uint8_t* pyr_prev, const uint8_t* pyr_cur, int k, int h, int w,
+                      const double* lm_prev, const double* w_prev, const float* m, int c, const flm_flow_opts* opts,
+                      double* lm_out, double* w_out, int32_t* err_out, int32_t* flags_out) {
+  const char* who = "flm_landmark_flow";
+  if (!pyr_prev || !pyr_cur || !lm_prev || !m || !lm_out || !flags_out) {
+    set_error("%s: null argument", who);  // (w_prev, opts, w_out and err_out are optional)
+    return FLM_ERR_ARG;
+  }
+  flm_flow_opts defaults;
+  flm_flow_opts_init(&defaults);
+  if (!opts) opts = &defaults;
+  if (opts->struct_size < sizeof(flm_flow_opts)) {
+    set_error("%s: flm_flow_opts struct_size %u is smaller than this library's %zu (initialise with "
+              "flm_flow_opts_init)", who, opts->struct_size, sizeof(flm_flow_opts));
+    return FLM_ERR_ARG;
+  }
+  if (opts->reserved != 0 || opts->pad != 0) {
+    set_error("%s: flm_flow_opts reserved=%u, pad=%d, both must be 0", who, opts->reserved, opts->pad);
+    return FLM_ERR_ARG;
+  }
+  if (!(opts->eps > 0.0)) {
+    set_error("%s: eps=%g, needs eps > 0", who, opts->eps);
+    return FLM_ERR_ARG;
+  }
+  if (!(opts->min_eig >= 0.0)) {
+    set_error("%s: min_eig=%g, needs min_eig >= 0", who, opts->min_eig);
+    return FLM_ERR_ARG;
+  }
+  if (!(opts->max_err >= 0.0)) {
+    set_error("%s: max_err=%g, needs max_err >= 0", who, opts->max_err);
+    return FLM_ERR_ARG;
+  }
+  if (!(opts->max_move > 0.0)) {
+    set_error("%s: max_move=%g, needs max_move > 0", who, opts->max_move);
+    return FLM_ERR_ARG;
+  }
+  if (k < 1 || k > 65535) {
+    set_error("%s: k=%d, needs 1 <= k <= 65535", who, k);
+    return FLM_ERR_SHAPE;
+  }
+  if (c < 1 || c > 1024) {
+    set_error("%s: c=%d, needs 1 <= c <= 1024", who, c);
+    return FLM_ERR_SHAPE;
+  }
+  if (opts->radius < 1 || opts->radius > 7) {
+    set_error("%s: radius=%d, needs 1 <= radius <= 7", who, opts->radius);
+    return FLM_ERR_SHAPE;
+  }
+  if (opts->max_iter < 1 || opts->max_iter > 64) {
+    set_error("%s: max_iter=%d, needs 1 <= max_iter <= 64", who, opts->max_iter);
+    return FLM_ERR_SHAPE;
+  }
+  if (int rc = check_flow_geometry(who, h, w, opts->levels)) return rc;
+  const size_t pyr = (size_t)k * flm_flow_pyramid_bytes(h, w, opts->levels), kc = (size_t)k * c;
+  const struct { const void* p; size_t bytes; const char* name; } in[] = {
+      {pyr_prev, pyr, "pyr_prev_dev"}, {pyr_cur, pyr, "pyr_cur_dev"}, {lm_prev, kc * 2 * sizeof(double), "lm_prev_dev"},
+      {w_prev, w_prev ? kc * sizeof(double) : 0, "w_prev_dev"}, {m, (size_t)k * 6 * sizeof(float), "m_dev"}};
+  const struct { const void* p; size_t bytes; const char* name; } out[] = {
+      {lm_out, kc * 2 * sizeof(double), "lm_out_dev"}, {w_out, w_out ? kc * sizeof(double) : 0, "w_out_dev"},
+      {err_out, err_out ? kc * sizeof(int32_t) : 0, "err_out_dev"}, {flags_out, kc * sizeof(int32_t), "flags_out_dev"}};
+  for (size_t a = 0; a < 4; ++a) {
+    if (!out[a].p) continue;
+    for (const auto& b : in) {
+      if (b.p && ranges_overlap(out[a].p, out[a].bytes, b.p, b.bytes)) {
+        set_error("%s: %s overlaps %s", who, out[a].name, b.name);
+        return FLM_ERR_ARG;
+      }
+    }
+    for (size_t b = a + 1; b < 4; ++b) {
+      if (out[b].p && ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) {
+        set_error("%s: %s overlaps %s", who, out[a].name, out[b].name);
+        return FLM_ERR_ARG;
+      }
+    }
+  }
+  return launch_landmark_flow(static_cast<hipStream_t>(stream), pyr_prev, pyr_cur, k, h, w, lm_prev, w_prev, m, c, opts,
+                              lm_out, w_out, err_out, flags_out);
+}
+
 }  // extern "C"

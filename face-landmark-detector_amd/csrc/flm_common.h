@@ -461,6 +461,12 @@ struct AnnotateArgs {
 };
 int launch_frames_annotate(hipStream_t s, const AnnotateArgs& g);
 
+// landmark flow (flm_flow.hip); sizes, options, pointers and overlaps have been checked by the caller (flm_api.hip)
+int launch_flow_pyramid(hipStream_t s, const uint8_t* src, int n, int h, int w, int ch, int levels, uint8_t* pyr);
+int launch_landmark_flow(hipStream_t s, const uint8_t* pyr_prev, const uint8_t* pyr_cur, int k, int h, int w,
+                         const double* lm_prev, const double* w_prev, const float* m, int c, const flm_flow_opts* opts,
+                         double* lm_out, double* w_out, int32_t* err_out, int32_t* flags_out);
+
 // Bijective XCD-aware remap of a 1-D grid: blocks that the dispatcher deals to the same XCD
 // (b % 8) receive consecutive logical ids, so neighbours in logical order share an L2.
 __device__ __forceinline__ int xcd_remap(int b, int nblk) {

@@ -666,6 +666,36 @@ def head_pose(landmarks, weights=None, pose=None):
                 count=rec[:, 13], ok=rec[:, 14], angles=rec[:, 15:18])
 
 
+def landmark_flow(prev_crops, cur_crops, points, flow=None):
+    """Points carried from one crop to the next by sparse optical flow (alignment.flow_pyramid_device and
+    alignment.landmark_flow_device: a pyramidal, translation-only Lucas-Kanade step per point, two launches), numpy in and
+    numpy out.  prev_crops, cur_crops: uint8 [K,H,W,3] (B,G,R) or [K,H,W] (luma) of one size, H and W multiples of
+    2^(flow.levels-1); points: float64 [K,C,2] in crop px of prev_crops, a negative or non-finite point is left out;
+    flow: None or an `alignment.LandmarkFlow`.  Returns (points float64 [K,C,2] in cur_crops, (-1,-1) for a rejected
+    point; err int32 [K,C], the window's sum of absolute differences in 1/1024 grey levels, -1 where it was not reached;
+    flags int32 [K,C], 0 or the alignment.FLOW_* bits that rejected the point)."""
+    import torch
+    if flow is None:
+        flow = alignment.LandmarkFlow()
+    elif not isinstance(flow, alignment.LandmarkFlow):
+        raise ValueError("flow must be None or an alignment.LandmarkFlow (got %r)" % (flow,))
+    prev_crops, cur_crops = np.ascontiguousarray(prev_crops), np.ascontiguousarray(cur_crops)
+    if (prev_crops.dtype != np.uint8 or prev_crops.shape != cur_crops.shape or cur_crops.dtype != np.uint8
+            or prev_crops.ndim not in (3, 4) or (prev_crops.ndim == 4 and prev_crops.shape[3] != 3)):
+        raise ValueError("prev_crops and cur_crops must be uint8 [K,H,W,3] or [K,H,W] arrays of one shape")
+    points = np.ascontiguousarray(points, np.float64)
+    k, h, w = prev_crops.shape[:3]
+    if points.ndim != 3 or points.shape[0] != k or points.shape[2] != 2:
+        raise ValueError("points must be float64 [%d,C,2]" % k)
+    flow.check_crop(h, w)
+    dev = _lib.require_gpu()
+    both = torch.from_numpy(np.concatenate([prev_crops, cur_crops])).to(dev)
+    pyr = alignment.flow_pyramid_device(both, flow.levels)
+    m = torch.eye(2, 3, dtype=torch.float32, device=dev).repeat(k, 1, 1).contiguous()
+    lm, _, err, flags = alignment.landmark_flow_device(pyr[:k], pyr[k:], torch.from_numpy(points).to(dev), m, (h, w), flow)
+    return lm.cpu().numpy(), err.cpu().numpy(), flags.cpu().numpy()
+
+
 # ---- tracking: faces followed across frames from their own landmarks ---------------------------------------------------
 class FaceTracker:
     """Faces followed across the frames of a stream on the device: the landmarks of frame t place the crop of frame t+1.
@@ -744,13 +774,25 @@ class FaceTracker:
     with the aligned faces that call returned, in `aligned_format`: a view of a [capacity,...] buffer the tracker owns,
     overwritten by the next step, with no download and no synchronisation.  A landmark the decode rejected is (-1,-1)
     and drags its triangles there; a slot without a face gives a zero face, as in `aligned`.  Without `mesh` the tracker
-    makes the launches it makes without it and returns the same bits."""
+    makes the launches it makes without it and returns the same bits.  flow: None, True (the defaults) or an
+    `alignment.LandmarkFlow` whose pyramid fits the network input: `step_flow` then serves a tick WITHOUT the forward, by
+    carrying the landmarks of the last step into the new frame with sparse optical flow; see `step_flow`.  The tracker
+    then keeps, by device copies alone, the last step's raw landmarks in frame px (before the filter), with
+    weights="score" their weights, and the ring slots that step cut from, and owns the two crop sets, their pyramids and
+    `flow_flags` and `flow_err` int32 [capacity,C].  Without `flow` the tracker allocates nothing more and `step` returns
+    the same bits."""
 
     def __init__(self, model, frame_hw, capacity, out_size=(112, 112), template=None, crop_template=None, n_points=4,
                  thresh=0.0, weights=None, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"),
                  crop_samples=1, samples=1, aligned_format=None, frame_format=None, smooth=None, associate=None,
-                 best_shot=None, streams=1, pose=None, mesh=None, exits=None, views=None):
+                 best_shot=None, streams=1, pose=None, mesh=None, flow=None, exits=None, views=None):
         import torch
+        if flow is True:
+            flow = alignment.LandmarkFlow()
+        elif flow is False:
+            flow = None
+        if flow is not None and not isinstance(flow, alignment.LandmarkFlow):
+            raise ValueError("flow must be None, True or an alignment.LandmarkFlow (got %r)" % (flow,))
         if mesh is not None and mesh is not False and mesh is not True and not isinstance(mesh, alignment.FaceMesh):
             raise ValueError("mesh must be None, True or an alignment.FaceMesh (got %r)" % (mesh,))
         if views is True:
@@ -805,6 +847,9 @@ class FaceTracker:
             raise ValueError("min_score, min_side and max_side must not be NaN")
         c = int(model.n_classes)
         ih, iw = int(model.input_height), int(model.input_width)
+        if flow is not None:
+            flow.check_crop(ih, iw)
+        self.flow, self._flow_ok = flow, False   # _flow_ok: the last call was `step` or `step_flow` (step_flow)
         tm = alignment.canonical_template(c, oh, ow) if template is None else template
         tc = alignment.canonical_template(c, ih, iw) if crop_template is None else crop_template
         tm, tc = [t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in (tm, tc)]
@@ -896,6 +941,18 @@ class FaceTracker:
             self._mesh_buf = torch.zeros(mfmt.shape(n, *self.out_size), dtype=mfmt.torch_dtype, device=dev)
             self.mesh.tensors(dev)
             self.mesh.map(dev, *self.out_size)
+        if self.flow is not None:       # (-1,-1): the landmark has no history
+            c = int(self.model.n_classes)
+            ih, iw = int(self.model.input_height), int(self.model.input_width)
+            self._flow_lm = torch.full((n, c, 2), -1.0, dtype=torch.float64, device=dev)   # the last step's RAW landmarks
+            self._flow_w = torch.zeros((n, c), dtype=torch.float64, device=dev) if self.weights is not None else None
+            self._flow_slots = torch.zeros((n,), dtype=torch.int32, device=dev)            # the ring slots of that step
+            self._flow_crops = torch.zeros((2 * n, ih, iw, 3), dtype=torch.uint8, device=dev)   # previous | current
+            self._flow_pyr = torch.zeros((2 * n, self.flow.pyramid_bytes(ih, iw)), dtype=torch.uint8, device=dev)
+            self._flow_crop_lm = torch.full((n, c, 2), -1.0, dtype=torch.float64, device=dev)
+            self._flow_crop_w = torch.zeros((n, c), dtype=torch.float64, device=dev)
+            self.flow_err = torch.full((n, c), -1, dtype=torch.int32, device=dev)
+            self.flow_flags = torch.zeros((n, c), dtype=torch.int32, device=dev)
         if self.view_opts is not None:  # -1: the bin holds nothing
             b = self.view_opts.bins
             face = tuple(self.gallery.shape[1:])
@@ -935,6 +992,7 @@ class FaceTracker:
         n = len(slots)
         if not n:
             return
+        self._flow_ok = False
         self._state()
         sq = np.asarray(face_boxes(boxes), np.int32).reshape(n, 4)
         both = torch.from_numpy(np.concatenate([sq.reshape(-1), np.asarray(slots, np.int32)])).to(self.boxes.device)
@@ -1012,6 +1070,7 @@ class FaceTracker:
             raise ValueError("update takes at least one row of detections (n says how many are valid)")
         if n is not None and not isinstance(n, torch.Tensor):
             raise ValueError("n must be None or a CUDA int32 tensor of one element")
+        self._flow_ok = False
         self._state()
         if not isinstance(det, torch.Tensor):
             det = torch.from_numpy(np.ascontiguousarray(det)).to(self.boxes.device)
@@ -1048,6 +1107,7 @@ class FaceTracker:
             raise ValueError("update takes at most %d detections per stream (got %d)" % (alignment.ASSOC_MAX, d))
         if d < 1:
             raise ValueError("update takes at least one row of detections per stream (n says how many are valid)")
+        self._flow_ok = False
         self._state()
         if not isinstance(detections, torch.Tensor):
             flat = np.zeros(s * d * 4 + s, np.int32)
@@ -1123,10 +1183,41 @@ class FaceTracker:
             raise ValueError("the ring holds %dx%d frames, the tracker was made for %dx%d" % ((rh, rw) + self.frame_hw))
         return frame_id, dt, nf
 
-    def _sequence(self, ring, src, step, best_update, workspace, frame_id, quality_out=None):
-        """The step sequence, stated once for `step` and `step_active`: the uint8 crop warp -> model.forward_device ->
-        (lm, wd) -> the step call -> with pose, the head-pose call (at the rows' slots where src has a "slot") -> the
-        aligned warp -> with best_shot, the quality call and the best update (with pose, times its factor).
+    def _forward_landmarks(self, ring, src, workspace):
+        """The landmark source of `step`, `step_active` and `step_live`: the uint8 crop warp -> model.forward_device.
+        Returns (lm on the output grid, wd: the scores or None, the grid's size)."""
+        model = self.model
+        crops = alignment.warp_frames_device(ring, src["m"], model.input_height, model.input_width, samples=self.crop_samples,
+                                             fmt=self._crop_format, frame_index_dev=src["frame_index"],
+                                             boxes_dev=src["boxes"], src=self.frame_format)
+        out = "landmarks" if self.weights is None else "landmark_stats"
+        res = model.forward_device(crops, out, n_points=self.n_points, thresh=self.thresh,
+                                   workspace=workspace(int(crops.shape[0]), out))
+        lm, wd = (res, None) if self.weights is None else (res[..., :2], res[..., 2])
+        return lm, wd, (model.output_height, model.output_width)
+
+    def _flow_landmarks(self, ring, src, workspace):
+        """The landmark source of `step_flow`: the uint8 crop warp of the PREVIOUS ring slots and of the new ones, both
+        with the slots' current matrices -> the pyramids of all 2*capacity crops in one launch ->
+        alignment.landmark_flow_device from the last step's raw landmarks.  Returns (lm in crop px, wd: the carried
+        weights or None, the crop's size: the grid of these landmarks is the crop itself)."""
+        n = self.capacity
+        ih, iw = self.model.input_height, self.model.input_width
+        for half, slots in ((self._flow_crops[:n], self._flow_slots), (self._flow_crops[n:], src["frame_index"])):
+            alignment.warp_frames_device(ring, src["m"], ih, iw, samples=self.crop_samples, fmt=self._crop_format,
+                                         frame_index_dev=slots, boxes_dev=src["boxes"], src=self.frame_format, out=half)
+        alignment.flow_pyramid_device(self._flow_crops, self.flow.levels, out=self._flow_pyr)
+        lm, wd, _, _ = alignment.landmark_flow_device(
+            self._flow_pyr[:n], self._flow_pyr[n:], self._flow_lm, src["m"], (ih, iw), self.flow, weights=self._flow_w,
+            out=(self._flow_crop_lm, self._flow_crop_w, self.flow_err, self.flow_flags))
+        return lm, (None if self.weights is None else wd), (ih, iw)
+
+    def _sequence(self, ring, src, step, best_update, workspace, frame_id, quality_out=None, landmarks=None,
+                  history=False):
+        """The step sequence, stated once for `step`, `step_flow` and `step_active`: the landmark source (`landmarks`;
+        None: the uint8 crop warp -> model.forward_device) -> (lm, wd) -> the step call -> with history, the raw landmarks
+        and weights kept for `step_flow` -> with pose, the head-pose call (at the rows' slots where src has a "slot") ->
+        the aligned warp -> with best_shot, the quality call and the best update (with pose, times its factor).
         src: where the matrices ("m"), boxes and ring slots ("frame_index") of the faces are read -- the state itself or
         the snapshot; step, best_update: the caller's wrapper of the two, with what only that wrapper takes bound;
         workspace(batch, mode): the forward workspace, or None for the model's cached ones.  Returns (aligned, m_align,
@@ -1134,16 +1225,17 @@ class FaceTracker:
         model = self.model
         ih, iw = model.input_height, model.input_width
         where = dict(frame_index_dev=src["frame_index"], boxes_dev=src["boxes"], src=self.frame_format)
-        crops = alignment.warp_frames_device(ring, src["m"], ih, iw, samples=self.crop_samples, fmt=self._crop_format, **where)
-        out = "landmarks" if self.weights is None else "landmark_stats"
-        res = model.forward_device(crops, out, n_points=self.n_points, thresh=self.thresh,
-                                   workspace=workspace(int(crops.shape[0]), out))
-        lm, wd = (res, None) if self.weights is None else (res[..., :2], res[..., 2])
+        lm, wd, grid_hw = (landmarks or self._forward_landmarks)(ring, src, workspace)
         filt = {} if self.smooth is None else dict(filter=self.smooth, state=self.filter_state)
-        stepped = step(lm, src["m"], src["boxes"], grid_hw=(model.output_height, model.output_width), in_hw=(ih, iw),
+        stepped = step(lm, src["m"], src["boxes"], grid_hw=grid_hw, in_hw=(ih, iw),
                        frame_hw=self.frame_hw, tmpl_crop=self.crop_template, tmpl_align=self.template, weights=wd,
                        **self.limits, **filt)
         lm_frame, m_align, status = stepped[0], stepped[1], stepped[-1]
+        if history:   # (a tracker that smooths had the step write its raw points into _flow_lm)
+            if self.smooth is None:
+                self._flow_lm.copy_(lm_frame)
+            if wd is not None:
+                self._flow_w.copy_(wd)
         factor = {}
         if self.head_pose is not None:
             if self.best_shot is not None:
@@ -1187,18 +1279,52 @@ class FaceTracker:
         on.  `dt`, for a tracker that smooths: the seconds since the previous step, a host number (None: 1/fps of the
         filter).  `frame_id`, for a tracker with `best_shot`: the host integer `best_frame` records for a face taken
         in this step (None: the number of steps this tracker has made before this one)."""
+        return self._step_all(ring, frame_index, dt, frame_id, None)
+
+    def step_flow(self, ring, frame_index, dt=None, frame_id=None):
+        """`step` without the forward, for a tracker made with `flow`: the landmarks of the last step are carried into the
+        new frame by sparse optical flow (alignment.landmark_flow_device) and take the forward's place; everything after
+        them -- the track step with its filter, both fits, the status and the next crop, then pose, the aligned warp,
+        mesh, best shot and views -- is the code of `step`.  Arguments and results as `step`.  Sequence: the uint8 crop
+        warp of the PREVIOUS ring slots (`frame_slots` of the last step) and of the new ones, both with the slots' current
+        matrices -> alignment.flow_pyramid_device over all of them -> alignment.landmark_flow_device from the last step's
+        RAW landmarks (before the filter) and, with weights="score", its weights -> alignment.track_step_device with the
+        crop as its grid -> the rest of `step`.  `flow_flags` and `flow_err` int32 [capacity,C], the tracker's own, say
+        what the flow did with every landmark (0, or the alignment.FLOW_* bits that rejected it; a landmark the forward
+        rejected at the key frame stays rejected until the next `step`).  No upload beyond `step`'s, no download, no
+        synchronisation.
+
+        May follow only `step` or `step_flow`: `seed`, `update`, `step_active`, `step_live` and `retire(flush=True)` leave
+        tracks without a history the device could use, and the next call must be `step`.  THE CALLER KEEPS THE PREVIOUS
+        FRAME IN THE RING until this call has run: it is read again here.  The usual loop is `update` + `step` on the
+        ticks the detector runs, `step_flow` on the others."""
+        if self.flow is None:
+            raise ValueError("step_flow needs a tracker made with flow")
+        if not self._flow_ok:
+            raise ValueError("step_flow may follow only step or step_flow: after seed, update, step_active, step_live or "
+                             "retire(flush=True) the next call must be step")
+        return self._step_all(ring, frame_index, dt, frame_id, self._flow_landmarks)
+
+    def _step_all(self, ring, frame_index, dt, frame_id, landmarks):
+        """`step` (landmarks None: the forward) and `step_flow` (the flow source), stated once."""
         import functools
         frame_id, dt, nf = self._step_prologue(ring, dt, frame_id, host_dt=True)
-        if self.streams > 1:
-            self._stream_frames(frame_index, nf)
-        else:
+        if self.streams == 1:
             frame_index = int(frame_index)
             if not 0 <= frame_index < nf:
                 raise ValueError("frame_index must name a ring slot in [0, %d)" % nf)
+        elif landmarks is not None:   # check before the copy below: a rejected call leaves the history as it was
+            self._stream_frame_index(frame_index, nf, range(self.streams))
+        history = self.flow is not None
+        if landmarks is not None:
+            self._flow_slots.copy_(self.frame_slots)
+        if self.streams > 1:
+            self._stream_frames(frame_index, nf)
         self._state()
         self._retire(frame_id)
         if self.streams == 1:
             self.frame_slots.fill_(frame_index)
+        raw = dict(lm_raw=self._flow_lm) if history and self.smooth is not None else {}
 
         def best_update(faces, rec, lm, status, **kw):
             alignment.track_best_update_device(faces, rec, lm, self.best_q, self._best_q_spare, status=status,
@@ -1207,8 +1333,10 @@ class FaceTracker:
         res = self._sequence(
             ring, dict(m=self.m_crop, boxes=self.boxes, frame_index=self.frame_slots),
             functools.partial(alignment.track_step_device, m_next=self.m_crop, boxes_next=self._boxes_spare,
-                              status=self.status, dt=dt),
-            best_update, lambda n, out: None, frame_id, quality_out=self._quality_rec if self.best_shot is not None else None)
+                              status=self.status, dt=dt, **raw),
+            best_update, lambda n, out: None, frame_id, quality_out=self._quality_rec if self.best_shot is not None else None,
+            landmarks=landmarks, history=history)
+        self._flow_ok = True
         self.boxes, self._boxes_spare = self._boxes_spare, self.boxes
         if self.best_shot is not None:
             self.best_q, self._best_q_spare = self._best_q_spare, self.best_q
@@ -1381,6 +1509,7 @@ class FaceTracker:
         # ---- frame_index
         fi_host = self._stream_frame_index(frame_index, nf, act_host)
         dt_host, dt_dev, dt_scalar = self._stream_dt(dt, named)
+        self._flow_ok = False
         self._state()
         dev = self.boxes.device
         model = self.model
@@ -1466,6 +1595,7 @@ class FaceTracker:
             on_host = [1 if i in set(named) else 0 for i in range(s)]
         fi_host = self._stream_frame_index(frame_index, nf, named)
         dt_host, dt_dev, dt_scalar = self._stream_dt(dt, range(s) if named is None else named)
+        self._flow_ok = False
         self._state()
         self._retire(frame_id)
         up = self._upload(dt_host, fi_host, on_host)
@@ -1530,6 +1660,8 @@ class FaceTracker:
         if self.exit_opts is None:
             raise ValueError("retire() needs a tracker made with exits")
         frame_id = self._steps if frame_id is None else alignment._frame_id(frame_id)
+        if flush:
+            self._flow_ok = False
         self._state()
         self._retire(frame_id, flush=bool(flush))
         return self.exit_head

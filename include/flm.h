@@ -1514,6 +1514,89 @@ int flm_frames_annotate(flm_stream_t stream, uint8_t* frames_dev, size_t frame_s
                         const double* lm_dev, size_t lm_stride, int k, int c,
                         const flm_annotate_opts* opts /* NULL = defaults */, int32_t* regions_dev /*[K,4], out*/);
 
+/* ---- landmark flow: carrying the landmarks from one frame to the next without a forward --------------------------------
+ * Between two forwards the landmarks of a track can be carried by sparse optical flow: a pyramidal, translation-only
+ * Lucas-Kanade step per landmark between two crops cut from two frames with the SAME matrix.  flm_flow_pyramid makes the
+ * luma pyramids of the crops (one launch), flm_landmark_flow moves every landmark (one launch, a wave per landmark); no
+ * workspace, no allocation, no atomics, no synchronisation.  The result is landmarks in CROP pixels with "negative means
+ * rejected", which flm_track_step takes as landmarks on a grid of the crop's own size (sx = sy = 1).
+ *
+ * Arithmetic.  Integers are int64 unless a range is given; everything summed over a window is an exact integer, so the
+ * order of a sum does not matter.  float64 lines are one IEEE operation per written operator, in the written order,
+ * nothing fused.  >> is an arithmetic shift.
+ *  Luma.  ch = 3 (B, G, R bytes): Y = (1868*b + 9617*g + 4899*r + 8192) >> 14, the weights of flm_face_quality's luma;
+ *    ch = 1: Y is the byte.
+ *  Pyramid.  Level 0 is Y [h,w]; level l+1 at (y,x) is (a + b + c + d + 2) >> 2 of the 2x2 block of level l at (2y,2x);
+ *    level l has (h >> l) x (w >> l) bytes.  The pyramid of one image is its levels 0 .. levels-1 one after the other,
+ *    dense: flm_flow_pyramid_bytes(h, w, levels) = sum over l of (h >> l)*(w >> l) bytes (0 for sizes < 1 or levels
+ *    outside [1, 6]); image i of a call starts at i times that.  A level-l coordinate is x_l = (x_0 + 0.5) / 2^l - 0.5.
+ *  Sample S(I, x, y) on a level of Hl x Wl:  ix = floor(x), ax = (int)((x - ix) * 32.0), likewise iy, ay; the four reads
+ *    are at ix, ix+1, iy, iy+1, each clamped to the level (the edge is replicated);
+ *    S = (32-ax)*(32-ay)*p00 + ax*(32-ay)*p01 + (32-ax)*ay*p10 + ax*ay*p11, an int32 in [0, 255*1024].
+ *  Per point (x, y) = lm_prev of face f, m = m_dev[f] widened to double, r = radius, n = (2r+1)^2, window offsets
+ *  i, j in [-r, r]:
+ *    NO_HISTORY (1) unless x >= 0 and y >= 0 and both are finite.  Otherwise
+ *    p0 = ((m00*x + m01*y) + m02, (m10*x + m11*y) + m12); NOT_FINITE (32) unless both |p0| <= 2^20.  Otherwise
+ *    for l = levels-1 down to 0:
+ *      p_l = (p0 + 0.5) / 2^l - 0.5;  at the top level the guess is q = p_l
+ *      T = S(prev_l, p_l + (i, j));  Gx = S(prev_l, p_l + (i+1, j)) - S(prev_l, p_l + (i-1, j));  Gy likewise in j
+ *        (twice the gradient; "p_l + (i, j)" is the float64 sum of the coordinate and the integer)
+ *      A = sum Gx*Gx, B = sum Gx*Gy, C = sum Gy*Gy (< 2^47), each converted to double;  det = A*C - B*B
+ *      e = (((A + C) - sqrt((A-C)*(A-C) + 4.0*B*B)) / 2.0) / ((double)n * 4194304.0)
+ *        (the smaller eigenvalue of the structure tensor per pixel, in grey levels squared)
+ *      if !(e >= min_eig): at l > 0 the level is skipped and q carried; at l = 0 LOW_TEXTURE (2) is set.  Otherwise
+ *      up to max_iter times:
+ *        D = T - S(cur_l, q + (i, j));  bx = sum D*Gx, by = sum D*Gy, each converted to double
+ *        dx = 2.0*(C*bx - B*by)/det;  dy = 2.0*(A*by - B*bx)/det;  q = q + (dx, dy)
+ *        unless both |q| <= 2^20 (a NaN fails): NOT_FINITE (32), and the point ends here, err = -1
+ *        stop after the update when dx*dx + dy*dy < eps*eps
+ *      between levels (l > 0): q = 2.0*q + 0.5
+ *    err = sum |T - S(cur_0, q + (i, j))| with the T of level 0 (<= 58.7 M: an int32)
+ *    RESIDUAL (4) if !((double)err / ((double)n * 1024.0) <= max_err)
+ *    OUTSIDE  (8) unless 0 <= qx <= w-1 and 0 <= qy <= h-1
+ *    MOVED   (16) if !((qx-p0x)*(qx-p0x) + (qy-p0y)*(qy-p0y) <= max_move*max_move)
+ *  Outputs.  flags == 0: lm_out = q and w_out = w_prev (1.0 for a NULL w_prev_dev).  Otherwise lm_out = (-1,-1), w_out =
+ *  0 and flags_out says why.  err_out is the SAD above, or -1 where it was not reached (NO_HISTORY, NOT_FINITE); a point
+ *  with LOW_TEXTURE has passed through the end and carries its err and gates.  An accepted point is non-negative.
+ * The matrix maps FRAME px to CROP px and must be the one BOTH crops were cut with; lm_prev_dev is in frame px.
+ * Defaults (flm_flow_opts_init): levels 4, radius 7, max_iter 10, eps 0.03, min_eig 0.5, max_err 12, max_move 64.  On
+ * synthetic multi-scale texture three levels lost shifts of 14 px in a 256 px crop to far-away minima that a residual gate
+ * accepted, four levels did not.  max_err and max_move are GUESSES: nothing has measured them on real faces.  radius,
+ * max_iter, eps and min_eig are the customary values of pyramidal Lucas-Kanade trackers, not measured here either.
+ * Errors, all found before anything is launched.  FLM_ERR_ARG: a null pointer other than the optional ones; a struct_size
+ * smaller than this library's; a non-zero reserved or pad; unless eps > 0, min_eig >= 0, max_err >= 0, max_move > 0 (a NaN
+ * fails each); an output overlapping an input or another output.  FLM_ERR_SHAPE, the limit named in flm_last_error(),
+ * unless 1 <= k <= 65535, 1 <= c <= 1024, 1 <= levels <= 6, 1 <= radius <= 7, 1 <= max_iter <= 64, h and w are
+ * multiples of 2^(levels-1) with (h >> (levels-1)) >= 2 and (w >> (levels-1)) >= 2, and h, w <= 32768;
+ * flm_flow_pyramid: 1 <= n <= 131070 (two crops of 65535 faces), ch 1 or 3, and fewer than 2^31 tiles of 32x32. */
+#define FLM_FLOW_NO_HISTORY 1
+#define FLM_FLOW_LOW_TEXTURE 2
+#define FLM_FLOW_RESIDUAL 4
+#define FLM_FLOW_OUTSIDE 8
+#define FLM_FLOW_MOVED 16
+#define FLM_FLOW_NOT_FINITE 32
+size_t flm_flow_pyramid_bytes(int h, int w, int levels);
+int flm_flow_pyramid(flm_stream_t stream, const uint8_t* src_dev /*[N,H,W,ch]*/, int n, int h, int w, int ch /*1 | 3*/,
+                     int levels, uint8_t* pyr_dev /*[N, flm_flow_pyramid_bytes]*/);
+typedef struct flm_flow_opts {
+  uint32_t struct_size;  /* as flm_track_opts */
+  uint32_t reserved;     /* 0 */
+  int32_t levels;        /* pyramid levels, 1..6 */
+  int32_t radius;        /* window radius r, 1..7: a window of (2r+1)^2 pixels */
+  int32_t max_iter;      /* iterations per level, 1..64 */
+  int32_t pad;           /* 0 */
+  double eps;            /* a level stops when the update is shorter than eps px */
+  double min_eig;        /* the least eigenvalue per pixel, grey levels squared, at which a level is solved */
+  double max_err;        /* the largest mean absolute residual, grey levels, of an accepted point (a guess) */
+  double max_move;       /* the longest move, crop px, of an accepted point (a guess) */
+} flm_flow_opts;
+void flm_flow_opts_init(flm_flow_opts* opts);
+int flm_landmark_flow(flm_stream_t stream, const uint8_t* pyr_prev_dev, const uint8_t* pyr_cur_dev, int k, int h, int w,
+                      const double* lm_prev_dev /*[K,C,2] frame px*/, const double* w_prev_dev /*[K,C] or NULL*/,
+                      const float* m_dev /*[K,2,3] frame px -> crop px*/, int c, const flm_flow_opts* opts /*NULL = defaults*/,
+                      double* lm_out_dev /*[K,C,2] crop px*/, double* w_out_dev /*[K,C] or NULL*/,
+                      int32_t* err_out_dev /*[K,C] or NULL*/, int32_t* flags_out_dev /*[K,C]*/);
+
 #ifdef __cplusplus
 }
 #endif
