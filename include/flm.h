@@ -205,7 +205,12 @@ int flm_fcn_forward(flm_stream_t stream, int arch, const void* packed_dev, const
  * lets the struct grow without breaking callers).
  *   landmark_candidates   1 (default): FLM_OUT_LANDMARKS with top-n, n <= 32, on the 68-class FCN-8 kernels selects
  *                         from candidate keys emitted by the last transposed conv instead of materialising the
- *                         [N,H'*W',C] probabilities (bit-identical landmarks, gated fallback); 0: always materialise
+ *                         [N,H'*W',C] probabilities (bit-identical landmarks, gated fallback) -- under those
+ *                         conditions and the output map has fewer than 2^17 pixels: 352 x 352 is the largest square
+ *                         input (a candidate key holds the pixel index in 17 bits).  Larger maps, the default
+ *                         416 x 608 geometry (424 x 616 = 261,184 pixels) among them, always materialise the
+ *                         probabilities: their layout holds no cand_* buffers and is the same for both values.
+ *                         0: always materialise
  *                         and decode (the decode of utils/metrics.py:102-109 on model.predict's output, literally)
  *   candidate_sub_phases  phases per tile in that path's sampling launch (1..16; 0 = by n_points: 4 up to n = 8 (fp32: 2),
  *                         6 up to 15, 8 beyond)

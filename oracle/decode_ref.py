@@ -25,10 +25,12 @@ from __future__ import annotations
 import numpy as np
 
 
-def get_average_xy_ref(hmi: np.ndarray, n_points: int = 4, thresh=0):
+def get_average_xy_ref(hmi: np.ndarray, n_points: int = 4, thresh=0, order=None):
     """utils/metrics.py:46-80 with `height, width` taken from the map itself
     (the reference builds its index grids from those two arguments, :61-63, so
-    they must equal the map's dims for the call to be meaningful)."""
+    they must equal the map's dims for the call to be meaningful).  `order`: the
+    map's `argsort(axis=None, kind="stable")`, when the caller already has it (a
+    test that decodes one large map at several n_points sorts it once)."""
     height, width = hmi.shape
     if n_points < 1:
         hsum, n_points = np.sum(hmi), hmi.size                               # :60
@@ -38,7 +40,9 @@ def get_average_xy_ref(hmi: np.ndarray, n_points: int = 4, thresh=0):
             ind = np.arange(height, dtype=np.int64)[:, None].repeat(width, 1)  # :63
             i0 = np.sum(ind * hmi) / hsum                                    # :64
     else:
-        ind = hmi.argsort(axis=None, kind="stable")[-n_points:]              # :66 (+ tie rule)
+        if order is None:
+            order = hmi.argsort(axis=None, kind="stable")                    # :66 (+ tie rule)
+        ind = order[-n_points:]
         top0, top1 = np.unravel_index(ind, hmi.shape)                        # :67
         i0, i1, hsum = 0, 0, 0                                               # :69
         for a, b in zip(top0, top1):                                         # :70-74
@@ -54,23 +58,27 @@ def get_average_xy_ref(hmi: np.ndarray, n_points: int = 4, thresh=0):
     return [i1, i0]                                                          # :80
 
 
-def transfer_xy_coord_ref(hm: np.ndarray, n_points: int = 64, thresh=0.2, as_shipped: bool = False):
+def transfer_xy_coord_ref(hm: np.ndarray, n_points: int = 64, thresh=0.2, as_shipped: bool = False, orders=None):
     """utils/metrics.py:83-99.  `as_shipped=True` reproduces the positional-argument
     slip at :98 (`get_average_xy(hmi, n_points, thresh)` binds height/width), which
-    makes every call behave as n_points=4, thresh=0."""
+    makes every call behave as n_points=4, thresh=0.  `orders`: per channel, the
+    stable argsort of its map (see get_average_xy_ref)."""
     assert hm.ndim == 3
     est = []
     for i in range(hm.shape[-1]):
+        order = None if orders is None else orders[i]
         if as_shipped:
-            est.extend(get_average_xy_ref(hm[:, :, i], 4, 0))
+            est.extend(get_average_xy_ref(hm[:, :, i], 4, 0, order))
         else:
-            est.extend(get_average_xy_ref(hm[:, :, i], n_points, thresh))
+            est.extend(get_average_xy_ref(hm[:, :, i], n_points, thresh, order))
     return est
 
 
-def transfer_target_ref(y_pred: np.ndarray, thresh=0, n_points: int = 64, as_shipped: bool = False) -> np.ndarray:
-    """utils/metrics.py:102-109: [N,H,W,L] -> float64 [N, 2L] (x0,y0,x1,y1,...)."""
-    return np.array([transfer_xy_coord_ref(y_pred[i], n_points, thresh, as_shipped)
+def transfer_target_ref(y_pred: np.ndarray, thresh=0, n_points: int = 64, as_shipped: bool = False,
+                        orders=None) -> np.ndarray:
+    """utils/metrics.py:102-109: [N,H,W,L] -> float64 [N, 2L] (x0,y0,x1,y1,...).  `orders[i][c]`: the stable
+    argsort of map (i, c), when the caller already has them."""
+    return np.array([transfer_xy_coord_ref(y_pred[i], n_points, thresh, as_shipped, None if orders is None else orders[i])
                      for i in range(y_pred.shape[0])], dtype=np.float64)
 
 

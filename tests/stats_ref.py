@@ -18,7 +18,7 @@ def topn_record_ref(hmi, n_points, thresh, order=None):
         order = hmi.argsort(axis=None, kind="stable")
     ind = order[-n_points:]
     with np.errstate(all="ignore"):
-        x, y = decode_ref.get_average_xy_ref(hmi, n_points, thresh)
+        x, y = decode_ref.get_average_xy_ref(hmi, n_points, thresh, order)
         hsum = np.float32(0)
         for i in ind:
             hsum = np.float32(hsum + hmi.flat[i])

@@ -66,6 +66,30 @@ def test_live_reference_property(golden_dir):
         assert float(expected[k, 0]) == float(got[0]) and float(expected[k, 1]) == float(got[1]), (k, h, w, n, t)
 
 
+def test_a_given_stable_order_changes_nothing(gold):
+    """`order` / `orders` (the caller's stable argsort, so that one sort serves every n_points of a large map) against the
+    default path: the golden maps, and random maps with a plateau of tied maxima, a zero map and rejections."""
+    for name in gold["names"]:
+        hm = gold["hm_" + str(name)]
+        order = hm.argsort(axis=None, kind="stable")
+        for n in (1, 4, 25):
+            with np.errstate(all="ignore"):
+                a, b = decode_ref.get_average_xy_ref(hm, n, 0, order), decode_ref.get_average_xy_ref(hm, n, 0)
+            assert np.array_equal(np.array(a, np.float64), np.array(b, np.float64), equal_nan=True), (name, n)
+    rng = np.random.default_rng(33)
+    y = rng.random((2, 19, 23, 4), dtype=np.float32)
+    y[0, 3:5, 2:12, 1] = 1.5
+    y[1, :, :, 2] = 0
+    y[..., 3] *= np.float32(0.125)
+    orders = [[np.ascontiguousarray(y[f, :, :, c]).argsort(axis=None, kind="stable") for c in range(4)] for f in range(2)]
+    for n in (1, 4, 25, 128, 0):
+        for t in (0, 0.2):
+            with np.errstate(all="ignore"):
+                a, b = decode_ref.transfer_target_ref(y, t, n, orders=orders), decode_ref.transfer_target_ref(y, t, n)
+            assert a.shape == (2, 8) and np.array_equal(a, b), (n, t)
+    assert (b == -1).any() and (b != -1).any()
+
+
 def test_topn_gap_rel_is_the_relative_gap_at_the_nth_place():
     """decode_ref.topn_gap_rel (the checker's "determined pair" criterion, used by bench.py and the config tests): against a
     full sort, with ties and with n + 1 = the whole map."""
