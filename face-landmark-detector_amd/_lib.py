@@ -29,6 +29,7 @@ YUV_BT601_LIMITED, YUV_BT709_LIMITED = 0, 1          # flm_yuv_matrix
 TRACK_DEAD, TRACK_FEW_POINTS, TRACK_LOW_SCORE, TRACK_SCALE, TRACK_OUTSIDE = 1, 2, 4, 8, 16   # flm_track_status
 TRACK_DUPLICATE, TRACK_UNCONFIRMED = 32, 64          # flm_track_status, set by flm_track_associate alone
 FLOW_NO_HISTORY, FLOW_LOW_TEXTURE, FLOW_RESIDUAL, FLOW_OUTSIDE, FLOW_MOVED, FLOW_NOT_FINITE = 1, 2, 4, 8, 16, 32  # FLM_FLOW_*
+FLOW_FB = 64               # FLM_FLOW_FB: the forward-backward check of flm_landmark_flow_rows
 
 EXPORTS = [
     "flm_abi_version", "flm_last_error",
@@ -59,6 +60,7 @@ EXPORTS = [
     "flm_views_opts_init", "flm_track_views_update", "flm_track_exit_views",
     "flm_annotate_opts_init", "flm_bgr_to_yuv", "flm_frames_annotate",
     "flm_flow_pyramid_bytes", "flm_flow_pyramid", "flm_flow_opts_init", "flm_landmark_flow",
+    "flm_track_gather_flow", "flm_landmark_flow_rows", "flm_track_flow_history_put",
 ]
 
 
@@ -482,6 +484,12 @@ def _declare(lib):
     lib.flm_flow_opts_init.argtypes = [C.POINTER(FlowOpts)]
     lib.flm_landmark_flow.restype = i
     lib.flm_landmark_flow.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp, i, C.POINTER(FlowOpts), vp, vp, vp, vp]
+    lib.flm_track_gather_flow.restype = i
+    lib.flm_track_gather_flow.argtypes = [vp, vp, i, i, i, i, i, vp, vp, d] + [vp] * 17
+    lib.flm_landmark_flow_rows.restype = i
+    lib.flm_landmark_flow_rows.argtypes = [vp, vp, vp, i, i, i, vp, i, vp, vp, vp, i, C.POINTER(FlowOpts), d] + [vp] * 5
+    lib.flm_track_flow_history_put.restype = i
+    lib.flm_track_flow_history_put.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp]
 
 
 def load():

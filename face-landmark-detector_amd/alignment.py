@@ -1410,23 +1410,10 @@ def track_gather_streams_device(active, m_crop, boxes, slots_per_stream, frame_i
     return out
 
 
-def track_gather_live_device(m_crop, boxes, slots_per_stream, frame_hw, budget, stream_on=None, frame_index=None,
-                             dt=None, best_q=None, reset=None, age=None, cursor=None, out=None):
-    """The snapshot a step of the LIVE slots starts from, in one launch (flm_track_gather_live; include/flm.h states it):
-    `track_gather_streams_device` with the row map made on the device from the slots' boxes.
-
-    m_crop CUDA float32 [S*K,2,3] and boxes CUDA int32 [S*K,4]: the tracker's state, K = slots_per_stream; frame_hw:
-    (H, W) of the frames, what a box is clipped to; budget: a host integer, the number of rows.  stream_on: None (every
-    stream) or CUDA int32 [S], non-zero for the streams whose slots may be served; frame_index: None (ring slot 0) or
-    CUDA int32 [S]; best_q: None or CUDA float64 [S*K]; reset: None or CUDA int32 [S*K], read and then cleared for the
-    slots that are served.  age: None or CUDA float64 [S*K], the seconds every slot has waited unserved, read and
-    written; with it `dt` is required, a host number or a CUDA float64 [S] tensor -- the time step of every stream -- and
-    a served row's dt is its stream's plus its slot's age.  cursor: None or CUDA int32 [1], the slot the order starts
-    from, read and written: live slots beyond the budget are served first by the next call.  Returns a dict of compact
-    CUDA tensors over the `budget` rows, as `track_gather_streams_device` returns them -- slot int32 (-1: inert), m,
-    boxes, frame_index, and dt (with age), best_q, reset, each present when its input is -- plus counts int32 [4]:
-    (eligible slots, rows served, eligible slots left out, the next cursor).  out: None or a dict that names where to
-    write (any of those keys); only what it does not name is allocated."""
+def _track_gather_live(m_crop, boxes, slots_per_stream, frame_hw, budget, stream_on, frame_index, dt, best_q, reset, age,
+                       cursor, out, flow_frame=None, flow_ready=None):
+    """The one statement of `track_gather_live_device` and, with flow_frame and flow_ready, of `track_gather_flow_device`:
+    the flow form adds the two state tensors, the "prev_frame_index" column and two more counts."""
     import torch
     k, n_rows = int(slots_per_stream), int(budget)
     fh, fw = [int(v) for v in frame_hw]
@@ -1448,7 +1435,9 @@ def track_gather_live_device(m_crop, boxes, slots_per_stream, frame_hw, budget, 
         raise ValueError("with age, dt must be a finite number > 0 or a CUDA float64 [%d] tensor (got %r)" % (s, dt))
     else:
         dt_host = float(dt)
+    flow = flow_ready is not None
     for x, dtype, shape, what in ((stream_on, torch.int32, (s,), "stream_on"), (frame_index, torch.int32, (s,), "frame_index"),
+                                  (flow_frame, torch.int32, (n,), "flow_frame"), (flow_ready, torch.int32, (n,), "flow_ready"),
                                   (dt_dev, torch.float64, (s,), "dt"), (best_q, torch.float64, (n,), "best_q"),
                                   (reset, torch.int32, (n,), "reset"), (age, torch.float64, (n,), "age"),
                                   (cursor, torch.int32, (1,), "cursor")):
@@ -1459,7 +1448,8 @@ def track_gather_live_device(m_crop, boxes, slots_per_stream, frame_hw, budget, 
     spec = (("slot", torch.int32, (n_rows,), True), ("m", torch.float32, (n_rows, 2, 3), True),
             ("boxes", torch.int32, (n_rows, 4), True), ("frame_index", torch.int32, (n_rows,), True),
             ("dt", torch.float64, (n_rows,), age is not None), ("best_q", torch.float64, (n_rows,), best_q is not None),
-            ("reset", torch.int32, (n_rows,), reset is not None), ("counts", torch.int32, (4,), True))
+            ("reset", torch.int32, (n_rows,), reset is not None), ("counts", torch.int32, (6 if flow else 4,), True),
+            ("prev_frame_index", torch.int32, (n_rows,), flow))
     if set(out) - {name for name, *_ in spec}:
         raise ValueError("out names %r, which the gather does not write" % sorted(set(out) - {n_ for n_, *_ in spec}))
     for name, dtype, shape, wanted in spec:
@@ -1477,12 +1467,60 @@ def track_gather_live_device(m_crop, boxes, slots_per_stream, frame_hw, budget, 
     _check_overlap(out.get("reset"), reset, "out['reset'] and reset")
     _check_overlap(out.get("dt"), age, "out['dt'] and age")
     p = _ptr
+    if flow:
+        _lib.check(_lib.load().flm_track_gather_flow(
+            _lib.stream_ptr(), p(stream_on), s, k, fh, fw, n_rows, p(frame_index), p(dt_dev), dt_host, _lib.ptr(m_crop),
+            _lib.ptr(boxes), p(best_q), p(reset), p(age), p(cursor), _lib.ptr(flow_frame), _lib.ptr(flow_ready),
+            _lib.ptr(out["slot"]), _lib.ptr(out["m"]), _lib.ptr(out["boxes"]), _lib.ptr(out["frame_index"]),
+            _lib.ptr(out["prev_frame_index"]), p(out.get("dt")), p(out.get("best_q")), p(out.get("reset")),
+            _lib.ptr(out["counts"])), "flm_track_gather_flow")
+        return out
     _lib.check(_lib.load().flm_track_gather_live(
         _lib.stream_ptr(), p(stream_on), s, k, fh, fw, n_rows, p(frame_index), p(dt_dev), dt_host, _lib.ptr(m_crop),
         _lib.ptr(boxes), p(best_q), p(reset), p(age), p(cursor), _lib.ptr(out["slot"]), _lib.ptr(out["m"]),
         _lib.ptr(out["boxes"]), _lib.ptr(out["frame_index"]), p(out.get("dt")), p(out.get("best_q")), p(out.get("reset")),
         _lib.ptr(out["counts"])), "flm_track_gather_live")
     return out
+
+
+def track_gather_live_device(m_crop, boxes, slots_per_stream, frame_hw, budget, stream_on=None, frame_index=None,
+                             dt=None, best_q=None, reset=None, age=None, cursor=None, out=None):
+    """The snapshot a step of the LIVE slots starts from, in one launch (flm_track_gather_live; include/flm.h states it):
+    `track_gather_streams_device` with the row map made on the device from the slots' boxes.
+
+    m_crop CUDA float32 [S*K,2,3] and boxes CUDA int32 [S*K,4]: the tracker's state, K = slots_per_stream; frame_hw:
+    (H, W) of the frames, what a box is clipped to; budget: a host integer, the number of rows.  stream_on: None (every
+    stream) or CUDA int32 [S], non-zero for the streams whose slots may be served; frame_index: None (ring slot 0) or
+    CUDA int32 [S]; best_q: None or CUDA float64 [S*K]; reset: None or CUDA int32 [S*K], read and then cleared for the
+    slots that are served.  age: None or CUDA float64 [S*K], the seconds every slot has waited unserved, read and
+    written; with it `dt` is required, a host number or a CUDA float64 [S] tensor -- the time step of every stream -- and
+    a served row's dt is its stream's plus its slot's age.  cursor: None or CUDA int32 [1], the slot the order starts
+    from, read and written: live slots beyond the budget are served first by the next call.  Returns a dict of compact
+    CUDA tensors over the `budget` rows, as `track_gather_streams_device` returns them -- slot int32 (-1: inert), m,
+    boxes, frame_index, and dt (with age), best_q, reset, each present when its input is -- plus counts int32 [4]:
+    (eligible slots, rows served, eligible slots left out, the next cursor).  out: None or a dict that names where to
+    write (any of those keys); only what it does not name is allocated."""
+    return _track_gather_live(m_crop, boxes, slots_per_stream, frame_hw, budget, stream_on, frame_index, dt, best_q, reset,
+                              age, cursor, out)
+
+
+def track_gather_flow_device(m_crop, boxes, flow_frame, flow_ready, slots_per_stream, frame_hw, budget, stream_on=None,
+                             frame_index=None, dt=None, best_q=None, reset=None, age=None, cursor=None, out=None):
+    """The snapshot a FLOW tick of the live slots starts from, in one launch (flm_track_gather_flow; include/flm.h states
+    it): `track_gather_live_device` over the live slots that have a usable history.
+
+    flow_frame CUDA int32 [S*K], the ring slot every slot's history was found in, and flow_ready CUDA int32 [S*K], 1 where
+    the history is usable -- read, and then cleared for every slot of a stream that is on (`track_flow_history_device`
+    sets it again for the rows the tick serves alive).  The other arguments as `track_gather_live_device` takes them;
+    cursor is a cursor of the flow ticks' own.  Returns its dict plus prev_frame_index int32 [budget], the ring slot of
+    every row's previous frame, and with counts int32 [6]: (live slots, eligible slots: live with a history, rows served,
+    eligible slots left out, live slots without a history, the next cursor)."""
+    import torch
+    for x, what in ((flow_frame, "flow_frame"), (flow_ready, "flow_ready")):
+        if not isinstance(x, torch.Tensor):
+            raise ValueError("%s must be a contiguous CUDA int32 [S*K] tensor" % what)
+    return _track_gather_live(m_crop, boxes, slots_per_stream, frame_hw, budget, stream_on, frame_index, dt, best_q, reset,
+                              age, cursor, out, flow_frame=flow_frame, flow_ready=flow_ready)
 
 
 def track_step_rows_device(lm, m_crop_c, boxes_c, slot, grid_hw, in_hw, frame_hw, tmpl_crop, m_next, boxes_next, status,
@@ -2099,6 +2137,7 @@ def annotate_frames_device(frames, lm, frame_index_dev=None, opts=None, src=None
 # ---- landmark flow: the landmarks carried between two forwards (include/flm.h, "landmark flow") -------------------------
 FLOW_NO_HISTORY, FLOW_LOW_TEXTURE, FLOW_RESIDUAL = _lib.FLOW_NO_HISTORY, _lib.FLOW_LOW_TEXTURE, _lib.FLOW_RESIDUAL
 FLOW_OUTSIDE, FLOW_MOVED, FLOW_NOT_FINITE = _lib.FLOW_OUTSIDE, _lib.FLOW_MOVED, _lib.FLOW_NOT_FINITE
+FLOW_FB = _lib.FLOW_FB
 
 
 class LandmarkFlow:
@@ -2108,9 +2147,13 @@ class LandmarkFlow:
     eigenvalue per pixel (grey levels squared) at which a level is solved; max_err: the largest mean absolute residual
     (grey levels) and max_move: the longest move (crop px) of an accepted point -- both defaults are guesses that no
     measurement on real faces backs.  levels=4 rests on a synthetic prototype (three levels lost 14 px shifts in a 256 px
-    crop); radius, max_iter, eps and min_eig are the customary values of such trackers, unmeasured here."""
+    crop); radius, max_iter, eps and min_eig are the customary values of such trackers, unmeasured here.  max_fb: None (the
+    default: off) or the largest round trip, in crop px, of the forward-backward check of flm_landmark_flow_rows: an
+    accepted point is flowed back from where it arrived, and rejected with FLOW_FB unless it returns to within max_fb of
+    where it started.  It costs a second walk.  The value one would start from, 1.0 as in median-flow trackers, is a GUESS
+    too: like max_err and max_move it has not been measured on real faces."""
 
-    def __init__(self, levels=4, radius=7, max_iter=10, eps=0.03, min_eig=0.5, max_err=12.0, max_move=64.0):
+    def __init__(self, levels=4, radius=7, max_iter=10, eps=0.03, min_eig=0.5, max_err=12.0, max_move=64.0, max_fb=None):
         for name, v, lo, hi in (("levels", levels, 1, 6), ("radius", radius, 1, 7), ("max_iter", max_iter, 1, 64)):
             if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= hi:
                 raise ValueError("%s must be an integer in [%d, %d], got %r" % (name, lo, hi, v))
@@ -2125,6 +2168,11 @@ class LandmarkFlow:
             raise ValueError("max_move must be > 0, got %r" % max_move)
         self.levels, self.radius, self.max_iter = int(levels), int(radius), int(max_iter)
         self.eps, self.min_eig, self.max_err, self.max_move = eps, min_eig, max_err, max_move
+        if max_fb is not None:
+            max_fb = float(max_fb)
+            if not (max_fb > 0.0 and max_fb < float("inf")):
+                raise ValueError("max_fb must be None (no forward-backward check) or a finite number > 0, got %r" % max_fb)
+        self.max_fb = max_fb
 
     def check_crop(self, h, w):
         """ValueError unless crops of h x w have a pyramid of `levels` levels."""
@@ -2140,8 +2188,9 @@ class LandmarkFlow:
         return _lib.FlowOpts.make(self.levels, self.radius, self.max_iter, self.eps, self.min_eig, self.max_err, self.max_move)
 
     def __repr__(self):
-        return ("LandmarkFlow(levels=%r, radius=%r, max_iter=%r, eps=%r, min_eig=%r, max_err=%r, max_move=%r)"
-                % (self.levels, self.radius, self.max_iter, self.eps, self.min_eig, self.max_err, self.max_move))
+        return ("LandmarkFlow(levels=%r, radius=%r, max_iter=%r, eps=%r, min_eig=%r, max_err=%r, max_move=%r%s)"
+                % (self.levels, self.radius, self.max_iter, self.eps, self.min_eig, self.max_err, self.max_move,
+                   "" if self.max_fb is None else ", max_fb=%r" % self.max_fb))
 
 
 def _check_flow(flow):
@@ -2221,3 +2270,110 @@ def landmark_flow_device(pyr_prev, pyr_cur, lm_prev, m, hw, flow, weights=None, 
                                                  _lib.ptr(o_lm), _lib.ptr(o_w), _lib.ptr(o_err), _lib.ptr(o_flags)),
                    "flm_landmark_flow")
     return outs
+
+
+def landmark_flow_rows_device(pyr_prev, pyr_cur, slot, lm_prev, m, hw, flow, weights=None, out=None):
+    """`landmark_flow_device` on the rows of a compacted batch, with the forward-backward check of `flow.max_fb`, in one
+    launch (flm_landmark_flow_rows; include/flm.h states it).
+
+    pyr_prev, pyr_cur CUDA uint8 [N, bytes] and m CUDA float32 [N,2,3] are read at the row; slot: contiguous CUDA int32
+    [N], the global slot of every row (outside [0, n_slots): the row is inert); lm_prev contiguous CUDA float64
+    [n_slots,C,2] in frame px and weights None or CUDA float64 [n_slots,C] -- the history store itself -- are read at the
+    slot.  out: None or a tuple (lm, w, err, fb, flags) of tensors to write, any of them None.
+    Returns (lm float64 [N,C,2] crop px, w float64 [N,C], err int32 [N,C], fb float64 [N,C], flags int32 [N,C]) over
+    the rows, as `landmark_flow_device` returns them; fb is the squared round trip of the forward-backward check in crop
+    px squared, -1.0 where it did not run or did not finish, and flags may carry FLOW_FB.  An inert row is (-1,-1),
+    weight 0, err -1, fb -1.0, FLOW_NO_HISTORY.  With flow.max_fb None, slot = arange(N) and N = n_slots the first three
+    and the flags are the bits of `landmark_flow_device`."""
+    import torch
+    _check_flow(flow)
+    h, w = _sizes(hw, "hw")
+    flow.check_crop(h, w)
+    if not isinstance(lm_prev, torch.Tensor) or lm_prev.dim() != 3 or int(lm_prev.shape[2]) != 2:
+        raise ValueError("lm_prev must be a contiguous CUDA float64 [n_slots,C,2] tensor")
+    n_slots, c = int(lm_prev.shape[0]), int(lm_prev.shape[1])
+    _check_out(lm_prev, torch.float64, (n_slots, c, 2), "lm_prev")
+    if not isinstance(slot, torch.Tensor) or slot.dim() != 1:
+        raise ValueError("slot must be a contiguous CUDA int32 [N] tensor")
+    n = int(slot.shape[0])
+    _check_out(slot, torch.int32, (n,), "slot")
+    if not 1 <= n_slots <= 65535 or n > 65535 or c > 1024:
+        raise ValueError("at most 65535 slots and 65535 rows of 1024 landmarks, at least one slot (got %d slots, %d rows of "
+                         "%d)" % (n_slots, n, c))
+    nb = flow.pyramid_bytes(h, w)
+    _check_out(pyr_prev, torch.uint8, (n, nb), "pyr_prev")
+    _check_out(pyr_cur, torch.uint8, (n, nb), "pyr_cur")
+    _check_matrices(m, n)
+    if weights is not None:
+        _check_out(weights, torch.float64, (n_slots, c), "weights")
+    o_lm, o_w, o_err, o_fb, o_flags = (None,) * 5 if out is None else out
+    dev = lm_prev.device
+    o_lm = _out(o_lm, torch.float64, (n, c, 2), "out lm", dev)
+    o_w = _out(o_w, torch.float64, (n, c), "out w", dev)
+    o_err = _out(o_err, torch.int32, (n, c), "out err", dev)
+    o_fb = _out(o_fb, torch.float64, (n, c), "out fb", dev)
+    o_flags = _out(o_flags, torch.int32, (n, c), "out flags", dev)
+    outs = (o_lm, o_w, o_err, o_fb, o_flags)
+    for a, t in enumerate(outs):
+        for src in (pyr_prev, pyr_cur, slot, lm_prev, m, weights):
+            _check_overlap(t, src, "an output and an input")
+        for u in outs[a + 1:]:
+            _check_overlap(t, u, "two outputs")
+    if n and c:
+        fo = flow.struct()
+        _lib.check(_lib.load().flm_landmark_flow_rows(
+            _lib.stream_ptr(), _lib.ptr(pyr_prev), _lib.ptr(pyr_cur), n, h, w, _lib.ptr(slot), n_slots, _lib.ptr(lm_prev),
+            _ptr(weights), _lib.ptr(m), c, _lib.C.byref(fo), 0.0 if flow.max_fb is None else flow.max_fb, _lib.ptr(o_lm),
+            _lib.ptr(o_w), _lib.ptr(o_err), _lib.ptr(o_fb), _lib.ptr(o_flags)), "flm_landmark_flow_rows")
+    return outs
+
+
+def track_flow_history_device(slot, status_rows, frame_index_c, flow_frame, flow_ready, lm_rows=None, hist_lm=None,
+                              w_rows=None, hist_w=None):
+    """The rows of a tick moved to the history of their slots, in one launch (flm_track_flow_history_put; include/flm.h
+    states it and the history rule).
+
+    slot, status_rows, frame_index_c: contiguous CUDA int32 [N], the global slot, the status and the ring slot of every
+    row; flow_frame, flow_ready: CUDA int32 [n_slots], the tracker's own.  A row served with status 0 sets flow_frame to
+    its ring slot and flow_ready to 1 at its slot, any other row of a slot clears flow_ready there; an inert row writes
+    nothing and a slot no row names keeps every bit.  lm_rows CUDA float64 [N,C,2] with hist_lm [n_slots,C,2], and w_rows
+    [N,C] with hist_w [n_slots,C]: the raw landmarks (and weights) of the rows served with status 0 are copied to their
+    slots; without them only flow_frame and flow_ready are written.  Returns flow_ready."""
+    import torch
+    if not isinstance(slot, torch.Tensor) or slot.dim() != 1:
+        raise ValueError("slot must be a contiguous CUDA int32 [N] tensor")
+    n = int(slot.shape[0])
+    for x, what in ((slot, "slot"), (status_rows, "status_rows"), (frame_index_c, "frame_index_c")):
+        _check_out(x, torch.int32, (n,), what)
+    if not isinstance(flow_ready, torch.Tensor) or flow_ready.dim() != 1:
+        raise ValueError("flow_ready must be a contiguous CUDA int32 [n_slots] tensor")
+    n_slots = int(flow_ready.shape[0])
+    _check_out(flow_ready, torch.int32, (n_slots,), "flow_ready")
+    _check_out(flow_frame, torch.int32, (n_slots,), "flow_frame")
+    if not 1 <= n_slots <= 65535 or n > 65535:
+        raise ValueError("at most 65535 slots and 65535 rows, at least one slot (got %d slots, %d rows)" % (n_slots, n))
+    if (lm_rows is None) != (hist_lm is None) or (w_rows is None) != (hist_w is None) or (w_rows is not None and lm_rows is None):
+        raise ValueError("lm_rows goes with hist_lm, w_rows with hist_w, and weights with landmarks")
+    c = 1
+    if lm_rows is not None:
+        if not isinstance(lm_rows, torch.Tensor) or lm_rows.dim() != 3:
+            raise ValueError("lm_rows must be a contiguous CUDA float64 [N,C,2] tensor")
+        c = int(lm_rows.shape[1])
+        _check_out(lm_rows, torch.float64, (n, c, 2), "lm_rows")
+        _check_out(hist_lm, torch.float64, (n_slots, c, 2), "hist_lm")
+        _check_overlap(lm_rows, hist_lm, "lm_rows and hist_lm")
+        if w_rows is not None:
+            _check_out(w_rows, torch.float64, (n, c), "w_rows")
+            _check_out(hist_w, torch.float64, (n_slots, c), "hist_w")
+            _check_overlap(w_rows, hist_w, "w_rows and hist_w")
+    for t in (flow_frame, flow_ready):
+        for src in (slot, status_rows, frame_index_c):
+            _check_overlap(t, src, "an output and an input")
+    if n and 1 <= c <= 1024:
+        _lib.check(_lib.load().flm_track_flow_history_put(
+            _lib.stream_ptr(), _lib.ptr(slot), _lib.ptr(status_rows), _lib.ptr(frame_index_c), _ptr(lm_rows), _ptr(w_rows), n,
+            n_slots, c, _ptr(hist_lm), _ptr(hist_w), _lib.ptr(flow_frame), _lib.ptr(flow_ready)),
+            "flm_track_flow_history_put")
+    elif n:
+        raise ValueError("at most 1024 landmarks (got %d)" % c)
+    return flow_ready

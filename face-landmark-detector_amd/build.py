@@ -45,6 +45,7 @@ SOURCES = [
     "flm_pose.hip",
     "flm_annotate.hip",
     "flm_flow.hip",
+    "flm_flow_rows.hip",
     "flm_mobile.hip",
 ]
 # -ffp-contract=off: only the fma() calls written in the sources fuse, so the arithmetic of the

@@ -6,6 +6,7 @@
 
 #include "flm_annotate_dev.h"
 #include "flm_common.h"
+#include "flm_flow_rows_dev.h"
 
 namespace flm {
 
@@ -2249,17 +2250,8 @@ void flm_flow_opts_init(flm_flow_opts* opts) {
   opts->max_move = 64.0;
 }
 
-int flm_landmark_flow(flm_stream_t stream, const uint8_t* pyr_prev, const uint8_t* pyr_cur, int k, int h, int w,
-                      const double* lm_prev, const double* w_prev, const float* m, int c, const flm_flow_opts* opts,
-                      double* lm_out, double* w_out, int32_t* err_out, int32_t* flags_out) {
-  const char* who = "flm_landmark_flow";
-  if (!pyr_prev || !pyr_cur || !lm_prev || !m || !lm_out || !flags_out) {
-    set_error("%s: null argument", who);  // (w_prev, opts, w_out and err_out are optional)
-    return FLM_ERR_ARG;
-  }
-  flm_flow_opts defaults;
-  flm_flow_opts_init(&defaults);
-  if (!opts) opts = &defaults;
+// The options every flow call takes: the struct's header and the four numbers.
+static int check_flow_opts(const char* who, const flm_flow_opts* opts) {
   if (opts->struct_size < sizeof(flm_flow_opts)) {
     set_error("%s: flm_flow_opts struct_size %u is smaller than this library's %zu (initialise with "
               "flm_flow_opts_init)", who, opts->struct_size, sizeof(flm_flow_opts));
@@ -2285,14 +2277,11 @@ int flm_landmark_flow(flm_stream_t stream, const uint8_t* pyr_prev, const uint8_
     set_error("%s: max_move=%g, needs max_move > 0", who, opts->max_move);
     return FLM_ERR_ARG;
   }
-  if (k < 1 || k > 65535) {
-    set_error("%s: k=%d, needs 1 <= k <= 65535", who, k);
-    return FLM_ERR_SHAPE;
-  }
-  if (c < 1 || c > 1024) {
-    set_error("%s: c=%d, needs 1 <= c <= 1024", who, c);
-    return FLM_ERR_SHAPE;
-  }
+  return FLM_OK;
+}
+
+// The window of every flow call: radius and max_iter (after the call's own sizes, the order flm_landmark_flow had).
+static int check_flow_window(const char* who, const flm_flow_opts* opts) {
   if (opts->radius < 1 || opts->radius > 7) {
     set_error("%s: radius=%d, needs 1 <= radius <= 7", who, opts->radius);
     return FLM_ERR_SHAPE;
@@ -2301,6 +2290,30 @@ int flm_landmark_flow(flm_stream_t stream, const uint8_t* pyr_prev, const uint8_
     set_error("%s: max_iter=%d, needs 1 <= max_iter <= 64", who, opts->max_iter);
     return FLM_ERR_SHAPE;
   }
+  return FLM_OK;
+}
+
+int flm_landmark_flow(flm_stream_t stream, const uint8_t* pyr_prev, const uint8_t* pyr_cur, int k, int h, int w,
+                      const double* lm_prev, const double* w_prev, const float* m, int c, const flm_flow_opts* opts,
+                      double* lm_out, double* w_out, int32_t* err_out, int32_t* flags_out) {
+  const char* who = "flm_landmark_flow";
+  if (!pyr_prev || !pyr_cur || !lm_prev || !m || !lm_out || !flags_out) {
+    set_error("%s: null argument", who);  // (w_prev, opts, w_out and err_out are optional)
+    return FLM_ERR_ARG;
+  }
+  flm_flow_opts defaults;
+  flm_flow_opts_init(&defaults);
+  if (!opts) opts = &defaults;
+  if (int rc = check_flow_opts(who, opts)) return rc;
+  if (k < 1 || k > 65535) {
+    set_error("%s: k=%d, needs 1 <= k <= 65535", who, k);
+    return FLM_ERR_SHAPE;
+  }
+  if (c < 1 || c > 1024) {
+    set_error("%s: c=%d, needs 1 <= c <= 1024", who, c);
+    return FLM_ERR_SHAPE;
+  }
+  if (int rc = check_flow_window(who, opts)) return rc;
   if (int rc = check_flow_geometry(who, h, w, opts->levels)) return rc;
   const size_t pyr = (size_t)k * flm_flow_pyramid_bytes(h, w, opts->levels), kc = (size_t)k * c;
   const struct { const void* p; size_t bytes; const char* name; } in[] = {
@@ -2326,6 +2339,161 @@ int flm_landmark_flow(flm_stream_t stream, const uint8_t* pyr_prev, const uint8_
   }
   return launch_landmark_flow(static_cast<hipStream_t>(stream), pyr_prev, pyr_cur, k, h, w, lm_prev, w_prev, m, c, opts,
                               lm_out, w_out, err_out, flags_out);
+}
+
+// ---- the flow tick on rows (flm_flow_rows.hip) ------------------------------------------------------------------------
+
+// Every output against every input and every other output; null entries are skipped.
+static int check_no_overlap(const char* who, const NamedRange* in, size_t n_in, const NamedRange* out, size_t n_out) {
+  for (size_t a = 0; a < n_out; ++a) {
+    if (!out[a].p) continue;
+    for (size_t b = 0; b < n_in; ++b) {
+      if (in[b].p && ranges_overlap(out[a].p, out[a].bytes, in[b].p, in[b].bytes)) {
+        set_error("%s: %s overlaps %s", who, out[a].name, in[b].name);
+        return FLM_ERR_ARG;
+      }
+    }
+    for (size_t b = a + 1; b < n_out; ++b) {
+      if (out[b].p && ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) {
+        set_error("%s: %s overlaps %s", who, out[a].name, out[b].name);
+        return FLM_ERR_ARG;
+      }
+    }
+  }
+  return FLM_OK;
+}
+
+int flm_track_gather_flow(flm_stream_t stream, const int32_t* stream_on, int s, int k, int fh, int fw, int n,
+                          const int32_t* frame_idx_stream, const double* dt_stream, double dt, const float* m_crop,
+                          const int32_t* boxes, const double* best_q, int32_t* reset, double* age, int32_t* cursor,
+                          const int32_t* flow_frame, int32_t* flow_ready, int32_t* slot_c, float* m_c, int32_t* boxes_c,
+                          int32_t* frame_idx_c, int32_t* prev_frame_idx_c, double* dt_c, double* best_q_c, int32_t* reset_c,
+                          int32_t* counts) {
+  const char* who = "flm_track_gather_flow";
+  if (!m_crop || !boxes || !flow_frame || !flow_ready || !slot_c || !m_c || !boxes_c || !frame_idx_c || !prev_frame_idx_c ||
+      !counts) {
+    set_error("%s: null argument", who);  // (stream_on, frame_idx_stream, cursor and the three optional groups may be null)
+    return FLM_ERR_ARG;
+  }
+  if ((age == nullptr) != (dt_c == nullptr) || (best_q == nullptr) != (best_q_c == nullptr) ||
+      (reset == nullptr) != (reset_c == nullptr)) {
+    set_error("%s: age_dev/dt_c, best_q_dev/best_q_c and reset_dev/reset_c go together (both or neither)", who);
+    return FLM_ERR_ARG;
+  }
+  if (dt_stream && !age) {
+    set_error("%s: dt_stream_dev goes with age_dev", who);
+    return FLM_ERR_ARG;
+  }
+  if (age && !dt_stream && !(dt > 0.0 && std::isfinite(dt))) {
+    set_error("%s: dt=%g, needs a finite dt > 0 (seconds since the previous step) or dt_stream_dev", who, dt);
+    return FLM_ERR_ARG;
+  }
+  TrackFlowArgs g;
+  g.boxes = boxes; g.m_crop = m_crop; g.s = s; g.k = k; g.fh = fh; g.fw = fw; g.n = n;
+  g.stream_on = stream_on; g.frame_idx_stream = frame_idx_stream; g.dt_stream = dt_stream; g.dt = dt;
+  g.best_q = best_q; g.reset = reset; g.age = age; g.cursor = cursor; g.flow_frame = flow_frame; g.flow_ready = flow_ready;
+  g.slot_c = slot_c; g.m_c = m_c; g.boxes_c = boxes_c; g.frame_idx_c = frame_idx_c; g.prev_frame_idx_c = prev_frame_idx_c;
+  g.dt_c = dt_c; g.best_q_c = best_q_c; g.reset_c = reset_c; g.counts = counts;
+  if (n >= 1 && n <= 65535 && s >= 1 && k >= 1 && (long long)s * k <= 65535) {   // (the launcher names a size outside)
+    const size_t ns = (size_t)s * k, nr = (size_t)n;
+    const NamedRange in[] = {{stream_on, stream_on ? (size_t)s * 4 : 0, "stream_on_dev"},
+                             {frame_idx_stream, frame_idx_stream ? (size_t)s * 4 : 0, "frame_idx_stream_dev"},
+                             {dt_stream, dt_stream ? (size_t)s * 8 : 0, "dt_stream_dev"}, {m_crop, ns * 24, "m_crop_dev"},
+                             {boxes, ns * 16, "boxes_dev"}, {best_q, best_q ? ns * 8 : 0, "best_q_dev"},
+                             {flow_frame, ns * 4, "flow_frame_dev"}};
+    const NamedRange out[] = {{reset, ns * 4, "reset_dev"}, {age, ns * 8, "age_dev"}, {cursor, 4, "cursor_dev"},
+                              {flow_ready, ns * 4, "flow_ready_dev"}, {slot_c, nr * 4, "slot_c"}, {m_c, nr * 24, "m_c"},
+                              {boxes_c, nr * 16, "boxes_c"}, {frame_idx_c, nr * 4, "frame_idx_c"},
+                              {prev_frame_idx_c, nr * 4, "prev_frame_idx_c"}, {dt_c, nr * 8, "dt_c"},
+                              {best_q_c, nr * 8, "best_q_c"}, {reset_c, nr * 4, "reset_c"}, {counts, 24, "counts_dev"}};
+    if (int rc = check_no_overlap(who, in, sizeof(in) / sizeof(in[0]), out, sizeof(out) / sizeof(out[0]))) return rc;
+  }
+  return launch_track_gather_flow(static_cast<hipStream_t>(stream), g);
+}
+
+int flm_landmark_flow_rows(flm_stream_t stream, const uint8_t* pyr_prev, const uint8_t* pyr_cur, int n, int h, int w,
+                           const int32_t* slot, int n_slots, const double* lm_prev, const double* w_prev, const float* m,
+                           int c, const flm_flow_opts* opts, double max_fb, double* lm_out, double* w_out,
+                           int32_t* err_out, double* fb_out, int32_t* flags_out) {
+  const char* who = "flm_landmark_flow_rows";
+  if (!pyr_prev || !pyr_cur || !slot || !lm_prev || !m || !lm_out || !fb_out || !flags_out) {
+    set_error("%s: null argument", who);  // (w_prev, opts, w_out and err_out are optional)
+    return FLM_ERR_ARG;
+  }
+  flm_flow_opts defaults;
+  flm_flow_opts_init(&defaults);
+  if (!opts) opts = &defaults;
+  if (int rc = check_flow_opts(who, opts)) return rc;
+  if (!(max_fb >= 0.0 && std::isfinite(max_fb))) {
+    set_error("%s: max_fb=%g, needs a finite max_fb >= 0 (0: no forward-backward check)", who, max_fb);
+    return FLM_ERR_ARG;
+  }
+  if (n < 1 || n > 65535) {
+    set_error("%s: n=%d, needs 1 <= n <= 65535", who, n);
+    return FLM_ERR_SHAPE;
+  }
+  if (n_slots < 1 || n_slots > 65535) {
+    set_error("%s: n_slots=%d, needs 1 <= n_slots <= 65535", who, n_slots);
+    return FLM_ERR_SHAPE;
+  }
+  if (c < 1 || c > 1024) {
+    set_error("%s: c=%d, needs 1 <= c <= 1024", who, c);
+    return FLM_ERR_SHAPE;
+  }
+  if (int rc = check_flow_window(who, opts)) return rc;
+  if (int rc = check_flow_geometry(who, h, w, opts->levels)) return rc;
+  const size_t pyr = (size_t)n * flm_flow_pyramid_bytes(h, w, opts->levels), nc = (size_t)n * c, sc = (size_t)n_slots * c;
+  const NamedRange in[] = {{pyr_prev, pyr, "pyr_prev_dev"}, {pyr_cur, pyr, "pyr_cur_dev"}, {slot, (size_t)n * 4, "slot_dev"},
+                           {lm_prev, sc * 16, "lm_prev_dev"}, {w_prev, w_prev ? sc * 8 : 0, "w_prev_dev"},
+                           {m, (size_t)n * 24, "m_dev"}};
+  const NamedRange out[] = {{lm_out, nc * 16, "lm_out_dev"}, {w_out, nc * 8, "w_out_dev"}, {err_out, nc * 4, "err_out_dev"},
+                            {fb_out, nc * 8, "fb_out_dev"}, {flags_out, nc * 4, "flags_out_dev"}};
+  if (int rc = check_no_overlap(who, in, sizeof(in) / sizeof(in[0]), out, sizeof(out) / sizeof(out[0]))) return rc;
+  return launch_landmark_flow_rows(static_cast<hipStream_t>(stream), pyr_prev, pyr_cur, n, h, w, slot, n_slots, lm_prev,
+                                   w_prev, m, c, opts, max_fb, lm_out, w_out, err_out, fb_out, flags_out);
+}
+
+int flm_track_flow_history_put(flm_stream_t stream, const int32_t* slot, const int32_t* status_rows,
+                               const int32_t* frame_idx_c, const double* lm_rows, const double* w_rows, int n, int n_slots,
+                               int c, double* hist_lm, double* hist_w, int32_t* flow_frame, int32_t* flow_ready) {
+  const char* who = "flm_track_flow_history_put";
+  if (!slot || !status_rows || !frame_idx_c || !flow_frame || !flow_ready) {
+    set_error("%s: null argument", who);  // (lm_rows/hist_lm_dev and w_rows/hist_w_dev are optional)
+    return FLM_ERR_ARG;
+  }
+  if ((lm_rows == nullptr) != (hist_lm == nullptr) || (w_rows == nullptr) != (hist_w == nullptr)) {
+    set_error("%s: lm_rows_dev/hist_lm_dev and w_rows_dev/hist_w_dev go together (both or neither)", who);
+    return FLM_ERR_ARG;
+  }
+  if (w_rows && !lm_rows) {
+    set_error("%s: w_rows_dev goes with lm_rows_dev", who);
+    return FLM_ERR_ARG;
+  }
+  if (n < 1 || n > 65535) {
+    set_error("%s: n=%d, needs 1 <= n <= 65535", who, n);
+    return FLM_ERR_SHAPE;
+  }
+  if (n_slots < 1 || n_slots > 65535) {
+    set_error("%s: n_slots=%d, needs 1 <= n_slots <= 65535", who, n_slots);
+    return FLM_ERR_SHAPE;
+  }
+  if (c < 1 || c > 1024) {
+    set_error("%s: c=%d, needs 1 <= c <= 1024", who, c);
+    return FLM_ERR_SHAPE;
+  }
+  const size_t nc = (size_t)n * c, sc = (size_t)n_slots * c;
+  const NamedRange in[] = {{slot, (size_t)n * 4, "slot_dev"}, {status_rows, (size_t)n * 4, "status_rows_dev"},
+                           {frame_idx_c, (size_t)n * 4, "frame_idx_c"}, {lm_rows, nc * 16, "lm_rows_dev"},
+                           {w_rows, nc * 8, "w_rows_dev"}};
+  const NamedRange out[] = {{hist_lm, sc * 16, "hist_lm_dev"}, {hist_w, sc * 8, "hist_w_dev"},
+                            {flow_frame, (size_t)n_slots * 4, "flow_frame_dev"},
+                            {flow_ready, (size_t)n_slots * 4, "flow_ready_dev"}};
+  if (int rc = check_no_overlap(who, in, sizeof(in) / sizeof(in[0]), out, sizeof(out) / sizeof(out[0]))) return rc;
+  FlowPutArgs g;
+  g.slot = slot; g.status_rows = status_rows; g.frame_idx_c = frame_idx_c; g.lm_rows = lm_rows; g.w_rows = w_rows;
+  g.n = n; g.n_slots = n_slots; g.c = c; g.hist_lm = hist_lm; g.hist_w = hist_w; g.flow_frame = flow_frame;
+  g.flow_ready = flow_ready;
+  return launch_flow_history_put(static_cast<hipStream_t>(stream), g);
 }
 
 }  // extern "C"

@@ -467,6 +467,17 @@ int launch_landmark_flow(hipStream_t s, const uint8_t* pyr_prev, const uint8_t* 
                          const double* lm_prev, const double* w_prev, const float* m, int c, const flm_flow_opts* opts,
                          double* lm_out, double* w_out, int32_t* err_out, int32_t* flags_out);
 
+// the flow tick on rows (flm_flow_rows.hip; flm_flow_rows_dev.h holds the two argument structs); pointers, their pairing,
+// sizes, options and overlaps have been checked by the caller (flm_api.hip), except the sizes launch_track_gather_flow names
+struct TrackFlowArgs;
+struct FlowPutArgs;
+int launch_track_gather_flow(hipStream_t s, const TrackFlowArgs& g);
+int launch_landmark_flow_rows(hipStream_t s, const uint8_t* pyr_prev, const uint8_t* pyr_cur, int n, int h, int w,
+                              const int32_t* slot, int n_slots, const double* lm_prev, const double* w_prev, const float* m,
+                              int c, const flm_flow_opts* opts, double max_fb, double* lm_out, double* w_out,
+                              int32_t* err_out, double* fb_out, int32_t* flags_out);
+int launch_flow_history_put(hipStream_t s, const FlowPutArgs& g);
+
 // Bijective XCD-aware remap of a 1-D grid: blocks that the dispatcher deals to the same XCD
 // (b % 8) receive consecutive logical ids, so neighbours in logical order share an L2.
 __device__ __forceinline__ int xcd_remap(int b, int nblk) {

@@ -99,23 +99,20 @@ FLM_FLOW_HD int flow_gates(int32_t err, int n, double qx, double qy, double p0x,
   return f;
 }
 
-// The whole flow of one point, serially: what a host program calls.  The kernel runs the same functions with the window
-// spread over the lanes of a wave.  Returns the flags; *qx, *qy: the guess where it stopped (p0, or -1, where no level
-// ran); *err: the SAD or -1.
-FLM_FLOW_HD int flow_point(const uint8_t* prev, const uint8_t* cur, int h, int w, const float* m, double x, double y,
-                           const FlowParams& o, double* qx_out, double* qy_out, int32_t* err_out) {
-  double p0x, p0y;
-  int flags = flow_start(m, x, y, &p0x, &p0y);
-  *qx_out = p0x;
-  *qy_out = p0y;
-  *err_out = -1;
-  if (flags) return flags;
-  const int r = o.radius, side = 2 * r + 1, n = side * side;
+// The pyramid walk of one point, serially: flow_point calls it once, flow_rows_point (flm_flow_rows_dev.h) once per pass.
+// From p0 in crop px, the window of image `a` is looked for in image `b`, as "for l = levels-1 down to 0" of
+// flm_landmark_flow states it.  Returns LOW_TEXTURE, NOT_FINITE or both bits; *qx, *qy: the guess where the walk stopped;
+// *sad: the residual sum of the end, or -1 after NOT_FINITE.
+FLM_FLOW_HD int flow_walk(const uint8_t* a, const uint8_t* b, int h, int w, double p0x, double p0y, const FlowParams& o,
+                          double* qx_out, double* qy_out, int32_t* sad_out) {
+  const int r = o.radius;
+  int flags = 0;
   double qx = 0.0, qy = 0.0, px = 0.0, py = 0.0;
+  *sad_out = -1;
   for (int l = o.levels - 1; l >= 0; --l) {
     const int hl = h >> l, wl = w >> l;
-    const uint8_t* P = prev + flow_level_offset(h, w, l);
-    const uint8_t* Q = cur + flow_level_offset(h, w, l);
+    const uint8_t* P = a + flow_level_offset(h, w, l);
+    const uint8_t* Q = b + flow_level_offset(h, w, l);
     px = flow_level_coord(p0x, l);
     py = flow_level_coord(p0y, l);
     if (l == o.levels - 1) {
@@ -135,7 +132,7 @@ FLM_FLOW_HD int flow_point(const uint8_t* prev, const uint8_t* cur, int h, int w
       }
     const double A = (double)sa, B = (double)sb, C = (double)sc;
     const double det = A * C - B * B;
-    const double e = flow_min_eig(A, B, C, n);
+    const double e = flow_min_eig(A, B, C, (2 * r + 1) * (2 * r + 1));
     if (!(e >= o.min_eig)) {
       if (l == 0) flags |= kFlowLowTexture;
     } else {
@@ -171,14 +168,31 @@ FLM_FLOW_HD int flow_point(const uint8_t* prev, const uint8_t* cur, int h, int w
   int64_t sad = 0;
   for (int j = -r; j <= r; ++j)
     for (int i = -r; i <= r; ++i) {
-      const int64_t d = (int64_t)flow_sample(prev, h, w, px + (double)i, py + (double)j) -
-                        flow_sample(cur, h, w, qx + (double)i, qy + (double)j);
+      const int64_t d = (int64_t)flow_sample(a, h, w, px + (double)i, py + (double)j) -
+                        flow_sample(b, h, w, qx + (double)i, qy + (double)j);
       sad += d < 0 ? -d : d;
     }
-  *err_out = (int32_t)sad;
+  *sad_out = (int32_t)sad;
   *qx_out = qx;
   *qy_out = qy;
-  return flags | flow_gates((int32_t)sad, n, qx, qy, p0x, p0y, h, w, o.max_err, o.max_move);
+  return flags;
+}
+
+// The whole flow of one point, serially: what a host program calls.  The kernel runs the same functions with the window
+// spread over the lanes of a wave.  Returns the flags; *qx, *qy: the guess where it stopped (p0, or -1, where no level
+// ran); *err: the SAD or -1.
+FLM_FLOW_HD int flow_point(const uint8_t* prev, const uint8_t* cur, int h, int w, const float* m, double x, double y,
+                           const FlowParams& o, double* qx_out, double* qy_out, int32_t* err_out) {
+  double p0x, p0y;
+  int flags = flow_start(m, x, y, &p0x, &p0y);
+  *qx_out = p0x;
+  *qy_out = p0y;
+  *err_out = -1;
+  if (flags) return flags;
+  flags = flow_walk(prev, cur, h, w, p0x, p0y, o, qx_out, qy_out, err_out);
+  if (flags & kFlowNotFinite) return flags;
+  const int side = 2 * o.radius + 1;
+  return flags | flow_gates(*err_out, side * side, *qx_out, *qy_out, p0x, p0y, h, w, o.max_err, o.max_move);
 }
 
 }  // namespace flm

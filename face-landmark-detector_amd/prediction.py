@@ -780,7 +780,16 @@ class FaceTracker:
     then keeps, by device copies alone, the last step's raw landmarks in frame px (before the filter), with
     weights="score" their weights, and the ring slots that step cut from, and owns the two crop sets, their pyramids and
     `flow_flags` and `flow_err` int32 [capacity,C].  Without `flow` the tracker allocates nothing more and `step` returns
-    the same bits."""
+    the same bits.  `step_flow_live` is the flow tick of the slots that hold a face and have a usable history, for a loop
+    of `update` + `step_live` on the detector's ticks and `step_flow_live` on the others.  For it a flow tracker also owns
+    `flow_frame` int32 [capacity], the ring slot every slot's history was found in, and `flow_ready` int32 [capacity]: 1
+    exactly when the slot was served with status 0 by the last tick of its stream -- `step`, `step_flow`, `step_active`,
+    `step_live` or `step_flow_live` -- and neither `seed` nor `update` has written its crop matrix since (include/flm.h
+    states the rule; every one of those calls keeps it by device work alone: a clear for the streams it steps, then one
+    launch, alignment.track_flow_history_device, for the rows it served), plus `flow_cursor`, `flow_counts` int32 [6]
+    and `flow_fb` float64 [capacity,C], the squared round trip of the forward-backward check that
+    `alignment.LandmarkFlow(max_fb=...)` switches on (off by default; -1.0 where it did not run).  After a rows tick
+    `flow_flags`, `flow_err` and `flow_fb` are views of the first `budget` rows."""
 
     def __init__(self, model, frame_hw, capacity, out_size=(112, 112), template=None, crop_template=None, n_points=4,
                  thresh=0.0, weights=None, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"),
@@ -953,6 +962,19 @@ class FaceTracker:
             self._flow_crop_w = torch.zeros((n, c), dtype=torch.float64, device=dev)
             self.flow_err = torch.full((n, c), -1, dtype=torch.int32, device=dev)
             self.flow_flags = torch.zeros((n, c), dtype=torch.int32, device=dev)
+            self.flow_fb = torch.full((n, c), -1.0, dtype=torch.float64, device=dev)
+            self._flow_out = (self.flow_err, self.flow_flags, self.flow_fb)   # the buffers; the three names are views of them
+            # the per-slot history rule (include/flm.h, "the flow tick on rows"): flow_ready[g] == 1 exactly when slot g was
+            # served with status 0 by the last tick of its stream and nothing has written its crop matrix since
+            self.flow_frame = torch.zeros((n,), dtype=torch.int32, device=dev)    # the ring slot the history was found in
+            self.flow_ready = torch.zeros((n,), dtype=torch.int32, device=dev)
+            self.flow_cursor = torch.zeros((1,), dtype=torch.int32, device=dev)   # step_flow_live: where its order starts
+            self.flow_counts = torch.zeros((6,), dtype=torch.int32, device=dev)   # step_flow_live: what its gather counted
+            self._flow_iota = torch.arange(n, dtype=torch.int32, device=dev)      # slot[r] = r: the all-slots ticks
+            self._flow_m_before = torch.zeros((n, 2, 3), dtype=torch.float32, device=dev)   # update: m_crop before it
+            self._flow_raw_rows = (torch.full((n, c, 2), -1.0, dtype=torch.float64, device=dev)
+                                   if self.smooth is not None else None)          # the raw landmarks of a rows tick
+            self._flow_rows = None                                                # (raw landmarks, weights, status) of it
         if self.view_opts is not None:  # -1: the bin holds nothing
             b = self.view_opts.bins
             face = tuple(self.gallery.shape[1:])
@@ -1008,6 +1030,8 @@ class FaceTracker:
             self._best_reset.index_fill_(0, idx, 1)
         if self.exit_opts is not None:
             self._born.index_fill_(0, idx, 1)
+        if self.flow is not None:
+            self.flow_ready.index_fill_(0, idx, 0)
 
     @staticmethod
     def _host_boxes(boxes, what):
@@ -1075,10 +1099,12 @@ class FaceTracker:
         if not isinstance(det, torch.Tensor):
             det = torch.from_numpy(np.ascontiguousarray(det)).to(self.boxes.device)
         was_empty = self._was_empty()
+        self._flow_before_update()
         out = alignment.track_associate_device(det, self.m_crop, self.boxes, self.status, self.misses,
                                                (self.model.input_height, self.model.input_width), self.frame_hw,
                                                n_det=n, state=self.filter_state, assoc=self.associate)
         self._mark_births(was_empty, out[1])
+        self._flow_after_update()
         return out
 
     def _update_streams(self, detections, n):
@@ -1119,11 +1145,47 @@ class FaceTracker:
             both = torch.from_numpy(flat).to(self.boxes.device)
             det, n = both[:s * d * 4].view(s, d, 4), both[s * d * 4:]
         was_empty = self._was_empty()
+        self._flow_before_update()
         out = alignment.track_associate_streams_device(det, self.m_crop, self.boxes, self.status, self.misses, k,
                                                        (self.model.input_height, self.model.input_width), self.frame_hw,
                                                        n_det=n, state=self.filter_state, assoc=self.associate)
         self._mark_births(was_empty, out[1])
+        self._flow_after_update()
         return out
+
+    def _flow_before_update(self):
+        """For a flow tracker: a device copy of the crop matrices before the association, for `_flow_after_update`."""
+        if self.flow is not None:
+            self._flow_m_before.copy_(self.m_crop)
+
+    def _flow_after_update(self):
+        """The history rule under `update`: a slot whose crop matrix the association wrote -- a birth or a restart -- has no
+        usable history.  One comparison of bits on the device, no download."""
+        import torch
+        if self.flow is not None:
+            wrote = (self.m_crop.view(torch.int32) != self._flow_m_before.view(torch.int32)).flatten(1).any(dim=1)
+            self.flow_ready.masked_fill_(wrote, 0)
+
+    def _flow_clear(self, on=None):
+        """The history rule, first half of a tick of a flow tracker: flow_ready = 0 for every slot of the streams the tick
+        steps.  on: None (all streams) or a CUDA bool [streams] mask."""
+        if self.flow is None:
+            return
+        if on is None:
+            self.flow_ready.zero_()
+        else:
+            self.flow_ready.view(self.streams, self.slots_per_stream).masked_fill_(on.view(-1, 1), 0)
+
+    def _flow_put(self, slot, status, frame_index, lm=None, wd=None):
+        """The history rule, second half: the rows served with status 0 become the history of their slots
+        (alignment.track_flow_history_device, one launch).  lm None: the all-slots ticks, which have copied their
+        landmarks themselves."""
+        if self.flow is None:
+            return
+        rows = {} if lm is None else dict(lm_rows=lm, hist_lm=self._flow_lm)
+        if lm is not None and wd is not None and self._flow_w is not None:
+            rows.update(w_rows=wd.contiguous(), hist_w=self._flow_w)
+        alignment.track_flow_history_device(slot, status, frame_index, self.flow_frame, self.flow_ready, **rows)
 
     def _stream_frame_index(self, frame_index, nf, named):
         """A per-stream `frame_index`, parsed: None for a contiguous CUDA int32 [streams] tensor, which is used where it
@@ -1207,9 +1269,34 @@ class FaceTracker:
             alignment.warp_frames_device(ring, src["m"], ih, iw, samples=self.crop_samples, fmt=self._crop_format,
                                          frame_index_dev=slots, boxes_dev=src["boxes"], src=self.frame_format, out=half)
         alignment.flow_pyramid_device(self._flow_crops, self.flow.levels, out=self._flow_pyr)
-        lm, wd, _, _ = alignment.landmark_flow_device(
-            self._flow_pyr[:n], self._flow_pyr[n:], self._flow_lm, src["m"], (ih, iw), self.flow, weights=self._flow_w,
-            out=(self._flow_crop_lm, self._flow_crop_w, self.flow_err, self.flow_flags))
+        self.flow_err, self.flow_flags, self.flow_fb = self._flow_out
+        if self.flow.max_fb is None:    # (flow_fb holds -1.0 everywhere: nothing writes anything else without max_fb)
+            lm, wd, _, _ = alignment.landmark_flow_device(
+                self._flow_pyr[:n], self._flow_pyr[n:], self._flow_lm, src["m"], (ih, iw), self.flow, weights=self._flow_w,
+                out=(self._flow_crop_lm, self._flow_crop_w, self.flow_err, self.flow_flags))
+        else:               # the forward-backward check lives in the rows kernel: slot[r] = r
+            lm, wd = alignment.landmark_flow_rows_device(
+                self._flow_pyr[:n], self._flow_pyr[n:], self._flow_iota, self._flow_lm, src["m"], (ih, iw), self.flow,
+                weights=self._flow_w, out=(self._flow_crop_lm, self._flow_crop_w, self.flow_err, self.flow_fb,
+                                           self.flow_flags))[:2]
+        return lm, (None if self.weights is None else wd), (ih, iw)
+
+    def _flow_landmarks_rows(self, ring, src, workspace):
+        """The landmark source of `step_flow_live`: `_flow_landmarks` on the snapshot's rows -- the crop warp of every row's
+        PREVIOUS ring slot (src["prev_frame_index"]) and of its new one, both with the snapshot's matrices, into 2*budget
+        crops -> their pyramids in one launch -> alignment.landmark_flow_rows_device, which reads the history at the rows'
+        slots."""
+        n = int(src["slot"].shape[0])
+        ih, iw = self.model.input_height, self.model.input_width
+        crops, pyr = self._flow_crops[:2 * n], self._flow_pyr[:2 * n]
+        for half, slots in ((crops[:n], src["prev_frame_index"]), (crops[n:], src["frame_index"])):
+            alignment.warp_frames_device(ring, src["m"], ih, iw, samples=self.crop_samples, fmt=self._crop_format,
+                                         frame_index_dev=slots, boxes_dev=src["boxes"], src=self.frame_format, out=half)
+        alignment.flow_pyramid_device(crops, self.flow.levels, out=pyr)
+        self.flow_err, self.flow_flags, self.flow_fb = [t[:n] for t in self._flow_out]
+        lm, wd = alignment.landmark_flow_rows_device(
+            pyr[:n], pyr[n:], src["slot"], self._flow_lm, src["m"], (ih, iw), self.flow, weights=self._flow_w,
+            out=(self._flow_crop_lm[:n], self._flow_crop_w[:n], self.flow_err, self.flow_fb, self.flow_flags))[:2]
         return lm, (None if self.weights is None else wd), (ih, iw)
 
     def _sequence(self, ring, src, step, best_update, workspace, frame_id, quality_out=None, landmarks=None,
@@ -1231,6 +1318,8 @@ class FaceTracker:
                        frame_hw=self.frame_hw, tmpl_crop=self.crop_template, tmpl_align=self.template, weights=wd,
                        **self.limits, **filt)
         lm_frame, m_align, status = stepped[0], stepped[1], stepped[-1]
+        if self.flow is not None:   # what `_flow_put` of a rows tick moves to the slots
+            self._flow_rows = (lm_frame, wd, status)
         if history:   # (a tracker that smooths had the step write its raw points into _flow_lm)
             if self.smooth is None:
                 self._flow_lm.copy_(lm_frame)
@@ -1292,7 +1381,10 @@ class FaceTracker:
         crop as its grid -> the rest of `step`.  `flow_flags` and `flow_err` int32 [capacity,C], the tracker's own, say
         what the flow did with every landmark (0, or the alignment.FLOW_* bits that rejected it; a landmark the forward
         rejected at the key frame stays rejected until the next `step`).  No upload beyond `step`'s, no download, no
-        synchronisation.
+        synchronisation.  With `LandmarkFlow(max_fb=...)` the flow launch is alignment.landmark_flow_rows_device with
+        slot[r] = r: a landmark that does not come back to within `max_fb` crop px of where it started is rejected with
+        alignment.FLOW_FB, and `flow_fb` float64 [capacity,C] holds the squared round trips; with max_fb=None the call
+        makes the launches, and returns the bits, it did before that option existed.
 
         May follow only `step` or `step_flow`: `seed`, `update`, `step_active`, `step_live` and `retire(flush=True)` leave
         tracks without a history the device could use, and the next call must be `step`.  THE CALLER KEEPS THE PREVIOUS
@@ -1325,6 +1417,7 @@ class FaceTracker:
         if self.streams == 1:
             self.frame_slots.fill_(frame_index)
         raw = dict(lm_raw=self._flow_lm) if history and self.smooth is not None else {}
+        self._flow_clear()
 
         def best_update(faces, rec, lm, status, **kw):
             alignment.track_best_update_device(faces, rec, lm, self.best_q, self._best_q_spare, status=status,
@@ -1337,6 +1430,8 @@ class FaceTracker:
             best_update, lambda n, out: None, frame_id, quality_out=self._quality_rec if self.best_shot is not None else None,
             landmarks=landmarks, history=history)
         self._flow_ok = True
+        if history:
+            self._flow_put(self._flow_iota, self.status, self.frame_slots)
         self.boxes, self._boxes_spare = self._boxes_spare, self.boxes
         if self.best_shot is not None:
             self.best_q, self._best_q_spare = self._best_q_spare, self.best_q
@@ -1528,6 +1623,11 @@ class FaceTracker:
         snap = alignment.track_gather_streams_device(
             active, self.m_crop, self.boxes, k, frame_index=frame_index, dt=dt_dev, best_q=self.best_q if best else None,
             reset=self._best_reset if best else None)
+        raw = {}
+        if self.flow is not None:   # (an id outside [0, streams) matches no stream)
+            self._flow_clear((torch.arange(s, dtype=torch.int32, device=dev).view(s, 1) == active.view(1, a)).any(dim=1))
+            if self.smooth is not None:
+                raw = dict(lm_raw=self._flow_raw_rows[:n])
 
         def best_update(faces, rec, lm, status_rows, **kw):
             alignment.track_best_update_rows_device(faces, rec, lm, snap["slot"], snap["best_q"], self.best_q,
@@ -1536,8 +1636,9 @@ class FaceTracker:
         res = self._sequence(
             ring, snap,
             functools.partial(alignment.track_step_rows_device, slot=snap["slot"], m_next=self.m_crop, boxes_next=self.boxes,
-                              status=self.status, dt=dt_scalar if dt_dev is None else snap["dt"]),
+                              status=self.status, dt=dt_scalar if dt_dev is None else snap["dt"], **raw),
             best_update, self._active_workspace, frame_id)
+        self._flow_put_rows(snap, raw)
         self._retire_served()
         self._served(snap["slot"])
         return res + (snap["slot"],)
@@ -1569,6 +1670,46 @@ class FaceTracker:
         status int32 [budget], slots int32 [budget]); rows past the served ones are zero faces, the identity, TRACK_DEAD
         and slot -1.  A dead slot is no row, so its `status` keeps the reason it was lost where `step` would overwrite it
         with TRACK_DEAD; `lost()` still names it."""
+        return self._step_live(ring, frame_index, budget, active, dt, frame_id, False)
+
+    def step_flow_live(self, ring, frame_index, budget, active=None, dt=None, frame_id=None):
+        """`step_live` without the forward, for a tracker made with `flow`: one frame for the slots that hold a face AND
+        have a usable history, at most `budget` of them, their landmarks carried into the new frame by sparse optical flow
+        as in `step_flow`.  Arguments, checks and results as `step_live`.  The usual loop is `update` + `step_live` on
+        the ticks the detector runs -- the forward, for the live faces alone -- and `step_flow_live` on the others.
+
+        Which slots have a history the device knows (`flow_ready`; the rule is stated in include/flm.h): a slot has one
+        exactly when the last tick of its stream -- `step`, `step_flow`, `step_active`, `step_live` or this call -- served
+        it with status 0 and no `seed` or `update` has written its crop matrix since.  So the call may follow ANY call.  A
+        live slot without a history -- born since the last tick, left out by that tick's budget -- is simply no row: every
+        bit of its state is kept, `flow_counts[4]` says how many there were, and the next `step_live` serves it.  A live
+        slot with a history that THIS budget leaves out loses it (its landmarks would be older than the previous frame)
+        and waits for a forward tick too.  The forward is never run here.  THE CALLER KEEPS EVERY STREAM'S PREVIOUS
+        FRAME IN THE RING until this call has run.
+
+        Sequence: alignment.track_gather_flow_device (a cursor of its own, `flow_cursor`) -> the uint8 crop warp of the
+        snapshot's previous ring slots and of the new ones, both with the snapshot's matrices, into 2*budget crops ->
+        alignment.flow_pyramid_device over them in one launch -> alignment.landmark_flow_rows_device (with
+        `LandmarkFlow(max_fb=...)`, its forward-backward check) -> alignment.track_step_rows_device with the crop as its
+        grid -> what `step_live` runs after its landmarks -> alignment.track_flow_history_device.  `flow_counts` int32
+        [6], the tracker's own: (live slots, live slots with a history, rows served, slots with a history left out, live
+        slots without a history, the next cursor); `flow_flags`, `flow_err` int32 and `flow_fb` float64 [budget,C] say
+        what the flow did with every landmark of every row.  Counts as a step; afterwards `step_flow`'s own host rule asks
+        for a `step`, as after `step_live`.  No download, no synchronisation."""
+        if self.flow is None:
+            raise ValueError("step_flow_live needs a tracker made with flow")
+        return self._step_live(ring, frame_index, budget, active, dt, frame_id, True)
+
+    def _flow_put_rows(self, snap, raw):
+        """`_flow_put` after a rows tick: the raw landmarks are the step's lm_raw for a tracker that smooths, else the
+        landmarks it returned."""
+        if self.flow is not None:
+            lm_frame, wd, status = self._flow_rows
+            self._flow_put(snap["slot"], status, snap["frame_index"], raw.get("lm_raw", lm_frame), wd)
+            self._flow_rows = None
+
+    def _step_live(self, ring, frame_index, budget, active, dt, frame_id, flow):
+        """`step_live` (flow False: the forward) and `step_flow_live` (the flow source), stated once."""
         import functools
         import torch
         s, k = self.streams, self.slots_per_stream
@@ -1601,12 +1742,21 @@ class FaceTracker:
         up = self._upload(dt_host, fi_host, on_host)
         dt_dev, frame_index, active = [b if a is None else a for a, b in zip(up, (dt_dev, frame_index, active))]
         best, smooth = self.best_shot is not None, self.smooth is not None
-        self._waiting = self._waiting or budget < self.capacity
-        snap = alignment.track_gather_live_device(
-            self.m_crop, self.boxes, k, self.frame_hw, budget, stream_on=active, frame_index=frame_index,
-            dt=(dt_scalar if dt_dev is None else dt_dev) if smooth else None, best_q=self.best_q if best else None,
-            reset=self._best_reset if best else None, age=self.slot_age if smooth else None, cursor=self.live_cursor,
-            out=dict(counts=self.live_counts))
+        self._waiting = self._waiting or budget < self.capacity or flow   # (a flow tick leaves the history-less waiting)
+        common = dict(stream_on=active, frame_index=frame_index,
+                      dt=(dt_scalar if dt_dev is None else dt_dev) if smooth else None, best_q=self.best_q if best else None,
+                      reset=self._best_reset if best else None, age=self.slot_age if smooth else None)
+        if flow:            # (the gather clears flow_ready for the streams that are on)
+            snap = alignment.track_gather_flow_device(
+                self.m_crop, self.boxes, self.flow_frame, self.flow_ready, k, self.frame_hw, budget, cursor=self.flow_cursor,
+                out=dict(counts=self.flow_counts), **common)
+        else:
+            snap = alignment.track_gather_live_device(
+                self.m_crop, self.boxes, k, self.frame_hw, budget, cursor=self.live_cursor,
+                out=dict(counts=self.live_counts), **common)
+            if self.flow is not None:
+                self._flow_clear(None if active is None else active != 0)
+        raw = dict(lm_raw=self._flow_raw_rows[:budget]) if self.flow is not None and smooth else {}
 
         def best_update(faces, rec, lm, status_rows, **kw):
             alignment.track_best_update_rows_device(faces, rec, lm, snap["slot"], snap["best_q"], self.best_q,
@@ -1615,8 +1765,9 @@ class FaceTracker:
         res = self._sequence(
             ring, snap,
             functools.partial(alignment.track_step_rows_device, slot=snap["slot"], m_next=self.m_crop, boxes_next=self.boxes,
-                              status=self.status, dt=snap.get("dt")),
-            best_update, self._active_workspace, frame_id)
+                              status=self.status, dt=snap.get("dt"), **raw),
+            best_update, self._active_workspace, frame_id, landmarks=self._flow_landmarks_rows if flow else None)
+        self._flow_put_rows(snap, raw)
         self._retire_served()
         return res + (snap["slot"],)
 
@@ -1663,6 +1814,8 @@ class FaceTracker:
         if flush:
             self._flow_ok = False
         self._state()
+        if flush:
+            self._flow_clear()
         self._retire(frame_id, flush=bool(flush))
         return self.exit_head
 

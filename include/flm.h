@@ -1602,6 +1602,96 @@ int flm_landmark_flow(flm_stream_t stream, const uint8_t* pyr_prev_dev, const ui
                       double* lm_out_dev /*[K,C,2] crop px*/, double* w_out_dev /*[K,C] or NULL*/,
                       int32_t* err_out_dev /*[K,C] or NULL*/, int32_t* flags_out_dev /*[K,C]*/);
 
+/* ---- the flow tick on rows: flow for the slots that hold a face and have a history ------------------------------------
+ * THE HISTORY RULE.  Beside the history store -- hist_lm float64 [n_slots,C,2], the raw landmarks of a slot's last tick in
+ * frame px, and hist_w float64 [n_slots,C] -- a tracker keeps flow_frame int32 [n_slots], the ring slot those landmarks
+ * were found in, and flow_ready int32 [n_slots]:
+ *     flow_ready[g] == 1 exactly when slot g was served with status 0 by the last tick of its stream, key or flow, and
+ *     nothing has written its crop matrix since.
+ * Every tick clears flow_ready for all slots of the streams it steps and then sets it for the rows it served alive
+ * (flm_track_flow_history_put); whoever writes a crop matrix (a seed, a birth or a restart of the association) clears the
+ * slot's entry.  A live slot a budget left out thereby loses its history -- its landmarks are older than the previous
+ * frame --, a slot of a stream that was not stepped keeps it.
+ *
+ * flm_track_gather_flow: flm_track_gather_live with one more condition and two more columns, in ONE launch (the same
+ * one-workgroup prefix count: the row order is a function of the inputs alone).  The arguments are those of
+ * flm_track_gather_live plus flow_frame_dev int32 [S*K] (in), flow_ready_dev int32 [S*K] (in/out) and prev_frame_idx_c
+ * int32 [N] (out); counts_dev is int32 [6]; cursor_dev is a cursor of the flow ticks' own.  Its contract is rules 1-7
+ * there with these changes:
+ *  1. Slot g is LIVE when it is eligible by rule 1 there.  It is ELIGIBLE here when it is live and flow_ready_dev[g] != 0.
+ *     L = the number of live slots, E = the number of eligible ones.
+ *  2-4. unchanged, over the eligible slots of this rule 1.  A served row r of slot g additionally gets prev_frame_idx_c[r]
+ *     = flow_frame_dev[g]; an inert row gets 0.
+ *  5. Time: a live slot that is not served -- it has no history, or it is beyond the budget -- ages as "eligible, not
+ *     served" there; a served slot and a slot that is on and not live as there.
+ *  5a. After its ranking, flow_ready_dev[g] = 0 for EVERY slot of a stream that is on.  A slot of a stream that is off is
+ *     neither read nor written, flow_ready_dev and flow_frame_dev included.
+ *  6. counts = (L, E, served, E - served, L - E, cursor_out), cursor_out as there with E and N.
+ *  7. unchanged; flow_frame_dev is only read.
+ * Errors as flm_track_gather_live, with flow_frame_dev, flow_ready_dev and prev_frame_idx_c among the required pointers,
+ * and FLM_ERR_ARG where an output overlaps an input or another output. */
+int flm_track_gather_flow(flm_stream_t stream, const int32_t* stream_on_dev /*[S] or NULL*/, int s, int k /*slots PER STREAM*/,
+                          int fh, int fw, int n /*the budget*/, const int32_t* frame_idx_stream_dev /*[S] or NULL*/,
+                          const double* dt_stream_dev /*[S] or NULL*/, double dt, const float* m_crop_dev /*[S*K,2,3]*/,
+                          const int32_t* boxes_dev /*[S*K,4]*/, const double* best_q_dev /*[S*K] or NULL*/,
+                          int32_t* reset_dev /*[S*K] or NULL, in/out*/, double* age_dev /*[S*K] or NULL, in/out*/,
+                          int32_t* cursor_dev /*[1] or NULL, in/out*/, const int32_t* flow_frame_dev /*[S*K]*/,
+                          int32_t* flow_ready_dev /*[S*K], in/out*/, int32_t* slot_c /*[N]*/, float* m_c /*[N,2,3]*/,
+                          int32_t* boxes_c /*[N,4]*/, int32_t* frame_idx_c /*[N]*/, int32_t* prev_frame_idx_c /*[N]*/,
+                          double* dt_c /*[N] or NULL*/, double* best_q_c /*[N] or NULL*/, int32_t* reset_c /*[N] or NULL*/,
+                          int32_t* counts_dev /*[6]*/);
+
+/* flm_landmark_flow_rows: flm_landmark_flow on the rows of a compacted batch, with an optional forward-backward check, in
+ * ONE launch (a wave per landmark of a row; no workspace, no allocation, no atomics, no synchronisation).
+ * Where the arguments live: pyr_prev_dev, pyr_cur_dev [N, flm_flow_pyramid_bytes] and m_dev [N,2,3] are read at row r;
+ * lm_prev_dev [n_slots,C,2] and w_prev_dev [n_slots,C] -- the history store itself, never copied -- at slot g =
+ * slot_dev[r]; every output is compact, at row r.
+ * A row whose slot lies outside [0, n_slots) is INERT (flm_track_gather_* write -1): it reads nothing and writes (-1,-1),
+ * weight 0, err -1, fb -1.0 and FLM_FLOW_NO_HISTORY for each of its C points.
+ * Forward pass: "Per point" of flm_landmark_flow, word for word.  With slot_dev[r] = r, n = n_slots and max_fb = 0 every
+ * output equals flm_landmark_flow's bit for bit.
+ * Forward-backward check, max_fb > 0, only for a point whose forward flags are 0: the same per-point procedure -- "for l =
+ * levels-1 down to 0" with the same levels, radius, max_iter, eps and min_eig -- with the two images exchanged, from
+ * p0' = q (q is in crop px: no matrix is applied), gives q' and the backward pass's own LOW_TEXTURE / NOT_FINITE.
+ *     fb2 = (q'x - p0x)*(q'x - p0x) + (q'y - p0y)*(q'y - p0y)     (one IEEE operation per operator, in this order)
+ *     FB (64) if the backward pass ended with NOT_FINITE or LOW_TEXTURE, or if !(fb2 <= max_fb*max_fb)
+ *   The backward pass's residual, OUTSIDE and MOVED gates are not applied.  A point with FB is rejected as any other:
+ *   (-1,-1), weight 0; err_out keeps the forward pass's SAD.
+ * fb_out_dev float64 [N,C]: fb2, or -1.0 where the backward pass did not run (max_fb = 0, an inert row, forward flags) or
+ * did not finish (NOT_FINITE).
+ * max_fb = 0 switches the check off, and off is the default of everything built on this call: the value a user would
+ * start from, 1 px as in median-flow trackers, is a GUESS that -- like max_err and max_move -- nothing has measured on
+ * real faces.
+ * Errors, all found before anything is launched: those of flm_landmark_flow with k read as n; FLM_ERR_ARG for a null
+ * slot_dev or fb_out_dev and unless max_fb is finite and >= 0; FLM_ERR_SHAPE unless 1 <= n_slots <= 65535. */
+#define FLM_FLOW_FB 64
+int flm_landmark_flow_rows(flm_stream_t stream, const uint8_t* pyr_prev_dev, const uint8_t* pyr_cur_dev, int n, int h, int w,
+                           const int32_t* slot_dev /*[N]*/, int n_slots, const double* lm_prev_dev /*[n_slots,C,2] frame px*/,
+                           const double* w_prev_dev /*[n_slots,C] or NULL*/, const float* m_dev /*[N,2,3] frame px -> crop px*/,
+                           int c, const flm_flow_opts* opts /*NULL = defaults*/, double max_fb /*crop px; 0 = off*/,
+                           double* lm_out_dev /*[N,C,2] crop px*/, double* w_out_dev /*[N,C] or NULL*/,
+                           int32_t* err_out_dev /*[N,C] or NULL*/, double* fb_out_dev /*[N,C]*/,
+                           int32_t* flags_out_dev /*[N,C]*/);
+
+/* flm_track_flow_history_put: the rows of a tick moved to the history of their slots, in ONE launch (a wave per row).
+ * For a row r with g = slot_dev[r] in [0, n_slots):
+ *   status_rows_dev[r] == 0:  hist_lm_dev[g] = lm_rows_dev[r] (the RAW landmarks of the track step, frame px) and
+ *                             hist_w_dev[g] = w_rows_dev[r], each where given; flow_frame_dev[g] = frame_idx_c[r];
+ *                             flow_ready_dev[g] = 1
+ *   otherwise:                flow_ready_dev[g] = 0, nothing else
+ * A row whose slot lies outside [0, n_slots) writes nothing; a slot no row names keeps every bit.  The rows name
+ * distinct slots.  lm_rows_dev and hist_lm_dev may both be NULL -- the all-slots ticks, which copy their landmarks
+ * themselves, then write flow_frame and flow_ready alone, with slot_dev[r] = r --, and so may w_rows_dev and hist_w_dev;
+ * weights go with landmarks.
+ * Errors, all found before anything is launched: FLM_ERR_ARG for a null slot_dev, status_rows_dev, frame_idx_c,
+ * flow_frame_dev or flow_ready_dev, a rows tensor without its store or the reverse, weights without landmarks, or an output
+ * overlapping an input or another output; FLM_ERR_SHAPE unless 1 <= n <= 65535, 1 <= n_slots <= 65535, 1 <= c <= 1024. */
+int flm_track_flow_history_put(flm_stream_t stream, const int32_t* slot_dev /*[N]*/, const int32_t* status_rows_dev /*[N]*/,
+                               const int32_t* frame_idx_c /*[N]*/, const double* lm_rows_dev /*[N,C,2] or NULL*/,
+                               const double* w_rows_dev /*[N,C] or NULL*/, int n, int n_slots, int c,
+                               double* hist_lm_dev /*[n_slots,C,2] or NULL*/, double* hist_w_dev /*[n_slots,C] or NULL*/,
+                               int32_t* flow_frame_dev /*[n_slots]*/, int32_t* flow_ready_dev /*[n_slots]*/);
+
 #ifdef __cplusplus
 }
 #endif
