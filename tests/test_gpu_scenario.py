@@ -139,24 +139,12 @@ def run_a(mods, S, ring):
     return run(P, S, ring, follower={}, **options(A))
 
 
-def fit_bound(sim, pts):
-    """The float32 rounding of the four numbers of a similarity, on the points it is applied to: per coordinate
-    2^-24 (|a| |x| + |b| |y| + |t|), and 1e-9 for the float64 arithmetic on either side."""
-    a, b, tx, ty = [abs(v) for v in sim]
-    x, y = np.abs(pts[:, 0]), np.abs(pts[:, 1])
-    return 2.0 ** -24 * np.stack([a * x + b * y + tx, b * x + a * y + ty], 1) + 1e-9
+fit_bound = sc.fit_bound
 
 
 def pose_tol(S):
-    """On a `step` tick the landmarks are within Script.step_bound() of truth, and the host module holds the reference's
-    angles on the truth within 1e-12 of the script.  The pose is read off the affine fit of the six centred model points:
-    a change d of every image point changes its rows I, J by at most sqrt(6) d / sigma_min of the centred model matrix,
-    their directions by that over the scale |I| = |J|, and each angle by at most the sum over the two rows; doubled for
-    the arc functions away from the identity (|angles| < 40 degrees)."""
-    x = sc.HEAD_POINTS - sc.HEAD_POINTS.mean(0)
-    sigma = np.linalg.svd(x, compute_uv=False).min()
-    scale = 0.1003 * 0.97
-    return 1e-12 + 2.0 * 2.0 * math.sqrt(6.0) * S.step_bound() / (sigma * scale)
+    """scenario.pose_tol on the bound of a `step` tick."""
+    return sc.pose_tol(S.step_bound())
 
 
 def test_tracker_a_follows_the_truth_at_every_tick(mods, S, run_a):

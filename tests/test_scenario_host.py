@@ -9,7 +9,13 @@ references, each printing its value.  tests/test_gpu_scenario.py relies on every
   * the bare step of tests/track_ref.py, in closed loop over the truth, keeps every face until its scripted exit and drops
     it there with TRACK_OUTSIDE;
   * the flow reference, in closed loop on crops cut from the rendered frames, carries the landmarks with an error e_ref of
-    at most a quarter of the smallest motion per tick."""
+    at most a quarter of the smallest motion per tick.
+
+And tests/test_gpu_scenario_rows.py, the row forms, on these:
+  * scenario.rows_truth (RowTruthSource in numpy) under a full budget is scenario.slots_truth (TruthSource) exactly;
+  * under each of the three row schedules the references alone (scenario.RowsReference) keep every track except P2 at its
+    exit, and pass every checker of scenario.py the GPU module calls;
+  * five faults of a row tick, each injected into that loop, each fail the checker named beside it."""
 import math
 
 import numpy as np
@@ -318,3 +324,108 @@ def test_flow_reference_carries_the_landmarks_far_closer_than_they_move(S, flowe
     assert sc.FLOW_RADIUS == flow_ref.DEFAULTS["radius"]
     assert n >= 40 and points >= 40 * n and rejected == 0
     assert e_ref <= sc.E_REF <= motion / 4.0
+
+
+# ---- the row forms ------------------------------------------------------------------------------------------------------
+def test_row_truth_with_a_full_budget_is_the_truth_source_exactly(S, bare):
+    """Row r of a full budget serves slot slots[r] through that slot's matrix: the same numbers through the same
+    operations.  Rows in any order, inert rows among them."""
+    truth = S.truth()
+    n = 0
+    for rec in bare:
+        whole = sc.slots_truth(truth[rec["t"]], rec["m_crop"])
+        assert np.array_equal(whole.view(np.uint64), np.asarray(rec_lm(rec, truth)).view(np.uint64))
+        for slot in (np.arange(sc.CAP), np.array([5, -1, 0, 4, 1, -1, -1, 9])):
+            m = np.where((slot >= 0)[:, None, None] & (slot < sc.CAP)[:, None, None], rec["m_crop"][np.clip(slot, 0, sc.CAP - 1)],
+                         track_ref.IDENTITY)
+            rows = sc.rows_truth(truth[rec["t"]], slot, m)
+            for r, g in enumerate(slot):
+                want = whole[g] if 0 <= g < sc.CAP else np.full((sc.C, 2), -1.0)
+                assert rows[r].tobytes() == want.tobytes(), (rec["t"], r, g)
+                n += 1
+    assert n == 2 * sc.CAP * sc.TICKS
+
+
+def rec_lm(rec, truth):
+    """What closed_loop above sent its step at a tick of the bare run: the statement scenario.slots_truth restates."""
+    p = truth[rec["t"]]
+    m = rec["m_crop"].astype(np.float64)
+    cx = (m[:, 0, 0, None] * p[..., 0] + m[:, 0, 1, None] * p[..., 1]) + m[:, 0, 2, None]
+    cy = (m[:, 1, 0, None] * p[..., 0] + m[:, 1, 1, None] * p[..., 1]) + m[:, 1, 2, None]
+    empty = p[..., 0] < 0
+    return np.stack([np.where(empty, -1.0, cx * (sc.GRID / sc.IN)), np.where(empty, -1.0, cy * (sc.GRID / sc.IN))], -1)
+
+
+ROW_RUNS = [("full", False), ("budget", False), ("budget", True), ("clock", False)]
+_row_runs = {}
+
+
+def row_run(S, name, smooth=False, fault=None):
+    key = (name, smooth, fault)
+    if key not in _row_runs:
+        _row_runs[key] = sc.RowsReference(S, sc.SCHEDULES[name], smooth=smooth, fault=fault).run()
+    return _row_runs[key]
+
+
+def check_rows(S, name, smooth, records, ref):
+    """Every checker tests/test_gpu_scenario_rows.py calls on a run of the schedule `name`, in its order."""
+    worst = {}
+    for rec, rref in zip(records, ref):
+        sc.check_row_map(rec)
+        sc.check_rows_written(rec)
+        sc.check_untouched(rec)
+        sc.check_flow_ready(rec)
+        if rec["call"] != "flow" and not smooth:
+            sc.check_truth(S, rec, rref, worst)
+    if name == "budget":
+        worst["wait"], worst["rows"] = sc.check_rotation(records)
+    if smooth:
+        worst["moved"] = sc.check_smoothing(S, records)
+    return worst
+
+
+@pytest.mark.parametrize("name,smooth", ROW_RUNS)
+def test_references_alone_keep_every_track_under_each_row_schedule(S, name, smooth):
+    """The condition before any device run: the schedule loses no track but P2 at its exit (a crop that is two ticks old
+    costs P1, which moves left by 4 px a tick, a jaw point or two at the crop's left edge, never its track), and the
+    reference's own run passes the checkers the device's run is held to."""
+    records = row_run(S, name, smooth)
+    seen = sc.check_lifetimes(S, records)
+    worst = check_rows(S, name, smooth, records, records)
+    lost = sum(int((rec["lm"][r] < 0).all(1).sum()) for rec in records if rec["call"] != "flow" for r in sc.served(rec)
+               if not rec["status_rows"][r] & track_ref.DEAD)
+    lag = max(b - a for ticks in seen.values() for a, b in zip(ticks, ticks[1:]))
+    print("L-%s%s: served %s; oldest crop %d ticks; %d truth points outside a lagged crop; %s"
+          % (name, " smooth" if smooth else "", {k: len(v) for k, v in seen.items()}, lag, lost, worst))
+    assert lag == dict(full=1, budget=2, clock=2)[name]
+    if name == "budget":
+        assert worst["wait"] == 1 and set(worst["rows"]) == {sc.BUDGET}
+        p2 = [f for f in S.faces if f.name == "P2"][0]
+        assert seen["P2"][-1] == p2.last + 1            # the budget leaves P2 out at its scripted exit: dropped a tick later
+    if smooth:
+        assert worst["moved"] > 1000
+    if name == "full":                                  # the flow ticks are those of closed_loop(S, True), served as rows
+        assert all(rec["call"] == ("live" if S.is_key(rec["t"]) else "flow") for rec in records)
+
+
+FAULT_CASES = [("rows swapped", "budget", False, "check_row_map"), ("wrong slot", "budget", False, "check_rows_written"),
+               ("wrong slot", "clock", False, "check_rows_written"), ("no wait", "budget", True, "check_smoothing"),
+               ("reset unserved", "budget", False, "check_untouched"), ("history kept", "budget", False, "check_flow_ready")]
+
+
+@pytest.mark.parametrize("fault,name,smooth,checker", FAULT_CASES)
+def test_each_fault_of_a_row_tick_fails_its_checker(S, fault, name, smooth, checker):
+    with pytest.raises(AssertionError, match="^" + checker + ":") as e:
+        check_rows(S, name, smooth, row_run(S, name, smooth, fault), row_run(S, name, smooth))
+    print("%s under L-%s: %s" % (fault, name, e.value))
+
+
+def test_a_swapped_map_and_a_wrong_slot_miss_the_truth_as_well(S):
+    """Both faults are seen by check_truth too: a swapped map sends a row the truth of another face through its matrix,
+    and a row written to another slot leaves that slot a crop matrix fitted to another face's landmarks."""
+    good = row_run(S, "budget")
+    for fault in ("rows swapped", "wrong slot"):
+        bad = row_run(S, "budget", False, fault)
+        with pytest.raises(AssertionError, match="^check_truth:"):
+            for rec, ref in zip(bad, good):
+                sc.check_truth(S, rec, ref, {})
