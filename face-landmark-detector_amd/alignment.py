@@ -2223,6 +2223,53 @@ def flow_pyramid_device(crops, levels, out=None):
     return out
 
 
+def _landmark_flow_args(pyr_prev, pyr_cur, slot, lm_prev, m, hw, flow, weights, out):
+    """The checks of `landmark_flow_device` (slot None: row r reads slot r, K rows) and of `landmark_flow_rows_device`,
+    stated once.  Returns (h, w, rows, n_slots, c, the outputs: (lm, w, err, flags), with fb before flags for rows)."""
+    import torch
+    _check_flow(flow)
+    h, w = _sizes(hw, "hw")
+    flow.check_crop(h, w)
+    if not isinstance(lm_prev, torch.Tensor) or lm_prev.dim() != 3 or int(lm_prev.shape[2]) != 2:
+        raise ValueError("lm_prev must be a contiguous CUDA float64 [%s,C,2] tensor"
+                         % ("K" if slot is None else "n_slots"))
+    n_slots, c = int(lm_prev.shape[0]), int(lm_prev.shape[1])
+    _check_out(lm_prev, torch.float64, (n_slots, c, 2), "lm_prev")
+    if slot is None:
+        n = n_slots
+        if n > 65535 or c > 1024:
+            raise ValueError("at most 65535 faces of 1024 landmarks per call (got %d of %d)" % (n, c))
+    else:
+        if not isinstance(slot, torch.Tensor) or slot.dim() != 1:
+            raise ValueError("slot must be a contiguous CUDA int32 [N] tensor")
+        n = int(slot.shape[0])
+        _check_out(slot, torch.int32, (n,), "slot")
+        if not 1 <= n_slots <= 65535 or n > 65535 or c > 1024:
+            raise ValueError("at most 65535 slots and 65535 rows of 1024 landmarks, at least one slot (got %d slots, "
+                             "%d rows of %d)" % (n_slots, n, c))
+    nb = flow.pyramid_bytes(h, w)
+    _check_out(pyr_prev, torch.uint8, (n, nb), "pyr_prev")
+    _check_out(pyr_cur, torch.uint8, (n, nb), "pyr_cur")
+    _check_matrices(m, n)
+    if weights is not None:
+        _check_out(weights, torch.float64, (n_slots, c), "weights")
+    kinds = [(torch.float64, (n, c, 2), "lm"), (torch.float64, (n, c), "w"), (torch.int32, (n, c), "err"),
+             (torch.float64, (n, c), "fb"), (torch.int32, (n, c), "flags")]
+    if slot is None:
+        del kinds[3]
+    given = (None,) * len(kinds) if out is None else tuple(out)
+    if len(given) != len(kinds):
+        raise ValueError("out must be None or a tuple (%s) of tensors, any of them None"
+                         % ", ".join(k[2] for k in kinds))
+    outs = tuple(_out(t, dtype, shape, "out " + what, lm_prev.device) for t, (dtype, shape, what) in zip(given, kinds))
+    for a, t in enumerate(outs):
+        for src in (pyr_prev, pyr_cur, slot, lm_prev, m, weights):
+            _check_overlap(t, src, "an output and an input")
+        for u in outs[a + 1:]:
+            _check_overlap(t, u, "two outputs")
+    return h, w, n, n_slots, c, outs
+
+
 def landmark_flow_device(pyr_prev, pyr_cur, lm_prev, m, hw, flow, weights=None, out=None):
     """The landmarks of K faces carried from the previous crops to the current ones in one launch (flm_landmark_flow;
     include/flm.h states it line by line).
@@ -2235,40 +2282,12 @@ def landmark_flow_device(pyr_prev, pyr_cur, lm_prev, m, hw, flow, weights=None, 
     without weights), 0 for a rejected point; err int32 [K,C], the window's sum of absolute differences, -1 where it was
     not reached; flags int32 [K,C], 0 or the FLOW_* bits that rejected the point).  The landmarks are what
     `track_step_device` takes with grid_hw = in_hw = hw."""
-    import torch
-    _check_flow(flow)
-    h, w = _sizes(hw, "hw")
-    flow.check_crop(h, w)
-    if not isinstance(lm_prev, torch.Tensor) or lm_prev.dim() != 3 or int(lm_prev.shape[2]) != 2:
-        raise ValueError("lm_prev must be a contiguous CUDA float64 [K,C,2] tensor")
-    k, c = int(lm_prev.shape[0]), int(lm_prev.shape[1])
-    _check_out(lm_prev, torch.float64, (k, c, 2), "lm_prev")
-    if k > 65535 or c > 1024:
-        raise ValueError("at most 65535 faces of 1024 landmarks per call (got %d of %d)" % (k, c))
-    nb = flow.pyramid_bytes(h, w)
-    _check_out(pyr_prev, torch.uint8, (k, nb), "pyr_prev")
-    _check_out(pyr_cur, torch.uint8, (k, nb), "pyr_cur")
-    _check_matrices(m, k)
-    if weights is not None:
-        _check_out(weights, torch.float64, (k, c), "weights")
-    o_lm, o_w, o_err, o_flags = (None,) * 4 if out is None else out
-    dev = lm_prev.device
-    o_lm = _out(o_lm, torch.float64, (k, c, 2), "out lm", dev)
-    o_w = _out(o_w, torch.float64, (k, c), "out w", dev)
-    o_err = _out(o_err, torch.int32, (k, c), "out err", dev)
-    o_flags = _out(o_flags, torch.int32, (k, c), "out flags", dev)
-    outs = (o_lm, o_w, o_err, o_flags)
-    for a, t in enumerate(outs):
-        for src in (pyr_prev, pyr_cur, lm_prev, m, weights):
-            _check_overlap(t, src, "an output and an input")
-        for u in outs[a + 1:]:
-            _check_overlap(t, u, "two outputs")
+    h, w, k, _, c, outs = _landmark_flow_args(pyr_prev, pyr_cur, None, lm_prev, m, hw, flow, weights, out)
     if k and c:
         fo = flow.struct()
         _lib.check(_lib.load().flm_landmark_flow(_lib.stream_ptr(), _lib.ptr(pyr_prev), _lib.ptr(pyr_cur), k, h, w,
                                                  _lib.ptr(lm_prev), _ptr(weights), _lib.ptr(m), c, _lib.C.byref(fo),
-                                                 _lib.ptr(o_lm), _lib.ptr(o_w), _lib.ptr(o_err), _lib.ptr(o_flags)),
-                   "flm_landmark_flow")
+                                                 *[_lib.ptr(t) for t in outs]), "flm_landmark_flow")
     return outs
 
 
@@ -2285,46 +2304,13 @@ def landmark_flow_rows_device(pyr_prev, pyr_cur, slot, lm_prev, m, hw, flow, wei
     px squared, -1.0 where it did not run or did not finish, and flags may carry FLOW_FB.  An inert row is (-1,-1),
     weight 0, err -1, fb -1.0, FLOW_NO_HISTORY.  With flow.max_fb None, slot = arange(N) and N = n_slots the first three
     and the flags are the bits of `landmark_flow_device`."""
-    import torch
-    _check_flow(flow)
-    h, w = _sizes(hw, "hw")
-    flow.check_crop(h, w)
-    if not isinstance(lm_prev, torch.Tensor) or lm_prev.dim() != 3 or int(lm_prev.shape[2]) != 2:
-        raise ValueError("lm_prev must be a contiguous CUDA float64 [n_slots,C,2] tensor")
-    n_slots, c = int(lm_prev.shape[0]), int(lm_prev.shape[1])
-    _check_out(lm_prev, torch.float64, (n_slots, c, 2), "lm_prev")
-    if not isinstance(slot, torch.Tensor) or slot.dim() != 1:
-        raise ValueError("slot must be a contiguous CUDA int32 [N] tensor")
-    n = int(slot.shape[0])
-    _check_out(slot, torch.int32, (n,), "slot")
-    if not 1 <= n_slots <= 65535 or n > 65535 or c > 1024:
-        raise ValueError("at most 65535 slots and 65535 rows of 1024 landmarks, at least one slot (got %d slots, %d rows of "
-                         "%d)" % (n_slots, n, c))
-    nb = flow.pyramid_bytes(h, w)
-    _check_out(pyr_prev, torch.uint8, (n, nb), "pyr_prev")
-    _check_out(pyr_cur, torch.uint8, (n, nb), "pyr_cur")
-    _check_matrices(m, n)
-    if weights is not None:
-        _check_out(weights, torch.float64, (n_slots, c), "weights")
-    o_lm, o_w, o_err, o_fb, o_flags = (None,) * 5 if out is None else out
-    dev = lm_prev.device
-    o_lm = _out(o_lm, torch.float64, (n, c, 2), "out lm", dev)
-    o_w = _out(o_w, torch.float64, (n, c), "out w", dev)
-    o_err = _out(o_err, torch.int32, (n, c), "out err", dev)
-    o_fb = _out(o_fb, torch.float64, (n, c), "out fb", dev)
-    o_flags = _out(o_flags, torch.int32, (n, c), "out flags", dev)
-    outs = (o_lm, o_w, o_err, o_fb, o_flags)
-    for a, t in enumerate(outs):
-        for src in (pyr_prev, pyr_cur, slot, lm_prev, m, weights):
-            _check_overlap(t, src, "an output and an input")
-        for u in outs[a + 1:]:
-            _check_overlap(t, u, "two outputs")
+    h, w, n, n_slots, c, outs = _landmark_flow_args(pyr_prev, pyr_cur, slot, lm_prev, m, hw, flow, weights, out)
     if n and c:
         fo = flow.struct()
         _lib.check(_lib.load().flm_landmark_flow_rows(
             _lib.stream_ptr(), _lib.ptr(pyr_prev), _lib.ptr(pyr_cur), n, h, w, _lib.ptr(slot), n_slots, _lib.ptr(lm_prev),
-            _ptr(weights), _lib.ptr(m), c, _lib.C.byref(fo), 0.0 if flow.max_fb is None else flow.max_fb, _lib.ptr(o_lm),
-            _lib.ptr(o_w), _lib.ptr(o_err), _lib.ptr(o_fb), _lib.ptr(o_flags)), "flm_landmark_flow_rows")
+            _ptr(weights), _lib.ptr(m), c, _lib.C.byref(fo), 0.0 if flow.max_fb is None else flow.max_fb,
+            *[_lib.ptr(t) for t in outs]), "flm_landmark_flow_rows")
     return outs
 
 

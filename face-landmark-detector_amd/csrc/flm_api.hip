@@ -2185,7 +2185,7 @@ int flm_frames_annotate(flm_stream_t stream, uint8_t* frames, size_t frame_strid
   return launch_frames_annotate(static_cast<hipStream_t>(stream), g);
 }
 
-// ---- landmark flow (flm_flow.hip) -----------------------------------------------------------------------------------
+// ---- landmark flow (flm_flow.hip; the flow launch of both calls is in flm_flow_rows.hip) ----------------------------
 
 size_t flm_flow_pyramid_bytes(int h, int w, int levels) {
   if (h < 1 || w < 1 || levels < 1 || levels > 6) return 0;
@@ -2293,6 +2293,26 @@ static int check_flow_window(const char* who, const flm_flow_opts* opts) {
   return FLM_OK;
 }
 
+// Every output against every input and every other output; null entries are skipped.
+static int check_no_overlap(const char* who, const NamedRange* in, size_t n_in, const NamedRange* out, size_t n_out) {
+  for (size_t a = 0; a < n_out; ++a) {
+    if (!out[a].p) continue;
+    for (size_t b = 0; b < n_in; ++b) {
+      if (in[b].p && ranges_overlap(out[a].p, out[a].bytes, in[b].p, in[b].bytes)) {
+        set_error("%s: %s overlaps %s", who, out[a].name, in[b].name);
+        return FLM_ERR_ARG;
+      }
+    }
+    for (size_t b = a + 1; b < n_out; ++b) {
+      if (out[b].p && ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) {
+        set_error("%s: %s overlaps %s", who, out[a].name, out[b].name);
+        return FLM_ERR_ARG;
+      }
+    }
+  }
+  return FLM_OK;
+}
+
 int flm_landmark_flow(flm_stream_t stream, const uint8_t* pyr_prev, const uint8_t* pyr_cur, int k, int h, int w,
                       const double* lm_prev, const double* w_prev, const float* m, int c, const flm_flow_opts* opts,
                       double* lm_out, double* w_out, int32_t* err_out, int32_t* flags_out) {
@@ -2316,52 +2336,17 @@ int flm_landmark_flow(flm_stream_t stream, const uint8_t* pyr_prev, const uint8_
   if (int rc = check_flow_window(who, opts)) return rc;
   if (int rc = check_flow_geometry(who, h, w, opts->levels)) return rc;
   const size_t pyr = (size_t)k * flm_flow_pyramid_bytes(h, w, opts->levels), kc = (size_t)k * c;
-  const struct { const void* p; size_t bytes; const char* name; } in[] = {
-      {pyr_prev, pyr, "pyr_prev_dev"}, {pyr_cur, pyr, "pyr_cur_dev"}, {lm_prev, kc * 2 * sizeof(double), "lm_prev_dev"},
-      {w_prev, w_prev ? kc * sizeof(double) : 0, "w_prev_dev"}, {m, (size_t)k * 6 * sizeof(float), "m_dev"}};
-  const struct { const void* p; size_t bytes; const char* name; } out[] = {
-      {lm_out, kc * 2 * sizeof(double), "lm_out_dev"}, {w_out, w_out ? kc * sizeof(double) : 0, "w_out_dev"},
-      {err_out, err_out ? kc * sizeof(int32_t) : 0, "err_out_dev"}, {flags_out, kc * sizeof(int32_t), "flags_out_dev"}};
-  for (size_t a = 0; a < 4; ++a) {
-    if (!out[a].p) continue;
-    for (const auto& b : in) {
-      if (b.p && ranges_overlap(out[a].p, out[a].bytes, b.p, b.bytes)) {
-        set_error("%s: %s overlaps %s", who, out[a].name, b.name);
-        return FLM_ERR_ARG;
-      }
-    }
-    for (size_t b = a + 1; b < 4; ++b) {
-      if (out[b].p && ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) {
-        set_error("%s: %s overlaps %s", who, out[a].name, out[b].name);
-        return FLM_ERR_ARG;
-      }
-    }
-  }
-  return launch_landmark_flow(static_cast<hipStream_t>(stream), pyr_prev, pyr_cur, k, h, w, lm_prev, w_prev, m, c, opts,
-                              lm_out, w_out, err_out, flags_out);
+  const NamedRange in[] = {{pyr_prev, pyr, "pyr_prev_dev"}, {pyr_cur, pyr, "pyr_cur_dev"},
+                           {lm_prev, kc * 16, "lm_prev_dev"}, {w_prev, w_prev ? kc * 8 : 0, "w_prev_dev"},
+                           {m, (size_t)k * 24, "m_dev"}};
+  const NamedRange out[] = {{lm_out, kc * 16, "lm_out_dev"}, {w_out, kc * 8, "w_out_dev"},
+                            {err_out, kc * 4, "err_out_dev"}, {flags_out, kc * 4, "flags_out_dev"}};
+  if (int rc = check_no_overlap(who, in, sizeof(in) / sizeof(in[0]), out, sizeof(out) / sizeof(out[0]))) return rc;
+  return launch_landmark_flow_rows(static_cast<hipStream_t>(stream), pyr_prev, pyr_cur, k, h, w, nullptr, k, lm_prev,
+                                   w_prev, m, c, opts, 0.0, lm_out, w_out, err_out, nullptr, flags_out);
 }
 
 // ---- the flow tick on rows (flm_flow_rows.hip) ------------------------------------------------------------------------
-
-// Every output against every input and every other output; null entries are skipped.
-static int check_no_overlap(const char* who, const NamedRange* in, size_t n_in, const NamedRange* out, size_t n_out) {
-  for (size_t a = 0; a < n_out; ++a) {
-    if (!out[a].p) continue;
-    for (size_t b = 0; b < n_in; ++b) {
-      if (in[b].p && ranges_overlap(out[a].p, out[a].bytes, in[b].p, in[b].bytes)) {
-        set_error("%s: %s overlaps %s", who, out[a].name, in[b].name);
-        return FLM_ERR_ARG;
-      }
-    }
-    for (size_t b = a + 1; b < n_out; ++b) {
-      if (out[b].p && ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) {
-        set_error("%s: %s overlaps %s", who, out[a].name, out[b].name);
-        return FLM_ERR_ARG;
-      }
-    }
-  }
-  return FLM_OK;
-}
 
 int flm_track_gather_flow(flm_stream_t stream, const int32_t* stream_on, int s, int k, int fh, int fw, int n,
                           const int32_t* frame_idx_stream, const double* dt_stream, double dt, const float* m_crop,

@@ -463,12 +463,10 @@ int launch_frames_annotate(hipStream_t s, const AnnotateArgs& g);
 
 // landmark flow (flm_flow.hip); sizes, options, pointers and overlaps have been checked by the caller (flm_api.hip)
 int launch_flow_pyramid(hipStream_t s, const uint8_t* src, int n, int h, int w, int ch, int levels, uint8_t* pyr);
-int launch_landmark_flow(hipStream_t s, const uint8_t* pyr_prev, const uint8_t* pyr_cur, int k, int h, int w,
-                         const double* lm_prev, const double* w_prev, const float* m, int c, const flm_flow_opts* opts,
-                         double* lm_out, double* w_out, int32_t* err_out, int32_t* flags_out);
 
 // the flow tick on rows (flm_flow_rows.hip; flm_flow_rows_dev.h holds the two argument structs); pointers, their pairing,
-// sizes, options and overlaps have been checked by the caller (flm_api.hip), except the sizes launch_track_gather_flow names
+// sizes, options and overlaps have been checked by the caller (flm_api.hip), except the sizes launch_track_gather_flow
+// names.  launch_landmark_flow_rows is the landmark flow of both calls: flm_landmark_flow passes slot and fb_out null
 struct TrackFlowArgs;
 struct FlowPutArgs;
 int launch_track_gather_flow(hipStream_t s, const TrackFlowArgs& g);

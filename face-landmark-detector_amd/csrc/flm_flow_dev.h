@@ -1,5 +1,6 @@
 // The arithmetic of flm_flow_pyramid and flm_landmark_flow (include/flm.h states the contract), as __host__ __device__
-// functions: the kernels of flm_flow.hip and a host program (tests/native/flow_host.cpp) run this text.  Everything summed
+// functions: the pyramid kernel of flm_flow.hip, the flow kernel of flm_flow_rows.hip and a host program
+// (tests/native/flow_host.cpp) run this text.  Everything summed
 // over a window is an exact integer; every float64 line is one IEEE operation per written operator, in the written order;
 // the file must be compiled without contraction.
 #ifndef FLM_FLOW_DEV_H_
@@ -99,7 +100,8 @@ FLM_FLOW_HD int flow_gates(int32_t err, int n, double qx, double qy, double p0x,
   return f;
 }
 
-// The pyramid walk of one point, serially: flow_point calls it once, flow_rows_point (flm_flow_rows_dev.h) once per pass.
+// The pyramid walk of one point, serially: flow_point calls it once, flow_rows_point (flm_flow_rows_dev.h) once more
+// for its backward pass.
 // From p0 in crop px, the window of image `a` is looked for in image `b`, as "for l = levels-1 down to 0" of
 // flm_landmark_flow states it.  Returns LOW_TEXTURE, NOT_FINITE or both bits; *qx, *qy: the guess where the walk stopped;
 // *sad: the residual sum of the end, or -1 after NOT_FINITE.

@@ -1,5 +1,5 @@
-// flm_track_gather_flow, flm_landmark_flow_rows and flm_track_flow_history_put (include/flm.h states every rule;
-// flm_flow_rows_dev.h holds them; the comments here only say how the work is laid out).
+// flm_track_gather_flow, flm_landmark_flow_rows, flm_landmark_flow and flm_track_flow_history_put (include/flm.h states
+// every rule; flm_flow_rows_dev.h holds them; the comments here only say how the work is laid out).
 //
 // track_gather_flow_kernel: the layout of track_gather_live_kernel (flm_track.hip) -- ONE workgroup walks the slots in the
 // cyclic order of the contract a chunk of blockDim.x positions at a time; a ballot and mbcnt give the prefix count of
@@ -7,12 +7,15 @@
 // slot's exclusive prefix count IS its rank.  The live slots are counted by the same ballots.  A thread owns its slot:
 // it reads flow_ready before it clears it.  No atomics: the order is a function of the inputs.
 //
-// landmark_flow_rows_kernel: a workgroup of one wave per landmark of a row, as landmark_flow_kernel (flm_flow.hip).  The
-// pyramid walk is ONE device function, flow_walk_wave, with the layout of that kernel: the (2r+3)^2 patch of the first
-// image around p_l in LDS; T, Gx, Gy of the window in registers, pixel k on lane k % 64, slot k / 64; every sum an integer
-// butterfly over the wave, so all lanes hold it, all lanes run the float64 solve and every branch is wave-uniform.  The
-// forward pass calls it with (prev, cur) from p0, the backward pass with (cur, prev) from q: a loop of two trips around
-// one call site, so the kernel holds the walk once.  No atomics, no private segment; lane 0 writes with plain stores.
+// landmark_flow_rows_kernel, the one landmark-flow kernel body: a workgroup of one wave per landmark of a row, as
+// head_pose_kernel; instantiated once for flm_landmark_flow_rows and once for flm_landmark_flow (slot[r] = r, no check,
+// no fb, one pass).  The pyramid walk is ONE device function, flow_walk_wave: per level the lanes sample the (2r+3)^2
+// patch of the first image around p_l into LDS; T, Gx, Gy of the window then sit in registers, pixel k on lane k % 64,
+// slot k / 64 (four slots hold the 225 pixels of radius 7); every sum is an integer butterfly over the wave
+// (__shfl_xor), so all lanes hold it, all lanes run the float64 solve and every branch is wave-uniform.  The second
+// image is read through L2 at the moving guess.  The forward pass calls the walk with (prev, cur) from p0, the backward
+// pass with (cur, prev) from q: a loop of two trips around one call site, so the kernel holds the walk once.  No
+// atomics, no private segment; lane 0 writes with plain stores.
 //
 // flow_history_put_kernel: a workgroup of one wave per row; the lanes share the row's landmarks.
 #include "flm_common.h"
@@ -84,13 +87,13 @@ int launch_track_gather_flow(hipStream_t s, const TrackFlowArgs& g) {
   return FLM_OK;
 }
 
-// ---- flm_landmark_flow_rows ---------------------------------------------------------------------------------------------
+// ---- flm_landmark_flow_rows and flm_landmark_flow -----------------------------------------------------------------------
 struct FlowRowsArgs {
   const uint8_t* pyr_prev;
   const uint8_t* pyr_cur;
   size_t pyr_bytes;
   int h, w, c, n_slots;
-  const int32_t* slot;    // [N]
+  const int32_t* slot;    // [N], or null: slot[r] = r (n_slots = N)
   const double* lm_prev;  // [n_slots,C,2], read at the slot
   const double* w_prev;   // [n_slots,C] or null, read at the slot
   const float* m;         // [N,2,3]
@@ -99,7 +102,7 @@ struct FlowRowsArgs {
   double* lm_out;
   double* w_out;          // or null
   int32_t* err_out;       // or null
-  double* fb_out;
+  double* fb_out;         // or null
   int32_t* flags_out;
 };
 
@@ -209,30 +212,37 @@ __device__ __forceinline__ int flow_walk_wave(int32_t* patch, const uint8_t* a, 
   return flags;
 }
 
+template <bool kRows>
 __device__ __forceinline__ void flow_rows_write(const FlowRowsArgs& g, size_t e, int lane, const FlowRowsOut& o) {
   if (lane != 0) return;
   g.lm_out[2 * e] = o.x;
   g.lm_out[2 * e + 1] = o.y;
   if (g.w_out) g.w_out[e] = o.w;
   if (g.err_out) g.err_out[e] = o.err;
-  g.fb_out[e] = o.fb;
+  if (kRows) g.fb_out[e] = o.fb;
   g.flags_out[e] = o.flags;
 }
 
+// The (2r+3)^2 window patch in LDS, every workgroup its own; declared once for both instantiations of the kernel below
+// (declared in each, it makes the compiler schedule the rows form differently than it does alone).
+__shared__ int32_t patch[kFlowRowsPatch * kFlowRowsPatch];
+
+// kRows: flm_landmark_flow_rows (slot, fb, the backward pass where max_fb > 0); without it: flm_landmark_flow (row r
+// reads slot r, no fb, one pass).  One body, two instantiations.
+template <bool kRows>
 __global__ __launch_bounds__(64) void landmark_flow_rows_kernel(const FlowRowsArgs g) {
-  __shared__ int32_t patch[kFlowRowsPatch * kFlowRowsPatch];
   const int lane = threadIdx.x, f = blockIdx.x / g.c, i = blockIdx.x - f * g.c;
   const size_t e = blockIdx.x;
-  const int gs = g.slot[f];
-  if (flow_row_inert(gs, g.n_slots)) {   // reads nothing more (the same for every lane, as every branch below)
-    flow_rows_write(g, e, lane, flow_rows_inert_out());
+  const int gs = kRows ? g.slot[f] : f;
+  if (kRows && flow_row_inert(gs, g.n_slots)) {   // reads nothing more (the same for every lane, as every branch below)
+    flow_rows_write<kRows>(g, e, lane, flow_rows_inert_out());
     return;
   }
   const size_t he = (size_t)gs * g.c + i;
   double p0x, p0y;
   int flags = flow_start(g.m + 6 * (size_t)f, g.lm_prev[2 * he], g.lm_prev[2 * he + 1], &p0x, &p0y);
   if (flags) {
-    flow_rows_write(g, e, lane, flow_rows_out(flags, -1.0, -1.0, 0.0, -1, -1.0));
+    flow_rows_write<kRows>(g, e, lane, flow_rows_out(flags, -1.0, -1.0, 0.0, -1, -1.0));
     return;
   }
   const uint8_t* prev = g.pyr_prev + (size_t)f * g.pyr_bytes;
@@ -240,7 +250,7 @@ __global__ __launch_bounds__(64) void landmark_flow_rows_kernel(const FlowRowsAr
   const int side = 2 * g.o.radius + 1;
   double qx = 0.0, qy = 0.0, fb2 = -1.0;
   int32_t err = -1;
-  const int passes = g.max_fb > 0.0 ? 2 : 1;
+  const int passes = kRows && g.max_fb > 0.0 ? 2 : 1;
   for (int pass = 0; pass < passes; ++pass) {
     double wx, wy;
     int32_t sad;
@@ -259,21 +269,27 @@ __global__ __launch_bounds__(64) void landmark_flow_rows_kernel(const FlowRowsAr
     }
   }
   const double wp = (flags == 0 && g.w_prev) ? g.w_prev[he] : 1.0;
-  flow_rows_write(g, e, lane, flow_rows_out(flags, qx, qy, wp, err, fb2));
+  flow_rows_write<kRows>(g, e, lane, flow_rows_out(flags, qx, qy, wp, err, fb2));
 }
 
+// slot null (flm_landmark_flow): row r reads slot r, n_slots is n, and neither fb nor the backward pass is run.
 int launch_landmark_flow_rows(hipStream_t s, const uint8_t* pyr_prev, const uint8_t* pyr_cur, int n, int h, int w,
                               const int32_t* slot, int n_slots, const double* lm_prev, const double* w_prev, const float* m,
                               int c, const flm_flow_opts* opts, double max_fb, double* lm_out, double* w_out,
                               int32_t* err_out, double* fb_out, int32_t* flags_out) {
   FlowRowsArgs g;
   g.pyr_prev = pyr_prev; g.pyr_cur = pyr_cur; g.pyr_bytes = flow_level_offset(h, w, opts->levels);
-  g.h = h; g.w = w; g.c = c; g.n_slots = n_slots; g.slot = slot; g.lm_prev = lm_prev; g.w_prev = w_prev; g.m = m;
+  g.h = h; g.w = w; g.c = c; g.n_slots = slot ? n_slots : n; g.slot = slot;
+  g.lm_prev = lm_prev; g.w_prev = w_prev; g.m = m;
   g.o.levels = opts->levels; g.o.radius = opts->radius; g.o.max_iter = opts->max_iter;
   g.o.eps = opts->eps; g.o.min_eig = opts->min_eig; g.o.max_err = opts->max_err; g.o.max_move = opts->max_move;
   g.max_fb = max_fb;
   g.lm_out = lm_out; g.w_out = w_out; g.err_out = err_out; g.fb_out = fb_out; g.flags_out = flags_out;
-  landmark_flow_rows_kernel<<<(unsigned)n * (unsigned)c, 64, 0, s>>>(g);
+  const unsigned blocks = (unsigned)n * (unsigned)c;
+  if (slot)
+    landmark_flow_rows_kernel<true><<<blocks, 64, 0, s>>>(g);
+  else
+    landmark_flow_rows_kernel<false><<<blocks, 64, 0, s>>>(g);
   FLM_LAUNCH_CHECK("landmark_flow_rows_kernel");
   return FLM_OK;
 }

@@ -29,23 +29,17 @@ FLM_FLOW_HD int flow_fb_gate(int bflags, double bx, double by, double p0x, doubl
 }
 
 // The whole flow of one point of flm_landmark_flow_rows, serially: what a host program calls.  The kernel runs the same
-// functions with the window spread over the lanes of a wave.  Returns the flags; *qx, *qy: the forward guess where it
-// stopped; *err: the forward SAD or -1; *fb2 as flow_fb_gate, -1.0 where the backward pass did not run.
+// functions with the window spread over the lanes of a wave.  The forward pass is flow_point; returns the flags; *qx,
+// *qy: the forward guess where it stopped; *err: the forward SAD or -1; *fb2 as flow_fb_gate, -1.0 where the backward
+// pass did not run.
 FLM_FLOW_HD int flow_rows_point(const uint8_t* prev, const uint8_t* cur, int h, int w, const float* m, double x, double y,
                                 const FlowParams& o, double max_fb, double* qx, double* qy, int32_t* err, double* fb2) {
-  double p0x, p0y;
-  int flags = flow_start(m, x, y, &p0x, &p0y);
-  *qx = p0x;
-  *qy = p0y;
-  *err = -1;
   *fb2 = -1.0;
-  if (flags) return flags;
-  flags = flow_walk(prev, cur, h, w, p0x, p0y, o, qx, qy, err);
-  if (flags & kFlowNotFinite) return flags;
-  flags |= flow_gates(*err, (2 * o.radius + 1) * (2 * o.radius + 1), *qx, *qy, p0x, p0y, h, w, o.max_err, o.max_move);
+  const int flags = flow_point(prev, cur, h, w, m, x, y, o, qx, qy, err);
   if (flags || !(max_fb > 0.0)) return flags;
-  double bx, by;
+  double p0x, p0y, bx, by;
   int32_t berr;
+  flow_start(m, x, y, &p0x, &p0y);   // (0: the forward pass started from this p0)
   const int bflags = flow_walk(cur, prev, h, w, *qx, *qy, o, &bx, &by, &berr);
   return flow_fb_gate(bflags, bx, by, p0x, p0y, max_fb, fb2);
 }

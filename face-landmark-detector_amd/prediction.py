@@ -1258,44 +1258,24 @@ class FaceTracker:
         lm, wd = (res, None) if self.weights is None else (res[..., :2], res[..., 2])
         return lm, wd, (model.output_height, model.output_width)
 
-    def _flow_landmarks(self, ring, src, workspace):
-        """The landmark source of `step_flow`: the uint8 crop warp of the PREVIOUS ring slots and of the new ones, both
-        with the slots' current matrices -> the pyramids of all 2*capacity crops in one launch ->
-        alignment.landmark_flow_device from the last step's raw landmarks.  Returns (lm in crop px, wd: the carried
-        weights or None, the crop's size: the grid of these landmarks is the crop itself)."""
-        n = self.capacity
-        ih, iw = self.model.input_height, self.model.input_width
-        for half, slots in ((self._flow_crops[:n], self._flow_slots), (self._flow_crops[n:], src["frame_index"])):
-            alignment.warp_frames_device(ring, src["m"], ih, iw, samples=self.crop_samples, fmt=self._crop_format,
-                                         frame_index_dev=slots, boxes_dev=src["boxes"], src=self.frame_format, out=half)
-        alignment.flow_pyramid_device(self._flow_crops, self.flow.levels, out=self._flow_pyr)
-        self.flow_err, self.flow_flags, self.flow_fb = self._flow_out
-        if self.flow.max_fb is None:    # (flow_fb holds -1.0 everywhere: nothing writes anything else without max_fb)
-            lm, wd, _, _ = alignment.landmark_flow_device(
-                self._flow_pyr[:n], self._flow_pyr[n:], self._flow_lm, src["m"], (ih, iw), self.flow, weights=self._flow_w,
-                out=(self._flow_crop_lm, self._flow_crop_w, self.flow_err, self.flow_flags))
-        else:               # the forward-backward check lives in the rows kernel: slot[r] = r
-            lm, wd = alignment.landmark_flow_rows_device(
-                self._flow_pyr[:n], self._flow_pyr[n:], self._flow_iota, self._flow_lm, src["m"], (ih, iw), self.flow,
-                weights=self._flow_w, out=(self._flow_crop_lm, self._flow_crop_w, self.flow_err, self.flow_fb,
-                                           self.flow_flags))[:2]
-        return lm, (None if self.weights is None else wd), (ih, iw)
-
-    def _flow_landmarks_rows(self, ring, src, workspace):
-        """The landmark source of `step_flow_live`: `_flow_landmarks` on the snapshot's rows -- the crop warp of every row's
-        PREVIOUS ring slot (src["prev_frame_index"]) and of its new one, both with the snapshot's matrices, into 2*budget
-        crops -> their pyramids in one launch -> alignment.landmark_flow_rows_device, which reads the history at the rows'
-        slots."""
-        n = int(src["slot"].shape[0])
+    def _flow_landmarks(self, ring, src, workspace, slot, prev_frame_index):
+        """The landmark source of `step_flow` (slot = _flow_iota, prev_frame_index = _flow_slots: every slot) and of
+        `step_flow_live` (the snapshot's slot and prev_frame_index: its rows), bound by the caller: the uint8 crop warp
+        of every row's PREVIOUS ring slot and of its new one, both with src's matrices, into 2*rows crops -> their
+        pyramids in one launch -> alignment.landmark_flow_rows_device from the raw landmarks of the history, read at the
+        rows' slots (with `LandmarkFlow(max_fb=...)`, its forward-backward check; without it flow_fb is -1.0).  Returns
+        (lm in crop px, wd: the carried weights or None, the crop's size: the grid of these landmarks is the crop
+        itself)."""
+        n = int(slot.shape[0])
         ih, iw = self.model.input_height, self.model.input_width
         crops, pyr = self._flow_crops[:2 * n], self._flow_pyr[:2 * n]
-        for half, slots in ((crops[:n], src["prev_frame_index"]), (crops[n:], src["frame_index"])):
+        for half, slots in ((crops[:n], prev_frame_index), (crops[n:], src["frame_index"])):
             alignment.warp_frames_device(ring, src["m"], ih, iw, samples=self.crop_samples, fmt=self._crop_format,
                                          frame_index_dev=slots, boxes_dev=src["boxes"], src=self.frame_format, out=half)
         alignment.flow_pyramid_device(crops, self.flow.levels, out=pyr)
         self.flow_err, self.flow_flags, self.flow_fb = [t[:n] for t in self._flow_out]
         lm, wd = alignment.landmark_flow_rows_device(
-            pyr[:n], pyr[n:], src["slot"], self._flow_lm, src["m"], (ih, iw), self.flow, weights=self._flow_w,
+            pyr[:n], pyr[n:], slot, self._flow_lm, src["m"], (ih, iw), self.flow, weights=self._flow_w,
             out=(self._flow_crop_lm[:n], self._flow_crop_w[:n], self.flow_err, self.flow_fb, self.flow_flags))[:2]
         return lm, (None if self.weights is None else wd), (ih, iw)
 
@@ -1372,19 +1352,19 @@ class FaceTracker:
 
     def step_flow(self, ring, frame_index, dt=None, frame_id=None):
         """`step` without the forward, for a tracker made with `flow`: the landmarks of the last step are carried into the
-        new frame by sparse optical flow (alignment.landmark_flow_device) and take the forward's place; everything after
-        them -- the track step with its filter, both fits, the status and the next crop, then pose, the aligned warp,
-        mesh, best shot and views -- is the code of `step`.  Arguments and results as `step`.  Sequence: the uint8 crop
-        warp of the PREVIOUS ring slots (`frame_slots` of the last step) and of the new ones, both with the slots' current
-        matrices -> alignment.flow_pyramid_device over all of them -> alignment.landmark_flow_device from the last step's
-        RAW landmarks (before the filter) and, with weights="score", its weights -> alignment.track_step_device with the
-        crop as its grid -> the rest of `step`.  `flow_flags` and `flow_err` int32 [capacity,C], the tracker's own, say
-        what the flow did with every landmark (0, or the alignment.FLOW_* bits that rejected it; a landmark the forward
-        rejected at the key frame stays rejected until the next `step`).  No upload beyond `step`'s, no download, no
-        synchronisation.  With `LandmarkFlow(max_fb=...)` the flow launch is alignment.landmark_flow_rows_device with
-        slot[r] = r: a landmark that does not come back to within `max_fb` crop px of where it started is rejected with
-        alignment.FLOW_FB, and `flow_fb` float64 [capacity,C] holds the squared round trips; with max_fb=None the call
-        makes the launches, and returns the bits, it did before that option existed.
+        new frame by sparse optical flow and take the forward's place; everything after them -- the track step with its
+        filter, both fits, the status and the next crop, then pose, the aligned warp, mesh, best shot and views -- is
+        the code of `step`.  Arguments and results as `step`.  Sequence: the uint8 crop warp of the PREVIOUS ring slots
+        (`frame_slots` of the last step) and of the new ones, both with the slots' current matrices ->
+        alignment.flow_pyramid_device over all of them -> alignment.landmark_flow_rows_device with slot[r] = r from the
+        last step's RAW landmarks (before the filter) and, with weights="score", its weights ->
+        alignment.track_step_device with the crop as its grid -> the rest of `step`.  `flow_flags` and `flow_err` int32
+        [capacity,C], views of the tracker's own buffers over all their rows, say what the flow did with every landmark
+        (0, or the alignment.FLOW_* bits that rejected it; a landmark the forward rejected at the key frame stays
+        rejected until the next `step`).  No upload beyond `step`'s, no download, no synchronisation.  With
+        `LandmarkFlow(max_fb=...)` a landmark that does not come back to within `max_fb` crop px of where it started is
+        rejected with alignment.FLOW_FB, and `flow_fb` float64 [capacity,C] (a view as well) holds the squared round
+        trips; with max_fb=None the call returns the bits of alignment.landmark_flow_device and `flow_fb` is -1.0.
 
         May follow only `step` or `step_flow`: `seed`, `update`, `step_active`, `step_live` and `retire(flush=True)` leave
         tracks without a history the device could use, and the next call must be `step`.  THE CALLER KEEPS THE PREVIOUS
@@ -1395,7 +1375,8 @@ class FaceTracker:
         if not self._flow_ok:
             raise ValueError("step_flow may follow only step or step_flow: after seed, update, step_active, step_live or "
                              "retire(flush=True) the next call must be step")
-        return self._step_all(ring, frame_index, dt, frame_id, self._flow_landmarks)
+        return self._step_all(ring, frame_index, dt, frame_id, lambda ring, src, workspace: self._flow_landmarks(
+            ring, src, workspace, self._flow_iota, self._flow_slots))   # (the state exists once _step_all has begun)
 
     def _step_all(self, ring, frame_index, dt, frame_id, landmarks):
         """`step` (landmarks None: the forward) and `step_flow` (the flow source), stated once."""
@@ -1766,7 +1747,8 @@ class FaceTracker:
             ring, snap,
             functools.partial(alignment.track_step_rows_device, slot=snap["slot"], m_next=self.m_crop, boxes_next=self.boxes,
                               status=self.status, dt=snap.get("dt"), **raw),
-            best_update, self._active_workspace, frame_id, landmarks=self._flow_landmarks_rows if flow else None)
+            best_update, self._active_workspace, frame_id, landmarks=(lambda ring, src, workspace: self._flow_landmarks(
+                ring, src, workspace, snap["slot"], snap["prev_frame_index"])) if flow else None)
         self._flow_put_rows(snap, raw)
         self._retire_served()
         return res + (snap["slot"],)

@@ -1,5 +1,5 @@
 """The arithmetic of flm_flow_pyramid and flm_landmark_flow on the host (no GPU): tests/native/flow_host.cpp runs
-csrc/flm_flow_dev.h -- the header the kernels of csrc/flm_flow.hip are built from -- over the cases of tests/flow_cases.py
+csrc/flm_flow_dev.h -- the header the flow kernels are built from -- over the cases of tests/flow_cases.py
 and must equal tests/flow_ref.py bit for bit: both pyramids byte for byte, every landmark as its uint64 bits, every err
 and every flag.  The program is built without contraction, as the library is, and with the host's address and
 undefined-behaviour sanitizers."""

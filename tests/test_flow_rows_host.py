@@ -124,8 +124,9 @@ def test_history_put_argument_checks_answer_without_a_gpu():
 
 def test_rows_source_compiles_without_scratch(tmp_path):
     """The method of tests/test_flow_host.py for csrc/flm_flow_rows.hip: built by build.py without contraction, compiles
-    for gfx950 with the build's flags, and none of the three kernels has a private segment; the fused two-pass flow kernel
-    stays within 128 VGPRs, four waves per SIMD, as the one-pass kernel."""
+    for gfx950 with the build's flags, and none of the kernels has a private segment; the fused two-pass flow kernel,
+    the one landmark-flow kernel body (instantiated for flm_landmark_flow_rows and for flm_landmark_flow), stays within
+    128 VGPRs, four waves per SIMD, in both instantiations."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("_flm_build", os.path.join(ROOT, "face-landmark-detector_amd", "build.py"))
     bld = importlib.util.module_from_spec(spec)
@@ -144,6 +145,10 @@ def test_rows_source_compiles_without_scratch(tmp_path):
     print(kernels)
     for name in ("track_gather_flow_kernel", "landmark_flow_rows_kernel", "flow_history_put_kernel"):
         assert any(name in k for k in kernels), name
+    flow_kernels = [k for k in kernels if "landmark_flow" in k]      # one body: its rows and its all-slots instantiation
+    assert len(flow_kernels) == 2 and all("landmark_flow_rows_kernelI" in k for k in flow_kernels), kernels
+    src = open(os.path.join(CSRC, "flm_flow_rows.hip")).read()
+    assert len(re.findall(r"__global__[^;{]*landmark_flow", src)) == 1
     bad = {k: v for k, v in kernels.items() if v[0] != 0}
     assert not bad, "kernels with a private segment (scratch): %s" % bad
     assert all(v[1] <= 128 for v in kernels.values()), kernels

@@ -71,7 +71,8 @@ def test_cases_reach_the_backward_pass_and_the_occlusion_condition_holds():
 
 @pytest.mark.parametrize("i", range(len(flow_cases.cases())), ids=[c["name"] for c in flow_cases.cases()])
 def test_identity_rows_with_the_check_off_equal_landmark_flow(mods, i):
-    """The equality contract: slot[r] = r, n = n_slots, max_fb = 0 -> the bits of flm_landmark_flow, on ITS cases."""
+    """The equality contract: slot[r] = r, n = n_slots, max_fb = 0 -> the bits of flm_landmark_flow, on ITS cases.  One
+    kernel serves both calls, so this compares its launch without a slot with its launch on slot[r] = r."""
     _, alignment, _ = mods
     c = flow_cases.cases()[i]
     k = c["lm"].shape[0]
