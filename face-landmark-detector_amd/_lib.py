@@ -38,6 +38,7 @@ EXPORTS = [
     "flm_fcn_packed_bytes", "flm_fcn_pack", "flm_fcn_workspace_bytes", "flm_fcn_forward",
     "flm_forward_opts_init", "flm_fcn_workspace_bytes_opts", "flm_fcn_forward_opts", "flm_fcn8_workspace_offset_opts",
     "flm_fcn_workspace_offset_opts", "flm_fcn_encoder_layers", "flm_fcn_encoder_layer",
+    "flm_fallback_opts_init", "flm_fcn_workspace_bytes_fb", "flm_fcn_workspace_offset_fb", "flm_fcn_forward_fb",
     "flm_fcn8_workspace_bytes", "flm_fcn8_forward", "flm_fcn8_workspace_offset", "flm_fcn8_run_layer",
     "flm_set_tuning", "flm_get_tuning", "flm_debug_query", "flm_profile_enable", "flm_profile_filter", "flm_profile_reset", "flm_profile_read", "flm_profile_disable",
     "flm_preprocess",
@@ -94,6 +95,18 @@ class ForwardOpts(C.Structure):
 
     def key(self):
         return (self.landmark_candidates, self.candidate_sub_phases, self.candidate_cap_div)
+
+
+class FallbackOpts(C.Structure):
+    """flm_fallback_opts: the row budget of the candidate path's per-face fallback (include/flm.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("faces", C.c_int32)]
+
+    @classmethod
+    def make(cls, faces=0):
+        o = cls()
+        load().flm_fallback_opts_init(C.byref(o))
+        o.faces = int(faces)
+        return o
 
 
 class EncLayerInfo(C.Structure):
@@ -331,6 +344,15 @@ def _declare(lib):
     lib.flm_fcn8_workspace_offset.argtypes = [C.c_char_p] + [i] * 8
     lib.flm_fcn_workspace_offset_opts.restype = C.c_int64
     lib.flm_fcn_workspace_offset_opts.argtypes = [i, C.c_char_p] + [i] * 8 + [C.POINTER(ForwardOpts)]
+    lib.flm_fallback_opts_init.restype = None
+    lib.flm_fallback_opts_init.argtypes = [C.POINTER(FallbackOpts)]
+    lib.flm_fcn_workspace_bytes_fb.restype = sz
+    lib.flm_fcn_workspace_bytes_fb.argtypes = [i] * 9 + [C.POINTER(ForwardOpts), C.POINTER(FallbackOpts)]
+    lib.flm_fcn_workspace_offset_fb.restype = C.c_int64
+    lib.flm_fcn_workspace_offset_fb.argtypes = [i, C.c_char_p] + [i] * 8 + [C.POINTER(ForwardOpts), C.POINTER(FallbackOpts)]
+    lib.flm_fcn_forward_fb.restype = i
+    lib.flm_fcn_forward_fb.argtypes = [vp, i, vp, vp, i, i, i, i, i, i, i, i, i, f, vp, vp, sz, C.POINTER(ForwardOpts),
+                                       C.POINTER(FallbackOpts)]
     lib.flm_fcn_encoder_layers.restype = i
     lib.flm_fcn_encoder_layers.argtypes = [i]
     lib.flm_fcn_encoder_layer.restype = i

@@ -114,6 +114,22 @@ static bool resolve_opts(const flm_forward_opts* o, CandOpts* c) {
   c->cap_div = o->candidate_cap_div;
   return true;
 }
+// flm_fallback_opts: the row budget of the per-face fallback (0 = off; clamped to n by the layout).  false: rejected.
+static bool resolve_fallback(const flm_fallback_opts* fb, int* faces) {
+  *faces = 0;
+  if (!fb) return true;
+  if (fb->struct_size < sizeof(flm_fallback_opts)) {
+    set_error("flm_fallback_opts: struct_size %u is smaller than this library's %zu (initialise with flm_fallback_opts_init)",
+              fb->struct_size, sizeof(flm_fallback_opts));
+    return false;
+  }
+  if (fb->faces < 0) {
+    set_error("flm_fallback_opts: faces must be >= 0 (got %d)", fb->faces);
+    return false;
+  }
+  *faces = fb->faces;
+  return true;
+}
 // More sampled phases cost 1/64 of up3 each and tighten the threshold: the key lists shrink about in proportion.  At
 // n = 4 the lists are short anyway (4 phases: 8-10 k keys per face); at n >= 16 their merge costs more than the extra
 // phases (batch 512 bf16, n = 25: 12.1 ms with 4 phases, 11.5 with 8; tools/ab_sub.py).
@@ -144,10 +160,11 @@ static size_t take(size_t& cur, size_t bytes) {
 }
 
 Fcn8Ws fcn8_ws_layout(int n, int h, int w, int C, int dtype, int out_mode, int decode_mode, int n_points,
-                      int arch, const flm_forward_opts* opts) {
+                      int arch, const flm_forward_opts* opts, const flm_fallback_opts* fb) {
   Fcn8Ws W;
   CandOpts co;
-  if (!resolve_opts(opts, &co)) {  // callers validate first (check_opts); an invalid struct sizes nothing
+  int fb_faces = 0;
+  if (!resolve_opts(opts, &co) || !resolve_fallback(fb, &fb_faces)) {  // callers validate first; an invalid struct sizes nothing
     W = Fcn8Ws();
     W.total = 0;
     return W;
@@ -185,6 +202,8 @@ Fcn8Ws fcn8_ws_layout(int n, int h, int w, int C, int dtype, int out_mode, int d
   W.decode = SIZE_MAX;
   W.sub = W.tau = W.cand = W.cand_cnt = SIZE_MAX;
   W.cand_cap = W.cand_sub = 0;
+  W.cand_redo = W.fb_rows = W.fb_counts = W.fb_decode = SIZE_MAX;
+  W.fb_faces = 0;
   const int stats = out_mode == FLM_OUT_LANDMARKS_STATS;  // (adds only the all-pixel mode's three further partial sums)
   if (out_mode == FLM_OUT_LANDMARKS || stats) {
     W.probs = take(cur, sizeof(float) * (size_t)n * W.oh * W.ow * C);
@@ -200,6 +219,15 @@ Fcn8Ws fcn8_ws_layout(int n, int h, int w, int C, int dtype, int out_mode, int d
       if (W.cand_cap < 64) W.cand_cap = 64;
       W.cand = take(cur, sizeof(unsigned long long) * (size_t)n * W.cand_cap);
       W.cand_cnt = take(cur, sizeof(unsigned) * ((size_t)n + 1));
+      if (fb_faces > 0) {
+        // per-face fallback (flm_fallback_opts): after cand_cnt, so no other name moves.  cand_redo follows cand_cnt
+        // directly: one memset clears both.  The compact decode plans its chunks for B rows, so it has partials of its own.
+        W.fb_faces = fb_faces < n ? fb_faces : n;
+        W.cand_redo = take(cur, sizeof(unsigned) * (size_t)n);
+        W.fb_rows = take(cur, sizeof(int) * (size_t)W.fb_faces);
+        W.fb_counts = take(cur, sizeof(unsigned) * 6);
+        W.fb_decode = take(cur, decode_ws_bytes(W.fb_faces, W.oh, W.ow, C, decode_mode, n_points, stats));
+      }
     }
   }
   W.total = cur;
@@ -442,10 +470,20 @@ size_t flm_fcn32_workspace_bytes(int n, int h, int w, int n_classes, int dtype, 
   if (check_fcn8_shape(n, h, w, n_classes, dtype)) return 0;
   return fcn8_ws_layout(n, h, w, n_classes, dtype, out_mode, decode_mode, n_points, FLM_ARCH_FCN32).total;
 }
+size_t flm_fcn_workspace_bytes_fb(int arch, int n, int h, int w, int n_classes, int dtype, int out_mode,
+                                  int decode_mode, int n_points, const flm_forward_opts* opts,
+                                  const flm_fallback_opts* fb) {
+  if (!arch_spec(arch).valid || check_fcn8_shape(n, h, w, n_classes, dtype)) return 0;
+  return fcn8_ws_layout(n, h, w, n_classes, dtype, out_mode, decode_mode, n_points, arch, opts, fb).total;
+}
 size_t flm_fcn_workspace_bytes_opts(int arch, int n, int h, int w, int n_classes, int dtype, int out_mode,
                                     int decode_mode, int n_points, const flm_forward_opts* opts) {
-  if (!arch_spec(arch).valid || check_fcn8_shape(n, h, w, n_classes, dtype)) return 0;
-  return fcn8_ws_layout(n, h, w, n_classes, dtype, out_mode, decode_mode, n_points, arch, opts).total;
+  return flm_fcn_workspace_bytes_fb(arch, n, h, w, n_classes, dtype, out_mode, decode_mode, n_points, opts, nullptr);
+}
+void flm_fallback_opts_init(flm_fallback_opts* fb) {
+  if (!fb) return;
+  fb->struct_size = (uint32_t)sizeof(flm_fallback_opts);
+  fb->faces = 0;
 }
 size_t flm_fcn_workspace_bytes(int arch, int n, int h, int w, int n_classes, int dtype, int out_mode, int decode_mode,
                                int n_points) {
@@ -471,10 +509,18 @@ int64_t flm_fcn8_workspace_offset_opts(const char* name, int n, int h, int w, in
 }
 int64_t flm_fcn_workspace_offset_opts(int arch, const char* name, int n, int h, int w, int n_classes, int dtype,
                                       int out_mode, int decode_mode, int n_points, const flm_forward_opts* opts) {
+  return flm_fcn_workspace_offset_fb(arch, name, n, h, w, n_classes, dtype, out_mode, decode_mode, n_points, opts, nullptr);
+}
+int64_t flm_fcn_workspace_offset_fb(int arch, const char* name, int n, int h, int w, int n_classes, int dtype,
+                                    int out_mode, int decode_mode, int n_points, const flm_forward_opts* opts,
+                                    const flm_fallback_opts* fb) {
   const ArchSpec A = arch_spec(arch);
   if (!name || !A.valid || check_fcn8_shape(n, h, w, n_classes, dtype)) return -1;
-  const Fcn8Ws W = fcn8_ws_layout(n, h, w, n_classes, dtype, out_mode, decode_mode, n_points, arch, opts);
+  const Fcn8Ws W = fcn8_ws_layout(n, h, w, n_classes, dtype, out_mode, decode_mode, n_points, arch, opts, fb);
   if (W.total == 0) return -1;
+  if (!strcmp(name, "cand_redo")) return W.cand_redo == SIZE_MAX ? -1 : (int64_t)W.cand_redo;
+  if (!strcmp(name, "fallback_rows")) return W.fb_rows == SIZE_MAX ? -1 : (int64_t)W.fb_rows;
+  if (!strcmp(name, "fallback_counts")) return W.fb_counts == SIZE_MAX ? -1 : (int64_t)W.fb_counts;
   if (name[0] == 'f' && name[1] >= '1' && name[1] <= '5' && name[2] == 0) return (int64_t)W.f[name[1] - '1'];
   if (!strncmp(name, "act", 3) && name[3] >= '0' && name[3] <= '9') {  // "act<i>": encoder layer i of ArchSpec::enc
     int i = 0;
@@ -553,10 +599,11 @@ int flm_fcn_encoder_layer(int arch, int index, int h, int w, flm_enc_layer_info*
 static int forward_impl(flm_stream_t stream, const void* packed_dev, const void* x_dev, int in_format, int n, int h,
                         int w, int C, int dtype, int out_mode, int decode_mode, int n_points, float thresh,
                         void* out_dev, void* workspace_dev, size_t workspace_bytes, int arch,
-                        const flm_forward_opts* opts = nullptr) {
+                        const flm_forward_opts* opts = nullptr, const flm_fallback_opts* fb = nullptr) {
   const ArchSpec A = arch_spec(arch);
   CandOpts co;
-  if (!resolve_opts(opts, &co)) return FLM_ERR_ARG;
+  int fb_faces = 0;
+  if (!resolve_opts(opts, &co) || !resolve_fallback(fb, &fb_faces)) return FLM_ERR_ARG;
   if (!A.valid) {
     set_error("flm_fcn_forward: unknown architecture %d", arch);
     return FLM_ERR_ARG;
@@ -572,7 +619,7 @@ static int forward_impl(flm_stream_t stream, const void* packed_dev, const void*
     set_error("flm_fcn8_forward: unknown output mode %d", out_mode);
     return FLM_ERR_ARG;
   }
-  const Fcn8Ws W = fcn8_ws_layout(n, h, w, C, dtype, out_mode, decode_mode, n_points, arch, opts);
+  const Fcn8Ws W = fcn8_ws_layout(n, h, w, C, dtype, out_mode, decode_mode, n_points, arch, opts, fb);
   if (workspace_bytes < W.total) {
     set_error("flm_fcn8_forward: workspace too small (%zu < %zu)", workspace_bytes, W.total);
     return FLM_ERR_WORKSPACE;
@@ -732,7 +779,10 @@ static int forward_impl(flm_stream_t stream, const void* packed_dev, const void*
     float* tau = reinterpret_cast<float*>(ws + W.tau);
     unsigned* cnt = reinterpret_cast<unsigned*>(ws + W.cand_cnt);
     unsigned long long* cand = reinterpret_cast<unsigned long long*>(ws + W.cand);
-    FLM_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned) * ((size_t)n + 1), s));
+    // per-face fallback (flm_fallback_opts): the flags lie right behind the counts, so the one memset clears both
+    const int B = W.fb_faces;
+    unsigned* redo = B ? reinterpret_cast<unsigned*>(ws + W.cand_redo) : nullptr;
+    FLM_HIP(hipMemsetAsync(cnt, 0, B ? (W.cand_redo - W.cand_cnt) + sizeof(unsigned) * (size_t)n : sizeof(unsigned) * ((size_t)n + 1), s));
     ConvTDesc ts = t;
     ts.y = sub; ts.epilogue = 4; ts.sub = W.cand_sub;
     { ProfScope ps(s, "up3_sub");
@@ -743,15 +793,36 @@ static int forward_impl(flm_stream_t stream, const void* packed_dev, const void*
     if (rc) return rc;
     ConvTDesc tc = t;
     tc.y = nullptr; tc.epilogue = 3; tc.tau = tau; tc.cand = cand; tc.cand_cnt = cnt; tc.cand_cap = W.cand_cap;
+    tc.cand_redo = redo;
     // (the probability region is written only by the gated fallback below, after this launch: its scratch until then)
     tc.scratch = probs; tc.scratch_bytes = sizeof(float) * (size_t)n * W.oh * W.ow * C;
     { ProfScope ps(s, "up3");
     rc = launch_convt(s, tc); }
     if (rc) return rc;
     { ProfScope ps(s, "decode");
-    rc = launch_cand_merge(s, cand, cnt, n, W.ow, C, n_points, thresh, W.cand_cap, static_cast<double*>(out_dev), stats); }
+    rc = launch_cand_merge(s, cand, cnt, n, W.ow, C, n_points, thresh, W.cand_cap, static_cast<double*>(out_dev), stats, redo); }
     if (rc) return rc;
     gate = cnt + n;  // overflow flag: non-zero -> redo this batch through the probability tensor
+    if (B) {
+      // only the faces that raised, as a compact batch of at most B rows (the first B rows of `probs`); more than B of
+      // them: the whole-batch redo below, gated on the plan's batch_gate instead of the flag
+      int* rows = reinterpret_cast<int*>(ws + W.fb_rows);
+      unsigned* counts = reinterpret_cast<unsigned*>(ws + W.fb_counts);
+      { ProfScope ps(s, "fallback_plan");
+      rc = launch_fallback_plan(s, redo, n, B, rows, counts); }
+      if (rc) return rc;
+      ConvTDesc tr = t;
+      tr.n = B; tr.y = probs; tr.epilogue = 1; tr.gate = counts + 4; tr.rows = rows; tr.rows_cnt = counts;
+      { ProfScope ps(s, "up3_rows");
+      rc = launch_convt(s, tr); }
+      if (rc) return rc;
+      { ProfScope ps(s, "decode_rows");
+      rc = launch_decode(s, probs, B, W.oh, W.ow, C, decode_mode, n_points, thresh, static_cast<double*>(out_dev),
+                         ws + W.fb_decode, decode_ws_bytes(B, W.oh, W.ow, C, decode_mode, n_points, stats), counts + 4, stats,
+                         rows, counts); }
+      if (rc) return rc;
+      gate = counts + 5;
+    }
     t.gate = gate;
   }
   t.y = probs;
@@ -804,8 +875,15 @@ int flm_fcn8_forward(flm_stream_t stream, const void* packed_dev, const void* x_
 int flm_fcn_forward_opts(flm_stream_t stream, int arch, const void* packed_dev, const void* x_dev, int in_format, int n,
                          int h, int w, int C, int dtype, int out_mode, int decode_mode, int n_points, float thresh,
                          void* out_dev, void* workspace_dev, size_t workspace_bytes, const flm_forward_opts* opts) {
+  return flm_fcn_forward_fb(stream, arch, packed_dev, x_dev, in_format, n, h, w, C, dtype, out_mode, decode_mode, n_points,
+                            thresh, out_dev, workspace_dev, workspace_bytes, opts, nullptr);
+}
+int flm_fcn_forward_fb(flm_stream_t stream, int arch, const void* packed_dev, const void* x_dev, int in_format, int n,
+                       int h, int w, int C, int dtype, int out_mode, int decode_mode, int n_points, float thresh,
+                       void* out_dev, void* workspace_dev, size_t workspace_bytes, const flm_forward_opts* opts,
+                       const flm_fallback_opts* fb) {
   return forward_impl(stream, packed_dev, x_dev, in_format, n, h, w, C, dtype, out_mode, decode_mode, n_points, thresh,
-                      out_dev, workspace_dev, workspace_bytes, arch, opts);
+                      out_dev, workspace_dev, workspace_bytes, arch, opts, fb);
 }
 int flm_fcn_forward(flm_stream_t stream, int arch, const void* packed_dev, const void* x_dev, int in_format, int n,
                     int h, int w, int C, int dtype, int out_mode, int decode_mode, int n_points, float thresh,

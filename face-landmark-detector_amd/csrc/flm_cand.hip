@@ -17,6 +17,7 @@ namespace flm {
 struct CandMergeArgs {
   const unsigned long long* cand;
   unsigned* cand_cnt;  // [n] fill counts, [n] = fallback flag
+  unsigned* cand_redo; // [n] or null: the fallback flag per face
   int n, w, l, n_points, cap;
   float thresh;
   double* out;  // [n][l][2], or landmark records [n][l][FLM_LANDMARK_REC] for the stats kernel
@@ -110,7 +111,10 @@ __global__ __launch_bounds__(NW * 64) void cand_merge_kernel(CandMergeArgs a) {
     if (c < cend) {
       // fewer than n keys: the threshold did not have n pixels above it (or the class has fewer than n non-zero
       // pixels), so the list may not hold the whole top n -> let the materialising path redo the batch
-      if (readlane64(list[k], a.n_points - 1) == 0ull && lane == 0) atomicOr(&a.cand_cnt[a.n], 1u);
+      if (readlane64(list[k], a.n_points - 1) == 0ull && lane == 0) {
+        atomicOr(&a.cand_cnt[a.n], 1u);
+        if (a.cand_redo) a.cand_redo[face] = 1u;
+      }
       if constexpr (STATS) finish_topn_stats(list[k], a.n_points, a.w, a.thresh, lane, a.out + ((size_t)face * a.l + c) * FLM_LANDMARK_REC);
       else finish_topn(list[k], a.n_points, a.w, a.thresh, lane, a.out + ((size_t)face * a.l + c) * 2);
     }
@@ -212,13 +216,13 @@ int launch_cand_tau(hipStream_t s, const unsigned* wave_max, int n, int slots, i
 }
 
 int launch_cand_merge(hipStream_t s, const unsigned long long* cand, unsigned* cand_cnt, int n, int w, int l,
-                      int n_points, float thresh, int cap, double* out, int stats) {
+                      int n_points, float thresh, int cap, double* out, int stats, unsigned* cand_redo) {
   if (l > 68 || n_points < 1 || n_points > 64) {
     set_error("cand_merge: unsupported l=%d n_points=%d", l, n_points);
     return FLM_ERR_UNSUPPORTED;
   }
   CandMergeArgs a;
-  a.cand = cand; a.cand_cnt = cand_cnt; a.n = n; a.w = w; a.l = l; a.n_points = n_points; a.cap = cap;
+  a.cand = cand; a.cand_cnt = cand_cnt; a.cand_redo = cand_redo; a.n = n; a.w = w; a.l = l; a.n_points = n_points; a.cap = cap;
   a.thresh = thresh; a.out = out;
   if (n < kCandFineBatch) {
     a.cpg = 17;
@@ -230,6 +234,59 @@ int launch_cand_merge(hipStream_t s, const unsigned long long* cand, unsigned* c
     else cand_merge_kernel<9, 8, false><<<dim3(1, n), 512, 0, s>>>(a);
   }
   FLM_LAUNCH_CHECK("cand_merge_kernel");
+  return FLM_OK;
+}
+
+// ---- per-face fallback: the faces that raised, compacted into the row budget -------------------------------------------
+// ONE workgroup of 256 walks cand_redo[0..n) a chunk of 256 faces at a time, as track_gather_live_kernel (flm_track.hip)
+// walks its slots: a ballot and mbcnt give a raised face's rank within its wave, the waves' totals meet in LDS, and a
+// carry every thread keeps for itself runs from chunk to chunk -- so the exclusive prefix count IS the row, no atomics, and
+// the order (ascending faces) is a function of the input.  R is known after the last chunk: the rows from R on, the counts
+// and the two gate words are written then.
+__global__ __launch_bounds__(256) void fallback_plan_kernel(const unsigned* __restrict__ cand_redo, int n, int budget,
+                                                            int* __restrict__ rows, unsigned* __restrict__ counts) {
+  __shared__ int wave_total[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int carry = 0;  // raised faces before this chunk
+  for (int base = 0; base < n; base += 256) {
+    const int face = base + tid;
+    const bool raised = face < n && cand_redo[face] != 0u;
+    const unsigned long long mask = __ballot(raised);
+    const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+    if (lane == 0) wave_total[wave] = __popcll(mask);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int t = wave_total[w];
+      before += w < wave ? t : 0;
+      total += t;
+    }
+    const int rank = carry + before + below;
+    carry += total;
+    if (raised && rank < budget) rows[rank] = face;
+    __syncthreads();  // wave_total is rewritten by the next chunk
+  }
+  const int R = carry;
+  for (int r = R + tid; r < budget; r += 256) rows[r] = -1;
+  if (tid == 0) {
+    const bool batch = R > budget;
+    counts[0] = (unsigned)R;
+    counts[1] = batch ? 0u : (unsigned)R;
+    counts[2] = batch ? 1u : 0u;
+    counts[3] = (unsigned)budget;
+    counts[4] = (R > 0 && !batch) ? 1u : 0u;  // rows_gate
+    counts[5] = batch ? 1u : 0u;              // batch_gate
+  }
+}
+
+int launch_fallback_plan(hipStream_t s, const unsigned* cand_redo, int n, int budget, int* rows, unsigned* counts) {
+  if (!cand_redo || !rows || !counts || n < 1 || budget < 1 || budget > n) {
+    set_error("fallback_plan: bad argument (n=%d budget=%d)", n, budget);
+    return FLM_ERR_ARG;
+  }
+  fallback_plan_kernel<<<1, 256, 0, s>>>(cand_redo, n, budget, rows, counts);
+  FLM_LAUNCH_CHECK("fallback_plan_kernel");
   return FLM_OK;
 }
 

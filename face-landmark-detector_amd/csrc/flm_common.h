@@ -136,13 +136,17 @@ struct Fcn8Ws {
   // landmark mode without the probability tensor (flm_convt.hip); cand == SIZE_MAX when not used
   size_t sub, tau, cand, cand_cnt;
   int cand_cap;
+  // per-face fallback (flm_fallback_opts, faces = fb_faces > 0 on the candidate path); SIZE_MAX / 0 otherwise.  fb_counts
+  // holds {R, served, batch, B} and behind them the two gate words: [4] rows_gate = (0 < R <= B), [5] batch_gate = (R > B)
+  size_t cand_redo, fb_rows, fb_counts, fb_decode;
+  int fb_faces;
   int cand_sub;  // phases the sampling launch takes per tile
   size_t total;
   int oh, ow;
 };
 // `opts` (NULL = defaults) carries the per-call options that change the layout (include/flm.h: flm_forward_opts).
 Fcn8Ws fcn8_ws_layout(int n, int h, int w, int C, int dtype, int out_mode, int decode_mode, int n_points,
-                      int arch = 0, const flm_forward_opts* opts = nullptr);
+                      int arch = 0, const flm_forward_opts* opts = nullptr, const flm_fallback_opts* fb = nullptr);
 
 // ---- A/B knobs (flm_set_tuning / flm_get_tuning; include/flm.h documents every key) ----------
 // One row per knob in the table of flm_api.hip, in this order.  A launcher reads each knob it uses exactly ONCE per
@@ -212,6 +216,11 @@ struct ConvTDesc {
   const unsigned* gate = nullptr;      // launch is a no-op unless *gate != 0
   void* scratch = nullptr;             // epilogue 3: memory the launch may use (the bf16 input copy of up3_wreg_kernel), or null
   size_t scratch_bytes = 0;
+  unsigned* cand_redo = nullptr;       // epilogue 3: [n] per-face form of the overflow flag (set where it is raised), or null
+  // epilogue 1 of the 68-class kernels on a compact batch: n is the row budget, row r reads x of face rows[r] and writes
+  // map row r; rows at index *rows_cnt and beyond do nothing.  Both null otherwise.
+  const int* rows = nullptr;
+  const unsigned* rows_cnt = nullptr;
 };
 int launch_convt(hipStream_t s, const ConvTDesc& d);
 int convt_candidates_supported(const ConvTGeom& g);
@@ -235,14 +244,20 @@ int launch_maxpool3(hipStream_t s, const void* x, int n, int h, int w, int c, vo
 // `stats`: `out` takes landmark records [n][l][FLM_LANDMARK_REC] instead of [n][l][2] (flm_decode_stats; include/flm.h)
 size_t decode_ws_bytes(int n, int h, int w, int l, int mode, int n_points, int stats = 0);
 int launch_decode(hipStream_t s, const float* hm, int n, int h, int w, int l, int mode, int n_points, float thresh,
-                  double* out, void* ws, size_t ws_bytes, const unsigned* gate = nullptr, int stats = 0);
+                  double* out, void* ws, size_t ws_bytes, const unsigned* gate = nullptr, int stats = 0,
+                  const int* rows = nullptr, const unsigned* rows_cnt = nullptr);
+// (rows / rows_cnt, top-n only: hm is a compact batch of n rows; rows at index *rows_cnt and beyond are skipped and row
+// r's result goes to out[rows[r]])
 size_t decode_sweep_ws_bytes(int n, int h, int w, int l, const int* modes, int n_modes);
 int launch_decode_sweep(hipStream_t s, const float* hm, int n, int h, int w, int l, const int* modes, int n_modes,
                         float thresh, double* out, void* ws, size_t ws_bytes);
 int launch_gaussian_heatmaps(hipStream_t s, const double* kp, int n, int l, int h, int w, double two_sigma_sq,
                              float* out);
 int launch_cand_merge(hipStream_t s, const unsigned long long* cand, unsigned* cand_cnt, int n, int w, int l,
-                      int n_points, float thresh, int cap, double* out, int stats = 0);
+                      int n_points, float thresh, int cap, double* out, int stats = 0, unsigned* cand_redo = nullptr);
+// The faces cand_redo[0..n) marks, ascending, into rows[0..budget) (-1 from index R on); counts = {R, R <= budget ? R : 0,
+// R > budget, budget}, counts[4] = (0 < R <= budget), counts[5] = (R > budget): the gates of the two redo paths.
+int launch_fallback_plan(hipStream_t s, const unsigned* cand_redo, int n, int budget, int* rows, unsigned* counts);
 
 int launch_preprocess(hipStream_t s, const uint8_t* img, int n, int h, int w, int norm, float* out);
 int launch_similarity(hipStream_t s, const double* lm, const double* tmpl, int n, int k, double sx, double sy, float* m);

@@ -57,8 +57,10 @@ constexpr int GCH_F32 = 6, GCH_BF16 = 3;  // k groups per LDS chunk (bf16: small
 
 
 // MODE: 0 = epilogues 0/1/2 (maps), 1 = epilogue 3 (top-n candidates), 2 = epilogue 4 (sampling launch: wave maxima)
-template <int MT, int G, bool BF, int NT, int MODE, bool SHARE>
+// ROWS (MODE 0, the 68-class kernels): the compact batch of the per-face fallback, see ConvTArgs::rows.
+template <int MT, int G, bool BF, int NT, int MODE, bool SHARE, bool ROWS = false>
 __global__ __launch_bounds__(256, (!BF && MT >= 5 && G >= 20) ? 1 : 2) void convt_kernel(ConvTArgs a) {
+  static_assert(!ROWS || MODE == 0, "the compact batch is a map-writing launch");
   constexpr bool CAND = MODE == 1;
   constexpr bool SAMPLE = MODE == 2;
   // The 68-class kernels know their class count, and their packed weights put classes 64..67 on rows 0, 4, 8, 12 of
@@ -68,6 +70,13 @@ __global__ __launch_bounds__(256, (!BF && MT >= 5 && G >= 20) ? 1 : 2) void conv
 #define FLM_CVALID(M, E) (C68 ? ((M) < 4 || (E) == 0) : (16 * (M) + 4 * q + (E) < a.C))
 #define FLM_CLS(M, E) ((C68 && (M) == 4) ? (64 + q) : (16 * (M) + 4 * q + (E)))
   if (a.gate && *a.gate == 0) return;
+  // compact batch: the positions of the live rows; a workgroup that starts at or beyond them has nothing to do
+  int p_live = a.P;
+  if constexpr (ROWS) {
+    const int live = (int)min(*a.rows_cnt, (unsigned)a.n);
+    p_live = live * (a.hi + 1) * (a.wi + 1);
+    if ((int)blockIdx.x * 64 * NT >= p_live) return;
+  }
   constexpr int GCH = BF ? GCH_BF16 : GCH_F32;
   constexpr int NCH = (G + GCH - 1) / GCH;
   constexpr int CHUNK_F4 = GCH * MT * 64;             // float4 per full chunk
@@ -110,6 +119,7 @@ __global__ __launch_bounds__(256, (!BF && MT >= 5 && G >= 20) ? 1 : 2) void conv
   const int wi1 = a.wi + 1, hi1 = a.hi + 1;
   bool pvalid[NT];
   int i0[NT], j0[NT], img[NT];
+  int ximg[NT];  // the face whose x the position reads (ROWS: rows[img], else img itself)
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     const int p = (blockIdx.x * 4 + wave) * 16 * NT + nt * 16 + r;
@@ -122,11 +132,16 @@ __global__ __launch_bounds__(256, (!BF && MT >= 5 && G >= 20) ? 1 : 2) void conv
       j0[nt] = pp % wi1;
       i0[nt] = pp / wi1;
     } else {
-      pvalid[nt] = p < a.P;
+      pvalid[nt] = p < p_live;
       const int pp = pvalid[nt] ? p : 0;
       j0[nt] = pp % wi1;
       i0[nt] = (pp / wi1) % hi1;
       img[nt] = pp / (wi1 * hi1);
+    }
+    ximg[nt] = img[nt];
+    if constexpr (ROWS) {
+      ximg[nt] = a.rows[img[nt]];  // (img < min(*rows_cnt, n): an entry the plan wrote; position 0 of row 0 when !pvalid)
+      if (ximg[nt] < 0) { ximg[nt] = 0; pvalid[nt] = false; }
     }
   }
   // candidate mode: thresholds of this WAVE's face for the 4*MT classes of a lane (16m + 4q + e).  Faces are padded at
@@ -156,7 +171,7 @@ __global__ __launch_bounds__(256, (!BF && MT >= 5 && G >= 20) ? 1 : 2) void conv
     const int tap = k0 / a.Cp, c = k0 % a.Cp;
     const int ii = i0[nt] - (tap >> 1), jj = j0[nt] - (tap & 1);
     const bool ok = pvalid[nt] && tap < 4 && (unsigned)ii < (unsigned)a.hi && (unsigned)jj < (unsigned)a.wi;
-    const size_t off = ok ? (((size_t)img[nt] * a.hi + ii) * a.wi + jj) * a.Cp + c : 0;
+    const size_t off = ok ? (((size_t)ximg[nt] * a.hi + ii) * a.wi + jj) * a.Cp + c : 0;
     // (component-wise selects: a float4 struct select goes through scratch memory)
     const float km = ok ? 1.f : 0.f;
     if constexpr (BF) {
@@ -234,15 +249,16 @@ __global__ __launch_bounds__(256, (!BF && MT >= 5 && G >= 20) ? 1 : 2) void conv
 #define FLM_CAND_FLUSH()                                                                          \
   {                                                                                               \
     const unsigned found_ = __builtin_amdgcn_readfirstlane(wcnt);                                 \
+    const unsigned cap_ = cand_cap_of(a.cand_cap);                                                \
     if (wg_img < a.n && found_) {                                                                 \
       unsigned base_ = 0;                                                                         \
       if (lane == 0) {                                                                            \
         base_ = atomicAdd(&a.cand_cnt[wg_img], found_);                                           \
-        if (base_ + found_ > (unsigned)a.cand_cap) atomicOr(&a.cand_cnt[a.n], 1u);                \
+        if (base_ + found_ > cap_) cand_raise(a.cand_cnt, a.n, a.cand_cap, wg_img);               \
       }                                                                                           \
       base_ = __builtin_amdgcn_readfirstlane(base_);                                              \
       for (unsigned i_ = lane; i_ < found_; i_ += 64)                                             \
-        if (base_ + i_ < (unsigned)a.cand_cap) a.cand[(size_t)wg_img * a.cand_cap + base_ + i_] = cwave[i_]; \
+        if (base_ + i_ < cap_) a.cand[(size_t)wg_img * cap_ + base_ + i_] = cwave[i_];            \
     }                                                                                             \
     wcnt = 0;                                                                                     \
   }
@@ -789,14 +805,15 @@ __global__ __launch_bounds__(WAVES * 64, 2) void up3_cand8_kernel(ConvTArgs a) {
   auto cand_flush = [&]() __attribute__((always_inline)) {
     const unsigned found = __builtin_amdgcn_readfirstlane(wcnt);
     if (wlive && found) {
+      const unsigned cap = cand_cap_of(a.cand_cap);
       unsigned base = 0;
       if (lane == 0) {
         base = atomicAdd(&a.cand_cnt[wimg], found);
-        if (base + found > (unsigned)a.cand_cap) atomicOr(&a.cand_cnt[a.n], 1u);
+        if (base + found > cap) cand_raise(a.cand_cnt, a.n, a.cand_cap, wimg);
       }
       base = __builtin_amdgcn_readfirstlane(base);
       for (unsigned i = lane; i < found; i += 64)
-        if (base + i < (unsigned)a.cand_cap) a.cand[(size_t)wimg * a.cand_cap + base + i] = cwave[i];
+        if (base + i < cap) a.cand[(size_t)wimg * cap + base + i] = cwave[i];
     }
     wcnt = 0;
   };
@@ -806,7 +823,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void up3_cand8_kernel(ConvTArgs a) {
   // between has dropped keys: the overflow flag sends the batch through the materialising launch.
   auto lane_flush = [&]() __attribute__((always_inline)) {
     const bool over = lcnt > (unsigned)LANE_CAP;
-    if (__any(over) && wlive && lane == 0) atomicOr(&a.cand_cnt[a.n], 1u);
+    if (__any(over) && wlive && lane == 0) cand_raise(a.cand_cnt, a.n, a.cand_cap, wimg);
     const unsigned mine = over ? (unsigned)LANE_CAP : lcnt;
     unsigned incl = mine;  // inclusive scan over the 64 lanes
 #pragma unroll
@@ -816,14 +833,15 @@ __global__ __launch_bounds__(WAVES * 64, 2) void up3_cand8_kernel(ConvTArgs a) {
     }
     const unsigned total = __builtin_amdgcn_readlane(incl, 63);
     if (wlive && total) {
+      const unsigned cap = cand_cap_of(a.cand_cap);
       unsigned base = 0;
       if (lane == 0) {
         base = atomicAdd(&a.cand_cnt[wimg], total);
-        if (base + total > (unsigned)a.cand_cap) atomicOr(&a.cand_cnt[a.n], 1u);
+        if (base + total > cap) cand_raise(a.cand_cnt, a.n, a.cand_cap, wimg);
       }
       base = __builtin_amdgcn_readfirstlane(base) + incl - mine;
       for (unsigned i = 0; i < mine; ++i)
-        if (base + i < (unsigned)a.cand_cap) a.cand[(size_t)wimg * a.cand_cap + base + i] = cwave[i * 64 + lane];
+        if (base + i < cap) a.cand[(size_t)wimg * cap + base + i] = cwave[i * 64 + lane];
     }
     lcnt = 0;
   };
@@ -957,7 +975,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void up3_cand8_kernel(ConvTArgs a) {
       }
     });
     if (wcnt > (unsigned)KEY_CAP) {  // keys were dropped: exactness now rests on the materialising launch
-      if (lane == 0) atomicOr(&a.cand_cnt[a.n], 1u);
+      if (lane == 0 && wlive) cand_raise(a.cand_cnt, a.n, a.cand_cap, wimg);  // (a wave without a face has no keys)
       wcnt = KEY_CAP;
     }
   };
@@ -1105,7 +1123,7 @@ static int launch_cand8(hipStream_t st, ConvTArgs a) {
   return FLM_OK;
 }
 
-template <int MT, int G, bool BF, int NT = 1, int MODE = 0, bool SHARE = false>
+template <int MT, int G, bool BF, int NT = 1, int MODE = 0, bool SHARE = false, bool ROWS = false>
 static int launch_t(hipStream_t st, ConvTArgs a) {
   constexpr bool CAND = MODE == 1;
   constexpr int GCH = BF ? GCH_BF16 : GCH_F32;
@@ -1116,7 +1134,7 @@ static int launch_t(hipStream_t st, ConvTArgs a) {
   // fp32 candidate kernel to 94 KiB cost 22 % of up3
   static_assert(!(MT == 5 && (G == 9 || G == 17)) || MODE == 2 || lds <= 80 * 1024, "convt: LDS budget of two workgroups per CU");
   static FuncAttrOnce attr;
-  FLM_FUNC_ATTR_ONCE(attr, (&convt_kernel<MT, G, BF, NT, MODE, SHARE>), lds);
+  FLM_FUNC_ATTR_ONCE(attr, (&convt_kernel<MT, G, BF, NT, MODE, SHARE, ROWS>), lds);
   int xblocks = cdiv(a.P, 64 * NT);
   if (a.ppf > 0 && CAND) {  // per-face padding at wave granularity: a WAVE's 16*NT positions belong to one face
     a.ppf = cdiv((a.hi + 1) * (a.wi + 1), 16 * NT) * 16 * NT;
@@ -1131,7 +1149,7 @@ static int launch_t(hipStream_t st, ConvTArgs a) {
     a.nb = rows * a.s;
   }
   dim3 grid(xblocks, a.sub ? 1 : a.s / rows);
-  convt_kernel<MT, G, BF, NT, MODE, SHARE><<<grid, 256, lds, st>>>(a);
+  convt_kernel<MT, G, BF, NT, MODE, SHARE, ROWS><<<grid, 256, lds, st>>>(a);
   FLM_LAUNCH_CHECK("convt_kernel");
   return FLM_OK;
 }
@@ -1161,6 +1179,14 @@ int launch_convt(hipStream_t st, const ConvTDesc& d) {
     return FLM_ERR_SHAPE;
   } a.ppf = (d.sub || d.epilogue == 3) ? 1 : 0;
   a.tau = d.tau; a.cand = d.cand; a.cand_cnt = d.cand_cnt; a.cand_cap = d.cand_cap; a.gate = d.gate;
+  a.rows = d.rows; a.rows_cnt = d.rows_cnt; a.rpw = 0;
+  if (d.cand_redo) {  // the kernels reach the per-face flags from the counts (cand_raise, flm_convt_dev.h)
+    if (d.epilogue != 3 || d.cand_redo != d.cand_cnt + cand_redo_base(d.n) || (d.cand_cap & 63)) {
+      set_error("convt: the per-face flags belong to the candidate epilogue and follow the counts' region");
+      return FLM_ERR_ARG;
+    }
+    a.cand_cap |= kCandRedoBit;
+  }
   const long long P = (long long)d.n * (d.hi + 1) * (d.wi + 1);
   if (P <= 0 || P > (1ll << 30) || d.ho > d.s * (d.hi + 1) || d.wo > d.s * (d.wi + 1)) {
     set_error("convt: bad geometry n=%d in=%dx%d out=%dx%d s=%d", d.n, d.hi, d.wi, d.ho, d.wo, d.s);
@@ -1170,6 +1196,14 @@ int launch_convt(hipStream_t st, const ConvTDesc& d) {
   if (d.epilogue == 0 && (d.ldy & 3)) {
     set_error("convt: raw epilogue needs a channel stride that is a multiple of 4");
     return FLM_ERR_SHAPE;
+  }
+  if (d.rows || d.rows_cnt) {  // the compact batch of the per-face fallback: probabilities of the 68-class kernels
+    if (!d.rows || !d.rows_cnt || d.epilogue != 1 || !convt_candidates_supported(d.g) || !d.y) {
+      set_error("convt: a row map needs the 68-class kernels, the softmax epilogue, the map and its count");
+      return FLM_ERR_UNSUPPORTED;
+    }
+    if (d.g.bf16) return a.share ? launch_t<5, 9, true, 2, 0, true, true>(st, a) : launch_t<5, 9, true, 2, 0, false, true>(st, a);
+    return a.share ? launch_t<5, 17, false, 1, 0, true, true>(st, a) : launch_t<5, 17, false, 1, 0, false, true>(st, a);
   }
   if (d.epilogue == 3) {
     if (!convt_candidates_supported(d.g) || !d.tau || !d.cand || !d.cand_cnt || d.cand_cap <= 0 ||

@@ -30,15 +30,33 @@ struct ConvTArgs {
   const float* tau;           // [n][C] candidate thresholds (epilogue 3)
   unsigned long long* cand;   // [n][cand_cap] keys: order_bits(p) << 32 | class << 17 | pixel
   unsigned* cand_cnt;         // [n] entries appended per face; cand_cnt[n] = overflow flag
-  int cand_cap;
+  int cand_cap;               // a multiple of 64, | kCandRedoBit: the per-face flags follow the counts (cand_raise below)
   const unsigned* gate;       // non-null: the launch does nothing unless *gate != 0
-  int rpw;                    // cand8 kernel: phase rows a0 one workgroup walks with the same X fragments (divides s)
+  int rpw;                   // cand8 kernel: phase rows a0 one workgroup walks with the same X fragments (divides s)
+  // compact batch (template ROWS of convt_kernel): position p of row r = p / ((hi+1)*(wi+1)) reads x of face rows[r] and
+  // writes map row r; rows at index min(*rows_cnt, n) and beyond are invalid
+  const int* rows;
+  const unsigned* rows_cnt;
 };
 
 // candidate keys one wave can hold in LDS: 128 (fp32) or 256 (bf16, NT = 2) pixels x 68 classes pass through it;
 // the fp32 kernel's 61 KiB weight ring leaves room for 512 per wave if two workgroups are to share a CU
 #define kCandWaveCap (512 * NT)
 constexpr int kMaxSamplePhases = 16;
+
+// The per-face form of the overflow flag (flm_fallback_opts): uint32 [n], 1 where the face raised.  The candidate kernels
+// sit at their register budgets and a further pointer would be live from the first instruction to the last for the sake
+// of branches that are almost never taken (it cost the 8-wave kernel an SGPR and the 4-wave shape five more SGPR spills).
+// So the flags are reached from what the raise sites hold anyway: the workspace puts them right behind the counts' region,
+// at cand_cnt[cand_redo_base(n) + face], and bit 0 of the list capacity (a multiple of 64) says that they are there.
+constexpr int kCandRedoBit = 1;
+__host__ __device__ inline int cand_redo_base(int n) { return (n + 64) & ~63; }  // (n + 1 counts, in 256-byte steps)
+__device__ __forceinline__ unsigned cand_cap_of(int cap_arg) { return (unsigned)cap_arg & ~(unsigned)kCandRedoBit; }
+// one lane raises the batch's flag and, where the layout has them, the face's
+__device__ __forceinline__ void cand_raise(unsigned* cand_cnt, int n, int cap_arg, int face) {
+  atomicOr(&cand_cnt[n], 1u);
+  if (cap_arg & kCandRedoBit) cand_cnt[cand_redo_base(n) + face] = 1u;
+}
 
 __device__ __forceinline__ unsigned cand_order_bits(float v) {
   const unsigned u = __float_as_uint(v);

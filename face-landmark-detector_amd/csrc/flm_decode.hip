@@ -119,7 +119,7 @@ __device__ __forceinline__ void group_sums_flush(const DecodeArgs& a, double* re
 // 256 x 3 doubles when ALL.
 template <int CPW, bool WIDE, bool ALL>
 __global__ __launch_bounds__(256) void decode_partial_kernel(DecodeArgs a) {
-  if (a.gate && *a.gate == 0) return;
+  if (decode_row_off(a, blockIdx.y)) return;
   extern __shared__ __attribute__((aligned(16))) float tile[];  // [PT][LS]
   const int L = a.l, LS = L | 1;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void decode_partial_kernel(DecodeArgs a) {
 // LDS-DMA form (68 landmarks, 16-byte-aligned faces, n_max <= 64); the group sums read the same ring slot, row stride 68.
 template <bool ALL>
 __global__ __launch_bounds__(256) void decode_partial_dma_kernel(DecodeArgs a) {
-  if (a.gate && *a.gate == 0) return;
+  if (decode_row_off(a, blockIdx.y)) return;
   extern __shared__ __attribute__((aligned(16))) char ring[];  // [D_RING][PT][DL] floats
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -222,12 +222,14 @@ __global__ __launch_bounds__(256) void decode_partial_dma_kernel(DecodeArgs a) {
 // and the mode loop costs its merge 4 %, so it keeps the loop-free form.
 template <bool WIDE>
 __global__ __launch_bounds__(64) void decode_merge_kernel(DecodeArgs a) {
-  if (a.gate && *a.gate == 0) return;
+  if (decode_row_off(a, blockIdx.y)) return;
   const int lane = threadIdx.x;
   const int c = blockIdx.x, face = blockIdx.y;
+  const int oface = decode_out_face(a, face);
+  if (oface < 0) return;
   unsigned long long list = 0ull, list_hi = 0ull, tau = 0ull;
   merge_chunk_lists<WIDE>(a, face, c, lane, list, list_hi, tau);
-  finish_topn(list, a.n_max, a.w, a.thresh, lane, a.out + ((size_t)face * a.l + c) * 2, list_hi);
+  finish_topn(list, a.n_max, a.w, a.thresh, lane, a.out + ((size_t)oface * a.l + c) * 2, list_hi);
 }
 
 template <bool WIDE>
@@ -432,7 +434,8 @@ static void with_bool(bool b, F f) {
 enum DecodeKind { kDecodeAll, kDecodeTopN, kDecodeSweep };
 static int decode_run(const char* who, hipStream_t s, const float* hm, int n, int h, int w, int l, const int* modes,
                       int n_modes, int n_max, int has_all, DecodeKind kind, float thresh, double* out, void* ws,
-                      size_t ws_bytes, const unsigned* gate, bool stats = false) {
+                      size_t ws_bytes, const unsigned* gate, bool stats = false, const int* rows = nullptr,
+                      const unsigned* rows_cnt = nullptr) {
   if (reinterpret_cast<uintptr_t>(hm) & 15) {
     set_error("%s: heatmap pointer must be 16-byte aligned", who);
     return FLM_ERR_ARG;
@@ -452,6 +455,7 @@ static int decode_run(const char* who, hipStream_t s, const float* hm, int n, in
   a.sums = reinterpret_cast<double*>(static_cast<char*>(ws) + kb);
   a.out = out;
   a.gate = gate;
+  a.rows = rows; a.rows_cnt = rows_cnt;
   a.n_modes = n_modes;
   for (int i = 0; i < FLM_SWEEP_MAX_MODES; ++i) a.modes[i] = i < n_modes ? modes[i] : 0;
 
@@ -501,9 +505,14 @@ static int decode_run(const char* who, hipStream_t s, const float* hm, int n, in
 }
 
 int launch_decode(hipStream_t s, const float* hm, int n, int h, int w, int l, int mode, int n_points, float thresh,
-                  double* out, void* ws, size_t ws_bytes, const unsigned* gate, int stats) {
+                  double* out, void* ws, size_t ws_bytes, const unsigned* gate, int stats, const int* rows,
+                  const unsigned* rows_cnt) {
   const int rc = decode_check_shape("decode", n, h, w, l);
   if (rc != FLM_OK) return rc;
+  if ((rows || rows_cnt) && (!rows || !rows_cnt || mode != FLM_DECODE_TOPN)) {
+    set_error("decode: a row map needs the top-n mode, the map and its count");
+    return FLM_ERR_UNSUPPORTED;
+  }
   if (mode == FLM_DECODE_TOPN && (n_points < 1 || n_points > 128)) {
     set_error("decode: top-n mode supports 1 <= n_points <= 128 (got %d)", n_points);
     return FLM_ERR_UNSUPPORTED;
@@ -515,7 +524,7 @@ int launch_decode(hipStream_t s, const float* hm, int n, int h, int w, int l, in
   if (mode == FLM_DECODE_ALL)
     return decode_run("decode", s, hm, n, h, w, l, nullptr, 0, 0, 1, kDecodeAll, thresh, out, ws, ws_bytes, gate, stats != 0);
   return decode_run("decode", s, hm, n, h, w, l, &n_points, 1, n_points, 0, kDecodeTopN, thresh, out, ws, ws_bytes, gate,
-                    stats != 0);
+                    stats != 0, rows, rows_cnt);
 }
 
 // ---- one-pass multi-n decode (flm_decode_sweep) ------------------------------------------------------------------------

@@ -25,7 +25,19 @@ struct DecodeArgs {
   const unsigned* gate;      // non-null: the launch does nothing unless *gate != 0
   int n_modes;
   int modes[FLM_SWEEP_MAX_MODES];
+  // compact batch (top-n kernels; the per-face fallback of the forward): hm holds n rows, of which those at index
+  // *rows_cnt and beyond are skipped; row r's result goes to out[rows[r]].  Both null: row = face.
+  const int* rows;
+  const unsigned* rows_cnt;
 };
+
+// nothing to do for map row `row`: the launch is gated off, or the row lies beyond the compact batch's live rows
+__device__ __forceinline__ bool decode_row_off(const DecodeArgs& a, int row) {
+  if (a.gate && *a.gate == 0) return true;
+  return a.rows_cnt && (unsigned)row >= *a.rows_cnt;
+}
+// the face whose result map row `row` holds
+__device__ __forceinline__ int decode_out_face(const DecodeArgs& a, int row) { return a.rows ? a.rows[row] : row; }
 
 // the pixel range [p_begin, p_end) of workgroup (chunk, face)
 struct Chunk {

@@ -13,12 +13,14 @@ namespace flm {
 
 template <bool WIDE>
 __global__ __launch_bounds__(64) void decode_merge_stats_kernel(DecodeArgs a) {
-  if (a.gate && *a.gate == 0) return;
+  if (decode_row_off(a, blockIdx.y)) return;
   const int lane = threadIdx.x;
   const int c = blockIdx.x, face = blockIdx.y;
+  const int oface = decode_out_face(a, face);
+  if (oface < 0) return;
   unsigned long long list = 0ull, list_hi = 0ull, tau = 0ull;
   merge_chunk_lists<WIDE>(a, face, c, lane, list, list_hi, tau);
-  finish_topn_stats(list, a.n_max, a.w, a.thresh, lane, a.out + ((size_t)face * a.l + c) * FLM_LANDMARK_REC, list_hi);
+  finish_topn_stats(list, a.n_max, a.w, a.thresh, lane, a.out + ((size_t)oface * a.l + c) * FLM_LANDMARK_REC, list_hi);
 }
 
 int launch_decode_merge_stats(hipStream_t s, dim3 mgrid, const DecodeArgs& a, bool wide) {

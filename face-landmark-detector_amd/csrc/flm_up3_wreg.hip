@@ -67,7 +67,7 @@ struct Args {
   unsigned long long* cand;
   unsigned* cand_cnt;
   const unsigned* gate;
-  int cand_cap;
+  int cand_cap;               // (| kCandRedoBit, as ConvTArgs::cand_cap)
   int n, hi, wi, ho, wo;
   int wi1;                    // positions per row (wi + 1)
   unsigned wi1_magic;         // floor(2^32 / wi1) + 1: pl / wi1 = umulhi(pl, magic) for pl < 2^16
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(wreg::WAVES * 64, 2) void up3_wreg_kernel(wreg::Arg
         unsigned gbase = 0;
         if (lane == 0) {
           gbase = atomicAdd(&a.cand_cnt[face], total);
-          if (gbase + total > (unsigned)a.cand_cap) atomicOr(&a.cand_cnt[a.n], 1u);
+          if (gbase + total > cand_cap_of(a.cand_cap)) cand_raise(a.cand_cnt, a.n, a.cand_cap, face);
         }
         unsigned at = __builtin_amdgcn_readfirstlane(gbase) + incl - mine;
         const unsigned pix = pixq & 0x1ffffu;
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(wreg::WAVES * 64, 2) void up3_wreg_kernel(wreg::Arg
             const unsigned pb = *reinterpret_cast<lds_u32*>(ra + 4 * i);
             const unsigned cls = i < 16 ? 16u * (i >> 2) + q4 + (i & 3) : 64u + (q4 >> 2);
             // (p >= tau > 0: its order bits are its bits with the sign set)
-            if (at < (unsigned)a.cand_cap) a.cand[(size_t)face * a.cand_cap + at] = ((unsigned long long)(pb | 0x80000000u) << 32) | (cls << 17) | pix;
+            if (at < cand_cap_of(a.cand_cap)) a.cand[(size_t)face * cand_cap_of(a.cand_cap) + at] = ((unsigned long long)(pb | 0x80000000u) << 32) | (cls << 17) | pix;
             ++at;
           }
       }

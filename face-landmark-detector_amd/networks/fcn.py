@@ -76,6 +76,9 @@ class Fcn8Model:
         self._ws = collections.OrderedDict()
         self._ws_cap = 4
         self._ws_lock = threading.Lock()
+        self._fb_layouts = {}   # (n, out mode, decode mode, n_points, opts, B) -> offsets of the per-face fallback's regions
+        self._fb_last = {}      # id(workspace) -> (weak reference to it, layout) of its last such forward (_fallback_note)
+        self._fb_cached = None  # weak reference to the cached workspace the last such forward without `workspace=` used
         self._level_layer = {}   # "f1".."f5" -> index of the encoder layer (intermediate)
         # per-model defaults of the per-call options that change the workspace layout (include/flm.h: flm_forward_opts)
         self.forward_opts = {}
@@ -167,33 +170,42 @@ class Fcn8Model:
         merged.update(opts or {})
         return _lib.ForwardOpts.make(**merged)
 
-    def workspace_bytes(self, n, out="probs", n_points=0, opts=None):
+    def _query_bytes(self, n, out_mode, dmode, npts, fo, fallback_faces):
+        """The workspace size of a call: the flm_fcn_*_opts query, or its _fb form when a row budget is set."""
+        lib = _lib.load()
+        args = (self._arch, n, self.input_height, self.input_width, self.n_classes, self._dt, out_mode, dmode, npts,
+                C.byref(fo))
+        if not fallback_faces:
+            return lib.flm_fcn_workspace_bytes_opts(*args)
+        return lib.flm_fcn_workspace_bytes_fb(*args, C.byref(_lib.FallbackOpts.make(fallback_faces)))
+
+    def workspace_bytes(self, n, out="probs", n_points=0, opts=None, fallback_faces=0):
         om = _OUT[out]
         dmode, npts = decode_mode_of(n_points) if om in _DECODING else (0, 0)
         fo = self._opts(opts)
-        nbytes = _lib.load().flm_fcn_workspace_bytes_opts(self._arch, n, self.input_height, self.input_width,
-                                                          self.n_classes, self._dt, om, dmode, npts, C.byref(fo))
+        nbytes = self._query_bytes(n, om, dmode, npts, fo, fallback_faces)
         if nbytes == 0:
             raise _lib.FlmError("workspace query failed: %s" % _lib.load().flm_last_error().decode())
         return int(nbytes)
 
-    def new_workspace(self, n, out="probs", n_points=0, opts=None):
+    def new_workspace(self, n, out="probs", n_points=0, opts=None, fallback_faces=0):
         """A workspace the CALLER owns (pass it as forward_device(..., workspace=ws)): what a captured HIP graph or any
-        other holder of raw pointers must use, since cached workspaces may be evicted."""
+        other holder of raw pointers must use, since cached workspaces may be evicted.  `fallback_faces`: as
+        forward_device's, and the same value there."""
         import torch
-        return torch.empty(self.workspace_bytes(n, out, n_points, opts), dtype=torch.uint8, device=_lib.require_gpu())
+        return torch.empty(self.workspace_bytes(n, out, n_points, opts, fallback_faces), dtype=torch.uint8,
+                           device=_lib.require_gpu())
 
-    def _workspace(self, n, out_mode, dmode, npts, fo):
+    def _workspace(self, n, out_mode, dmode, npts, fo, fallback_faces=0):
         import torch
         stream = torch.cuda.current_stream().cuda_stream
-        key = (stream, n, out_mode, dmode, npts) + fo.key()
+        key = (stream, n, out_mode, dmode, npts) + fo.key() + ((int(fallback_faces),) if fallback_faces else ())
         with self._ws_lock:
             ws = self._ws.get(key)
             if ws is not None:
                 self._ws.move_to_end(key)
                 return ws
-        nbytes = _lib.load().flm_fcn_workspace_bytes_opts(self._arch, n, self.input_height, self.input_width,
-                                                          self.n_classes, self._dt, out_mode, dmode, npts, C.byref(fo))
+        nbytes = self._query_bytes(n, out_mode, dmode, npts, fo, fallback_faces)
         if nbytes == 0:
             raise _lib.FlmError("workspace query failed: %s" % _lib.load().flm_last_error().decode())
         with self._ws_lock:
@@ -205,7 +217,8 @@ class Fcn8Model:
             self._ws[key] = ws
         return ws
 
-    def forward_device(self, x, out="probs", n_points=0, thresh=0.0, out_tensor=None, workspace=None, opts=None):
+    def forward_device(self, x, out="probs", n_points=0, thresh=0.0, out_tensor=None, workspace=None, opts=None,
+                       fallback_faces=0):
         """One launch sequence on the current stream; everything stays in HBM.  Streams may call one model concurrently,
         from one thread or several: a cached workspace belongs to (model, current stream) and is never shared between
         streams.  A holder of raw pointers (a captured graph) passes its own `workspace=`: cached ones may be evicted.
@@ -218,6 +231,9 @@ class Fcn8Model:
              landmark record; columns 0-1 are "landmarks" bit for bit).
         workspace: a caller-owned workspace from `new_workspace` (same n / out / n_points / opts); default: a cached one.
         opts: dict of flm_forward_opts fields (landmark_candidates, candidate_sub_phases, candidate_cap_div).
+        fallback_faces: B > 0: where the landmark outputs take the candidate path, only the faces whose candidate lists
+            fail are redone through the probability tensor, as a compact batch of at most B rows (more than B of them:
+            the whole batch, as with 0, the default).  Same landmarks bit for bit (include/flm.h: flm_fallback_opts).
         """
         import torch
         lib = _lib.load()
@@ -261,16 +277,82 @@ class Fcn8Model:
                 raise ValueError("a caller-owned workspace cannot serve a batch beyond max_batch (%d)" % self.max_batch)
             for lo in range(0, n, self.max_batch):
                 hi = min(n, lo + self.max_batch)
-                self.forward_device(x[lo:hi], out, n_points, thresh, out_tensor[lo:hi], opts=opts)
+                self.forward_device(x[lo:hi], out, n_points, thresh, out_tensor[lo:hi], opts=opts,
+                                    fallback_faces=fallback_faces)
             return out_tensor
         fo = self._opts(opts)
-        ws = workspace if workspace is not None else self._workspace(n, om, dmode, npts, fo)
-        _lib.check(lib.flm_fcn_forward_opts(_lib.stream_ptr(), self._arch, _lib.ptr(self._packed), _lib.ptr(x), fmt, n,
-                                             self.input_height, self.input_width, c, self._dt, om, dmode, npts,
-                                             float(thresh), _lib.ptr(out_tensor), _lib.ptr(ws), ws.numel(),
-                                             C.byref(fo)),
-                   "flm_fcn_forward_opts")
+        if int(fallback_faces) < 0:
+            raise ValueError("fallback_faces must be >= 0 (got %r)" % (fallback_faces,))
+        ws = workspace if workspace is not None else self._workspace(n, om, dmode, npts, fo, fallback_faces)
+        args = (_lib.stream_ptr(), self._arch, _lib.ptr(self._packed), _lib.ptr(x), fmt, n, self.input_height,
+                self.input_width, c, self._dt, om, dmode, npts, float(thresh), _lib.ptr(out_tensor), _lib.ptr(ws),
+                ws.numel(), C.byref(fo))
+        if not fallback_faces:
+            _lib.check(lib.flm_fcn_forward_opts(*args), "flm_fcn_forward_opts")
+        else:
+            _lib.check(lib.flm_fcn_forward_fb(*args, C.byref(_lib.FallbackOpts.make(fallback_faces))),
+                       "flm_fcn_forward_fb")
+            self._fallback_note(ws, workspace is None, self._fallback_layout(n, om, dmode, npts, fo, fallback_faces))
         return out_tensor
+
+    def _fallback_note(self, ws, cached, lay):
+        """Remember where the per-face fallback's regions lie in `ws` after a forward into it (lay None: nowhere).  The
+        model holds the workspace WEAKLY: a caller-owned one stays the caller's, and a cached one lives as long as the
+        cache keeps it.  Keyed by id(ws); the entry goes when the tensor does, so an id that is reused finds nothing."""
+        import weakref
+        table = self._fb_last
+
+        def gone(ref, key=id(ws)):      # (no lock: a dict operation is atomic, and this may run inside any allocation)
+            ent = table.get(key)
+            if ent is not None and ent[0] is ref:
+                table.pop(key, None)
+        with self._ws_lock:
+            if lay is not None:
+                table[id(ws)] = (weakref.ref(ws, gone), lay)
+                if cached:
+                    self._fb_cached = weakref.ref(ws)
+            else:
+                table.pop(id(ws), None)
+
+    def _fallback_layout(self, n, om, dmode, npts, fo, fallback_faces):
+        """Byte offsets (fallback_counts, fallback_rows, cand_redo) and the budget B of a call's layout, or None where it
+        has no per-face fallback (not the candidate path); looked up once per configuration."""
+        key = (n, om, dmode, npts) + fo.key() + (int(fallback_faces),)
+        lay = self._fb_layouts.get(key)
+        if lay is None and key not in self._fb_layouts:
+            fb = _lib.FallbackOpts.make(fallback_faces)
+            offs = [_lib.load().flm_fcn_workspace_offset_fb(
+                self._arch, nm, n, self.input_height, self.input_width, self.n_classes, self._dt, om, dmode, npts,
+                C.byref(fo), C.byref(fb)) for nm in (b"fallback_counts", b"fallback_rows", b"cand_redo")]
+            lay = None if min(offs) < 0 else tuple(int(o) for o in offs) + (min(int(fallback_faces), n), n)
+            self._fb_layouts[key] = lay
+        return lay
+
+    def _fallback_views(self, workspace):
+        import torch
+        ws = workspace if workspace is not None else (self._fb_cached() if self._fb_cached is not None else None)
+        with self._ws_lock:
+            ent = self._fb_last.get(id(ws)) if ws is not None else None
+        if ent is None or ent[0]() is not ws:
+            raise KeyError("no forward with fallback_faces > 0 on the candidate path has run into this workspace")
+        oc, orow, oredo, b, n = ent[1]
+        return (ws[oc:oc + 16].view(torch.int32), ws[orow:orow + 4 * b].view(torch.int32),
+                ws[oredo:oredo + 4 * n].view(torch.int32))
+
+    def fallback_counts(self, workspace=None):
+        """int32 [4] CUDA view, no synchronisation, of what the last forward with fallback_faces > 0 into `workspace`
+        (None: the last one that used a cached workspace) did about failed candidate lists: {R faces raised, faces redone
+        per face (R when R <= B, else 0), whole-batch redo taken 0 | 1, B}.  Read it in stream order after that forward.
+        KeyError when no such forward has run (fallback_faces = 0, or the call does not take the candidate path), or when
+        the cached workspace it used has been evicted since.  The model keeps no workspace alive for this.  A batch beyond
+        max_batch runs in slices into one cached workspace: the counts are then those of the LAST slice only."""
+        return self._fallback_views(workspace)[0]
+
+    def fallback_rows(self, workspace=None):
+        """(tests and tools/bench_face_fallback.py) (rows, redo) of that forward: int32 [B], the faces it planned to redo, ascending, -1 from index R on; and
+        int32 [n], 1 where a face's candidate list failed ("fallback_rows" and "cand_redo" of include/flm.h)."""
+        v = self._fallback_views(workspace)
+        return v[1], v[2]
 
     def encoder_layer_names(self):
         """The encoder's layers by their Keras names, in network order: index i is the layer whose output is

@@ -141,7 +141,7 @@ def _aligned_format(aligned_format, numpy_io):
                          % aligned_format.dtype)
 
 
-def predict(crops, model, n_points=4, thresh=0.0, to_input_space=False, return_stats=False):
+def predict(crops, model, n_points=4, thresh=0.0, to_input_space=False, return_stats=False, fallback_faces=0):
     """Batched landmarks: crops [N,H,W,3] (numpy or CUDA tensor; uint8 BGR or float32
     preprocessed) -> float64 [N,C,2] (x,y).
 
@@ -156,6 +156,8 @@ def predict(crops, model, n_points=4, thresh=0.0, to_input_space=False, return_s
     (utils/metrics.py:80); `to_input_space=True` rescales to input-crop pixels
     (x * W / W').  n_points < 1 selects the all-pixel centroid, else top-n (utils/metrics.py:58,66);
     the reference as shipped always runs n_points=4, thresh=0.
+    `fallback_faces` = B > 0 (here, in `align`, in `align_frames` and in `FaceTracker`): the forward redoes only the
+    faces whose candidate lists fail, at most B of them, instead of the whole batch (forward_device; same landmarks).
     Returns the type it was given (numpy -> numpy, CUDA tensor -> CUDA tensor).
     """
     import torch
@@ -165,7 +167,8 @@ def predict(crops, model, n_points=4, thresh=0.0, to_input_space=False, return_s
         raise ValueError("crops must be [N,H,W,3]")
     was_np = not isinstance(crops, torch.Tensor)
     xd = torch.from_numpy(np.ascontiguousarray(crops)).to(_lib.require_gpu()) if was_np else crops
-    rec = model.forward_device(xd, "landmark_stats" if return_stats else "landmarks", n_points=n_points, thresh=thresh)
+    rec = model.forward_device(xd, "landmark_stats" if return_stats else "landmarks", n_points=n_points, thresh=thresh,
+                               fallback_faces=fallback_faces)
     if was_np and return_stats:
         rec = rec.cpu()
     lm = rec[..., :2] if return_stats else rec
@@ -183,7 +186,7 @@ def predict(crops, model, n_points=4, thresh=0.0, to_input_space=False, return_s
 
 
 def align(crops, model=None, landmarks=None, template=None, out_size=None, n_points=4, thresh=0.0, weights=None,
-          aligned_format=None):
+          aligned_format=None, fallback_faces=0):
     """Align face crops by the similarity transform that maps their landmarks onto a template.
 
     crops [N,H,W,3] uint8/float32; `landmarks` float64 [N,C,2] in output-grid pixels (predicted
@@ -212,10 +215,11 @@ def align(crops, model=None, landmarks=None, template=None, out_size=None, n_poi
         if model is None:
             raise ValueError("align needs either landmarks or a model")
         if isinstance(weights, str):   # "score"
-            rec = model.forward_device(xd, "landmark_stats", n_points=n_points, thresh=thresh)
+            rec = model.forward_device(xd, "landmark_stats", n_points=n_points, thresh=thresh,
+                                       fallback_faces=fallback_faces)
             lm, wd = rec[..., :2], rec[..., 2]
         else:
-            lm = model.forward_device(xd, "landmarks", n_points=n_points, thresh=thresh)
+            lm = model.forward_device(xd, "landmarks", n_points=n_points, thresh=thresh, fallback_faces=fallback_faces)
     else:
         lm = torch.as_tensor(landmarks, dtype=torch.float64).to(dev)
     if weights is not None and not isinstance(weights, str):
@@ -402,7 +406,7 @@ _TEMPLATES = {}   # (landmarks, out_h, out_w, device) -> canonical template on t
 
 
 def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 112), n_points=4, thresh=0.0,
-                 frame_index=None, samples=1, weights=None, aligned_format=None, frame_format=None):
+                 frame_index=None, samples=1, weights=None, aligned_format=None, frame_format=None, fallback_faces=0):
     """The multi-face stream end to end in FRAME coordinates: detector boxes of a group of frames -> aligned faces
     sampled from the frames themselves.
 
@@ -476,10 +480,11 @@ def align_frames(frames, faces_per_frame, model, template=None, out_size=(112, 1
         raise ValueError("template must be [%d,2]" % c)
     wd = None
     if isinstance(weights, str):   # "score"
-        rec = model.forward_device(crops, "landmark_stats", n_points=n_points, thresh=thresh)
+        rec = model.forward_device(crops, "landmark_stats", n_points=n_points, thresh=thresh,
+                                   fallback_faces=fallback_faces)
         lm, wd = rec[..., :2].contiguous(), rec[..., 2]
     else:
-        lm = model.forward_device(crops, "landmarks", n_points=n_points, thresh=thresh)
+        lm = model.forward_device(crops, "landmarks", n_points=n_points, thresh=thresh, fallback_faces=fallback_faces)
         if weights is not None:
             wd = _weights_on_device(weights, k, c, dev)
     lm = alignment.landmarks_to_frame_device(lm, boxes_dev, (model.output_height, model.output_width), (fh, fw))
@@ -706,7 +711,8 @@ class FaceTracker:
     in, and its status (0 or `_lib.TRACK_*` bits); it is allocated by the first seed, step or lost.
 
     model: a landmark model of this package; frame_hw: (H, W) of the frames; out_size, template, samples,
-    aligned_format, frame_format, n_points, thresh: as `align_frames` takes them; weights: None or "score" (the forward
+    aligned_format, frame_format, n_points, thresh, fallback_faces: as `align_frames` takes them (every forward the
+    tracker runs gets the budget; empty slots are zero crops, the faces most likely to need it); weights: None or "score" (the forward
     runs in its "landmark_stats" mode and both fits read the record tensor in place); crop_template float64 [C,2] in
     network-input px: where the landmarks sit in the next crop -- upright, centred, at a fixed scale (default
     `alignment.canonical_template(C, in_h, in_w)`); crop_samples: 1, 2 or 4 samples per axis and crop pixel, for faces
@@ -794,8 +800,12 @@ class FaceTracker:
     def __init__(self, model, frame_hw, capacity, out_size=(112, 112), template=None, crop_template=None, n_points=4,
                  thresh=0.0, weights=None, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"),
                  crop_samples=1, samples=1, aligned_format=None, frame_format=None, smooth=None, associate=None,
-                 best_shot=None, streams=1, pose=None, mesh=None, flow=None, exits=None, views=None):
+                 best_shot=None, streams=1, pose=None, mesh=None, flow=None, fallback_faces=0, exits=None,
+                 views=None):
         import torch
+        if isinstance(fallback_faces, bool) or not isinstance(fallback_faces, (int, np.integer)) or fallback_faces < 0:
+            raise ValueError("fallback_faces must be an integer >= 0 (got %r)" % (fallback_faces,))
+        self.fallback_faces = int(fallback_faces)
         if flow is True:
             flow = alignment.LandmarkFlow()
         elif flow is False:
@@ -1253,8 +1263,9 @@ class FaceTracker:
                                              fmt=self._crop_format, frame_index_dev=src["frame_index"],
                                              boxes_dev=src["boxes"], src=self.frame_format)
         out = "landmarks" if self.weights is None else "landmark_stats"
+        fb = dict(fallback_faces=self.fallback_faces) if self.fallback_faces else {}   # (0: the call as it always was)
         res = model.forward_device(crops, out, n_points=self.n_points, thresh=self.thresh,
-                                   workspace=workspace(int(crops.shape[0]), out))
+                                   workspace=workspace(int(crops.shape[0]), out), **fb)
         lm, wd = (res, None) if self.weights is None else (res[..., :2], res[..., 2])
         return lm, wd, (model.output_height, model.output_width)
 
@@ -1478,7 +1489,8 @@ class FaceTracker:
         if n > self.model.max_batch:
             return None
         if self._ws_active is None:
-            self._ws_active = self.model.new_workspace(min(self.capacity, self.model.max_batch), out, self.n_points)
+            fb = dict(fallback_faces=self.fallback_faces) if self.fallback_faces else {}
+            self._ws_active = self.model.new_workspace(min(self.capacity, self.model.max_batch), out, self.n_points, **fb)
         return self._ws_active
 
     def _stream_dt(self, dt, named):

@@ -231,6 +231,40 @@ int flm_fcn_forward_opts(flm_stream_t stream, int arch, const void* packed_dev, 
 int64_t flm_fcn8_workspace_offset_opts(const char* name, int n, int h, int w, int n_classes, int dtype,
                                        int out_mode, int decode_mode, int n_points, const flm_forward_opts* opts);
 
+/* Per-face fallback of the candidate path (landmark_candidates = 1 above).  One word, cand_cnt[n], guards the whole batch
+ * there: when any face raises it, every face is redone through the materialised probabilities.  With `faces` = B > 0 the
+ * forward records WHICH faces raised (cand_redo), compacts them on the device into at most B rows (fallback_rows) and
+ * redoes only those -- the materialising up3 and the decode run on a batch of B rows whose row r reads face
+ * fallback_rows[r], writes probability row r (the first B rows of "probs") and puts its landmarks at face
+ * fallback_rows[r].  When more than B faces raised, today's whole-batch redo runs instead.  Every launch shape is a host
+ * number; nothing is downloaded.  Landmarks are bit for bit those of faces = 0 in every case.
+ *   faces   0 (default, and NULL): the flm_fcn_*_opts entry points, launch for launch and byte for byte of layout.
+ *           < 0: FLM_ERR_ARG.  > n: n.  Where the call does not take the candidate path (another class count, fcn_32, the
+ *           all-pixel mode, n_points > 32, landmark_candidates = 0, a map of 2^17 pixels or more) the option adds nothing.
+ * The same struct goes to the workspace query and to the forward, as flm_forward_opts does.  Regions it adds, after
+ * cand_cnt (no other name moves), by flm_fcn_workspace_offset_fb:
+ *   "cand_redo"        uint32 [n]: 1 where the face raised (every site that raises cand_cnt[n] sets it)
+ *   "fallback_rows"    int32 [B]: the faces that raised, ascending; -1 from index R on (R > B: the first B of them)
+ *   "fallback_counts"  uint32 [4]: { R faces raised, faces served per face (R when R <= B, else 0), whole-batch redo
+ *                      taken 0 | 1, B }
+ * cand_cnt[0..n-1] and cand_cnt[n] keep their meaning and values.  Profile records: "fallback_plan", "up3_rows",
+ * "decode_rows", then "up3_fallback" and "decode_fallback". */
+typedef struct flm_fallback_opts {
+  uint32_t struct_size;  /* as flm_forward_opts: lets the struct grow */
+  int32_t faces;
+} flm_fallback_opts;
+void flm_fallback_opts_init(flm_fallback_opts* fb);
+size_t flm_fcn_workspace_bytes_fb(int arch, int n, int h, int w, int n_classes, int dtype, int out_mode,
+                                  int decode_mode, int n_points, const flm_forward_opts* opts,
+                                  const flm_fallback_opts* fb);
+int64_t flm_fcn_workspace_offset_fb(int arch, const char* name, int n, int h, int w, int n_classes, int dtype,
+                                    int out_mode, int decode_mode, int n_points, const flm_forward_opts* opts,
+                                    const flm_fallback_opts* fb);
+int flm_fcn_forward_fb(flm_stream_t stream, int arch, const void* packed_dev, const void* x_dev, int in_format,
+                       int n, int h, int w, int n_classes, int dtype, int out_mode, int decode_mode,
+                       int n_points, float thresh, void* out_dev, void* workspace_dev, size_t workspace_bytes,
+                       const flm_forward_opts* opts, const flm_fallback_opts* fb);
+
 /* ---- where every layer's output lies, for every architecture (tests compare layer by layer) ------------------------
  * flm_fcn_workspace_offset_opts: byte offset inside the workspace of a named intermediate of `arch`, or -1 (null or
  * unknown name, unknown architecture, a shape or option struct the workspace query refuses, a tensor this call's layout
