@@ -20,6 +20,9 @@ LIB_PATH = os.path.join(HERE, "libflm_hip.so")
 
 SOURCES = [
     "flm_api.hip",
+    "flm_api_fcn.hip",
+    "flm_api_image.hip",
+    "flm_api_track.hip",
     "flm_pack.hip",
     "flm_enc1.hip",
     "flm_igemm.hip",

@@ -161,6 +161,8 @@ enum KnobId {
 int tuning(KnobId id);  // the knob's current value (relaxed load)
 
 // ---- kernel launchers (each returns FLM_OK or an error) --------------------------------------
+// "The caller" below is the extern "C" entry point: flm_api_fcn.hip (network), flm_api_image.hip (fits, warps, frames,
+// mesh, annotation) or flm_api_track.hip (tracker, quality, pose, views, flow), each through flm_api_checks.h.
 int launch_pack_fcn(hipStream_t s, const flm_fcn_params& p, int C, const Fcn8Pack& L, char* blob);
 
 int launch_enc1(hipStream_t s, const void* x, int in_format, int n, int h, int w, const float* w1p,
@@ -457,8 +459,8 @@ struct TrackExitViewsArgs {
 };
 int launch_track_exit_views(hipStream_t s, const TrackExitViewsArgs& g);
 
-// flm_frames_annotate (flm_annotate.hip); every argument has been checked by the caller (flm_api.hip), which resolves the
-// frame format's defaults and converts the two colours for an NV12 ring
+// flm_frames_annotate (flm_annotate.hip); every argument has been checked by the caller (flm_api_image.hip), which resolves
+// the frame format's defaults and converts the two colours for an NV12 ring
 struct AnnotateArgs {
   uint8_t* frames;
   size_t frame_stride;
@@ -476,11 +478,11 @@ struct AnnotateArgs {
 };
 int launch_frames_annotate(hipStream_t s, const AnnotateArgs& g);
 
-// landmark flow (flm_flow.hip); sizes, options, pointers and overlaps have been checked by the caller (flm_api.hip)
+// landmark flow (flm_flow.hip); sizes, options, pointers and overlaps have been checked by the caller (flm_api_track.hip)
 int launch_flow_pyramid(hipStream_t s, const uint8_t* src, int n, int h, int w, int ch, int levels, uint8_t* pyr);
 
 // the flow tick on rows (flm_flow_rows.hip; flm_flow_rows_dev.h holds the two argument structs); pointers, their pairing,
-// sizes, options and overlaps have been checked by the caller (flm_api.hip), except the sizes launch_track_gather_flow
+// sizes, options and overlaps have been checked by the caller (flm_api_track.hip), except the sizes launch_track_gather_flow
 // names.  launch_landmark_flow_rows is the landmark flow of both calls: flm_landmark_flow passes slot and fb_out null
 struct TrackFlowArgs;
 struct FlowPutArgs;

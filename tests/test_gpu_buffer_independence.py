@@ -17,7 +17,7 @@ Audit by reading, before the first run: the integer fields of the workspaces.  A
 index would steer WRITES, not values, so each was traced to the statement that initialises it in the same call.
 
     field (include/flm.h name)         what it is                                  initialised in the same call by
-    cand_cnt [n] + flag [n]            keys appended per face; overflow flag       hipMemsetAsync, csrc/flm_api.hip forward_impl
+    cand_cnt [n] + flag [n]            keys appended per face; overflow flag       hipMemsetAsync, csrc/flm_api_fcn.hip forward_impl
                                                                                    ("FLM_HIP(hipMemsetAsync(cnt, 0, ...))"),
                                                                                    issued before the three launches that add to it
     cand_sub                           per (face, tile, wave, sampled phase)       csrc/flm_convt.hip convt_kernel, "if (SAMPLE)":

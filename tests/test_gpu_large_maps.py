@@ -2,7 +2,7 @@
 
 Every model class defaults to the reference's geometry, 416 x 608 (networks/fcn.py:167) -> a 424 x 616 map of 261,184
 pixels; the other GPU tests stay at or below 256 x 256 (264 x 264 = 69,696).  Between the two lies the candidate path's
-limit: a candidate key holds the pixel index in 17 bits, so landmark_candidates_enabled (flm_api.hip) and launch_convt
+limit: a candidate key holds the pixel index in 17 bits, so landmark_candidates_enabled (flm_api_fcn.hip) and launch_convt
 (flm_convt.hip) turn the path off from 2^17 output pixels on.  352 x 352 (360 x 360 = 129,600) is the last shape with
 candidate lists, 352 x 384 (360 x 392 = 141,120) the first without.  tests/test_large_maps_host.py sweeps the layout rule
 on the host; here:
@@ -68,7 +68,7 @@ scores equal the oracle bit for bit; all-pixel coordinates differ from numpy's f
 slices equal the single decodes (all-pixel: 0 px).
 
 Fault injection (scratch builds, not committed; wrong values or a refused call only; each run once).  (1) `1 << 17` as
-`1 << 18` in landmark_candidates_enabled (flm_api.hip), launch_convt unchanged: the host sweep fails in all six
+`1 << 18` in landmark_candidates_enabled (flm_api_fcn.hip), launch_convt unchanged: the host sweep fails in all six
 (n_points, type) cases and for the record layout (first at 128 x 960); on the GPU test_first_shape_without_candidate_lists
 fails in both types, and so do test_default_geometry (both types: 261,184 < 2^18, the layout holds lists) and the captured
 pipeline's test -- the forward there is refused by launch_convt ("a map below 2^17 pixels"); the 352 x 352 cases, the layer

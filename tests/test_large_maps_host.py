@@ -1,6 +1,6 @@
 """Host arithmetic of the workspace layout around the candidate path's map-size limit (no GPU: size and offset queries).
 
-The candidate key is order_bits(p) << 32 | class << 17 | pixel: 17 bits of pixel index.  The layout (flm_api.hip,
+The candidate key is order_bits(p) << 32 | class << 17 | pixel: 17 bits of pixel index.  The layout (flm_api_fcn.hip,
 landmark_candidates_enabled) therefore holds candidate buffers only while the OUTPUT map, (h + 8) x (w + 8), has fewer
 than 2^17 pixels -- 352 x 352 (360 x 360 = 129,600) is the largest square input that has them, 352 x 384 (360 x 392 =
 141,120) and the default 416 x 608 geometry (424 x 616 = 261,184) have none.  Swept here over every input size in
