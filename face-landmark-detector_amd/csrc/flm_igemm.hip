@@ -44,9 +44,15 @@
 // costs 1.5 % of a layer).  Per-tile cost (timing only, results wrong; profiles/igemm_tile_cost.json): 32 the workgroup returns
 // after the k-loop and its closing sums, no write-out; 64 the LEAN = false set-up takes its rows apart with shifts and
 // assumes every tap in bounds -- no division, no tap-mask loop.
+// Bits 7-8: where a step's operand requests stand among the MFMAs behind the barrier (profiles/igemm_request_spread.json) --
+// 0 as shipped: one request behind each of the first eight MFMAs (64-row form: six); 1 (128) one per two MFMAs of group 3;
+// 2 (256) the placement up to then: (A, B) pairs back to back behind the four MFMA quads of group 3; 3 (384) one per four
+// MFMAs over group 3 and the next step's group 0 (a quarter of a step less cover).  Same requests into the same stages,
+// waited for at the same barrier: results are right in all four.
 #ifndef FLM_IGEMM_VAR
 #define FLM_IGEMM_VAR 0
 #endif
+#define FLM_IGEMM_REQ ((FLM_IGEMM_VAR >> 7) & 3)
 
 namespace flm {
 
@@ -321,7 +327,11 @@ __global__ __launch_bounds__(256, BMT == BM ? 2 : FLM_IGEMM_ROWS64_WAVES) void i
   // The 128 registers of the two extra sets are the staging registers of the other form and its slack: operands reach
   // LDS by buffer_load_dwordx4 ... lds (flm_igemm_args.h), zero padding by the buffer bounds check.  Tile t+2 is
   // requested in group 3 of step t, into the stage that step's barrier has just retired, and waited for (vmcnt(0)) at
-  // the barrier of step t+1: three quarters of a step (3,072 MFMA cycles) of cover.
+  // the barrier of step t+1: three quarters of a step (3,072 MFMA cycles) of cover.  The requests go out ONE per MFMA,
+  // behind the first eight MFMAs after the barrier (64-row form: six), each MFMA and each request pinned: every M0 write
+  // and its wait state fall into a gap of their own.  In (A, B) pairs back to back behind every fourth MFMA the layers
+  // ran 0.8-3 % slower; one per two MFMAs, or the second half a quarter of a step later, times the same as this
+  // (FLM_IGEMM_VAR bits 7-8; profiles/igemm_request_spread.json).
   // The third level is 128 VALU instructions behind a wave-uniform branch right after the barrier of a group's first
   // step (no LDS read is in flight there: at the end of the step the branch cost an lgkmcnt(0) per step, 3 % of the
   // layer).  The second level costs no matrix time: the first slot of a step adds each tile's accumulators to the second
@@ -379,6 +389,19 @@ __global__ __launch_bounds__(256, BMT == BM ? 2 : FLM_IGEMM_ROWS64_WAVES) void i
     dma_load16(xdma, dma_a + (STG) * (TILE_A * 4) + (J) * 32 * 128, ok_ ? rowoff[J] : kOobOffset, ld_delta); \
   }
 #define FLM_DMA_B(J, STG) dma_load16(wdma, dma_b + (STG) * (TILE_F * 4) + (J) * 32 * 128, wrow0, (J) * wstep + ld_koff);
+  // request N of a step: A0 B0 A1 B1 A2 B2 A3 B3; 64-row form: A0 B0 A1 B1 B2 B3; N < 0: none
+#define FLM_REQ(N, STG)                                                                                     \
+  if constexpr (!(FLM_IGEMM_VAR & 8) && (N) >= 0) {                                                         \
+    constexpr int n_ = (N), j_ = (HALF && n_ >= 4) ? n_ - 2 : n_ / 2;                                       \
+    constexpr bool b_ = HALF && n_ >= 4 ? true : (n_ & 1) != 0;                                             \
+    if constexpr (!b_ && j_ == 0) FLM_DMA_A(0, STG)                                                         \
+    if constexpr (!b_ && j_ == 1) FLM_DMA_A(1, STG)                                                         \
+    if constexpr (!b_ && j_ == 2) FLM_DMA_A(2, STG)                                                         \
+    if constexpr (!b_ && j_ == 3) FLM_DMA_A(3, STG)                                                         \
+    if constexpr (b_ && j_ < 4) FLM_DMA_B(j_, STG)                                                          \
+    __builtin_amdgcn_sched_barrier(0);                                                                      \
+  }
+#define FLM_RQ(N128, N64) (HALF ? (N64) : (N128))
 #define FLM_READ_FRAGS(AF0, AF1, BF0, BF1, T, STG)                                                          \
   {                                                                                                         \
     int oa_ = off_a, ob_ = off_b;                                                                           \
@@ -400,6 +423,17 @@ __global__ __launch_bounds__(256, BMT == BM ? 2 : FLM_IGEMM_ROWS64_WAVES) void i
 #define FLM_MFMA4(AF0, AF1, BF0, BF1, E)                                                     \
   mfma_slot<false, FLM_SLOT_##E, HALF>(AF0, AF1, BF0, BF1, acc00, acc01, acc10, acc11);      \
   __builtin_amdgcn_sched_barrier(0);
+  // the four MFMAs of FLM_MFMA4, each pinned, with request R0..R3 behind the first..fourth
+#define FLM_MFMA1(ACC, AV, BV, E)                                                            \
+  ACC = __builtin_amdgcn_mfma_f32_32x32x2f32(f4c(AV, FLM_SLOT_##E), f4c(BV, FLM_SLOT_##E), ACC, 0, 0, 0); \
+  __builtin_amdgcn_sched_barrier(0);
+#define FLM_MFMA4R(AF0, AF1, BF0, BF1, E, R0, R1, R2, R3, STG)                               \
+  FLM_MFMA1(acc00, AF0, BF0, E) FLM_REQ(R0, STG)                                             \
+  FLM_MFMA1(acc01, AF0, BF1, E) FLM_REQ(R1, STG)                                             \
+  if constexpr (!HALF) {                                                                     \
+    FLM_MFMA1(acc10, AF1, BF0, E) FLM_REQ(R2, STG)                                           \
+    FLM_MFMA1(acc11, AF1, BF1, E) FLM_REQ(R3, STG)                                           \
+  }
   // first slot of a step: close the previous step tile by tile and restart the tile from C = 0
 #define FLM_FLUSH1(SUM, ACC, AV, BV)                                                         \
   SUM += ACC;                                                                                \
@@ -416,14 +450,16 @@ __global__ __launch_bounds__(256, BMT == BM ? 2 : FLM_IGEMM_ROWS64_WAVES) void i
   // One step on stage BUF (compile-time).
 #define FLM_STEP2(BUF)                                                                                \
   {                                                                                                   \
-    FLM_TILE_PARAMS()                                                                                 \
+    if constexpr (FLM_IGEMM_REQ != 3) FLM_TILE_PARAMS()                                               \
     __builtin_amdgcn_sched_barrier(0);                                                                \
     /* group 0 (fragments fetched during the previous step's group 3) */                              \
-    FLM_MFMA4_FLUSH(afx0, afx1, bfx0, bfx1)                                                           \
+    /* (placement 3: the second half of the previous step's requests, into the stage that step retired) */\
+    FLM_MFMA4_FLUSH(afx0, afx1, bfx0, bfx1) if constexpr (FLM_IGEMM_REQ == 3) FLM_REQ(4, (BUF) ^ 1)   \
     FLM_READ_FRAGS(afy0, afy1, bfy0, bfy1, 1, BUF)                                                    \
-    FLM_MFMA4(afx0, afx1, bfx0, bfx1, y)                                                              \
-    FLM_MFMA4(afx0, afx1, bfx0, bfx1, z)                                                              \
-    FLM_MFMA4(afx0, afx1, bfx0, bfx1, w)                                                              \
+    FLM_MFMA4(afx0, afx1, bfx0, bfx1, y) if constexpr (FLM_IGEMM_REQ == 3) FLM_REQ(5, (BUF) ^ 1)      \
+    FLM_MFMA4(afx0, afx1, bfx0, bfx1, z) if constexpr (FLM_IGEMM_REQ == 3) FLM_REQ(FLM_RQ(6, -1), (BUF) ^ 1)\
+    FLM_MFMA4(afx0, afx1, bfx0, bfx1, w) if constexpr (FLM_IGEMM_REQ == 3) FLM_REQ(FLM_RQ(7, -1), (BUF) ^ 1)\
+    if constexpr (FLM_IGEMM_REQ == 3) FLM_TILE_PARAMS()                                               \
     /* group 1 */                                                                                     \
     FLM_MFMA4(afy0, afy1, bfy0, bfy1, x) FLM_READ_FRAGS(afx0, afx1, bfx0, bfx1, 2, BUF)               \
     FLM_MFMA4(afy0, afy1, bfy0, bfy1, y)                                                              \
@@ -448,7 +484,26 @@ __global__ __launch_bounds__(256, BMT == BM ? 2 : FLM_IGEMM_ROWS64_WAVES) void i
       }                                                                                               \
     }                                                                                                 \
     /* group 3: the next step's first fragments come from the next stage; tile it+2 is requested into this one */ \
-    {                                                                                                 \
+    if constexpr (FLM_IGEMM_REQ == 1) { /* one request per two MFMAs (64-row form: per MFMA) */       \
+      FLM_MFMA4R(afy0, afy1, bfy0, bfy1, x, FLM_RQ(-1, 0), FLM_RQ(0, 1), -1, 1, BUF)                  \
+      FLM_READ_FRAGS(afx0, afx1, bfx0, bfx1, 0, (BUF) ^ 1)                                            \
+      FLM_MFMA4R(afy0, afy1, bfy0, bfy1, y, FLM_RQ(-1, 2), FLM_RQ(2, 3), -1, 3, BUF)                  \
+      FLM_MFMA4R(afy0, afy1, bfy0, bfy1, z, FLM_RQ(-1, 4), FLM_RQ(4, 5), -1, 5, BUF)                  \
+      FLM_MFMA4R(afy0, afy1, bfy0, bfy1, w, -1, FLM_RQ(6, -1), -1, 7, BUF)                            \
+    } else if constexpr (FLM_IGEMM_REQ == 0) { /* shipped: one request per MFMA from the barrier on */\
+      FLM_MFMA4R(afy0, afy1, bfy0, bfy1, x, 0, 1, 2, 3, BUF)                                          \
+      FLM_READ_FRAGS(afx0, afx1, bfx0, bfx1, 0, (BUF) ^ 1)                                            \
+      FLM_MFMA4R(afy0, afy1, bfy0, bfy1, y, FLM_RQ(4, 2), FLM_RQ(5, 3), 6, 7, BUF)                    \
+      FLM_MFMA4R(afy0, afy1, bfy0, bfy1, z, FLM_RQ(-1, 4), FLM_RQ(-1, 5), -1, -1, BUF)                \
+      FLM_MFMA4(afy0, afy1, bfy0, bfy1, w)                                                            \
+    } else if constexpr (FLM_IGEMM_REQ == 3) { /* one request per four MFMAs; the rest in the next step's group 0 */\
+      FLM_MFMA4(afy0, afy1, bfy0, bfy1, x)                                                            \
+      FLM_READ_FRAGS(afx0, afx1, bfx0, bfx1, 0, (BUF) ^ 1)                                            \
+      FLM_REQ(0, BUF)                                                                                 \
+      FLM_MFMA4(afy0, afy1, bfy0, bfy1, y) FLM_REQ(1, BUF)                                            \
+      FLM_MFMA4(afy0, afy1, bfy0, bfy1, z) FLM_REQ(2, BUF)                                            \
+      FLM_MFMA4(afy0, afy1, bfy0, bfy1, w) FLM_REQ(3, BUF)                                            \
+    } else { /* (A, B) pairs behind the four MFMA quads: the placement before this one */             \
       FLM_MFMA4(afy0, afy1, bfy0, bfy1, x)                                                            \
       FLM_READ_FRAGS(afx0, afx1, bfx0, bfx1, 0, (BUF) ^ 1)                                            \
       if (!(FLM_IGEMM_VAR & 8)) { FLM_DMA_A(0, BUF) FLM_DMA_B(0, BUF) }                               \
@@ -502,6 +557,10 @@ __global__ __launch_bounds__(256, BMT == BM ? 2 : FLM_IGEMM_ROWS64_WAVES) void i
 #undef FLM_DMA_B
 #undef FLM_READ_FRAGS
 #undef FLM_MFMA4
+#undef FLM_MFMA1
+#undef FLM_MFMA4R
+#undef FLM_REQ
+#undef FLM_RQ
 #undef FLM_FLUSH1
 #undef FLM_MFMA4_FLUSH
 #undef FLM_SLOT_x
