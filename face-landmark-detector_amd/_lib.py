@@ -18,6 +18,9 @@ OUT_PROBS, OUT_CLASSMAP, OUT_LANDMARKS, OUT_LOGITS, OUT_LANDMARKS_STATS = 0, 1, 
 LANDMARK_REC = 6  # FLM_LANDMARK_REC: x, y, score, var_x, var_y, cov_xy
 QUALITY_REC = 8   # FLM_QUALITY_REC: n_pix, sum Y, sum Y*Y, n_lap, sum L, sum L*L, dark, bright
 POSE_REC = 18     # FLM_POSE_REC: R row by row, s, mx, my, rms, cnt, ok, yaw, pitch, roll
+PARTS_MAX, PART_MAX_POINTS, PART_MAX_SIDE = 8, 32, 256   # FLM_PARTS_MAX, FLM_PART_MAX_POINTS, FLM_PART_MAX_SIDE
+OPEN_REC, OPEN_STATE = 4, 8                              # FLM_OPEN_REC: o, dw, ok, sum; FLM_OPEN_STATE
+OPEN_MAX_MEASURES, OPEN_MAX_PAIRS = 8, 4                 # FLM_OPEN_MAX_MEASURES, FLM_OPEN_MAX_PAIRS
 DECODE_ALL, DECODE_TOPN = 0, 1
 NORM_SUB_MEAN, NORM_SUB_AND_DIVIDE, NORM_DIVIDE = 0, 1, 2
 ABI_VERSION = 2
@@ -57,6 +60,7 @@ EXPORTS = [
     "flm_quality_opts_init", "flm_face_quality", "flm_best_opts_init", "flm_track_best_update",
     "flm_track_gather_streams", "flm_track_step_rows", "flm_track_best_update_rows", "flm_track_gather_live",
     "flm_pose_opts_init", "flm_head_pose",
+    "flm_part_affines", "flm_warp_parts_frames", "flm_open_opts_init", "flm_face_openness",
     "flm_exit_opts_init", "flm_track_retire",
     "flm_views_opts_init", "flm_track_views_update", "flm_track_exit_views",
     "flm_annotate_opts_init", "flm_bgr_to_yuv", "flm_frames_annotate",
@@ -216,6 +220,33 @@ class PoseOpts(C.Structure):
         load().flm_pose_opts_init(C.byref(o))
         o.min_volume = float(min_volume)
         o.min_frontal = float(min_frontal)
+        return o
+
+
+class OpenOpts(C.Structure):
+    """flm_open_opts: the measures and thresholds of flm_face_openness (include/flm.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n_measures", C.c_int32),
+                ("n_pairs", C.c_int32 * OPEN_MAX_MEASURES), ("width", (C.c_int32 * 2) * OPEN_MAX_MEASURES),
+                ("upper", (C.c_int32 * OPEN_MAX_PAIRS) * OPEN_MAX_MEASURES),
+                ("lower", (C.c_int32 * OPEN_MAX_PAIRS) * OPEN_MAX_MEASURES),
+                ("close_below", C.c_double), ("open_above", C.c_double), ("min_closed", C.c_double),
+                ("max_closed", C.c_double), ("min_width", C.c_double)]
+
+    @classmethod
+    def make(cls, measures=None, **numbers):
+        """measures: None (the library's defaults) or a sequence of ((a, b), ((u, l), ...)); numbers: the five doubles."""
+        o = cls()
+        load().flm_open_opts_init(C.byref(o))
+        if measures is not None:
+            o.n_measures = len(measures)
+            for g in range(OPEN_MAX_MEASURES):
+                (a, b), pairs = measures[g] if g < len(measures) else ((0, 0), ())
+                o.n_pairs[g] = len(pairs)
+                o.width[g][0], o.width[g][1] = int(a), int(b)
+                for v in range(OPEN_MAX_PAIRS):
+                    o.upper[g][v], o.lower[g][v] = [int(x) for x in pairs[v]] if v < len(pairs) else (0, 0)
+        for name, v in numbers.items():
+            setattr(o, name, float(v))
         return o
 
 
@@ -479,6 +510,15 @@ def _declare(lib):
     lib.flm_pose_opts_init.argtypes = [C.POINTER(PoseOpts)]
     lib.flm_head_pose.restype = i
     lib.flm_head_pose.argtypes = [vp, vp, sz, vp, sz, i, i, vp, vp, i, C.POINTER(PoseOpts), vp, i, vp, vp]
+    lib.flm_part_affines.restype = i
+    lib.flm_part_affines.argtypes = [vp, vp, sz, vp, sz, i, i, vp, vp, C.POINTER(C.c_int32), i, vp, vp]
+    lib.flm_warp_parts_frames.restype = i
+    lib.flm_warp_parts_frames.argtypes = [vp, vp, sz, i, i, i, vp, vp, vp, sz, vp, sz, i, vp, vp, C.POINTER(C.c_int32), i, i,
+                                          vp, i, i, i, C.POINTER(ImageFormat), C.POINTER(FrameFormat), vp, vp]
+    lib.flm_open_opts_init.restype = None
+    lib.flm_open_opts_init.argtypes = [C.POINTER(OpenOpts)]
+    lib.flm_face_openness.restype = i
+    lib.flm_face_openness.argtypes = [vp, vp, sz, vp, sz, i, i, C.POINTER(OpenOpts), vp, i, vp, vp, vp, vp, d, vp, C.c_int64]
     lib.flm_exit_opts_init.restype = None
     lib.flm_exit_opts_init.argtypes = [C.POINTER(ExitOpts)]
     lib.flm_track_retire.restype = i

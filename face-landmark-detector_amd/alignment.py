@@ -1694,6 +1694,309 @@ def head_pose_device(lm, model, weights=None, opts=None, slot=None, out=None, fa
     return out
 
 
+# ---- face parts: eye and mouth patches, openness and blink state (include/flm.h, "face parts", "openness") -------------
+OPEN_REC, OPEN_STATE = _lib.OPEN_REC, _lib.OPEN_STATE
+PART_FILL = 0.8   # FaceParts.default: the share of the patch's width that the part's width fills (an unmeasured guess)
+
+
+class FaceParts:
+    """A set of face parts for flm_part_affines / flm_warp_parts_frames: R parts, 1 <= R <= 8, each `indices[r]`, 2 to 32
+    landmark numbers, and `templates[r]`, float64 [len(indices[r]),2], where those landmarks belong in PATCH pixels
+    (x, y); `size` = (patch_h, patch_w), 1 to 256 each, one size for all parts.  A part is fitted over its points in the
+    order given; an index may repeat.  The device tensors are uploaded once per device and cached."""
+
+    def __init__(self, indices, templates, size):
+        idx = [np.asarray(v) for v in indices]
+        tm = [np.asarray(t, np.float64) for t in templates]
+        if not 1 <= len(idx) <= _lib.PARTS_MAX or len(tm) != len(idx):
+            raise ValueError("a set of parts has 1 to %d parts, one template per part" % _lib.PARTS_MAX)
+        for v, t in zip(idx, tm):
+            if v.ndim != 1 or v.dtype.kind not in "iu" or not 2 <= v.shape[0] <= _lib.PART_MAX_POINTS:
+                raise ValueError("a part is 2 to %d integer landmark indices" % _lib.PART_MAX_POINTS)
+            if v.min() < 0 or v.max() >= 2 ** 31:
+                raise ValueError("a landmark index must be in [0, 2^31)")
+            if t.shape != (v.shape[0], 2) or not np.isfinite(t).all():
+                raise ValueError("the template of a part is finite float64 [points,2]")
+        ph, pw = _sizes(size, "the patch size")
+        if ph > _lib.PART_MAX_SIDE or pw > _lib.PART_MAX_SIDE:
+            raise ValueError("a patch is at most %d x %d (got %dx%d)" % (_lib.PART_MAX_SIDE, _lib.PART_MAX_SIDE, ph, pw))
+        r = len(idx)
+        self.size = (ph, pw)
+        self.counts = np.array([v.shape[0] for v in idx], np.int32)
+        self.indices = np.full((r, _lib.PART_MAX_POINTS), -1, np.int32)
+        self.templates = np.zeros((r, _lib.PART_MAX_POINTS, 2), np.float64)
+        for i, (v, t) in enumerate(zip(idx, tm)):
+            self.indices[i, :v.shape[0]] = v
+            self.templates[i, :v.shape[0]] = t
+        for a in (self.counts, self.indices, self.templates):
+            a.setflags(write=False)
+        self._dev, self._counts_arg = {}, None
+
+    @classmethod
+    def default(cls, n_landmarks, size=(32, 48)):
+        """The right eye (36-41), the left eye (42-47) and the mouth (48-67) of the 68-landmark layout.  Each part's
+        template is the part's points of `canonical_template`, scaled by one factor and centred in the patch so that the
+        part's WIDTH fills PART_FILL = 0.8 of the patch's width; the factor, like the default size, is an unmeasured guess."""
+        if int(n_landmarks) != 68:
+            raise ValueError("the default face parts are defined for 68 landmarks; pass an alignment.FaceParts for %d"
+                             % int(n_landmarks))
+        ph, pw = _sizes(size, "the patch size")
+        base = canonical_template(68, 2, 2)   # the unit square
+        idx, tm = [], []
+        for lo, hi in ((36, 42), (42, 48), (48, 68)):
+            p = base[lo:hi]
+            mn, mx = p.min(axis=0), p.max(axis=0)
+            s = PART_FILL * (pw - 1) / (mx[0] - mn[0])
+            tm.append((p - (mn + mx) / 2) * s + np.array([(pw - 1) / 2, (ph - 1) / 2]))
+            idx.append(np.arange(lo, hi))
+        return cls(idx, tm, (ph, pw))
+
+    def __len__(self):
+        return int(self.counts.shape[0])
+
+    def part(self, r):
+        """(indices int32 [n], template float64 [n,2]) of part r, as given."""
+        n = int(self.counts[r])
+        return self.indices[r, :n].copy(), self.templates[r, :n].copy()
+
+    def tensors(self, device):
+        """(indices int32 [R,32], templates float64 [R,32,2]) on `device`."""
+        import torch
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = (torch.from_numpy(self.indices.copy()).to(device), torch.from_numpy(self.templates.copy()).to(device))
+        return self._dev[key]
+
+    def counts_arg(self):
+        """The host array `part_n` of the C calls, made once: the calls only read it."""
+        if self._counts_arg is None:
+            self._counts_arg = (_lib.C.c_int32 * len(self))(*[int(v) for v in self.counts])
+        return self._counts_arg
+
+    def __repr__(self):
+        return "FaceParts(%d parts of %s points, %dx%d)" % (len(self), list(self.counts), self.size[0], self.size[1])
+
+
+def _check_parts(parts):
+    if not isinstance(parts, FaceParts):
+        raise ValueError("parts must be an alignment.FaceParts (got %r)" % (parts,))
+
+
+def part_affines_device(lm, parts, weights=None, out=None, ok_out=None):
+    """lm: CUDA float64 [K,C,2] frame-space landmarks and `weights` None or CUDA float64 [K,C] (both may be views of a
+    landmark record tensor, read in place); parts: a `FaceParts` -> (CUDA float32 [K,R,2,3], the similarity frame px ->
+    patch px of every part of every face, fitted to the part's own landmarks; CUDA int32 [K,R], 1 where the fit had two
+    participating points or more and a positive variance -- elsewhere the matrix is the identity) (flm_part_affines)."""
+    import torch
+    _check_parts(parts)
+    lm, ls = _strided_points(lm)
+    k, c, r = int(lm.shape[0]), int(lm.shape[1]), len(parts)
+    weights, wst = _weights_arg(weights, k, c)
+    if out is None:
+        out = torch.empty((k, r, 2, 3), dtype=torch.float32, device=lm.device)
+    else:
+        _check_out(out, torch.float32, (k, r, 2, 3), "out")
+    ok_out = _out(ok_out, torch.int32, (k, r), "ok_out", lm.device)
+    if k and c:
+        idx, tm = parts.tensors(lm.device)
+        _lib.check(_lib.load().flm_part_affines(_lib.stream_ptr(), _lib.ptr(lm), ls, _ptr(weights), wst, k, c, _lib.ptr(idx),
+                                                _lib.ptr(tm), parts.counts_arg(), r, _lib.ptr(out), _lib.ptr(ok_out)),
+                   "flm_part_affines")
+    return out, ok_out
+
+
+def warp_parts_frames_device(frames, lm, parts, weights=None, frame_index_dev=None, boxes_dev=None, samples=1, fmt=None,
+                             src=None, out=None, affines_out=None, ok_out=None):
+    """The patches of every part of every face in one launch (flm_warp_parts_frames): each part is cut from the frame
+    under the similarity that takes the part's own landmarks onto its template.  frames, frame_index_dev, boxes_dev,
+    samples, fmt, src: as warp_frames_device takes them (and with its result for a ring slot outside the ring and an empty
+    box: a zero face); lm, weights, parts: as part_affines_device takes them.  Returns CUDA [K,R,ph,pw,3] float32, or
+    [K,R] faces in `fmt`; `out`, when given, has that shape.  affines_out: None or contiguous CUDA float32 [K,R,2,3];
+    ok_out: None or contiguous CUDA int32 [K,R]: they receive what part_affines_device returns.  A part whose fit is not
+    ok gives a zero face.  Patch (f, r) has the bits warp_frames_device gives with m = affines[:, r] at the patch size."""
+    import torch
+    _check_parts(parts)
+    if fmt is not None:
+        _check_format(fmt)
+    if src is not None:
+        _check_frame_format(src)
+        ring = src.ring(frames)
+    elif (not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8
+            or not frames.is_cuda or not frames.is_contiguous()):
+        raise ValueError("frames must be a contiguous CUDA uint8 [F,H,W,3] tensor")
+    lm, ls = _strided_points(lm)
+    k, c, r = int(lm.shape[0]), int(lm.shape[1]), len(parts)
+    weights, wst = _weights_arg(weights, k, c)
+    if lm.device != frames.device:
+        raise ValueError("lm must be on the device of frames (%s, got %s)" % (frames.device, lm.device))
+    if samples not in (1, 2, 4):
+        raise ValueError("samples must be 1, 2 or 4")
+    ph, pw = parts.size
+    if src is not None:
+        nf, fh, fw, stride = ring
+    else:
+        nf, fh, fw = [int(v) for v in frames.shape[:3]]
+        stride = fh * fw * 3
+    if frame_index_dev is not None:
+        _check_out(frame_index_dev, torch.int32, (k,), "frame_index_dev")
+    if boxes_dev is not None:
+        _check_boxes(boxes_dev, k)
+    ofmt = fmt if fmt is not None else AlignedFormat()
+    shape = (k, r) + tuple(ofmt.shape(1, ph, pw)[1:])
+    if out is None:
+        out = torch.empty(shape, dtype=ofmt.torch_dtype, device=frames.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != ofmt.torch_dtype or tuple(out.shape) != shape or not out.is_cuda
+          or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous CUDA %s tensor of shape %s" % (ofmt.dtype, list(shape)))
+    if affines_out is not None:
+        _check_out(affines_out, torch.float32, (k, r, 2, 3), "affines_out")
+    if ok_out is not None:
+        _check_out(ok_out, torch.int32, (k, r), "ok_out")
+    if not k or not c:
+        return out
+    idx, tm = parts.tensors(frames.device)
+    cf = None if fmt is None else fmt.struct()
+    cs = None if src is None else src.struct(frames)
+    _lib.check(_lib.load().flm_warp_parts_frames(
+        _lib.stream_ptr(), _lib.ptr(frames), stride, nf, fh, fw, _ptr(frame_index_dev), _ptr(boxes_dev), _lib.ptr(lm), ls,
+        _ptr(weights), wst, c, _lib.ptr(idx), _lib.ptr(tm), parts.counts_arg(), r, k, _lib.ptr(out), ph, pw, int(samples),
+        None if cf is None else _lib.C.byref(cf), None if cs is None else _lib.C.byref(cs), _ptr(affines_out),
+        _ptr(ok_out)), "flm_warp_parts_frames")
+    return out
+
+
+class Openness:
+    """The measures and thresholds of flm_face_openness (include/flm.h).  measures: a sequence of 1 to 8 entries
+    ((a, b), ((u, l), ...)) -- the width pair of landmarks and 1 to 4 pairs across the opening -- or None for
+    `Openness.default(68)`'s; close_below < open_above: the hysteresis of the closed state; min_closed <= max_closed:
+    the closures that count as an event, in the unit of dt; min_width: the least width in frame px at which a measure is
+    read; dt: the time step a FaceTracker without `smooth` gives every tick (one with `smooth` uses the step's own).
+    THE FIVE DEFAULT NUMBERS ARE UNMEASURED GUESSES: no trained checkpoint and no labelled blink data stand behind them."""
+
+    DEFAULT_MEASURES = (((36, 39), ((37, 41), (38, 40))), ((42, 45), ((43, 47), (44, 46))),
+                        ((60, 64), ((61, 67), (62, 66), (63, 65))))
+
+    def __init__(self, measures=None, close_below=0.18, open_above=0.22, min_closed=0.03, max_closed=0.5, min_width=4.0,
+                 dt=1.0 / 30.0):
+        import math
+        if measures is None:
+            measures = self.DEFAULT_MEASURES
+        try:
+            ms = tuple(((int(a), int(b)), tuple((int(u), int(l)) for u, l in pairs)) for (a, b), pairs in measures)
+        except (TypeError, ValueError):
+            raise ValueError("a measure is ((a, b), ((u, l), ...)): a width pair and 1 to 4 pairs of landmark indices") from None
+        if not 1 <= len(ms) <= _lib.OPEN_MAX_MEASURES or any(not 1 <= len(p) <= _lib.OPEN_MAX_PAIRS for _, p in ms):
+            raise ValueError("openness takes 1 to %d measures of 1 to %d pairs each" % (_lib.OPEN_MAX_MEASURES, _lib.OPEN_MAX_PAIRS))
+        if any(not -2 ** 31 <= v < 2 ** 31 for (a, b), p in ms for v in (a, b) + tuple(x for q in p for x in q)):
+            raise ValueError("a landmark index must fit int32")
+        close_below, open_above, min_closed, max_closed, min_width, dt = [
+            float(v) for v in (close_below, open_above, min_closed, max_closed, min_width, dt)]
+        if not close_below < open_above:
+            raise ValueError("close_below must be below open_above (got %r, %r)" % (close_below, open_above))
+        if not (min_closed >= 0.0 and max_closed >= 0.0 and min_width >= 0.0):
+            raise ValueError("min_closed, max_closed and min_width must be >= 0")
+        if max_closed < min_closed:
+            raise ValueError("max_closed must not be below min_closed")
+        if not (dt > 0.0 and math.isfinite(dt)):
+            raise ValueError("dt must be finite and > 0 (got %r)" % dt)
+        self.measures = ms
+        self.close_below, self.open_above, self.min_closed, self.max_closed = close_below, open_above, min_closed, max_closed
+        self.min_width, self.dt = min_width, dt
+        self._struct = None
+
+    @classmethod
+    def default(cls, n_landmarks, **kw):
+        """Both eyes and the inner mouth of the 68-landmark layout: right eye, width (36,39), pairs (37,41) (38,40); left
+        eye, width (42,45), pairs (43,47) (44,46); inner mouth, width (60,64), pairs (61,67) (62,66) (63,65)."""
+        if int(n_landmarks) != 68:
+            raise ValueError("the default openness measures are defined for 68 landmarks; pass an alignment.Openness for %d"
+                             % int(n_landmarks))
+        return cls(cls.DEFAULT_MEASURES, **kw)
+
+    def __len__(self):
+        return len(self.measures)
+
+    def struct(self):
+        """The flm_open_opts of these options, made once: the calls only read it."""
+        if self._struct is None:
+            self._struct = _lib.OpenOpts.make(self.measures, close_below=self.close_below, open_above=self.open_above,
+                                              min_closed=self.min_closed, max_closed=self.max_closed,
+                                              min_width=self.min_width)
+        return self._struct
+
+    def __repr__(self):
+        return ("Openness(%d measures, close_below=%r, open_above=%r, min_closed=%r, max_closed=%r, min_width=%r)"
+                % (len(self), self.close_below, self.open_above, self.min_closed, self.max_closed, self.min_width))
+
+
+OPEN_STATE_EMPTY = (0.0, 0.0, 0.0, -1.0, 0.0, 0.0, -1.0, 0.0)   # the state of a measure after a reset
+
+
+def face_openness_device(lm, opts=None, weights=None, slot=None, out=None, state=None, reset=None, dt=None,
+                         status_rows=None, frame_id=0):
+    """How open the eyes and the mouth of N faces are, and their closure counts, in one launch (flm_face_openness;
+    include/flm.h states it line by line).
+
+    lm: CUDA float64 [N,C,2] and `weights` None or CUDA float64 [N,C] (views of a landmark record tensor are read in
+    place); opts: None (`Openness()`) or an `Openness` of G measures.  slot: None -- `out` is float64 [N,G,4] and row r
+    writes record r -- or CUDA int32 [N]: `out`, required, is float64 [n_slots,G,4], a row writes at its slot, an inert
+    row writes nothing and a slot no row names keeps its bits.  state: None, or contiguous CUDA float64 [N or n_slots,G,8],
+    updated in place, with `reset` CUDA int32 [N or n_slots] (a non-zero flag empties the slot's state first and is
+    cleared by the call), dt: a host number or a CUDA float64 [N] tensor by row (None: the Openness's dt), status_rows:
+    None or CUDA int32 [N] (a row whose status is not 0 leaves its state alone) and frame_id.  Returns `out`:
+    {openness or -1, width, ok, sum} per face and measure."""
+    import torch
+    if opts is None:
+        opts = Openness()
+    elif not isinstance(opts, Openness):
+        raise ValueError("opts must be None or an alignment.Openness (got %r)" % (opts,))
+    lm, ls = _strided_points(lm)
+    n, c, g = int(lm.shape[0]), int(lm.shape[1]), len(opts)
+    weights, wst = _weights_arg(weights, n, c)
+    if slot is None:
+        out = _out(out, torch.float64, (n, g, OPEN_REC), "out", lm.device)
+        rows, n_slots = n, 0
+    else:
+        _check_out(slot, torch.int32, (n,), "slot")
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or out.dim() != 3
+                or tuple(out.shape[1:]) != (g, OPEN_REC) or not out.is_cuda or not out.is_contiguous()
+                or not 1 <= int(out.shape[0]) <= 65535):
+            raise ValueError("with slot, out must be a contiguous CUDA float64 [n_slots,%d,%d] tensor of 1 to 65535 slots"
+                             % (g, OPEN_REC))
+        rows = n_slots = int(out.shape[0])
+    dt_dev, dt_host = None, opts.dt
+    if state is not None:
+        _check_out(state, torch.float64, (rows, g, OPEN_STATE), "state")
+        if reset is None:
+            raise ValueError("state goes with reset, a CUDA int32 [%d] tensor" % rows)
+        _check_out(reset, torch.int32, (rows,), "reset")
+        if isinstance(dt, torch.Tensor):
+            _check_out(dt, torch.float64, (n,), "dt")
+            dt_dev = dt
+        elif dt is not None:
+            dt_host = float(dt)
+            if not (dt_host > 0.0 and dt_host < float("inf")):
+                raise ValueError("dt must be finite and > 0 (got %r)" % (dt,))
+        if status_rows is not None:
+            _check_out(status_rows, torch.int32, (n,), "status_rows")
+    elif reset is not None or dt is not None or status_rows is not None:
+        raise ValueError("reset, dt and status_rows go with state")
+    frame_id = _frame_id(frame_id)
+    outs = [(out, "out"), (state, "state"), (reset, "reset")]
+    for a, what in ((lm, "lm"), (weights, "weights"), (slot, "slot"), (dt_dev, "dt"), (status_rows, "status_rows")):
+        for b, name in outs:
+            _check_span_overlap(a, b, "%s and %s" % (what, name))
+    for i, (a, what) in enumerate(outs):
+        for b, name in outs[i + 1:]:
+            _check_span_overlap(a, b, "%s and %s" % (what, name))
+    if n and c:
+        co = opts.struct()
+        _lib.check(_lib.load().flm_face_openness(
+            _lib.stream_ptr(), _lib.ptr(lm), ls, _ptr(weights), wst, n, c, _lib.C.byref(co), _ptr(slot), n_slots,
+            _lib.ptr(out), _ptr(state), _ptr(reset), _ptr(dt_dev), dt_host, _ptr(status_rows), frame_id), "flm_face_openness")
+    return out
+
+
 # ---- finished tracks: track ids and the exit queue of best shots (include/flm.h, flm_track_retire) ---------------------
 EXIT_META = 8   # FLM_EXIT_META: track_id, slot, born_frame, frame_id of the end, best_frame, end, seq, 0
 

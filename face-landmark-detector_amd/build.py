@@ -46,6 +46,7 @@ SOURCES = [
     "flm_track_exit.hip",
     "flm_track_views.hip",
     "flm_pose.hip",
+    "flm_parts.hip",
     "flm_annotate.hip",
     "flm_flow.hip",
     "flm_flow_rows.hip",

@@ -203,6 +203,39 @@ int flm_warp_mesh_frames(flm_stream_t stream, const uint8_t* frames, size_t fram
                                  src ? src : &bgr, min_det, aff_out);
 }
 
+// ---- face parts (flm_parts.hip) -----------------------------------------------------------------------------------------
+
+int flm_part_affines(flm_stream_t stream, const double* lm, size_t lm_stride, const double* wt, size_t w_stride, int k, int c,
+                     const int32_t* part_idx, const double* part_tmpl, const int32_t* part_n, int r, float* aff,
+                     int32_t* part_ok) {
+  if (!lm || !part_idx || !part_tmpl || !part_n || !aff || !part_ok) return null_argument("flm_part_affines");  // (w is optional)
+  return launch_part_affines(static_cast<hipStream_t>(stream), lm, lm_stride, wt, w_stride, k, c, part_idx, part_tmpl,
+                             part_n, r, aff, part_ok);
+}
+
+int flm_warp_parts_frames(flm_stream_t stream, const uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
+                          const int32_t* frame_idx, const int32_t* boxes, const double* lm, size_t lm_stride,
+                          const double* wt, size_t w_stride, int c, const int32_t* part_idx, const double* part_tmpl,
+                          const int32_t* part_n, int r, int k, void* dst, int ph, int pw, int samples,
+                          const flm_image_format* fmt, const flm_frame_format* src, float* aff_out, int32_t* part_ok_out) {
+  // frame_idx, boxes, w, fmt, src and the last two outputs are optional
+  if (!frames || !lm || !part_idx || !part_tmpl || !part_n || !dst) return null_argument("flm_warp_parts_frames");
+  flm_frame_format bgr;  // src NULL: the dense BGR ring
+  flm_frame_format_init(&bgr);
+  if (src) {
+    if (const int rc = check_frame_format("flm_warp_parts_frames", src)) return rc;
+  }
+  flm_image_format plain;  // fmt NULL: float32 NHWC BGR, scale 1, bias 0
+  flm_image_format_init(&plain);
+  if (fmt) {
+    if (const int rc = check_image_format("flm_warp_parts_frames", fmt)) return rc;
+  }
+  if (const int rc = check_image_dst("flm_warp_parts_frames", dst, fmt ? fmt : &plain)) return rc;
+  return launch_warp_parts_frames(static_cast<hipStream_t>(stream), frames, frame_stride, nframes, fh, fw, frame_idx, boxes,
+                                  lm, lm_stride, wt, w_stride, c, part_idx, part_tmpl, part_n, r, k, dst, ph, pw, samples,
+                                  fmt ? fmt : &plain, src ? src : &bgr, aff_out, part_ok_out);
+}
+
 // ---- frame annotation (flm_annotate.hip) ------------------------------------------------------------------------------
 
 void flm_annotate_opts_init(flm_annotate_opts* opts) {

@@ -546,6 +546,91 @@ int flm_head_pose(flm_stream_t stream, const double* lm, size_t lm_stride, const
                           n_slots, pose, factor);
 }
 
+// ---- openness and blink state (flm_parts.hip) -----------------------------------------------------------------------
+
+void flm_open_opts_init(flm_open_opts* opts) {
+  if (!opts) return;
+  memset(opts, 0, sizeof(*opts));
+  opts->struct_size = (uint32_t)sizeof(flm_open_opts);
+  opts->n_measures = 3;
+  static const int32_t width[3][2] = {{36, 39}, {42, 45}, {60, 64}};
+  static const int32_t upper[3][4] = {{37, 38, 0, 0}, {43, 44, 0, 0}, {61, 62, 63, 0}};
+  static const int32_t lower[3][4] = {{41, 40, 0, 0}, {47, 46, 0, 0}, {67, 66, 65, 0}};
+  for (int g = 0; g < 3; ++g) {
+    opts->n_pairs[g] = g < 2 ? 2 : 3;
+    for (int j = 0; j < 2; ++j) opts->width[g][j] = width[g][j];
+    for (int j = 0; j < 4; ++j) {
+      opts->upper[g][j] = upper[g][j];
+      opts->lower[g][j] = lower[g][j];
+    }
+  }
+  opts->close_below = 0.18;
+  opts->open_above = 0.22;
+  opts->min_closed = 0.03;
+  opts->max_closed = 0.5;
+  opts->min_width = 4.0;
+}
+
+int flm_face_openness(flm_stream_t stream, const double* lm, size_t lm_stride, const double* wt, size_t w_stride, int n, int c,
+                      const flm_open_opts* opts, const int32_t* slot, int n_slots, double* rec, double* state,
+                      int32_t* reset, const double* dt_dev, double dt, const int32_t* status, int64_t frame_id) {
+  const char* who = "flm_face_openness";
+  if (!lm || !rec) return null_argument(who);  // (w, opts, slot, state, dt_dev and status_rows are optional)
+  if (state && !reset) {
+    set_error("%s: state_dev needs reset_dev", who);
+    return FLM_ERR_ARG;
+  }
+  flm_open_opts defaults;
+  if (const int rc = check_opts<true>(who, FLM_OPTS(flm_open_opts), &opts, &defaults)) return rc;
+  if (opts->n_measures < 1 || opts->n_measures > FLM_OPEN_MAX_MEASURES) {
+    set_error("%s: n_measures=%d outside 1 <= n_measures <= %d", who, opts->n_measures, FLM_OPEN_MAX_MEASURES);
+    return FLM_ERR_ARG;
+  }
+  for (int g = 0; g < opts->n_measures; ++g)
+    if (opts->n_pairs[g] < 1 || opts->n_pairs[g] > FLM_OPEN_MAX_PAIRS) {
+      set_error("%s: n_pairs[%d]=%d outside 1 <= n_pairs <= %d", who, g, opts->n_pairs[g], FLM_OPEN_MAX_PAIRS);
+      return FLM_ERR_ARG;
+    }
+  if (!(opts->close_below < opts->open_above)) {
+    set_error("%s: close_below=%g, open_above=%g, needs close_below < open_above", who, opts->close_below, opts->open_above);
+    return FLM_ERR_ARG;
+  }
+  if (!(opts->min_closed >= 0.0) || !(opts->max_closed >= 0.0) || !(opts->min_width >= 0.0)) {
+    set_error("%s: min_closed=%g, max_closed=%g, min_width=%g, each needs to be >= 0", who, opts->min_closed,
+              opts->max_closed, opts->min_width);
+    return FLM_ERR_ARG;
+  }
+  if (opts->max_closed < opts->min_closed) {
+    set_error("%s: max_closed=%g is below min_closed=%g", who, opts->max_closed, opts->min_closed);
+    return FLM_ERR_ARG;
+  }
+  if (state && !dt_dev && !(dt > 0.0 && std::isfinite(dt))) {
+    set_error("%s: dt=%g, needs dt finite and > 0", who, dt);
+    return FLM_ERR_ARG;
+  }
+  if (const int rc = check_range(who, "n", n, 1, 65535)) return rc;
+  if (const int rc = check_range(who, "c", c, 1, 1024)) return rc;
+  if (const int rc = check_lm_strides(who, lm_stride, wt, w_stride)) return rc;
+  if (slot)
+    if (const int rc = check_range(who, "n_slots", n_slots, 1, 65535)) return rc;
+  const size_t last = (size_t)n * c - 1;  // the last landmark read
+  const size_t rows = (size_t)(slot ? n_slots : n), gm = (size_t)opts->n_measures;
+  const NamedRange in[] = {
+      {lm, (last * lm_stride + 2) * sizeof(double), "lm_dev"},
+      {wt, wt ? (last * w_stride + 1) * sizeof(double) : 0, "w_dev"},
+      {slot, slot ? (size_t)n * sizeof(int32_t) : 0, "slot_dev"},
+      {dt_dev, dt_dev ? (size_t)n * sizeof(double) : 0, "dt_dev"},
+      {status, status ? (size_t)n * sizeof(int32_t) : 0, "status_rows_dev"}};
+  const NamedRange out[] = {
+      {rec, rows * gm * FLM_OPEN_REC * sizeof(double), "rec_dev"},
+      {state, state ? rows * gm * FLM_OPEN_STATE * sizeof(double) : 0, "state_dev"},
+      {state ? reset : nullptr, rows * sizeof(int32_t), "reset_dev"}};
+  if (const int rc = check_outputs_apart(who, in, out, "%s: %s overlaps %s", "%s: %s and %s overlap")) return rc;
+  return launch_face_openness(static_cast<hipStream_t>(stream), lm, lm_stride, wt, w_stride, n, c, opts, slot, n_slots, rec,
+                              state, state ? reset : nullptr, state ? dt_dev : nullptr, dt, state ? status : nullptr,
+                              frame_id);
+}
+
 // ---- pose-binned best shots (flm_track_views.hip) -------------------------------------------------------------------
 
 void flm_views_opts_init(flm_views_opts* opts) {

@@ -314,6 +314,19 @@ int launch_warp_mesh_frames(hipStream_t s, const uint8_t* frames, size_t frame_s
                             const uint8_t* map, int k, void* dst, int hd, int wd, int samples,
                             const flm_image_format* fmt, const flm_frame_format* src, double min_det, float* aff_out);
 
+// face parts and openness (flm_parts.hip); null pointers, the formats (never null here), the option struct and the
+// overlaps have been checked by the caller
+int launch_part_affines(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride, int k, int c,
+                        const int32_t* idx, const double* tmpl, const int32_t* part_n, int r, float* aff, int32_t* ok);
+int launch_warp_parts_frames(hipStream_t s, const uint8_t* frames, size_t frame_stride, int nframes, int fh, int fw,
+                             const int32_t* frame_idx, const int32_t* boxes, const double* lm, size_t lm_stride,
+                             const double* wt, size_t w_stride, int c, const int32_t* idx, const double* tmpl,
+                             const int32_t* part_n, int r, int k, void* dst, int ph, int pw, int samples,
+                             const flm_image_format* fmt, const flm_frame_format* src, float* aff_out, int32_t* ok_out);
+int launch_face_openness(hipStream_t s, const double* lm, size_t lm_stride, const double* wt, size_t w_stride, int n, int c,
+                         const flm_open_opts* opts, const int32_t* slot, int n_slots, double* rec, double* state,
+                         int32_t* reset, const double* dt_dev, double dt, const int32_t* status, int64_t frame_id);
+
 // tracking (flm_track.hip); null pointers and the option struct have been checked by the caller, `opts` is never null
 int launch_track_seed(hipStream_t s, const int32_t* boxes, int k, int in_h, int in_w, int fh, int fw, float* m,
                       int32_t* status);

@@ -671,6 +671,86 @@ def head_pose(landmarks, weights=None, pose=None):
                 count=rec[:, 13], ok=rec[:, 14], angles=rec[:, 15:18])
 
 
+def _parts_for(parts, n_landmarks):
+    """parts None or True -> `FaceParts.default` of the landmark count; a FaceParts is used as it is (an index beyond
+    the landmark count takes no part in its fit)."""
+    if parts is None or parts is True:
+        return alignment.FaceParts.default(n_landmarks)
+    if not isinstance(parts, alignment.FaceParts):
+        raise ValueError("parts must be None, True or an alignment.FaceParts (got %r)" % (parts,))
+    return parts
+
+
+def _openness_for(openness, n_landmarks):
+    if openness is None or openness is True:
+        return alignment.Openness.default(n_landmarks)
+    if not isinstance(openness, alignment.Openness):
+        raise ValueError("openness must be None, True or an alignment.Openness (got %r)" % (openness,))
+    return openness
+
+
+def face_parts(ring, landmarks, parts=None, weights=None, frame_index=None, samples=1, aligned_format=None,
+               frame_format=None):
+    """Eye and mouth patches for landmarks that `align_frames` returned, cut from the ring in one launch
+    (alignment.warp_parts_frames_device): every part under a similarity fitted to its own landmarks.
+
+    ring, frame_format, samples, aligned_format: as `align_frames` takes them; landmarks: CUDA float64 [K,C,2] in frame
+    pixels; parts: None (`alignment.FaceParts.default(C)`: right eye, left eye, mouth at 32x48, for 68 landmarks) or an
+    `alignment.FaceParts`; weights: None or CUDA float64 [K,C]; frame_index: None (every face lies in slot 0), a host
+    sequence of K ring slots (one upload) or a CUDA int32 [K] tensor.  Returns CUDA tensors (patches [K,R,ph,pw,3] float32
+    or [K,R] faces of the format, M float32 [K,R,2,3] frame px -> patch px, ok int32 [K,R]); a part that is not ok -- fewer
+    than two usable points, or coincident ones -- is a zero patch under the identity."""
+    import torch
+    _aligned_format(aligned_format, False)
+    _frame_format(frame_format)
+    if not isinstance(landmarks, torch.Tensor) or landmarks.dim() != 3 or not landmarks.is_cuda:
+        raise ValueError("landmarks must be a CUDA float64 [K,C,2] tensor")
+    k, c = int(landmarks.shape[0]), int(landmarks.shape[1])
+    parts = _parts_for(parts, c)
+    if frame_index is not None and not isinstance(frame_index, torch.Tensor):
+        idx = [int(v) for v in frame_index]
+        if len(idx) != k:
+            raise ValueError("frame_index must name a ring slot for each of the %d faces" % k)
+        frame_index = torch.tensor(idx, dtype=torch.int32).to(landmarks.device)
+    aff = torch.empty((k, len(parts), 2, 3), dtype=torch.float32, device=landmarks.device)
+    ok = torch.empty((k, len(parts)), dtype=torch.int32, device=landmarks.device)
+    out = alignment.warp_parts_frames_device(ring, landmarks, parts, weights=weights, frame_index_dev=frame_index,
+                                             samples=samples, fmt=aligned_format, src=frame_format, affines_out=aff,
+                                             ok_out=ok)
+    return out, aff, ok
+
+
+def face_openness(landmarks, weights=None, openness=None):
+    """How open the eyes and the mouth of every face are (alignment.face_openness_device, one launch).  landmarks:
+    float64 [N,C,2] in frame pixels, (-1,-1) for a rejected point; weights: None or float64 [N,C]; both numpy arrays (one
+    upload, one download) or CUDA tensors (nothing leaves the device).  openness: None (`alignment.Openness.default(C)`:
+    both eyes and the inner mouth, for 68 landmarks) or an `alignment.Openness`.  Returns a dict of the kind of
+    `landmarks`, every entry a view of "record" float64 [N,G,4]: "openness" [N,G] (for the eyes the eye aspect ratio; -1
+    where the measure is not ok), "width" [N,G] in pixels, "ok" [N,G] (1.0 or 0.0) and "sum" [N,G].  The blink state
+    needs a history and lives in `FaceTracker(openness=...)` or `alignment.face_openness_device(state=...)`."""
+    import torch
+    numpy_io = not isinstance(landmarks, torch.Tensor)
+    if numpy_io:
+        lm_np = np.ascontiguousarray(landmarks, np.float64)
+        if lm_np.ndim != 3 or lm_np.shape[2] != 2:
+            raise ValueError("landmarks must be float64 [N,C,2]")
+        if weights is not None:
+            weights = np.ascontiguousarray(weights, np.float64)
+            if weights.shape != lm_np.shape[:2]:
+                raise ValueError("weights must be float64 [%d,%d]" % lm_np.shape[:2])
+    elif landmarks.dim() != 3:
+        raise ValueError("landmarks must be float64 [N,C,2]")
+    openness = _openness_for(openness, int(landmarks.shape[1]))
+    if numpy_io:
+        dev = _lib.require_gpu()
+        landmarks = torch.from_numpy(lm_np).to(dev)
+        weights = None if weights is None else torch.from_numpy(weights).to(dev)
+    rec = alignment.face_openness_device(landmarks, openness, weights=weights)
+    if numpy_io:
+        rec = rec.cpu().numpy()
+    return dict(record=rec, openness=rec[..., 0], width=rec[..., 1], ok=rec[..., 2], sum=rec[..., 3])
+
+
 def landmark_flow(prev_crops, cur_crops, points, flow=None):
     """Points carried from one crop to the next by sparse optical flow (alignment.flow_pyramid_device and
     alignment.landmark_flow_device: a pyramidal, translation-only Lucas-Kanade step per point, two launches), numpy in and
@@ -795,14 +875,36 @@ class FaceTracker:
     launch, alignment.track_flow_history_device, for the rows it served), plus `flow_cursor`, `flow_counts` int32 [6]
     and `flow_fb` float64 [capacity,C], the squared round trip of the forward-backward check that
     `alignment.LandmarkFlow(max_fb=...)` switches on (off by default; -1.0 where it did not run).  After a rows tick
-    `flow_flags`, `flow_err` and `flow_fb` are views of the first `budget` rows."""
+    `flow_flags`, `flow_err` and `flow_fb` are views of the first `budget` rows.  parts: None, True
+    (`alignment.FaceParts.default` of the landmark count: right eye, left eye, mouth) or an `alignment.FaceParts`: after
+    the aligned warp every step cuts the parts' patches from the ring in one more launch
+    (alignment.warp_parts_frames_device, from the landmarks the step returns, with `samples`, `aligned_format` and
+    weights="score"'s weights); `part_faces` [rows,R,...], `part_M` float32 [rows,R,2,3] and `part_ok` int32 [rows,R]
+    are then views of the tracker's own buffers, row for row beside `aligned`.  openness: None, True
+    (`alignment.Openness.default` of the landmark count: both eyes and the inner mouth) or an `alignment.Openness`:
+    after the head pose every step measures the openness of its faces and advances their blink state in one more launch
+    (alignment.face_openness_device) at the rows' slots; the tracker then owns `openness` float64 [capacity,G,4] and
+    `open_state` float64 [capacity,G,8], and a slot no step serves keeps both and its pending reset.  The state of a slot
+    is emptied when a track is born there (`seed`, a birth of `update`).  The time step is the step's own `dt` for a
+    tracker that smooths -- the rows' dt, waits included, on the rows ticks -- and the Openness's `dt` otherwise;
+    `frame_id` is also taken by a tracker with openness alone.  With `smooth` the openness reads the FILTERED landmarks:
+    the One-Euro filter lags a blink, and nothing has been measured about that.  Without the two options the tracker
+    launches nothing more and allocates nothing more."""
 
     def __init__(self, model, frame_hw, capacity, out_size=(112, 112), template=None, crop_template=None, n_points=4,
                  thresh=0.0, weights=None, min_points=2, min_score=0.0, min_side=0.0, max_side=float("inf"),
                  crop_samples=1, samples=1, aligned_format=None, frame_format=None, smooth=None, associate=None,
-                 best_shot=None, streams=1, pose=None, mesh=None, flow=None, fallback_faces=0, exits=None,
-                 views=None):
+                 best_shot=None, streams=1, pose=None, mesh=None, flow=None, fallback_faces=0, parts=None, openness=None,
+                 exits=None, views=None):
         import torch
+        if parts is False:
+            parts = None
+        if parts is not None:
+            parts = _parts_for(parts, int(model.n_classes))
+        if openness is False:
+            openness = None
+        if openness is not None:
+            openness = _openness_for(openness, int(model.n_classes))
         if isinstance(fallback_faces, bool) or not isinstance(fallback_faces, (int, np.integer)) or fallback_faces < 0:
             raise ValueError("fallback_faces must be an integer >= 0 (got %r)" % (fallback_faces,))
         self.fallback_faces = int(fallback_faces)
@@ -898,6 +1000,8 @@ class FaceTracker:
             raise ValueError("the mesh has %d landmark points, the model %d landmarks" % (mesh.n_landmarks, c))
         self.mesh, self.mesh_faces, self._mesh_buf = mesh, None, None
         self._head_model = None if pose is None else pose.model_for(c)
+        self.parts, self.part_faces, self.part_ok, self.part_M = parts, None, None, None
+        self.open_opts, self.openness, self.open_state = openness, None, None
         self._ws_active = None   # the forward workspace of step_active (_active_workspace)
         self._waiting = False    # step_live has run below capacity: slot_age may hold a wait (_served)
         self._crop_format = alignment.AlignedFormat("nhwc", "uint8")
@@ -960,6 +1064,20 @@ class FaceTracker:
             self._mesh_buf = torch.zeros(mfmt.shape(n, *self.out_size), dtype=mfmt.torch_dtype, device=dev)
             self.mesh.tensors(dev)
             self.mesh.map(dev, *self.out_size)
+        if self.parts is not None:      # the patches, matrices and ok flags of the last step: the rows of `aligned`
+            pfmt = self.aligned_format or alignment.AlignedFormat()
+            r = len(self.parts)
+            self._part_buf = torch.zeros((n, r) + tuple(pfmt.shape(1, *self.parts.size)[1:]), dtype=pfmt.torch_dtype,
+                                         device=dev)
+            self._part_m_buf = torch.eye(2, 3, dtype=torch.float32, device=dev).repeat(n, r, 1, 1).contiguous()
+            self._part_ok_buf = torch.zeros((n, r), dtype=torch.int32, device=dev)
+            self.parts.tensors(dev)
+        if self.open_opts is not None:  # the not-ok record and the empty state of a slot no step has measured
+            g = len(self.open_opts)
+            self.openness = torch.tensor([-1.0, -1.0, 0.0, -1.0], dtype=torch.float64, device=dev).repeat(n, g, 1).contiguous()
+            self.open_state = torch.tensor(alignment.OPEN_STATE_EMPTY, dtype=torch.float64,
+                                           device=dev).repeat(n, g, 1).contiguous()
+            self._open_reset = torch.zeros((n,), dtype=torch.int32, device=dev)
         if self.flow is not None:       # (-1,-1): the landmark has no history
             c = int(self.model.n_classes)
             ih, iw = int(self.model.input_height), int(self.model.input_width)
@@ -1038,6 +1156,8 @@ class FaceTracker:
             self.filter_state.index_fill_(0, idx, -1.0)
         if self.best_shot is not None:
             self._best_reset.index_fill_(0, idx, 1)
+        if self.open_opts is not None:
+            self._open_reset.index_fill_(0, idx, 1)
         if self.exit_opts is not None:
             self._born.index_fill_(0, idx, 1)
         if self.flow is not None:
@@ -1054,8 +1174,9 @@ class FaceTracker:
         return arr
 
     def _was_empty(self):
-        """For a tracker with best_shot, the slots that hold no track now: the association's own test, on the device."""
-        if self.best_shot is None:
+        """For a tracker with best_shot or openness, the slots that hold no track now: the association's own test, on the
+        device."""
+        if self.best_shot is None and self.open_opts is None:
             return None
         fh, fw = self.frame_hw
         b = self.boxes
@@ -1064,12 +1185,15 @@ class FaceTracker:
 
     def _mark_births(self, was_empty, slot_det):
         """A birth forgets the slot's best with the next step; a restart is the same face and keeps it, and a skipped
-        stream has slot_det == -1 and resets nothing."""
+        stream has slot_det == -1 and resets nothing.  The openness state is forgotten by the same rule, through a flag
+        of its own that the openness call clears."""
         if self.best_shot is not None:
             births = was_empty & (slot_det >= 0)
             self._best_reset.masked_fill_(births, 1)
             if self.exit_opts is not None:
                 self._born.masked_fill_(births, 1)
+        if self.open_opts is not None:
+            self._open_reset.masked_fill_(was_empty & (slot_det >= 0), 1)
 
     def update(self, detections, n=None):
         """The boxes of a detector against the tracks, on the device (alignment.track_associate_device with the
@@ -1243,7 +1367,7 @@ class FaceTracker:
         """What `step` and `step_active` check before anything else: frame_id (None: the steps made so far), "dt goes
         with smooth" -- and, for host_dt, dt as the one host number `step` takes -- and the ring's geometry against
         frame_hw.  Returns (frame_id, dt, the slots of the ring)."""
-        if self.best_shot is None and frame_id is not None:
+        if self.best_shot is None and self.open_opts is None and frame_id is not None:
             raise ValueError("frame_id goes with best_shot")
         frame_id = self._steps if frame_id is None else alignment._frame_id(frame_id)
         if self.smooth is None and dt is not None:
@@ -1291,7 +1415,7 @@ class FaceTracker:
         return lm, (None if self.weights is None else wd), (ih, iw)
 
     def _sequence(self, ring, src, step, best_update, workspace, frame_id, quality_out=None, landmarks=None,
-                  history=False):
+                  history=False, open_dt=None):
         """The step sequence, stated once for `step`, `step_flow` and `step_active`: the landmark source (`landmarks`;
         None: the uint8 crop warp -> model.forward_device) -> (lm, wd) -> the step call -> with history, the raw landmarks
         and weights kept for `step_flow` -> with pose, the head-pose call (at the rows' slots where src has a "slot") ->
@@ -1322,8 +1446,19 @@ class FaceTracker:
                 factor = dict(factor=self._pose_factor[:int(lm_frame.shape[0])])
             alignment.head_pose_device(lm_frame, self._head_model, weights=wd, opts=self.head_pose, slot=src.get("slot"),
                                        out=self.pose, factor_out=factor.get("factor"))
+        if self.open_opts is not None:   # one more launch: records and blink state at the rows' slots.  open_dt: the
+            # step's own time step (a host number, or the rows' on the device), None for the Openness's dt
+            alignment.face_openness_device(lm_frame, self.open_opts, weights=wd, slot=src.get("slot"), out=self.openness,
+                                           state=self.open_state, reset=self._open_reset, dt=open_dt, status_rows=status,
+                                           frame_id=frame_id)
         aligned = alignment.warp_frames_device(ring, m_align, self.out_size[0], self.out_size[1], samples=self.samples,
                                                fmt=self.aligned_format, **where)
+        if self.parts is not None:   # one more launch, into the tracker's own buffers: the rows of `aligned`
+            n = int(m_align.shape[0])
+            self.part_M, self.part_ok = self._part_m_buf[:n], self._part_ok_buf[:n]
+            self.part_faces = alignment.warp_parts_frames_device(
+                ring, lm_frame, self.parts, weights=wd, samples=self.samples, fmt=self.aligned_format,
+                out=self._part_buf[:n], affines_out=self.part_M, ok_out=self.part_ok, **where)
         if self.mesh is not None:   # one more launch, into the tracker's own buffer: the rows of `aligned`
             n = int(m_align.shape[0])
             self.mesh_faces = alignment.warp_mesh_frames_device(
@@ -1420,7 +1555,7 @@ class FaceTracker:
             functools.partial(alignment.track_step_device, m_next=self.m_crop, boxes_next=self._boxes_spare,
                               status=self.status, dt=dt, **raw),
             best_update, lambda n, out: None, frame_id, quality_out=self._quality_rec if self.best_shot is not None else None,
-            landmarks=landmarks, history=history)
+            landmarks=landmarks, history=history, open_dt=dt)
         self._flow_ok = True
         if history:
             self._flow_put(self._flow_iota, self.status, self.frame_slots)
@@ -1630,7 +1765,7 @@ class FaceTracker:
             ring, snap,
             functools.partial(alignment.track_step_rows_device, slot=snap["slot"], m_next=self.m_crop, boxes_next=self.boxes,
                               status=self.status, dt=dt_scalar if dt_dev is None else snap["dt"], **raw),
-            best_update, self._active_workspace, frame_id)
+            best_update, self._active_workspace, frame_id, open_dt=dt_scalar if dt_dev is None else snap["dt"])
         self._flow_put_rows(snap, raw)
         self._retire_served()
         self._served(snap["slot"])
@@ -1760,7 +1895,7 @@ class FaceTracker:
             functools.partial(alignment.track_step_rows_device, slot=snap["slot"], m_next=self.m_crop, boxes_next=self.boxes,
                               status=self.status, dt=snap.get("dt"), **raw),
             best_update, self._active_workspace, frame_id, landmarks=(lambda ring, src, workspace: self._flow_landmarks(
-                ring, src, workspace, snap["slot"], snap["prev_frame_index"])) if flow else None)
+                ring, src, workspace, snap["slot"], snap["prev_frame_index"])) if flow else None, open_dt=snap.get("dt"))
         self._flow_put_rows(snap, raw)
         self._retire_served()
         return res + (snap["slot"],)

@@ -1726,6 +1726,132 @@ int flm_track_flow_history_put(flm_stream_t stream, const int32_t* slot_dev /*[N
                                double* hist_lm_dev /*[n_slots,C,2] or NULL*/, double* hist_w_dev /*[n_slots,C] or NULL*/,
                                int32_t* flow_frame_dev /*[n_slots]*/, int32_t* flow_ready_dev /*[n_slots]*/);
 
+/* ---- face parts: eye and mouth patches straight from the frames ---------------------------------------------------------
+ * A gaze, liveness or lip-reading network reads patches of the eyes and the mouth.  flm_warp_parts_frames cuts R patches
+ * per face, each under a similarity fitted to the part's OWN landmarks, in ONE launch with ONE output tensor.
+ *
+ * A SET OF PARTS: R parts, 1 <= R <= FLM_PARTS_MAX (8).  Part r names part_n[r] landmarks, 2 <= part_n[r] <=
+ * FLM_PART_MAX_POINTS (32): part_idx_dev int32 [R,32] holds their numbers and part_tmpl_dev float64 [R,32,2] where each
+ * belongs in PATCH pixels (x, y); part_n is an array of R ints in HOST memory, read during the call (it sizes the checks
+ * and travels to the kernel by value).  The entries of a row past part_n[r] -- padded with -1 by convention -- are never
+ * read.  All parts share one patch size ph x pw.
+ *
+ * flm_part_affines: aff_dev float32 [K,R,2,3], the matrix FRAME px -> PATCH px of every (face, part), and part_ok_dev
+ * int32 [K,R].  The matrix of (f, r) is word for word the arithmetic of flm_similarity_from_landmarks_weighted with
+ * sx = sy = 1 (so no product by sx, sy is made), over the part's entries i = 0 .. part_n[r]-1 IN THE ORDER part_idx LISTS
+ * THEM: point i is landmark id = part_idx[r][i] of face f, the two doubles at lm_dev + (f*c + id)*lm_stride, its weight
+ * the double at w_dev + (f*c + id)*w_stride (w_dev == NULL: 1), its template point part_tmpl[r][i].  An entry takes part
+ * when 0 <= id < c, both coordinates are >= 0 and the weight is > 0 (a NaN fails each test).  float64, one IEEE operation
+ * per written operator, nothing fused, every sum sequential from 0.0 over the participating entries in ascending i:
+ *   W = sum w;  mpx = sum(w*px) / W, likewise mpy, mqx, mqy (q: the template);  p' = p - mp, q' = q - mq
+ *   sa = sum w*(px'*qx' + py'*qy');  sb = sum w*(px'*qy' - py'*qx');  var = sum w*(px'*px' + py'*py')
+ *   a = sa / var, b = sb / var, tx = mqx - (a*mpx - b*mpy), ty = mqy - (b*mpx + a*mpy);  M = [[a,-b,tx],[b,a,ty]]
+ * each of the six rounded to float32 once.  part_ok = 1 when two entries or more take part and var > 0 (a NaN var fails
+ * the test); otherwise part_ok = 0 and the matrix is the identity.  An index may appear in several parts, and twice in one.
+ *
+ * flm_warp_parts_frames: dst_dev [K,R,...] -- K*R faces of ph x pw in the image format, face f*R + r being patch (f, r)
+ * -- in ONE launch of K*R workgroups; the fit above is part of that launch and runs ONCE per (face, part).  aff_out_dev
+ * and part_ok_out_dev, each optional, receive the bits of flm_part_affines, zero faces included.
+ *   THE CONTRACT: patch (f, r) has, pixel for pixel, the bits flm_warp_affine_frames_src stores for a face whose matrix
+ *   is aff[f][r], with hd = ph, wd = pw, face f's frame_idx_dev[f] and boxes_dev[f] (each optional, as there), and the
+ *   same samples, fmt and src (NULL: the dense BGR24 ring; or NV12).  A part that is not ok stores a ZERO face -- what
+ *   that call stores for a slot outside the ring or an empty clipped box, which give a zero face here too.
+ * No atomics, no allocation, no workspace; no byte outside the outputs is written; every launch shape is a host number.
+ * Errors, all found before anything is launched, with the codes of flm_warp_affine_frames_src for what it shares with
+ * that call (samples, ring, formats, dst alignment).  FLM_ERR_ARG: a null frames / lm / part_idx / part_tmpl / part_n /
+ * dst (aff and part_ok for flm_part_affines), r outside [1,8], a part_n[r] outside [2,32].  FLM_ERR_SHAPE, the limit named
+ * in flm_last_error(): lm_stride < 2, w_stride < 1 (with w_dev), k outside [1,65535], c outside [1,1024], ph or pw
+ * outside [1,256]. */
+#define FLM_PARTS_MAX 8
+#define FLM_PART_MAX_POINTS 32
+#define FLM_PART_MAX_SIDE 256
+int flm_part_affines(flm_stream_t stream, const double* lm_dev, size_t lm_stride, const double* w_dev /*or NULL*/,
+                     size_t w_stride, int k, int c, const int32_t* part_idx_dev /*[R,32]*/,
+                     const double* part_tmpl_dev /*[R,32,2]*/, const int32_t* part_n /*HOST [R]*/, int r,
+                     float* aff_dev /*[K,R,2,3]*/, int32_t* part_ok_dev /*[K,R]*/);
+int flm_warp_parts_frames(flm_stream_t stream, const uint8_t* frames_dev, size_t frame_stride, int nframes, int fh, int fw,
+                          const int32_t* frame_idx_dev /*[K] or NULL*/, const int32_t* boxes_dev /*[K,4] or NULL*/,
+                          const double* lm_dev, size_t lm_stride, const double* w_dev /*or NULL*/, size_t w_stride, int c,
+                          const int32_t* part_idx_dev /*[R,32]*/, const double* part_tmpl_dev /*[R,32,2]*/,
+                          const int32_t* part_n /*HOST [R]*/, int r, int k, void* dst_dev /*[K,R,...]*/, int ph, int pw,
+                          int samples, const flm_image_format* fmt /*or NULL*/, const flm_frame_format* src /*or NULL*/,
+                          float* aff_out_dev /*[K,R,2,3] or NULL*/, int32_t* part_ok_out_dev /*[K,R] or NULL*/);
+
+/* ---- openness and blink state: how open the eyes and the mouth are, and a count of closures -----------------------------
+ * flm_face_openness, ONE launch (one thread per row, looping over the measures), no workspace, no allocation, no atomics.
+ *
+ * A MEASURE g is a width pair of landmarks (width[g][0], width[g][1]) and V = n_pairs[g] pairs (upper[g][v], lower[g][v]),
+ * 1 <= V <= FLM_OPEN_MAX_PAIRS (4); flm_open_opts holds G = n_measures of them, 1 <= G <= FLM_OPEN_MAX_MEASURES (8).
+ * Landmarks and weights are read at element strides as flm_head_pose reads them, and a landmark TAKES PART as there: its
+ * index lies in [0, c), both coordinates are >= 0 and its weight (1 without w_dev) is > 0; a NaN fails each test.
+ * Per row and measure, float64, one IEEE operation per written operator, in the written order, nothing fused:
+ *   dist(i, j) = sqrt(dx*dx + dy*dy),  dx = x_i - x_j,  dy = y_i - y_j
+ *   dw  = dist(width[g][0], width[g][1])
+ *   sum = 0.0;  sum = sum + dist(upper[g][v], lower[g][v])  for v = 0 .. V-1 in ascending v
+ *   o   = (sum / (double)V) / dw
+ *   OK  = every landmark the measure names takes part, dw >= min_width, and o is finite
+ * For six eye points with V = 2, o is the eye aspect ratio of Soukupova and Cech (2016).
+ * The record, FLM_OPEN_REC = 4 doubles: { o, dw, ok ? 1.0 : 0.0, sum }.  When not ok, o = -1; when a named landmark does not
+ * take part nothing was measured and dw = sum = -1 as well.  (Coordinates are expected finite: +inf takes part and yields
+ * NaNs whose sign the platform chooses.)
+ * Rows and slots follow flm_head_pose: without slot_dev row r writes rec_dev[r] ([N,G,4]); with slot_dev int32 [N] a valid
+ * row writes at slot s = slot_dev[r] of rec_dev [n_slots,G,4], an inert row (s outside [0, n_slots)) writes nothing, and a
+ * slot no row names keeps its bits.  Valid rows name distinct slots.
+ *
+ * STATE, optional, in the same launch: state_dev float64 [N or n_slots,G,FLM_OPEN_STATE = 8], indexed as rec_dev,
+ *   { closed, run, events, last_closed, closed_total, seen_total, last_event_frame, 0 }
+ * with reset_dev int32 [N or n_slots] (in/out, required with state_dev), dt_dev float64 [N] by ROW or NULL (NULL: the scalar
+ * dt for every row), status_rows_dev int32 [N] by row or NULL (NULL: 0), and frame_id.  The thread of row r is the ONLY
+ * reader and writer of its slot's G entries and of its reset flag, which is why the state is updated in place; it reads
+ * the flag once, walks g = 0 .. G-1, and stores 0 to the flag after the last measure -- program order within one thread,
+ * no atomics.  Per valid row:
+ *   if reset_dev[s] != 0: every measure's state becomes { 0, 0, 0, -1, 0, 0, -1, 0 } first, whatever follows; the flag
+ *     is then set to 0.  An inert row and a slot no row names leave flag and state alone: a pending reset waits.
+ *   if the measure is not ok, or status != 0, or the row's dt is not finite and > 0: the state keeps every bit.
+ *   otherwise seen_total = seen_total + dt, then one of four cases:
+ *     closed == 0 and o < close_below:   closed = 1;  run = 0;  closed_total = closed_total + dt
+ *     closed == 0 otherwise:             run = run + dt
+ *     closed != 0 and o > open_above:    d = run + dt;  last_closed = d;
+ *                                        if min_closed <= d && d <= max_closed: events = events + 1,
+ *                                                                               last_event_frame = (double)frame_id
+ *                                        closed = 0;  run = 0
+ *     closed != 0 otherwise:             run = run + dt;  closed_total = closed_total + dt
+ * Defaults (flm_open_opts_init): the three measures of the 68-point layout -- right eye: width (36,39), pairs (37,41)
+ * (38,40); left eye: width (42,45), pairs (43,47) (44,46); inner mouth: width (60,64), pairs (61,67) (62,66) (63,65) --
+ * close_below = 0.18, open_above = 0.22, min_closed = 0.03 s, max_closed = 0.5 s, min_width = 4 px.  These five numbers
+ * are UNMEASURED GUESSES: there is no trained checkpoint and no labelled blink data behind them.
+ * Errors, all found before anything is launched.  FLM_ERR_ARG: a null lm_dev or rec_dev, state_dev without reset_dev,
+ * a struct_size smaller than this library's, a non-zero reserved, n_measures outside [1,8], an n_pairs outside [1,4],
+ * close_below not below open_above (or either NaN), a min_closed, max_closed or min_width that is NaN or negative,
+ * max_closed < min_closed, with state_dev and without dt_dev a dt that is not finite and > 0, an output overlapping an
+ * input or another output.  FLM_ERR_SHAPE: lm_stride < 2, w_stride < 1 (with w_dev), n outside [1,65535], c outside
+ * [1,1024], with slot_dev n_slots outside [1,65535]. */
+#define FLM_OPEN_REC 4
+#define FLM_OPEN_STATE 8
+#define FLM_OPEN_MAX_MEASURES 8
+#define FLM_OPEN_MAX_PAIRS 4
+typedef struct flm_open_opts {
+  uint32_t struct_size;  /* as flm_track_opts */
+  uint32_t reserved;     /* 0 */
+  int32_t n_measures;    /* G */
+  int32_t n_pairs[FLM_OPEN_MAX_MEASURES];                    /* V of measure g */
+  int32_t width[FLM_OPEN_MAX_MEASURES][2];
+  int32_t upper[FLM_OPEN_MAX_MEASURES][FLM_OPEN_MAX_PAIRS];
+  int32_t lower[FLM_OPEN_MAX_MEASURES][FLM_OPEN_MAX_PAIRS];
+  double close_below;    /* an open measure closes when o < close_below */
+  double open_above;     /* a closed measure opens when o > open_above; close_below < open_above */
+  double min_closed;     /* a closure of min_closed <= d <= max_closed (the unit of dt) counts as an event */
+  double max_closed;
+  double min_width;      /* frame px: below this dw the measure is not ok */
+} flm_open_opts;
+void flm_open_opts_init(flm_open_opts* opts);
+int flm_face_openness(flm_stream_t stream, const double* lm_dev, size_t lm_stride, const double* w_dev /*or NULL*/,
+                      size_t w_stride, int n, int c, const flm_open_opts* opts /*NULL = defaults*/,
+                      const int32_t* slot_dev /*[N] or NULL*/, int n_slots, double* rec_dev /*[N or n_slots,G,4]*/,
+                      double* state_dev /*[N or n_slots,G,8] or NULL*/, int32_t* reset_dev /*[N or n_slots] or NULL*/,
+                      const double* dt_dev /*[N] or NULL*/, double dt, const int32_t* status_rows_dev /*[N] or NULL*/,
+                      int64_t frame_id);
+
 #ifdef __cplusplus
 }
 #endif
